@@ -441,8 +441,49 @@ def emit(out, detail_path):
     sys.stdout.flush()
 
 
+DUMP_BYTES = 63_000_000      # --dump-outputs: what it writes at most, all files together (under 64 MB)
+DUMP_SEED = 20240601         # ... and the seed of the indices at which a vector is sampled when the whole would not fit
+DUMP_LOG = ("obj", "evol_x", "r_pri_total", "r_dual_total", "cg_it", "cg_relres", "rho", "gamma", "r_pri", "r_dual")
+
+
+def dump_outputs(path, x, l, y, log, its):
+    """--dump-outputs: what the timed path computed by its last step, as a caller of PARSDMM receives it -- x, every l_i and
+    y_i, the log rows of iterations 1..its (log.timing left out: wall clocks; evol_x from iteration 2 on: at iteration 1 it
+    is ||x_old - x|| / ||x|| with both zero, NaN by the reference's own definition, PARSDMM.jl:145) -- written as
+    path/<name>.npy in the precision of the run (the log in float64).  When the whole would exceed DUMP_BYTES each vector is sampled at fixed, seeded, sorted
+    indices (x keeps at least half of the room, the l_i and y_i share the rest by size): the same indices for every run with
+    the same arguments, so that two builds can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    out = {f"log_{k}": np.asarray(getattr(log, k), np.float64)[1 if k == "evol_x" else 0:its] for k in DUMP_LOG}
+    vecs = {"x": x}
+    for i, (li, yi) in enumerate(zip(l or [], y or [])):
+        vecs[f"l_{i + 1}"], vecs[f"y_{i + 1}"] = li, yi
+    header = 128                                                       # bytes of an .npy header (format 1.0, a few dimensions)
+    room = max(0, DUMP_BYTES - sum(a.nbytes + header for a in out.values()) - header * len(vecs))
+    whole = sum(v.nbytes for v in vecs.values())
+    keep = {k: v.size for k, v in vecs.items()}
+    if whole > room:
+        rest = whole - x.nbytes
+        keep["x"] = min(x.size, (room if rest == 0 else max(room // 2, room - rest)) // x.itemsize)
+        for k, v in vecs.items():
+            if k != "x":
+                keep[k] = min(v.size, int((room - keep["x"] * x.itemsize) * (v.nbytes / rest)) // v.itemsize)
+    picks = {}
+    for k, v in vecs.items():
+        if keep[k] >= v.size:
+            out[k] = v
+            continue
+        if (v.size, keep[k]) not in picks:
+            picks[v.size, keep[k]] = np.sort(np.random.default_rng(DUMP_SEED).choice(v.size, keep[k], replace=False))
+        out[k] = v[picks[v.size, keep[k]]]
+    for k, v in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(v))
+    return sum(v.nbytes for v in out.values())
+
+
 def bench_options(mod, TF, maxit):
-    # tolerances at zero: the stop rules never fire, so exactly `steps` iterations are timed
+    # tolerances at zero: stop rules 1 / 2 never fire (3 / 4 may: measure() then goes on in a new solve), so exactly `steps`
+    # iterations are timed
     return mod.PARSDMM_options(FL=TF, maxit=maxit, evol_rel_tol=0.0, feas_tol=0.0, obj_tol=0.0)
 
 
@@ -789,7 +830,9 @@ def dry_comm(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20,
+                    help="timed PARSDMM iterations of the headline, exactly this many (a solve that ends by itself is followed by a "
+                         "new one on the same context); ms_per_step = their wall time / steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -815,7 +858,15 @@ def main():
                     help="rehearsal of the N > 1 flow WITHOUT the engine: launcher, rendezvous, stdout contract, both decompositions and the "
                          "comm probe, each step being the collective skeleton of one PARSDMM iteration (DESIGN 5) on dummy buffers; "
                          "gloo on CPU tensors when no GPU is visible.  What it prints is NOT a measurement of the metric")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline, write what they computed -- x, every l_i and y_i, the log of the "
+                         "iterations so far -- as DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed, seeded sample of each "
+                         "vector beyond that); the inputs are the same for every run with the same arguments")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs is not None and args.dry_comm:
+        raise SystemExit("--dump-outputs: --dry-comm computes nothing to write")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # plain invocation: become the launcher (before any GPU call)
         raise SystemExit(spawn_ranks(args.gpus, args.deadline))
@@ -874,11 +925,12 @@ def main():
             os.close(saved_stdout)
             saved_stdout = None
 
-    def measure(config, steps, warmup, decomp=None, comm_mode=None, slab_full=False, mid_hook=None):
+    def measure(config, steps, warmup, decomp=None, comm_mode=None, slab_full=False, mid_hook=None, dump=None):
         """One workload: builds the context, runs `warmup` untimed and `steps` timed PARSDMM iterations of the native loop
         (sipx_parsdmm_begin / _steps; sharded: the same loop with the engine's collectives inside), returns the numbers.
         comm_mode: "rccl" (native, inside the engine) or "torch" (torch.distributed collectives as callbacks); slab_full: whole
-        arrays on every rank of a slab-decomposed context instead of the rank's planes (the headline's fallbacks)."""
+        arrays on every rank of a slab-decomposed context instead of the rank's planes (the headline's fallbacks); dump: a
+        directory for what the timed steps computed (--dump-outputs), written before anything else runs on the context."""
         n, h, kinds = CONFIGS[config]
         N = int(np.prod(n))
         m = synthetic_model(n, TF, 20240601 + 3)
@@ -910,10 +962,35 @@ def main():
                 if slab:
                     cx.set_decomp("slab_full" if slab_full else "slab")
         ctx = sipx.host.build_context(m, AtA, A, prop, P, g, opt, device=local_rank, owned=owned, attach=attach)
+        # Stop rules 3 / 4 of stop_PARSDMM (r_pri_total rising again, stop_PARSDMM.jl:34-52) do not depend on the tolerances: a
+        # long run ends by itself (c3: after about 210 iterations).  The iterations then go on in a new solve on the same context
+        # (sipx_parsdmm_begin: x, l, y, rho and Q as the stopped one left them -- where a caller's next PARSDMM call starts), so
+        # that warm-up and timed region hold exactly `warmup` and `steps` iterations.
         ctx.parsdmm_begin(opt)
-        logs = ctx._run[2]
+        cur = {"it": 0, "done": False}              # iterations of the current solve; has it ended?
+        solves = []                                 # [run (log arrays), first, last iteration of it inside the timed region]
+
+        def advance(k, timed):
+            """k more PARSDMM iterations of the native loop (ONE call while no solve ends: a call per step from Python put 20-30 us
+            of interpreter time between two iterations)"""
+            while k > 0:
+                if cur["done"]:
+                    ctx.parsdmm_begin(opt)
+                    cur.update(it=0, done=False)
+                if timed and (not solves or solves[-1][0] is not ctx._run):
+                    solves.append([ctx._run, cur["it"] + 1, cur["it"]])
+                before = cur["it"]
+                cur["done"] = ctx.parsdmm_steps(k)
+                ran = ctx._run[1].n_iter - before if cur["done"] else k
+                if ran <= 0:
+                    raise RuntimeError(f"a new solve ended before its first iteration (after {before} iterations)")
+                cur["it"] += ran
+                k -= ran
+                if timed:
+                    solves[-1][2] = cur["it"]
+
         for _ in range(warmup):
-            ctx.parsdmm_steps(1)
+            advance(1, False)
         if mid_hook is not None:
             mid_hook()
         restore_stdout()
@@ -931,25 +1008,29 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        steps_asked = steps
         if os.environ.get("SIPX_BENCH_DEBUG"):
-            ended = False
-            for k in range(steps):
-                ended = ctx.parsdmm_steps(1)
-                i = warmup + k
+            for _ in range(steps):
+                advance(1, True)
+                i, logs = cur["it"] - 1, ctx._run[2]
                 print(i + 1, "cg", logs["cg_it"][i], "obj %.4e" % logs["obj"][i], "rpri", logs["r_pri"][i], "rho", logs["rho"][i],
                       file=sys.stderr, flush=True)
-                if ended:
-                    break
         else:
-            # ONE call for the K timed steps: the native loop runs them back to back, as sipx_parsdmm does in a real solve (a
-            # call per step from Python put 20-30 us of interpreter time between two iterations)
-            ended = ctx.parsdmm_steps(steps)
+            advance(steps, True)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
+        ended = cur["done"]
         coll1 = collective_counts()
+        if dump is not None:
+            # x, l, y as they stand after the last timed step, the log of the solve they belong to up to that step (sets-sharded:
+            # every rank holds only its own l_i, y_i -- x alone)
+            its = solves[-1][2]
+            xs, ls, ys = ctx.download(want_ly=dist is None or slab)
+            if rank == 0:
+                nb = dump_outputs(dump, xs, ls, ys, ctx.parsdmm_log(), its)
+                progress(f"outputs of iterations 1..{its} of the last solve written to {dump} ({nb / 1e6:.1f} MB)")
+            del xs, ls, ys
         coll_per_step = None
         if coll0 and coll1:
             coll_per_step = {k: round((coll1[k] - coll0.get(k, 0)) / max(steps, 1), 2) for k in coll1}
@@ -998,15 +1079,13 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=red_dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        log = ctx.parsdmm_log()
-        if ended and len(log.obj) < warmup + steps_asked + (stat_steps if want_table else 0):
-            # stop rules 3 / 4 of stop_PARSDMM do not depend on the tolerances: a very long run may end by itself; what was
-            # executed inside the timed region is what is reported
-            steps = max(1, min(steps_asked, len(log.obj) - warmup))
-        if steps != steps_asked:
-            print(f"bench: the solve stopped by itself after {warmup + steps} iterations; {steps} of the {steps_asked} requested steps were timed",
-                  file=sys.stderr)
-        cg_its = int(np.asarray(log.cg_it)[warmup:warmup + steps].sum())
+        # the log of every solve the timed steps ran in, with the first and last of its iterations among them
+        timed = [(ctx._log_result(run[1], run[2]), a, b) for run, a, b in solves]
+        if len(timed) > 1:
+            print(f"bench: the solve stopped by itself {len(timed) - 1} time(s) inside the timed steps; a new solve on the same context "
+                  f"went on each time (timed iterations per solve: {[b - a + 1 for _, a, b in timed]})", file=sys.stderr)
+        cg_its = sum(int(np.asarray(lg.cg_it)[a - 1:b].sum()) for lg, a, b in timed)
+        log = timed[-1][0]                                    # the solve the context holds now
         row0, row1, _ = ctx.slab()
         d = len(np.unique(np.concatenate([np.asarray(o) for o in prop.AtA_offsets])))
         # B_spmv = (d+2) N w per launch -- over the rows this rank's product covers (all N on one GPU)
@@ -1034,25 +1113,25 @@ def main():
                                    f"{rec['libsipx_sha16']}), 2*FETCH_SIZE + WRITE_SIZE per launch (gfx950 correction); not measured in this run")
             except Exception:
                 traffic, traffic_src = None, None
-        finite = bool(np.isfinite(log.obj).all() and np.isfinite(log.r_pri_total).all())
+        finite = all(bool(np.isfinite(lg.obj).all() and np.isfinite(lg.r_pri_total).all()) for lg, _, _ in timed)
         # Whole-iteration roofline with SURVEY 8(d)'s algorithmic bytes: B_rhs + B_resid0 + k B_cg_iter + B_yl + B_log
         # (+ B_adapt + B_Q when rho / gamma are re-adapted, + B_feas every 10th iteration), summed over the timed steps.
         rows = [int(op.shape[0]) for op in A]
         d_i = [len(np.asarray(o)) for o in prop.AtA_offsets]
         pp = len(P)
-        i0 = warmup + 1
         it_bytes = 0.0
-        for i in range(i0, i0 + steps):                       # 1-based PARSDMM iteration numbers of the timed steps
-            k = int(log.cg_it[i - 1])
-            b = (sum(2 * r for r in rows) + N) + (d + 4) * N + k * ((d + 2) * N + 9 * N) + sum(N + 7 * r for r in rows) + 3 * N
-            if i % int(opt.rho_update_frequency) == 0:
-                b += sum(13 * r for r in rows)
-            if i < len(log.rho):
-                changed = np.nonzero(np.asarray(log.rho[i]) != np.asarray(log.rho[i - 1]))[0]
-                b += sum(3 * d_i[j] * N for j in changed)
-            if i % 10 == 0:
-                b += sum(2 * r for r in rows[:pp])
-            it_bytes += b * w
+        for lg, i0, i1 in timed:
+            for i in range(i0, i1 + 1):                       # 1-based PARSDMM iteration numbers (of their solve) of the timed steps
+                k = int(lg.cg_it[i - 1])
+                b = (sum(2 * r for r in rows) + N) + (d + 4) * N + k * ((d + 2) * N + 9 * N) + sum(N + 7 * r for r in rows) + 3 * N
+                if i % int(opt.rho_update_frequency) == 0:
+                    b += sum(13 * r for r in rows)
+                if i < len(lg.rho):
+                    changed = np.nonzero(np.asarray(lg.rho[i]) != np.asarray(lg.rho[i - 1]))[0]
+                    b += sum(3 * d_i[j] * N for j in changed)
+                if i % 10 == 0:
+                    b += sum(2 * r for r in rows[:pp])
+                it_bytes += b * w
         it_gbs = it_bytes / dt / 1e9 / max(world, 1)                # per GPU
         # Sharded: do the ranks hold the same x?  Every rank completes x (a collective in the slab decomposition), takes an exact
         # integer checksum of its bits and the ranks compare -- the first thing to look at in a first multi-GPU run.
@@ -1104,6 +1183,7 @@ def main():
                                        (f"sets sharded over {world} ranks (set i on rank i mod {world}); x-step on z-slabs: reduce-scatter(rhs) -> "
                                         "slab CG (halo plane per product, all-reduced dot partials) -> all-gather(x)")) if world > 1 else "single GPU",
                        "cg_iterations_in_timed_steps": cg_its, "all_logs_finite": finite,
+                       "timed_iterations_per_solve": [b - a + 1 for _, a, b in timed],
                        "driver": "native loop (sipx_parsdmm_begin/_steps)" + (", collectives inside the engine (RCCL)" if dist is not None else "")},
             "roofline": {"bound": "hbm", "kernel": "k_cds<MODE=1> (cds_spmv + p.Ap partials)" if args.q_mode == "cds" else
                          "k_sq<MODE=1> (stencil Q product + p.Ap partials)",
@@ -1282,7 +1362,7 @@ def main():
                 raise RuntimeError("test hook: this rank fails in the middle of the headline's first attempt")
         res, err = None, None
         try:
-            res = measure(args.config, args.steps, args.warmup, mid_hook=mid, **kw)
+            res = measure(args.config, args.steps, args.warmup, mid_hook=mid, dump=args.dump_outputs, **kw)
         except BaseException as e:                                         # (SystemExit of --decomp slab on an unsuitable list included)
             if isinstance(e, KeyboardInterrupt):
                 raise
@@ -1320,7 +1400,7 @@ def main():
     progress(f"headline {args.config}: {args.warmup} warm-up + {args.steps} timed steps")
     r = None
     if dist is None or (world == 1 and not os.environ.get("SIPX_BENCH_HEADLINE_CHAIN")):
-        r = measure(args.config, args.steps, args.warmup)
+        r = measure(args.config, args.steps, args.warmup, dump=args.dump_outputs)
     else:
         native = None if share_gpu else "rccl"                              # (the rehearsal on one GPU runs on callbacks throughout)
         chain = []

@@ -34,7 +34,9 @@ def c1_problem(m, mod, TF=np.float32):
 
 if __name__ == "__main__":
     import scipy.io as sio
-    D = sio.loadmat("/root/reference/examples/Data/compass_velocity.mat")["Data"]
+    if len(sys.argv) != 2:
+        raise SystemExit("usage: python tests/golden/make_golden.py <reference checkout>/examples/Data/compass_velocity.mat")
+    D = sio.loadmat(sys.argv[1])["Data"]
     m2 = D[100:228, 700:828].T                      # (x, z) like permutedims(m,[2,1]) in the example
     m = np.ascontiguousarray(m2.reshape(-1, order="F").astype(np.float32))
     np.save(os.path.join(HERE, "c1_compass_128_m.npy"), m)

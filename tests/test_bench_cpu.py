@@ -102,3 +102,36 @@ def test_headline_fits_what_the_driver_keeps():
         fat = dict(out, comm_probe_us={f"probe_{k}_us (padding)": float(k) for k in range(400)})
         line = bench.headline(fat, None)
         assert len(line) < bench.LINE_LIMIT and json.loads(line)["value"] > 0 and "roofline" in json.loads(line)
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: whole vectors when they fit; beyond the budget a sample at fixed, seeded, sorted indices, x keeping at
+    least half of the room -- the same files from two calls on the same arrays, float32 / float64 only."""
+    from types import SimpleNamespace
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(7)
+    x = np.arange(100_000, dtype=np.float32) + 0.5
+    l = [rng.standard_normal(n).astype(np.float32) for n in (100_000, 99_000)]
+    y = [v + 1 for v in l]
+    log = SimpleNamespace(**{k: np.arange(24.0).reshape(12, 2) if k in ("rho", "gamma", "r_pri", "r_dual") else np.arange(12.0)
+                             for k in bench.DUMP_LOG})
+    log.evol_x[0] = np.nan                                             # iteration 1: 0 / 0, as the engine and the reference log it
+    bench.dump_outputs(str(tmp_path / "whole"), x, l, y, log, 9)
+    assert np.array_equal(np.load(tmp_path / "whole" / "x.npy"), x) and np.array_equal(np.load(tmp_path / "whole" / "y_2.npy"), y[1])
+    assert np.load(tmp_path / "whole" / "log_rho.npy").shape == (9, 2) and np.load(tmp_path / "whole" / "log_cg_it.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "whole" / "log_evol_x.npy"), log.evol_x[1:9])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 600_000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), x, l, y, log, 9)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "whole"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 600_000
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b) and np.isfinite(a).all(), f
+    xs = np.load(tmp_path / "a" / "x.npy")
+    assert 300_000 // 4 > xs.size >= (600_000 - 20_000) // 2 // 4
+    idx = (xs - 0.5).astype(np.int64)                                  # x[i] = i + 1/2: the values name their indices
+    assert np.array_equal(x[idx], xs) and np.all(np.diff(idx) > 0)

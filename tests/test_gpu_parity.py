@@ -2068,3 +2068,83 @@ def test_bench_contract_line(dist_env):
         assert ss["speculative_exchange"] > 0 and 0 <= ss["fallbacks"] <= ss["speculative_exchange"]
     else:
         assert h["comm"]["rccl_version"] == "none" and "decompositions" not in h
+
+
+@pytest.mark.timeout(300)
+def test_bench_dumps_what_the_timed_steps_computed(sipx, tmp_path):
+    """bench.py --dump-outputs DIR: after the timed steps, x, every l_i and y_i and the log of iterations 1..warmup+steps as
+    DIR/<name>.npy in the run's precision -- what the same iterations give through the host API, and the log the line's
+    figures came from (the statistics window that follows the timed steps does not reach the files)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c3-small", "--steps", "4", "--warmup", "2", "--detail", "",
+                        "--dump-outputs", str(out), "--no-cpu-baseline", "--no-512", "--no-c4", "--no-c5"],
+                       capture_output=True, text=True, timeout=280, env=dict(os.environ))
+    assert r.returncode == 0, r.stderr[-2000:]
+    h = json.loads(r.stdout.strip().splitlines()[-1])
+    assert h["steps"] == 4 and h["ms_per_step"] > 0
+    files = sorted(os.listdir(out))
+    assert {"x.npy", "l_1.npy", "y_5.npy", "log_obj.npy", "log_cg_it.npy", "log_rho.npy"} <= set(files)
+    assert sum(os.path.getsize(out / f) for f in files) <= 64_000_000
+    for f in files:
+        assert np.isfinite(np.load(out / f)).all(), f
+    x = np.load(out / "x.npy")
+    assert x.dtype == np.float32 and x.shape == (64 ** 3,) and np.isfinite(x).all()
+    cg = np.load(out / "log_cg_it.npy")
+    assert cg.shape == (6,) and int(cg[2:].sum()) == h["config"]["cg_iterations_in_timed_steps"]
+    sys.path.insert(0, root)
+    import bench
+    n, hh, kinds = bench.CONFIGS["c3-small"]
+    m = bench.synthetic_model(n, np.float32, 20240601 + 3)
+    gs = sipx.compgrid(hh, n)
+
+    def radius_of(opname):
+        return float(0.5 * np.abs((sipx.get_TD_operator(gs, opname, np.float32)[0] @ m).astype(np.float64)).sum())
+    g, c = bench.build_problem(sipx, n, hh, kinds, m, np.float32, radius_of)
+    P, A, prop = sipx.setup_constraints(c, g, np.float32)
+    opt = bench.bench_options(sipx, np.float32, 2 + 4 + 4 + 1)
+    A, AtA, _, _ = sipx.PARSDMM_precompute_distribute(A, prop, g, opt)
+    ctx = sipx.host.build_context(m, AtA, A, prop, P, g, opt)
+    try:
+        ctx.parsdmm_begin(opt)
+        ctx.parsdmm_steps(6)
+        xr, lr, yr = ctx.download()
+        log = ctx.parsdmm_log()
+    finally:
+        ctx.close()
+    assert np.array_equal(cg, log.cg_it[:6])
+    assert np.allclose(np.load(out / "log_obj.npy"), log.obj[:6], rtol=1e-6, atol=0)
+    assert np.allclose(np.load(out / "log_evol_x.npy"), log.evol_x[1:6], rtol=1e-6, atol=0)
+    scale = float(np.abs(xr).max())
+    assert np.abs(x.astype(np.float64) - xr).max() <= 1e-5 * scale
+    for i in range(len(lr)):
+        for name, ref in ((f"l_{i + 1}", lr[i]), (f"y_{i + 1}", yr[i])):
+            v = np.load(out / f"{name}.npy")
+            assert v.dtype == np.float32 and v.shape == ref.shape, name
+            assert np.abs(v.astype(np.float64) - ref).max() <= 1e-5 * max(float(np.abs(ref).max()), 1.0), name
+
+
+@pytest.mark.timeout(300)
+def test_bench_times_exactly_the_steps_asked_for():
+    """--steps K times K iterations even where the solve ends by itself first (stop rules 3 / 4 of stop_PARSDMM do not depend
+    on the tolerances): a new solve on the same context goes on, and the line's ms_per_step is the wall time of K iterations / K."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    detail = os.path.join(tempfile.mkdtemp(prefix="sipx_bench_"), "detail.json")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c3-small", "--steps", "600", "--warmup", "2", "--detail", detail,
+                        "--no-cpu-baseline", "--no-512", "--no-c4", "--no-c5"], capture_output=True, text=True, timeout=280, env=dict(os.environ))
+    assert r.returncode == 0, r.stderr[-2000:]
+    h = json.loads(r.stdout.strip().splitlines()[-1])
+    d = json.load(open(detail))
+    per_solve = d["config"]["timed_iterations_per_solve"]
+    assert h["steps"] == 600 and sum(per_solve) == 600 and min(per_solve) >= 1, per_solve
+    assert h["ms_per_step"] > 0 and abs(h["value"] * h["ms_per_step"] - 1e3) <= 0.2          # (five significant digits each)
+    assert d["config"]["cg_iterations_in_timed_steps"] > 0 and d["config"]["all_logs_finite"]

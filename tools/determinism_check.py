@@ -2,7 +2,8 @@
 stream raced with a kernel on the non-blocking engine stream at set-up, and the runs differed; every collective protocol of the slab
 decomposition rests on all ranks deciding alike from identical state.)  usage: python tools/determinism_check.py  (on a GPU box)"""
 import sys, os, tempfile, numpy as np
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch.multiprocessing as mp
 import test_gpu_parity as TP
 def run(kinds, n, world, reps, tag, env=None):

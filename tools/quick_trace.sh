@@ -2,7 +2,7 @@
 # Kernel trace + timeline of one bench configuration (run through gpurun from the repo root): tools/quick_trace.sh <tag> [bench args...]
 set -e -o pipefail
 TAG=$1; shift
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 O=gpurun_out/prof; mkdir -p $O
 rm -rf $O/kt_$TAG
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/kt_$TAG -o t --output-format csv -- python3 bench.py --no-cpu-baseline --no-512 --no-c4 "$@" > $O/${TAG}_bench_under_rocprof.json 2>$O/${TAG}_kt.err

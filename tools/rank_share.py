@@ -1,6 +1,6 @@
-import sys, json, time
+import sys, json, os, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from __graft_entry__ import load_package
 sipx = load_package()
 import bench

@@ -6,7 +6,7 @@
 set -e -o pipefail
 R=${1:-r05}
 PART=${2:-all}
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 O=gpurun_out/prof; mkdir -p $O
 T="timeout -k 10 500"
 # profiled runs: the headline workload only, without the all-kernel statistics window (its event records would show up as gaps)

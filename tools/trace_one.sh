@@ -3,7 +3,7 @@
 # usage (through gpurun, from the repo root): tools/trace_one.sh <config> <tag> [bench args...]   -> gpurun_out/prof/<tag>_*
 set -e -o pipefail
 cfg=$1; tag=$2; shift 2
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 O=gpurun_out/prof; mkdir -p $O
 B="--no-cpu-baseline --no-512 --no-c4 --no-c5 --no-kernel-table"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/kt_$tag -o t --output-format csv -- python3 bench.py $B --config $cfg "$@" > $O/${tag}_bench_under_rocprof.json 2>$O/kt_$tag.err
