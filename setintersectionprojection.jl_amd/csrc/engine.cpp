@@ -38,6 +38,7 @@ void refresh_env_knobs() {
   k.rhs_march = (int)num("SIPX_RHS_MARCH", 1);
   k.rhs_march_zchunk = num("SIPX_RHS_MARCH_ZCHUNK", 0);
   k.q_plan = (int)num("SIPX_Q_PLAN", 1);
+  k.q_table = (int)num("SIPX_Q_TABLE", 1);
   k.mark_stride = (int)std::max<long long>(0, num("SIPX_MARK_STRIDE", 0));
   k.trace_searches = (int)num("SIPX_TRACE_SEARCHES", 0);
   k.trace_kernels = (int)num("SIPX_TRACE_KERNELS", 0);
@@ -435,7 +436,7 @@ class Engine : public EngineBase {
     if (loose_owned_) { dfree(loose_v_); dfree(loose_w_); }
     (void)hipStreamSynchronize(stream_);
     for (auto& s : sets_) free_set(s);
-    for (void* p : {(void*)xr_base_[0], (void*)xr_base_[1], (void*)xr_base_[2], (void*)w_base_, (void*)rhs_, (void*)m_base_, (void*)r_base_, (void*)p_base_, (void*)p2_base_, (void*)Ap_, (void*)Q_, (void*)Q2_,
+    for (void* p : {(void*)xr_base_[0], (void*)xr_base_[1], (void*)xr_base_[2], (void*)w_base_, (void*)rhs_, (void*)m_base_, (void*)r_base_, (void*)p_base_, (void*)p2_base_, (void*)Ap_, (void*)Q_, (void*)Q2_, (void*)qtab_,
                     (void*)scr_v_, (void*)scr_c_, (void*)scr_i_, (void*)scr_w_, (void*)part_cg_, (void*)part_tmp_, (void*)part_sets_,
                     (void*)maxpart_, (void*)cg_dev_, (void*)gbuf_, (void*)stage_, (void*)sstage_, (void*)fbuf_, (void*)agree_buf_})
       dfree(p);
@@ -1033,6 +1034,7 @@ class Engine : public EngineBase {
 
     assemble_Q();
     if (q_fused_ && !stencil_q_ && !comm_ && cds_.march != 0) Q2_ = dalloc<T>((size_t)Nx_ * cds_.d);     // (SIPX_Q_FUSED=1 only)
+    build_q_table();
     {
       // The lane: one rank, a list the sweep takes in part (C4) -- the slice-rank / nuclear-norm set, a chain of batched GEMMs and
       // small factorisations with host round trips in it (ext_proj.hip), runs on a stream of its own, queued by a host thread of
@@ -1178,6 +1180,7 @@ class Engine : public EngineBase {
     mark_step_[0] = mark_step_[1] = 0;
     run_ = Run();
     assemble_Q();
+    build_q_table();
     initial_feasibility(feasibility_initial);
   }
 
@@ -2784,12 +2787,65 @@ class Engine : public EngineBase {
         return;
       }
     }
-    K<T>::q_update(stream_, G_, qr0_, qr1_, cds_, a, Q_);
+    q_apply(a);
   }
   void flush_q_pending() {
     if (!q_pending_) return;
     q_pending_ = false;
-    K<T>::q_update(stream_, G_, qr0_, qr1_, cds_, q_pending_args_, Q_);
+    q_apply(q_pending_args_);
+  }
+  // a batch of the Q update (Q[:, b] += alpha_i A_i'A_i[:, b], set order): on the class table while the products use it -- the
+  // bands go stale -- else on the bands
+  void q_apply(const QArgs<T>& a) {
+    if (cds_.qtab) {
+      if (K<T>::qtab_update(stream_, G_, cds_, a, qtab_)) {
+        q_stale_ = q_stale_ || a.nsets > 0;
+        return;
+      }
+      ensure_q_bands();                    // no plan (explicit A'A bands, SIPX_Q_PLAN=0): the bands for the rest of the context
+      cds_.qtab = nullptr;
+      qtab_reason_ = "an update without a plan";
+    }
+    K<T>::q_update(stream_, G_, qr0_, qr1_, cds_, a, Q_);
+  }
+  // the four stored bands written from the class table, if an update went to the table only: before anything reads Q_ itself
+  void ensure_q_bands() {
+    if (!q_stale_) return;
+    K<T>::qtab_write_bands(stream_, Nx_, cds_, qtab_, Q_);
+    q_stale_ = false;
+  }
+  // The class table of Q (CdsArgs::qtab, kernels_cds.hip): the z-marching products take the coefficients of the 7-band matrix
+  // from 4 x 27 values -- one per stored band and boundary class of a row -- instead of loading four bands (8 -> 4, 7 -> 3,
+  // 6 -> 2 N w per product), and a planned update touches the table only.  Seeded from the assembled Q and used only if every
+  // stored value equals its class's entry bit for bit (the check reads the bands once per solve); a Q that is not constant on
+  // the classes (caller-supplied A'A bands that vary per point) keeps the bands.
+  void build_q_table() {
+    cds_.qtab = nullptr;
+    q_stale_ = false;
+    const char* why = nullptr;
+    if (!env_knobs().q_table) why = "SIPX_Q_TABLE=0";
+    else if (stencil_q_) why = "stencil Q";
+    else if (q_fused_) why = "SIPX_Q_FUSED";
+    else if (mk_) why = "Minkowski";
+    else if (comm_) why = "sharded";
+    else if (!cds_.march || !cds_.sym || cds_.d != 7) why = "not the 7-band matrix of a 3-D grid";
+    else if (qr0_ != 0 || qr1_ != Nx_ || !K<T>::march_applies(Nx_, cds_)) why = "the z-marching product does not apply";
+    if (why) {
+      qtab_reason_ = why;
+      return;
+    }
+    if (!qtab_) qtab_ = dalloc<T>(QT_N + 8);          // (+ the check's flag)
+    int* ok = (int*)(qtab_ + QT_N);
+    K<T>::qtab_build(stream_, Nx_, cds_, Q_, qtab_, ok);
+    int h = 0;
+    SIPX_HIP(hipMemcpyAsync(&h, ok, sizeof(int), hipMemcpyDeviceToHost, stream_));
+    SIPX_HIP(hipStreamSynchronize(stream_));
+    if (!h) {
+      qtab_reason_ = "Q is not constant on the boundary classes";
+      return;
+    }
+    cds_.qtab = qtab_;
+    qtab_reason_ = "";
   }
 
   // Warm start of this (finer) level from a solved coarser one, device to device: x by nearest-neighbour resampling of the
@@ -3293,6 +3349,7 @@ class Engine : public EngineBase {
     if (Q && stencil_q_) throw std::runtime_error("stencil Q mode stores no bands (use sipx_apply_Q)");
     if (Q && comm_ && comm_->world > 1) throw std::runtime_error("a sharded context maintains its slab of Q only");
     flush_q_pending();
+    if (Q) ensure_q_bands();
     if (Q && cds_.sym) {      // the negative bands are not maintained while solving: rebuild them from their partners
       K<T>::mirror_bands(stream_, Nx_, cds_, Q_);
       SIPX_HIP(hipStreamSynchronize(stream_));
@@ -3393,7 +3450,8 @@ class Engine : public EngineBase {
       for (auto& ch : t) if (ch == '"' || ch == '\\' || (unsigned char)ch < 32) ch = ' ';
       o += ", \"comm_selftest\": \"" + t + "\"";
     }
-    o += ", \"lane_set\": " + std::to_string(lane_set_);       // the set updated on a stream of its own (-1: none), lane_start
+    o += ", \"lane_set\": " + std::to_string(lane_set_);
+    o += std::string(", \"q_table\": {\"on\": ") + (cds_.qtab ? "true" : "false") + ", \"reason\": \"" + qtab_reason_ + "\"}";       // the set updated on a stream of its own (-1: none), lane_start
     o += ", \"batched_searches\": {\"searches\": " + std::to_string(batch_searches_) + ", \"fallbacks\": " + std::to_string(batch_fallbacks_) + "}";
     // slice-rank / matrix-rank sets: which route their projector took since the context was finalised (ext_proj.hip)
     long long rc[6] = {0, 0, 0, 0, 0, 0};
@@ -3843,6 +3901,8 @@ class Engine : public EngineBase {
   }
 
   void assemble_Q() {      // PARSDMM_initialize.jl:222-230
+    cds_.qtab = nullptr;      // (the bands are assembled; build_q_table decides about the table afterwards)
+    q_stale_ = false;
     if (stencil_q_) {
       for (auto& s : sets_)
         if (s.ata) throw std::runtime_error("stencil Q mode needs descriptor-generated AtA for every set (pass ata_R = NULL)");
@@ -3876,7 +3936,7 @@ class Engine : public EngineBase {
     QArgs<T> a;
     a.nsets = 0;
     for (int i = 0; i < p_n_; ++i) push_qset(a, sets_[i], rho_[i]);   // Q = 0 + rho_1 AtA_1 + rho_2 AtA_2 + ...
-    K<T>::q_update(stream_, G_, qr0_, qr1_, cds_, a, Q_);
+    q_apply(a);
   }
 
   // Minkowski mode: Q[:, b] += alpha_i AtA_i[:, b] for the sets with alpha_i != 0, batches of MAX_SETS in set order
@@ -3904,7 +3964,7 @@ class Engine : public EngineBase {
     if (s.ata_off.size() > 9) throw std::runtime_error("more than 9 bands in one set's AtA are not supported");
     for (long long o : s.ata_off) (void)q_col(o);     // CDS_scaled_add!.jl:18-20: the diagonal must exist in Q
     if (a.nsets == MAX_SETS) {                         // flush a full batch, keep the order
-      K<T>::q_update(stream_, G_, qr0_, qr1_, cds_, a, Q_);
+      q_apply(a);
       a.nsets = 0;
     }
     QSet<T>& q = a.s[a.nsets++];
@@ -4331,6 +4391,9 @@ class Engine : public EngineBase {
   // the 512-thread march kernel more than the traffic saves (512^3: 115 -> 109 it/s), and at 256^3 the separate kernels meet
   // in the Infinity Cache (k_q_update leaves the four bands there: 46 us for 8 N w; 774 -> 732 it/s).
   bool q_fused_ = false, q_pending_ = false, q_defer_ = false;
+  T* qtab_ = nullptr;                   // class table of Q + the check's flag (build_q_table)
+  bool q_stale_ = false;                // the stored bands lag the table (ensure_q_bands)
+  std::string qtab_reason_ = "not built";   // why the products use the bands ("": they use the table)
   QArgs<T> q_pending_args_;
   T* Q2_ = nullptr;
   long long dev_bytes_ = 0;           // device bytes this context allocated (dalloc + the library-backed projectors' own buffers)

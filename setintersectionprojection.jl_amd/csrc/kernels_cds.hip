@@ -213,6 +213,19 @@ struct QUpd {
   Grid G;
 };
 struct NoExtra {};
+// The products on the CLASS TABLE of Q (CdsArgs::qtab): no band is loaded.  Q = sum alpha_i A_i'A_i (+ planned updates) takes
+// one value per stored band and boundary class of the row -- (cx, cy, cz), each 0 / 1 / 2 for the first / an interior / the
+// last point of its line -- the same products added in the same order in every class (k_q_update_plan), so the table holds
+// the bits of the bands (and the engine checks that it does, value by value, before using it).  Layout: tab[27 role +
+// cx + 3 cy + 9 cz], roles 0..3 = offsets 0, +1, +n1, +n1n2.
+template <typename T>
+struct QTab {
+  const T* tab;
+};
+template <typename X>
+struct IsQTab { static constexpr bool value = false; };
+template <typename T>
+struct IsQTab<QTab<T>> { static constexpr bool value = true; };
 // value of stored band `role` at the point with coordinates c after the pending update; tab: the plan's products (LDS copy)
 template <typename T>
 __device__ __forceinline__ T q_upd_val(const QUpd<T>& u, const T* __restrict__ tab, int role, const Coord& c, T qv) {
@@ -242,14 +255,20 @@ __device__ __forceinline__ T q_upd_val(const QUpd<T>& u, const T* __restrict__ t
 template <typename T>
 __device__ __forceinline__ T q_upd_val(const NoExtra&, const T*, int, const Coord&, T qv) { return qv; }
 template <typename T>
+__device__ __forceinline__ T q_upd_val(const QTab<T>&, const T*, int, const Coord&, T qv) { return qv; }
+template <typename T>
 __device__ __forceinline__ void load_plan_tab(const QUpd<T>& u, T* tab) {
   for (int i = threadIdx.x; i < u.plan.ntab; i += blockDim.x) tab[i] = u.plan.tab[i];
 }
 template <typename T>
 __device__ __forceinline__ void load_plan_tab(const NoExtra&, T*) {}
 template <typename T>
+__device__ __forceinline__ void load_plan_tab(const QTab<T>&, T*) {}
+template <typename T>
 __device__ __forceinline__ const Grid& extra_grid(const QUpd<T>& u) { return u.G; }
 __device__ __forceinline__ Grid extra_grid(const NoExtra&) { return Grid{}; }
+template <typename T>
+__device__ __forceinline__ Grid extra_grid(const QTab<T>&) { return Grid{}; }
 template <typename T, int V>
 __device__ __forceinline__ void store_bands(const QUpd<T>& u, long long r, const Vec<T, V>& r0, const Vec<T, V>& r1, const Vec<T, V>& r2,
                                             const Vec<T, V>& r3) {
@@ -260,6 +279,26 @@ __device__ __forceinline__ void store_bands(const QUpd<T>& u, long long r, const
 }
 template <typename T, int V>
 __device__ __forceinline__ void store_bands(const NoExtra&, long long, const Vec<T, V>&, const Vec<T, V>&, const Vec<T, V>&, const Vec<T, V>&) {}
+template <typename T, int V>
+__device__ __forceinline__ void store_bands(const QTab<T>&, long long, const Vec<T, V>&, const Vec<T, V>&, const Vec<T, V>&, const Vec<T, V>&) {}
+template <typename T>
+__device__ __forceinline__ void load_class_tab(const QTab<T>& u, T* tab) {
+  for (int i = threadIdx.x; i < QT_N; i += blockDim.x) tab[i] = u.tab[i];
+}
+template <typename X, typename T>
+__device__ __forceinline__ void load_class_tab(const X&, T*) {}
+__device__ __forceinline__ int line_class(long long c, long long n) { return c == 0 ? 0 : (c == n - 1 ? 2 : 1); }
+// stored band `role` at the V points from (i0, j, k) of a row whose classes along y and z are cyz = 3 cy + 9 cz: three values
+// per row, a select on the first / last point of the line per element
+template <typename T, int V>
+__device__ __forceinline__ Vec<T, V> tab_row(const T* tab, int role, int cyz, long long i0, long long n1) {
+  const T* e = tab + 27 * role + cyz;
+  const T first = e[0], mid = e[1], last = e[2];
+  Vec<T, V> v;
+#pragma unroll
+  for (int k = 0; k < V; ++k) v.v[k] = i0 + k == 0 ? first : (i0 + k == n1 - 1 ? last : mid);
+  return v;
+}
 __device__ __forceinline__ void publish_ticket(unsigned long long* ticket, unsigned seq, int iter, int done);      // (defined with the CG scalar steps below)
 constexpr int MARCH_NT = 512;
 template <typename T, int V, int ORD, int MODE, typename X>
@@ -271,6 +310,7 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
                                                         long long items, CgState<T>* __restrict__ st, CgState<T>* __restrict__ host,
                                                         unsigned long long* ticket, X extra) {
   constexpr bool UPD = MODE == 4;         // MODE 4 = MODE 2 (residual form) with the pending Q update applied on the fly
+  constexpr bool TAB = IsQTab<X>::value;  // coefficients from the class table of Q, no band loaded (QTab)
   if (MODE == 1 && *done) return;
   // MODE 3 (fused CG iteration, see k_cds_fused): the scalar step of iteration k (resvec, stop test, beta) and the product of
   // iteration k + 1 on p_{k+1} = r_{k+1} + beta p_k, formed wherever it is loaded (x = r_{k+1}, b = p_k; same arithmetic as
@@ -303,10 +343,15 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
     return v;
   };
   auto ldx1 = [&](long long at) -> T { return MODE == 3 ? x[at] + beta * b[at] : x[at]; };
-  __shared__ T sx[2][V][MARCH_NT], sr[2][V][MARCH_NT];
+  __shared__ T sx[2][V][MARCH_NT], sr[TAB ? 1 : 2][TAB ? 1 : V][TAB ? 1 : MARCH_NT];
   __shared__ T qtab[UPD ? QP_TAB : 1];
+  __shared__ T ctab[TAB ? QT_N : 1];
   if (UPD) {
     load_plan_tab<T>(extra, qtab);
+    __syncthreads();
+  }
+  if (TAB) {
+    load_class_tab(extra, ctab);
     __syncthreads();
   }
   const int tid = threadIdx.x, LX = 1 << lgLX, tx = tid & (LX - 1), ty = tid >> lgLX, TY = MARCH_NT >> lgLX;
@@ -325,7 +370,9 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
     if (active) {
       xm = ldx(st2 * (k0 - 1) + go);                            // (x carries a halo of a plane on both sides)
       x0 = ldx(st2 * k0 + go);
-      if (k0 > 0) {
+      if (k0 > 0 && TAB) {
+        rzm = tab_row<T, V>(ctab, 3, 3 * line_class(j, n2) + 9 * line_class(k0 - 1, n3), i0, n1);
+      } else if (k0 > 0) {
         rzm = ldv<T, V>(R3 + st2 * (k0 - 1) + go);
         if (UPD) {
 #pragma unroll
@@ -337,12 +384,23 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
       const int par = (int)(kz & 1);
       const long long pz = st2 * kz;
       Vec<T, V> xp = zerov<T, V>(), r0 = xp, r1 = xp, r2 = xp, r3 = xp, bv = xp;
+      // (TAB) classes of this row along y and z, of the row above (j - 1, or the last row of the plane below) and the one in
+      // front of element 0 (i0 - 1, or the last point of the row above)
+      const int cz = TAB ? line_class(kz, n3) : 0, cyz = TAB ? 3 * line_class(j, n2) + 9 * cz : 0;
+      const int cyz_up = !TAB ? 0 : (j > 0 ? 3 * line_class(j - 1, n2) + 9 * cz : 3 * line_class(n2 - 1, n2) + 9 * line_class(kz - 1, n3));
       if (active) {
         xp = ldx(pz + st2 + go);
-        r0 = ldv_nt<T, V>(R0 + pz + go);
-        r1 = ldv_nt<T, V>(R1 + pz + go);
-        r2 = ldv_nt<T, V>(R2 + pz + go);
-        r3 = ldv_nt<T, V>(R3 + pz + go);
+        if constexpr (TAB) {
+          r0 = tab_row<T, V>(ctab, 0, cyz, i0, n1);
+          r1 = tab_row<T, V>(ctab, 1, cyz, i0, n1);
+          r2 = tab_row<T, V>(ctab, 2, cyz, i0, n1);
+          r3 = tab_row<T, V>(ctab, 3, cyz, i0, n1);
+        } else {
+          r0 = ldv_nt<T, V>(R0 + pz + go);
+          r1 = ldv_nt<T, V>(R1 + pz + go);
+          r2 = ldv_nt<T, V>(R2 + pz + go);
+          r3 = ldv_nt<T, V>(R3 + pz + go);
+        }
         if (MODE == 2 || MODE == 4) bv = ldv<T, V>(b + pz + go);
         if (UPD) {
 #pragma unroll
@@ -356,14 +414,19 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
         }
       }
 #pragma unroll
-      for (int k = 0; k < V; ++k) { sx[par][k][tid] = x0.v[k]; sr[par][k][tid] = r2.v[k]; }
+      for (int k = 0; k < V; ++k) {
+        sx[par][k][tid] = x0.v[k];
+        if constexpr (!TAB) sr[par][k][tid] = r2.v[k];
+      }
       // the points next door along x: lanes, or (tile edge / wave edge) one element from memory
-      T xl = __shfl_up(x0.v[V - 1], 1, 64), xr = __shfl_down(x0.v[0], 1, 64), rl = __shfl_up(r1.v[V - 1], 1, 64);
+      T xl = __shfl_up(x0.v[V - 1], 1, 64), xr = __shfl_down(x0.v[0], 1, 64), rl = TAB ? T(0) : __shfl_up(r1.v[V - 1], 1, 64);
       const long long r = pz + go;               // row of element 0
+      if (TAB && r > 0)                          // band +1 at r - 1: (i0 - 1, j, kz), or the last point of the row in front
+        rl = i0 > 0 ? ctab[27 + line_class(i0 - 1, n1) + cyz] : ctab[27 + line_class(n1 - 1, n1) + cyz_up];
       if (active) {
         if (tx == 0 || (tid & 63) == 0) {
           xl = ldx1(r - 1);
-          rl = r > 0 ? R1[r - 1] : T(0);
+          if (!TAB) rl = r > 0 ? R1[r - 1] : T(0);
           if (UPD && r > 0) rl = q_upd_val<T>(extra, qtab, 1, coords(extra_grid(extra), r - 1), rl);     // (still the old value in memory)
         }
         if (tx == LX - 1 || (tid & 63) == 63) xr = ldx1(r + V);
@@ -371,12 +434,16 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
       __syncthreads();
       if (active) {
         Vec<T, V> xu = zerov<T, V>(), xd = xu, ru = xu;    // x of the row above (j - 1) / below (j + 1), +n1 band of the row above
+        if (TAB && r - st1 >= 0) ru = tab_row<T, V>(ctab, 2, cyz_up, i0, n1);
         if (ty > 0) {
 #pragma unroll
-          for (int k = 0; k < V; ++k) { xu.v[k] = sx[par][k][tid - LX]; ru.v[k] = sr[par][k][tid - LX]; }
+          for (int k = 0; k < V; ++k) {
+            xu.v[k] = sx[par][k][tid - LX];
+            if constexpr (!TAB) ru.v[k] = sr[par][k][tid - LX];
+          }
         } else {
           xu = ldx(r - st1);
-          if (r - st1 >= 0) {
+          if (!TAB && r - st1 >= 0) {
             ru = ldv<T, V>(R2 + r - st1);
             if (UPD) {
 #pragma unroll
@@ -390,21 +457,22 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
         } else {
           xd = ldx(r + st1);
         }
+        // k_cds's mask, column rr + offset inside [0, N), per role: the V points of a thread lie on one line of x (i0 + V <= n1),
+        // so only the +-1 neighbours of the first / last element of the matrix differ from the row's answer
+        const bool up = r >= st1, down = r + st1 < N, below = r >= st2, above = r + st2 < N, first = r == 0, last = r + V == N;
         Vec<T, V> o4;
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-          const long long rr = r + k;
           // band value and vector entry of each role
           const T rv[7] = {r0.v[k], k == 0 ? rl : r1.v[k - 1], r1.v[k], ru.v[k], r2.v[k], rzm.v[k], r3.v[k]};
           const T xv[7] = {x0.v[k], k == 0 ? xl : x0.v[k - 1], k == V - 1 ? xr : x0.v[k + 1], xu.v[k], xd.v[k], xm.v[k], xp.v[k]};
-          const long long co[7] = {0, -1, 1, -st1, st1, -st2, st2};
+          const bool in[7] = {true, k > 0 || !first, k < V - 1 || !last, up, down, below, above};
           T acc = T(0);
 #pragma unroll
           for (int q = 0; q < 7; ++q) {
             const int role = march_role(ORD, q);
             const T t = acc + rv[role] * xv[role];
-            const long long c = rr + co[role];
-            acc = (c >= 0 && c < N) ? t : acc;
+            acc = in[role] ? t : acc;
           }
           o4.v[k] = acc;
         }
@@ -452,10 +520,13 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
 
 // the march applies when the engine marked the matrix (CdsArgs::march) and the row range is whole planes; small grids, where
 // a launch would not fill the chip, keep k_cds
-template <typename T, int MODE>
-static bool try_march(hipStream_t s, long long N, long long r0, long long r1, const T* R, const CdsArgs& a, const T* x, T* y, const T* b,
-                      T* pout, T* xold, double* partials, const int* done, CgState<T>* st = nullptr, CgState<T>* host = nullptr,
-                      unsigned long long* ticket = nullptr, const QUpd<T>* upd = nullptr) {
+// launch geometry of the march over rows [r0, r1); false: it does not apply
+struct MarchGeom {
+  int lg, tiles_x, tiles_y, zchunk, grid;
+  long long items;
+};
+template <typename T>
+static bool march_geom(long long N, long long r0, long long r1, const CdsArgs& a, MarchGeom& m) {
   // SIPX_CDS_MARCH=0: never; =2: also on grids too small to fill the chip that way, in chunks of SIPX_CDS_MARCH_ZCHUNK planes (tests)
   // (one copy for all instantiations, refreshed whenever a context is finalised: env_knobs)
   const int sw = env_knobs().cds_march;
@@ -476,17 +547,40 @@ static bool try_march(hipStream_t s, long long N, long long r0, long long r1, co
   if (zchunk > planes) zchunk = planes;
   const long long nchunks = (planes + zchunk - 1) / zchunk, items = tiles * nchunks;
   if (items < 384 && sw != 2) return false;
-  const int grid = (int)(items < NB ? items : NB);
+  m = MarchGeom{lg, tiles_x, tiles_y, (int)zchunk, (int)(items < NB ? items : NB), items};
+  return true;
+}
+template <typename T>
+bool K<T>::march_applies(long long N, const CdsArgs& a) {
+  MarchGeom m;
+  return march_geom<T>(N, 0, N, a, m);
+}
+
+template <typename T, int MODE>
+static bool try_march(hipStream_t s, long long N, long long r0, long long r1, const T* R, const CdsArgs& a, const T* x, T* y, const T* b,
+                      T* pout, T* xold, double* partials, const int* done, CgState<T>* st = nullptr, CgState<T>* host = nullptr,
+                      unsigned long long* ticket = nullptr, const QUpd<T>* upd = nullptr) {
+  MarchGeom m;
+  if (!march_geom<T>(N, r0, r1, a, m)) return false;
+  constexpr int V = sizeof(T) == 8 ? 2 : 4;
+  const long long n1 = a.gn[0], n2 = a.gn[1], n3 = a.gn[2], st2 = n1 * n2;
   const T *R0 = R + (long long)a.mb[0] * N, *R1 = R + (long long)a.mb[1] * N, *R2 = R + (long long)a.mb[2] * N, *R3 = R + (long long)a.mb[3] * N;
 #define SIPX_MARCH(ORD, XT, XV)                                                                                                      \
-  hipLaunchKernelGGL((k_cds_march<T, V, ORD, MODE, XT>), dim3(grid), dim3(MARCH_NT), 0, s, n1, n2, n3, r0 / st2, r1 / st2, R0, R1, R2, R3, x, y, b, pout, \
-                     xold, partials, done, lg, tiles_x, tiles_y, (int)zchunk, items, st, host, ticket, XV)
+  hipLaunchKernelGGL((k_cds_march<T, V, ORD, MODE, XT>), dim3(m.grid), dim3(MARCH_NT), 0, s, n1, n2, n3, r0 / st2, r1 / st2, R0, R1, R2, R3, x, y, b, \
+                     pout, xold, partials, done, m.lg, m.tiles_x, m.tiles_y, m.zchunk, m.items, st, host, ticket, XV)
   if constexpr (MODE == 4) {
     if (a.march == 1) SIPX_MARCH(1, QUpd<T>, *upd);
     else SIPX_MARCH(2, QUpd<T>, *upd);
   } else {
-    if (a.march == 1) SIPX_MARCH(1, NoExtra, NoExtra{});
-    else SIPX_MARCH(2, NoExtra, NoExtra{});
+    if (a.qtab) {
+      const QTab<T> tab{(const T*)a.qtab};
+      if (a.march == 1) SIPX_MARCH(1, QTab<T>, tab);
+      else SIPX_MARCH(2, QTab<T>, tab);
+    } else if (a.march == 1) {
+      SIPX_MARCH(1, NoExtra, NoExtra{});
+    } else {
+      SIPX_MARCH(2, NoExtra, NoExtra{});
+    }
   }
 #undef SIPX_MARCH
   return true;
@@ -499,8 +593,10 @@ static void launch_cds(hipStream_t s, long long N, long long r0, long long r1, c
   if (r0 < 0 || r1 > N || r0 > r1) throw std::runtime_error("cds: row range outside the matrix");
   // algorithmic bytes: SURVEY 8(d) counts all d bands + the vector read + the result written ((d+2) rows w; the residual form
   // also reads b and writes x_old: +2); what has to move: only the bands with a non-negative offset under the symmetric read
+  // (the class table of Q: no band moves)
   int read_bands = a.d;
   if (a.sym) { read_bands = 0; for (int b = 0; b < a.d; ++b) read_bands += a.off[b] >= 0 ? 1 : 0; }
+  if (a.qtab) read_bands = 0;
   const double rw = (double)(r1 - r0) * sizeof(T), extra = MODE == 2 ? 4.0 : 2.0;
   const double moved_extra = (MODE == 2 && !xold) ? 3.0 : extra;      // (x_old kept by buffer rotation: not written)
   ObsScope obs(MODE == 0 ? KID_CDS_SPMV : (MODE == 1 ? KID_CDS_DOT : KID_CDS_RESID), s, (a.d + extra) * rw, (read_bands + moved_extra) * rw);
@@ -508,6 +604,7 @@ static void launch_cds(hipStream_t s, long long N, long long r0, long long r1, c
     SIPX_HIP(hipGetLastError());
     return;
   }
+  if (a.qtab) throw std::runtime_error("internal: Q's class table is in use but the z-marching product does not apply");
 #define SIPX_CDS(V, D) \
   hipLaunchKernelGGL((k_cds<T, V, D, MODE>), dim3(fit_grid((r1 - r0) / V, SIPX_CG_GRID)), dim3(BLOCK), 0, s, N, r0, r1, R, a, x, y, b, pout, xold, partials, done)
   // 16 bytes per thread and band: four floats or two doubles (four doubles leave the 7-band kernel 3 waves per SIMD)
@@ -904,6 +1001,127 @@ void K<T>::mirror_bands(hipStream_t s, long long N, const CdsArgs& q, T* Q) {
   SIPX_HIP(hipGetLastError());
 }
 
+// ---- the class table of the march matrix (CdsArgs::qtab, QTab) ---------------------------------------------------------------
+// Seed: entry (role, cx + 3 cy + 9 cz) from one point of that class (the first point, the second, or the last of each line);
+// zero for a class the grid does not have (a line of one or two points).  One workgroup.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_qtab_seed(long long n1, long long n2, long long n3, CdsArgs q, const T* __restrict__ Q,
+                                                     T* __restrict__ tab, int* __restrict__ ok) {
+  const int t = threadIdx.x;
+  if (t == 0) *ok = 1;
+  if (t >= QT_N) return;
+  const int role = t / 27, c = t % 27, cl[3] = {c % 3, (c / 3) % 3, c / 9};
+  const long long n[3] = {n1, n2, n3};
+  long long at[3];
+  bool exists = true;
+  for (int d = 0; d < 3; ++d) {
+    at[d] = cl[d] == 0 ? 0 : (cl[d] == 2 ? n[d] - 1 : 1);
+    exists = exists && line_class(at[d], n[d]) == cl[d];
+  }
+  tab[t] = exists ? Q[(long long)q.mb[role] * n1 * n2 * n3 + at[0] + n1 * (at[1] + n2 * at[2])] : T(0);
+}
+template <typename T>
+__device__ __forceinline__ bool same_bits(T a, T b) {
+  if constexpr (sizeof(T) == 8) return __double_as_longlong(a) == __double_as_longlong(b);
+  else return __float_as_uint(a) == __float_as_uint(b);
+}
+// Check: every value of the four stored bands against its class's entry, bit for bit (-0 and NaN are mismatches); one row of
+// the grid per workgroup step.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_qtab_check(long long n1, long long n2, long long n3, CdsArgs q, const T* __restrict__ Q,
+                                                      const T* __restrict__ tab, int* __restrict__ ok) {
+  __shared__ T ctab[QT_N];
+  for (int i = threadIdx.x; i < QT_N; i += BLOCK) ctab[i] = tab[i];
+  __syncthreads();
+  const long long N = n1 * n2 * n3;
+  bool bad = false;
+  for (long long row = blockIdx.x; row < n2 * n3; row += gridDim.x) {
+    const long long k = row / n2, j = row - k * n2;
+    const int cyz = 3 * line_class(j, n2) + 9 * line_class(k, n3);
+    for (long long i = threadIdx.x; i < n1; i += BLOCK) {
+      const int c = line_class(i, n1) + cyz;
+      for (int role = 0; role < 4; ++role) bad |= !same_bits(Q[(long long)q.mb[role] * N + row * n1 + i], ctab[27 * role + c]);
+    }
+  }
+  if (bad) *ok = 0;
+}
+template <typename T>
+void K<T>::qtab_build(hipStream_t s, long long N, const CdsArgs& q, const T* Q, T* tab, int* ok) {
+  const long long n1 = q.gn[0], n2 = q.gn[1], n3 = q.gn[2];
+  if (n1 * n2 * n3 != N) throw std::runtime_error("qtab_build: the grid is not the matrix's");
+  hipLaunchKernelGGL((k_qtab_seed<T>), dim3(1), dim3(BLOCK), 0, s, n1, n2, n3, q, Q, tab, ok);
+  SIPX_HIP(hipGetLastError());
+  hipLaunchKernelGGL((k_qtab_check<T>), dim3(NB), dim3(BLOCK), 0, s, n1, n2, n3, q, Q, tab, ok);
+  SIPX_HIP(hipGetLastError());
+}
+// Bands from the table: the four stored bands of Q, every value (what the Q of the band path holds after the same updates).
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_qtab_bands(long long n1, long long n2, long long n3, CdsArgs q, const T* __restrict__ tab,
+                                                      T* __restrict__ Q) {
+  __shared__ T ctab[QT_N];
+  for (int i = threadIdx.x; i < QT_N; i += BLOCK) ctab[i] = tab[i];
+  __syncthreads();
+  const long long N = n1 * n2 * n3;
+  for (long long row = blockIdx.x; row < n2 * n3; row += gridDim.x) {
+    const long long k = row / n2, j = row - k * n2;
+    const int cyz = 3 * line_class(j, n2) + 9 * line_class(k, n3);
+    for (long long i = threadIdx.x; i < n1; i += BLOCK) {
+      const int c = line_class(i, n1) + cyz;
+      for (int role = 0; role < 4; ++role) Q[(long long)q.mb[role] * N + row * n1 + i] = ctab[27 * role + c];
+    }
+  }
+}
+template <typename T>
+void K<T>::qtab_write_bands(hipStream_t s, long long N, const CdsArgs& q, const T* tab, T* Q) {
+  const long long n1 = q.gn[0], n2 = q.gn[1], n3 = q.gn[2];
+  if (n1 * n2 * n3 != N) throw std::runtime_error("qtab_write_bands: the grid is not the matrix's");
+  ObsScope obs(KID_Q_UPDATE, s, 4.0 * (double)N * sizeof(T), 4.0 * (double)N * sizeof(T));
+  hipLaunchKernelGGL((k_qtab_bands<T>), dim3(NB), dim3(BLOCK), 0, s, n1, n2, n3, q, tab, Q);
+  SIPX_HIP(hipGetLastError());
+}
+// A planned update on the table: entry (role, class) takes the plan's products of its band in set order, with the class
+// arithmetic of k_q_update_plan -- the same numbers added in the same order as every element of that class there.  One workgroup.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_qtab_update(QPlan<T> p, CdsArgs q, T* __restrict__ tab) {
+  const int t = threadIdx.x;
+  if (t >= QT_N) return;
+  const int role = t / 27, c = t % 27, cx = c % 3, cy = (c / 3) % 3, cz = c / 9;
+  int b = -1;
+  for (int u = 0; u < p.nbands; ++u)
+    if (p.col[u] == q.mb[role]) b = u;
+  if (b < 0) return;
+  T qv = tab[t];
+  for (int ti = 0; ti < p.nterms[b]; ++ti) {
+    const QPlanTerm& m = p.t[b][ti];
+    if (m.kind == 0) {
+      qv = qv + p.tab[m.tab];
+    } else if (m.kind == 1) {
+      int idx = 0, m3 = 1;
+      for (int u = 0; u < m.nblk; ++u) {
+        const int d = m.dir[u];
+        idx += (d == 0 ? cx : (d == 1 ? cy : cz)) * m3;
+        m3 *= 3;
+      }
+      qv = qv + p.tab[m.tab + idx];
+    } else {
+      const int d = m.dir[0], cl = d == 0 ? cx : (d == 1 ? cy : cz);
+      qv = qv + (cl != (m.kind == 2 ? 2 : 0) ? p.tab[m.tab] : p.tab[m.tab + 1]);
+    }
+  }
+  tab[t] = qv;
+}
+template <typename T>
+bool K<T>::qtab_update(hipStream_t s, const Grid& g, const CdsArgs& q, const QArgs<T>& a, T* tab) {
+  if (a.nsets == 0) return true;
+  QPlan<T> plan;
+  if (!env_knobs().q_plan || !make_q_plan<T>(g, q, a, plan)) return false;
+  if (plan.nbands == 0) return true;
+  ObsScope obs(KID_Q_UPDATE, s, 2.0 * QT_N * sizeof(T), 2.0 * QT_N * sizeof(T));
+  hipLaunchKernelGGL((k_qtab_update<T>), dim3(1), dim3(BLOCK), 0, s, plan, q, tab);
+  SIPX_HIP(hipGetLastError());
+  return true;
+}
+
 // Minkowski mode: Q is 2N x d.  Row g = (block row br, local point gl), band offset O -> column (bc, cl); the entry of
 // set i is (A_i'A_i)[gl, cl] when block (br, bc) of its AtA is populated ([B 0;0 0], [0 0;0 B] or [B B;B B]).
 // Q[:, b] += alpha_i * AtA_i[:, b] for every listed set (assembly: alpha = rho; update: alpha = delta rho).
@@ -1184,11 +1402,13 @@ void K<T>::spmv_fused(hipStream_t s, long long N, const T* R, const CdsArgs& a, 
   if (a.d < 1 || a.d > MAXD) throw std::runtime_error("cds: band count out of range");
   int read_bands = a.d;
   if (a.sym) { read_bands = 0; for (int b = 0; b < a.d; ++b) read_bands += a.off[b] >= 0 ? 1 : 0; }
+  if (a.qtab) read_bands = 0;
   ObsScope obs(KID_CDS_FUSED, s, (a.d + 4.0) * (double)N * sizeof(T), (read_bands + 4.0) * (double)N * sizeof(T));   // r, p_k read; p_k+1, Ap written
   if (try_march<T, 3>(s, N, 0, N, R, a, r, Ap, p_old, p_new, nullptr, partials, nullptr, st, host, ticket)) {
     SIPX_HIP(hipGetLastError());
     return;
   }
+  if (a.qtab) throw std::runtime_error("internal: Q's class table is in use but the z-marching product does not apply");
 #define SIPX_CDSF(V, D) \
   hipLaunchKernelGGL((k_cds_fused<T, V, D>), dim3(fit_grid(N / V, SIPX_CG_GRID)), dim3(BLOCK), 0, s, N, R, a, r, p_old, p_new, Ap, partials, st, host, ticket)
   constexpr int VW = sizeof(T) == 8 ? SIPX_F64_VEC : 4;
@@ -1287,6 +1507,10 @@ void K<T>::copy_f64(hipStream_t s, const double* src, double* dst, int n) {
   template void K<T>::q_axpy(hipStream_t, long long, T*, const T*, T);                                               \
   template void K<T>::q_update_mk(hipStream_t, const Grid&, const CdsArgs&, const MkArgs<T>&, T*);                    \
   template void K<T>::mirror_bands(hipStream_t, long long, const CdsArgs&, T*);                                       \
+  template bool K<T>::march_applies(long long, const CdsArgs&);                                                      \
+  template void K<T>::qtab_build(hipStream_t, long long, const CdsArgs&, const T*, T*, int*);                         \
+  template bool K<T>::qtab_update(hipStream_t, const Grid&, const CdsArgs&, const QArgs<T>&, T*);                     \
+  template void K<T>::qtab_write_bands(hipStream_t, long long, const CdsArgs&, const T*, T*);                         \
   template void K<T>::sq_spmv(hipStream_t, const Grid&, const StencilQ<T>&, const T*, T*);                           \
   template void K<T>::sq_spmv_dot(hipStream_t, const Grid&, const StencilQ<T>&, const T*, T*, double*,               \
                                   const CgState<T>*);                                                                 \

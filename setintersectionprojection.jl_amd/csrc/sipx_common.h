@@ -37,6 +37,7 @@ inline int launch_blocks(int per_cu) {
 }
 constexpr int MAXD = 32;          // CDS bands held in kernel arguments
 constexpr int MAX_SETS = 16;      // sets fused in one rhs_compose launch
+constexpr int QT_N = 4 * 27;      // class table of Q: 4 stored bands x 27 boundary classes (CdsArgs::qtab)
 constexpr int YL_SLOTS = 13;      // reductions produced by one y/l-update launch
 constexpr int L1_K = 8;          // probe thresholds of the l1-ball threshold search
 #define SIPX_SOLVE_SLOTS 64      // most workgroups a cooperative k_l1_solve may be launched with
@@ -93,6 +94,7 @@ struct EnvKnobs {
   int trace_searches = 0;         // SIPX_TRACE_SEARCHES=1: every threshold search of the batched chain that needed its fallback sweeps, on stderr
   int mark_stride = 0;            // SIPX_MARK_STRIDE: section timing marks on iterations 1-4 and every such iteration after them (1: every iteration; 0: by grid size, parsdmm_step)
   int q_plan = 1;                 // SIPX_Q_PLAN=0: the Q update regenerates every band value per element (k_q_update) instead of adding planned products
+  int q_table = 1;                // SIPX_Q_TABLE=0: the z-marching products read Q's four stored bands instead of its class table
 };
 const EnvKnobs& env_knobs();
 void refresh_env_knobs();
@@ -177,6 +179,9 @@ struct CdsArgs {
   int march = 0;
   int mb[4] = {0, 0, 0, 0};
   long long gn[3] = {0, 0, 0};
+  // class table of Q (engine: build_q_table), QT_N values of T, or NULL: the march products take the coefficients from it
+  // instead of loading the four stored bands, which may then be stale (the engine writes them back before anything reads them)
+  const void* qtab = nullptr;
 };
 
 // Q = sum_i rho_i A_i'A_i as stencil coefficients (sipx_set_q_mode(SIPX_Q_STENCIL)): w0 = sum of rho over identity
@@ -525,6 +530,13 @@ struct K {
   static void log3(hipStream_t s, long long N, const T* x, const T* m, const T* xold, double* partials);
   static void q_update_mk(hipStream_t s, const Grid& g, const CdsArgs& q, const MkArgs<T>& a, T* Q);
   static void mirror_bands(hipStream_t s, long long N, const CdsArgs& q, T* Q);
+  // class table of the march matrix (kernels_cds.hip): whether the march takes the whole matrix; the table seeded from Q and
+  // checked against every stored band value (*ok = 0 on a mismatch); a planned update applied to it (false: no plan); the
+  // four stored bands written from it
+  static bool march_applies(long long N, const CdsArgs& a);
+  static void qtab_build(hipStream_t s, long long N, const CdsArgs& q, const T* Q, T* tab, int* ok);
+  static bool qtab_update(hipStream_t s, const Grid& g, const CdsArgs& q, const QArgs<T>& a, T* tab);
+  static void qtab_write_bands(hipStream_t s, long long N, const CdsArgs& q, const T* tab, T* Q);
   static void sum_uv(hipStream_t s, long long N, const T* u, const T* v, T* w);
   // caller-supplied sparse operator: s = A x (CSR view), out (+)= A'(rho y + l), partial sum of (A' dy)^2
   static void csr_spmv(hipStream_t s, long long M, const long long* rowptr, const long long* col, const T* val, const T* x, T* out);
