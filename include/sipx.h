@@ -68,7 +68,17 @@ enum {
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
 enum { SIPX_MODE_WHOLE = 0, SIPX_MODE_FIBER = 1, SIPX_MODE_SLICE = 2 };
-enum { SIPX_TRANSFORM_NONE = 0, SIPX_TRANSFORM_DCT = 1 };
+/* SIPX_TRANSFORM_WAVELET: TD_OP = "wavelet", joDWT(n1, n2, wavelet(WT.db4); L = maxtransformlevels(min(n)))
+ * (src/get_TD_operator.jl:86-88; the reference has no 3-D wavelet, get_TD_operator.jl:53-54 -- here the same transform on all three
+ * dimensions).  Orthonormal, periodic, separable, multilevel, db4 (8 taps), lo = the db4 decomposition low-pass (sum sqrt(2)),
+ * hi[j] = (-1)^(j+1) lo[7-j].  One level along an axis of length m:
+ *     a[k] = sum_j lo[j] x[(2k + 4 - j) mod m],   d[k] = sum_j hi[j] x[(2k + 4 - j) mod m],   k = 0 .. m/2-1,
+ * a to positions [0, m/2), d to [m/2, m) of that axis.  L = the largest integer with 2^L dividing min(n) (over all dimensions of
+ * the grid); level l transforms every axis of the box n / 2^(l-1), in place (Mallat layout: pywt.coeffs_to_array of
+ * pywt.wavedecn(x, "db4", mode="periodization")).  L = 0: the identity.  A grid with a dimension not divisible by 2^L is
+ * refused.  CAVEAT: the subsampling phase of Wavelets.jl (the "+4" above) is not pinned by any reference test; the l2 ball and the
+ * annulus do not depend on it, the l1 ball, cardinality and scalar bounds do (the precedent of the DCT's assumed normalisation). */
+enum { SIPX_TRANSFORM_NONE = 0, SIPX_TRANSFORM_DCT = 1, SIPX_TRANSFORM_WAVELET = 2 };
 
 typedef struct {
   int32_t op;        /* SIPX_OP_*   */
@@ -96,7 +106,8 @@ typedef struct {
   int32_t transform; /* SIPX_TRANSFORM_*: an orthogonal transform folded into the projector, x -> A' P(A x) with TD_OP = I
                         (src/get_projector.jl: the branches `constraint.TD_OP in special_operator_list`,
                         src/setup_constraints.jl:54,76-80).  DCT = orthonormal DCT-II along every grid dimension; proj must be
-                        BOUNDS, BOUNDS_VEC, L1 or CARDINALITY (mode WHOLE), op the identity.  The DFT has its own kinds above. */
+                        BOUNDS, BOUNDS_VEC, L1 or CARDINALITY (mode WHOLE), op the identity.  WAVELET = the db4 transform above;
+                        proj must be BOUNDS (scalar), L1 or CARDINALITY (mode WHOLE), op the identity.  The DFT has its own kinds above. */
   int32_t pad_;
 } sipx_set_desc;
 
@@ -216,6 +227,10 @@ int sipx_project(sipx_ctx* ctx, const sipx_set_desc* desc, void* v, int64_t len)
  * out[k] = in[round(1 + (k-1)(nc-1)/(nf-1))] per axis (Interpolations.BSpline(Constant()) evaluated on
  * range(1, stop=nc, length=nf); src/PARSDMM_multi_level.jl:41-45,61-65, src/interpolate_y_l.jl:32-88) */
 int sipx_resample_nn(int dtype, int ndim, const int64_t* nc, const int64_t* nf, const void* in, void* out, int device);
+/* the wavelet transform of SIPX_TRANSFORM_WAVELET on its own, out = W in (inverse = 0) or W' in (inverse != 0), on host arrays of the
+ * grid n (ndim = 2 or 3, column-major), through the kernels of the projector -- W x sets a radius (the reference's constraint
+ * learning, src/constraint_learning_by_observation.jl:68,114) */
+int sipx_dwt(int dtype, int ndim, const int64_t* n, int inverse, const void* in, void* out, int device);
 /* Q as assembled / updated (N x d column-major) and its offsets */
 int sipx_get_Q(sipx_ctx* ctx, void* Q, int64_t* offsets, int* d);
 /* device-side timing of the dominant kernel: runs cds_spmv on Q `reps` times, returns avg ms (HIP events on the engine stream) */

@@ -85,8 +85,14 @@ function projector_fields(c, TF)
         st == "bounds" && vecb && return (12, 0.0, 0.0, nothing, convert(Vector{TF}, c.max), Int32(0))   # SIPX_PROJ_BOUNDS_DFT (mask)
         st in ("l2", "annulus") && return (st == "l2" ? 3 : 4, st == "annulus" ? Float64(c.min) : 0.0, Float64(c.max), nothing, nothing, Int32(0))
         error("of the DFT-domain sets libsipx builds the l1 ball, masking bounds, the l2 ball and the annulus")
+    elseif op == "wavelet"                           # x -> W' P(W x), periodic db4 (SIPX_TRANSFORM_WAVELET = 2)
+        st in ("l2", "annulus") && return (st == "l2" ? 3 : 4, st == "annulus" ? Float64(c.min) : 0.0, Float64(c.max), nothing, nothing, Int32(0))
+        st == "l1" && return (2, 0.0, Float64(c.max), nothing, nothing, Int32(2))
+        st == "cardinality" && return (5, 0.0, Float64(c.max), nothing, nothing, Int32(2))
+        st == "bounds" && !vecb && return (0, Float64(c.min), Float64(c.max), nothing, nothing, Int32(2))
+        error("set type $st behind the wavelet transform is not built in libsipx")
     elseif op in SPECIAL
-        error("operator $op is outside libsipx (JOLI wavelet / curvelet transforms)")
+        error("operator $op is outside libsipx (JOLI curvelet transform)")
     end
     st == "bounds"      && !vecb && return (0, Float64(c.min), Float64(c.max), nothing, nothing, Int32(0))
     st == "bounds"      && return (1, 0.0, 0.0, convert(Vector{TF}, c.min), convert(Vector{TF}, c.max), Int32(0))

@@ -5,6 +5,7 @@
 #include "comm.h"
 #include "dist_dft.h"
 #include "ext_proj.h"
+#include "dwt.h"
 
 #include <algorithm>
 #include <chrono>
@@ -3630,6 +3631,17 @@ class Engine : public EngineBase {
       ext(EXT_DCT);
       s.spec.inner = d->proj;
       return;
+    } else if (d->transform == SIPX_TRANSFORM_WAVELET) {      // x -> W' P(W x): P acts on the db4 wavelet coefficients (kernels_dwt.hip)
+      if (d->op != SIPX_OP_IDENTITY || mode != SIPX_MODE_WHOLE)
+        throw std::runtime_error("sets behind the wavelet transform act in their own domain: TD_OP must be the identity, mode matrix/tensor");
+      if (d->proj != SIPX_PROJ_BOUNDS && d->proj != SIPX_PROJ_L1 && d->proj != SIPX_PROJ_CARDINALITY)
+        throw std::runtime_error("behind the wavelet transform: scalar bounds, the l1 ball and cardinality are built (l2 / annulus commute "
+                                 "with it; per-element bounds would depend on the coefficient layout)");
+      if (d->proj == SIPX_PROJ_L1 && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+      dwt_check_grid(ndim_, G_.n);
+      ext(EXT_DWT);
+      s.spec.inner = d->proj;
+      return;
     } else if (d->transform != SIPX_TRANSFORM_NONE) {
       throw std::runtime_error("unknown transform");
     }
@@ -4497,6 +4509,33 @@ void resample_nn_host(int dtype, int ndim, const int64_t* nc, const int64_t* nf,
   SIPX_HIP(hipSetDevice(device));
   if (dtype == SIPX_F32) resample_T<float>(ndim, nc, nf, in, out);
   else if (dtype == SIPX_F64) resample_T<double>(ndim, nc, nf, in, out);
+  else throw std::runtime_error("dtype must be SIPX_F32 or SIPX_F64");
+}
+
+template <typename T>
+static void dwt_T(int ndim, const long long* n, int inverse, const void* in, void* out) {
+  const long long N = n[0] * n[1] * n[2];
+  T* di = dalloc<T>(N, false);
+  T* dout = dalloc<T>(N, false);
+  T* ds = dalloc<T>(N, false);
+  SIPX_HIP(hipMemcpy(di, in, N * sizeof(T), hipMemcpyHostToDevice));
+  if (inverse) dwt_inverse<T>(nullptr, ndim, n, di, dout, ds);
+  else dwt_forward<T>(nullptr, ndim, n, di, dout, ds);
+  SIPX_HIP(hipDeviceSynchronize());
+  SIPX_HIP(hipMemcpy(out, dout, N * sizeof(T), hipMemcpyDeviceToHost));
+  dfree(di); dfree(dout); dfree(ds);
+}
+void dwt_host(int dtype, int ndim, const int64_t* n, int inverse, const void* in, void* out, int device) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+    throw std::runtime_error("libsipx: no HIP device visible -- this engine has no CPU fallback");
+  if (ndim != 2 && ndim != 3) throw std::runtime_error("wavelet transform: ndim must be 2 or 3");
+  long long nn[3] = {1, 1, 1};
+  for (int q = 0; q < ndim; ++q) nn[q] = n[q];
+  dwt_check_grid(ndim, nn);
+  SIPX_HIP(hipSetDevice(device));
+  if (dtype == SIPX_F32) dwt_T<float>(ndim, nn, inverse, in, out);
+  else if (dtype == SIPX_F64) dwt_T<double>(ndim, nn, inverse, in, out);
   else throw std::runtime_error("dtype must be SIPX_F32 or SIPX_F64");
 }
 

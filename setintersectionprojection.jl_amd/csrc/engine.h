@@ -58,6 +58,7 @@ struct EngineBase {
 
 EngineBase* make_engine(int dtype, int ndim, const int64_t* n, const double* h, int device);
 void resample_nn_host(int dtype, int ndim, const int64_t* nc, const int64_t* nf, const void* in, void* out, int device);
+void dwt_host(int dtype, int ndim, const int64_t* n, int inverse, const void* in, void* out, int device);
 void prox_l2s_host(int dtype, int64_t n, void* x, double rho, const void* m, int device);
 void cds_spmv_host(int dtype, int64_t N, int d, const void* R, const int64_t* off, const void* x, void* y, int device);
 

@@ -31,6 +31,7 @@
 
 #include "../../include/sipx.h"
 #include "ext_proj.h"
+#include "dwt.h"
 #include "sipx_device.h"
 
 namespace sipx {
@@ -1431,6 +1432,19 @@ ExtProj<T>::ExtProj(const ExtSpec& spec, hipStream_t stream) {
       SIPX_HIP(hipMemcpy(I.dlb, spec.lb, sizeof(T) * N, hipMemcpyHostToDevice));
       SIPX_HIP(hipMemcpy(I.dub, spec.ub, sizeof(T) * N, hipMemcpyHostToDevice));
     }
+  } else if (kind == EXT_DWT) {
+    // db4 wavelet transform (kernels_dwt.hip): the coefficients in W1, W2 the transform's scratch, inner projector state
+    dwt_check_grid(spec.ndim, G.n);
+    I.W1 = I.template alloc<T>(N);
+    I.W2 = I.template alloc<T>(N);
+    const int in = spec.inner;
+    if (in == SIPX_PROJ_L1 || in == SIPX_PROJ_CARDINALITY) {
+      I.ps = I.template alloc<ProjScalars<T>>(1);
+      I.psf = I.template alloc<ProjScalars<T>>(1);
+      if (in == SIPX_PROJ_CARDINALITY) I.cidx = I.template alloc<long long>(N);
+      K<T>::ps_init(stream, I.ps, I.cidx);
+      K<T>::ps_init(stream, I.psf, I.cidx);
+    }
   } else if (kind == EXT_CARD_SEG) {
     if (spec.mode != SIPX_MODE_FIBER && spec.mode != SIPX_MODE_SLICE)
       throw std::runtime_error("segmented cardinality needs a fiber or slice mode");
@@ -2660,6 +2674,20 @@ void ExtProj<T>::project(T* v, bool feas, double* partials, T* maxpart, T* compa
     // C'C = I: inside the l1 ball the round trip only adds rounding noise -- v is kept bit for bit there (as for the DFT)
     hipLaunchKernelGGL((k_copy_if_needed<T>), dim3(NB), dim3(BLOCK), 0, s, N, oth, v,
                        in == SIPX_PROJ_L1 ? (const ProjScalars<T>*)ps : (const ProjScalars<T>*)nullptr);
+  } else if (kind == EXT_DWT) {
+    const Grid& G = I.sp.G;
+    dwt_forward<T>(s, I.sp.ndim, G.n, v, I.W1, I.W2);
+    // the inner projector on the coefficient array, as for the DCT
+    const int in = I.sp.inner;
+    const bool two = in == SIPX_PROJ_L1 || in == SIPX_PROJ_CARDINALITY;
+    ProjScalars<T>* ps = two ? (feas ? I.psf : I.ps) : nullptr;
+    Grid g1;
+    g1.n[0] = N; g1.n[1] = 1; g1.n[2] = 1; g1.N = N; g1.st[0] = 1; g1.st[1] = N; g1.st[2] = N;
+    if (two) K<T>::proj_scalars_arr(s, N, I.W1, in, (T)I.sp.pmin, (T)I.sp.pmax, ps, partials, maxpart, compact, N);
+    proj_apply_grid<T>(s, g1, 0, nullptr, N, I.W1, in, (T)I.sp.pmin, (T)I.sp.pmax, nullptr, nullptr, ps);
+    // W'W = I: inside the l1 ball every launch of the inverse returns at once and v keeps its bits (as for the DFT / DCT);
+    // otherwise its last launch writes v
+    dwt_inverse<T>(s, I.sp.ndim, G.n, I.W1, v, I.W2, in == SIPX_PROJ_L1 ? (const ProjScalars<T>*)ps : (const ProjScalars<T>*)nullptr);
   } else if (kind == EXT_CARD_SEG) {
     const long long nb = I.map.nseg < (long long)NB * 4 ? I.map.nseg : (long long)NB * 4;
     hipLaunchKernelGGL((k_seg_card<T>), dim3((unsigned)nb), dim3(BLOCK), 0, s, I.map, v, (long long)I.sp.pmax);

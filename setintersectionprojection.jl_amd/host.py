@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = [
     "sipx_stream",
     "sipx_dev_rhs", "sipx_dev_x", "sipx_set_owned", "sipx_get_rhs", "sipx_prox_l2s",
     "sipx_rccl_unique_id", "sipx_set_comm_rccl", "sipx_set_comm", "sipx_slab", "sipx_warm_start_from", "sipx_set_decomp",
-    "sipx_kernel_stats_json", "sipx_comm_info", "sipx_device_bytes", "sipx_reset",
+    "sipx_kernel_stats_json", "sipx_comm_info", "sipx_device_bytes", "sipx_reset", "sipx_dwt",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
@@ -42,7 +42,7 @@ OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4,
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12}
 MODES = {"matrix": 0, "tensor": 0, "fiber": 1, "slice": 2}
-TRANSFORMS = {"DCT": 1}
+TRANSFORMS = {"DCT": 1, "wavelet": 2}
 SPECIAL_OPERATORS = ("DFT", "DCT", "wavelet", "curvelet")     # src/setup_constraints.jl:54
 YL_FEAS, YL_BB, YL_FIRST = 1, 2, 4
 Q_MODES = {"cds": 0, "stencil": 1}
@@ -342,6 +342,25 @@ class Projector:
                 raise SipxError(f"set type {st!r} behind the DCT is not built")
             if self.mode:
                 raise SipxError("sets behind the DCT apply to the whole array (matrix / tensor mode)")
+        elif constraint.TD_OP == "wavelet":
+            # x -> W' P(W x) with the orthonormal periodic db4 transform (sipx.h, SIPX_TRANSFORM_WAVELET); the l2 ball and the
+            # annulus commute with it and are applied to x itself
+            if st in ("l2", "annulus"):
+                self.kind, self.pmax = st, float(constraint.max)
+                self.pmin = float(constraint.min) if st == "annulus" else 0.0
+            elif st == "l1":
+                self.kind, self.pmax, self.transform = st, float(constraint.max), TRANSFORMS["wavelet"]
+            elif st == "cardinality":
+                self.kind, self.pmax, self.transform = st, float(int(constraint.max)), TRANSFORMS["wavelet"]
+            elif st == "bounds" and np.ndim(constraint.min) == 0:
+                self.kind, self.pmin, self.pmax, self.transform = "bounds", float(constraint.min), float(constraint.max), TRANSFORMS["wavelet"]
+            else:
+                raise SipxError(f"set type {st!r} behind the wavelet transform is not built: scalar bounds, l1, cardinality, "
+                                "l2 and annulus are")
+            if self.mode:
+                raise SipxError("sets behind the wavelet transform apply to the whole array (matrix / tensor mode)")
+            if self.transform:
+                _dwt_check_grid(n)
         elif constraint.TD_OP in SPECIAL_OPERATORS:
             if constraint.TD_OP == "DFT" and st == "l1":
                 self.kind, self.pmax = "l1_dft", float(constraint.max)
@@ -447,7 +466,7 @@ class Projector:
 def get_TD_operator(comp_grid, TD_type: str, TF):
     """src/get_TD_operator.jl:12-95 for the banded operators."""
     n, _ = _grid(comp_grid)
-    if TD_type in ("DFT", "DCT"):   # src/get_TD_operator.jl:45-51,80-86; setup_constraints.jl:76-80 swaps in the identity
+    if TD_type in ("DFT", "DCT", "wavelet"):   # src/get_TD_operator.jl:45-51,80-88; setup_constraints.jl:76-80 swaps in the identity
         return TDOperator("identity", comp_grid, TF), True, True, n, False
     if TD_type == "D_xz":      # src/get_TD_operator.jl:66-70 (2-D only): TD_OP = D_z * D_x, shipped as a sparse matrix
         if len(n) != 2:
@@ -1056,6 +1075,41 @@ def resample_nn(a, nc, nf, device=None):
     out = np.empty(int(np.prod(nf)), TF)
     _chk(lib().sipx_resample_nn(_dtype_code(TF), len(nc), (C.c_int64 * len(nc))(*nc), (C.c_int64 * len(nf))(*nf),
                                 _ptr(a), _ptr(out), device))
+    return out
+
+
+def _dwt_check_grid(n):
+    """The grids the wavelet transform takes: 2-D or 3-D, every dimension divisible by 2^L, L = maxtransformlevels(min(n))."""
+    n = tuple(int(v) for v in n)
+    if len(n) not in (2, 3):
+        raise SipxError("wavelet transform: 2-D and 3-D grids only")
+    m, L = min(n), 0
+    while m > 0 and m % 2 == 0:
+        m //= 2
+        L += 1
+    for a, v in enumerate(n):
+        if v % (1 << L):
+            raise SipxError(f"wavelet transform: the grid {' x '.join(map(str, n))} has {L} levels (2^L divides the smallest "
+                            f"dimension) but dimension {a + 1} is not divisible by 2^{L}")
+    return L
+
+
+def dwt(x, n, inverse=False, device=None):
+    """W x (or W' x with inverse=True): the orthonormal periodic multilevel db4 transform behind TD_OP = "wavelet"
+    (sipx.h, SIPX_TRANSFORM_WAVELET) of the column-major grid n, on the device.  ||W x||_1 sets the radius of an l1 ball
+    behind it (src/constraint_learning_by_observation.jl:68,114)."""
+    device = _default_device if device is None else device
+    x = np.ascontiguousarray(x)
+    TF = x.dtype.type
+    n = [int(v) for v in n]
+    if len(n) == 3 and n[2] == 1:
+        n = n[:2]
+    _dwt_check_grid(n)
+    if x.size != int(np.prod(n)):
+        raise SipxError("dwt: array size does not match the grid")
+    x = x.reshape(-1)
+    out = np.empty(x.size, TF)
+    _chk(lib().sipx_dwt(_dtype_code(TF), len(n), (C.c_int64 * len(n))(*n), int(bool(inverse)), _ptr(x), _ptr(out), device))
     return out
 
 
