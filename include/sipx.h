@@ -231,6 +231,39 @@ int sipx_resample_nn(int dtype, int ndim, const int64_t* nc, const int64_t* nf, 
  * grid n (ndim = 2 or 3, column-major), through the kernels of the projector -- W x sets a radius (the reference's constraint
  * learning, src/constraint_learning_by_observation.jl:68,114) */
 int sipx_dwt(int dtype, int ndim, const int64_t* n, int inverse, const void* in, void* out, int device);
+
+/* Constraint learning (src/constraint_learning_by_observation.jl:8-163, constraint_learning_by_obseration): statistics of
+ * n_train training images on the 2-D grid n (n1, n2 >= 2) with spacings h.  Image i is m_train[i*s0 + a*s1 + b*s2] at grid
+ * point (a, b), strides in elements (s0 = image, s1 = dim 1, s2 = dim 2); the layout must be dense with the image index
+ * slowest (C-like blocks per image) or fastest (Julia's m_train[i,:,:]).  N = n1 n2, M = (n1-1) n2 + n1 (n2-1), D_x / D_z
+ * are the forward differences along dim 1 / dim 2 with entries -+fl(1/h) in TF (the TDOperator's bits), TV = [D_z; D_x], F
+ * the unitary 2-D DFT, W the transform of sipx_dwt, sigma the singular values in descending order.  TF is the dtype, TI is
+ * int32 for SIPX_F32 and int64 for SIPX_F64.  Each field is a caller-owned host array, NULL = not wanted (that work is not
+ * done).  Per image (n_train entries):
+ *   nuclear_norm, nuclear_Dx, nuclear_Dz  TF  sum sigma of the image, of D_x img as (n1-1) x n2, of D_z img as n1 x (n2-1)
+ *   rank_095                              TI  first 1-based k with cumsum(sigma)[k] / sum(sigma) > 0.95 (0 if sigma = 0)
+ *   TV, Dx_l1, Dz_l1                      TF  ||TV img||_1, ||D_x img||_1, ||D_z img||_1
+ *   wavelet_l1                            TF  ||W img||_1 if n1 == n2, else 0
+ *   DFT_l1                                TF  ||F img||_1 over all N coefficients
+ *   DFT_card_095, TV_card_095             TI  len(c) - k, k the first 1-based index with cumsum(sort(|c|))/sum > 0.05, c = F img
+ *                                             or TV img (0 if c = 0)
+ *   annulus, TV_annulus, D_l2             TF  ||img||_2, ||TV img||_2, ||TV img||_2
+ *   D_x_min, D_x_max, D_z_min, D_z_max    TF  extrema of D_x img and D_z img
+ * Across images (element-wise over the batch, the reference's starting values included):
+ *   hist_min (N), hist_TV_min (M)         float64  min(1e8, sort(img)), min(1e8, sort(TV img))
+ *   hist_max (N), hist_TV_max (M)         TF       max(0, sort(img)), max(0, sort(TV img))
+ *   DCT_x_LB (n1), DCT_y_LB (n2)          float64  min(1e8, orthonormal DCT-II along dim 1 / dim 2, over the other dim)
+ *   DCT_x_UB (n1), DCT_y_UB (n2)          TF       max(0, the same)
+ * Sums run in float64 and round to TF once.  The images go through in chunks of max_batch (0 = sized from free device
+ * memory); the results are bit-identical for every chunking. */
+typedef struct {
+  void* nuclear_norm; void* nuclear_Dx; void* nuclear_Dz; void* rank_095; void* TV; void* wavelet_l1; void* Dx_l1;
+  void* Dz_l1; void* DFT_l1; void* DFT_card_095; void* TV_card_095; void* annulus; void* TV_annulus; void* D_l2;
+  void* D_x_min; void* D_x_max; void* D_z_min; void* D_z_max; void* DCT_x_LB; void* DCT_x_UB; void* DCT_y_LB;
+  void* DCT_y_UB; void* hist_min; void* hist_max; void* hist_TV_min; void* hist_TV_max;
+} sipx_observations;
+int sipx_learn_observations(int dtype, const int64_t* n, const double* h, int64_t n_train, const void* m_train,
+                            const int64_t* strides, int64_t max_batch, sipx_observations* out, int device);
 /* Q as assembled / updated (N x d column-major) and its offsets */
 int sipx_get_Q(sipx_ctx* ctx, void* Q, int64_t* offsets, int* d);
 /* device-side timing of the dominant kernel: runs cds_spmv on Q `reps` times, returns avg ms (HIP events on the engine stream) */

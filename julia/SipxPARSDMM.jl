@@ -24,7 +24,7 @@ using SparseArrays
 using TimerOutputs
 import SetIntersectionProjection: log_type_PARSDMM, convert_options!
 
-export PARSDMM, release_contexts
+export PARSDMM, release_contexts, constraint_learning_by_obseration
 
 const libsipx = get(ENV, "SIPX_LIBRARY", "libsipx.so")
 
@@ -366,5 +366,32 @@ end
 #   :213-226 feasibility doubling, clamp  unchanged Julia
 #   :230-243 Q_update! + prox rebind  ->  ccall((:sipx_q_update, libsipx), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx[], rho64, Float64.(log_PARSDMM.rho[i,:]))
 # tests/c_abi/phases.c runs exactly this sequence from C and checks it against sipx_parsdmm bit for bit.
+
+# ---- constraint learning (src/constraint_learning_by_observation.jl:8-163) on the device ---------------------------------
+const LEARN_KEYS = ("nuclear_norm", "nuclear_Dx", "nuclear_Dz", "rank_095", "TV", "wavelet_l1", "Dx_l1", "Dz_l1", "DFT_l1",
+                    "DFT_card_095", "TV_card_095", "annulus", "TV_annulus", "D_l2", "D_x_min", "D_x_max", "D_z_min", "D_z_max",
+                    "DCT_x_LB", "DCT_x_UB", "DCT_y_LB", "DCT_y_UB", "hist_min", "hist_max", "hist_TV_min", "hist_TV_max")
+
+"""The reference's dictionary for m_train[i,:,:] on a 2-D grid (sipx_learn_observations): Julia's own strides are passed, the
+*_min / *_LB arrays are Float64 (as the reference's `zeros(TF,n) .+ 1e8` makes them), counts are Int32 (Float32) or Int64."""
+function constraint_learning_by_obseration(comp_grid, m_train::Array{TF}; max_batch::Integer=0, device::Integer=0) where {TF<:Union{Float32,Float64}}
+    m = ndims(m_train) == 2 ? reshape(m_train, 1, size(m_train)...) : m_train
+    ndims(m) == 3 || error("constraint learning: m_train must be n_train x n1 x n2")
+    (nt, n1, n2) = size(m)
+    TI = TF == Float64 ? Int64 : Int32
+    N, M = n1 * n2, (n1 - 1) * n2 + n1 * (n2 - 1)
+    len = Dict("DCT_x_LB" => n1, "DCT_x_UB" => n1, "DCT_y_LB" => n2, "DCT_y_UB" => n2, "hist_min" => N, "hist_max" => N,
+               "hist_TV_min" => M, "hist_TV_max" => M)
+    typ(k) = k in ("rank_095", "DFT_card_095", "TV_card_095") ? TI : (k in ("DCT_x_LB", "DCT_y_LB", "hist_min", "hist_TV_min") ? Float64 : TF)
+    out = Dict{String,Any}(k => zeros(typ(k), get(len, k, nt)) for k in LEARN_KEYS)
+    ptrs = Ptr{Cvoid}[pointer(out[k]) for k in LEARN_KEYS]
+    n = Int64[n1, n2]
+    h = Float64[comp_grid.d[1], comp_grid.d[2]]
+    st = Int64[strides(m)...]
+    GC.@preserve out ptrs m check(ccall((:sipx_learn_observations, libsipx), Cint,
+        (Cint, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Ptr{Cvoid}}, Cint),
+        TF == Float64 ? 1 : 0, n, h, nt, m, st, max_batch, ptrs, device))
+    return out
+end
 
 end # module

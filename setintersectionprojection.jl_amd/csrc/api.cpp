@@ -4,6 +4,7 @@
 
 #include "comm.h"
 #include "engine.h"
+#include "learn.h"
 
 struct sipx_ctx {
   sipx::EngineBase* e;
@@ -104,6 +105,10 @@ int sipx_resample_nn(int dtype, int ndim, const int64_t* nc, const int64_t* nf, 
 }
 int sipx_dwt(int dtype, int ndim, const int64_t* n, int inverse, const void* in, void* out, int device) {
   SIPX_TRY(sipx::dwt_host(dtype, ndim, n, inverse, in, out, device))
+}
+int sipx_learn_observations(int dtype, const int64_t* n, const double* h, int64_t n_train, const void* m_train,
+                            const int64_t* strides, int64_t max_batch, sipx_observations* out, int device) {
+  SIPX_TRY(sipx::learn_observations_host(dtype, n, h, n_train, m_train, strides, max_batch, out, device))
 }
 int sipx_apply_op(sipx_ctx* c, int op, const void* x, void* s) { SIPX_TRY(c->e->apply_op(op, x, s, false)) }
 int sipx_apply_op_adj(sipx_ctx* c, int op, const void* v, void* t) { SIPX_TRY(c->e->apply_op(op, v, t, true)) }

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "sipx_dev_rhs", "sipx_dev_x", "sipx_set_owned", "sipx_get_rhs", "sipx_prox_l2s",
     "sipx_rccl_unique_id", "sipx_set_comm_rccl", "sipx_set_comm", "sipx_slab", "sipx_warm_start_from", "sipx_set_decomp",
     "sipx_kernel_stats_json", "sipx_comm_info", "sipx_device_bytes", "sipx_reset", "sipx_dwt",
+    "sipx_learn_observations",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
@@ -1111,6 +1112,73 @@ def dwt(x, n, inverse=False, device=None):
     out = np.empty(x.size, TF)
     _chk(lib().sipx_dwt(_dtype_code(TF), len(n), (C.c_int64 * len(n))(*n), int(bool(inverse)), _ptr(x), _ptr(out), device))
     return out
+
+
+# keys of the reference's dictionary (src/constraint_learning_by_observation.jl:27-58), in its order and in sipx_observations'
+LEARN_KEYS = ("nuclear_norm", "nuclear_Dx", "nuclear_Dz", "rank_095", "TV", "wavelet_l1", "Dx_l1", "Dz_l1", "DFT_l1", "DFT_card_095",
+              "TV_card_095", "annulus", "TV_annulus", "D_l2", "D_x_min", "D_x_max", "D_z_min", "D_z_max", "DCT_x_LB", "DCT_x_UB",
+              "DCT_y_LB", "DCT_y_UB", "hist_min", "hist_max", "hist_TV_min", "hist_TV_max")
+
+
+class _Observations(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in LEARN_KEYS]
+
+
+def _learn_layout(n, TF, n_train):
+    """Length and dtype of every key (sipx.h, sipx_observations)."""
+    n1, n2 = n
+    N, M = n1 * n2, (n1 - 1) * n2 + n1 * (n2 - 1)
+    TI = np.int32 if TF == np.float32 else np.int64
+    lay = {k: (n_train, TF) for k in LEARN_KEYS}
+    lay.update({k: (n_train, TI) for k in ("rank_095", "DFT_card_095", "TV_card_095")})
+    lay.update({"hist_min": (N, np.float64), "hist_max": (N, TF), "hist_TV_min": (M, np.float64), "hist_TV_max": (M, TF),
+                "DCT_x_LB": (n1, np.float64), "DCT_x_UB": (n1, TF), "DCT_y_LB": (n2, np.float64), "DCT_y_UB": (n2, TF)})
+    return lay
+
+
+def constraint_learning_by_obseration(comp_grid, m_train, keys=None, max_batch=0, device=None):
+    """src/constraint_learning_by_observation.jl:8-163 (the reference's spelling; constraint_learning_by_observation is an
+    alias): a dict of statistics of the training images m_train[i, :, :] on the 2-D grid, computed on the device.
+
+    m_train is (n_train, n1, n2) in C or Fortran order (numpy strides are passed through), or one (n1, n2) image.  keys selects
+    what is computed (default: every key of the reference); a key not asked for costs nothing.  max_batch bounds the images per
+    device chunk (0: from free memory); every chunking gives the same bits.  Dtypes and lengths: include/sipx.h.  As in the
+    reference, the *_min / *_LB arrays start at 1e8 and are float64 (Julia promotes zeros(TF, n) .+ 1e8), the *_max / *_UB
+    arrays start at 0 in TF.  Unlike the reference, a count whose magnitudes are all zero is 0 (Julia throws), the cumulative
+    sums run in float64, and wavelet_l1 is 0 unless n1 == n2."""
+    n = tuple(int(v) for v in comp_grid.n)
+    if len(n) == 3 and n[2] == 1:
+        n = n[:2]
+    if len(n) != 2:
+        raise SipxError("constraint learning: 2-D grids only")
+    if n[0] < 2 or n[1] < 2:
+        raise SipxError("constraint learning: the grid needs n1 >= 2 and n2 >= 2")
+    h = tuple(float(v) for v in comp_grid.d[:2])
+    m = np.asarray(m_train)
+    if np.iscomplexobj(m) or m.dtype.type not in (np.float32, np.float64):
+        raise SipxError("constraint learning: m_train must be real Float32 or Float64")
+    if m.ndim == 2:
+        m = m[None]
+    if m.ndim != 3 or m.shape[1:] != n or m.shape[0] < 1:
+        raise SipxError(f"constraint learning: m_train of shape {np.shape(m_train)} does not match the grid {n}")
+    wanted = LEARN_KEYS if keys is None else tuple(keys)
+    for k in wanted:
+        if k not in LEARN_KEYS:
+            raise SipxError(f"constraint learning: unknown key {k!r}")
+    if not (m.flags.c_contiguous or m.flags.f_contiguous):
+        m = np.ascontiguousarray(m)
+    TF = m.dtype.type
+    device = _default_device if device is None else device
+    lay = _learn_layout(n, TF, m.shape[0])
+    out = {k: np.empty(lay[k][0], lay[k][1]) for k in LEARN_KEYS if k in wanted}
+    obs = _Observations(**{k: v.ctypes.data for k, v in out.items()})
+    strides = (C.c_int64 * 3)(*[s // m.itemsize for s in m.strides])
+    _chk(lib().sipx_learn_observations(_dtype_code(TF), (C.c_int64 * 2)(*n), (C.c_double * 2)(*h), C.c_int64(m.shape[0]),
+                                       _ptr(m), strides, C.c_int64(int(max_batch)), C.byref(obs), int(device)))
+    return out
+
+
+constraint_learning_by_observation = constraint_learning_by_obseration
 
 
 def CDS_MVp(N, ndiags, R, offset, x, y):
