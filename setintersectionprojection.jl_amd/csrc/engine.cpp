@@ -437,7 +437,7 @@ class Engine : public EngineBase {
     if (loose_owned_) { dfree(loose_v_); dfree(loose_w_); }
     (void)hipStreamSynchronize(stream_);
     for (auto& s : sets_) free_set(s);
-    for (void* p : {(void*)xr_base_[0], (void*)xr_base_[1], (void*)xr_base_[2], (void*)w_base_, (void*)rhs_, (void*)m_base_, (void*)r_base_, (void*)p_base_, (void*)p2_base_, (void*)Ap_, (void*)Q_, (void*)Q2_, (void*)qtab_,
+    for (void* p : {(void*)xr_base_[0], (void*)xr_base_[1], (void*)xr_base_[2], (void*)w_base_, (void*)rhs_, (void*)m_base_, (void*)r_base_, (void*)p_base_, (void*)p2_base_, (void*)Ap_, (void*)Q_, (void*)qtab_,
                     (void*)scr_v_, (void*)scr_c_, (void*)scr_i_, (void*)scr_w_, (void*)part_cg_, (void*)part_tmp_, (void*)part_sets_,
                     (void*)maxpart_, (void*)cg_dev_, (void*)gbuf_, (void*)stage_, (void*)sstage_, (void*)fbuf_, (void*)agree_buf_})
       dfree(p);
@@ -747,7 +747,6 @@ class Engine : public EngineBase {
       const char* mu = std::getenv("SIPX_YL_MULTI");            // 0: one k_yl launch per set on every iteration (A/B switch, tests)
       yl_multi_ = !(mu && mu[0] == '0');
       if (const char* ra = std::getenv("SIPX_RESID_AHEAD")) resid_ahead_ = ra[0] != '0';      // A/B switch
-      if (const char* qf = std::getenv("SIPX_Q_FUSED")) q_fused_ = qf[0] != '0';               // A/B switch
       // the lean first passes of the l1 searches in one sweep: pays where the re-reads of x are real traffic (512^3, settled
       // iterations: 133 -> 139 it/s); at 256^3 three concurrent per-set passes on their own streams are as fast or faster
       // (1028 against 1012 it/s settled, default window equal), so it is the default above 2^24 grid points only
@@ -1034,7 +1033,6 @@ class Engine : public EngineBase {
     }
 
     assemble_Q();
-    if (q_fused_ && !stencil_q_ && !comm_ && cds_.march != 0) Q2_ = dalloc<T>((size_t)Nx_ * cds_.d);     // (SIPX_Q_FUSED=1 only)
     build_q_table();
     {
       // The lane: one rank, a list the sweep takes in part (C4) -- the slice-rank / nuclear-norm set, a chain of batched GEMMs and
@@ -1123,7 +1121,7 @@ class Engine : public EngineBase {
     // ---- arrays
     for (int k = 0; k < 3; ++k) dzero(xr_base_[k], stream_);
     dzero(p_base_, stream_); dzero(rhs_, stream_); dzero(r_base_, stream_); dzero(Ap_, stream_);
-    dzero(p2_base_, stream_); dzero(w_base_, stream_); dzero(Q2_, stream_);
+    dzero(p2_base_, stream_); dzero(w_base_, stream_);
     dzero(part_cg_, stream_); dzero(part_tmp_, stream_); dzero(part_sets_, stream_); dzero(maxpart_, stream_);
     dzero(cg_dev_, stream_); dzero(sums_ticket_, stream_);
     dzero(fbuf_, stream_); dzero(stage_, stream_); dzero(sstage_, stream_); dzero(gbuf_, stream_);
@@ -1172,7 +1170,7 @@ class Engine : public EngineBase {
     spec_searches_ = spec_fallbacks_ = spec_rounds_ = 0;
     batch_searches_ = batch_fallbacks_ = 0;
     head_done_ = false; rs_pending_ = false; sums_pending_ = false; defer_sums_ = false; merge_sums_ = false; merged_nslots_ = 0;
-    q_pending_ = false; q_defer_ = false; rhs_fused_ = false; fuse_rhs_ = false; have_log_sums_ = false;
+    rhs_fused_ = false; fuse_rhs_ = false; have_log_sums_ = false;
     obj_ss_ = evo_ss_ = xx_ss_ = 0;
     sums_flags_ = 0; word_sums_ = false;
     for (bool& v : open_valid_) v = false;
@@ -1334,18 +1332,9 @@ class Engine : public EngineBase {
     const int dt = dtype_code();
     // the initial residual goes straight into the p buffer (p_1 = r_0, cg.jl:57): the first iteration reads it from there
     // as both r and p and writes r_1 into the r buffer, so the copy p <- r is never made
-    bool done = false;
-    if (q_pending_ && !stencil_q_ && !comm_ && r0 == 0 && r1 == Nx_) {
-      if (!Q2_) throw std::runtime_error("internal: the second copy of Q (SIPX_Q_FUSED) was not allocated at sipx_finalize");
-      done = K<T>::resid_qupdate(stream_, G_, Nx_, Q_, Q2_, cds_, q_pending_args_, x_, rhs_, p_, (T*)nullptr, (T*)nullptr, part_cg_);
-      if (done) { std::swap(Q_, Q2_); q_pending_ = false; }
-    }
-    if (!done) {
-      flush_q_pending();
-      // (x_old is not written: the x-step leaves x_k behind in its own buffer, see the ring of x buffers)
-      if (stencil_q_) K<T>::sq_resid(stream_, G_, sq_, x_, rhs_, p_, (T*)nullptr, (T*)nullptr, part_cg_);
-      else K<T>::resid(stream_, Nx_, r0, r1, Q_, cds_, x_, rhs_, p_, (T*)nullptr, (T*)nullptr, part_cg_);
-    }
+    // (x_old is not written: the x-step leaves x_k behind in its own buffer, see the ring of x buffers)
+    if (stencil_q_) K<T>::sq_resid(stream_, G_, sq_, x_, rhs_, p_, (T*)nullptr, (T*)nullptr, part_cg_);
+    else K<T>::resid(stream_, Nx_, r0, r1, Q_, cds_, x_, rhs_, p_, (T*)nullptr, (T*)nullptr, part_cg_);
     if (comm_) {         // ||r_0||^2, ||rhs||^2 block partials [+ the per-set sums of the y/l update queued just before]; p_1 = r_0 is in p_
       comm_->allreduce_with_halo(part_cg_, (size_t)(2 * NB + merged_nslots_), SIPX_F64, p_ + r0, p_ + r0 - plane_, prev_, p_ + r1 - plane_,
                                  p_ + r1, next_, (size_t)plane_, dt, stream_);
@@ -2772,28 +2761,13 @@ class Engine : public EngineBase {
       mk_q_update(al);
       return;
     }
-    flush_q_pending();
     QArgs<T> a;
     a.nsets = 0;
     for (int i = 0; i < p_n_; ++i) {
       if (rho_new[i] == rho_old[i]) continue;                       // ind_updated, PARSDMM.jl:230
       push_qset(a, sets_[i], (T)rho_new[i] - (T)rho_old[i]);        // Q_update!.jl:47
     }
-    if (q_defer_ && q_fused_ && cds_.march != 0 && !comm_ && a.nsets > 0) {
-      bool generated = true;
-      for (int k = 0; k < a.nsets; ++k) generated &= a.s[k].ata == nullptr;
-      if (generated) {                       // applied by the residual product of the coming x-step
-        q_pending_args_ = a;
-        q_pending_ = true;
-        return;
-      }
-    }
     q_apply(a);
-  }
-  void flush_q_pending() {
-    if (!q_pending_) return;
-    q_pending_ = false;
-    q_apply(q_pending_args_);
   }
   // a batch of the Q update (Q[:, b] += alpha_i A_i'A_i[:, b], set order): on the class table while the products use it -- the
   // bands go stale -- else on the bands
@@ -2826,7 +2800,6 @@ class Engine : public EngineBase {
     const char* why = nullptr;
     if (!env_knobs().q_table) why = "SIPX_Q_TABLE=0";
     else if (stencil_q_) why = "stencil Q";
-    else if (q_fused_) why = "SIPX_Q_FUSED";
     else if (mk_) why = "Minkowski";
     else if (comm_) why = "sharded";
     else if (!cds_.march || !cds_.sym || cds_.d != 7) why = "not the 7-band matrix of a 3-D grid";
@@ -3226,10 +3199,8 @@ class Engine : public EngineBase {
         R.rhs_ready = true;
       }
       if (changed) {
-        q_defer_ = i < maxit;               // (the last iteration's update is applied at once: the context keeps a current Q)
         q_update(rho_new.data(), rho.data());                          // :230-243
-        q_defer_ = false;
-        if (!q_pending_) mark(6);
+        mark(6);
       }
       rho = rho_new;
     }
@@ -3244,7 +3215,6 @@ class Engine : public EngineBase {
       SIPX_HIP(hipStreamWaitEvent(stream_, ev_c_[1], 0));
       rs_pending_ = false;
     }
-    flush_q_pending();
     resolve_timing(log, 0);
     resolve_timing(log, 1);
     log->n_iter = n_iter;
@@ -3349,7 +3319,6 @@ class Engine : public EngineBase {
     if (offsets) for (int b = 0; b < cds_.d; ++b) offsets[b] = cds_.off[b];
     if (Q && stencil_q_) throw std::runtime_error("stencil Q mode stores no bands (use sipx_apply_Q)");
     if (Q && comm_ && comm_->world > 1) throw std::runtime_error("a sharded context maintains its slab of Q only");
-    flush_q_pending();
     if (Q) ensure_q_bands();
     if (Q && cds_.sym) {      // the negative bands are not maintained while solving: rebuild them from their partners
       K<T>::mirror_bands(stream_, Nx_, cds_, Q_);
@@ -3363,7 +3332,6 @@ class Engine : public EngineBase {
     if (comm_ && comm_->world > 1) throw std::runtime_error("a sharded context maintains its slab of Q only");
     SIPX_HIP(hipStreamSynchronize(stream_));
     SIPX_HIP(hipMemcpy(p_, x, Nx_ * sizeof(T), hipMemcpyHostToDevice));
-    flush_q_pending();
     if (stencil_q_) K<T>::sq_spmv(stream_, G_, sq_, p_, Ap_);
     else K<T>::spmv(stream_, G_, Nx_, Q_, cds_, p_, Ap_);
     SIPX_HIP(hipStreamSynchronize(stream_));
@@ -3372,7 +3340,6 @@ class Engine : public EngineBase {
 
   double time_spmv(int reps) override {
     need_final();
-    flush_q_pending();
     hipEvent_t a, b;
     SIPX_HIP(hipEventCreate(&a));
     SIPX_HIP(hipEventCreate(&b));
@@ -3455,16 +3422,15 @@ class Engine : public EngineBase {
     o += std::string(", \"q_table\": {\"on\": ") + (cds_.qtab ? "true" : "false") + ", \"reason\": \"" + qtab_reason_ + "\"}";       // the set updated on a stream of its own (-1: none), lane_start
     o += ", \"batched_searches\": {\"searches\": " + std::to_string(batch_searches_) + ", \"fallbacks\": " + std::to_string(batch_fallbacks_) + "}";
     // slice-rank / matrix-rank sets: which route their projector took since the context was finalised (ext_proj.hip)
-    long long rc[6] = {0, 0, 0, 0, 0, 0};
+    long long rc[4] = {0, 0, 0, 0};
     for (const auto& st : sets_) {
       if (!st.ext || st.ext_kind != EXT_RANK) continue;
-      long long c[6];
+      long long c[4];
       st.ext->route_counts(c);
-      for (int q = 0; q < 6; ++q) rc[q] += c[q];
+      for (int q = 0; q < 4; ++q) rc[q] += c[q];
     }
     o += ", \"rank_route\": {\"calls\": " + std::to_string(rc[0]) + ", \"warm_started_subspace\": " + std::to_string(rc[1]) +
-         ", \"full_decomposition\": " + std::to_string(rc[2]) + ", \"products_with_gram\": " + std::to_string(rc[3]) +
-         ", \"float32_loops\": " + std::to_string(rc[4]) + ", \"float32_gave_up\": " + std::to_string(rc[5]) + "}}";
+         ", \"full_decomposition\": " + std::to_string(rc[2]) + ", \"products_with_gram\": " + std::to_string(rc[3]) + "}}";
     if (!peek) start_stats(enable);
     return o.c_str();
   }
@@ -4396,18 +4362,9 @@ class Engine : public EngineBase {
   double* dres_ = nullptr;                  // device copy of the reduced per-set sums (all-reduce buffer)
   hipEvent_t ev_sums_ = nullptr, ev_cgb_ = nullptr;
   bool sums_pending_ = false, defer_sums_ = false;
-  // SIPX_Q_FUSED=1 (measured, NOT the default): a Q update decided at the end of an iteration of the whole-solve loop is not
-  // applied at once; the residual product that opens the next x-step applies it on the fly (K::resid_qupdate, z-marching matrices
-  // on one rank) into the second copy of Q, and the two copies swap roles; whoever else reads Q first flushes it through
-  // k_q_update.  Bit-identical (tested), 8 N w instead of 12 for update + product -- and slower: regenerating the band values costs
-  // the 512-thread march kernel more than the traffic saves (512^3: 115 -> 109 it/s), and at 256^3 the separate kernels meet
-  // in the Infinity Cache (k_q_update leaves the four bands there: 46 us for 8 N w; 774 -> 732 it/s).
-  bool q_fused_ = false, q_pending_ = false, q_defer_ = false;
   T* qtab_ = nullptr;                   // class table of Q + the check's flag (build_q_table)
   bool q_stale_ = false;                // the stored bands lag the table (ensure_q_bands)
   std::string qtab_reason_ = "not built";   // why the products use the bands ("": they use the table)
-  QArgs<T> q_pending_args_;
-  T* Q2_ = nullptr;
   long long dev_bytes_ = 0;           // device bytes this context allocated (dalloc + the library-backed projectors' own buffers)
   bool slab_dist_logs_ = false;       // slab-decomposed and a distance term among the sets: obj / evol_x sums come from its y/l update
   bool lean_multi_ = false;           // k_lean_multi for the lean first passes of the l1 searches (finalize: above 2^24 grid points; SIPX_LEAN_MULTI=0/1)

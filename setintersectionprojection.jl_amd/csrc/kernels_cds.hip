@@ -184,10 +184,7 @@ __device__ __forceinline__ T ata_value(const Grid& G, int nblk, const int* dir, 
   return val;
 }
 
-// What the residual product needs to apply a pending Q update on the fly (MODE 4 of the march): the changed sets with their
-// rho differences (the arithmetic of k_q_update, band values regenerated from the operator descriptors) and where the updated
-// bands go -- a second copy of Q: the tile in front, the row above and the plane below are still read from the old one.
-// (the plan of the update: see k_q_update_plan below for what it holds and why its products are the bits of k_q_update's)
+// The plan of a Q update: see k_q_update_plan below for what it holds and why its products are the bits of k_q_update's
 constexpr int QP_MAXB = 9, QP_MAXT = 8, QP_TAB = 160;
 struct QPlanTerm {
   int kind;          // 0: one value; 1: diagonal of a difference set -- table over the classes of its nblk directions, index
@@ -205,13 +202,6 @@ struct QPlan {
   T tab[QP_TAB];
 };
 
-template <typename T>
-struct QUpd {
-  QPlan<T> plan;  // alpha_i * (A_i'A_i)[g, g + o] per boundary class of g, the changed sets in order (Q_update!.jl:45-48)
-  int pb[4];      // the plan's band for the stored bands with offsets 0, +1, +n1, +n1 n2 (-1: not touched by this update)
-  T* qn[4];       // the four stored bands of the updated matrix
-  Grid G;
-};
 struct NoExtra {};
 // The products on the CLASS TABLE of Q (CdsArgs::qtab): no band is loaded.  Q = sum alpha_i A_i'A_i (+ planned updates) takes
 // one value per stored band and boundary class of the row -- (cx, cy, cz), each 0 / 1 / 2 for the first / an interior / the
@@ -226,61 +216,6 @@ template <typename X>
 struct IsQTab { static constexpr bool value = false; };
 template <typename T>
 struct IsQTab<QTab<T>> { static constexpr bool value = true; };
-// value of stored band `role` at the point with coordinates c after the pending update; tab: the plan's products (LDS copy)
-template <typename T>
-__device__ __forceinline__ T q_upd_val(const QUpd<T>& u, const T* __restrict__ tab, int role, const Coord& c, T qv) {
-  const int b = u.pb[role];
-  if (b < 0) return qv;
-  const int cx = c.i == 0 ? 0 : (c.i == (int)u.G.n[0] - 1 ? 2 : 1), cy = c.j == 0 ? 0 : (c.j == (int)u.G.n[1] - 1 ? 2 : 1),
-            cz = c.k == 0 ? 0 : (c.k == (int)u.G.n[2] - 1 ? 2 : 1);
-  for (int ti = 0; ti < u.plan.nterms[b]; ++ti) {
-    const QPlanTerm& t = u.plan.t[b][ti];
-    if (t.kind == 0) {
-      qv = qv + tab[t.tab];
-    } else if (t.kind == 1) {
-      int idx = 0, m3 = 1;
-      for (int q = 0; q < t.nblk; ++q) {
-        const int d = t.dir[q];
-        idx += (d == 0 ? cx : (d == 1 ? cy : cz)) * m3;
-        m3 *= 3;
-      }
-      qv = qv + tab[t.tab + idx];
-    } else {
-      const int d = t.dir[0], cl = d == 0 ? cx : (d == 1 ? cy : cz);
-      qv = qv + (cl != (t.kind == 2 ? 2 : 0) ? tab[t.tab] : tab[t.tab + 1]);
-    }
-  }
-  return qv;
-}
-template <typename T>
-__device__ __forceinline__ T q_upd_val(const NoExtra&, const T*, int, const Coord&, T qv) { return qv; }
-template <typename T>
-__device__ __forceinline__ T q_upd_val(const QTab<T>&, const T*, int, const Coord&, T qv) { return qv; }
-template <typename T>
-__device__ __forceinline__ void load_plan_tab(const QUpd<T>& u, T* tab) {
-  for (int i = threadIdx.x; i < u.plan.ntab; i += blockDim.x) tab[i] = u.plan.tab[i];
-}
-template <typename T>
-__device__ __forceinline__ void load_plan_tab(const NoExtra&, T*) {}
-template <typename T>
-__device__ __forceinline__ void load_plan_tab(const QTab<T>&, T*) {}
-template <typename T>
-__device__ __forceinline__ const Grid& extra_grid(const QUpd<T>& u) { return u.G; }
-__device__ __forceinline__ Grid extra_grid(const NoExtra&) { return Grid{}; }
-template <typename T>
-__device__ __forceinline__ Grid extra_grid(const QTab<T>&) { return Grid{}; }
-template <typename T, int V>
-__device__ __forceinline__ void store_bands(const QUpd<T>& u, long long r, const Vec<T, V>& r0, const Vec<T, V>& r1, const Vec<T, V>& r2,
-                                            const Vec<T, V>& r3) {
-  stv<T, V>(u.qn[0] + r, r0);
-  stv<T, V>(u.qn[1] + r, r1);
-  stv<T, V>(u.qn[2] + r, r2);
-  stv<T, V>(u.qn[3] + r, r3);
-}
-template <typename T, int V>
-__device__ __forceinline__ void store_bands(const NoExtra&, long long, const Vec<T, V>&, const Vec<T, V>&, const Vec<T, V>&, const Vec<T, V>&) {}
-template <typename T, int V>
-__device__ __forceinline__ void store_bands(const QTab<T>&, long long, const Vec<T, V>&, const Vec<T, V>&, const Vec<T, V>&, const Vec<T, V>&) {}
 template <typename T>
 __device__ __forceinline__ void load_class_tab(const QTab<T>& u, T* tab) {
   for (int i = threadIdx.x; i < QT_N; i += blockDim.x) tab[i] = u.tab[i];
@@ -309,7 +244,6 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
                                                         const int* __restrict__ done, int lgLX, int tiles_x, int tiles_y, int zchunk,
                                                         long long items, CgState<T>* __restrict__ st, CgState<T>* __restrict__ host,
                                                         unsigned long long* ticket, X extra) {
-  constexpr bool UPD = MODE == 4;         // MODE 4 = MODE 2 (residual form) with the pending Q update applied on the fly
   constexpr bool TAB = IsQTab<X>::value;  // coefficients from the class table of Q, no band loaded (QTab)
   if (MODE == 1 && *done) return;
   // MODE 3 (fused CG iteration, see k_cds_fused): the scalar step of iteration k (resvec, stop test, beta) and the product of
@@ -344,12 +278,7 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
   };
   auto ldx1 = [&](long long at) -> T { return MODE == 3 ? x[at] + beta * b[at] : x[at]; };
   __shared__ T sx[2][V][MARCH_NT], sr[TAB ? 1 : 2][TAB ? 1 : V][TAB ? 1 : MARCH_NT];
-  __shared__ T qtab[UPD ? QP_TAB : 1];
   __shared__ T ctab[TAB ? QT_N : 1];
-  if (UPD) {
-    load_plan_tab<T>(extra, qtab);
-    __syncthreads();
-  }
   if (TAB) {
     load_class_tab(extra, ctab);
     __syncthreads();
@@ -374,10 +303,6 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
         rzm = tab_row<T, V>(ctab, 3, 3 * line_class(j, n2) + 9 * line_class(k0 - 1, n3), i0, n1);
       } else if (k0 > 0) {
         rzm = ldv<T, V>(R3 + st2 * (k0 - 1) + go);
-        if (UPD) {
-#pragma unroll
-          for (int k = 0; k < V; ++k) rzm.v[k] = q_upd_val<T>(extra, qtab, 3, Coord{(int)(i0 + k), (int)j, (int)(k0 - 1)}, rzm.v[k]);
-        }
       }
     }
     for (long long kz = k0; kz < k1; ++kz) {
@@ -401,17 +326,7 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
           r2 = ldv_nt<T, V>(R2 + pz + go);
           r3 = ldv_nt<T, V>(R3 + pz + go);
         }
-        if (MODE == 2 || MODE == 4) bv = ldv<T, V>(b + pz + go);
-        if (UPD) {
-#pragma unroll
-          for (int k = 0; k < V; ++k) {
-            const Coord ck{(int)(i0 + k), (int)j, (int)kz};
-            r0.v[k] = q_upd_val<T>(extra, qtab, 0, ck, r0.v[k]);
-            r1.v[k] = q_upd_val<T>(extra, qtab, 1, ck, r1.v[k]);
-            r2.v[k] = q_upd_val<T>(extra, qtab, 2, ck, r2.v[k]);
-            r3.v[k] = q_upd_val<T>(extra, qtab, 3, ck, r3.v[k]);
-          }
-        }
+        if (MODE == 2) bv = ldv<T, V>(b + pz + go);
       }
 #pragma unroll
       for (int k = 0; k < V; ++k) {
@@ -427,7 +342,6 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
         if (tx == 0 || (tid & 63) == 0) {
           xl = ldx1(r - 1);
           if (!TAB) rl = r > 0 ? R1[r - 1] : T(0);
-          if (UPD && r > 0) rl = q_upd_val<T>(extra, qtab, 1, coords(extra_grid(extra), r - 1), rl);     // (still the old value in memory)
         }
         if (tx == LX - 1 || (tid & 63) == 63) xr = ldx1(r + V);
       }
@@ -443,13 +357,7 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
           }
         } else {
           xu = ldx(r - st1);
-          if (!TAB && r - st1 >= 0) {
-            ru = ldv<T, V>(R2 + r - st1);
-            if (UPD) {
-#pragma unroll
-              for (int k = 0; k < V; ++k) ru.v[k] = q_upd_val<T>(extra, qtab, 2, coords(extra_grid(extra), r - st1 + k), ru.v[k]);
-            }
-          }
+          if (!TAB && r - st1 >= 0) ru = ldv<T, V>(R2 + r - st1);
         }
         if (ty < TY - 1 && j + 1 < n2) {
 #pragma unroll
@@ -494,7 +402,6 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
           stv<T, V>(y + r, o);
           if (pout) stv<T, V>(pout + r, o);
           if (xold) stv<T, V>(xold + r, x0);
-          if (UPD) store_bands<T, V>(extra, r, r0, r1, r2, r3);
         }
       }
       xm = x0; x0 = xp; rzm = r3;
@@ -507,7 +414,7 @@ __global__ __launch_bounds__(MARCH_NT) void k_cds_march(long long n1, long long 
     __syncthreads();
     if ((tid & 63) == 0) { sm[0][tid >> 6] = v0; sm[1][tid >> 6] = v1; }
     __syncthreads();
-    if (tid < ((MODE == 2 || MODE == 4) ? 2 : 1)) {
+    if (tid < (MODE == 2 ? 2 : 1)) {
       double s = 0;
 #pragma unroll
       for (int i = 0; i < MARCH_NT / 64; ++i) s += sm[tid][i];
@@ -559,7 +466,7 @@ bool K<T>::march_applies(long long N, const CdsArgs& a) {
 template <typename T, int MODE>
 static bool try_march(hipStream_t s, long long N, long long r0, long long r1, const T* R, const CdsArgs& a, const T* x, T* y, const T* b,
                       T* pout, T* xold, double* partials, const int* done, CgState<T>* st = nullptr, CgState<T>* host = nullptr,
-                      unsigned long long* ticket = nullptr, const QUpd<T>* upd = nullptr) {
+                      unsigned long long* ticket = nullptr) {
   MarchGeom m;
   if (!march_geom<T>(N, r0, r1, a, m)) return false;
   constexpr int V = sizeof(T) == 8 ? 2 : 4;
@@ -568,19 +475,14 @@ static bool try_march(hipStream_t s, long long N, long long r0, long long r1, co
 #define SIPX_MARCH(ORD, XT, XV)                                                                                                      \
   hipLaunchKernelGGL((k_cds_march<T, V, ORD, MODE, XT>), dim3(m.grid), dim3(MARCH_NT), 0, s, n1, n2, n3, r0 / st2, r1 / st2, R0, R1, R2, R3, x, y, b, \
                      pout, xold, partials, done, m.lg, m.tiles_x, m.tiles_y, m.zchunk, m.items, st, host, ticket, XV)
-  if constexpr (MODE == 4) {
-    if (a.march == 1) SIPX_MARCH(1, QUpd<T>, *upd);
-    else SIPX_MARCH(2, QUpd<T>, *upd);
+  if (a.qtab) {
+    const QTab<T> tab{(const T*)a.qtab};
+    if (a.march == 1) SIPX_MARCH(1, QTab<T>, tab);
+    else SIPX_MARCH(2, QTab<T>, tab);
+  } else if (a.march == 1) {
+    SIPX_MARCH(1, NoExtra, NoExtra{});
   } else {
-    if (a.qtab) {
-      const QTab<T> tab{(const T*)a.qtab};
-      if (a.march == 1) SIPX_MARCH(1, QTab<T>, tab);
-      else SIPX_MARCH(2, QTab<T>, tab);
-    } else if (a.march == 1) {
-      SIPX_MARCH(1, NoExtra, NoExtra{});
-    } else {
-      SIPX_MARCH(2, NoExtra, NoExtra{});
-    }
+    SIPX_MARCH(2, NoExtra, NoExtra{});
   }
 #undef SIPX_MARCH
   return true;
@@ -1427,30 +1329,6 @@ void K<T>::spmv_fused(hipStream_t s, long long N, const T* R, const CdsArgs& a, 
   SIPX_HIP(hipGetLastError());
 }
 
-// The residual product of an x-step that follows a change of rho, with the Q update applied on the fly (z-marching matrices, one
-// rank, band values generated from the descriptors): reads the four stored bands of the OLD matrix once, adds the changed sets'
-// rho differences in k_q_update's order (same arithmetic: the same bits), uses the result in the product and writes it into the
-// second copy of Q -- 8 N w for update + product instead of 8 + 4, and one launch less.  false: not applicable (caller: k_q_update, then the product).
-template <typename T>
-bool K<T>::resid_qupdate(hipStream_t s, const Grid& g, long long N, const T* R_old, T* R_new, const CdsArgs& a, const QArgs<T>& qa, const T* x,
-                         const T* b, T* r, T* p, T* xold, double* partials) {
-  if (!a.march || !a.sym || a.d != 7 || qa.nsets == 0) return false;
-  for (int i = 0; i < qa.nsets; ++i)
-    if (qa.s[i].ata) return false;                     // caller-supplied A'A bands: the separate kernel reads them
-  QUpd<T> u;
-  if (!make_q_plan<T>(g, a, qa, u.plan)) return false;
-  for (int q = 0; q < 4; ++q) {
-    u.qn[q] = R_new + (long long)a.mb[q] * N;
-    u.pb[q] = -1;
-    for (int b = 0; b < u.plan.nbands; ++b)
-      if (u.plan.col[b] == a.mb[q]) u.pb[q] = b;
-  }
-  u.G = g;
-  const double rw = (double)N * sizeof(T);
-  ObsScope obs(KID_CDS_RESID, s, (a.d + 4.0) * rw + 3.0 * 4.0 * rw, (4.0 + 4.0) * rw + 4.0 * rw);      // SURVEY: B_resid0 + B_Q; moved: 4 bands + x, b, r, x_old + 4 bands written
-  return try_march<T, 4>(s, N, 0, N, R_old, a, x, r, b, p, xold, partials, nullptr, nullptr, nullptr, nullptr, &u);
-}
-
 // ---------------------------------------------------------------------------------------------
 // out[slot] = sum of the NB partials of each slot (one block per slot, fixed order)
 // word (pinned, optional): the workgroup that finishes last publishes `seq` there with a system-scope release store, behind every
@@ -1502,8 +1380,6 @@ void K<T>::copy_f64(hipStream_t s, const double* src, double* dst, int n) {
                                  CgState<T>*, CgState<T>*, unsigned long long*);                                      \
   template void K<T>::resid(hipStream_t, long long, long long, long long, const T*, const CdsArgs&, const T*, const T*, T*, \
                             T*, T*, double*);                                                                         \
-  template bool K<T>::resid_qupdate(hipStream_t, const Grid&, long long, const T*, T*, const CdsArgs&, const QArgs<T>&, const T*, \
-                                    const T*, T*, T*, T*, double*);                                                   \
   template void K<T>::q_axpy(hipStream_t, long long, T*, const T*, T);                                               \
   template void K<T>::q_update_mk(hipStream_t, const Grid&, const CdsArgs&, const MkArgs<T>&, T*);                    \
   template void K<T>::mirror_bands(hipStream_t, long long, const CdsArgs&, T*);                                       \
