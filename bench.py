@@ -14,6 +14,12 @@ or a factorisation (the c4 leg) are sharded by constraint set, the x-step on z-s
 Prints ONE JSON line (rank 0).  roofline = the dominant kernel (cds_spmv fused with the CG dot
 product), timed with HIP events on the engine stream over the timed steps; cpu_baseline = the
 oracle's C/OpenMP port of the reference algorithm on the host cores (rank 0, N=1 only).
+
+A plain run does what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the
+line.  --full adds everything else: the all-kernel statistics window (dominant_kernel, kernels,
+iteration_roofline.frac), the legs c3_512, c4_512, c5, c5_layered, c2_2048, whole_call and
+cpu_baseline, and at N > 1 the set-sharded headline, c4_512_slab, the ranks' comparison of x and
+the comm probe (the --no-* switches leave parts of it out).
 """
 import argparse
 import json
@@ -835,14 +841,20 @@ def main():
                          "new one on the same context); ms_per_step = their wall time / steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-512", action="store_true", help="skip the short 512^3 leg that follows the default 256^3 headline run")
-    ap.add_argument("--no-c4", action="store_true", help="skip the short leg on BASELINE config 4 (512^3, eight sets) that follows the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the bench measures or checks: the all-kernel statistics window, the legs "
+                         "(c3_512, c4_512, c5, c5_layered, c2_2048, whole_call, cpu_baseline) and at N > 1 the set-sharded headline, "
+                         "c4_512_slab, the ranks' comparison of x and the comm probe; the --no-* switches leave parts of it out.  "
+                         "Without it: set-up, warm-up, the timed steps, --dump-outputs and the line only (--dry-comm rehearses its "
+                         "whole flow either way)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-512", action="store_true", help="--full: skip the short 512^3 leg that follows the 256^3 headline run")
+    ap.add_argument("--no-c4", action="store_true", help="--full: skip the short leg on BASELINE config 4 (512^3, eight sets)")
     ap.add_argument("--no-kernel-table", action="store_true",
-                    help="skip the all-kernel statistics window that follows the timed steps (profiling runs: its event records would show up as gaps)")
-    ap.add_argument("--no-c2", action="store_true", help="skip the leg on BASELINE config 2 (2048^2, {bounds, l1:TV})")
-    ap.add_argument("--no-whole-call", action="store_true", help="skip the whole-call leg (first and later calls of PARSDMM(...) with default options)")
-    ap.add_argument("--no-c5", action="store_true", help="skip the leg on BASELINE config 5 (PARSDMM_multi_level, 512^3 Float64, 3 levels) that follows the default run")
+                    help="--full: skip the all-kernel statistics window that follows the timed steps (profiling runs: its event records would show up as gaps)")
+    ap.add_argument("--no-c2", action="store_true", help="--full: skip the leg on BASELINE config 2 (2048^2, {bounds, l1:TV})")
+    ap.add_argument("--no-whole-call", action="store_true", help="--full: skip the whole-call leg (first and later calls of PARSDMM(...) with default options)")
+    ap.add_argument("--no-c5", action="store_true", help="--full: skip the leg on BASELINE config 5 (PARSDMM_multi_level, 512^3 Float64, 3 levels)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"],
                     help="f32 = the contract workload; f64 = the same sets in Float64 (BASELINE config 5 computes in Float64)")
     ap.add_argument("--decomp", default="auto", choices=["auto", "sets", "slab"],
@@ -1035,9 +1047,9 @@ def main():
         if coll0 and coll1:
             coll_per_step = {k: round((coll1[k] - coll0.get(k, 0)) / max(steps, 1), 2) for k in coll1}
             coll_per_step["total"] = round(sum(coll_per_step.values()), 2)
-        # the product of the CG iteration over the timed steps; then EVERY kernel over a window of its own (two event records
-        # around each launch cost about 5 us: not something to have inside the timed region)
-        want_table = not ended and not args.no_kernel_table
+        # the product of the CG iteration over the timed steps; then, with --full, EVERY kernel over a window of its own (two
+        # event records around each launch cost about 5 us: not something to have inside the timed region)
+        want_table = args.full and not ended and not args.no_kernel_table
         launches, kms = ctx.kernel_stats(2 if want_table else 0)
         per_kernel = None
         moved = None
@@ -1133,10 +1145,10 @@ def main():
                     b += sum(2 * r for r in rows[:pp])
                 it_bytes += b * w
         it_gbs = it_bytes / dt / 1e9 / max(world, 1)                # per GPU
-        # Sharded: do the ranks hold the same x?  Every rank completes x (a collective in the slab decomposition), takes an exact
-        # integer checksum of its bits and the ranks compare -- the first thing to look at in a first multi-GPU run.
+        # Sharded, --full: do the ranks hold the same x?  Every rank completes x (a collective in the slab decomposition), takes an
+        # exact integer checksum of its bits and the ranks compare -- the first thing to look at in a first multi-GPU run.
         agree = None
-        if dist is not None:
+        if dist is not None and args.full:
             try:
                 xs, _, _ = ctx.download(want_ly=False)
                 bits = xs.view(np.uint32 if xs.dtype == np.float32 else np.uint64)
@@ -1168,10 +1180,10 @@ def main():
                      "device_bytes_per_rank": dev_bytes["context"], "device_used_bytes": dev_bytes["device_used"]},
             "dominant_kernel": dominant, "kernels": table,
             # one rank: threshold searches through the batched chain since the context was built, and how many needed their fallback sweeps
-            "batched_searches": (per_kernel.get("batched_searches") if per_kernel else None),
+            "batched_searches": counters.get("batched_searches"),
             # a slice-rank set in the list: which route its projector took since the context was built (engine counters: calls,
             # calls served by the warm-started filtered subspace iteration, full decompositions, products with the Gram matrices)
-            "rank_route": (per_kernel.get("rank_route") if per_kernel and (per_kernel.get("rank_route") or {}).get("calls") else None),
+            "rank_route": (counters.get("rank_route") if (counters.get("rank_route") or {}).get("calls") else None),
             "value": steps / dt, "ms_per_step": dt / steps * 1e3, "decomposition": ("slab" if slab else "sets") if dist is not None else None,
             # log.timing of the whole run (warm-up included), per iteration: where the time of an iteration goes on this rank
             "timing_ms_per_iteration": {k: round(float(v) * 1e3 / max(len(log.obj), 1), 4) for k, v in (log.timing or {}).items()},
@@ -1225,7 +1237,7 @@ def main():
             o["batched_searches"] = r["batched_searches"]
         return o
 
-    # ---- secondary legs that cannot take the headline with them ----------------------------------------------------------
+    # ---- secondary legs (--full) that cannot take the headline with them -------------------------------------------------------
     # One rank, or an engine error that every rank raises alike (a threshold search that does not fit its exchange segments on
     # some node): the error is recorded under the leg's key and the run goes on.  A failure on ONE rank only (round 4's rehearsal
     # with four ranks on one GPU: the fourth ran out of device memory in the c5 leg) used to send that rank on into the next
@@ -1452,12 +1464,12 @@ def main():
         out["rehearsal"] = f"SIPX_BENCH_SHARE_GPU: {world} ranks share GPU 0, the engine's collectives over gloo callbacks -- a rehearsal of the N > 1 flow, not a measurement"
     partial["out"] = out
     both = None
-    if (world > 1 or force_dist) and args.decomp == "auto" and r.get("decomposition") == "slab":
+    if args.full and (world > 1 or force_dist) and args.decomp == "auto" and r.get("decomposition") == "slab":
         # (the set-sharded run keeps the communicator the headline ended up with)
         sets_mode = (r["comm"].get("comm_mode") if r["comm"].get("fell_back_from") else None)
         # Which of the two decompositions is faster on a given node depends on RCCL's small-message latency (slab: small
-        # collectives only) against its bandwidth (sets: two N-vector exchanges).  Both are timed for the same K steps and
-        # reported under fixed keys; the headline `value` is ALWAYS the slab decomposition -- the one DESIGN 5 chooses for this
+        # collectives only) against its bandwidth (sets: two N-vector exchanges).  With --full both are timed for the same K steps
+        # and reported under fixed keys; the headline `value` is ALWAYS the slab decomposition -- the one DESIGN 5 chooses for this
         # set list -- so that it means the same thing from run to run and from node to node.
         progress("headline workload again, sharded by constraint set")
         r2 = safe("sets-decomposed headline", lambda: measure(args.config, args.steps, args.warmup, decomp="sets", comm_mode=sets_mode))
@@ -1468,14 +1480,14 @@ def main():
         out["decompositions"] = both
         out["faster_decomposition"] = max(both, key=lambda k: both[k].get("value", 0.0))
     elif dist is not None and r.get("decomposition"):
-        # (a headline that ended up set-sharded, or --decomp sets / slab: the one decomposition that ran, under the same key)
+        # (a plain run, a headline that ended up set-sharded, or --decomp sets / slab: the one decomposition that ran, under the same key)
         out["decompositions"] = {r["decomposition"]: {"value": r["value"], "ms_per_step": r["ms_per_step"], "comm": r["comm"],
                                                       "parallelism": r["config"]["parallelism"], "timing_ms_per_iteration": r["timing_ms_per_iteration"]}}
-    if args.config == "c3" and args.dtype == "f32" and not args.no_512:
+    if args.full and args.config == "c3" and args.dtype == "f32" and not args.no_512:
         # the honest HBM point (Q = 3.5 GiB, nothing fits the 256 MiB Infinity Cache): a short run of the same sets at 512^3
         progress("c3_512 leg")
         out["c3_512"] = safe("c3_512", lambda: leg(measure("c3-512", 10, 5), 10, 5))
-    if args.config == "c3" and args.dtype == "f32" and args.q_mode == "cds" and not args.no_c4:
+    if args.full and args.config == "c3" and args.dtype == "f32" and args.q_mode == "cds" and not args.no_c4:
         # BASELINE configs[3]: 512^3, the eight constraint sets + distance term, at every N (the scaling target of the
         # contract is quoted on THIS set list: ">= 3.5x at 8 GPUs when 8 constraint sets are sharded").  Sets one per rank;
         # the slice-rank set, half of the single-GPU time (94 % before its warm-started subspace route), is projected by all ranks (each its slab of slices).
@@ -1487,7 +1499,7 @@ def main():
             # owner rank on the gathered vector
             progress("c4_512 leg, slab-decomposed")
             out["c4_512_slab"] = safe("c4_512_slab", lambda: leg(measure("c4", 6, 2, decomp="slab", comm_mode=("torch" if share_gpu else None)), 6, 2, full=False))
-    if args.config == "c3" and args.dtype == "f32" and args.q_mode == "cds" and not args.no_c5:
+    if args.full and args.config == "c3" and args.dtype == "f32" and args.q_mode == "cds" and not args.no_c5:
         # BASELINE configs[4]: PARSDMM_multi_level, 512^3 Float64, 3 levels, {bounds, l1:TV}, timed as ONE call
         # (examples/test_scaling_3D.jl:144-148); at N > 1 every level is slab-decomposed over the ranks.  `c5`: SURVEY 8(d)'s
         # model; `c5_layered`: a velocity-model-like field, the kind the reference's own timing runs on (c5_model).
@@ -1502,20 +1514,20 @@ def main():
             r5m = safe(key, lambda: run_c5(sipx, n5, maxit=100, model=model, device=local_rank, dist=dist))
             r5m["n_gpus"] = world
             out[key] = r5m
-    if dist is not None and (world > 1 or force_dist):
+    if args.full and dist is not None and (world > 1 or force_dist):
         progress("comm probe")
         out["comm_probe_us"] = safe("comm probe", lambda: comm_probe(dist, torch, world, rank, dev=torch.device("cpu") if share_gpu else None))
-    if args.config == "c3" and args.dtype == "f32" and args.q_mode == "cds" and world == 1 and dist is None and not args.no_c2:
+    if args.full and args.config == "c3" and args.dtype == "f32" and args.q_mode == "cds" and world == 1 and dist is None and not args.no_c2:
         # BASELINE configs[1]: 2048^2 Float32, {bounds, l1:TV} -- launch bound, Infinity-Cache resident (Q = 80 MiB): it/s only
         progress("c2_2048 leg")
         out["c2_2048"] = safe("c2_2048", lambda: leg(measure("c2", 20, 5), 20, 5, full=False))
-    if args.config == "c3" and args.dtype == "f32" and args.q_mode == "cds" and world == 1 and dist is None and not args.no_whole_call:
+    if args.full and args.config == "c3" and args.dtype == "f32" and args.q_mode == "cds" and world == 1 and dist is None and not args.no_whole_call:
         # the reference's own measurement is one wall clock around the call (examples/test_scaling_3D.jl:116-117: `@timed PARSDMM(...)`
         # after a first call): PARSDMM(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options) with default options, stop rules active,
         # first call (the context is built) and the calls after it (the context is reset: sipx_reset)
         progress("whole-call leg")
         out["whole_call"] = safe("whole_call", lambda: whole_call(sipx, args.config, TF))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.dtype == "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.dtype == "f32":
         progress("cpu baseline")
         out["cpu_baseline"] = safe("cpu_baseline", lambda: cpu_baseline(args.config, n, h, kinds))
     restore_stdout()

@@ -2037,7 +2037,7 @@ def test_bench_contract_line(dist_env):
     import tempfile
     detail = os.path.join(tempfile.mkdtemp(prefix="sipx_bench_"), "detail.json")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c3-small", "--steps", "4", "--warmup", "2", "--detail", detail,
-                        "--no-cpu-baseline", "--no-512", "--no-c4", "--no-c5"], capture_output=True, text=True, timeout=280, env=env)
+                        "--full", "--no-cpu-baseline", "--no-512", "--no-c4", "--no-c5"], capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -2148,3 +2148,31 @@ def test_bench_times_exactly_the_steps_asked_for():
     assert h["steps"] == 600 and sum(per_solve) == 600 and min(per_solve) >= 1, per_solve
     assert h["ms_per_step"] > 0 and abs(h["value"] * h["ms_per_step"] - 1e3) <= 0.2          # (five significant digits each)
     assert d["config"]["cg_iterations_in_timed_steps"] > 0 and d["config"]["all_logs_finite"]
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_the_headline_alone():
+    """bench.py without --full on the headline workload (C3, 256^3): set-up, warm-up, the timed steps and the line -- the roofline
+    of the product kernel comes from the timed steps themselves; no statistics window, no leg, no CPU baseline (those are --full's)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    detail = os.path.join(tempfile.mkdtemp(prefix="sipx_bench_"), "detail.json")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--detail", detail],
+                       capture_output=True, text=True, timeout=280, env=dict(os.environ))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 4096, r.stdout
+    h = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+        assert k in h, k
+    assert h["n_gpus"] == 1 and h["steps"] == 3 and h["warmup"] == 1 and h["value"] > 0 and h["dtype"] == "f32"
+    assert h["roofline"]["launches"] > 0 and h["config"]["all_logs_finite"]
+    d = json.load(open(detail))
+    legs = ("c3_512", "c4_512", "c4_512_slab", "c5", "c5_layered", "c2_2048", "whole_call", "cpu_baseline", "comm_probe_us", "decompositions")
+    assert not [k for k in legs if k in d or k in h], sorted(d)
+    assert d["dominant_kernel"] is None and d["kernels"] is None and d["iteration_roofline"]["frac"] is None
+    assert d["iteration_roofline"]["frac_survey"] > 0

@@ -567,7 +567,7 @@ def test_bench_two_ranks_share_the_gpu():
         env.pop(k, None)
     import tempfile
     detail = os.path.join(tempfile.mkdtemp(prefix="sipx_bench_"), "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-c4", "--no-c5",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-c4", "--no-c5",
                         "--detail", detail], capture_output=True, text=True, timeout=380, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]

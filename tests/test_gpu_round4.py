@@ -393,7 +393,7 @@ def test_bench_headline_survives_a_leg_that_fails_on_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     detail = os.path.join(tempfile.mkdtemp(prefix="sipx_bench_"), "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-c4", "--no-c5",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full", "--no-c4", "--no-c5",
                         "--detail", detail], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]

@@ -329,7 +329,7 @@ def test_bench_headline_survives_a_rank_that_fails_it():
     planes), and the line carries `value`, both decompositions, what was fallen back from and the error; exit code 0.  Round 4 ran the
     headline outside every protection: the run came back empty."""
     import json
-    r, lines, d = _bench_two_ranks({"SIPX_BENCH_FAIL_LEG": "headline:1"})
+    r, lines, d = _bench_two_ranks({"SIPX_BENCH_FAIL_LEG": "headline:1"}, ("--full",))
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1 and len(lines[0]) < 4096, r.stdout[:2000]
     h = json.loads(lines[0])

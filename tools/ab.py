@@ -25,7 +25,7 @@ for r in range(rounds):
                 if os.path.exists(p):
                     env["SIPX_LIBRARY"] = p
         detail = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"sipx_ab_detail_{os.getpid()}.json")
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-c4", "--no-c5", "--config", config,
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-c4", "--no-c5", "--config", config,
                               "--detail", detail] + extra, env=env, capture_output=True, text=True, timeout=300)
         if out.returncode != 0:
             print(v, "FAILED", out.stderr[-400:], flush=True)

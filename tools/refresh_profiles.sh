@@ -11,7 +11,7 @@ O=gpurun_out/prof; mkdir -p $O
 T="timeout -k 10 500"
 # profiled runs: the headline workload only, without the all-kernel statistics window (its event records would show up as gaps)
 B="--no-cpu-baseline --no-512 --no-c4 --no-c5 --no-c2 --no-whole-call --no-kernel-table"
-S="--no-cpu-baseline --no-c4 --no-c5 --no-c2 --no-whole-call"      # plain runs of one workload (the 512^3 leg kept where the config is c3)
+S="--full --no-cpu-baseline --no-c4 --no-c5 --no-c2 --no-whole-call"      # runs of one workload with the kernel table (the 512^3 leg kept where the config is c3)
 pmc_pair() {   # <config> <tag>: the two HBM-side passes (FETCH_SIZE / WRITE_SIZE in separate runs, --kernel-trace only)
   $T rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_f -o t --output-format csv -- python3 bench.py $B --config $1 --steps 6 --warmup 2 > /dev/null 2>$O/pmc.err
   $T rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_w -o t --output-format csv -- python3 bench.py $B --config $1 --steps 6 --warmup 2 > /dev/null 2>>$O/pmc.err
@@ -67,7 +67,7 @@ PY
   rm -rf $O/sp_engine_* $O/sp_march_*
 fi
 cp $O/${R}_c3_256_pmc.json $O/${R}_c3_512_pmc.json profiles/      # (this box's copy: the bench line quotes `traffic` from a profile of the running build)
-$T python bench.py --detail $O/${R}_bench_default_detail.json > $O/${R}_bench_default.json 2>$O/bench.err
+$T python bench.py --full --detail $O/${R}_bench_default_detail.json > $O/${R}_bench_default.json 2>$O/bench.err
 fi
 if [[ $PART == b || $PART == all ]]; then
   # C4 (eight sets, 512^3) iteration by iteration: with the slice-rank set on its lane (the product), and in turn on the engine
@@ -110,7 +110,7 @@ if [[ $PART == c || $PART == all ]]; then
   # a chain of dependent small kernels, launched one by one and as a captured graph: what a launch-bound iteration (2048^2) can gain
   if [ -x scratch/launch_gap_bench ]; then $T scratch/launch_gap_bench > $O/${R}_launch_gap.txt 2>&1; fi
   # NOT a measurement: the N > 1 flow of the whole bench with four ranks on this one GPU (headline chain, every leg incl. c4_512_slab)
-  SIPX_BENCH_SHARE_GPU=1 timeout -k 10 700 python bench.py --gpus 4 --no-c5 --no-512 --detail $O/${R}_bench_4ranks_share_one_gpu_rehearsal_detail.json > $O/${R}_bench_4ranks_share_one_gpu_rehearsal.json 2>>$O/bench.err
+  SIPX_BENCH_SHARE_GPU=1 timeout -k 10 700 python bench.py --gpus 4 --full --no-c5 --no-512 --detail $O/${R}_bench_4ranks_share_one_gpu_rehearsal_detail.json > $O/${R}_bench_4ranks_share_one_gpu_rehearsal.json 2>>$O/bench.err
   # the slice-rank projector on slices without a spectral gap (C4's model), filtered subspace route against the full decomposition
   $T python tools/rank_flat_bench.py 512 32 12 > $O/${R}_rank_flat_512.json 2>>$O/bench.err
   $T python tools/rank_flat_bench.py 256 32 12 > $O/${R}_rank_flat_256.json 2>>$O/bench.err
