@@ -200,6 +200,39 @@ int sipx_q_update(sipx_ctx* ctx, const double* rho_new, const double* rho_old);
 /* copy out x, l[i], y[i] (any pointer may be NULL)                     (src/PARSDMM.jl:257) */
 int sipx_download(sipx_ctx* ctx, void* x, void* const* l, void* const* y);
 
+/* ---- the same boundary for data that lives on the GPU ----
+ * The reference's callers use PARSDMM as a projector inside a loop whose data is already on the device (an FWI iterate per gradient
+ * step, examples/constrained_freq_FWI_simple.jl:468; the output of a network per training step,
+ * examples/GeneralizedMinkowski/ConstrainedNeuralNetworkSegmentation_*.jl).  sipx_finalize_dev / sipx_reset_dev / sipx_download_dev
+ * are sipx_finalize / sipx_reset / sipx_download with every VECTOR argument -- m, x0, l0[i], y0[i], x, l[i], y[i] -- a pointer to
+ * device memory on the context's GPU (the pointer arrays l0 / y0 / l / y themselves, rho_ini and feasibility_initial stay host
+ * memory); same lengths, same row order, same meaning, and the context is left in the same state: a solve gives the same bits
+ * whichever form started it, and the two forms may be mixed on one context.  No vector crosses PCIe, nothing is allocated, and one
+ * launch moves all vectors of a call between the caller's buffers and the padded arrays of the context.
+ * ORDERING.  The engine works on streams of its own.  sipx_set_caller_stream names the stream the caller produces m (and the warm
+ * start) on and consumes the results on (a hipStream_t; NULL, the default, is the default stream); it holds until changed.
+ *   - The import of _finalize_dev / _reset_dev waits, on the device, for an event recorded on the caller's stream when the call is
+ *     made: work queued there before the call is seen.  Both calls end with the host wait of the initial feasibility, as their
+ *     host forms do; when they return the caller's input buffers have been read and may be reused.
+ *   - sipx_download_dev first lets the engine wait for the caller's stream (so that work still reading the result buffers
+ *     finishes first), writes the results on the engine stream, records an event there and makes the caller's stream wait for
+ *     it.  It returns without waiting on the host: the results are valid for work queued on the caller's stream after the call
+ *     (for the host: after synchronising that stream).
+ * Single-process contexts only: with a communicator attached, a slab decomposition requested or set ownership given, the three
+ * calls fail with a message (use the host forms there).  Every set kind, both precisions, Minkowski contexts (x of length 2N)
+ * and feasibility_only are taken. */
+int sipx_set_caller_stream(sipx_ctx* ctx, void* stream);
+int sipx_finalize_dev(sipx_ctx* ctx, const void* m, const double* rho_ini, int n_rho, double gamma_ini, int feasibility_only,
+                      int zero_ini_guess, const void* x0, const void* const* l0, const void* const* y0,
+                      double* feasibility_initial);
+int sipx_reset_dev(sipx_ctx* ctx, const void* m, const double* rho_ini, int n_rho, double gamma_ini, int zero_ini_guess,
+                   const void* x0, const void* const* l0, const void* const* y0, double* feasibility_initial);
+int sipx_download_dev(sipx_ctx* ctx, void* x, void* const* l, void* const* y);
+/* Bytes of the N-sized transfers between host and device that sipx_finalize, sipx_reset and sipx_download (and their _dev forms)
+ * have made on this context since it was created or since the last call with reset != 0: m, x, l_i, y_i, bound vectors and
+ * explicit A'A bands.  The _dev forms add nothing for m, x, l_i, y_i.  Either pointer may be NULL. */
+int sipx_io_bytes(sipx_ctx* ctx, int64_t* host_to_device, int64_t* device_to_host, int reset);
+
 /* Multilevel (src/PARSDMM_multi_level.jl:61-83, src/interpolate_y_l.jl:16-94): warm start of a finalized context on a finer
  * grid from a solved context on a coarser one, DEVICE TO DEVICE -- x, every l_i and y_i are resampled (nearest neighbour,
  * the set-by-set block arithmetic of interpolate_y_l) without visiting the host.  Both contexts hold the same sets, in the

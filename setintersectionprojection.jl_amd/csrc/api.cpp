@@ -81,6 +81,21 @@ int sipx_adapt_rho_gamma(sipx_ctx* c, int adjust_rho, int adjust_gamma, double* 
 }
 int sipx_q_update(sipx_ctx* c, const double* rho_new, const double* rho_old) { SIPX_TRY(c->e->q_update(rho_new, rho_old)) }
 int sipx_download(sipx_ctx* c, void* x, void* const* l, void* const* y) { SIPX_TRY(c->e->download(x, l, y)) }
+int sipx_finalize_dev(sipx_ctx* c, const void* m, const double* rho_ini, int n_rho, double gamma_ini, int feasibility_only,
+                      int zero_ini_guess, const void* x0, const void* const* l0, const void* const* y0,
+                      double* feasibility_initial) {
+  SIPX_TRY(c->e->finalize_dev(m, rho_ini, n_rho, gamma_ini, feasibility_only, zero_ini_guess, x0, l0, y0,
+                              feasibility_initial))
+}
+int sipx_reset_dev(sipx_ctx* c, const void* m, const double* rho_ini, int n_rho, double gamma_ini, int zero_ini_guess,
+                   const void* x0, const void* const* l0, const void* const* y0, double* feasibility_initial) {
+  SIPX_TRY(c->e->reset_dev(m, rho_ini, n_rho, gamma_ini, zero_ini_guess, x0, l0, y0, feasibility_initial))
+}
+int sipx_download_dev(sipx_ctx* c, void* x, void* const* l, void* const* y) { SIPX_TRY(c->e->download_dev(x, l, y)) }
+int sipx_set_caller_stream(sipx_ctx* c, void* stream) { SIPX_TRY(c->e->set_caller_stream(stream)) }
+int sipx_io_bytes(sipx_ctx* c, int64_t* host_to_device, int64_t* device_to_host, int reset) {
+  SIPX_TRY(c->e->io_bytes(host_to_device, device_to_host, reset))
+}
 int sipx_warm_start_from(sipx_ctx* fine, sipx_ctx* coarse) {
   SIPX_TRY({
     if (!fine || !coarse) throw std::runtime_error("null context");

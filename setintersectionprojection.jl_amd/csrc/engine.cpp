@@ -459,6 +459,8 @@ class Engine : public EngineBase {
     for (auto e : stat_ev_) (void)hipEventDestroy(e);
     for (auto e : cg_ev_) if (e) (void)hipEventDestroy(e);
     for (hipStream_t q : pool_) if (q != stream_) (void)hipStreamDestroy(q);
+    if (ev_io_in_) (void)hipEventDestroy(ev_io_in_);
+    if (ev_io_out_) (void)hipEventDestroy(ev_io_out_);
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_fork2_) (void)hipEventDestroy(ev_fork2_);
     (void)hipStreamDestroy(stream_);
@@ -736,7 +738,11 @@ class Engine : public EngineBase {
     }
     {
       const long long c0 = std::max<long long>(0, wlo_), c1 = std::min<long long>(N, whi_);      // (sparse arrays: the rank's share only)
-      if (c1 > c0) SIPX_HIP(hipMemcpy(m_ + c0, (const T*)m + c0, (c1 - c0) * sizeof(T), hipMemcpyHostToDevice));
+      // (device-resident call: m arrives with the warm start, in the one launch of import_dev below)
+      if (c1 > c0 && !dev_io_) {
+        SIPX_HIP(hipMemcpy(m_ + c0, (const T*)m + c0, (c1 - c0) * sizeof(T), hipMemcpyHostToDevice));
+        io_h2d_ += (c1 - c0) * (long long)sizeof(T);
+      }
     }
     {
       // x0 mode of the one-sweep update: when EVERY y/l update of this context goes through the sweep (its block layout is
@@ -921,6 +927,7 @@ class Engine : public EngineBase {
       if (!s.host_ata.empty()) {
         s.ata = dalloc<T>((size_t)N * s.ata_off.size(), false);
         SIPX_HIP(hipMemcpy(s.ata, s.host_ata.data(), s.host_ata.size() * sizeof(T), hipMemcpyHostToDevice));
+        io_h2d_ += (long long)(s.host_ata.size() * sizeof(T));
         s.host_ata.clear();
         s.host_ata.shrink_to_fit();
       }
@@ -1018,8 +1025,8 @@ class Engine : public EngineBase {
         upload_rows(s, s.host_lb.data(), s.lb);
         upload_rows(s, s.host_ub.data(), s.ub);
       }
-      if (warm && l0 && l0[i]) upload_rows_ranged(s, (const T*)l0[i], s.l);
-      if (warm && y0 && y0[i]) upload_rows_ranged(s, (const T*)y0[i], s.y);
+      if (warm && !dev_io_ && l0 && l0[i]) upload_rows_ranged(s, (const T*)l0[i], s.l);
+      if (warm && !dev_io_ && y0 && y0[i]) upload_rows_ranged(s, (const T*)y0[i], s.y);
     }
     if (search_batch_) {                    // the sets' header segments and decision registers of the batched searches
       int n2 = 0;
@@ -1027,9 +1034,14 @@ class Engine : public EngineBase {
       fbuf_ = dalloc<T>((size_t)n2 * fast_hdr<T>());
       stage_ = dalloc<double>((size_t)n2 * (PREP_SLOTS + 1 + 2));
     }
-    if (warm && x0) {                        // Minkowski: [u; v], 2N entries (sparse arrays: the rank's share)
+    if (dev_io_) {
+      import_dev(m, warm ? x0 : nullptr, warm ? l0 : nullptr, warm ? y0 : nullptr);
+    } else if (warm && x0) {                 // Minkowski: [u; v], 2N entries (sparse arrays: the rank's share)
       const long long c0 = slab_local_ ? std::max<long long>(0, wlo_) : 0, c1 = slab_local_ ? std::min<long long>(Nx_, whi_) : Nx_;
-      if (c1 > c0) SIPX_HIP(hipMemcpy(x_ + c0, (const T*)x0 + c0, (c1 - c0) * sizeof(T), hipMemcpyHostToDevice));
+      if (c1 > c0) {
+        SIPX_HIP(hipMemcpy(x_ + c0, (const T*)x0 + c0, (c1 - c0) * sizeof(T), hipMemcpyHostToDevice));
+        io_h2d_ += (c1 - c0) * (long long)sizeof(T);
+      }
     }
 
     assemble_Q();
@@ -1128,7 +1140,10 @@ class Engine : public EngineBase {
     dzero(scr_v_, stream_); dzero(scr_c_, stream_); dzero(scr_w_, stream_);
     if (scr_i_) dzero(scr_i_, stream_);
     dzero(lane_v_, stream_);
-    SIPX_HIP(hipMemcpyAsync(m_, m, N * sizeof(T), hipMemcpyHostToDevice, stream_));
+    if (!dev_io_) {
+      SIPX_HIP(hipMemcpyAsync(m_, m, N * sizeof(T), hipMemcpyHostToDevice, stream_));
+      io_h2d_ += N * (long long)sizeof(T);
+    }
     x_cur_ = 0; x_snap_ = -1;
     x_ = xr_[0]; xold_ = x_;
     // ---- rho, gamma (PARSDMM_initialize.jl:58-63,107-114,159)
@@ -1154,10 +1169,15 @@ class Engine : public EngineBase {
       if (s.ps) K<T>::ps_init(stream_, s.ps, scr_i_);
       if (s.psf) K<T>::ps_init(stream_, s.psf, scr_i_);
       if (s.ext) { s.ext->set_stream(stream_); s.ext->reset(); }
-      if (warm && l0 && l0[i]) upload_rows_ranged(s, (const T*)l0[i], s.l);
-      if (warm && y0 && y0[i]) upload_rows_ranged(s, (const T*)y0[i], s.y);
+      if (warm && !dev_io_ && l0 && l0[i]) upload_rows_ranged(s, (const T*)l0[i], s.l);
+      if (warm && !dev_io_ && y0 && y0[i]) upload_rows_ranged(s, (const T*)y0[i], s.y);
     }
-    if (warm && x0) SIPX_HIP(hipMemcpyAsync(x_, x0, Nx_ * sizeof(T), hipMemcpyHostToDevice, stream_));
+    if (dev_io_) {
+      import_dev(m, warm ? x0 : nullptr, warm ? l0 : nullptr, warm ? y0 : nullptr);
+    } else if (warm && x0) {
+      SIPX_HIP(hipMemcpyAsync(x_, x0, Nx_ * sizeof(T), hipMemcpyHostToDevice, stream_));
+      io_h2d_ += Nx_ * (long long)sizeof(T);
+    }
     // ---- pinned words and the scalars that live beside them
     std::memset(cg_host_, 0, 2 * sizeof(CgState<T>));
     std::memset((void*)ticket_, 0xff, 64);
@@ -2926,6 +2946,7 @@ class Engine : public EngineBase {
       SIPX_HIP(hipStreamSynchronize(stream_));
       host_prefault(x, N * sizeof(T));
       SIPX_HIP(hipMemcpy(x, exch, N * sizeof(T), hipMemcpyDeviceToHost));
+      io_d2h_ += N * (long long)sizeof(T);
     }
     for (int i = 0; i < p_n_; ++i)
       for (int which = 0; which < 2; ++which) {
@@ -2955,12 +2976,106 @@ class Engine : public EngineBase {
     if (x) {
       host_prefault(x, Nx_ * sizeof(T));
       SIPX_HIP(hipMemcpy(x, x_, Nx_ * sizeof(T), hipMemcpyDeviceToHost));
+      io_d2h_ += Nx_ * (long long)sizeof(T);
     }
     for (int i = 0; i < p_n_; ++i) {
       if (!sets_[i].owned) continue;
       if (l && l[i]) download_rows(sets_[i], sets_[i].l, (T*)l[i]);
       if (y && y[i]) download_rows(sets_[i], sets_[i].y, (T*)y[i]);
     }
+  }
+
+  // ------------------------------------------------------------------------------------------
+  // Device-resident boundary: m, x0, l0[i], y0[i] and the results x, l[i], y[i] are buffers of the caller on this context's GPU,
+  // in the reference's row order.  A call that uses PARSDMM as a projector inside a loop whose data lives on the device
+  // (examples/constrained_freq_FWI_simple.jl:468) then moves no N-vector over PCIe.  finalize / reset run as in the host form
+  // -- same arrays, same values in the same places, so the solve that follows returns the same bits -- with the uploads
+  // replaced by ONE launch that reads the caller's buffers (import_dev); download_dev is one launch that writes them.
+  // Ordering: the import waits for an event recorded on the caller's stream, the export records an event the caller's stream
+  // waits for; neither waits on the host (sipx_finalize / sipx_reset end with the host wait of the initial feasibility, as ever).
+  void need_dev_io(const char* what) const {
+    if (comm_ || slab_req_ || !owned_.empty())
+      throw std::runtime_error(std::string(what) + " takes single-process contexts only: this one is slab-decomposed or set-sharded (use the host form)");
+  }
+  void set_caller_stream(void* stream) override {
+    SIPX_HIP(hipSetDevice(device_));
+    caller_ = (hipStream_t)stream;                      // null: the default stream
+    if (!ev_io_in_) SIPX_HIP(hipEventCreateWithFlags(&ev_io_in_, hipEventDisableTiming));
+    if (!ev_io_out_) SIPX_HIP(hipEventCreateWithFlags(&ev_io_out_, hipEventDisableTiming));
+  }
+  void io_bytes(int64_t* host_to_device, int64_t* device_to_host, int reset) override {
+    if (host_to_device) *host_to_device = io_h2d_;
+    if (device_to_host) *device_to_host = io_d2h_;
+    if (reset) io_h2d_ = io_d2h_ = 0;
+  }
+  // the engine stream goes on once the caller's stream has reached this point / the caller's stream once the engine stream has
+  void engine_after_caller() {
+    if (!ev_io_in_) set_caller_stream((void*)caller_);
+    SIPX_HIP(hipEventRecord(ev_io_in_, caller_));
+    SIPX_HIP(hipStreamWaitEvent(stream_, ev_io_in_, 0));
+  }
+  void caller_after_engine() {
+    SIPX_HIP(hipEventRecord(ev_io_out_, stream_));
+    SIPX_HIP(hipStreamWaitEvent(caller_, ev_io_out_, 0));
+  }
+  void io_add(IoArgs<T>& A, bool pack, int dir, long long nrows, const T* rows, const T* pad) {
+    if (nrows <= 0) return;
+    if (A.nseg == IO_MAXSEG) {           // (more than 32 operator blocks in one call: another launch)
+      io_rows<T>(stream_, A, pack, NB);
+      A.nseg = 0;
+    }
+    io_seg_shape<T>(A.seg[A.nseg++], G_, dir, nrows, rows, pad);
+  }
+  void io_add_set(IoArgs<T>& A, bool pack, const SetState<T>& s, const T* rows, const T* dev) {
+    if (s.ident || s.custom) { io_add(A, pack, -1, s.Mtrue, rows, dev); return; }
+    long long r0 = 0;
+    for (int q = 0; q < s.nblk; ++q) {
+      io_add(A, pack, s.dir[q], s.blk_rows[q], rows + r0, dev + (long long)q * G_.N);
+      r0 += s.blk_rows[q];
+    }
+  }
+  // m, and the warm start where there is one, from the caller's buffers into the (zero-filled) arrays of the context
+  void import_dev(const void* m, const void* x0, const void* const* l0, const void* const* y0) {
+    engine_after_caller();
+    IoArgs<T> A;
+    io_add(A, false, -1, G_.N, (const T*)m, m_);
+    if (x0) io_add(A, false, -1, Nx_, (const T*)x0, x_);
+    for (int i = 0; i < p_n_; ++i) {
+      const SetState<T>& s = sets_[i];
+      if (l0 && l0[i]) io_add_set(A, false, s, (const T*)l0[i], s.l);
+      if (y0 && y0[i]) io_add_set(A, false, s, (const T*)y0[i], s.y);
+    }
+    io_rows<T>(stream_, A, false, NB);
+  }
+  void finalize_dev(const void* m, const double* rho_ini, int n_rho, double gamma_ini, int feasibility_only, int zero_ini_guess,
+                    const void* x0, const void* const* l0, const void* const* y0, double* feasibility_initial) override {
+    need_dev_io("sipx_finalize_dev");
+    if (!m) throw std::runtime_error("sipx_finalize_dev: m is a null pointer");
+    DevIoGuard g(&dev_io_);
+    finalize(m, rho_ini, n_rho, gamma_ini, feasibility_only, zero_ini_guess, x0, l0, y0, feasibility_initial);
+  }
+  void reset_dev(const void* m, const double* rho_ini, int n_rho, double gamma_ini, int zero_ini_guess, const void* x0,
+                 const void* const* l0, const void* const* y0, double* feasibility_initial) override {
+    need_final();
+    need_dev_io("sipx_reset_dev");
+    if (!m) throw std::runtime_error("sipx_reset_dev: m is a null pointer");       // (before anything of the context is zeroed)
+    DevIoGuard g(&dev_io_);
+    reset(m, rho_ini, n_rho, gamma_ini, zero_ini_guess, x0, l0, y0, feasibility_initial);
+  }
+  void download_dev(void* x, void* const* l, void* const* y) override {
+    need_final();
+    need_dev_io("sipx_download_dev");
+    SIPX_HIP(hipSetDevice(device_));
+    engine_after_caller();                // (whatever the caller's stream still does with the result buffers comes first)
+    IoArgs<T> A;
+    if (x) io_add(A, true, -1, Nx_, (const T*)x, x_);
+    for (int i = 0; i < p_n_; ++i) {
+      const SetState<T>& s = sets_[i];
+      if (l && l[i]) io_add_set(A, true, s, (const T*)l[i], s.l);
+      if (y && y[i]) io_add_set(A, true, s, (const T*)y[i], s.y);
+    }
+    io_rows<T>(stream_, A, true, NB);
+    caller_after_engine();
   }
 
   // ------------------------------------------------------------------------------------------
@@ -4063,6 +4178,7 @@ class Engine : public EngineBase {
   // Import / export between the reference's row order (host) and the padded layout (device): one contiguous PCIe
   // copy plus a device gather / scatter per operator block (the pads keep the zeros they were allocated with).
   void upload_rows(const SetState<T>& s, const T* rows, T* dev) const {
+    io_h2d_ += s.Mtrue * (long long)sizeof(T);
     if (s.ident || s.custom) {
       SIPX_HIP(hipMemcpy(dev, rows, (size_t)s.Mtrue * sizeof(T), hipMemcpyHostToDevice));
       return;
@@ -4089,6 +4205,7 @@ class Engine : public EngineBase {
     dfree(full);
   }
   void download_rows(const SetState<T>& s, const T* dev, T* rows) const {
+    io_d2h_ += s.Mtrue * (long long)sizeof(T);
     SIPX_HIP(hipStreamSynchronize(stream_));
     if (s.ident || s.custom) {
       host_prefault(rows, (size_t)s.Mtrue * sizeof(T));
@@ -4268,6 +4385,17 @@ class Engine : public EngineBase {
   Run run_;
   int device_ = 0, ndim_ = 2;
   hipStream_t stream_ = nullptr;
+  // device-resident boundary: the caller's stream and the two events that order it against the engine stream; whether the call
+  // in progress reads device buffers; bytes of the N-sized host transfers of finalize / reset / download (sipx_io_bytes)
+  hipStream_t caller_ = nullptr;
+  hipEvent_t ev_io_in_ = nullptr, ev_io_out_ = nullptr;
+  bool dev_io_ = false;
+  mutable long long io_h2d_ = 0, io_d2h_ = 0;
+  struct DevIoGuard {
+    bool* f;
+    explicit DevIoGuard(bool* flag) : f(flag) { *f = true; }
+    ~DevIoGuard() { *f = false; }
+  };
   Grid G_;
   T ih_[3];
   std::vector<SetState<T>> sets_;

@@ -31,6 +31,16 @@ struct EngineBase {
   virtual void q_update(const double* rho_new, const double* rho_old) = 0;
   virtual void download(void* x, void* const* l, void* const* y) = 0;
   virtual void warm_start_from(EngineBase* coarse) = 0;
+  // device-resident forms of finalize / reset / download: every vector pointer is device memory of the context's GPU, the
+  // work is ordered against the caller's stream (set_caller_stream), no N-vector visits the host
+  virtual void finalize_dev(const void* m, const double* rho_ini, int n_rho, double gamma_ini, int feasibility_only,
+                            int zero_ini_guess, const void* x0, const void* const* l0, const void* const* y0,
+                            double* feasibility_initial) = 0;
+  virtual void reset_dev(const void* m, const double* rho_ini, int n_rho, double gamma_ini, int zero_ini_guess, const void* x0,
+                         const void* const* l0, const void* const* y0, double* feasibility_initial) = 0;
+  virtual void download_dev(void* x, void* const* l, void* const* y) = 0;
+  virtual void set_caller_stream(void* stream) = 0;
+  virtual void io_bytes(int64_t* host_to_device, int64_t* device_to_host, int reset) = 0;
   virtual void parsdmm(const sipx_options* opt, sipx_log* log) = 0;
   virtual void parsdmm_begin(const sipx_options* opt, sipx_log* log) = 0;
   virtual bool parsdmm_step() = 0;

@@ -606,6 +606,29 @@ template <typename T>
 void resample_nn_padded(hipStream_t s, const long long* nc, const long long* nf, const long long* cc, const long long* cf, long long e0,
                         long long e1, const T* in, T* out);
 
+// One launch moves every vector of a device-resident call between the caller's buffers (row order) and the padded arrays
+// (kernels_io.hip).  A segment: `nrows` rows of one operator block (extents d0 x d1 x . of the rows, n0 x n1 x . of the grid);
+// linear: both layouts coincide; vec: 16-byte accesses fit; blk0: its first workgroup (io_rows deals them).
+constexpr int IO_MAXSEG = 32;     // segments held in the arguments of one launch
+template <typename T>
+struct IoSeg {
+  T* rows;
+  T* pad;
+  unsigned nrows, d0, d1, n0, n1, blk0, linear, vec;
+};
+template <typename T>
+struct IoArgs {
+  int nseg = 0;
+  unsigned nblocks = 0;
+  IoSeg<T> seg[IO_MAXSEG];
+};
+// dir: direction of the block's difference operator, < 0 for a whole vector (identity, caller-supplied operator, m, x)
+template <typename T>
+void io_seg_shape(IoSeg<T>& S, const Grid& g, int dir, long long nrows, const T* rows, const T* pad);
+// pack: rows <- pad; otherwise pad <- rows.  max_blocks: workgroups of the launch (at least one per segment)
+template <typename T>
+void io_rows(hipStream_t s, IoArgs<T>& A, bool pack, int max_blocks);
+
 #define SIPX_HIP(expr)                                                                       \
   do {                                                                                       \
     hipError_t _e = (expr);                                                                  \

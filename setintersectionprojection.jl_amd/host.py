@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "sipx_rccl_unique_id", "sipx_set_comm_rccl", "sipx_set_comm", "sipx_slab", "sipx_warm_start_from", "sipx_set_decomp",
     "sipx_kernel_stats_json", "sipx_comm_info", "sipx_device_bytes", "sipx_reset", "sipx_dwt",
     "sipx_learn_observations",
+    "sipx_finalize_dev", "sipx_reset_dev", "sipx_download_dev", "sipx_set_caller_stream", "sipx_io_bytes",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
@@ -746,6 +747,89 @@ class Context:
         self.feasibility_initial = feas[:npp]
         return self.feasibility_initial
 
+    # ---- device-resident forms (sipx_finalize_dev / sipx_reset_dev / sipx_download_dev): torch tensors on this context's GPU ----
+    def set_caller_stream(self, stream):
+        """The stream the caller's tensors are produced and consumed on (a hipStream_t as an integer, e.g.
+        torch.cuda.current_stream().cuda_stream; 0 / None: the default stream).  The device-resident calls order themselves against it."""
+        _chk(lib().sipx_set_caller_stream(self.h, C.c_void_p(int(stream or 0))))
+
+    def io_bytes(self, reset=False):
+        """(host-to-device, device-to-host) bytes of the N-sized transfers finalize, reset and download have made (sipx_io_bytes)."""
+        a, b = C.c_int64(), C.c_int64()
+        _chk(lib().sipx_io_bytes(self.h, C.byref(a), C.byref(b), int(bool(reset))))
+        return a.value, b.value
+
+    def _dev_args(self, m, x0, l0, y0, rows_all):
+        import torch
+        dev = m.device
+        _check_tensor("m", m, self.TF, self.N, dev)
+        if x0 is not None:
+            _check_tensor("x", x0, self.TF, self.Nx, dev)
+        keep = [m, x0]
+
+        def ptr_list(name, lst):
+            if lst is None or len(lst) == 0:
+                return None
+            _check_tensor_list(name, lst, self.TF, rows_all, dev)
+            keep.extend(lst)
+            return (C.c_void_p * len(lst))(*[t.data_ptr() for t in lst])
+        self.set_caller_stream(torch.cuda.current_stream(dev).cuda_stream)
+        return (C.c_void_p(m.data_ptr()), None if x0 is None else C.c_void_p(x0.data_ptr()), ptr_list("l", l0), ptr_list("y", y0), keep)
+
+    def finalize_dev(self, m, rho_ini, gamma_ini, feasibility_only=False, zero_ini_guess=True, x0=None, l0=None, y0=None):
+        """finalize with m and the warm start as torch tensors on this context's GPU, ordered against torch's current stream."""
+        rho = np.ascontiguousarray(rho_ini, np.float64)
+        npp = len(self.rows)
+        feas = np.zeros(max(npp, 1))
+        rows_all = list(self.rows) + ([] if feasibility_only else [self.N])
+        mp, xp, lp, yp, keep = self._dev_args(m, x0, l0, y0, rows_all)
+        _chk(lib().sipx_finalize_dev(self.h, mp, rho.ctypes.data_as(C.c_void_p), len(rho), C.c_double(gamma_ini),
+                                     int(feasibility_only), int(zero_ini_guess), xp, lp, yp, feas.ctypes.data_as(C.c_void_p)))
+        p, pp = C.c_int(), C.c_int()
+        _chk(lib().sipx_num_terms(self.h, C.byref(p), C.byref(pp)))
+        self.p, self.pp = p.value, pp.value
+        if self.p > npp:
+            self.rows.append(self.N)
+        return feas[:npp]
+
+    def reset_dev(self, m, rho_ini, gamma_ini, zero_ini_guess=True, x0=None, l0=None, y0=None):
+        """reset with m and the warm start as torch tensors on this context's GPU, ordered against torch's current stream."""
+        rho = np.ascontiguousarray(rho_ini, np.float64)
+        npp = self.pp
+        feas = np.zeros(max(npp, 1))
+        mp, xp, lp, yp, keep = self._dev_args(m, x0, l0, y0, list(self.rows))
+        _chk(lib().sipx_reset_dev(self.h, mp, rho.ctypes.data_as(C.c_void_p), len(rho), C.c_double(gamma_ini),
+                                  int(zero_ini_guess), xp, lp, yp, feas.ctypes.data_as(C.c_void_p)))
+        self.feasibility_initial = feas[:npp]
+        return self.feasibility_initial
+
+    def download_dev(self, device, want_ly=True, out=None):
+        """x, l, y as torch tensors on `device` (this context's GPU), written on the engine stream; torch's current stream waits
+        for them by an event, the host does not.  out = (x, l, y): preallocated tensors that are filled and returned."""
+        import torch
+        dt = torch.float32 if self.TF == np.float32 else torch.float64
+        ox, ol, oy = (None, None, None) if out is None else out
+        if ox is None:
+            ox = torch.empty(self.Nx, dtype=dt, device=device)
+        else:
+            _check_tensor("out x", ox, self.TF, self.Nx, device)
+        res = [ox]
+        for name, lst in (("out l", ol), ("out y", oy)):
+            if not want_ly:
+                res.append(None)
+            elif lst is None:
+                res.append([torch.empty(r, dtype=dt, device=device) for r in self.rows])
+            else:
+                _check_tensor_list(name, lst, self.TF, self.rows, device)
+                res.append(lst)
+        x, l, y = res
+
+        def ptrs(lst):
+            return None if lst is None else (C.c_void_p * len(lst))(*[t.data_ptr() for t in lst])
+        self.set_caller_stream(torch.cuda.current_stream(device).cuda_stream)
+        _chk(lib().sipx_download_dev(self.h, C.c_void_p(x.data_ptr()), ptrs(l), ptrs(y)))
+        return x, l, y
+
     # ---- phases ----
     def rhs_compose(self, rho):
         rho = np.ascontiguousarray(rho, np.float64)
@@ -1035,6 +1119,142 @@ def PARSDMM(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x=None, l=None, 
     if x is not None and xo is not x and len(x) == len(xo):
         x[:] = xo                         # the reference overwrites the x argument in place
         xo = x
+    return xo, log, lo, yo
+
+
+# --------------------------------------------------------------------------------------------------
+# the device-resident form of the whole solve
+# --------------------------------------------------------------------------------------------------
+def _tensor_TF(name, t):
+    """Working precision of a torch tensor (checked without importing torch: by the names of its type and dtype)."""
+    if type(t).__module__.split(".")[0] != "torch" or not hasattr(t, "data_ptr"):
+        raise SipxError(f"{name} must be a torch tensor on a GPU (PARSDMM takes numpy arrays)")
+    TF = {"torch.float32": np.float32, "torch.float64": np.float64}.get(str(t.dtype))
+    if TF is None:
+        raise SipxError(f"{name} must be Float32 or Float64, not {t.dtype}")
+    return TF
+
+
+def _check_tensor(name, t, TF, length, device):
+    if _tensor_TF(name, t) != np.dtype(TF).type:
+        raise SipxError(f"{name} has dtype {t.dtype}: not the working precision ({np.dtype(TF).name})")
+    if not t.is_cuda:
+        raise SipxError(f"{name} must live on a GPU, not on {t.device}")
+    if device is not None and t.device != device:
+        raise SipxError(f"{name} lives on {t.device}, m on {device}")
+    if t.dim() != 1:
+        raise SipxError(f"{name} must be 1-D, not of shape {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise SipxError(f"{name} must be contiguous (strided tensors are not taken)")
+    if t.shape[0] != length:
+        raise SipxError(f"{name} has {t.shape[0]} entries, {length} are needed")
+
+
+def _check_tensor_list(name, lst, TF, rows, device):
+    if not isinstance(lst, (list, tuple)) or len(lst) != len(rows):
+        raise SipxError(f"{name} needs one vector per term (sets plus the distance term): {len(rows)}, not "
+                        f"{len(lst) if isinstance(lst, (list, tuple)) else type(lst).__name__}")
+    for i, t in enumerate(lst):
+        _check_tensor(f"{name}[{i}]", t, TF, rows[i], device)
+
+
+_one_runtime_checked = False
+
+
+def _check_one_hip_runtime():
+    """torch wheels bring a HIP runtime of their own.  Imported BEFORE libsipx.so is loaded, torch's copy serves both (the
+    loader matches the library name); the other way round the process holds two runtimes, and a stream or a buffer of one means
+    nothing to the other.  Looked at once per process."""
+    global _one_runtime_checked
+    if _one_runtime_checked:
+        return
+    lib()
+    try:
+        with open("/proc/self/maps") as f:
+            paths = {ln.split()[-1] for ln in f if "libamdhip64" in ln}
+    except OSError:
+        paths = set()
+    if len(paths) > 1:
+        raise SipxError("two HIP runtimes are loaded in this process (" + ", ".join(sorted(paths)) + "): torch tensors cannot be "
+                        "shared with the engine.  Import torch before the first call into sipx")
+    _one_runtime_checked = True
+
+
+def PARSDMM_device(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x=None, l=None, y=None, outputs="all", out=None):
+    """PARSDMM for data that lives on the GPU: m, x, l[i], y[i] are 1-D contiguous torch tensors of the working precision on one
+    ROCm device (taken from m), in the reference's row order; returns (x, log_PARSDMM, l, y) with tensors on that device
+    (l, y = None with outputs="x").  No vector crosses PCIe and the host waits for nothing but the solve: the call orders itself
+    against torch.cuda.current_stream(m.device) -- whatever that stream has queued before the call is seen, and work queued on
+    it afterwards sees the results.  out = (x, l, y) supplies preallocated result tensors (l, y may be None with outputs="x"),
+    which are filled and returned, so that a loop allocates nothing.  Contexts are cached as for PARSDMM (the same keys: a
+    host-form and a device-form call of one problem share a context); the solve and its log are those of PARSDMM, bit for bit."""
+    import time
+    t0 = time.perf_counter()
+    if outputs not in ("all", "x"):
+        raise SipxError("outputs must be 'all' or 'x'")
+    # ---- everything that can be wrong with the arguments, before the library is touched
+    TF = _tensor_TF("m", m)
+    n, _ = _grid(comp_grid)
+    N = int(np.prod(n))
+    pp, p = len(P_sub), len(TD_OP)
+    if (not options.feasibility_only and p != pp + 1) or (options.feasibility_only and p != pp):
+        raise SipxError("TD_OP must hold one operator per set plus the identity of the distance term "
+                        "(output of PARSDMM_precompute_distribute)")
+    Nx = 2 * N if any(int(getattr(A, "component", 0)) for A in TD_OP) else N
+    rows = [int(A.shape[0]) for A in TD_OP]
+    dev = m.device
+    _check_tensor("m", m, TF, N, None)
+    if x is not None:
+        _check_tensor("x", x, TF, Nx, dev)
+    for name, lst in (("l", l), ("y", y)):
+        if lst is not None:
+            _check_tensor_list(name, lst, TF, rows, dev)
+    if out is not None:
+        if not isinstance(out, (list, tuple)) or len(out) != 3:
+            raise SipxError("out must be (x, l, y): the result tensors (l, y may be None with outputs='x')")
+        if out[0] is not None:
+            _check_tensor("out x", out[0], TF, Nx, dev)
+        for name, lst in (("out l", out[1]), ("out y", out[2])):
+            if lst is not None and outputs == "all":
+                _check_tensor_list(name, lst, TF, rows, dev)
+    import torch
+    _check_one_hip_runtime()
+    device = dev.index if dev.index is not None else torch.cuda.current_device()
+    dev = torch.device("cuda", device)
+    limit = _cache_limit()
+    key = _context_key(np.empty(0, TF), AtA, TD_OP, set_Prop, P_sub, comp_grid, options, device) if limit > 0 else None
+    ctx = _ctx_cache.pop(key, None) if key is not None else None
+    reused = ctx is not None
+    zero = bool(options.zero_ini_guess)
+    rho_ini = [float(TF(r)) for r in options.rho_ini]
+    warm = (None, None, None) if zero else (x, l, y)
+    try:
+        if reused:
+            ctx.reset_dev(m, rho_ini, float(TF(options.gamma_ini)), zero, *warm)
+        else:
+            ctx = Context(comp_grid, TF, device)
+            for i in range(pp):
+                A = AtA[i] if AtA is not None else None
+                ctx.add_set(TD_OP[i], P_sub[i], set_Prop.ncvx[i], A, set_Prop.AtA_offsets[i] if A is not None else None)
+            ctx.set_q_mode(getattr(options, "Q_mode", "cds"))
+            ctx.feasibility_initial = ctx.finalize_dev(m, rho_ini, float(TF(options.gamma_ini)), options.feasibility_only, zero, *warm)
+        t_init = time.perf_counter() - t0
+        log, _ = ctx.parsdmm(options)
+        log.timing[TIMING_SECTIONS[0]] = t_init
+        if out is None and x is not None:
+            out = (x, None, None)                     # the reference overwrites the x argument in place
+        xo, lo, yo = ctx.download_dev(dev, want_ly=(outputs == "all"), out=out)
+    except Exception:
+        if ctx is not None:
+            ctx.close()
+        raise
+    if key is not None:
+        while len(_ctx_cache) >= limit:
+            _ctx_cache.pop(next(iter(_ctx_cache))).close()
+        _ctx_cache[key] = ctx
+    else:
+        ctx.close()
+    log.context_reused = reused
     return xo, log, lo, yo
 
 
