@@ -1,5 +1,6 @@
 // extern "C" surface of libsipx.so (see include/sipx.h).  Exceptions never cross the ABI:
-// every entry returns 0 / non-zero and leaves the text in sipx_last_error().
+// every entry returns 0 / non-zero and leaves the text in sipx_last_error().  Every entry that begins something refreshes the table
+// of SIPX_* switches (env_knobs.h) before anything reads it; sipx_finalize does so inside Engine::finalize.
 #include <string>
 
 #include "comm.h"
@@ -32,6 +33,7 @@ int sipx_create(sipx_ctx** out, int dtype, int ndim, const int64_t* n, const dou
   SIPX_TRY({
     if (!out) throw std::runtime_error("null output handle");
     *out = nullptr;
+    sipx::refresh_env_knobs();      // (the constructor reads switches: env_knobs.h)
     sipx::EngineBase* e = sipx::make_engine(dtype, ndim, n, h, device);
     *out = new sipx_ctx{e};
   })
@@ -65,7 +67,7 @@ int sipx_finalize(sipx_ctx* c, const void* m, const double* rho_ini, int n_rho, 
 }
 int sipx_reset(sipx_ctx* c, const void* m, const double* rho_ini, int n_rho, double gamma_ini, int zero_ini_guess, const void* x0,
                const void* const* l0, const void* const* y0, double* feasibility_initial) {
-  SIPX_TRY(c->e->reset(m, rho_ini, n_rho, gamma_ini, zero_ini_guess, x0, l0, y0, feasibility_initial))
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->reset(m, rho_ini, n_rho, gamma_ini, zero_ini_guess, x0, l0, y0, feasibility_initial))
 }
 int sipx_rhs_compose(sipx_ctx* c, const double* rho) { SIPX_TRY(c->e->rhs_compose(rho)) }
 int sipx_argmin_x(sipx_ctx* c, int it, double* tol_ref_io, int64_t* cg_it, double* cg_relres, int* cg_flag) {
@@ -89,7 +91,7 @@ int sipx_finalize_dev(sipx_ctx* c, const void* m, const double* rho_ini, int n_r
 }
 int sipx_reset_dev(sipx_ctx* c, const void* m, const double* rho_ini, int n_rho, double gamma_ini, int zero_ini_guess,
                    const void* x0, const void* const* l0, const void* const* y0, double* feasibility_initial) {
-  SIPX_TRY(c->e->reset_dev(m, rho_ini, n_rho, gamma_ini, zero_ini_guess, x0, l0, y0, feasibility_initial))
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->reset_dev(m, rho_ini, n_rho, gamma_ini, zero_ini_guess, x0, l0, y0, feasibility_initial))
 }
 int sipx_download_dev(sipx_ctx* c, void* x, void* const* l, void* const* y) { SIPX_TRY(c->e->download_dev(x, l, y)) }
 int sipx_set_caller_stream(sipx_ctx* c, void* stream) { SIPX_TRY(c->e->set_caller_stream(stream)) }
@@ -113,21 +115,21 @@ int sipx_parsdmm_steps(sipx_ctx* c, int nsteps, int* done) {
 }
 
 int sipx_cds_spmv(int dtype, int64_t N, int d, const void* R, const int64_t* off, const void* x, void* y, int device) {
-  SIPX_TRY(sipx::cds_spmv_host(dtype, N, d, R, off, x, y, device))
+  SIPX_TRY(sipx::refresh_env_knobs(); sipx::cds_spmv_host(dtype, N, d, R, off, x, y, device))
 }
 int sipx_resample_nn(int dtype, int ndim, const int64_t* nc, const int64_t* nf, const void* in, void* out, int device) {
-  SIPX_TRY(sipx::resample_nn_host(dtype, ndim, nc, nf, in, out, device))
+  SIPX_TRY(sipx::refresh_env_knobs(); sipx::resample_nn_host(dtype, ndim, nc, nf, in, out, device))
 }
 int sipx_dwt(int dtype, int ndim, const int64_t* n, int inverse, const void* in, void* out, int device) {
-  SIPX_TRY(sipx::dwt_host(dtype, ndim, n, inverse, in, out, device))
+  SIPX_TRY(sipx::refresh_env_knobs(); sipx::dwt_host(dtype, ndim, n, inverse, in, out, device))
 }
 int sipx_learn_observations(int dtype, const int64_t* n, const double* h, int64_t n_train, const void* m_train,
                             const int64_t* strides, int64_t max_batch, sipx_observations* out, int device) {
-  SIPX_TRY(sipx::learn_observations_host(dtype, n, h, n_train, m_train, strides, max_batch, out, device))
+  SIPX_TRY(sipx::refresh_env_knobs(); sipx::learn_observations_host(dtype, n, h, n_train, m_train, strides, max_batch, out, device))
 }
 int sipx_apply_op(sipx_ctx* c, int op, const void* x, void* s) { SIPX_TRY(c->e->apply_op(op, x, s, false)) }
 int sipx_apply_op_adj(sipx_ctx* c, int op, const void* v, void* t) { SIPX_TRY(c->e->apply_op(op, v, t, true)) }
-int sipx_project(sipx_ctx* c, const sipx_set_desc* d, void* v, int64_t len) { SIPX_TRY(c->e->project(d, v, len)) }
+int sipx_project(sipx_ctx* c, const sipx_set_desc* d, void* v, int64_t len) { SIPX_TRY(sipx::refresh_env_knobs(); c->e->project(d, v, len)) }
 int sipx_get_Q(sipx_ctx* c, void* Q, int64_t* offsets, int* d) { SIPX_TRY(c->e->get_Q(Q, offsets, d)) }
 int sipx_time_spmv(sipx_ctx* c, int reps, double* avg_ms) { SIPX_TRY(*avg_ms = c->e->time_spmv(reps)) }
 int sipx_kernel_stats(sipx_ctx* c, int enable, int64_t* launches, double* total_ms) {
@@ -150,12 +152,13 @@ void* sipx_dev_rhs(sipx_ctx* c) { return c->e->dev_rhs(); }
 void* sipx_dev_x(sipx_ctx* c) { return c->e->dev_x(); }
 int sipx_get_rhs(sipx_ctx* c, void* rhs) { SIPX_TRY(c->e->get_rhs(rhs)) }
 int sipx_prox_l2s(int dtype, int64_t n, void* x, double rho, const void* m, int device) {
-  SIPX_TRY(sipx::prox_l2s_host(dtype, n, x, rho, m, device))
+  SIPX_TRY(sipx::refresh_env_knobs(); sipx::prox_l2s_host(dtype, n, x, rho, m, device))
 }
 int sipx_set_owned(sipx_ctx* c, const int32_t* owned) { SIPX_TRY(c->e->set_owned(owned)) }
 int sipx_rccl_unique_id(void* id128) { SIPX_TRY(sipx::rccl_unique_id(id128)) }
 int sipx_set_comm_rccl(sipx_ctx* c, const void* id128, int world, int rank) {
   SIPX_TRY({
+    sipx::refresh_env_knobs();
     c->e->bind_device();      // ncclCommInitRank binds the communicator to the current device
     c->e->set_comm(sipx::make_rccl_comm(id128, world, rank));
   })
@@ -163,6 +166,7 @@ int sipx_set_comm_rccl(sipx_ctx* c, const void* id128, int world, int rank) {
 int sipx_set_comm(sipx_ctx* c, const sipx_comm* comm) {
   SIPX_TRY({
     if (!comm) throw std::runtime_error("null communicator");
+    sipx::refresh_env_knobs();
     c->e->set_comm(sipx::make_callback_comm(comm));
   })
 }

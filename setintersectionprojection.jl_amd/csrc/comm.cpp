@@ -1,5 +1,6 @@
 // Collectives of the sharded solve: RCCL (native, over xGMI) and caller-supplied callbacks.  See comm.h.
 #include "comm.h"
+#include "env_knobs.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -92,8 +93,7 @@ class RcclComm : public Comm {
     // failure.  Any RCCL error during a solve is fatal (nccl_check).
     int v = 0;
     if (rccl().GetVersion) (void)rccl().GetVersion(&v);
-    const char* e = std::getenv("SIPX_COMM_GROUP");
-    grouped_ = v >= 20800 && !(e && e[0] == '0');
+    grouped_ = v >= 20800 && env_knobs().comm_group;
   }
   ~RcclComm() override {
     if (comm_) (void)rccl().CommDestroy(comm_);

@@ -246,7 +246,7 @@ void DistDft<T>::project(T* v, bool feas, Comm* comm, const ChainHooks* hooks, d
   ChainHooks hk = *hooks;
   hk.gbuf = I.sg;
   K<T>::proj_scalars_arr_slab(s, I.n[2] * I.m1 * I.n[0], I.mag, PX_L1, T(0), I.radius_raw, ps, I.sp, I.sm, I.sc, I.N, &hk, I.sc_len, host_ovf);
-  static const bool dbg = getenv("SIPX_DFT_DEBUG") != nullptr;      // the state the search ended in, per rank, on stderr (synchronises)
+  const bool dbg = env_knobs().dft_debug;      // SIPX_DFT_DEBUG: the state the search ended in, per rank, on stderr (synchronises)
   if (dbg) {
     ProjScalars<T> h;
     SIPX_HIP(hipStreamSynchronize(s));

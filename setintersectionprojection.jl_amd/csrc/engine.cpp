@@ -30,21 +30,7 @@ namespace {
 EnvKnobs g_env_knobs;
 }
 const EnvKnobs& env_knobs() { return g_env_knobs; }
-void refresh_env_knobs() {
-  auto num = [](const char* name, long long dflt) { const char* e = std::getenv(name); return e ? std::atoll(e) : dflt; };
-  EnvKnobs k;
-  k.cds_march = (int)num("SIPX_CDS_MARCH", 1);
-  k.cds_march_zchunk = num("SIPX_CDS_MARCH_ZCHUNK", 0);
-  k.multi_zchunk = num("SIPX_MULTI_ZCHUNK", 0);
-  k.rhs_march = (int)num("SIPX_RHS_MARCH", 1);
-  k.rhs_march_zchunk = num("SIPX_RHS_MARCH_ZCHUNK", 0);
-  k.q_plan = (int)num("SIPX_Q_PLAN", 1);
-  k.q_table = (int)num("SIPX_Q_TABLE", 1);
-  k.mark_stride = (int)std::max<long long>(0, num("SIPX_MARK_STRIDE", 0));
-  k.trace_searches = (int)num("SIPX_TRACE_SEARCHES", 0);
-  k.trace_kernels = (int)num("SIPX_TRACE_KERNELS", 0);
-  g_env_knobs = k;
-}
+void refresh_env_knobs() { g_env_knobs = read_env_knobs(); }
 long long*& alloc_tally() {
   static thread_local long long* t = nullptr;
   return t;
@@ -195,12 +181,11 @@ inline void* sparse_alloc_bytes(size_t total_bytes, std::vector<std::pair<size_t
 // microseconds per GiB to this.)
 inline void host_prefault(void* p, size_t bytes) {
   constexpr size_t PAGE = 4096, MIN_BYTES = 8u << 20;
-  static const int nthreads = [] {
-    const char* e = std::getenv("SIPX_PREFAULT_THREADS");        // 0: off (A/B switch)
-    if (e) return std::max(0, std::atoi(e));
+  int nthreads = env_knobs().prefault_threads;                      // SIPX_PREFAULT_THREADS (0: off)
+  if (nthreads < 0) {
     const unsigned hc = std::thread::hardware_concurrency();
-    return (int)std::min<unsigned>(16u, hc > 1 ? hc / 2 : 1u);      // (9 GiB: 0.64 s without, 0.34 / 0.27 s with 4 / 16 threads)
-  }();
+    nthreads = (int)std::min<unsigned>(16u, hc > 1 ? hc / 2 : 1u);      // (9 GiB: 0.64 s without, 0.34 / 0.27 s with 4 / 16 threads)
+  }
   if (!p || bytes < MIN_BYTES || nthreads < 1) return;
   char* base = static_cast<char*>(p);
   const size_t first = (PAGE - (reinterpret_cast<uintptr_t>(base) & (PAGE - 1))) & (PAGE - 1);      // first page boundary inside
@@ -399,14 +384,7 @@ class Engine : public EngineBase {
     SIPX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     SIPX_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
     SIPX_HIP(hipEventCreateWithFlags(&ev_fork2_, hipEventDisableTiming));
-    {
-      const char* e = std::getenv("SIPX_SERIAL_SETS");
-      set_streams_ = !(e && e[0] == '1');
-      const char* f = std::getenv("SIPX_CDS_FULL");
-      cds_full_ = f && f[0] == '1';
-      const char* k = std::getenv("SIPX_SET_STREAMS");
-      if (k && std::atoi(k) > 0) { n_set_streams_ = std::atoi(k); set_streams_forced_ = true; }
-    }
+    set_streams_ = env_knobs().serial_sets != 1;
     ndim_ = ndim;
     for (int a = 0; a < 3; ++a) {
       G_.n[a] = a < ndim ? n[a] : 1;
@@ -417,8 +395,8 @@ class Engine : public EngineBase {
     G_.N = G_.n[0] * G_.n[1] * G_.n[2];
     // Up to 2^22 grid points the kernels of the searches are too short for a second stream to hide anything: the cross-stream
     // dependencies (an event wait costs 15-25 us on this stack) outweigh the overlap.  2048^2, C2: 2130 -> 2300 it/s on one
-    // stream; 256^3 gains 6 % from its three.  SIPX_SERIAL_SETS=0 / SIPX_SET_STREAMS=k keep the streams whatever the size.
-    if (G_.N <= (1ll << 22) && !set_streams_forced_ && !std::getenv("SIPX_SERIAL_SETS")) set_streams_ = false;
+    // stream; 256^3 gains 6 % from its three.  SIPX_SERIAL_SETS=0 keeps the streams whatever the size.
+    if (G_.N <= (1ll << 22) && env_knobs().serial_sets < 0) set_streams_ = false;
     G_.st[0] = 1;
     G_.st[1] = G_.n[0];
     G_.st[2] = G_.n[0] * G_.n[1];
@@ -601,12 +579,10 @@ class Engine : public EngineBase {
           throw std::runtime_error("the slab decomposition has no form for a caller-supplied sparse operator (set " + std::to_string(i) + "): use the set decomposition");
         const bool sliced = (s.ext_kind == EXT_RANK || s.ext_kind == EXT_NUCLEAR) && s.spec.mode == SIPX_MODE_SLICE &&
                             s.spec.dir == ndim_ - 1 && s.ident;
-        if (const char* fo = std::getenv("SIPX_FAN_OVERLAP")) fan_overlap_ = fo[0] != '0';
-        const char* gc = std::getenv("SIPX_SLAB_CARD_GATHER");      // 1: cardinality through an owner rank as well (A/B switch, tests)
-        const char* gd = std::getenv("SIPX_SLAB_DFT_GATHER");       // 1: the l1-DFT set through an owner rank (A/B switch, tests)
+        // (SIPX_SLAB_CARD_GATHER=1 / SIPX_SLAB_DFT_GATHER=1: cardinality / the l1-DFT set through an owner rank as well -- A/B switches, tests)
         if (sliced) s.slab_ext = true;
-        else if (s.prox == PX_CARD && !s.ext_kind && !(gc && gc[0] == '1')) s.slab_card = true;
-        else if (s.ext_kind == EXT_L1_DFT && ndim_ == 3 && s.ident && G_.n[0] >= 2 && !(gd && gd[0] == '1')) s.slab_dft = true;
+        else if (s.prox == PX_CARD && !s.ext_kind && !env_knobs().slab_card_gather) s.slab_card = true;
+        else if (s.ext_kind == EXT_L1_DFT && ndim_ == 3 && s.ident && G_.n[0] >= 2 && !env_knobs().slab_dft_gather) s.slab_dft = true;
         else if (s.ext_kind || s.prox == PX_CARD) { s.fan = true; s.fan_owner = (nfan++) % comm_->world; }
         if (s.fan && s.nblk > 1) throw std::runtime_error("internal: a gathered set with more than one operator block");
         slab_loose_ |= s.slab_ext || s.fan || s.slab_card || s.slab_dft;
@@ -671,16 +647,13 @@ class Engine : public EngineBase {
     wlo_ = -halo_; whi_ = Npad + halo_;
     bool sparse_wanted = false;
     if (slab_ && !slab_full_req_) {
-      const char* e = std::getenv("SIPX_SLAB_LOCAL");        // 0: full-size arrays on every rank, as before (A/B switch)
       int vmm = 0;
       (void)hipDeviceGetAttribute(&vmm, hipDeviceAttributeVirtualMemoryManagementSupported, device_);
-      sparse_wanted = vmm != 0 && !(e && e[0] == '0');
+      sparse_wanted = vmm != 0 && env_knobs().slab_local;        // SIPX_SLAB_LOCAL=0: full-size arrays on every rank, as before (A/B switch)
       for (const auto& st : sets_)
         if (st.prox == PX_BOUNDS_VEC || (!st.two_pass && st.nblk > 0) || !st.host_ata.empty()) sparse_wanted = false;
       // (lists with materialised sets keep sparse arrays too: their vectors are addressed by global index -- loose_v_ / loose_w_ --
-      //  and whole only on the rank that projects a gathered set.  SIPX_SLAB_LOOSE_SPARSE=0: whole arrays for such lists, A/B switch)
-      if (slab_loose_)
-        if (const char* ls = std::getenv("SIPX_SLAB_LOOSE_SPARSE")) if (ls[0] == '0') sparse_wanted = false;
+      //  and whole only on the rank that projects a gathered set)
     }
     if (comm_) {                                            // (every rank takes the same branch: the verdict is all-reduced)
       bool any_dft = false;
@@ -699,8 +672,8 @@ class Engine : public EngineBase {
     // self-test's plain buffer and all of them throw together (bench.py then falls back to the next decomposition on every rank).
     std::string alloc_err;
     try {
-    if (const char* f = std::getenv("SIPX_FINALIZE_FAIL_RANK"))       // tests: this rank "runs out of memory"
-      if (comm_ && std::atoi(f) == comm_->rank) throw std::runtime_error("test hook: out of device memory");
+    if (comm_ && env_knobs().finalize_fail_rank == comm_->rank)       // SIPX_FINALIZE_FAIL_RANK (tests): this rank "runs out of memory"
+      throw std::runtime_error("test hook: out of device memory");
     if (slab_ && !slab_full_req_) {
       slab_local_ = sparse_wanted && !selftest_mapped_failed_;
       for (const auto& st : sets_) {
@@ -729,11 +702,11 @@ class Engine : public EngineBase {
       // CG iterations from the second on as ONE kernel (scalar step + product on p = r + beta p_old formed on the fly,
       // k_cds_fused): one launch and a host round trip less per iteration -- what a launch-bound grid (2048^2) is made of --
       // against a product that reads two vectors instead of one.  SIPX_CG_FUSED=0 / 1 forces it off / on.
-      const char* e = std::getenv("SIPX_CG_FUSED");
+      const int forced = env_knobs().cg_fused;
       const bool small = Nx_ <= (1ll << 23);
       // (the z-marching product has a fused form of its own, k_cds_march<MODE 3>: there the fusion also saves traffic -- 8 N w
       //  instead of the 9 of product + p-update -- so it is the default at every size for the matrices the march takes)
-      cg_fused_ = !comm_ && !stencil_q_ && (e ? e[0] == '1' : (small || cds_.march != 0));
+      cg_fused_ = !comm_ && !stencil_q_ && (forced >= 0 ? forced == 1 : (small || cds_.march != 0));
       if (cg_fused_) { p2_base_ = dalloc<T>(Nx_ + 2 * halo_); p2_ = p2_base_ + halo_; }
     }
     {
@@ -748,16 +721,12 @@ class Engine : public EngineBase {
       // x0 mode of the one-sweep update: when EVERY y/l update of this context goes through the sweep (its block layout is
       // compiled in, no set needs the per-set kernels on feasibility iterations), s_0 = A x_0 is recomputed from a snapshot of
       // x instead of being stored per set: two N-vectors instead of one M_i-vector per set, and 8 N w less traffic on every
-      // Barzilai-Borwein iteration of the headline list.  SIPX_X0_SNAPSHOT=0 keeps the per-set s_0 arrays (A/B switch, tests).
-      const char* e = std::getenv("SIPX_X0_SNAPSHOT");
-      const char* mu = std::getenv("SIPX_YL_MULTI");            // 0: one k_yl launch per set on every iteration (A/B switch, tests)
-      yl_multi_ = !(mu && mu[0] == '0');
-      if (const char* ra = std::getenv("SIPX_RESID_AHEAD")) resid_ahead_ = ra[0] != '0';      // A/B switch
+      // Barzilai-Borwein iteration of the headline list.  (A list the sweep does not take whole keeps the per-set s_0 arrays.)
+      yl_multi_ = env_knobs().yl_multi;            // SIPX_YL_MULTI=0: one k_yl launch per set on every iteration (A/B switch, tests)
       // the lean first passes of the l1 searches in one sweep: pays where the re-reads of x are real traffic (512^3, settled
       // iterations: 133 -> 139 it/s); at 256^3 three concurrent per-set passes on their own streams are as fast or faster
       // (1028 against 1012 it/s settled, default window equal), so it is the default above 2^24 grid points only
-      lean_multi_ = G_.N > (1ll << 24);
-      if (const char* lm = std::getenv("SIPX_LEAN_MULTI")) lean_multi_ = lm[0] != '0';         // A/B switch, tests
+      lean_multi_ = env_knobs().lean_multi >= 0 ? env_knobs().lean_multi != 0 : G_.N > (1ll << 24);      // SIPX_LEAN_MULTI: A/B switch, tests
       {
         // which sets the sweep takes: all of them (the layouts of C2 / C3 / C5 and of the short lists), or -- one rank only -- the
         // element-wise and l1 / l2 terms of a list with sets it cannot take (C4), provided the layout of that subset is compiled in
@@ -768,23 +737,17 @@ class Engine : public EngineBase {
           st.in_sweep = any_sweep && sweep_eligible(st);
           has_loose_ |= any_sweep && st.owned && !st.in_sweep;
         }
-        const char* sp = std::getenv("SIPX_SWEEP_PARTIAL");      // 0: such lists keep one k_yl launch per set (A/B switch, tests)
-        if (has_loose_ && sp && sp[0] == '0') {
-          for (auto& st : sets_) st.in_sweep = false;
-          has_loose_ = false;
-          yl_multi_ = false;
-        }
         sweep_partial_ = has_loose_;
       }
       MultiArgs<T> probe;
-      x0_mode_ = !(e && e[0] == '0') && !has_loose_ && sweep_applicable(SIPX_YL_FEAS | SIPX_YL_BB, probe, true);
+      x0_mode_ = !has_loose_ && sweep_applicable(SIPX_YL_FEAS | SIPX_YL_BB, probe, true);
       // Set streams when the sweep does the updates: all that runs on them is the threshold / scale searches, chains of short
       // kernels whose latencies should overlap -- every searching set a stream of its own (up to three; one of them the engine
       // stream, so that its search starts without a cross-stream dependency), the other sets on the engine stream.  256^3, C3:
       // 715 -> 760 it/s with three instead of two; 512^3 unchanged; four lose (no search left on the engine stream); 2048^2 with
       // its one searching set keeps two.  Without the sweep the per-set y/l kernels run there too: two streams, sets dealt round robin.
       MultiArgs<T> probe2;
-      search_streams_ = !set_streams_forced_ && sweep_applicable(SIPX_YL_BB, probe2, true);
+      search_streams_ = sweep_applicable(SIPX_YL_BB, probe2, true);
       if (search_streams_) {
         int ntp = 0;
         for (const auto& st : sets_) ntp += st.two_pass ? 1 : 0;
@@ -795,13 +758,10 @@ class Engine : public EngineBase {
         // stream (batched_searches) -- no set streams at all.  SIPX_SEARCH_BATCH=0 keeps the per-set chains (A/B switch, tests).
         int ntp = 0;
         for (const auto& st : sets_) ntp += (st.two_pass && st.in_sweep) ? 1 : 0;
-        const char* sb = std::getenv("SIPX_SEARCH_BATCH");
         MultiArgs<T> probe3;
-        search_batch_ = !comm_ && !(sb && sb[0] == '0') && ntp >= 1 && ntp <= SPEC_MAX_SETS &&
+        search_batch_ = !comm_ && env_knobs().search_batch && ntp >= 1 && ntp <= SPEC_MAX_SETS &&
                         sweep_applicable(SIPX_YL_FEAS | SIPX_YL_BB, probe3, true);
         if (search_batch_) set_streams_ = false;
-        if (const char* fs = std::getenv("SIPX_FEAS_SAMPLE")) feas_sample_ = fs[0] != '0';
-        if (const char* pm = std::getenv("SIPX_PASS_MULTI")) pass_multi_ = pm[0] == '1';
       }
       {
         MultiArgs<T> probe4;
@@ -837,8 +797,7 @@ class Engine : public EngineBase {
       // what a search may gather inside its final bracket over ALL ranks (and the size of a rank's full-size exchange segment:
       // the all-gather moves whole segments): 2^17 magnitudes up to 256^3, N / 512 above (512^3: 2^18), at most 2^20
       hooks_.gcap = std::min<long long>(std::min<long long>(1ll << 20, std::max<long long>(1ll << 17, G_.N / 512)), (maxpad + 3) / 4 * 4);
-      if (const char* e = std::getenv("SIPX_GATHER_CAP"))                      // tests: a segment small enough to overflow
-        if (std::atoll(e) >= 4) hooks_.gcap = std::atoll(e) / 4 * 4;
+      if (env_knobs().gather_cap >= 4) hooks_.gcap = env_knobs().gather_cap / 4 * 4;      // SIPX_GATHER_CAP (tests): a segment small enough to overflow
       int n2 = 0, nl1 = 0;
       for (auto& s : sets_) { n2 += s.two_pass ? 1 : 0; nl1 += (s.two_pass && s.prox == PX_L1) ? 1 : 0; }
       // the searches of all sets run in lock step: one staging buffer for their sums (one all-reduce per stage), one exchange
@@ -849,11 +808,7 @@ class Engine : public EngineBase {
       // gathered inside the speculative range: a few thousand magnitudes once theta moves slowly)
       // (a rank's share of what the full-size segment holds, times two for uneven shares; at least 16 K values)
       hooks_.fcap = std::min<long long>(hooks_.gcap, std::max<long long>(1ll << 14, (2 * hooks_.gcap / comm_->world + 3) / 4 * 4));
-      if (const char* e = std::getenv("SIPX_GATHER_FAST_CAP"))
-        if (std::atoll(e) >= 4) hooks_.fcap = std::min<long long>(hooks_.gcap, std::atoll(e) / 4 * 4);
-      if (const char* e = std::getenv("SIPX_SPEC_EXCHANGE")) spec_exchange_ = std::atoi(e) != 0;
-      if (const char* e = std::getenv("SIPX_SPEC_BATCH")) spec_batch_ = std::atoi(e) != 0;
-      if (const char* e = std::getenv("SIPX_SLAB_LEAN_MULTI")) slab_lean_multi_ = std::atoi(e) != 0;
+      if (env_knobs().gather_fast_cap >= 4) hooks_.fcap = std::min<long long>(hooks_.gcap, env_knobs().gather_fast_cap / 4 * 4);      // SIPX_GATHER_FAST_CAP (tests)
       fbuf_ = dalloc<T>((size_t)comm_->world * std::max(n2, 1) * (hooks_.fcap + fast_hdr<T>()));
       stage_ = dalloc<double>((size_t)std::max(n2, 1) * (PREP_SLOTS + 1 + 2 * comm_->world));
       sstage_ = dalloc<double>((size_t)std::max(n2, 1) * (2 * SAMPLE_BINS + 3));
@@ -907,12 +862,6 @@ class Engine : public EngineBase {
     std::memset((void*)hovf_, 0, sizeof(int) * (p_n_ + 1));
     SIPX_HIP(hipHostMalloc((void**)&hverd_, sizeof(unsigned) * (p_n_ + 1), hipHostMallocDefault));
     std::memset((void*)hverd_, 0, sizeof(unsigned) * (p_n_ + 1));
-    {
-      const char* e = std::getenv("SIPX_L1_SAMPLE");
-      l1_sample_ = !(e && e[0] == '0');
-      const char* r = std::getenv("SIPX_L1_SAMPLE_RUNS");       // tests: sample small grids too
-      l1_sample_runs_ = r ? std::atoll(r) : 0;
-    }
     for (int k = 0; k < 2 * MAXMARK; ++k) {      // two sets of section marks: a step never waits for its own timing
       hipEvent_t e;
       SIPX_HIP(hipEventCreate(&e));
@@ -1051,9 +1000,9 @@ class Engine : public EngineBase {
       // small factorisations with host round trips in it (ext_proj.hip), runs on a stream of its own, queued by a host thread of
       // its own, beside the searches, the sweep and the other loose sets on the engine stream; its update only needs x.
       // SIPX_RANK_LANE=0: in turn on the engine stream (A/B switch, tests).
-      const char* ln = std::getenv("SIPX_RANK_LANE");
+      const bool lane_on = env_knobs().rank_lane;
       lane_set_ = -1;
-      if (!comm_ && !mk_ && sweep_partial_ && !(ln && ln[0] == '0'))
+      if (!comm_ && !mk_ && sweep_partial_ && lane_on)
         for (int i = 0; i < p_n_ && lane_set_ < 0; ++i) {
           const SetState<T>& s = sets_[i];
           if (s.owned && !s.in_sweep && !s.dist_ext && s.ident && !s.custom && s.ext && (s.ext_kind == EXT_RANK || s.ext_kind == EXT_NUCLEAR)) lane_set_ = i;
@@ -1062,7 +1011,7 @@ class Engine : public EngineBase {
       // anywhere in its update -- so it takes the same lane, beside the lock-step searches, the sweep and the transform set with
       // their collectives on the engine stream.  A rank's share of C4 is where this pays most: a call on 64 slices is a chain of
       // small launches with host round trips in it that leaves most of the chip idle.
-      if (comm_ && slab_ && slab_loose_ && !mk_ && sweep_partial_ && !(ln && ln[0] == '0'))
+      if (comm_ && slab_ && slab_loose_ && !mk_ && sweep_partial_ && lane_on)
         for (int i = 0; i < p_n_ && lane_set_ < 0; ++i) {
           const SetState<T>& s = sets_[i];
           if (s.owned && !s.in_sweep && s.slab_ext && s.ident && !s.custom && s.ext && (s.ext_kind == EXT_RANK || s.ext_kind == EXT_NUCLEAR)) lane_set_ = i;      // (s.ext: a rank without planes has no projector and nothing to overlap)
@@ -1072,12 +1021,9 @@ class Engine : public EngineBase {
         // queue with the engine stream (streams of one priority are dealt onto four queues in turn; in the slab-decomposed
         // context the lane had landed on the engine stream's queue and ran strictly behind it: tools/lane_overlap.py, 0.00 ms
         // together), and the chain of small launches that is the iteration's critical path does not wait behind the sweep.
-        // SIPX_LANE_PRIORITY=0: a plain stream (A/B switch).
-        const char* lp = std::getenv("SIPX_LANE_PRIORITY");
         int pr_least = 0, pr_greatest = 0;
         SIPX_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-        if (lp && lp[0] == '0') SIPX_HIP(hipStreamCreateWithFlags(&lane_st_, hipStreamNonBlocking));
-        else SIPX_HIP(hipStreamCreateWithPriority(&lane_st_, hipStreamNonBlocking, lp && lp[0] == 'l' ? pr_least : pr_greatest));
+        SIPX_HIP(hipStreamCreateWithPriority(&lane_st_, hipStreamNonBlocking, pr_greatest));
         SIPX_HIP(hipEventCreateWithFlags(&lane_fork_, hipEventDisableTiming));
         SIPX_HIP(hipEventCreateWithFlags(&lane_ev_, hipEventDisableTiming));
         // (slab-decomposed: a vector of the exchange layout addressed by global index, like loose_v_)
@@ -1533,7 +1479,7 @@ class Engine : public EngineBase {
         std::vector<SetArgs<T>> args(tp.size());
         std::vector<T*> gseg(tp.size(), nullptr);
         int k1 = 0;
-        const bool batch = spec_exchange_ && spec_batch_ && (int)tp.size() <= SPEC_MAX_SETS;
+        const bool batch = env_knobs().spec_exchange && (int)tp.size() <= SPEC_MAX_SETS;
         RescaleMulti<T> rs;
         rs.n = 0;
         for (size_t j = 0; j < tp.size(); ++j) {
@@ -1556,9 +1502,9 @@ class Engine : public EngineBase {
           ctl[j].host_want = (int*)hlean_ + tp[j];
           ctl[j].host_ovf = (int*)hovf_ + tp[j];
           ctl[j].compact_cap = sets_[tp[j]].cbuf_len;
-          ctl[j].runs = l1_sample_runs_;
+          ctl[j].runs = env_knobs().l1_sample_runs;
           const bool rescaled = s.prox == PX_L1 && s.last_rho > T(0) && s.last_rho != args[j].rho;
-          ctl[j].enable = l1_sample_ && s.prox == PX_L1 && (rescaled || (hlean_[tp[j]] & 0xff) != 0);
+          ctl[j].enable = env_knobs().l1_sample && s.prox == PX_L1 && (rescaled || (hlean_[tp[j]] & 0xff) != 0);
           any_sample |= ctl[j].enable != 0;
         }
         if (any_sample && batch && Gr_.n[0] % 4 == 0) {      // every sampling set in one launch per stage
@@ -1570,9 +1516,9 @@ class Engine : public EngineBase {
             S.a = args[j]; S.a.ps = sets_[tp[j]].ps; S.ps = sets_[tp[j]].ps; S.partials = sets_[tp[j]].ptmp;
             S.reg = sstage_ + j * SS; S.true_len = sets_[tp[j]].Mtrue;
           }
-          K<T>::sample_multi(10, stream_, Gr_, sm, l1_sample_runs_, &hooks_);
+          K<T>::sample_multi(10, stream_, Gr_, sm, env_knobs().l1_sample_runs, &hooks_);
           comm_->allreduce_sum(sstage_, tp.size() * SS, SIPX_F64, stream_);
-          K<T>::sample_multi(11, stream_, Gr_, sm, l1_sample_runs_, &hooks_);
+          K<T>::sample_multi(11, stream_, Gr_, sm, env_knobs().l1_sample_runs, &hooks_);
         } else if (any_sample) {
           for (int stage = 10; stage <= 11; ++stage) {
             for (size_t j = 0; j < tp.size(); ++j)
@@ -1597,9 +1543,9 @@ class Engine : public EngineBase {
           rounds = std::max(rounds, want);
           s.searches_done += 1;
         }
-        if (const char* e = std::getenv("SIPX_L1_ROUNDS_MIN")) rounds = std::min(6, std::max(rounds, std::atoi(e)));      // a problem whose brackets shrink slowly
-        if (const char* e = std::getenv("SIPX_L1_ROUNDS_MAX")) rounds = std::max(1, std::min(rounds, std::atoi(e)));      // tests: force an overflow
-        if (spec_exchange_) {
+        rounds = std::min(6, std::max(rounds, env_knobs().l1_rounds_min));      // SIPX_L1_ROUNDS_MIN: a problem whose brackets shrink slowly
+        rounds = std::max(1, std::min(rounds, env_knobs().l1_rounds_max));      // SIPX_L1_ROUNDS_MAX (tests): force an overflow
+        if (env_knobs().spec_exchange) {
           spec_exchange_searches(tp, args, ctl, gseg, chunk, 0, false, it, rs.n == 0 && !any_sample);
         } else {
         const int order[4] = {0, 1, 2, 3};
@@ -1627,7 +1573,7 @@ class Engine : public EngineBase {
       for (int i = 0; i < p_n_; ++i)
         if (sets_[i].two_pass) { sets_[i].last_rho = (T)rho[i]; sets_[i].last_gamma = (T)gamma[i]; }
       sweep_launch(flags, rho, gamma, ma);
-      if ((flags & SIPX_YL_FEAS) && spec_exchange_) {
+      if ((flags & SIPX_YL_FEAS) && env_knobs().spec_exchange) {
         // the feasibility estimates ||P_i(A_i x) - A_i x|| of the two-pass sets: their searches (on v = A_i x itself, each set's
         // second scalar state) in lock step through the same exchange -- one all-gather for all of them -- then the distances
         std::vector<int> tf;
@@ -1747,8 +1693,8 @@ class Engine : public EngineBase {
         SampleCtl ctl;
         ctl.host_want = (int*)hlean_ + i;
         ctl.host_ovf = (int*)hovf_ + i;
-        ctl.runs = l1_sample_runs_;
-        ctl.enable = l1_sample_ && !slab_ && a.prox == PX_L1 && !s.custom && (rescaled || (hlean_[i] & 0xff) != 0);
+        ctl.runs = env_knobs().l1_sample_runs;
+        ctl.enable = env_knobs().l1_sample && !slab_ && a.prox == PX_L1 && !s.custom && (rescaled || (hlean_[i] & 0xff) != 0);
         K<T>::proj_scalars_set(q, gs, ap, 0, s.ps, ptmp, mpart, cbuf, s.Mtrue, ctl, hooks());
         s.last_rho = a.rho;
         s.last_gamma = a.gamma;
@@ -1935,8 +1881,7 @@ class Engine : public EngineBase {
   // torch.distributed callbacks); a failure of the mapped exchange alone switches THIS context to full-size arrays on every
   // rank.  SIPX_COMM_SELFTEST=0 skips it.  The same code runs through the callback communicator (tests: 2-4 ranks on one GPU).
   void comm_self_test(bool want_mapped, bool want_a2a = false) {
-    const char* e = std::getenv("SIPX_COMM_SELFTEST");
-    if (e && e[0] == '0') {
+    if (!env_knobs().comm_selftest) {
       selftest_ = "skipped (SIPX_COMM_SELFTEST=0)";
       if (!agree_buf_) agree_buf_ = dalloc<double>(64);
       return;
@@ -2064,7 +2009,7 @@ class Engine : public EngineBase {
         mapped_why_ = ex.what();
       }
     }
-    if (const char* f = std::getenv("SIPX_COMM_SELFTEST_FAIL")) {      // tests: "mapped" / "base", optionally ":rank" (one rank only)
+    if (const char* f = env_knobs().comm_selftest_fail; f[0]) {      // SIPX_COMM_SELFTEST_FAIL (tests): "mapped" / "base", optionally ":rank" (one rank only)
       const char* colon = std::strchr(f, ':');
       if (!colon || std::atoi(colon + 1) == R) {
         if (!std::strncmp(f, "mapped", 6) && want_mapped) { mapped_ok = false; mapped_why_ = "test hook"; }
@@ -2207,7 +2152,7 @@ class Engine : public EngineBase {
         SIPX_HIP(hipStreamWaitEvent(stream_, last->ev, 0));
       }
     };
-    if (spec_batch_ && (int)tp.size() <= SPEC_MAX_SETS) {
+    if ((int)tp.size() <= SPEC_MAX_SETS) {
       // Batched form (the default): every set's first pass on the engine stream, then TWO launches for all sets -- sums of
       // the partial slots + packing, and, after the all-gather, decision + unpacking + solve (one workgroup per set).  A rank's
       // share of the grid is small when the ranks are many and the iteration is then bound by the launches the host can
@@ -2220,7 +2165,7 @@ class Engine : public EngineBase {
       // (the lean first passes of the l1 sets in one sweep: everything that prepares a search -- rescaling, sampled prediction --
       //  was queued on this very stream before, so the device-side state a lean pass reads is final when the sweep starts)
       (void)lean_group;
-      if (!feas_ps && !v_is_s && Gr_.n[0] % 4 == 0 && slab_lean_multi_) {
+      if (!feas_ps && !v_is_s && Gr_.n[0] % 4 == 0) {
         LeanMulti<T> lm;
         lm.ns = 0;
         std::vector<size_t> who;
@@ -2251,7 +2196,7 @@ class Engine : public EngineBase {
         P.is_l1 = s.prox == PX_L1 ? 1 : 0;
         SpecFinishSet<T>& F = fa.s[j];
         F.ps = PS(tp[j]);
-        F.da = DecideArgs{args[j].prox, (args[j].flags & F_NOSPEC) ? 1 : 0, (double)args[j].plo, (double)args[j].phi, 64.0, (double)hooks_.gcap, s.Mtrue};
+        F.da = DecideArgs{args[j].prox, (args[j].flags & F_NOSPEC) ? 1 : 0, (double)args[j].plo, (double)args[j].phi, (double)hooks_.gcap, s.Mtrue};
         F.reg = stage_ + j * RS;
         F.fseg0 = fbuf_ + (long long)j * fseg;
         F.compact = s.cbuf; F.partials = s.ptmp; F.radius = args[j].phi;
@@ -2294,7 +2239,7 @@ class Engine : public EngineBase {
     }
     spec_searches_ += (long long)tp.size();
     spec_fallbacks_ += (long long)fb.size();
-    static const bool spec_debug = std::getenv("SIPX_SPEC_DEBUG") != nullptr;
+    const bool spec_debug = env_knobs().spec_debug;
     if (spec_debug) {
       for (size_t j : fb) dump_ps(tp[j], stage_ + j * RS);
       std::fprintf(stderr, "[sipx spec] it %d:", it);
@@ -2307,8 +2252,7 @@ class Engine : public EngineBase {
       // the exchange segments take (the host reads that from the sets' pinned words after every round: exactly as many
       // all-reduces as are needed, at most L1_REFINES_SLAB), then the compaction of every final bracket and the full-size
       // all-gather.  The sets the exchange settled take no part.
-      int max_rounds = 6;
-      if (const char* e = std::getenv("SIPX_L1_ROUNDS_MAX")) max_rounds = std::max(0, std::min(6, std::atoi(e)));      // tests: force an overflow
+      const int max_rounds = std::max(0, std::min(6, env_knobs().l1_rounds_max));      // SIPX_L1_ROUNDS_MAX (tests): force an overflow
       for (int rep = 0; refine && rep < max_rounds; ++rep) {
         const unsigned rseq = ++spec_seq_ & 0x3fffffffu;
         for (size_t j : fb) {
@@ -2394,18 +2338,18 @@ class Engine : public EngineBase {
         // the search of a feasibility estimate comes every tenth iteration: its own last theta is ten iterations old and missed
         // the range every time (three fallbacks of two sweeps each per such iteration: 7 % of the 512^3 window) -- a sampled
         // estimate first, whenever the set's last such search asked for one (device side: ProjScalars::want_sample)
-        if (feas_sample_ && l1_sample_ && s.prox == PX_L1 && vec) {
+        if (env_knobs().l1_sample && s.prox == PX_L1 && vec) {
           SampleSet<T>& S = sm.s[sm.ns++];
           S.a = args[j]; S.a.ps = s.psf; S.ps = s.psf; S.partials = s.ptmp; S.reg = nullptr; S.true_len = s.Mtrue;
         }
         continue;
       }
       ctl[j].host_want = (int*)hlean_ + tp[j];
-      ctl[j].runs = l1_sample_runs_;
+      ctl[j].runs = env_knobs().l1_sample_runs;
       const bool l1 = s.prox == PX_L1;
       const bool rescaled = l1 && s.last_rho > T(0) && s.last_rho != args[j].rho;      // v rescaled: theta moves like 1/rho
       if (rescaled) { rs.ps[rs.n] = s.ps; rs.factor[rs.n++] = (double)s.last_rho / (double)args[j].rho; }
-      if (l1_sample_ && l1 && vec && (rescaled || (hlean_[tp[j]] & 0xff) != 0)) {
+      if (env_knobs().l1_sample && l1 && vec && (rescaled || (hlean_[tp[j]] & 0xff) != 0)) {
         SampleSet<T>& S = sm.s[sm.ns++];
         S.a = args[j]; S.a.ps = s.ps; S.ps = s.ps; S.partials = s.ptmp; S.reg = nullptr; S.true_len = s.Mtrue;
       }
@@ -2414,7 +2358,7 @@ class Engine : public EngineBase {
     }
     K<T>::ps_rescale_multi(stream_, rs);
     sm.v_is_s = v_is_s;
-    if (sm.ns > 0) K<T>::sample_multi(10, stream_, Gr_, sm, l1_sample_runs_, nullptr);
+    if (sm.ns > 0) K<T>::sample_multi(10, stream_, Gr_, sm, env_knobs().l1_sample_runs, nullptr);
     // the passes: groups of up to LEAN_MAX sets per launch (x read once per group) -- the lean first passes of the l1 sets whose
     // device-side state asks for one, then the full first passes of everybody else; each kernel returns at once when no set
     // of its group wants it.  (A grid whose lines are no multiple of four points keeps one scalar pass per set.)
@@ -2432,10 +2376,10 @@ class Engine : public EngineBase {
     };
     std::vector<size_t> all(tp.size());
     for (size_t j = 0; j < tp.size(); ++j) all[j] = j;
-    // (pass_multi_: the FULL first passes and the fallback passes of a group in one sweep as well -- measured and NOT the
+    // (SIPX_PASS_MULTI=1: the FULL first passes and the fallback passes of a group in one sweep as well -- measured and NOT the
     //  default: eight probes for three sets make that kernel ALU-bound at 161-173 VGPRs, 512^3 first passes 800-1000 us against
     //  3 x 285 us one after the other, refinement 1009 against 3 x 264; 512^3 116.2 against 118.7 it/s.  SIPX_PASS_MULTI=1, tests)
-    if (vec && pass_multi_) {
+    if (vec && env_knobs().pass_multi) {
       std::vector<size_t> l1s;
       for (size_t j = 0; j < tp.size(); ++j)
         if (sets_[tp[j]].prox == PX_L1 && !(args[j].flags & F_NOSPEC)) l1s.push_back(j);
@@ -2474,7 +2418,7 @@ class Engine : public EngineBase {
       P.is_l1 = s.prox == PX_L1 ? 1 : 0;
       SpecFinishSet<T>& F = fa.s[j];
       F.ps = PS(tp[j]);
-      F.da = DecideArgs{args[j].prox, (args[j].flags & F_NOSPEC) ? 1 : 0, (double)args[j].plo, (double)args[j].phi, 64.0, 0.0, s.Mtrue};
+      F.da = DecideArgs{args[j].prox, (args[j].flags & F_NOSPEC) ? 1 : 0, (double)args[j].plo, (double)args[j].phi, 0.0, s.Mtrue};
       F.reg = stage_ + j * RS;
       F.fseg0 = fbuf_ + (long long)j * fseg;
       F.compact = s.cbuf; F.partials = s.ptmp; F.radius = args[j].phi;
@@ -2497,7 +2441,7 @@ class Engine : public EngineBase {
       fb.push_back(j);
       refine |= (w & 2u) != 0;
     }
-    static const bool spec_debug = std::getenv("SIPX_SPEC_DEBUG") != nullptr;
+    const bool spec_debug = env_knobs().spec_debug;
     if (spec_debug && !feas_ps) {                // (diagnostics: the state every search of the chain ended its first stage with; synchronises)
       std::fprintf(stderr, "[sipx spec] batched chain, search seq %u\n", seq);
       for (size_t j = 0; j < tp.size(); ++j) dump_ps(tp[j], stage_ + j * RS);
@@ -2509,7 +2453,7 @@ class Engine : public EngineBase {
         K<T>::search_tail(stage, stream_, args[j], PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], stage_ + j * RS);
       }
     };
-    if (vec && pass_multi_) {
+    if (vec && env_knobs().pass_multi) {
       if (refine) {
         for (size_t k = 0; k < fb.size(); k += LEAN_MAX) K<T>::pass_multi(1, stream_, Gr_, group(fb, k), v_is_s);
         tail(1);
@@ -2547,7 +2491,7 @@ class Engine : public EngineBase {
         SetArgs<T> a = set_args(s, (T)rho[i], (T)gamma[i], flags);
         if (a.flags & F_NOSPEC) continue;
         const bool rescaled = s.last_rho > T(0) && s.last_rho != a.rho;
-        const bool sampled = l1_sample_ && (rescaled || (hlean_[i] & 0xff) != 0);
+        const bool sampled = env_knobs().l1_sample && (rescaled || (hlean_[i] & 0xff) != 0);
         if (rescaled || sampled) { ok = false; break; }
         if (lm.ns == LEAN_MAX) break;
         LeanSet<T>& L = lm.s[lm.ns++];
@@ -2580,16 +2524,16 @@ class Engine : public EngineBase {
       SampleCtl ctl;
       ctl.host_want = (int*)hlean_ + i;
       ctl.host_ovf = (int*)hovf_ + i;
-      ctl.runs = l1_sample_runs_;
-      ctl.enable = l1_sample_ && a.prox == PX_L1 && (rescaled || (hlean_[i] & 0xff) != 0);
+      ctl.runs = env_knobs().l1_sample_runs;
+      ctl.enable = env_knobs().l1_sample && a.prox == PX_L1 && (rescaled || (hlean_[i] & 0xff) != 0);
       ctl.lean_done = lean_done[i];
       K<T>::proj_scalars_set(q, Gr_, a, 0, s.ps, ptmp, mpart, cbuf, s.Mtrue, ctl, nullptr);
       s.last_rho = a.rho;
       s.last_gamma = a.gamma;
       if (feas && i < pp_n_) {                 // ||P_i(s) - s|| with s = A_i x produced on the fly; its own warm-started scalars
         SampleCtl cf;                          // (a sampled estimate first, as in the batched chain: run_batched)
-        cf.runs = l1_sample_runs_;
-        cf.enable = feas_sample_ && l1_sample_ && a.prox == PX_L1;
+        cf.runs = env_knobs().l1_sample_runs;
+        cf.enable = env_knobs().l1_sample && a.prox == PX_L1;
         K<T>::proj_scalars_set(q, Gr_, a, 1, s.psf, ptmp, mpart, cbuf, s.Mtrue, cf, nullptr);
         K<T>::proj_dist_set(q, Gr_, a, 1, s.psf, part + (size_t)SL_FE2 * NB);
       }
@@ -3197,7 +3141,7 @@ class Engine : public EngineBase {
       defer_sums_ = true;                  // queue the kernels and the reduction of their sums, collect them further down
       const bool rhs_known = i < maxit && !rho_may_change(i);
       fuse_rhs_ = rhs_known;               // rhs_{i+1} may be formed by the sweep that forms y_{i+1}, l_{i+1}
-      merge_sums_ = rhs_known && resid_ahead_ && comm_ != nullptr;
+      merge_sums_ = rhs_known && comm_ != nullptr;
       update_y_l(i, flags, rho.data(), gamma.data(), rpri.data(), rdual.data(), feas.data());
       fuse_rhs_ = false;
       defer_sums_ = false;
@@ -3222,7 +3166,7 @@ class Engine : public EngineBase {
       // (round 3 had the product store x_old <- x, which a context without a distance term -- feasibility only -- still had to read
       //  for evol_x after this point: its logged evol_x was zero.  The product no longer touches x_old: x_k stays behind in its own
       //  ring buffer when the x-step moves on, tests/test_gpu_round4.py::test_feasibility_only_logs_evol_x...)
-      if (R.rhs_ready && resid_ahead_) {     // ... and so is the residual product of the coming x-step
+      if (R.rhs_ready) {     // ... and so is the residual product of the coming x-step
         if (next_timed) open_section(i + 1);         // (the coming step is a timed one: its x-step section opens here)
         argmin_x_head();
         if (comm_) {                         // (sharded: the sums arrive with the grouped call of the head)
@@ -3931,7 +3875,7 @@ class Engine : public EngineBase {
     for (int b = 0; b < cds_.d; ++b) cds_.off[b] = seen[b];
     // symmetric read of Q (CdsArgs::sym): every negative band needs its positive partner, at a band index >= 1 so that
     // the shifted address never leaves the allocation; explicit AtA bands must be symmetric bit for bit
-    bool ok = !cds_full_;
+    bool ok = !env_knobs().cds_full;      // SIPX_CDS_FULL=1: read all d bands of Q (no symmetric partner reads)
     for (int b = 0; b < cds_.d && ok; ++b) {
       cds_.partner[b] = b;
       if (cds_.off[b] >= 0) continue;
@@ -4136,7 +4080,7 @@ class Engine : public EngineBase {
     fan_collect(s, a, 0, s.fanv);
     if (comm_->rank != s.fan_owner) return;
     // (the all-kernel statistics window times one kernel at a time on the engine stream: in turn there)
-    hipStream_t q = (fan_st_ && stats_mode_ != 2 && fan_overlap_) ? fan_st_ : stream_;
+    hipStream_t q = (fan_st_ && stats_mode_ != 2) ? fan_st_ : stream_;
     if (q != stream_) {
       SIPX_HIP(hipEventRecord(fan_fork_, stream_));
       SIPX_HIP(hipStreamWaitEvent(q, fan_fork_, 0));
@@ -4416,11 +4360,10 @@ class Engine : public EngineBase {
   bool loose_owned_ = false, loose_whole_ = false;
   bool need_idx_ = false, need_ext_ = false;
   CdsArgs cds_;
-  bool cds_full_ = false;         // SIPX_CDS_FULL=1: read all d bands of Q (no symmetric partner reads)
   bool set_streams_ = true;       // SIPX_SERIAL_SETS=1 keeps every set on the engine stream (A/B measurements)
   hipEvent_t ev_fork_ = nullptr, ev_fork2_ = nullptr;
   std::vector<hipStream_t> pool_;   // streams the sets are dealt onto, round robin
-  bool set_streams_forced_ = false, search_streams_ = false;
+  bool search_streams_ = false;
   int search_next_ = 0;
   int n_set_streams_ = 2, pool_next_ = 0;   // measured: 2 beats 1 by 1-4 %, 3+ lose again at 512^3 (streaming passes collide)
   bool mk_ = false;               // Minkowski mode: unknowns [u; v]
@@ -4440,7 +4383,6 @@ class Engine : public EngineBase {
   volatile unsigned* hverd_ = nullptr;   // per set: verdict of the speculative exchange of a slab-decomposed search (k_spec_decide)
   unsigned spec_seq_ = 0;
   long long spec_searches_ = 0, spec_fallbacks_ = 0, spec_rounds_ = 0;     // searches through the speculative exchange / of those, fallbacks / refinement rounds (all-reduces) of the fallbacks
-  bool spec_exchange_ = true;         // SIPX_SPEC_EXCHANGE=0: every search through (all-reduce, ..., all-gather), as before
   // the lane of the slice-rank / nuclear-norm set (sipx_finalize, lane_start)
   int lane_set_ = -1;
   hipStream_t lane_st_ = nullptr;
@@ -4451,16 +4393,10 @@ class Engine : public EngineBase {
   long long lane_sample_ = -1;        // index of the statistics sample that books the lane's interval (-1: none open)
   SetArgs<T> lane_args_;
   bool sweep_partial_ = false, has_loose_ = false;   // the sweep takes a subset of the sets (in_sweep); some owned set keeps its per-set kernels
-  bool pass_multi_ = false;           // SIPX_PASS_MULTI=1: full first passes / fallback passes of the batched searches in one sweep per group (measured slower)
   bool sweep_plain_ = false;          // the sweep takes the plain iterations of this context: every set carries a third y / l pair
-  bool feas_sample_ = true;           // SIPX_FEAS_SAMPLE=0: the feasibility searches of the batched chain start from their own last theta (A/B switch)
   bool search_batch_ = false;         // one rank + sweep: the searches of all sets as one chain of launches (batched_searches; SIPX_SEARCH_BATCH=0: per-set chains on the set streams)
   long long batch_searches_ = 0, batch_fallbacks_ = 0;
-  bool spec_batch_ = true;            // SIPX_SPEC_BATCH=0: the small steps of the exchange as one kernel per set on the set streams
-  bool slab_lean_multi_ = true;       // SIPX_SLAB_LEAN_MULTI=0: one lean first pass per set in the batched exchange
   T* fbuf_ = nullptr;                 // fast segments: world x two-pass sets x (fcap + header)
-  long long l1_sample_runs_ = 0;
-  bool l1_sample_ = true;             // SIPX_L1_SAMPLE=0: no sampled prediction of theta (A/B switch)
   bool yl_multi_ = true;              // SIPX_YL_MULTI=0: never take the one-sweep y/l update (A/B switch)
   bool x0_mode_ = false;              // s_0 = A x_0 recomputed from a snapshot of x (see finalize)
   // x lives in a RING of three buffers (round 4): the x-step writes x_{k+1} = x_k + alpha_1 p_1 into a buffer that holds neither
@@ -4499,7 +4435,6 @@ class Engine : public EngineBase {
   bool head_done_ = false;            // the residual product of the coming x-step is queued already (argmin_x_head)
   bool merge_sums_ = false;           // sharded whole-solve loop: the coming reduction of the set sums leaves its all-reduce to argmin_x_head
   int merged_nslots_ = 0;
-  bool resid_ahead_ = true;           // SIPX_RESID_AHEAD=0: the residual product waits for the host's stop rule, as before
   int sums_flags_ = 0;
   volatile unsigned long long* ticket_ = nullptr;   // pinned: verdict of the latest CG iteration (publish_ticket)
   unsigned cg_seq_ = 0;
@@ -4511,7 +4446,6 @@ class Engine : public EngineBase {
   double* fan_ptmp_ = nullptr;
   T *fan_mpart_ = nullptr, *fan_c_ = nullptr;
   long long fan_exchanges_ = 0;       // gathers + scatters of the gathered sets so far (stats)
-  bool fan_overlap_ = true;           // SIPX_FAN_OVERLAP=0: the owner projects in turn on the engine stream (A/B switch)
   bool slab_loose_ = false;           // slab-decomposed with sets projected on a materialised v (SetState::slab_ext, fan)
   // slab-decomposed with SPARSE arrays: every N-sized array of the context is backed by memory for the rank's planes (and the
   // halo planes around them) only -- see SparseBlock.  [wlo_, whi_): the grid points whose entries exist on this rank.

@@ -564,7 +564,7 @@ __global__ __launch_bounds__(BLOCK) void k_sub_residual(int k, int b, int r, int
 // lies above a is amplified -- an interval 5 % short loses a factor T_m(1.1) (250 at degree 14) of the contraction, one 5 %
 // long about 10.  And never below 0.9 of the (r+1)-th Ritz value: a guard column that had to be re-seeded (k_chol_inv) carries
 // a Rayleigh quotient from the middle of the spectrum, far below the block's true lower end.
-__device__ double g_cheb_floor_factor = 0.9;      // SIPX_RANK_FLOOR (experiments): the interval never ends below this share of the (r+1)-th Ritz value
+__device__ double g_cheb_floor_factor = 0.9;      // the interval never ends below this share of the (r+1)-th Ritz value
 __device__ __forceinline__ double cheb_floor(const double* __restrict__ W, int b, int g, int r) {
   const double top = W[b - 1];
   double a = W[g];
@@ -1050,13 +1050,10 @@ struct ExtImpl {
   bool cheb = false;
   double *Ys = nullptr, *Bd = nullptr, *Cs = nullptr;
   // the matrices that still need a filter when most of the batch has converged, packed (rank_cheb_route)
-  // switches of the rank routes, read once when the projector is built (tests and A/B runs set them before they build a context)
+  // switches of the rank routes, taken from env_knobs() once when the projector is built (tests and A/B runs set them before they
+  // build a context)
   struct RankKnobs {
     int dbg = 0;                  // SIPX_EXT_DEBUG: 1 the route of every call on stderr, 2 milliseconds per phase, 3 open matrices and Jacobi sweeps per step
-    int budget = 160;             // SIPX_RANK_CHEB_BUDGET: multiplications with G a call may spend
-    int m_cap = 16;               // SIPX_RANK_CHEB_MMAX: degree of one filter at most
-    double tol = 1e-12;           // SIPX_RANK_CHEB_TOL (experiments: is a difference between the routes a matter of this tolerance?)
-    int guard = -1;               // SIPX_RANK_CHEB_GUARD: index of the Ritz value that ends the damped interval (-1: chosen from the block)
     bool pack = true;             // SIPX_RANK_PACK=0: every filter on the whole batch
     bool cert_check = false;      // SIPX_RANK_CERT_CHECK: both factorisations, compared matrix by matrix (tests)
     // Round 5.  eps_bw: the acceptance level of a Ritz pair as a backward error on the slice itself, ||E||_2 <= eps_bw ||X||_2
@@ -1191,8 +1188,7 @@ ExtProj<T>::ExtProj(const ExtSpec& spec, hipStream_t stream) {
     SIPX_HIP(hipMemcpy(I.mag, spec.ub, sizeof(T) * N, hipMemcpyHostToDevice));
   } else if (kind == EXT_L1_DFT) {
     if (!(spec.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-    const char* rf_e = getenv("SIPX_DFT_REAL");            // 0: the complex transform of the packed model (A/B switch, tests)
-    I.real_fft = !(rf_e && rf_e[0] == '0') && G.n[0] >= 4;
+    I.real_fft = env_knobs().dft_real && G.n[0] >= 4;      // SIPX_DFT_REAL=0: the complex transform of the packed model (A/B switch, tests)
     if (I.real_fft) {
       const hipfftType tf = sizeof(T) == 4 ? HIPFFT_R2C : HIPFFT_D2Z, tb = sizeof(T) == 4 ? HIPFFT_C2R : HIPFFT_Z2D;
       if (spec.ndim == 2) {
@@ -1259,30 +1255,19 @@ ExtProj<T>::ExtProj(const ExtSpec& spec, hipStream_t stream) {
       I.Wd = I.template alloc<double>((size_t)k * I.batch);
       if (kind == EXT_NUCLEAR) I.Gs = I.template alloc<double>((size_t)k * k * I.batch);
       {
-        auto env = [](const char* n) { return getenv(n); };
+        const EnvKnobs& E = env_knobs();
         auto& K_ = I.knobs;
-        if (const char* e = env("SIPX_EXT_DEBUG")) K_.dbg = atoi(e);
-        if (const char* e = env("SIPX_RANK_CHEB_BUDGET")) K_.budget = atoi(e) > 0 ? atoi(e) : K_.budget;
-        if (const char* e = env("SIPX_RANK_CHEB_MMAX")) K_.m_cap = atoi(e) >= 2 ? atoi(e) : K_.m_cap;
-        if (const char* e = env("SIPX_RANK_CHEB_TOL")) K_.tol = atof(e) > 0 ? atof(e) : K_.tol;
-        if (const char* e = env("SIPX_RANK_CHEB_GUARD")) K_.guard = std::max(0, atoi(e));
-        if (const char* e = env("SIPX_RANK_PACK")) K_.pack = e[0] != '0';
-        K_.cert_check = env("SIPX_RANK_CERT_CHECK") != nullptr;
-        if (const char* e = env("SIPX_RANK_STRICT")) { if (e[0] != '0') K_.eps_bw = 0.0; }
-        if (const char* e = env("SIPX_RANK_EPS")) K_.eps_bw = atof(e) >= 0 ? atof(e) : K_.eps_bw;
-        if (const char* e = env("SIPX_RANK_FLOOR")) {
-          const double f = atof(e);
-          if (f > 0 && f < 1) SIPX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_cheb_floor_factor), &f, sizeof(double)));
-        }
+        K_.dbg = E.ext_debug;
+        K_.pack = E.rank_pack;
+        K_.cert_check = E.rank_cert_check;
+        if (E.rank_strict) K_.eps_bw = 0.0;
       }
-      const char* sub_e = getenv("SIPX_RANK_SUBSPACE");      // read per projector: 0 keeps the full decomposition every call
-      const int sub_env = sub_e ? atoi(sub_e) : 1;
+      const int sub_env = env_knobs().rank_subspace;      // SIPX_RANK_SUBSPACE=0 keeps the full decomposition every call
       // columns the block holds beyond the r wanted ones: 24 where the matrices are large enough for the route with them, else 16.
       // (C4, 512 slices of 512 x 512, r = 32, round 4: 12 / 16 / 20 / 24 / 28 / 32 guards -> 15.7 / 15.4 / 16.3 / 16.5 / 16.4 / 16.1 it/s:
       //  more guards move the end of the damped interval away from theta_r, and the library's GEMM tiles are 32 columns wide --
-      //  48 columns cost what 64 do.)  SIPX_RANK_GUARDS: experiments.
-      const char* ex_e = getenv("SIPX_RANK_GUARDS");
-      const int extra = ex_e && atoi(ex_e) >= 4 ? atoi(ex_e) : ((I.r + 24) * 4 <= k && I.r + 24 <= 64 ? 24 : 16);
+      //  48 columns cost what 64 do.)
+      const int extra = (I.r + 24) * 4 <= k && I.r + 24 <= 64 ? 24 : 16;
       if (kind == EXT_RANK && sub_env && (I.r + extra) * 4 <= k && I.r + extra <= 64) {      // worth it only for r << k
         I.sub_b = I.r + extra;
         const size_t nb = (size_t)k * I.sub_b * I.batch;
@@ -1296,8 +1281,7 @@ ExtProj<T>::ExtProj(const ExtSpec& spec, hipStream_t stream) {
         I.FroPart = I.template alloc<double>((size_t)I.batch * FRO_PARTS);
         I.sub_res = I.template alloc<unsigned long long>(8);
         SIPX_HIP(hipHostMalloc((void**)&I.sub_res_host, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-        const char* ch_e = getenv("SIPX_RANK_CHEB");           // 0: plain subspace iteration only (spectra with a gap)
-        I.cheb = !(ch_e && ch_e[0] == '0');
+        I.cheb = env_knobs().rank_cheb;           // SIPX_RANK_CHEB=0: plain subspace iteration only (spectra with a gap)
         if (I.cheb) {
           I.Ys = I.template alloc<double>(nb);
           I.Cs = I.template alloc<double>((size_t)I.sub_b * I.sub_b * I.batch);
@@ -1511,10 +1495,6 @@ __global__ __launch_bounds__(256) void k_hash_bits(const unsigned long long* __r
 }
 static std::mutex& gemm_tune_mutex() { static std::mutex m; return m; }
 static std::map<GemmShape, int>& gemm_tune_table() { static std::map<GemmShape, int> t; return t; }
-static bool gemm_tune_on() {
-  static const bool on = [] { const char* e = getenv("SIPX_GEMM_TUNE"); return !(e && e[0] == '0'); }();
-  return on;
-}
 static rocblas_status dgemm_ex(rocblas_handle h, rocblas_operation ta, rocblas_operation tb, int m, int n, int k, const double* alpha, const double* A, int lda,
                                long long sa, const double* B, int ldb, long long sb, const double* beta, double* C, int ldc, long long sc, int batch, int sol) {
   return rocblas_gemm_strided_batched_ex(h, ta, tb, m, n, k, alpha, A, rocblas_datatype_f64_r, lda, sa, B, rocblas_datatype_f64_r, ldb, sb, beta, C,
@@ -1585,7 +1565,7 @@ static int gemm_tune(rocblas_handle h, const GemmShape& key, const double* A, lo
         if (kv.second.first <= 1.05f * t_best && lowest[kv.first] < low) { low = lowest[kv.first]; pick = kv.first; }
       choice = best[pick].second;
     }
-    if (getenv("SIPX_GEMM_TUNE_DEBUG"))
+    if (env_knobs().gemm_tune_debug)
       fprintf(stderr, "[sipx gemm] %c%c %d x %d x %d, batch %d: %d solutions in %zu groups by bits; library %.3f ms, fastest %.3f ms; solution %d\n",
               key.ta == rocblas_operation_none ? 'N' : 'T', key.tb == rocblas_operation_none ? 'N' : 'T', key.m, key.n, key.k, batch, ns, best.size(),
               def.ms / 2, t_best / 2, choice);
@@ -1607,7 +1587,7 @@ static rocblas_status gemm_sbx(rocblas_handle h, rocblas_operation ta, rocblas_o
   //  solution kept for every row count (a call it does not take falls back to the library's); 0: the library's choice)
   //  3: no trial, but the kernel a trial of the same shape has chosen, if there was one -- products that accumulate, beta = 1)
   const bool may_try = (tune == 1 || tune == 2) && alpha == 1.0 && beta == 0.0 && (const double*)C != A && (const double*)C != B;
-  if (tune && gemm_tune_on() && batch > 0 && (long long)m * n * k >= (1ll << 16)) {
+  if (tune && env_knobs().gemm_tune && batch > 0 && (long long)m * n * k >= (1ll << 16)) {
     const GemmShape key{(int)ta, (int)tb, tune == 2 ? -1 : m, n, k, lda, ldb, ldc};
     int sol = 0;
     bool known = false;
@@ -1669,10 +1649,12 @@ static int cheb_loop(ExtImpl<T>& I, RouteBufs B, ChebCtl& C) {
   const long long sG = (long long)k * k, sX = (long long)k * b, sH = (long long)b * b;
   const auto N_ = rocblas_operation_none, T_ = rocblas_operation_transpose;
   const auto& KN = I.knobs;
-  const int dbg = KN.dbg, budget = KN.budget, m_cap = KN.m_cap;
-  const double tol = KN.tol;
+  constexpr int budget = 160;      // multiplications with G a call may spend
+  constexpr int m_cap = 16;        // degree of one filter at most
+  constexpr double tol = 1e-12;    // convergence level of a Ritz pair relative to theta_max
+  const int dbg = KN.dbg;
   // index of the Ritz value that ends the damped interval (C4 with 24 guards: 2 / 3 / 4 / 6 -> 16.8 / 16.5 / 16.6 / 16.0 it/s)
-  const int g = KN.guard >= 0 ? std::min(KN.guard, b - r - 1) : std::max(2, (b - r) / 12);
+  const int g = std::max(2, (b - r) / 12);
   auto mark = [&](int which) {
     if (dbg < 2) return;
     SIPX_HIP(hipStreamSynchronize(s));

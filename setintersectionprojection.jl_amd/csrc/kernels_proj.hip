@@ -42,7 +42,6 @@ namespace sipx {
 #error "kernels_proj.hip: the relaxed-atomics hand-offs assume gfx950 (see the comment above); port them to release/acquire first"
 #endif
 
-constexpr long long SOLVE_COOP_MIN_DEFAULT = 1ll << 17;
 constexpr double L1_CAP = 131072.0;     // bracket population above which one more probe pass is run (floor; scales with the length)
 constexpr int L1_REFINES = 1;           // gated refinement passes enqueued per search (one rank: the final gather never drops)
 constexpr int L1_REFINES_SLAB = 6;      // slab-decomposed: rounds the caller may enqueue until the bracket fits the exchange segments
@@ -50,19 +49,8 @@ constexpr int L1_REFINES_SLAB = 6;      // slab-decomposed: rounds the caller ma
 #define SIPX_SPEC_CAP 1024
 #endif
 constexpr int SPEC_CAP = SIPX_SPEC_CAP;  // per-workgroup LDS buffer of the speculative compaction
-// largest relative half-width of the speculative range (SIPX_L1_HWMAX overrides; A/B switch)
-static int l1_lean_on() {       // SIPX_L1_LEAN=0: every first pass evaluates all eight probes (A/B switch)
-  static const int v = [] { const char* e = getenv("SIPX_L1_LEAN"); return e ? atoi(e) : 1; }();
-  return v;
-}
-static long long solve_coop_min() {      // SIPX_SOLVE_COOP_MIN: gathered values from which the sweeps of the solve are shared (A/B switch)
-  static const long long v = [] { const char* e = getenv("SIPX_SOLVE_COOP_MIN"); return e ? atoll(e) : SOLVE_COOP_MIN_DEFAULT; }();
-  return v;
-}
-static double l1_hw_max() {
-  static const double v = [] { const char* e = getenv("SIPX_L1_HWMAX"); return e ? atof(e) : 1e-2; }();
-  return v;
-}
+constexpr double L1_HW_MAX = 1e-2;       // largest relative half-width of the speculative range
+constexpr double L1_CAPDIV = 64.0;       // a bracket may hold the 1 / L1_CAPDIV-th part of the vector before one more probe pass is run (above L1_CAP)
 // Probe thresholds of the next call, as multiples of the half-width hw around the predicted theta: the two inner probes
 // are the edges of the speculative gather range, the outer ones catch a theta that moved further (geometric spacing, so one
 // pass brackets it between neighbouring probes whatever the size of the move up to 64 hw).
@@ -693,7 +681,7 @@ __device__ __forceinline__ void place_probes(ProjScalars<T>* ps, double lo, doub
   }
 }
 template <typename T, int STAGE>
-__device__ void decide_body(ProjScalars<T>* ps, int prox, T pmin, T pmax, long long true_len, int nospec, double capdiv, int world,
+__device__ void decide_body(ProjScalars<T>* ps, int prox, T pmin, T pmax, long long true_len, int nospec, int world,
                             double cap_max, const double* reg);
 
 // FUSE (one rank: no all-reduce between the sums and the decision): every workgroup hands its value over with a device-scope
@@ -721,7 +709,7 @@ __global__ __launch_bounds__(BLOCK) void k_slot_sums(const double* __restrict__ 
     __syncthreads();
     if (threadIdx.x != 0) return;
     __hip_atomic_store(&ps->pass_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    decide_body<T, STAGE>(ps, da.prox, (T)da.pmin, (T)da.pmax, da.true_len, da.nospec, da.capdiv, world, da.cap_max, sreg);
+    decide_body<T, STAGE>(ps, da.prox, (T)da.pmin, (T)da.pmax, da.true_len, da.nospec, world, da.cap_max, sreg);
   };
   if (blockIdx.x < PREP_SLOTS) {
     const double v = block_sum_partials(partials + (long long)blockIdx.x * NB);
@@ -759,7 +747,7 @@ __global__ __launch_bounds__(BLOCK) void k_slot_sums(const double* __restrict__ 
 // Scalar decisions after a probe pass (one thread; the sums come from k_slot_sums).  STAGE 0: after the first pass;
 // STAGE 1: after the gated refinement.
 template <typename T, int STAGE>
-__device__ void decide_body(ProjScalars<T>* ps, int prox, T pmin, T pmax, long long true_len, int nospec, double capdiv, int world,
+__device__ void decide_body(ProjScalars<T>* ps, int prox, T pmin, T pmax, long long true_len, int nospec, int world,
                             double cap_max, const double* reg) {
   const double* red = reg;
   T vmax = T(0), vmin = (T)INFINITY;
@@ -848,7 +836,7 @@ __device__ void decide_body(ProjScalars<T>* ps, int prox, T pmin, T pmax, long l
         hi = hi < t4 ? hi : t4;
         ps->lo = lo;
         ps->hi = hi;
-        double cap = fmax(L1_CAP, (double)true_len / capdiv);
+        double cap = fmax(L1_CAP, (double)true_len / L1_CAPDIV);
         if (cap_max > 0 && cap > cap_max) cap = cap_max;
         double pop = C3 - C4;
         if (t4 > t3 && !(cap_max > 0)) pop *= fmin(1.0, 2.0 * (hi - lo) / (t4 - t3));
@@ -933,7 +921,7 @@ __device__ void decide_body(ProjScalars<T>* ps, int prox, T pmin, T pmax, long l
   // (each gated refinement pass narrows it by >= L1_K-1 and by the Newton/secant step on top)
   // one more probe pass costs a full sweep of the vector, gathering a larger bracket costs the one-workgroup solve a
   // longer scan: the break-even population grows with the length (measured at 256^3 and 512^3)
-  double cap = fmax(L1_CAP, (double)true_len / capdiv);
+  double cap = fmax(L1_CAP, (double)true_len / L1_CAPDIV);
   if (cap_max > 0 && cap > cap_max) cap = cap_max;
   // population of the tightened bracket (lo, hi]: the count between the two probes, scaled by the share of the interval
   // that is left (factor 2 for a density that is not flat).  A wrong guess only costs time: the gather never drops.
@@ -961,21 +949,20 @@ __device__ void decide_body(ProjScalars<T>* ps, int prox, T pmin, T pmax, long l
 // the decision as a kernel of its own (slab-decomposed grid: an all-reduce sits between the sums and the decision)
 template <typename T, int STAGE>
 __global__ __launch_bounds__(64) void k_decide(ProjScalars<T>* ps, int prox, T pmin, T pmax, long long true_len,
-                                               int nospec, double capdiv, int world, double cap_max, const double* __restrict__ reg) {
+                                               int nospec, int world, double cap_max, const double* __restrict__ reg) {
   if (STAGE == 1 && !(ps->need && !ps->spec_ok && ps->refine)) return;
   if (threadIdx.x != 0) return;
-  decide_body<T, STAGE>(ps, prox, pmin, pmax, true_len, nospec, capdiv, world, cap_max, reg);
+  decide_body<T, STAGE>(ps, prox, pmin, pmax, true_len, nospec, world, cap_max, reg);
 }
 
 
 // ... and, in the fallback of a speculative exchange, with the verdict the host reads: does this set need another refinement round?
 template <typename T>
-__global__ __launch_bounds__(64) void k_decide_round(ProjScalars<T>* ps, int prox, T pmin, T pmax, long long true_len, double capdiv,
-                                                     int world, double cap_max, const double* __restrict__ reg, unsigned seq,
-                                                     unsigned* verdict) {
+__global__ __launch_bounds__(64) void k_decide_round(ProjScalars<T>* ps, int prox, T pmin, T pmax, long long true_len, int world,
+                                                     double cap_max, const double* __restrict__ reg, unsigned seq, unsigned* verdict) {
   if (threadIdx.x != 0) return;
   const bool live = ps->need && !ps->spec_ok && ps->refine;
-  if (live) decide_body<T, 1>(ps, prox, pmin, pmax, true_len, 0, capdiv, world, cap_max, reg);
+  if (live) decide_body<T, 1>(ps, prox, pmin, pmax, true_len, 0, world, cap_max, reg);
   const unsigned word = (seq << 2) | 1u | ((live && ps->refine) ? 2u : 0u);
   __hip_atomic_store(verdict, word, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -1039,7 +1026,7 @@ constexpr unsigned long long SAMPLE_SUM_MASK = (1ull << (64 - SAMPLE_CNT_BITS)) 
 // Everything the other workgroups contributed was written with device-scope atomics and is read with device-scope loads.
 template <typename T>
 __device__ __forceinline__ void sample_decide(ProjScalars<T>* ps, double* __restrict__ partials, int nwg, T radius,
-                                              long long true_len, double hw_max, int lean_on, double gather_cap, double* sS,
+                                              long long true_len, double gather_cap, double* sS,
                                               double* sC, const double* __restrict__ dsrc = nullptr) {
   // dsrc (slab-decomposed grid): counts [0, BINS), fixed-point sums [BINS, 2 BINS) and the three partial sums, all-reduced
   // over the ranks as float64 (integers below 2^53: exact, whatever the order) -- instead of ps->hist and the partial slots
@@ -1184,14 +1171,14 @@ __device__ __forceinline__ void sample_decide(ProjScalars<T>* ps, double* __rest
   const double ctr = 0.5 * (lo + hi);
   double hw = (hi - lo) / (2.0 * ctr);
   hw = hw < 1e-3 ? 1e-3 : hw;
-  ps->hw = hw < hw_max ? hw : hw_max;      // (the next search's own rule starts from a range of the usual width)
+  ps->hw = hw < L1_HW_MAX ? hw : L1_HW_MAX;      // (the next search's own rule starts from a range of the usual width)
   for (int k = 0; k < L1_K; ++k) {
     const double t = ctr * (1.0 + hw * l1_probe_mult(k));
     ps->t[k] = t > 0 ? (double)(T)t : 0.0;
   }
   ps->spec_lo = ps->t[L1_WIN_LO];
   ps->spec_hi = ps->t[L1_WIN_HI];
-  ps->lean = lean_on ? 1 : 0;
+  ps->lean = 1;
   ps->sampled = 1;
   ps->samp_theta = th;
   ps->samp_lo = sh_thN; ps->samp_hi = sh_thS; ps->samp_c = c_act;
@@ -1202,7 +1189,7 @@ __device__ __forceinline__ void sample_decide(ProjScalars<T>* ps, double* __rest
 template <typename T, int V>
 __device__ void sample_body(const Grid& G, const SetArgs<T>& a, ProjScalars<T>* ps, double* __restrict__ partials,
                             long long nchunks, long long nsamp, unsigned int stride, long long true_len,
-                            double hw_max, int lean_on, double gather_cap, double* __restrict__ defer_to, int v_is_s = 0) {
+                            double gather_cap, double* __restrict__ defer_to, int v_is_s = 0) {
   if (!ps->want_sample || !(ps->theta_prev > 0)) return;
   constexpr int NT = SAMPLE_NT;
   __shared__ unsigned long long hs[SAMPLE_BINS];
@@ -1323,35 +1310,35 @@ __device__ void sample_body(const Grid& G, const SetArgs<T>& a, ProjScalars<T>* 
   // (a feasibility estimate's last sample is ten iterations old: what it was off by then says nothing now -- iteration 20 of the
   //  headline run missed its range WITH the correction of iteration 10)
   if (v_is_s && threadIdx.x == 0) ps->samp_bias_ok = 0;
-  sample_decide<T>(ps, partials, (int)gridDim.x, a.phi, true_len, hw_max, lean_on, gather_cap, sS, sC);
+  sample_decide<T>(ps, partials, (int)gridDim.x, a.phi, true_len, gather_cap, sS, sC);
 }
 
 template <typename T, int V>
 __global__ __launch_bounds__(SAMPLE_NT) void k_sample(Grid G, SetArgs<T> a, ProjScalars<T>* ps, double* __restrict__ partials,
                                                       long long nchunks, long long nsamp, unsigned int stride, long long true_len,
-                                                      double hw_max, int lean_on, double gather_cap, double* __restrict__ defer_to, int v_is_s) {
-  sample_body<T, V>(G, a, ps, partials, nchunks, nsamp, stride, true_len, hw_max, lean_on, gather_cap, defer_to, v_is_s);
+                                                      double gather_cap, double* __restrict__ defer_to, int v_is_s) {
+  sample_body<T, V>(G, a, ps, partials, nchunks, nsamp, stride, true_len, gather_cap, defer_to, v_is_s);
 }
 template <typename T, int V>
 __global__ __launch_bounds__(SAMPLE_NT) void k_sample_multi(Grid G, SampleMulti<T> A, long long nchunks, long long nsamp, unsigned int stride,
-                                                            double hw_max, int lean_on, double gather_cap) {
+                                                            double gather_cap) {
   const SampleSet<T>& S = A.s[blockIdx.y];
-  sample_body<T, V>(G, S.a, S.ps, S.partials, nchunks, nsamp, stride, S.true_len, hw_max, lean_on, gather_cap, S.reg, A.v_is_s);
+  sample_body<T, V>(G, S.a, S.ps, S.partials, nchunks, nsamp, stride, S.true_len, gather_cap, S.reg, A.v_is_s);
 }
 template <typename T>
-__global__ __launch_bounds__(SAMPLE_NT) void k_sample_decide2_multi(SampleMulti<T> A, double hw_max, int lean_on, double gather_cap) {
+__global__ __launch_bounds__(SAMPLE_NT) void k_sample_decide2_multi(SampleMulti<T> A, double gather_cap) {
   const SampleSet<T>& S = A.s[blockIdx.x];
   if (!S.ps->want_sample || !(S.ps->theta_prev > 0)) return;
   __shared__ double sS[SAMPLE_NT], sC[SAMPLE_NT];
-  sample_decide<T>(S.ps, nullptr, 0, S.a.phi, S.true_len, hw_max, lean_on, gather_cap, sS, sC, S.reg);
+  sample_decide<T>(S.ps, nullptr, 0, S.a.phi, S.true_len, gather_cap, sS, sC, S.reg);
 }
 
 template <typename T>
 __global__ __launch_bounds__(SAMPLE_NT) void k_sample_decide2(ProjScalars<T>* ps, const double* __restrict__ dsrc, T radius,
-                                                              long long true_len, double hw_max, int lean_on, double gather_cap) {
+                                                              long long true_len, double gather_cap) {
   if (!ps->want_sample || !(ps->theta_prev > 0)) return;
   __shared__ double sS[SAMPLE_NT], sC[SAMPLE_NT];
-  sample_decide<T>(ps, nullptr, 0, radius, true_len, hw_max, lean_on, gather_cap, sS, sC, dsrc);
+  sample_decide<T>(ps, nullptr, 0, radius, true_len, gather_cap, sS, sC, dsrc);
 }
 
 // Double-double accumulation (Knuth's TwoSum): the gathered magnitudes arrive in an order that changes from run to run (they
@@ -1400,14 +1387,14 @@ __device__ __forceinline__ DD wave_sum_dd(DD v) {
 // The workgroup that finishes last writes theta and prepares the next call (nobody may reset the state while another
 // workgroup has yet to read it).
 constexpr int SOLVE_G = 32;
-constexpr long long SOLVE_COOP_MIN = 1ll << 17;      // (documentation of the default; see solve_coop_min())
+constexpr long long SOLVE_COOP_MIN = 1ll << 17;      // gathered values from which the sweeps of the solve are shared among the workgroups
 static_assert(SOLVE_G <= SIPX_SOLVE_SLOTS, "ProjScalars holds SIPX_SOLVE_SLOTS cooperative slots");
 
 // (the body as a device function: k_l1_solve runs it on its own grid, k_spec_finish -- one workgroup per set -- behind the
 //  decision and the unpacking of a slab-decomposed search; G workgroups take part, this one is number wg)
 template <typename T>
 __device__ void l1_solve_body(ProjScalars<T>* ps, T radius, const T* __restrict__ compact, const double* __restrict__ partials,
-                              long long true_len, double hw_max, int lean_on, int* host_want, long long coop_min, int only_if_settled,
+                              long long true_len, int* host_want, int only_if_settled,
                               const int G, const int wg) {
   constexpr int NT = SIPX_SOLVE_NT;
   // (slab-decomposed, speculative exchange: queued before the host knows whether the search needs its fallback sweeps --
@@ -1420,7 +1407,7 @@ __device__ void l1_solve_body(ProjScalars<T>* ps, T radius, const T* __restrict_
   __shared__ int sh_done;
   const int need = ps->need;
   const long long n_all = need ? (long long)ps->n_compact : 0;
-  const bool coop = G > 1 && n_all >= coop_min;
+  const bool coop = G > 1 && n_all >= SOLVE_COOP_MIN;
   if (!coop && wg != 0) return;
   double theta = 0;
   int iters_done = 0;
@@ -1552,7 +1539,7 @@ __device__ void l1_solve_body(ProjScalars<T>* ps, T radius, const T* __restrict_
     ps->dbg[3] = (coop && ps->dbg[3] < 0) ? -1.0 : (double)iters_done;       // -1: a cooperative sweep was abandoned
     // ---- state for the next call ----
     // a search that the speculative gather settled is followed by a LEAN first pass (two probes instead of eight)
-    ps->lean = (lean_on && need && theta > 0 && ps->spec_ok && !ps->spec_overflow && sh_ca < (double)true_len) ? 1 : 0;
+    ps->lean = (need && theta > 0 && ps->spec_ok && !ps->spec_overflow && sh_ca < (double)true_len) ? 1 : 0;
     ps->want_sample = 0;
     if (need && theta > 0) {
       double hw = ps->hw;
@@ -1565,11 +1552,11 @@ __device__ void l1_solve_body(ProjScalars<T>* ps, T radius, const T* __restrict_
         // and the same from one iteration to the next because the sample is the same subset), so against a small theta it is
         // percent while theta itself moves by hundredths of a percent -- there the previous theta is the better prediction
         // (512^3, default window: searches of the D_x set missed their range on every iteration from 18 on, sampled each time).
-        ps->want_sample = (3.0 * d > hw_max) ? 1 : 0;
+        ps->want_sample = (3.0 * d > L1_HW_MAX) ? 1 : 0;
         // this search followed a change of rho: was theta_prev * rho_old / rho_new (k_ps_rescale) good to the range it gets?
         // Early on it is not (theta is set by x_hat, not by l / rho) and the sampled estimate is; late it is, and then more
         // accurate than a sample, whose error grows as theta shrinks against the spread of the values
-        if (ps->rescaled) ps->resc_bad = d > hw_max ? 1 : 0;
+        if (ps->rescaled) ps->resc_bad = d > L1_HW_MAX ? 1 : 0;
         hw = 3.0 * d;                                  // theta moves slowly while rho, gamma stay put
         // The floor of the half-width follows what the range GATHERS, not a fixed relative width: theta wanders by +-0.1 ... 0.2 %
         // from one iteration to the next long after rho and gamma have settled (256^3, iterations 22 and 26 of the headline run:
@@ -1583,7 +1570,7 @@ __device__ void l1_solve_body(ProjScalars<T>* ps, T radius, const T* __restrict_
           hw_floor = ps->hw * tgt / (double)n_all;
           hw_floor = hw_floor < 1e-3 ? 1e-3 : (hw_floor > 4e-3 ? 4e-3 : hw_floor);
         }
-        hw = hw < hw_floor ? hw_floor : (hw > hw_max ? hw_max : hw);
+        hw = hw < hw_floor ? hw_floor : (hw > L1_HW_MAX ? L1_HW_MAX : hw);
         if (ps->spec_overflow) hw = ps->hw * 0.5;      // the last range gathered too much
       }
       ps->hw = hw;
@@ -1612,9 +1599,8 @@ __device__ void l1_solve_body(ProjScalars<T>* ps, T radius, const T* __restrict_
 
 template <typename T>
 __global__ __launch_bounds__(SIPX_SOLVE_NT) void k_l1_solve(ProjScalars<T>* ps, T radius, const T* __restrict__ compact,
-                                                   const double* __restrict__ partials, long long true_len, double hw_max,
-                                                   int lean_on, int* host_want, long long coop_min, int only_if_settled) {
-  l1_solve_body<T>(ps, radius, compact, partials, true_len, hw_max, lean_on, host_want, coop_min, only_if_settled, (int)gridDim.x,
+                                                   const double* __restrict__ partials, long long true_len, int* host_want, int only_if_settled) {
+  l1_solve_body<T>(ps, radius, compact, partials, true_len, host_want, only_if_settled, (int)gridDim.x,
                    (int)blockIdx.x);
 }
 
@@ -1921,7 +1907,7 @@ __global__ __launch_bounds__(64) void k_spec_decide(ProjScalars<T>* ps, DecideAr
   __syncthreads();
   if (i < PREP_SLOTS + 1 + 2 * world) reg[i] = sreg[i];
   if (i != 0) return;
-  decide_body<T, 0>(ps, da.prox, (T)da.pmin, (T)da.pmax, da.true_len, da.nospec, da.capdiv, world, da.cap_max, sreg);
+  decide_body<T, 0>(ps, da.prox, (T)da.pmin, (T)da.pmax, da.true_len, da.nospec, world, da.cap_max, sreg);
   const bool settled = !(da.prox == PX_L1 && ps->need && !ps->spec_ok);
   if (da.prox == PX_L1 && ps->need && ps->spec_ok) ps->n_compact = (unsigned long long)scount;     // what k_spec_unpack strings together
   ps->gather_overflow = 0;
@@ -2024,7 +2010,7 @@ __global__ __launch_bounds__(SIPX_SOLVE_NT) void k_spec_finish(SpecFinishArgs<T>
   __syncthreads();
   if (i < PREP_SLOTS + 1 + 2 * world) S.reg[i] = sreg[i];
   if (i == 0) {
-    decide_body<T, 0>(ps, S.da.prox, (T)S.da.pmin, (T)S.da.pmax, S.da.true_len, S.da.nospec, S.da.capdiv, world, S.da.cap_max, sreg);
+    decide_body<T, 0>(ps, S.da.prox, (T)S.da.pmin, (T)S.da.pmax, S.da.true_len, S.da.nospec, world, S.da.cap_max, sreg);
     const bool settled = !(S.da.prox == PX_L1 && ps->need && !ps->spec_ok);
     if (S.da.prox == PX_L1 && ps->need && ps->spec_ok) ps->n_compact = (unsigned long long)scount;
     ps->gather_overflow = 0;
@@ -2046,16 +2032,11 @@ __global__ __launch_bounds__(SIPX_SOLVE_NT) void k_spec_finish(SpecFinishArgs<T>
   }
   __threadfence_block();
   __syncthreads();
-  l1_solve_body<T>(ps, S.radius, S.compact, S.partials, S.da.true_len, A.hw_max, A.lean_on, S.host_want, A.coop_min, 1, 1, 0);
+  l1_solve_body<T>(ps, S.radius, S.compact, S.partials, S.da.true_len, S.host_want, 1, 1, 0);
 }
 template <typename T>
 void K<T>::spec_finish(hipStream_t s, SpecFinishArgs<T>& A) {
   if (A.nsets < 1 || A.nsets > SPEC_MAX_SETS) throw std::runtime_error("spec_finish: set count out of range");
-  static const double capdiv = [] { const char* e = getenv("SIPX_L1_CAPDIV"); return e ? atof(e) : 64.0; }();
-  for (int j = 0; j < A.nsets; ++j) A.s[j].da.capdiv = capdiv;
-  A.hw_max = l1_hw_max();
-  A.lean_on = l1_lean_on();
-  A.coop_min = solve_coop_min();
   ObsScope obs_(KID_L1_SOLVE, s, 0.0);
   hipLaunchKernelGGL((k_spec_finish<T>), dim3(A.nsets), dim3(SIPX_SOLVE_NT), 0, s, A);
   SIPX_HIP(hipGetLastError());
@@ -2064,10 +2045,10 @@ void K<T>::spec_finish(hipStream_t s, SpecFinishArgs<T>& A) {
 // v = x_hat - l/rho: where the multiplier term dominates, theta moves like 1/rho when rho is changed.  Re-centre the
 // probes of the coming call on the scaled prediction (and widen the range: the prediction is good to a few percent).
 template <typename T>
-__global__ void k_ps_rescale(ProjScalars<T>* ps, double factor, double hw_max) {
+__global__ void k_ps_rescale(ProjScalars<T>* ps, double factor) {
   if (!(ps->theta_prev > 0)) return;
   ps->theta_prev *= factor;
-  ps->hw = hw_max;
+  ps->hw = L1_HW_MAX;
   ps->rescaled = 1;
   if (ps->resc_bad) ps->want_sample = 1;   // the last such prediction missed the range: sample
   for (int k = 0; k < L1_K; ++k) ps->t[k] = (double)(T)(ps->theta_prev * (1.0 + ps->hw * l1_probe_mult(k)));
@@ -2077,17 +2058,17 @@ __global__ void k_ps_rescale(ProjScalars<T>* ps, double factor, double hw_max) {
 template <typename T>
 void K<T>::ps_rescale(hipStream_t s, ProjScalars<T>* ps, double factor) {
   ObsScope obs_(KID_PS_RESCALE, s, 0.0);
-  hipLaunchKernelGGL((k_ps_rescale<T>), dim3(1), dim3(1), 0, s, ps, factor, l1_hw_max());
+  hipLaunchKernelGGL((k_ps_rescale<T>), dim3(1), dim3(1), 0, s, ps, factor);
   SIPX_HIP(hipGetLastError());
 }
 
 template <typename T>
-__global__ void k_ps_rescale_multi(RescaleMulti<T> A, double hw_max) {
+__global__ void k_ps_rescale_multi(RescaleMulti<T> A) {
   ProjScalars<T>* ps = A.ps[blockIdx.x];
   const double factor = A.factor[blockIdx.x];
   if (!(ps->theta_prev > 0)) return;
   ps->theta_prev *= factor;
-  ps->hw = hw_max;
+  ps->hw = L1_HW_MAX;
   ps->rescaled = 1;
   if (ps->resc_bad) ps->want_sample = 1;   // the last such prediction missed the range: sample
   for (int k = 0; k < L1_K; ++k) ps->t[k] = (double)(T)(ps->theta_prev * (1.0 + ps->hw * l1_probe_mult(k)));
@@ -2098,7 +2079,7 @@ template <typename T>
 void K<T>::ps_rescale_multi(hipStream_t s, const RescaleMulti<T>& A) {
   if (A.n < 1) return;
   ObsScope obs_(KID_PS_RESCALE, s, 0.0);
-  hipLaunchKernelGGL((k_ps_rescale_multi<T>), dim3(A.n), dim3(1), 0, s, A, l1_hw_max());
+  hipLaunchKernelGGL((k_ps_rescale_multi<T>), dim3(A.n), dim3(1), 0, s, A);
   SIPX_HIP(hipGetLastError());
 }
 // The sampled prediction of every sampling set of a slab-decomposed iteration: stage 10 = each rank's share of the sample of
@@ -2123,9 +2104,9 @@ void K<T>::sample_multi(int stage, hipStream_t s, const Grid& g, const SampleMul
   ObsScope obs_(stage != 11 ? KID_SAMPLE : KID_DECIDE, s, 0.0);
   if (stage != 11)
     hipLaunchKernelGGL((k_sample_multi<T, 4>), dim3((unsigned)(nsamp < 1 ? 1 : (nsamp < SAMPLE_WG ? nsamp : SAMPLE_WG)), A.ns), dim3(SAMPLE_NT), 0, s, g, A,
-                       nchunks, nsamp, (unsigned int)stride, l1_hw_max(), l1_lean_on(), gcap);
+                       nchunks, nsamp, (unsigned int)stride, gcap);
   else
-    hipLaunchKernelGGL((k_sample_decide2_multi<T>), dim3(A.ns), dim3(SAMPLE_NT), 0, s, A, l1_hw_max(), l1_lean_on(), gcap);
+    hipLaunchKernelGGL((k_sample_decide2_multi<T>), dim3(A.ns), dim3(SAMPLE_NT), 0, s, A, gcap);
   SIPX_HIP(hipGetLastError());
 }
 
@@ -2156,9 +2137,8 @@ static void chain_stage(int stage, hipStream_t s, const Grid& g, const SetArgs<T
   const int world = hk ? hk->world : 1, rank = hk ? hk->rank : 0;
   const double cap_max = hk ? (double)hk->gcap : 0.0;      // what ALL ranks gather together fits one rank's segment
   const bool vec = SRC == 1 && g.n[0] % 4 == 0;
-  static const double capdiv = [] { const char* e = getenv("SIPX_L1_CAPDIV"); return e ? atof(e) : 64.0; }();
-  const DecideArgs da0{a.prox, (a.flags & F_NOSPEC) ? 1 : 0, (double)a.plo, (double)a.phi, capdiv, cap_max, true_len};
-  const DecideArgs da1{a.prox, 0, (double)a.plo, (double)a.phi, capdiv, cap_max, true_len};
+  const DecideArgs da0{a.prox, (a.flags & F_NOSPEC) ? 1 : 0, (double)a.plo, (double)a.phi, cap_max, true_len};
+  const DecideArgs da1{a.prox, 0, (double)a.plo, (double)a.phi, cap_max, true_len};
 #define SIPX_PASS(MODE)                                                                                            \
   do {                                                                                                             \
     ObsScope obs_(pass_kid(MODE), s, pass_bytes<T>(g, a, v_is_s, SRC, len, false));                                \
@@ -2193,10 +2173,10 @@ static void chain_stage(int stage, hipStream_t s, const Grid& g, const SetArgs<T
         ObsScope obs_(stage != 11 ? KID_SAMPLE : KID_DECIDE, s, 0.0);
         if (stage != 11)
           hipLaunchKernelGGL((k_sample<T, 4>), dim3((unsigned)(nsamp < 1 ? 1 : (nsamp < SAMPLE_WG ? nsamp : SAMPLE_WG))), dim3(SAMPLE_NT), 0, s, g, a, ps,
-                             partials, nchunks, nsamp, (unsigned int)stride, true_len, l1_hw_max(), l1_lean_on(), gcap,
+                             partials, nchunks, nsamp, (unsigned int)stride, true_len, gcap,
                              stage == 10 ? reg : (double*)nullptr, v_is_s);
         else
-          hipLaunchKernelGGL((k_sample_decide2<T>), dim3(1), dim3(SAMPLE_NT), 0, s, ps, reg, a.phi, true_len, l1_hw_max(), l1_lean_on(), gcap);
+          hipLaunchKernelGGL((k_sample_decide2<T>), dim3(1), dim3(SAMPLE_NT), 0, s, ps, reg, a.phi, true_len, gcap);
       }
     }
     if (stage != 0) {
@@ -2228,13 +2208,12 @@ static void chain_stage(int stage, hipStream_t s, const Grid& g, const SetArgs<T
         hipLaunchKernelGGL((k_spec_unpack<T>), dim3(16), dim3(BLOCK), 0, s, ps, compact, gseg0, chunk, world);
       }
       ObsScope obs_(KID_L1_SOLVE, s, 0.0);
-      hipLaunchKernelGGL((k_l1_solve<T>), dim3(1), dim3(SIPX_SOLVE_NT), 0, s, ps, a.phi, compact, partials, true_len, l1_hw_max(), l1_lean_on(),
-                         ctl.host_want, solve_coop_min(), 1);
+      hipLaunchKernelGGL((k_l1_solve<T>), dim3(1), dim3(SIPX_SOLVE_NT), 0, s, ps, a.phi, compact, partials, true_len, ctl.host_want, 1);
     }
   } else if (stage == 9) {      // fallback of a speculative exchange: decision on the all-reduced sums of a refinement round + verdict
     if (a.prox == PX_L1) {
       ObsScope obs_(KID_DECIDE, s, 0.0);
-      hipLaunchKernelGGL((k_decide_round<T>), dim3(1), dim3(64), 0, s, ps, a.prox, a.plo, a.phi, true_len, capdiv, world, cap_max, reg, ctl.seq,
+      hipLaunchKernelGGL((k_decide_round<T>), dim3(1), dim3(64), 0, s, ps, a.prox, a.plo, a.phi, true_len, world, cap_max, reg, ctl.seq,
                          ctl.verdict);
     }
   } else if (stage == 12) {     // ... its bracket is final: gated compaction pass, the rank's magnitudes into its segment
@@ -2246,8 +2225,8 @@ static void chain_stage(int stage, hipStream_t s, const Grid& g, const SetArgs<T
   } else if (stage == 1 || stage == 8) {      // (8: a refinement round whose decision was taken already -- k_spec_decide, k_decide_round)
     if (hk && stage == 1) {
       ObsScope obs_(KID_DECIDE, s, 0.0);
-      hipLaunchKernelGGL((k_decide<T, 0>), dim3(1), dim3(64), 0, s, ps, a.prox, a.plo, a.phi, true_len, da0.nospec, capdiv,
-                         world, cap_max, reg);
+      hipLaunchKernelGGL((k_decide<T, 0>), dim3(1), dim3(64), 0, s, ps, a.prox, a.plo, a.phi, true_len, da0.nospec, world,
+                         cap_max, reg);
     }
     if (a.prox == PX_L1) {
       SIPX_PASS(M_PROBE);
@@ -2259,7 +2238,7 @@ static void chain_stage(int stage, hipStream_t s, const Grid& g, const SetArgs<T
     if (a.prox == PX_L1 && hk) {
       {
         ObsScope obs_(KID_DECIDE, s, 0.0);
-        hipLaunchKernelGGL((k_decide<T, 1>), dim3(1), dim3(64), 0, s, ps, a.prox, a.plo, a.phi, true_len, 0, capdiv, world, cap_max, reg);
+        hipLaunchKernelGGL((k_decide<T, 1>), dim3(1), dim3(64), 0, s, ps, a.prox, a.plo, a.phi, true_len, 0, world, cap_max, reg);
       }
       SIPX_PASS(M_PROBE);
       ObsScope obs_(KID_SLOT_SUMS, s, 0.0);
@@ -2269,7 +2248,7 @@ static void chain_stage(int stage, hipStream_t s, const Grid& g, const SetArgs<T
     if (a.prox == PX_L1) {
       if (hk) {
         ObsScope obs_(KID_DECIDE, s, 0.0);
-        hipLaunchKernelGGL((k_decide<T, 1>), dim3(1), dim3(64), 0, s, ps, a.prox, a.plo, a.phi, true_len, 0, capdiv, world, cap_max, reg);
+        hipLaunchKernelGGL((k_decide<T, 1>), dim3(1), dim3(64), 0, s, ps, a.prox, a.plo, a.phi, true_len, 0, world, cap_max, reg);
       }
       SIPX_PASS(M_COMPACT);
       if (hk) {
@@ -2284,8 +2263,7 @@ static void chain_stage(int stage, hipStream_t s, const Grid& g, const SetArgs<T
                          ctl.host_ovf);
     }
     ObsScope obs_(KID_L1_SOLVE, s, 0.0);
-    hipLaunchKernelGGL((k_l1_solve<T>), dim3(hk ? 1 : SOLVE_G), dim3(SIPX_SOLVE_NT), 0, s, ps, a.phi, compact, partials, true_len, l1_hw_max(),
-                       l1_lean_on(), ctl.host_want, solve_coop_min(), 0);
+    hipLaunchKernelGGL((k_l1_solve<T>), dim3(hk ? 1 : SOLVE_G), dim3(SIPX_SOLVE_NT), 0, s, ps, a.phi, compact, partials, true_len, ctl.host_want, 0);
   }
 #undef SIPX_PASS
   SIPX_HIP(hipGetLastError());
@@ -2378,16 +2356,14 @@ static void launch_chain(hipStream_t s, const Grid& g, const SetArgs<T>& a, int 
 template <typename T>
 void K<T>::search_tail(int stage, hipStream_t s, const SetArgs<T>& a, ProjScalars<T>* ps, double* partials, T* maxpart, T* compact,
                        long long true_len, SampleCtl ctl, double* reg) {
-  static const double capdiv = [] { const char* e = getenv("SIPX_L1_CAPDIV"); return e ? atof(e) : 64.0; }();
   if (a.prox != PX_L1) return;
   if (stage == 1) {
-    const DecideArgs da1{a.prox, 0, (double)a.plo, (double)a.phi, capdiv, 0.0, true_len};
+    const DecideArgs da1{a.prox, 0, (double)a.plo, (double)a.phi, 0.0, true_len};
     ObsScope obs_(KID_SLOT_SUMS, s, 0.0);
     hipLaunchKernelGGL((k_slot_sums<T, 1, true>), dim3(PREP_SLOTS), dim3(BLOCK), 0, s, partials, maxpart, ps, 0, 1, reg ? reg : ps->red, da1);
   } else {
     ObsScope obs_(KID_L1_SOLVE, s, 0.0);
-    hipLaunchKernelGGL((k_l1_solve<T>), dim3(SOLVE_G), dim3(SIPX_SOLVE_NT), 0, s, ps, a.phi, compact, partials, true_len, l1_hw_max(), l1_lean_on(),
-                       ctl.host_want, solve_coop_min(), 0);
+    hipLaunchKernelGGL((k_l1_solve<T>), dim3(SOLVE_G), dim3(SIPX_SOLVE_NT), 0, s, ps, a.phi, compact, partials, true_len, ctl.host_want, 0);
   }
   SIPX_HIP(hipGetLastError());
 }

@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <cstdio>
 
+#include "env_knobs.h"
+
 namespace sipx {
 
 constexpr int BLOCK = 256;        // 4 waves of 64
@@ -82,22 +84,6 @@ struct LaunchObserver {
 // the observer of the calling host thread (a context is driven by one thread at a time); nullptr: nothing is recorded
 const LaunchObserver*& launch_observer();
 
-// A/B switches of the launchers, read from the environment ONCE per context (sipx_finalize -> refresh_env_knobs) instead of by a
-// getenv at every launch: a test that sets a switch builds a new context afterwards.
-struct EnvKnobs {
-  int cds_march = 1;              // SIPX_CDS_MARCH: 0 never, 2 also on grids too small to fill the chip (tests)
-  long long cds_march_zchunk = 0; // SIPX_CDS_MARCH_ZCHUNK (with =2)
-  long long multi_zchunk = 0;     // SIPX_MULTI_ZCHUNK
-  int rhs_march = 1;              // SIPX_RHS_MARCH
-  long long rhs_march_zchunk = 0; // SIPX_RHS_MARCH_ZCHUNK
-  int trace_kernels = 0;          // SIPX_TRACE_KERNELS=1 (debugging): name every launch on stderr and drain the stream behind it
-  int trace_searches = 0;         // SIPX_TRACE_SEARCHES=1: every threshold search of the batched chain that needed its fallback sweeps, on stderr
-  int mark_stride = 0;            // SIPX_MARK_STRIDE: section timing marks on iterations 1-4 and every such iteration after them (1: every iteration; 0: by grid size, parsdmm_step)
-  int q_plan = 1;                 // SIPX_Q_PLAN=0: the Q update regenerates every band value per element (k_q_update) instead of adding planned products
-  int q_table = 1;                // SIPX_Q_TABLE=0: the z-marching products read Q's four stored bands instead of its class table
-};
-const EnvKnobs& env_knobs();
-void refresh_env_knobs();
 // device bytes allocated on behalf of the context the calling thread is building (nullptr: not counted)
 long long*& alloc_tally();
 struct ObsScope {
@@ -305,7 +291,7 @@ struct SetArgs {
 
 struct DecideArgs {        // what the scalar decision of a search needs besides the sums
   int prox, nospec;
-  double pmin, pmax, capdiv, cap_max;
+  double pmin, pmax, cap_max;
   long long true_len;
 };
 // the small steps of a slab-decomposed search for all sets of an iteration at once (kernels_proj.hip: k_spec_sums_pack, k_spec_finish)
@@ -344,9 +330,6 @@ struct SpecFinishArgs {
   int nsets, world;
   long long fchunk;
   unsigned seq;
-  double hw_max;
-  int lean_on;
-  long long coop_min;
   SpecFinishSet<T> s[SPEC_MAX_SETS];
 };
 
