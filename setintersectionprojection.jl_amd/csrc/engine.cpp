@@ -8,6 +8,7 @@
 #include "dwt.h"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -306,6 +307,12 @@ template <typename T>
 struct SetState {
   int op = 0, prox = 0, nblk = 0, ncvx = 0;
   int nblk_or1() const { return nblk > 0 ? nblk : 1; }
+  bool rank_like() const { return ext_kind == EXT_RANK || ext_kind == EXT_NUCLEAR; }
+  // a slice-wise rank / nuclear set on the last grid dimension of the identity: every rank can project the slices of its own z-slab
+  bool sliced_on_last_dim(int ndim) const { return rank_like() && spec.mode == SIPX_MODE_SLICE && spec.dir == ndim - 1 && ident; }
+  // rho changed since this set's last l1 search: v is rescaled and theta moves like 1/rho -- by rescale_factor
+  bool rescaled(T rho) const { return prox == PX_L1 && last_rho > T(0) && last_rho != rho; }
+  double rescale_factor(T rho) const { return (double)last_rho / (double)rho; }
   // caller-supplied sparse operator (SIPX_OP_CSC): CSC for the adjoint, a CSR copy for the forward product; s = A x is
   // materialised in sbuf and every set kernel then runs in its identity shape on a 1-D grid of M entries
   bool custom = false;
@@ -327,7 +334,7 @@ struct SetState {
   // been read), on the others into the pair that is not the snapshot -- the reference's copies y_0 <- y, l_0 <- l never
   // happen (PARSDMM.jl:174-177,200-203).
   T *y = nullptr, *l = nullptr, *dy = nullptr, *lh0 = nullptr, *y0 = nullptr, *s0 = nullptr, *l0 = nullptr;
-  T *y2 = nullptr, *l2 = nullptr;    // third pair of the one-sweep update (allocated on first need, see update_all_sets_in_one_sweep)
+  T *y2 = nullptr, *l2 = nullptr;    // third pair of the one-sweep update (allocated by sipx_finalize, see sweep_launch)
   int snap = -1;                     // -1: no snapshot yet; 0: (y, l) is also the snapshot; 1: (y0, l0) is
   T *lb = nullptr, *ub = nullptr, *ata = nullptr;
   std::vector<void*> halo_allocs;   // bases of the vectors allocated with a front halo
@@ -425,14 +432,8 @@ class Engine : public EngineBase {
     if (ev_sums_) (void)hipEventDestroy(ev_sums_);
     for (hipEvent_t e : open_ev_) if (e) (void)hipEventDestroy(e);
     if (ev_cgb_) (void)hipEventDestroy(ev_cgb_);
-    if (ticket_) (void)hipHostFree((void*)ticket_);
-    if (cg_host_) (void)hipHostFree(cg_host_);
-    if (hres_) (void)hipHostFree(hres_);
-    if (sums_word_) (void)hipHostFree((void*)sums_word_);
+    for (const PinnedBlock& b : pinned_blocks()) if (*b.p) (void)hipHostFree(*b.p);
     dfree(sums_ticket_);
-    if (hlean_) (void)hipHostFree((void*)hlean_);
-    if (hovf_) (void)hipHostFree((void*)hovf_);
-    if (hverd_) (void)hipHostFree((void*)hverd_);
     for (auto e : ev_) (void)hipEventDestroy(e);
     for (auto e : stat_ev_) (void)hipEventDestroy(e);
     for (auto e : cg_ev_) if (e) (void)hipEventDestroy(e);
@@ -524,6 +525,12 @@ class Engine : public EngineBase {
   }
 
   // ------------------------------------------------------------------------------------------
+  // sipx_finalize, step by step.  What the steps hand on that is not state of the context:
+  struct FinalizePlan {
+    long long Npad = 0;          // length of a vector of the exchange layout (world equal chunks; N without a communicator)
+    long long fullpad = 0;       // what a whole vector of the exchange layout takes: the owner of a gathered set
+    bool sparse_wanted = false;  // slab-decomposed: the list allows sparse arrays and the device can map them
+  };
   void finalize(const void* m, const double* rho_ini, int n_rho, double gamma_ini, int feasibility_only,
                 int zero_ini_guess, const void* x0, const void* const* l0, const void* const* y0,
                 double* feasibility_initial) override {
@@ -531,8 +538,44 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
     refresh_env_knobs();                  // the launchers' A/B switches: read once per context, not per launch
     TallyGuard tally(&dev_bytes_);
-    pp_n_ = (int)sets_.size();
     feasibility_only_ = feasibility_only != 0;
+    FinalizePlan P;
+    plan_sets();
+    init_rho_gamma(rho_ini, n_rho, gamma_ini);
+    plan_layout(P);
+    const bool warm = !zero_ini_guess;     // PARSDMM_initialize.jl:304-313
+    all_ranks_or_none([&] {
+      plan_sparse_windows(P);
+      plan_sweep_and_streams();
+      alloc_iterate_arrays(P, m);
+      alloc_scratch_and_partials(P);
+      for (int i = 0; i < p_n_; ++i) init_set(i, P, warm ? l0 : nullptr, warm ? y0 : nullptr);
+      if (search_batch_) {                    // the sets' header segments and decision registers of the batched searches
+        int n2 = 0;
+        for (auto& s : sets_) n2 += s.two_pass ? 1 : 0;
+        fbuf_ = dalloc<T>((size_t)n2 * fast_hdr<T>());
+        stage_ = dalloc<double>((size_t)n2 * (PREP_SLOTS + 1 + 2));
+      }
+      if (dev_io_) {
+        import_dev(m, warm ? x0 : nullptr, warm ? l0 : nullptr, warm ? y0 : nullptr);
+      } else if (warm && x0) {                 // Minkowski: [u; v], 2N entries (sparse arrays: the rank's share)
+        const long long c0 = slab_local_ ? std::max<long long>(0, wlo_) : 0, c1 = slab_local_ ? std::min<long long>(Nx_, whi_) : Nx_;
+        if (c1 > c0) {
+          SIPX_HIP(hipMemcpy(x_ + c0, (const T*)x0 + c0, (c1 - c0) * sizeof(T), hipMemcpyHostToDevice));
+          io_h2d_ += (c1 - c0) * (long long)sizeof(T);
+        }
+      }
+      assemble_Q();
+      build_q_table();
+      create_lane(P);
+    });
+    finalized_ = true;
+    initial_feasibility(feasibility_initial);
+  }
+
+  // step 1: the set list as the solve sees it (the distance term appended), what it allows, which decomposition it gets
+  void plan_sets() {
+    pp_n_ = (int)sets_.size();
     if (!feasibility_only_) {             // PARSDMM_precompute_distribute.jl:17-26: identity operator for 1/2||x-m||^2
       SetState<T> s;
       configure_op(s, SIPX_OP_IDENTITY);
@@ -570,29 +613,28 @@ class Engine : public EngineBase {
     // globally indexed arrays; no N-vector crosses the fabric any more.  For the sets whose projector needs no
     // more than sums over the grid: element-wise ones, l1 / l2 balls and the annulus on the identity or D_x / D_y / D_z / TV.
     slab_ = slab_req_ && comm_ != nullptr;
-    if (slab_) {
-      if (mk_ || stencil_q_) throw std::runtime_error("the slab decomposition is not available for Minkowski contexts or the stencil form of Q");
-      int nfan = 0;
-      for (int i = 0; i < p_n_; ++i) {
-        SetState<T>& s = sets_[i];
-        if (s.custom)
-          throw std::runtime_error("the slab decomposition has no form for a caller-supplied sparse operator (set " + std::to_string(i) + "): use the set decomposition");
-        const bool sliced = (s.ext_kind == EXT_RANK || s.ext_kind == EXT_NUCLEAR) && s.spec.mode == SIPX_MODE_SLICE &&
-                            s.spec.dir == ndim_ - 1 && s.ident;
-        // (SIPX_SLAB_CARD_GATHER=1 / SIPX_SLAB_DFT_GATHER=1: cardinality / the l1-DFT set through an owner rank as well -- A/B switches, tests)
-        if (sliced) s.slab_ext = true;
-        else if (s.prox == PX_CARD && !s.ext_kind && !env_knobs().slab_card_gather) s.slab_card = true;
-        else if (s.ext_kind == EXT_L1_DFT && ndim_ == 3 && s.ident && G_.n[0] >= 2 && !env_knobs().slab_dft_gather) s.slab_dft = true;
-        else if (s.ext_kind || s.prox == PX_CARD) { s.fan = true; s.fan_owner = (nfan++) % comm_->world; }
-        if (s.fan && s.nblk > 1) throw std::runtime_error("internal: a gathered set with more than one operator block");
-        slab_loose_ |= s.slab_ext || s.fan || s.slab_card || s.slab_dft;
-        s.owned = true;
-      }
-      // (the searches with their collectives run on the engine stream, in one order on every rank; the y/l updates that
-      // follow have no collectives inside and are dealt onto the set streams as usual)
+    if (!slab_) return;
+    if (mk_ || stencil_q_) throw std::runtime_error("the slab decomposition is not available for Minkowski contexts or the stencil form of Q");
+    int nfan = 0;
+    for (int i = 0; i < p_n_; ++i) {
+      SetState<T>& s = sets_[i];
+      if (s.custom)
+        throw std::runtime_error("the slab decomposition has no form for a caller-supplied sparse operator (set " + std::to_string(i) + "): use the set decomposition");
+      // (SIPX_SLAB_CARD_GATHER=1 / SIPX_SLAB_DFT_GATHER=1: cardinality / the l1-DFT set through an owner rank as well -- A/B switches, tests)
+      if (s.sliced_on_last_dim(ndim_)) s.slab_ext = true;
+      else if (s.prox == PX_CARD && !s.ext_kind && !env_knobs().slab_card_gather) s.slab_card = true;
+      else if (s.ext_kind == EXT_L1_DFT && ndim_ == 3 && s.ident && G_.n[0] >= 2 && !env_knobs().slab_dft_gather) s.slab_dft = true;
+      else if (s.ext_kind || s.prox == PX_CARD) { s.fan = true; s.fan_owner = (nfan++) % comm_->world; }
+      if (s.fan && s.nblk > 1) throw std::runtime_error("internal: a gathered set with more than one operator block");
+      slab_loose_ |= s.slab_ext || s.fan || s.slab_card || s.slab_dft;
+      s.owned = true;
     }
-    const long long N = G_.N;
-    // rho, gamma (PARSDMM_initialize.jl:58-63,107-114,159)
+    // (the searches with their collectives run on the engine stream, in one order on every rank; the y/l updates that
+    // follow have no collectives inside and are dealt onto the set streams as usual)
+  }
+
+  // step 2 (and sipx_reset): rho, gamma at their initial values (PARSDMM_initialize.jl:58-63,107-114,159)
+  void init_rho_gamma(const double* rho_ini, int n_rho, double gamma_ini) {
     rho_.resize(p_n_);
     gamma_.resize(p_n_);
     if (n_rho == 1) std::fill(rho_.begin(), rho_.end(), (T)rho_ini[0]);
@@ -603,7 +645,11 @@ class Engine : public EngineBase {
     for (int i = 0; i < pp_n_; ++i) any_ncvx_ |= sets_[i].ncvx != 0;
     if (any_ncvx_) g0 = T(0.75);
     std::fill(gamma_.begin(), gamma_.end(), g0);
+  }
 
+  // step 3: halo, the rank's slab and the grids of its kernels, whether sparse arrays are wanted; the communicator's self-test
+  void plan_layout(FinalizePlan& P) {
+    const long long N = G_.N;
     // Q offsets first: the SpMV inputs (x, p) carry a zero halo of max|offset| on both sides so that the
     // kernels need no bounds checks on neighbour loads
     plan_Q_offsets();
@@ -612,7 +658,7 @@ class Engine : public EngineBase {
     for (int a = 0; a < 3; ++a) halo_ = std::max<long long>(halo_, G_.st[a]);
     halo_ = (halo_ + 3) / 4 * 4;
     r0_ = 0; r1_ = Nx_;
-    long long Npad = Nx_;
+    P.Npad = Nx_;
     if (comm_) {
       // z-slabs of the x-step: ceil(n_last / world) planes per rank (the last ranks may hold fewer, or none); the exchange
       // buffers (rhs, x) are padded to world equal chunks, the pad stays zero
@@ -623,7 +669,7 @@ class Engine : public EngineBase {
       if (maxoff > plane_) throw std::runtime_error("the sharded solve needs operators whose A'A reaches no further than one plane of the grid");
       const long long planes = (nlast + comm_->world - 1) / comm_->world;
       chunk_ = planes * plane_;
-      Npad = chunk_ * comm_->world;
+      P.Npad = chunk_ * comm_->world;
       r0_ = std::min<long long>(N, (long long)comm_->rank * chunk_);
       r1_ = std::min<long long>(N, (long long)(comm_->rank + 1) * chunk_);
       prev_ = (r0_ > 0 && r0_ < N) ? comm_->rank - 1 : -1;
@@ -644,21 +690,18 @@ class Engine : public EngineBase {
       Gyl_.e0 = (prev_ >= 0) ? r0_ - plane_ : r0_; Gyl_.e1 = r1_; Gyl_.s0 = r0_;
       if (r1_ <= r0_) { Gr_.e0 = Gr_.e1 = 0; Gyl_.e0 = Gyl_.e1 = 0; }
     }
-    wlo_ = -halo_; whi_ = Npad + halo_;
-    bool sparse_wanted = false;
+    wlo_ = -halo_; whi_ = P.Npad + halo_;
     if (slab_ && !slab_full_req_) {
       int vmm = 0;
       (void)hipDeviceGetAttribute(&vmm, hipDeviceAttributeVirtualMemoryManagementSupported, device_);
-      sparse_wanted = vmm != 0 && env_knobs().slab_local;        // SIPX_SLAB_LOCAL=0: full-size arrays on every rank, as before (A/B switch)
-      for (const auto& st : sets_)
-        if (st.prox == PX_BOUNDS_VEC || (!st.two_pass && st.nblk > 0) || !st.host_ata.empty()) sparse_wanted = false;
+      P.sparse_wanted = vmm != 0 && env_knobs().slab_local && list_allows_sparse();      // SIPX_SLAB_LOCAL=0: full-size arrays on every rank (A/B switch)
       // (lists with materialised sets keep sparse arrays too: their vectors are addressed by global index -- loose_v_ / loose_w_ --
       //  and whole only on the rank that projects a gathered set)
     }
     if (comm_) {                                            // (every rank takes the same branch: the verdict is all-reduced)
       bool any_dft = false;
       for (const auto& st : sets_) any_dft |= st.slab_dft;
-      comm_self_test(sparse_wanted, any_dft);
+      comm_self_test(P.sparse_wanted, any_dft);
       if (selftest_alltoall_failed_) {       // the transposition of the slab-decomposed DFT does not work here: an owner rank projects such sets
         int nfan = 0;
         for (auto& st : sets_) nfan += st.fan ? 1 : 0;
@@ -666,29 +709,118 @@ class Engine : public EngineBase {
           if (st.slab_dft) { st.slab_dft = false; st.fan = true; st.fan_owner = (nfan++) % comm_->world; }
       }
     }
-    // Everything from here to the initial feasibility allocates and uploads -- no collective.  A rank that fails in there (out of
-    // device memory: the likeliest rank-local failure of a first multi-GPU run) used to throw by itself while the others went on
-    // into the collectives of the initial feasibility and waited for it for ever; now every rank reports to one all-reduce on the
-    // self-test's plain buffer and all of them throw together (bench.py then falls back to the next decomposition on every rank).
+  }
+  // per-element bound vectors arrive whole; the initial feasibility of an element-wise set on a difference operator
+  // takes the whole-grid kernels: such lists keep full-size arrays
+  bool list_allows_sparse() const {
+    for (const auto& st : sets_)
+      if (st.prox == PX_BOUNDS_VEC || (!st.two_pass && st.nblk > 0) || !st.host_ata.empty()) return false;
+    return true;
+  }
+
+  // Everything from the communicator's self-test to the initial feasibility allocates and uploads -- no collective.  A rank that
+  // fails in there (out of device memory: the likeliest rank-local failure of a first multi-GPU run) must not throw by itself:
+  // the others would go on into the collectives of the initial feasibility and wait for it for ever.  Every rank reports to one
+  // all-reduce on the self-test's plain buffer and all of them throw together (bench.py then falls back to the next
+  // decomposition on every rank).
+  template <typename Steps>
+  void all_ranks_or_none(Steps allocate_and_upload) {
     std::string alloc_err;
     try {
-    if (comm_ && env_knobs().finalize_fail_rank == comm_->rank)       // SIPX_FINALIZE_FAIL_RANK (tests): this rank "runs out of memory"
-      throw std::runtime_error("test hook: out of device memory");
-    if (slab_ && !slab_full_req_) {
-      slab_local_ = sparse_wanted && !selftest_mapped_failed_;
-      for (const auto& st : sets_) {
-        // per-element bound vectors arrive whole; the initial feasibility of an element-wise set on a difference operator
-        // takes the whole-grid kernels: such lists keep full-size arrays
-        if (st.prox == PX_BOUNDS_VEC || (!st.two_pass && st.nblk > 0) || !st.host_ata.empty()) slab_local_ = false;
-      }
-      if (slab_local_) {
-        // what a rank's kernels touch: its planes, one plane behind (forward differences, the neighbour's copy of x and p), two
-        // planes in front (the recomputed last plane of the rank below, and the plane the z-march loads in front of THAT one)
-        const long long a = r1_ > r0_ ? r0_ : N, b = r1_ > r0_ ? r1_ : N;
-        wlo_ = std::max<long long>(-halo_, a - 2 * plane_ - 64);
-        whi_ = std::min<long long>(Npad + halo_, b + plane_ + 64);
-      }
+      if (comm_ && env_knobs().finalize_fail_rank == comm_->rank)       // SIPX_FINALIZE_FAIL_RANK (tests): this rank "runs out of memory"
+        throw std::runtime_error("test hook: out of device memory");
+      allocate_and_upload();
+    } catch (const std::exception& ex) {
+      if (!comm_ || comm_->world <= 1 || !agree_buf_) throw;
+      alloc_err = ex.what();
     }
+    if (!comm_ || comm_->world <= 1 || !agree_buf_) return;
+    const double flag = alloc_err.empty() ? 0.0 : 1.0;
+    double sum = flag;
+    try {
+      SIPX_HIP(hipMemcpy(agree_buf_, &flag, sizeof(double), hipMemcpyHostToDevice));
+      comm_->allreduce_sum(agree_buf_, 1, SIPX_F64, stream_);
+      SIPX_HIP(hipStreamSynchronize(stream_));
+      SIPX_HIP(hipMemcpy(&sum, agree_buf_, sizeof(double), hipMemcpyDeviceToHost));
+    } catch (const std::exception& ex) {
+      throw std::runtime_error(std::string("sipx_finalize: the ranks could not agree on the outcome of their allocations (") + ex.what() + ")" +
+                               (alloc_err.empty() ? "" : "; this rank: " + alloc_err));
+    }
+    if (sum != 0.0)
+      throw std::runtime_error("sipx_finalize failed on " + std::to_string((int)sum) + " of " + std::to_string(comm_->world) + " ranks while allocating" +
+                               (alloc_err.empty() ? std::string(" (not on this one)") : ": " + alloc_err));
+  }
+
+  // sparse arrays or not (the self-test's verdict is in), and the grid points [wlo_, whi_) a rank then backs with memory
+  void plan_sparse_windows(const FinalizePlan& P) {
+    if (!slab_ || slab_full_req_) return;
+    slab_local_ = P.sparse_wanted && !selftest_mapped_failed_;
+    if (!slab_local_) return;
+    // what a rank's kernels touch: its planes, one plane behind (forward differences, the neighbour's copy of x and p), two
+    // planes in front (the recomputed last plane of the rank below, and the plane the z-march loads in front of THAT one)
+    const long long N = G_.N, a = r1_ > r0_ ? r0_ : N, b = r1_ > r0_ ? r1_ : N;
+    wlo_ = std::max<long long>(-halo_, a - 2 * plane_ - 64);
+    whi_ = std::min<long long>(P.Npad + halo_, b + plane_ + 64);
+  }
+
+  // step 4: which sets the sweep takes, how many set streams exist, whether the searches are batched (nothing is allocated)
+  void plan_sweep_and_streams() {
+    // x0 mode of the one-sweep update: when EVERY y/l update of this context goes through the sweep (its block layout is
+    // compiled in, no set needs the per-set kernels on feasibility iterations), s_0 = A x_0 is recomputed from a snapshot of
+    // x instead of being stored per set: two N-vectors instead of one M_i-vector per set, and 8 N w less traffic on every
+    // Barzilai-Borwein iteration of the headline list.  (A list the sweep does not take whole keeps the per-set s_0 arrays.)
+    yl_multi_ = env_knobs().yl_multi;            // SIPX_YL_MULTI=0: one k_yl launch per set on every iteration (A/B switch, tests)
+    // the lean first passes of the l1 searches in one sweep: pays where the re-reads of x are real traffic (512^3, settled
+    // iterations: 133 -> 139 it/s); at 256^3 three concurrent per-set passes on their own streams are as fast or faster
+    // (1028 against 1012 it/s settled, default window equal), so it is the default above 2^24 grid points only
+    lean_multi_ = env_knobs().lean_multi >= 0 ? env_knobs().lean_multi != 0 : G_.N > (1ll << 24);      // SIPX_LEAN_MULTI: A/B switch, tests
+    {
+      // which sets the sweep takes: all of them (the layouts of C2 / C3 / C5 and of the short lists), or -- one rank only -- the
+      // element-wise and l1 / l2 terms of a list with sets it cannot take (C4), provided the layout of that subset is compiled in
+      MultiArgs<T> probe0;
+      const bool any_sweep = sweep_applicable(0, probe0, true);
+      has_loose_ = false;
+      for (auto& st : sets_) {
+        st.in_sweep = any_sweep && sweep_eligible(st);
+        has_loose_ |= any_sweep && st.owned && !st.in_sweep;
+      }
+      sweep_partial_ = has_loose_;
+    }
+    MultiArgs<T> probe;
+    x0_mode_ = !has_loose_ && sweep_applicable(SIPX_YL_FEAS | SIPX_YL_BB, probe, true);
+    // Set streams when the sweep does the updates: all that runs on them is the threshold / scale searches, chains of short
+    // kernels whose latencies should overlap -- every searching set a stream of its own (up to three; one of them the engine
+    // stream, so that its search starts without a cross-stream dependency), the other sets on the engine stream.  256^3, C3:
+    // 715 -> 760 it/s with three instead of two; 512^3 unchanged; four lose (no search left on the engine stream); 2048^2 with
+    // its one searching set keeps two.  Without the sweep the per-set y/l kernels run there too: two streams, sets dealt round robin.
+    MultiArgs<T> probe2;
+    search_streams_ = sweep_applicable(SIPX_YL_BB, probe2, true);
+    if (search_streams_) {
+      int ntp = 0;
+      for (const auto& st : sets_) ntp += st.two_pass ? 1 : 0;
+      n_set_streams_ = std::max(2, std::min(3, ntp));
+    }
+    {
+      // One rank and EVERY update through the sweep: the searches of all two-pass sets as one chain of launches on the engine
+      // stream (batched_searches) -- no set streams at all.  SIPX_SEARCH_BATCH=0 keeps the per-set chains (A/B switch, tests).
+      int ntp = 0;
+      for (const auto& st : sets_) ntp += (st.two_pass && st.in_sweep) ? 1 : 0;
+      MultiArgs<T> probe3;
+      search_batch_ = !comm_ && env_knobs().search_batch && ntp >= 1 && ntp <= SPEC_MAX_SETS &&
+                      sweep_applicable(SIPX_YL_FEAS | SIPX_YL_BB, probe3, true);
+      if (search_batch_) set_streams_ = false;
+    }
+    {
+      MultiArgs<T> probe4;
+      sweep_plain_ = sweep_applicable(0, probe4, true);
+    }
+    for (const auto& st : sets_) slab_dist_logs_ |= slab_ && !mk_ && st.is_dist;
+    // (the snapshot of x of the x0 mode is a member of the ring of x buffers: nothing to allocate)
+  }
+
+  // step 5a: the vectors of the x-step, and m uploaded
+  void alloc_iterate_arrays(const FinalizePlan& P, const void* m) {
+    const long long N = G_.N, Npad = P.Npad;
     for (int k = 0; k < 3; ++k) { xr_base_[k] = galloc(Npad + 2 * halo_, halo_, 1, 0); xr_[k] = xr_base_[k] + halo_; }
     x_cur_ = 0; x_snap_ = -1;
     x_ = xr_[0]; xold_ = x_;                // (no x-step yet: x_old names x itself)
@@ -709,76 +841,42 @@ class Engine : public EngineBase {
       cg_fused_ = !comm_ && !stencil_q_ && (forced >= 0 ? forced == 1 : (small || cds_.march != 0));
       if (cg_fused_) { p2_base_ = dalloc<T>(Nx_ + 2 * halo_); p2_ = p2_base_ + halo_; }
     }
-    {
-      const long long c0 = std::max<long long>(0, wlo_), c1 = std::min<long long>(N, whi_);      // (sparse arrays: the rank's share only)
-      // (device-resident call: m arrives with the warm start, in the one launch of import_dev below)
-      if (c1 > c0 && !dev_io_) {
-        SIPX_HIP(hipMemcpy(m_ + c0, (const T*)m + c0, (c1 - c0) * sizeof(T), hipMemcpyHostToDevice));
-        io_h2d_ += (c1 - c0) * (long long)sizeof(T);
-      }
+    const long long c0 = std::max<long long>(0, wlo_), c1 = std::min<long long>(N, whi_);      // (sparse arrays: the rank's share only)
+    // (device-resident call: m arrives with the warm start, in the one launch of import_dev)
+    if (c1 > c0 && !dev_io_) {
+      SIPX_HIP(hipMemcpy(m_ + c0, (const T*)m + c0, (c1 - c0) * sizeof(T), hipMemcpyHostToDevice));
+      io_h2d_ += (c1 - c0) * (long long)sizeof(T);
     }
-    {
-      // x0 mode of the one-sweep update: when EVERY y/l update of this context goes through the sweep (its block layout is
-      // compiled in, no set needs the per-set kernels on feasibility iterations), s_0 = A x_0 is recomputed from a snapshot of
-      // x instead of being stored per set: two N-vectors instead of one M_i-vector per set, and 8 N w less traffic on every
-      // Barzilai-Borwein iteration of the headline list.  (A list the sweep does not take whole keeps the per-set s_0 arrays.)
-      yl_multi_ = env_knobs().yl_multi;            // SIPX_YL_MULTI=0: one k_yl launch per set on every iteration (A/B switch, tests)
-      // the lean first passes of the l1 searches in one sweep: pays where the re-reads of x are real traffic (512^3, settled
-      // iterations: 133 -> 139 it/s); at 256^3 three concurrent per-set passes on their own streams are as fast or faster
-      // (1028 against 1012 it/s settled, default window equal), so it is the default above 2^24 grid points only
-      lean_multi_ = env_knobs().lean_multi >= 0 ? env_knobs().lean_multi != 0 : G_.N > (1ll << 24);      // SIPX_LEAN_MULTI: A/B switch, tests
-      {
-        // which sets the sweep takes: all of them (the layouts of C2 / C3 / C5 and of the short lists), or -- one rank only -- the
-        // element-wise and l1 / l2 terms of a list with sets it cannot take (C4), provided the layout of that subset is compiled in
-        MultiArgs<T> probe0;
-        const bool any_sweep = sweep_applicable(0, probe0, true);
-        has_loose_ = false;
-        for (auto& st : sets_) {
-          st.in_sweep = any_sweep && sweep_eligible(st);
-          has_loose_ |= any_sweep && st.owned && !st.in_sweep;
-        }
-        sweep_partial_ = has_loose_;
-      }
-      MultiArgs<T> probe;
-      x0_mode_ = !has_loose_ && sweep_applicable(SIPX_YL_FEAS | SIPX_YL_BB, probe, true);
-      // Set streams when the sweep does the updates: all that runs on them is the threshold / scale searches, chains of short
-      // kernels whose latencies should overlap -- every searching set a stream of its own (up to three; one of them the engine
-      // stream, so that its search starts without a cross-stream dependency), the other sets on the engine stream.  256^3, C3:
-      // 715 -> 760 it/s with three instead of two; 512^3 unchanged; four lose (no search left on the engine stream); 2048^2 with
-      // its one searching set keeps two.  Without the sweep the per-set y/l kernels run there too: two streams, sets dealt round robin.
-      MultiArgs<T> probe2;
-      search_streams_ = sweep_applicable(SIPX_YL_BB, probe2, true);
-      if (search_streams_) {
-        int ntp = 0;
-        for (const auto& st : sets_) ntp += st.two_pass ? 1 : 0;
-        n_set_streams_ = std::max(2, std::min(3, ntp));
-      }
-      {
-        // One rank and EVERY update through the sweep: the searches of all two-pass sets as one chain of launches on the engine
-        // stream (batched_searches) -- no set streams at all.  SIPX_SEARCH_BATCH=0 keeps the per-set chains (A/B switch, tests).
-        int ntp = 0;
-        for (const auto& st : sets_) ntp += (st.two_pass && st.in_sweep) ? 1 : 0;
-        MultiArgs<T> probe3;
-        search_batch_ = !comm_ && env_knobs().search_batch && ntp >= 1 && ntp <= SPEC_MAX_SETS &&
-                        sweep_applicable(SIPX_YL_FEAS | SIPX_YL_BB, probe3, true);
-        if (search_batch_) set_streams_ = false;
-      }
-      {
-        MultiArgs<T> probe4;
-        sweep_plain_ = sweep_applicable(0, probe4, true);
-      }
-      for (const auto& st : sets_) slab_dist_logs_ |= slab_ && !mk_ && st.is_dist;
-      // (the snapshot of x of the x0 mode is a member of the ring of x buffers: nothing to allocate)
-    }
+  }
+
+  // The pinned host blocks of a context {pointer, bytes, fill byte}: sipx_finalize allocates and fills them, sipx_reset fills
+  // them again, the destructor frees them -- each walks this one table.
+  struct PinnedBlock {
+    void** p;
+    size_t bytes;
+    int fill;
+  };
+  std::array<PinnedBlock, 7> pinned_blocks() {
+    const size_t np = (size_t)p_n_ + 1;
+    return {{{(void**)&cg_host_, 2 * sizeof(CgState<T>), 0},
+             {(void**)&ticket_, 64, 0xff},
+             {(void**)&hres_, sizeof(double) * np * SLOTS, 0},
+             {(void**)&sums_word_, 64, 0},
+             {(void**)&hlean_, sizeof(int) * np, 0},
+             {(void**)&hovf_, sizeof(int) * np, 0},
+             {(void**)&hverd_, sizeof(unsigned) * np, 0}}};
+  }
+
+  // step 5b: the exchange buffers of the slab-decomposed searches, the engine-wide scratch, the partial sums, the pinned blocks
+  void alloc_scratch_and_partials(FinalizePlan& P) {
+    const long long N = G_.N, Npad = P.Npad;
     long long maxpad = N;
     for (auto& s : sets_) maxpad = std::max(maxpad, s.Mpad);
     if (comm_) {
       for (int i = 0; i < p_n_; ++i) {
         SetState<T>& s = sets_[i];
         s.owner_rank = i % comm_->world;
-        const bool sliced = (s.ext_kind == EXT_RANK || s.ext_kind == EXT_NUCLEAR) && s.spec.mode == SIPX_MODE_SLICE &&
-                            s.spec.dir == ndim_ - 1 && s.ident;
-        if (!sliced || slab_) continue;               // (slab-decomposed: SetState::slab_ext, no exchange at all)
+        if (!s.sliced_on_last_dim(ndim_) || slab_) continue;               // (slab-decomposed: SetState::slab_ext, no exchange at all)
         if (s.owned != (s.owner_rank == comm_->rank))
           throw std::runtime_error("a slice-wise rank / nuclear set is projected by all ranks: it needs the default set ownership (set i on rank i mod world)");
         s.dist_ext = true;
@@ -813,7 +911,7 @@ class Engine : public EngineBase {
       stage_ = dalloc<double>((size_t)std::max(n2, 1) * (PREP_SLOTS + 1 + 2 * comm_->world));
       sstage_ = dalloc<double>((size_t)std::max(n2, 1) * (2 * SAMPLE_BINS + 3));
     }
-    const long long fullpad = maxpad;   // (what a whole vector of the exchange layout takes: the owner of a gathered set)
+    P.fullpad = maxpad;
     if (slab_local_) {                 // the whole-array scratch is not needed: searches compact at most what the rank's planes hold
       int nbmax = 1;
       for (auto& s : sets_) nbmax = std::max(nbmax, s.nblk_or1());
@@ -833,8 +931,8 @@ class Engine : public EngineBase {
       bool owner = false;
       for (auto& st : sets_) owner |= st.fan && st.fan_owner == comm_->rank;
       loose_whole_ = owner;
-      loose_v_ = owner ? dalloc<T>(fullpad) : loose_alloc(Npad);
-      loose_w_ = owner ? dalloc<T>(fullpad) : loose_alloc(Npad);
+      loose_v_ = owner ? dalloc<T>(P.fullpad) : loose_alloc(Npad);
+      loose_w_ = owner ? dalloc<T>(P.fullpad) : loose_alloc(Npad);
       loose_owned_ = true;
     }
     // (the reduced per-set sums sit right behind the CG partials: sharded, ONE all-reduce can carry both, see argmin_x_head)
@@ -844,216 +942,160 @@ class Engine : public EngineBase {
     maxpart_ = dalloc<T>(2 * NB);     // per-block max | per-block smallest non-zero magnitude
     cg_dev_ = dalloc<CgState<T>>(1);
     dres_ = part_cg_ + 2 * NB;
-    SIPX_HIP(hipHostMalloc((void**)&cg_host_, 2 * sizeof(CgState<T>), hipHostMallocDefault));
-    std::memset(cg_host_, 0, 2 * sizeof(CgState<T>));
-    SIPX_HIP(hipHostMalloc((void**)&ticket_, 64, hipHostMallocDefault));
-    std::memset((void*)ticket_, 0xff, 64);
+    sums_ticket_ = dalloc<unsigned>(1);
+    for (const PinnedBlock& b : pinned_blocks()) {
+      SIPX_HIP(hipHostMalloc(b.p, b.bytes, hipHostMallocDefault));
+      std::memset(*b.p, b.fill, b.bytes);
+    }
     for (int k = 0; k < 2; ++k) SIPX_HIP(hipEventCreateWithFlags(&cg_ev_[k], hipEventDisableTiming));
     SIPX_HIP(hipEventCreateWithFlags(&ev_cgb_, hipEventDisableTiming));
     SIPX_HIP(hipEventCreateWithFlags(&ev_sums_, hipEventDisableTiming));
-    SIPX_HIP(hipHostMalloc((void**)&hres_, sizeof(double) * (p_n_ + 1) * SLOTS, hipHostMallocDefault));
-    std::memset(hres_, 0, sizeof(double) * (p_n_ + 1) * SLOTS);
-    SIPX_HIP(hipHostMalloc((void**)&sums_word_, 64, hipHostMallocDefault));
-    std::memset((void*)sums_word_, 0, 64);
-    sums_ticket_ = dalloc<unsigned>(1);
-    SIPX_HIP(hipHostMalloc((void**)&hlean_, sizeof(int) * (p_n_ + 1), hipHostMallocDefault));
-    std::memset((void*)hlean_, 0, sizeof(int) * (p_n_ + 1));
-    SIPX_HIP(hipHostMalloc((void**)&hovf_, sizeof(int) * (p_n_ + 1), hipHostMallocDefault));
-    std::memset((void*)hovf_, 0, sizeof(int) * (p_n_ + 1));
-    SIPX_HIP(hipHostMalloc((void**)&hverd_, sizeof(unsigned) * (p_n_ + 1), hipHostMallocDefault));
-    std::memset((void*)hverd_, 0, sizeof(unsigned) * (p_n_ + 1));
     for (int k = 0; k < 2 * MAXMARK; ++k) {      // two sets of section marks: a step never waits for its own timing
       hipEvent_t e;
       SIPX_HIP(hipEventCreate(&e));
       ev_.push_back(e);
     }
+  }
 
-    const bool warm = !zero_ini_guess;     // PARSDMM_initialize.jl:304-313
-    for (int i = 0; i < p_n_; ++i) {
-      SetState<T>& s = sets_[i];
-      // explicit AtA bands are kept on the device (every rank: Q is global); descriptor-generated
-      // ones are never stored -- the fused Q update regenerates their values on the fly
-      if (!s.host_ata.empty()) {
-        s.ata = dalloc<T>((size_t)N * s.ata_off.size(), false);
-        SIPX_HIP(hipMemcpy(s.ata, s.host_ata.data(), s.host_ata.size() * sizeof(T), hipMemcpyHostToDevice));
-        io_h2d_ += (long long)(s.host_ata.size() * sizeof(T));
-        s.host_ata.clear();
-        s.host_ata.shrink_to_fit();
+  // step 6: the device state of set i, its streams and scratch; step 7 for its own vectors: bounds and the warm start of l, y
+  void init_set(int i, const FinalizePlan& P, const void* const* l0, const void* const* y0) {
+    const long long N = G_.N;
+    SetState<T>& s = sets_[i];
+    // explicit AtA bands are kept on the device (every rank: Q is global); descriptor-generated
+    // ones are never stored -- the fused Q update regenerates their values on the fly
+    if (!s.host_ata.empty()) {
+      s.ata = dalloc<T>((size_t)N * s.ata_off.size(), false);
+      SIPX_HIP(hipMemcpy(s.ata, s.host_ata.data(), s.host_ata.size() * sizeof(T), hipMemcpyHostToDevice));
+      io_h2d_ += (long long)(s.host_ata.size() * sizeof(T));
+      s.host_ata.clear();
+      s.host_ata.shrink_to_fit();
+    }
+    if ((s.dist_ext || s.slab_ext) && r1_ > r0_) {              // this rank's share of the slices: the projector on the slab grid
+      ExtSpec sp = s.spec;
+      const long long planes = (r1_ - r0_) / plane_;
+      sp.G.n[ndim_ - 1] = planes;
+      sp.G.N = planes * plane_;
+      sp.dims[ndim_ - 1] = planes;
+      s.ext = std::make_shared<ExtProj<T>>(sp, stream_);
+    }
+    if (!s.owned) return;
+    // vectors read through adjoint stencils (w[g - stride]) carry a zero front halo: no bounds checks in the kernels
+    auto halloc = [&](long long n) {
+      T* base = galloc(n + halo_, halo_, s.nblk_or1(), N);
+      s.halo_allocs.push_back(base);
+      return base + halo_;
+    };
+    s.y = halloc(s.Mpad); s.l = halloc(s.Mpad);
+    s.lh0 = galloc(s.Mpad, 0, s.nblk_or1(), N);
+    if (!x0_mode_) s.s0 = galloc(s.Mpad, 0, s.nblk_or1(), N);
+    s.y0 = halloc(s.Mpad); s.l0 = halloc(s.Mpad);       // take turns with y, l as the current iterate: same halo
+    if (!s.ident) s.dy = halloc(s.Mpad);
+    // the third pair of the one-sweep update (two plain iterations in a row: the snapshot has to survive in the other pair
+    // and the sweep never writes in place) -- allocated HERE, so that running out of memory is an error of sipx_finalize and
+    // not of an iteration whose state has already advanced
+    if (sweep_plain_ && s.in_sweep) { s.y2 = halloc(s.Mpad); s.l2 = halloc(s.Mpad); }
+    if (s.custom) upload_custom(s);
+    if (s.slab_dft) {
+      const long long nn[3] = {G_.n[0], G_.n[1], G_.n[2]};
+      s.ddft = std::make_shared<DistDft<T>>(nn, r0_ / plane_, r1_ / plane_, chunk_ / plane_, comm_->world, comm_->rank, (double)s.spec.pmax, stream_);
+    }
+    if (s.ext_kind && !s.dist_ext && !s.slab_ext && !s.slab_dft && !(s.fan && s.fan_owner != comm_->rank)) {      // (a gathered set: its owner only)
+      s.spec.lb = s.host_lb.empty() ? nullptr : s.host_lb.data();
+      s.spec.ub = s.host_ub.empty() ? nullptr : s.host_ub.data();
+      s.spec.basis = s.host_basis.empty() ? nullptr : s.host_basis.data();
+      s.ext = std::make_shared<ExtProj<T>>(s.spec, stream_);
+      if (s.ext_kind == EXT_HISTOGRAM) { s.host_lb.clear(); s.host_ub.clear(); }
+      s.host_basis.clear();
+      s.host_basis.shrink_to_fit();
+    }
+    if (s.fan) {
+      // the gathered sets are collected FIRST in an update (update_y_l), their owners project on a stream of their own while
+      // every rank goes on with the sets of its own slab: each such set keeps its own whole-size vector, the fan stream its scratch
+      s.fanv = (s.fan_owner == comm_->rank || !slab_local_) ? dalloc<T>(P.fullpad) : loose_alloc(P.Npad);
+      SIPX_HIP(hipEventCreateWithFlags(&s.fan_ev, hipEventDisableTiming));
+      if (s.fan_owner == comm_->rank && !fan_st_) {
+        SIPX_HIP(hipStreamCreateWithFlags(&fan_st_, hipStreamNonBlocking));
+        SIPX_HIP(hipEventCreateWithFlags(&fan_fork_, hipEventDisableTiming));
+        fan_ptmp_ = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
+        fan_mpart_ = dalloc<T>(2 * NB);
+        fan_c_ = dalloc<T>(P.fullpad);
       }
-      if ((s.dist_ext || s.slab_ext) && r1_ > r0_) {              // this rank's share of the slices: the projector on the slab grid
-        ExtSpec sp = s.spec;
-        const long long planes = (r1_ - r0_) / plane_;
-        sp.G.n[ndim_ - 1] = planes;
-        sp.G.N = planes * plane_;
-        sp.dims[ndim_ - 1] = planes;
-        s.ext = std::make_shared<ExtProj<T>>(sp, stream_);
-      }
-      if (!s.owned) continue;
-      // vectors read through adjoint stencils (w[g - stride]) carry a zero front halo: no bounds checks in the kernels
-      auto halloc = [&](long long n) {
-        T* base = galloc(n + halo_, halo_, s.nblk_or1(), N);
-        s.halo_allocs.push_back(base);
-        return base + halo_;
+    }
+    if (s.two_pass) {
+      s.ps = dalloc<ProjScalars<T>>(1);
+      s.psf = dalloc<ProjScalars<T>>(1);
+      K<T>::ps_init(stream_, s.ps, scr_i_);
+      K<T>::ps_init(stream_, s.psf, scr_i_);
+    }
+    if ((slab_ || search_batch_) && s.two_pass) {        // searches in lock step: every set keeps its own partial slots and gather buffer
+      s.ptmp = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
+      s.mpart = dalloc<T>(2 * NB);
+      s.cbuf_len = slab_local_ ? std::min<long long>(s.Mpad, std::max<long long>((long long)s.nblk_or1() * (whi_ - wlo_), hooks_.gcap + 64)) : s.Mpad;
+      s.cbuf = dalloc<T>(s.cbuf_len);
+    }
+    const bool had_scratch = s.ptmp != nullptr;
+    if (set_streams_ && !s.ext_kind && s.prox != PX_CARD) {     // those two share the engine-wide scratch: main stream
+      // the engine stream itself is the first of the set streams: the set dealt onto it starts right behind the x-step,
+      // with no cross-stream dependency (about 20 us) on the critical path; that of the others hides behind its work
+      auto grow_pool = [&]() {
+        hipStream_t q = stream_;
+        if (!pool_.empty()) SIPX_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+        pool_.push_back(q);
       };
-      s.y = halloc(s.Mpad); s.l = halloc(s.Mpad);
-      s.lh0 = galloc(s.Mpad, 0, s.nblk_or1(), N);
-      if (!x0_mode_) s.s0 = galloc(s.Mpad, 0, s.nblk_or1(), N);
-      s.y0 = halloc(s.Mpad); s.l0 = halloc(s.Mpad);       // take turns with y, l as the current iterate: same halo
-      if (!s.ident) s.dy = halloc(s.Mpad);
-      // the third pair of the one-sweep update (two plain iterations in a row: the snapshot has to survive in the other pair
-      // and the sweep never writes in place) -- allocated HERE, so that running out of memory is an error of sipx_finalize and
-      // not of an iteration whose state has already advanced
-      if (sweep_plain_ && s.in_sweep) { s.y2 = halloc(s.Mpad); s.l2 = halloc(s.Mpad); }
-      if (s.custom) upload_custom(s);
-      if (s.slab_dft) {
-        const long long nn[3] = {G_.n[0], G_.n[1], G_.n[2]};
-        s.ddft = std::make_shared<DistDft<T>>(nn, r0_ / plane_, r1_ / plane_, chunk_ / plane_, comm_->world, comm_->rank, (double)s.spec.pmax, stream_);
+      if ((int)pool_.size() < n_set_streams_) grow_pool();
+      if (search_streams_) {               // searching sets: streams 1, 2, 0, 1, ... ; the others: the engine stream
+        while ((int)pool_.size() < n_set_streams_) grow_pool();
+        s.st = s.two_pass ? pool_[(size_t)(++search_next_) % pool_.size()] : pool_[0];
+      } else {
+        s.st = pool_[pool_next_++ % pool_.size()];
       }
-      if (s.ext_kind && !s.dist_ext && !s.slab_ext && !s.slab_dft && !(s.fan && s.fan_owner != comm_->rank)) {      // (a gathered set: its owner only)
-        s.spec.lb = s.host_lb.empty() ? nullptr : s.host_lb.data();
-        s.spec.ub = s.host_ub.empty() ? nullptr : s.host_ub.data();
-        s.spec.basis = s.host_basis.empty() ? nullptr : s.host_basis.data();
-        s.ext = std::make_shared<ExtProj<T>>(s.spec, stream_);
-        if (s.ext_kind == EXT_HISTOGRAM) { s.host_lb.clear(); s.host_ub.clear(); }
-        s.host_basis.clear();
-        s.host_basis.shrink_to_fit();
-      }
-      if (s.fan) {
-        // the gathered sets are collected FIRST in an update (update_y_l), their owners project on a stream of their own while
-        // every rank goes on with the sets of its own slab: each such set keeps its own whole-size vector, the fan stream its scratch
-        s.fanv = (s.fan_owner == comm_->rank || !slab_local_) ? dalloc<T>(fullpad) : loose_alloc(Npad);
-        SIPX_HIP(hipEventCreateWithFlags(&s.fan_ev, hipEventDisableTiming));
-        if (s.fan_owner == comm_->rank && !fan_st_) {
-          SIPX_HIP(hipStreamCreateWithFlags(&fan_st_, hipStreamNonBlocking));
-          SIPX_HIP(hipEventCreateWithFlags(&fan_fork_, hipEventDisableTiming));
-          fan_ptmp_ = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-          fan_mpart_ = dalloc<T>(2 * NB);
-          fan_c_ = dalloc<T>(fullpad);
-        }
-      }
-      if (s.two_pass) {
-        s.ps = dalloc<ProjScalars<T>>(1);
-        s.psf = dalloc<ProjScalars<T>>(1);
-        K<T>::ps_init(stream_, s.ps, scr_i_);
-        K<T>::ps_init(stream_, s.psf, scr_i_);
-      }
-      if ((slab_ || search_batch_) && s.two_pass) {        // searches in lock step: every set keeps its own partial slots and gather buffer
+      SIPX_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+      if (s.two_pass && !had_scratch) {
         s.ptmp = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
         s.mpart = dalloc<T>(2 * NB);
-        s.cbuf_len = slab_local_ ? std::min<long long>(s.Mpad, std::max<long long>((long long)s.nblk_or1() * (whi_ - wlo_), hooks_.gcap + 64)) : s.Mpad;
-        s.cbuf = dalloc<T>(s.cbuf_len);
-      }
-      const bool had_scratch = s.ptmp != nullptr;
-      if (set_streams_ && !s.ext_kind && s.prox != PX_CARD) {     // those two share the engine-wide scratch: main stream
-        if ((int)pool_.size() < n_set_streams_) {
-          // the engine stream itself is the first of the set streams: the set dealt onto it starts right behind the x-step,
-          // with no cross-stream dependency (about 20 us) on the critical path; that of the others hides behind its work
-          hipStream_t q = stream_;
-          if (!pool_.empty()) SIPX_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-          pool_.push_back(q);
-        }
-        if (search_streams_) {               // searching sets: streams 1, 2, 0, 1, ... ; the others: the engine stream
-          while ((int)pool_.size() < n_set_streams_) {
-            hipStream_t q2 = stream_;
-            if (!pool_.empty()) SIPX_HIP(hipStreamCreateWithFlags(&q2, hipStreamNonBlocking));
-            pool_.push_back(q2);
-          }
-          s.st = s.two_pass ? pool_[(size_t)(++search_next_) % pool_.size()] : pool_[0];
-        } else {
-          s.st = pool_[pool_next_++ % pool_.size()];
-        }
-        SIPX_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-        if (s.two_pass && !had_scratch) {
-          s.ptmp = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-          s.mpart = dalloc<T>(2 * NB);
-          s.cbuf = dalloc<T>(s.Mpad);
-        }
-      }
-      if (s.prox == SIPX_PROJ_BOUNDS_VEC) {
-        s.lb = dalloc<T>(s.Mpad); s.ub = dalloc<T>(s.Mpad);
-        upload_rows(s, s.host_lb.data(), s.lb);
-        upload_rows(s, s.host_ub.data(), s.ub);
-      }
-      if (warm && !dev_io_ && l0 && l0[i]) upload_rows_ranged(s, (const T*)l0[i], s.l);
-      if (warm && !dev_io_ && y0 && y0[i]) upload_rows_ranged(s, (const T*)y0[i], s.y);
-    }
-    if (search_batch_) {                    // the sets' header segments and decision registers of the batched searches
-      int n2 = 0;
-      for (auto& s : sets_) n2 += s.two_pass ? 1 : 0;
-      fbuf_ = dalloc<T>((size_t)n2 * fast_hdr<T>());
-      stage_ = dalloc<double>((size_t)n2 * (PREP_SLOTS + 1 + 2));
-    }
-    if (dev_io_) {
-      import_dev(m, warm ? x0 : nullptr, warm ? l0 : nullptr, warm ? y0 : nullptr);
-    } else if (warm && x0) {                 // Minkowski: [u; v], 2N entries (sparse arrays: the rank's share)
-      const long long c0 = slab_local_ ? std::max<long long>(0, wlo_) : 0, c1 = slab_local_ ? std::min<long long>(Nx_, whi_) : Nx_;
-      if (c1 > c0) {
-        SIPX_HIP(hipMemcpy(x_ + c0, (const T*)x0 + c0, (c1 - c0) * sizeof(T), hipMemcpyHostToDevice));
-        io_h2d_ += (c1 - c0) * (long long)sizeof(T);
+        s.cbuf = dalloc<T>(s.Mpad);
       }
     }
+    if (s.prox == SIPX_PROJ_BOUNDS_VEC) {
+      s.lb = dalloc<T>(s.Mpad); s.ub = dalloc<T>(s.Mpad);
+      upload_rows(s, s.host_lb.data(), s.lb);
+      upload_rows(s, s.host_ub.data(), s.ub);
+    }
+    if (!dev_io_ && l0 && l0[i]) upload_rows_ranged(s, (const T*)l0[i], s.l);
+    if (!dev_io_ && y0 && y0[i]) upload_rows_ranged(s, (const T*)y0[i], s.y);
+  }
 
-    assemble_Q();
-    build_q_table();
-    {
-      // The lane: one rank, a list the sweep takes in part (C4) -- the slice-rank / nuclear-norm set, a chain of batched GEMMs and
-      // small factorisations with host round trips in it (ext_proj.hip), runs on a stream of its own, queued by a host thread of
-      // its own, beside the searches, the sweep and the other loose sets on the engine stream; its update only needs x.
-      // SIPX_RANK_LANE=0: in turn on the engine stream (A/B switch, tests).
-      const bool lane_on = env_knobs().rank_lane;
-      lane_set_ = -1;
-      if (!comm_ && !mk_ && sweep_partial_ && lane_on)
-        for (int i = 0; i < p_n_ && lane_set_ < 0; ++i) {
-          const SetState<T>& s = sets_[i];
-          if (s.owned && !s.in_sweep && !s.dist_ext && s.ident && !s.custom && s.ext && (s.ext_kind == EXT_RANK || s.ext_kind == EXT_NUCLEAR)) lane_set_ = i;
-        }
-      // Slab-decomposed (round 5): the slice-rank set of a long list projects the z-slices of the rank's own planes -- no collective
-      // anywhere in its update -- so it takes the same lane, beside the lock-step searches, the sweep and the transform set with
-      // their collectives on the engine stream.  A rank's share of C4 is where this pays most: a call on 64 slices is a chain of
-      // small launches with host round trips in it that leaves most of the chip idle.
-      if (comm_ && slab_ && slab_loose_ && !mk_ && sweep_partial_ && lane_on)
-        for (int i = 0; i < p_n_ && lane_set_ < 0; ++i) {
-          const SetState<T>& s = sets_[i];
-          if (s.owned && !s.in_sweep && s.slab_ext && s.ident && !s.custom && s.ext && (s.ext_kind == EXT_RANK || s.ext_kind == EXT_NUCLEAR)) lane_set_ = i;      // (s.ext: a rank without planes has no projector and nothing to overlap)
-        }
-      if (lane_set_ >= 0) {
-        // A stream of the highest priority: the runtime keeps its hardware queues per priority, so the lane can never share a
-        // queue with the engine stream (streams of one priority are dealt onto four queues in turn; in the slab-decomposed
-        // context the lane had landed on the engine stream's queue and ran strictly behind it: tools/lane_overlap.py, 0.00 ms
-        // together), and the chain of small launches that is the iteration's critical path does not wait behind the sweep.
-        int pr_least = 0, pr_greatest = 0;
-        SIPX_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-        SIPX_HIP(hipStreamCreateWithPriority(&lane_st_, hipStreamNonBlocking, pr_greatest));
-        SIPX_HIP(hipEventCreateWithFlags(&lane_fork_, hipEventDisableTiming));
-        SIPX_HIP(hipEventCreateWithFlags(&lane_ev_, hipEventDisableTiming));
-        // (slab-decomposed: a vector of the exchange layout addressed by global index, like loose_v_)
-        if (slab_) lane_v_ = (slab_local_ && !loose_whole_) ? loose_alloc(Npad) : dalloc<T>((size_t)std::max<long long>(fullpad, sets_[lane_set_].Mpad));
-        else lane_v_ = dalloc<T>((size_t)sets_[lane_set_].Mpad);
+  // step 9: The lane: one rank, a list the sweep takes in part (C4) -- the slice-rank / nuclear-norm set, a chain of batched GEMMs and
+  // small factorisations with host round trips in it (ext_proj.hip), runs on a stream of its own, queued by a host thread of
+  // its own, beside the searches, the sweep and the other loose sets on the engine stream; its update only needs x.
+  // SIPX_RANK_LANE=0: in turn on the engine stream (A/B switch, tests).
+  // Slab-decomposed (round 5): the slice-rank set of a long list projects the z-slices of the rank's own planes -- no collective
+  // anywhere in its update -- so it takes the same lane, beside the lock-step searches, the sweep and the transform set with
+  // their collectives on the engine stream.  A rank's share of C4 is where this pays most: a call on 64 slices is a chain of
+  // small launches with host round trips in it that leaves most of the chip idle.
+  void create_lane(const FinalizePlan& P) {
+    const bool one_rank = !comm_ && !mk_ && sweep_partial_;
+    const bool slabbed = comm_ && slab_ && slab_loose_ && !mk_ && sweep_partial_;
+    lane_set_ = -1;
+    if (env_knobs().rank_lane && (one_rank || slabbed))
+      for (int i = 0; i < p_n_ && lane_set_ < 0; ++i) {
+        const SetState<T>& s = sets_[i];
+        // (s.ext: a slab-decomposed rank without planes has no projector and nothing to overlap)
+        if (s.owned && !s.in_sweep && (one_rank ? !s.dist_ext : s.slab_ext) && s.ident && !s.custom && s.ext && s.rank_like()) lane_set_ = i;
       }
-    }
-    } catch (const std::exception& ex) {
-      if (!comm_ || comm_->world <= 1 || !agree_buf_) throw;
-      alloc_err = ex.what();
-    }
-    if (comm_ && comm_->world > 1 && agree_buf_) {
-      const double flag = alloc_err.empty() ? 0.0 : 1.0;
-      double sum = flag;
-      try {
-        SIPX_HIP(hipMemcpy(agree_buf_, &flag, sizeof(double), hipMemcpyHostToDevice));
-        comm_->allreduce_sum(agree_buf_, 1, SIPX_F64, stream_);
-        SIPX_HIP(hipStreamSynchronize(stream_));
-        SIPX_HIP(hipMemcpy(&sum, agree_buf_, sizeof(double), hipMemcpyDeviceToHost));
-      } catch (const std::exception& ex) {
-        throw std::runtime_error(std::string("sipx_finalize: the ranks could not agree on the outcome of their allocations (") + ex.what() + ")" +
-                                 (alloc_err.empty() ? "" : "; this rank: " + alloc_err));
-      }
-      if (sum != 0.0)
-        throw std::runtime_error("sipx_finalize failed on " + std::to_string((int)sum) + " of " + std::to_string(comm_->world) + " ranks while allocating" +
-                                 (alloc_err.empty() ? std::string(" (not on this one)") : ": " + alloc_err));
-    }
-    finalized_ = true;
-
-    initial_feasibility(feasibility_initial);
+    if (lane_set_ < 0) return;
+    // A stream of the highest priority: the runtime keeps its hardware queues per priority, so the lane can never share a
+    // queue with the engine stream (streams of one priority are dealt onto four queues in turn; in the slab-decomposed
+    // context the lane had landed on the engine stream's queue and ran strictly behind it: tools/lane_overlap.py, 0.00 ms
+    // together), and the chain of small launches that is the iteration's critical path does not wait behind the sweep.
+    int pr_least = 0, pr_greatest = 0;
+    SIPX_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
+    SIPX_HIP(hipStreamCreateWithPriority(&lane_st_, hipStreamNonBlocking, pr_greatest));
+    SIPX_HIP(hipEventCreateWithFlags(&lane_fork_, hipEventDisableTiming));
+    SIPX_HIP(hipEventCreateWithFlags(&lane_ev_, hipEventDisableTiming));
+    // (slab-decomposed: a vector of the exchange layout addressed by global index, like loose_v_)
+    if (slab_) lane_v_ = (slab_local_ && !loose_whole_) ? loose_alloc(P.Npad) : dalloc<T>((size_t)std::max<long long>(P.fullpad, sets_[lane_set_].Mpad));
+    else lane_v_ = dalloc<T>((size_t)sets_[lane_set_].Mpad);
   }
 
   // ------------------------------------------------------------------------------------------
@@ -1092,13 +1134,7 @@ class Engine : public EngineBase {
     }
     x_cur_ = 0; x_snap_ = -1;
     x_ = xr_[0]; xold_ = x_;
-    // ---- rho, gamma (PARSDMM_initialize.jl:58-63,107-114,159)
-    if (n_rho == 1) std::fill(rho_.begin(), rho_.end(), (T)rho_ini[0]);
-    else if (n_rho == p_n_) for (int i = 0; i < p_n_; ++i) rho_[i] = (T)rho_ini[i];
-    else throw std::runtime_error("rho_ini must have 1 or p entries");
-    T g0 = (T)gamma_ini;
-    if (any_ncvx_) g0 = T(0.75);
-    std::fill(gamma_.begin(), gamma_.end(), g0);
+    init_rho_gamma(rho_ini, n_rho, gamma_ini);
     // ---- sets
     const bool warm = !zero_ini_guess;
     for (int i = 0; i < p_n_; ++i) {
@@ -1125,13 +1161,7 @@ class Engine : public EngineBase {
       io_h2d_ += Nx_ * (long long)sizeof(T);
     }
     // ---- pinned words and the scalars that live beside them
-    std::memset(cg_host_, 0, 2 * sizeof(CgState<T>));
-    std::memset((void*)ticket_, 0xff, 64);
-    std::memset(hres_, 0, sizeof(double) * (p_n_ + 1) * SLOTS);
-    std::memset((void*)sums_word_, 0, 64);
-    std::memset((void*)hlean_, 0, sizeof(int) * (p_n_ + 1));
-    std::memset((void*)hovf_, 0, sizeof(int) * (p_n_ + 1));
-    std::memset((void*)hverd_, 0, sizeof(unsigned) * (p_n_ + 1));
+    for (const PinnedBlock& b : pinned_blocks()) std::memset(*b.p, b.fill, b.bytes);
     sums_seq_ = 0; cg_seq_ = 0; spec_seq_ = 0;
     spec_searches_ = spec_fallbacks_ = spec_rounds_ = 0;
     batch_searches_ = batch_fallbacks_ = 0;
@@ -1155,24 +1185,24 @@ class Engine : public EngineBase {
     for (int i = 0; i < pp_n_; ++i) {
       SetState<T>& s = sets_[i];
       if (s.dist_ext || s.slab_ext || s.slab_dft) {           // every rank: its slab of slices / its planes of the transform
-        dist_feasibility(s, m_, part_sets_ + ((size_t)i * SLOTS + SL_FE2) * NB, i);
+        dist_feasibility(s, m_, fe2_part(i), i);
         continue;
       }
       if (s.fan) {                              // the set's owner, on the gathered array
         SetArgs<T> a = set_args(s, rho_[i], gamma_[i], 0);
         a.x = m_;
-        fan_feasibility(s, a, part_sets_ + ((size_t)i * SLOTS + SL_FE2) * NB);
+        fan_feasibility(s, a, fe2_part(i));
         continue;
       }
       if (!s.owned) continue;
       if (slab_local_ && !s.two_pass && !s.ext_kind && !s.custom) {      // an element-wise set on the identity: every rank its planes
         SetArgs<T> a = set_args(s, rho_[i], gamma_[i], 0);
         a.x = m_;
-        K<T>::proj_dist_set(stream_, Gr_, a, 1, (const ProjScalars<T>*)nullptr, part_sets_ + ((size_t)i * SLOTS + SL_FE2) * NB);
+        K<T>::proj_dist_set(stream_, Gr_, a, 1, (const ProjScalars<T>*)nullptr, fe2_part(i));
         continue;
       }
       if (slab_ && !s.two_pass && comm_->rank != 0) continue;      // an element-wise set: rank 0 takes the whole grid (one-off)
-      double* dst = part_sets_ + ((size_t)i * SLOTS + SL_FE2) * NB;
+      double* dst = fe2_part(i);
       // Minkowski: TD_OP[i] * [m; 0] = A m for components 1 and 3, A 0 = 0 for component 2 (w_ is still all zero here)
       const T* mm = s.comp == 2 ? w_ : m_;
       if (s.ext_kind) {
@@ -1230,42 +1260,21 @@ class Engine : public EngineBase {
     if (mk_) {    // rhs = sum_i [A 0]'w_i / [0 A]'w_i / [A A]'w_i, w_i = rho_i y_i + l_i, sets added in order per half
       for (int half = 0; half < 2; ++half) {
         T* out = rhs_ + (long long)half * G_.N;
-        int launched = 0;
+        RhsBatch b(stream_, G_, out, false);
         for (int pass = 0; pass < 2; ++pass) {            // own component first (it precedes the sum sets in TD_OP order)
-          RhsArgs<T> a;
-          a.nsets = 0;
-          for (int i = 0; i < p_n_; ++i) {
-            const SetState<T>& s = sets_[i];
-            if (s.comp != (pass == 0 ? half + 1 : 3)) continue;
-            RhsSet<T>& r = a.s[a.nsets++];
-            r.y = s.y; r.l = s.l; r.rho = (T)rho[i]; r.nblk = s.nblk;
-            for (int q = 0; q < 3; ++q) { r.dir[q] = s.dir[q]; r.ih[q] = s.ih[q]; }
-            if (a.nsets == MAX_SETS) {
-              K<T>::rhs_compose(stream_, G_, a, out, launched++ > 0);
-              a.nsets = 0;
-            }
-          }
-          if (a.nsets > 0) K<T>::rhs_compose(stream_, G_, a, out, launched++ > 0);
+          for (int i = 0; i < p_n_; ++i)
+            if (sets_[i].comp == (pass == 0 ? half + 1 : 3)) b.add(sets_[i], (T)rho[i]);
+          b.finish();
         }
-        if (launched == 0) SIPX_HIP(hipMemsetAsync(out, 0, G_.N * sizeof(T), stream_));
+        if (b.launched == 0) SIPX_HIP(hipMemsetAsync(out, 0, G_.N * sizeof(T), stream_));
       }
       return;
     }
-    RhsArgs<T> a;
-    a.nsets = 0;
-    int launched = 0;
-    for (int i = 0; i < p_n_; ++i) {
-      const SetState<T>& s = sets_[i];
-      if (!s.owned || s.custom) continue;
-      RhsSet<T>& r = a.s[a.nsets++];
-      r.y = s.y; r.l = s.l; r.rho = (T)rho[i]; r.nblk = s.nblk;
-      for (int q = 0; q < 3; ++q) { r.dir[q] = s.dir[q]; r.ih[q] = s.ih[q]; }
-      if (a.nsets == MAX_SETS) {
-        K<T>::rhs_compose(stream_, Gr_, a, rhs_, launched++ > 0);
-        a.nsets = 0;
-      }
-    }
-    if (a.nsets > 0 || launched == 0) K<T>::rhs_compose(stream_, Gr_, a, rhs_, launched > 0);
+    RhsBatch b(stream_, Gr_, rhs_, false);
+    for (int i = 0; i < p_n_; ++i)
+      if (sets_[i].owned && !sets_[i].custom) b.add(sets_[i], (T)rho[i]);
+    if (b.launched == 0) b.flush();            // (no set at all: the launch still writes rhs = 0)
+    else b.finish();
     for (int i = 0; i < p_n_; ++i) {       // caller-supplied sparse operators: rhs += A_i'(rho_i y_i + l_i), one launch each
       const SetState<T>& s = sets_[i];
       if (s.owned && s.custom)
@@ -1413,11 +1422,33 @@ class Engine : public EngineBase {
     if (cg_flag) *cg_flag = cg_host_->flag;
   }
 
+  // The four mutually exclusive regimes of a y/l update.  Which one a call is follows from the context and from whether the
+  // sweep takes this call's flags; update_y_l decides it once and runs that regime's steps in order.
+  enum class YlRegime {
+    SweepAll,       // one rank, the sweep takes every set
+    SweepPartial,   // one rank, the sweep takes a subset: loose sets with their per-set kernels, one of them maybe on the lane
+    Slab,           // slab-decomposed: lock-step searches with their collectives, then the sweep or the per-set kernels
+    PerSet          // per-set kernels on the set streams: Minkowski, set-sharded, custom operators, SIPX_YL_MULTI=0
+  };
+  struct LaneGuard {                       // whatever ends update_y_l, the lane's host thread is joined first
+    Engine<T>* e;
+    ~LaneGuard() {
+      if (!e->lane_thr_.joinable()) return;              // (lane_join has run: nothing is left over)
+      // an exception on the caller's thread between lane_start and lane_join: the lane's work is waited for, its projector
+      // goes back to the engine stream, its own error (if any) is dropped in favour of the one that is propagating.  The
+      // iterate of the lane set may be half updated: the solve is over, sipx_reset gives the context a defined state again.
+      e->lane_thr_.join();
+      if (e->lane_st_) (void)hipStreamSynchronize(e->lane_st_);
+      try { e->sets_[e->lane_set_].ext->set_stream(e->stream_); } catch (...) {}
+      e->lane_err_ = nullptr;
+      e->lane_sample_ = -1;
+    }
+  };
+
   void update_y_l(int it, int flags, const double* rho, const double* gamma, double* r_pri, double* r_dual,
                   double* feas) override {
     need_final();
     ObserverGuard og(observer());
-    (void)it;
     rhs_fused_ = false;
     MultiArgs<T> ma;
     const bool sweep = sweep_applicable(flags, ma);
@@ -1425,363 +1456,52 @@ class Engine : public EngineBase {
     // PARTIAL sweep (round 4): set lists with terms the sweep cannot take -- a projector behind a transform or a factorisation,
     // cardinality (BASELINE config 4: l1 behind the DFT, slice rank, cardinality on D_z) -- have their element-wise and l1 / l2 terms
     // updated by the sweep all the same (x read once for them, r_dual in the same pass); the other sets ("loose") keep their
-    // per-set kernels below, on the engine stream.  The fused right-hand side then holds the sets in front of the first loose
+    // per-set kernels, on the engine stream.  The fused right-hand side then holds the sets in front of the first loose
     // one (MultiBlk::in_rhs; the sets are added in order, rhs_compose.jl:24-31) and k_rhs adds the rest.
-    const bool loose_only = sweep && !slab_;
+    const YlRegime regime = slab_ ? YlRegime::Slab : !sweep ? YlRegime::PerSet : has_loose_ ? YlRegime::SweepPartial : YlRegime::SweepAll;
     // (the all-kernel statistics window keeps everything on the engine stream: its event pairs time one kernel at a time)
-    const bool lane_now = (loose_only || (slab_ && sweep)) && lane_set_ >= 0 && stats_mode_ != 2;
-    struct LaneGuard {                       // whatever ends this call, the lane's host thread is joined first
-      Engine<T>* e;
-      ~LaneGuard() {
-        if (!e->lane_thr_.joinable()) return;              // (lane_join has run: nothing is left over)
-        // an exception on the caller's thread between lane_start and lane_join: the lane's work is waited for, its projector
-        // goes back to the engine stream, its own error (if any) is dropped in favour of the one that is propagating.  The
-        // iterate of the lane set may be half updated: the solve is over, sipx_reset gives the context a defined state again.
-        e->lane_thr_.join();
-        if (e->lane_st_) (void)hipStreamSynchronize(e->lane_st_);
-        try { e->sets_[e->lane_set_].ext->set_stream(e->stream_); } catch (...) {}
-        e->lane_err_ = nullptr;
-        e->lane_sample_ = -1;
-      }
-    } lane_guard{this};
+    const bool lane_now = sweep && lane_set_ >= 0 && stats_mode_ != 2;
+    LaneGuard lane_guard{this};
     if (lane_now) lane_start(flags, rho, gamma);
-    if (loose_only) {
-      if (search_batch_) batched_searches(flags, rho, gamma);
-      else sweep_searches(flags, rho, gamma);
-      sweep_launch(flags, rho, gamma, ma);
-      if (!has_loose_) {
-        reduce_set_sums(p_n_ * SLOTS);
-        sums_flags_ = flags;
-        sums_pending_ = true;
-        if (!defer_sums_) {
-          SIPX_HIP(hipEventRecord(ev_sums_, stream_));
-          sums_event_ = ev_sums_;
-          collect_set_sums(rho, r_pri, r_dual, feas);
+    switch (regime) {
+      case YlRegime::SweepAll:
+        one_rank_searches(flags, rho, gamma);
+        sweep_launch(flags, rho, gamma, ma);
+        break;
+      case YlRegime::SweepPartial:
+        one_rank_searches(flags, rho, gamma);
+        sweep_launch(flags, rho, gamma, ma);
+        update_sets_in_turn(flags, rho, gamma, /*skip_swept*/ true, lane_now, /*own_streams*/ false);
+        if (lane_now) lane_join(flags);
+        rest_of_fused_rhs(rho);
+        break;
+      case YlRegime::Slab:
+        slab_lockstep_searches(it, flags, rho, gamma);
+        if (sweep) {
+          // the searches ran in lock step above; every set's update in one sweep over the rank's planes (plus the last plane of
+          // the rank below, recomputed), then the feasibility searches of the two-pass sets with their collectives, on the
+          // engine stream, in one order on every rank
+          for (int i = 0; i < p_n_; ++i)
+            if (sets_[i].two_pass) { sets_[i].last_rho = (T)rho[i]; sets_[i].last_gamma = (T)gamma[i]; }
+          sweep_launch(flags, rho, gamma, ma);
+          if (flags & SIPX_YL_FEAS) slab_feasibility_searches(it, flags, rho, gamma);
+        } else if (set_streams_) {
+          SIPX_HIP(hipEventRecord(ev_fork_, stream_));      // the searches are done: the updates may start
         }
-        return;
-      }
-    }
-    if (mk_) K<T>::sum_uv(stream_, G_.N, x_, x_ + G_.N, w_);
-    if (set_streams_ && !slab_ && !loose_only) SIPX_HIP(hipEventRecord(ev_fork_, stream_));     // x (and u + v) are final: the sets may start
-    if (slab_) {
-      // Slab-decomposed iteration: the threshold / scale searches of ALL sets in lock step -- every rank sweeps its planes,
-      // ONE all-reduce makes the probe sums of all sets global (twice: first pass, gated refinement), ONE all-gather strings
-      // the gathered magnitudes of all l1 sets together; every rank then solves the same small problems (same bits).
-      std::vector<int> tp;
-      for (int i = 0; i < p_n_; ++i)
-        if (sets_[i].two_pass && !sets_[i].fan && !sets_[i].slab_card) tp.push_back(i);
-      if (!tp.empty()) {
-        const size_t RS = (size_t)(PREP_SLOTS + 1 + 2 * comm_->world);
-        const long long seg = hooks_.gcap + GATHER_HDR;
-        int nl1 = 0;
-        for (int i : tp) nl1 += sets_[i].prox == PX_L1 ? 1 : 0;
-        const long long chunk = (long long)std::max(nl1, 1) * seg;
-        std::vector<SetArgs<T>> args(tp.size());
-        std::vector<T*> gseg(tp.size(), nullptr);
-        int k1 = 0;
-        const bool batch = env_knobs().spec_exchange && (int)tp.size() <= SPEC_MAX_SETS;
-        RescaleMulti<T> rs;
-        rs.n = 0;
-        for (size_t j = 0; j < tp.size(); ++j) {
-          SetState<T>& s = sets_[tp[j]];
-          args[j] = set_args(s, (T)rho[tp[j]], (T)gamma[tp[j]], flags);
-          if (s.prox == PX_L1) gseg[j] = gbuf_ + (long long)(k1++) * seg;
-          if (s.prox == PX_L1 && s.last_rho > T(0) && s.last_rho != args[j].rho) {    // v rescaled: theta moves like 1/rho
-            if (batch && rs.n < SPEC_MAX_SETS) { rs.ps[rs.n] = s.ps; rs.factor[rs.n++] = (double)s.last_rho / (double)args[j].rho; }
-            else K<T>::ps_rescale(stream_, s.ps, (double)s.last_rho / (double)args[j].rho);
-          }
-        }
-        K<T>::ps_rescale_multi(stream_, rs);          // (one launch for all of them)
-        // sampled prediction of theta (kernels_proj.hip, k_sample) for the l1 sets whose last search asked for it: every rank
-        // samples its planes, ONE all-reduce adds the histograms (float64 holding exact integers), every rank decides alike
-        std::vector<SampleCtl> ctl(tp.size());
-        bool any_sample = false;
-        const size_t SS = (size_t)(2 * SAMPLE_BINS + 3);
-        for (size_t j = 0; j < tp.size(); ++j) {
-          SetState<T>& s = sets_[tp[j]];
-          ctl[j].host_want = (int*)hlean_ + tp[j];
-          ctl[j].host_ovf = (int*)hovf_ + tp[j];
-          ctl[j].compact_cap = sets_[tp[j]].cbuf_len;
-          ctl[j].runs = env_knobs().l1_sample_runs;
-          const bool rescaled = s.prox == PX_L1 && s.last_rho > T(0) && s.last_rho != args[j].rho;
-          ctl[j].enable = env_knobs().l1_sample && s.prox == PX_L1 && (rescaled || (hlean_[tp[j]] & 0xff) != 0);
-          any_sample |= ctl[j].enable != 0;
-        }
-        if (any_sample && batch && Gr_.n[0] % 4 == 0) {      // every sampling set in one launch per stage
-          SampleMulti<T> sm;
-          sm.ns = 0;
-          for (size_t j = 0; j < tp.size(); ++j) {
-            if (!ctl[j].enable || sets_[tp[j]].prox != PX_L1) continue;
-            SampleSet<T>& S = sm.s[sm.ns++];
-            S.a = args[j]; S.a.ps = sets_[tp[j]].ps; S.ps = sets_[tp[j]].ps; S.partials = sets_[tp[j]].ptmp;
-            S.reg = sstage_ + j * SS; S.true_len = sets_[tp[j]].Mtrue;
-          }
-          K<T>::sample_multi(10, stream_, Gr_, sm, env_knobs().l1_sample_runs, &hooks_);
-          comm_->allreduce_sum(sstage_, tp.size() * SS, SIPX_F64, stream_);
-          K<T>::sample_multi(11, stream_, Gr_, sm, env_knobs().l1_sample_runs, &hooks_);
-        } else if (any_sample) {
-          for (int stage = 10; stage <= 11; ++stage) {
-            for (size_t j = 0; j < tp.size(); ++j)
-              if (ctl[j].enable)
-                K<T>::proj_scalars_stage(stage, stream_, Gr_, args[j], 0, sets_[tp[j]].ps, sets_[tp[j]].ptmp, sets_[tp[j]].mpart,
-                                         sets_[tp[j]].cbuf, sets_[tp[j]].Mtrue, ctl[j], &hooks_, sstage_ + j * SS, gseg[j], chunk);
-            if (stage == 10) comm_->allreduce_sum(sstage_, tp.size() * SS, SIPX_F64, stream_);
-          }
-        }
-        for (size_t j = 0; j < tp.size(); ++j) ctl[j].enable = 0;
-        // Refinement rounds (a gated probe pass + one all-reduce each): the bracket has to shrink until what it holds, over
-        // all ranks, fits the exchange segments -- a rank cannot keep what does not fit.  How many rounds are enqueued follows
-        // the previous search of each l1 set (pinned word written by k_l1_solve; the same on every rank): two more than it
-        // used, all of them while nothing is known (the first searches of a solve); a search that needs more ends in the
-        // error return of collect_set_sums, never in a wrong theta.
-        int rounds = 1;
-        for (size_t j = 0; j < tp.size(); ++j) {
-          SetState<T>& s = sets_[tp[j]];
-          if (s.prox != PX_L1) continue;
-          const int used = (hlean_[tp[j]] >> 8) & 0xff;
-          const int want = s.searches_done < 2 ? 6 : std::min(6, std::max(2, used + 2));
-          rounds = std::max(rounds, want);
-          s.searches_done += 1;
-        }
-        rounds = std::min(6, std::max(rounds, env_knobs().l1_rounds_min));      // SIPX_L1_ROUNDS_MIN: a problem whose brackets shrink slowly
-        rounds = std::max(1, std::min(rounds, env_knobs().l1_rounds_max));      // SIPX_L1_ROUNDS_MAX (tests): force an overflow
-        if (env_knobs().spec_exchange) {
-          spec_exchange_searches(tp, args, ctl, gseg, chunk, 0, false, it, rs.n == 0 && !any_sample);
-        } else {
-        const int order[4] = {0, 1, 2, 3};
-        for (int si = 0; si < 4; ++si) {
-          const int stage = order[si];
-          const int reps = stage == 1 ? rounds : 1;
-          for (int rep = 0; rep < reps; ++rep) {
-            const int st = (stage == 1 && rep > 0) ? 4 : stage;
-            for (size_t j = 0; j < tp.size(); ++j) {
-              SetState<T>& s = sets_[tp[j]];
-              K<T>::proj_scalars_stage(st, stream_, Gr_, args[j], 0, s.ps, s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], &hooks_,
-                                       stage_ + j * RS, gseg[j], chunk);
-            }
-            if (stage < 2 && (stage == 0 || nl1 > 0)) comm_->allreduce_sum(stage_, tp.size() * RS, SIPX_F64, stream_);
-          }
-          if (stage == 2 && nl1 > 0) comm_->allgather(gbuf_, (size_t)chunk, dtype_code(), stream_);
-        }
-        }
-      }
-    }
-    if (slab_ && sweep) {
-      // slab-decomposed: the searches ran in lock step above; every set's update in one sweep over the rank's planes (plus
-      // the last plane of the rank below, recomputed), then the feasibility searches of the two-pass sets with their
-      // collectives, on the engine stream, in one order on every rank
-      for (int i = 0; i < p_n_; ++i)
-        if (sets_[i].two_pass) { sets_[i].last_rho = (T)rho[i]; sets_[i].last_gamma = (T)gamma[i]; }
-      sweep_launch(flags, rho, gamma, ma);
-      if ((flags & SIPX_YL_FEAS) && env_knobs().spec_exchange) {
-        // the feasibility estimates ||P_i(A_i x) - A_i x|| of the two-pass sets: their searches (on v = A_i x itself, each set's
-        // second scalar state) in lock step through the same exchange -- one all-gather for all of them -- then the distances
-        std::vector<int> tf;
-        for (int i = 0; i < pp_n_; ++i)
-          if (sets_[i].two_pass && !sets_[i].fan && !sets_[i].slab_card) tf.push_back(i);
-        if (!tf.empty()) {
-          const long long seg = hooks_.gcap + GATHER_HDR;
-          int nl1 = 0;
-          for (int i = 0; i < p_n_; ++i) nl1 += (sets_[i].two_pass && sets_[i].prox == PX_L1) ? 1 : 0;
-          const long long chunk = (long long)std::max(nl1, 1) * seg;
-          std::vector<SetArgs<T>> fa(tf.size());
-          std::vector<SampleCtl> fc(tf.size());
-          std::vector<T*> fg(tf.size(), nullptr);
-          int k1 = 0;
-          for (size_t j = 0; j < tf.size(); ++j) {
-            fa[j] = set_args(sets_[tf[j]], (T)rho[tf[j]], (T)gamma[tf[j]], flags);
-            fc[j].host_ovf = (int*)hovf_ + tf[j];
-            fc[j].compact_cap = sets_[tf[j]].cbuf_len;
-            if (sets_[tf[j]].prox == PX_L1) fg[j] = gbuf_ + (long long)(k1++) * seg;
-          }
-          spec_exchange_searches(tf, fa, fc, fg, chunk, 1, true, it);
-          for (size_t j = 0; j < tf.size(); ++j)
-            K<T>::proj_dist_set(stream_, Gr_, fa[j], 1, sets_[tf[j]].psf, part_sets_ + ((size_t)tf[j] * SLOTS + SL_FE2) * NB);
-        }
-      } else if (flags & SIPX_YL_FEAS) {
-        for (int i = 0; i < pp_n_; ++i) {
-          SetState<T>& s = sets_[i];
-          if (!s.two_pass || s.fan || s.slab_card) continue;
-          SetArgs<T> a = set_args(s, (T)rho[i], (T)gamma[i], flags);
-          SampleCtl cf;
-          cf.host_ovf = (int*)hovf_ + i;
-          cf.compact_cap = s.cbuf ? s.cbuf_len : scr_c_len_;
-          K<T>::proj_scalars_set(stream_, Gr_, a, 1, s.psf, s.ptmp ? s.ptmp : part_tmp_, s.mpart ? s.mpart : maxpart_, s.cbuf ? s.cbuf : scr_c_,
-                                 s.Mtrue, cf, hooks());
-          K<T>::proj_dist_set(stream_, Gr_, a, 1, s.psf, part_sets_ + ((size_t)i * SLOTS + SL_FE2) * NB);
-        }
-      }
-    }
-    if (set_streams_ && slab_ && !sweep) SIPX_HIP(hipEventRecord(ev_fork_, stream_));      // the searches are done: the updates may start
-    for (int i = 0; i < p_n_ && slab_loose_; ++i)          // the gathered sets first: their owners project beside what follows
-      if (sets_[i].fan) fan_begin(sets_[i], set_args(sets_[i], (T)rho[i], (T)gamma[i], flags));
-    for (int i = 0; i < p_n_; ++i) {
-      SetState<T>& s = sets_[i];
-      if (!s.owned || s.dist_ext) continue;
-      if ((loose_only || (slab_ && sweep)) && s.in_sweep) continue;             // (updated by the sweep above)
-      if (lane_now && i == lane_set_) continue;           // (on its lane, lane_start)
-      SetArgs<T> a = set_args(s, (T)rho[i], (T)gamma[i], flags);
-      if (mk_) a.x = s.comp == 1 ? x_ : (s.comp == 2 ? x_ + G_.N : w_);
-      double* part = part_sets_ + (size_t)i * SLOTS * NB;
-      hipStream_t q = (s.st && !loose_only) ? s.st : stream_;
-      // slab-decomposed: a feasibility search carries collectives -- those stay on the engine stream, in one order on every rank
-      if (slab_ && (flags & SIPX_YL_FEAS) && s.two_pass && i < pp_n_) q = stream_;
-      double* ptmp = s.ptmp ? s.ptmp : part_tmp_;
-      T* mpart = s.mpart ? s.mpart : maxpart_;
-      T* cbuf = s.cbuf ? s.cbuf : scr_c_;
-      if (q != stream_) SIPX_HIP(hipStreamWaitEvent(q, ev_fork_, 0));
-      // where y_new, l_new go (see SetState): snapshot iterations overwrite the old snapshot, the others stay off it
-      const bool snapshot = (flags & (SIPX_YL_BB | SIPX_YL_FIRST)) != 0;
-      const bool first = (flags & SIPX_YL_FIRST) != 0;
-      bool to_other;
-      if (snapshot) to_other = !first && s.snap != 0;     // first: in place, (y, l) becomes the snapshot; no snapshot yet:
-      else to_other = s.snap == 0;                        // the zero-filled other pair stands in for it, as before
-      a.yo = to_other ? s.y0 : s.y;
-      a.lo = to_other ? s.l0 : s.l;
-      const Grid& gs = s.custom ? s.gm : Gr_;          // (the rank's slab when the whole iteration is slab-decomposed)
-      const Grid& gy = s.custom ? s.gm : Gyl_;
-      if (s.custom) {     // s = A x once, then the identity-shaped kernels on the M entries of s
-        K<T>::csr_spmv(q, s.Mtrue, s.d_rowptr, s.d_colidx, s.d_rval, a.x, s.sbuf);
-        a.x = s.sbuf;
-        a.flags |= F_STORE_DY;
-      }
-      if (s.slab_ext) {   // slab-decomposed, slices of the rank's own planes: nothing crosses the fabric
-        q = stream_;
-        K<T>::store_v(q, Gr_, a, 0, loose_v_);
-        if (r1_ > r0_) {
-          ObsScope obs(KID_EXT, stream_, 0.0);
-          s.ext->project(loose_v_ + r0_, false, ptmp, mpart, cbuf);
-        }
-        a.v = loose_v_;
-        a.vsrc = 2;
-      } else if (s.slab_dft) {   // slab-decomposed transform: every rank its planes, one all-to-all each way, the threshold over all ranks
-        q = stream_;
-        K<T>::store_v(q, Gr_, a, 0, loose_v_);
-        {
-          ObsScope obs(KID_EXT, stream_, 0.0);
-          s.ddft->project(loose_v_ + r0_, false, comm_.get(), &hooks_, part_tmp_, maxpart_, scr_c_, scr_c_len_, (int*)hovf_ + i);
-        }
-        a.v = loose_v_;
-        a.vsrc = 2;
-      } else if (s.fan) { // slab-decomposed, a projector that needs the whole array: its owner has gathered v (fan_begin, in front of
-        q = stream_;      // this loop) and scatters P(v)
-        fan_return(s);
-        a.v = s.fanv;
-        a.vsrc = 2;
-      } else if (s.ext_kind) {   // library-backed projector: materialise v, project it in place, hand y to the fused update
-        K<T>::store_v(q, G_, a, 0, scr_v_);
-        {
-          ObsScope obs(KID_EXT, stream_, 0.0);
-          s.ext->project(scr_v_, false, ptmp, mpart, cbuf);
-        }
-        a.vsrc = 2;
-      }
-      if (s.fan) {                        // (projected above)
-        s.last_rho = a.rho;
-        s.last_gamma = a.gamma;
-      } else if (s.two_pass && slab_ && !s.slab_card) {          // (searched above, in lock step with the other sets)
-        s.last_rho = a.rho;
-        s.last_gamma = a.gamma;
-      } else if (s.two_pass) {   // threshold / scale of prox_i from one pass that produces v on the fly (nothing stored)
-        SetArgs<T> ap = a;
-        const bool rescaled = a.prox == PX_L1 && s.last_rho > T(0) && s.last_rho != a.rho;
-        if (rescaled)                                                               // v rescaled: theta moves like 1/rho
-          K<T>::ps_rescale(q, s.ps, (double)s.last_rho / (double)a.rho);
-        // Sampled prediction of theta in front of the search (kernels_proj.hip, k_sample) when the previous search of this
-        // set asked for it (theta moved, fallback sweeps were needed) or rho was changed: its verdict sits in pinned memory, written by k_l1_solve before the sums of that
-        // iteration reached the host.  (A stale word costs time only: the kernels check the device-side state themselves.)
-        SampleCtl ctl;
-        ctl.host_want = (int*)hlean_ + i;
-        ctl.host_ovf = (int*)hovf_ + i;
-        ctl.runs = env_knobs().l1_sample_runs;
-        ctl.enable = env_knobs().l1_sample && !slab_ && a.prox == PX_L1 && !s.custom && (rescaled || (hlean_[i] & 0xff) != 0);
-        K<T>::proj_scalars_set(q, gs, ap, 0, s.ps, ptmp, mpart, cbuf, s.Mtrue, ctl, hooks());
-        s.last_rho = a.rho;
-        s.last_gamma = a.gamma;
-      }
-      K<T>::yl(q, (s.slab_ext || s.slab_dft || (s.fan && s.ident)) ? gs : gy, a, part);      // (no adjoint stencil reads the plane below: nothing to recompute)
-      if (s.custom) K<T>::csc_adj_norm(q, G_.N, s.d_colptr, s.d_rowval, s.d_nzval, s.dy, part + (size_t)SL_ADJ * NB);
-      else if (!s.ident) K<T>::adj_norm(q, gs, a, part + (size_t)SL_ADJ * NB);
-      if ((flags & SIPX_YL_FEAS) && (s.slab_ext || s.slab_dft) && i < pp_n_) dist_feasibility(s, x_, part + (size_t)SL_FE2 * NB, i);
-      else if ((flags & SIPX_YL_FEAS) && s.fan && i < pp_n_) fan_feasibility(s, a, part + (size_t)SL_FE2 * NB);
-      else if ((flags & SIPX_YL_FEAS) && s.ext_kind && i < pp_n_) ext_feasibility(s, a, part + (size_t)SL_FE2 * NB);
-      if ((flags & SIPX_YL_FEAS) && s.two_pass && !s.fan && i < pp_n_) {
-        // ||P_i(s) - s|| with s = A_i x produced on the fly; its own warm-started scalars (psf)
-        SampleCtl cf;
-        cf.host_ovf = (int*)hovf_ + i;
-        cf.compact_cap = s.cbuf ? s.cbuf_len : scr_c_len_;
-        K<T>::proj_scalars_set(q, gs, a, 1, s.psf, ptmp, mpart, cbuf, s.Mtrue, cf, hooks());
-        K<T>::proj_dist_set(q, gs, a, 1, s.psf, part + (size_t)SL_FE2 * NB);
-      }
-      if (to_other) { std::swap(s.y, s.y0); std::swap(s.l, s.l0); }     // (y, l) always names the current iterate
-      if (snapshot) s.snap = 0;
-      else if (to_other && s.snap == 0) s.snap = 1;
-    }
-    // Sets whose projector is shared by all ranks (slice-wise rank / nuclear norm), in set order on every rank, after the
-    // rank's own sets are queued: the owner materialises v = x_hat - l / rho and scatters it by slab (seven links at once:
-    // 7/8 of N w bytes leave it, a broadcast would move seven times that), every rank projects the slices of its slab, a
-    // gather returns P(v), the owner finishes the update with it.  (Engine stream: the
-    // collectives are ordered against the rank's other work; what runs on the second set stream overlaps.)
-    for (int i = 0; i < p_n_; ++i) {
-      SetState<T>& s = sets_[i];
-      if (!s.dist_ext) continue;
-      const int dt = dtype_code();
-      double* part = part_sets_ + (size_t)i * SLOTS * NB;
-      SetArgs<T> a;
-      bool to_other = false;
-      const bool snapshot = (flags & (SIPX_YL_BB | SIPX_YL_FIRST)) != 0;
-      if (s.owned) {
-        a = set_args(s, (T)rho[i], (T)gamma[i], flags);
-        const bool first = (flags & SIPX_YL_FIRST) != 0;
-        if (snapshot) to_other = !first && s.snap != 0;
-        else to_other = s.snap == 0;
-        a.yo = to_other ? s.y0 : s.y;
-        a.lo = to_other ? s.l0 : s.l;
-        K<T>::store_v(stream_, G_, a, 0, scr_v_);
-      }
-      comm_->scatter(scr_v_, (size_t)chunk_, dt, s.owner_rank, stream_);
-      if (s.ext) {
-        ObsScope obs(KID_EXT, stream_, 0.0);
-        s.ext->project(scr_v_ + r0_, false, part_tmp_, maxpart_, scr_c_);
-      }
-      comm_->gather(scr_v_, (size_t)chunk_, dt, s.owner_rank, stream_);
-      if (s.owned) {
-        a.vsrc = 2;
-        K<T>::yl(stream_, G_, a, part);
-        if (to_other) { std::swap(s.y, s.y0); std::swap(s.l, s.l0); }
-        if (snapshot) s.snap = 0;
-        else if (to_other && s.snap == 0) s.snap = 1;
-      }
-      if ((flags & SIPX_YL_FEAS) && i < pp_n_) dist_feasibility(s, x_, part + (size_t)SL_FE2 * NB);
-    }
-    if (lane_now) lane_join(flags);
-    if ((loose_only || (slab_ && sweep)) && rhs_fused_) {
-      // the sweep wrote the sum over the sets in front of the first loose one; the rest, in order
-      RhsArgs<T> ra;
-      ra.nsets = 0;
-      bool behind = false;
-      for (int i = 0; i < p_n_; ++i) {
-        const SetState<T>& s = sets_[i];
-        behind |= !s.in_sweep;
-        if (!behind) continue;
-        RhsSet<T>& r = ra.s[ra.nsets++];
-        r.y = s.y; r.l = s.l; r.rho = (T)rho[i]; r.nblk = s.nblk;
-        for (int qd = 0; qd < 3; ++qd) { r.dir[qd] = s.dir[qd]; r.ih[qd] = s.ih[qd]; }
-        if (ra.nsets == MAX_SETS) {
-          K<T>::rhs_compose(stream_, Gr_, ra, rhs_, 1);
-          ra.nsets = 0;
-        }
-      }
-      if (ra.nsets > 0) K<T>::rhs_compose(stream_, Gr_, ra, rhs_, 1);
-    }
-    for (size_t k = 0; k < pool_.size() && !(slab_ && sweep) && !loose_only; ++k) {   // join: the reductions below see every set
-      if (pool_[k] == stream_) continue;
-      SetState<T>* last = nullptr;                                      // (one event per set stream: after its last set)
-      for (int i = 0; i < p_n_; ++i)
-        if (sets_[i].owned && sets_[i].st == pool_[k]) last = &sets_[i];
-      if (!last) continue;
-      SIPX_HIP(hipEventRecord(last->ev, last->st));
-      SIPX_HIP(hipStreamWaitEvent(stream_, last->ev, 0));
+        for (int i = 0; i < p_n_ && slab_loose_; ++i)          // the gathered sets first: their owners project beside what follows
+          if (sets_[i].fan) fan_begin(sets_[i], set_args(sets_[i], (T)rho[i], (T)gamma[i], flags));
+        update_sets_in_turn(flags, rho, gamma, /*skip_swept*/ sweep, lane_now, /*own_streams*/ true);
+        if (lane_now) lane_join(flags);
+        if (sweep) rest_of_fused_rhs(rho);
+        else join_set_streams([this](int i) { return sets_[i].owned; });      // the reductions see every set
+        break;
+      case YlRegime::PerSet:
+        if (mk_) K<T>::sum_uv(stream_, G_.N, x_, x_ + G_.N, w_);
+        if (set_streams_) SIPX_HIP(hipEventRecord(ev_fork_, stream_));     // x (and u + v) are final: the sets may start
+        update_sets_in_turn(flags, rho, gamma, /*skip_swept*/ false, /*lane_now*/ false, /*own_streams*/ true);
+        update_sets_of_all_ranks(flags, rho, gamma);
+        join_set_streams([this](int i) { return sets_[i].owned; });      // the reductions see every set
+        break;
     }
     // Minkowski: evol_x runs over all 2N unknowns (PARSDMM.jl:145); the distance-term kernel only saw u + v
     if (mk_) K<T>::log3(stream_, Nx_, x_, (const T*)nullptr, xold_, part_sets_ + (size_t)p_n_ * SLOTS * NB);
@@ -1795,17 +1515,388 @@ class Engine : public EngineBase {
     }
   }
 
+  // one rank, the sweep does the updates: the searches of its two-pass sets, batched or on the set streams
+  void one_rank_searches(int flags, const double* rho, const double* gamma) {
+    if (search_batch_) batched_searches(flags, rho, gamma);
+    else sweep_searches(flags, rho, gamma);
+  }
+
+  // ---- small rules of the y/l update, each written once --------------------------------------------------------------------
+  double* set_part(int i) const { return part_sets_ + (size_t)i * SLOTS * NB; }                 // the reduction slots of set i
+  double* fe2_part(int i) const { return part_sets_ + ((size_t)i * SLOTS + SL_FE2) * NB; }      // ... its feasibility slots
+
+  // a set's search scratch: its own (searches in lock step, set streams) or the engine-wide one; cap: elements the gather buffer holds
+  struct SetScratch {
+    double* ptmp;
+    T *mpart, *cbuf;
+    long long cap;
+  };
+  SetScratch scratch_of(const SetState<T>& s) const {
+    return {s.ptmp ? s.ptmp : part_tmp_, s.mpart ? s.mpart : maxpart_, s.cbuf ? s.cbuf : scr_c_, s.cbuf ? s.cbuf_len : scr_c_len_};
+  }
+
+  // SampleCtl of set i's prox search: the set's pinned words, and the sampled prediction of theta in front of the search
+  // (kernels_proj.hip, k_sample) when the previous search of this set asked for it (theta moved, fallback sweeps were needed) or
+  // rho was changed: its verdict sits in pinned memory, written by k_l1_solve before the sums of that iteration reached the
+  // host.  (A stale word costs time only: the kernels check the device-side state themselves.)  `here`: what the calling
+  // regime adds to that rule.
+  SampleCtl search_ctl(int i, bool rescaled, bool here) const {
+    SampleCtl c;
+    c.host_want = (int*)hlean_ + i;
+    c.host_ovf = (int*)hovf_ + i;
+    c.runs = env_knobs().l1_sample_runs;
+    c.enable = env_knobs().l1_sample && here && sets_[i].prox == PX_L1 && (rescaled || (hlean_[i] & 0xff) != 0);
+    return c;
+  }
+
+  // Where a per-set update writes y_new, l_new (a.yo, a.lo) and how (y, l) / (y0, l0) / snap rotate once it is queued (see
+  // SetState): snapshot iterations overwrite the old snapshot, the others stay off it.  First iteration: in place, (y, l) becomes
+  // the snapshot; no snapshot yet: the zero-filled other pair stands in for it.  (The sweep never writes in place and has a
+  // third pair: its own rule is in sweep_launch.)
+  struct YlTarget {
+    bool to_other, snapshot;
+  };
+  static YlTarget aim(const SetState<T>& s, int flags, SetArgs<T>& a) {
+    const bool snapshot = (flags & (SIPX_YL_BB | SIPX_YL_FIRST)) != 0, first = (flags & SIPX_YL_FIRST) != 0;
+    const bool to_other = snapshot ? (!first && s.snap != 0) : (s.snap == 0);
+    a.yo = to_other ? s.y0 : s.y;
+    a.lo = to_other ? s.l0 : s.l;
+    return {to_other, snapshot};
+  }
+  static void rotate(SetState<T>& s, YlTarget t) {
+    if (t.to_other) { std::swap(s.y, s.y0); std::swap(s.l, s.l0); }     // (y, l) always names the current iterate
+    if (t.snapshot) s.snap = 0;
+    else if (t.to_other && s.snap == 0) s.snap = 1;
+  }
+
+  // the engine stream waits for every set stream, behind the last of the sets `on` names that was dealt onto it (one event per stream)
+  template <typename Pred>
+  void join_set_streams(Pred on) {
+    for (size_t k = 0; k < pool_.size(); ++k) {
+      if (pool_[k] == stream_) continue;
+      SetState<T>* last = nullptr;
+      for (int i = 0; i < p_n_; ++i)
+        if (sets_[i].st == pool_[k] && on(i)) last = &sets_[i];
+      if (!last) continue;
+      SIPX_HIP(hipEventRecord(last->ev, last->st));
+      SIPX_HIP(hipStreamWaitEvent(stream_, last->ev, 0));
+    }
+  }
+
+  // the sets of a right-hand side, MAX_SETS to a launch: the first launch writes `out` (unless it accumulates), the others add
+  struct RhsBatch {
+    hipStream_t q;
+    const Grid& g;
+    T* out;
+    int launched;
+    RhsArgs<T> a;
+    RhsBatch(hipStream_t q_, const Grid& g_, T* out_, bool accumulate) : q(q_), g(g_), out(out_), launched(accumulate ? 1 : 0) { a.nsets = 0; }
+    void add(const SetState<T>& s, T rho) {
+      RhsSet<T>& r = a.s[a.nsets++];
+      r.y = s.y; r.l = s.l; r.rho = rho; r.nblk = s.nblk;
+      for (int d = 0; d < 3; ++d) { r.dir[d] = s.dir[d]; r.ih[d] = s.ih[d]; }
+      if (a.nsets == MAX_SETS) flush();
+    }
+    void flush() {
+      K<T>::rhs_compose(q, g, a, out, launched++ > 0);
+      a.nsets = 0;
+    }
+    void finish() { if (a.nsets > 0) flush(); }
+  };
+
+  // ---- steps of the y/l update ------------------------------------------------------------------------------------------------
+  // The two-pass sets among the first n that search in lock step on a slab-decomposed grid (a gathered set and cardinality have
+  // searches of their own), their arguments and their segments in rank 0's chunk of the full-size exchange buffer: one per l1
+  // set, `chunk` to the next rank's.  (The distance term is never a two-pass set: n = p_n_ and n = pp_n_ name the same sets.)
+  struct LockStep {
+    std::vector<int> tp;
+    std::vector<SetArgs<T>> args;
+    std::vector<SampleCtl> ctl;
+    std::vector<T*> gseg;              // (empty: no exchange -- the batched searches of one rank)
+    long long chunk = 0;
+    int nl1 = 0;
+    size_t RS = 0;                     // doubles of a set's region of stage_
+    int v_is_s = 0;
+    bool feas_ps = false;              // the searches of the feasibility estimates: each set's second scalar state
+    const ChainHooks* hk = nullptr;
+  };
+  LockStep lockstep_sets(int n, int flags, const double* rho, const double* gamma) {
+    LockStep L;
+    for (int i = 0; i < n; ++i)
+      if (sets_[i].two_pass && !sets_[i].fan && !sets_[i].slab_card) L.tp.push_back(i);
+    if (L.tp.empty()) return L;
+    const long long seg = hooks_.gcap + GATHER_HDR;
+    L.args.resize(L.tp.size());
+    L.ctl.resize(L.tp.size());
+    L.gseg.assign(L.tp.size(), nullptr);
+    for (size_t j = 0; j < L.tp.size(); ++j) {
+      const SetState<T>& s = sets_[L.tp[j]];
+      L.args[j] = set_args(s, (T)rho[L.tp[j]], (T)gamma[L.tp[j]], flags);
+      if (s.prox == PX_L1) L.gseg[j] = gbuf_ + (long long)(L.nl1++) * seg;
+    }
+    L.chunk = (long long)std::max(L.nl1, 1) * seg;
+    L.RS = (size_t)(PREP_SLOTS + 1 + 2 * comm_->world);
+    L.hk = &hooks_;
+    return L;
+  }
+  // one stage of the search of set j of a lock-step group; reg: the set's region of the staging buffer, seg / segchunk: its
+  // segment in rank 0's chunk of an exchange buffer and the distance to the next rank's
+  void search_stage(int stage, hipStream_t q, const LockStep& L, size_t j, double* reg, T* seg, long long segchunk) {
+    SetState<T>& s = sets_[L.tp[j]];
+    K<T>::proj_scalars_stage(stage, q, Gr_, L.args[j], L.v_is_s, L.feas_ps ? s.psf : s.ps, s.ptmp, s.mpart, s.cbuf, s.Mtrue, L.ctl[j], L.hk,
+                             reg, seg, segchunk);
+  }
+  void search_stage(int stage, hipStream_t q, const LockStep& L, size_t j) {      // (staging region, full-size exchange segment)
+    search_stage(stage, q, L, j, stage_ + j * L.RS, L.gseg.empty() ? nullptr : L.gseg[j], L.chunk);
+  }
+
+  // Slab-decomposed iteration: the threshold / scale searches of ALL sets in lock step -- every rank sweeps its planes,
+  // ONE all-reduce makes the probe sums of all sets global (twice: first pass, gated refinement), ONE all-gather strings
+  // the gathered magnitudes of all l1 sets together; every rank then solves the same small problems (same bits).
+  void slab_lockstep_searches(int it, int flags, const double* rho, const double* gamma) {
+    LockStep L = lockstep_sets(p_n_, flags, rho, gamma);
+    if (L.tp.empty()) return;
+    const std::vector<int>& tp = L.tp;
+    const bool batch = env_knobs().spec_exchange && (int)tp.size() <= SPEC_MAX_SETS;
+    RescaleMulti<T> rs;
+    rs.n = 0;
+    // sampled prediction of theta (kernels_proj.hip, k_sample) for the l1 sets whose last search asked for it: every rank
+    // samples its planes, ONE all-reduce adds the histograms (float64 holding exact integers), every rank decides alike
+    bool any_sample = false;
+    const size_t SS = (size_t)(2 * SAMPLE_BINS + 3);
+    for (size_t j = 0; j < tp.size(); ++j) {
+      SetState<T>& s = sets_[tp[j]];
+      const bool rescaled = s.rescaled(L.args[j].rho);
+      if (rescaled) {
+        if (batch && rs.n < SPEC_MAX_SETS) { rs.ps[rs.n] = s.ps; rs.factor[rs.n++] = s.rescale_factor(L.args[j].rho); }
+        else K<T>::ps_rescale(stream_, s.ps, s.rescale_factor(L.args[j].rho));
+      }
+      L.ctl[j] = search_ctl(tp[j], rescaled, true);
+      L.ctl[j].compact_cap = s.cbuf_len;
+      any_sample |= L.ctl[j].enable != 0;
+    }
+    K<T>::ps_rescale_multi(stream_, rs);          // (one launch for all of them)
+    if (any_sample && batch && Gr_.n[0] % 4 == 0) {      // every sampling set in one launch per stage
+      SampleMulti<T> sm;
+      sm.ns = 0;
+      for (size_t j = 0; j < tp.size(); ++j) {
+        if (!L.ctl[j].enable || sets_[tp[j]].prox != PX_L1) continue;
+        SampleSet<T>& S = sm.s[sm.ns++];
+        S.a = L.args[j]; S.a.ps = sets_[tp[j]].ps; S.ps = sets_[tp[j]].ps; S.partials = sets_[tp[j]].ptmp;
+        S.reg = sstage_ + j * SS; S.true_len = sets_[tp[j]].Mtrue;
+      }
+      K<T>::sample_multi(10, stream_, Gr_, sm, env_knobs().l1_sample_runs, &hooks_);
+      comm_->allreduce_sum(sstage_, tp.size() * SS, SIPX_F64, stream_);
+      K<T>::sample_multi(11, stream_, Gr_, sm, env_knobs().l1_sample_runs, &hooks_);
+    } else if (any_sample) {
+      for (int stage = 10; stage <= 11; ++stage) {
+        for (size_t j = 0; j < tp.size(); ++j)
+          if (L.ctl[j].enable) search_stage(stage, stream_, L, j, sstage_ + j * SS, L.gseg[j], L.chunk);
+        if (stage == 10) comm_->allreduce_sum(sstage_, tp.size() * SS, SIPX_F64, stream_);
+      }
+    }
+    for (size_t j = 0; j < tp.size(); ++j) L.ctl[j].enable = 0;
+    // Refinement rounds (a gated probe pass + one all-reduce each): the bracket has to shrink until what it holds, over
+    // all ranks, fits the exchange segments -- a rank cannot keep what does not fit.  How many rounds are enqueued follows
+    // the previous search of each l1 set (pinned word written by k_l1_solve; the same on every rank): two more than it
+    // used, all of them while nothing is known (the first searches of a solve); a search that needs more ends in the
+    // error return of collect_set_sums, never in a wrong theta.
+    int rounds = 1;
+    for (size_t j = 0; j < tp.size(); ++j) {
+      SetState<T>& s = sets_[tp[j]];
+      if (s.prox != PX_L1) continue;
+      const int used = (hlean_[tp[j]] >> 8) & 0xff;
+      const int want = s.searches_done < 2 ? 6 : std::min(6, std::max(2, used + 2));
+      rounds = std::max(rounds, want);
+      s.searches_done += 1;
+    }
+    rounds = std::min(6, std::max(rounds, env_knobs().l1_rounds_min));      // SIPX_L1_ROUNDS_MIN: a problem whose brackets shrink slowly
+    rounds = std::max(1, std::min(rounds, env_knobs().l1_rounds_max));      // SIPX_L1_ROUNDS_MAX (tests): force an overflow
+    if (env_knobs().spec_exchange) {
+      spec_exchange_searches(L, it);
+      return;
+    }
+    for (int stage = 0; stage < 4; ++stage) {
+      const int reps = stage == 1 ? rounds : 1;
+      for (int rep = 0; rep < reps; ++rep) {
+        const int st = (stage == 1 && rep > 0) ? 4 : stage;
+        for (size_t j = 0; j < tp.size(); ++j) search_stage(st, stream_, L, j);
+        if (stage < 2 && (stage == 0 || L.nl1 > 0)) comm_->allreduce_sum(stage_, tp.size() * L.RS, SIPX_F64, stream_);
+      }
+      if (stage == 2 && L.nl1 > 0) comm_->allgather(gbuf_, (size_t)L.chunk, dtype_code(), stream_);
+    }
+  }
+
+  // Slab-decomposed, behind the sweep: the feasibility estimates ||P_i(A_i x) - A_i x|| of the two-pass sets.
+  void slab_feasibility_searches(int it, int flags, const double* rho, const double* gamma) {
+    if (env_knobs().spec_exchange) {
+      // their searches (on v = A_i x itself, each set's second scalar state) in lock step through the same exchange -- one
+      // all-gather for all of them -- then the distances
+      LockStep L = lockstep_sets(pp_n_, flags, rho, gamma);
+      if (L.tp.empty()) return;
+      for (size_t j = 0; j < L.tp.size(); ++j) {
+        L.ctl[j].host_ovf = (int*)hovf_ + L.tp[j];
+        L.ctl[j].compact_cap = sets_[L.tp[j]].cbuf_len;
+      }
+      L.v_is_s = 1;
+      L.feas_ps = true;
+      spec_exchange_searches(L, it);
+      for (size_t j = 0; j < L.tp.size(); ++j) K<T>::proj_dist_set(stream_, Gr_, L.args[j], 1, sets_[L.tp[j]].psf, fe2_part(L.tp[j]));
+      return;
+    }
+    for (int i = 0; i < pp_n_; ++i) {
+      SetState<T>& s = sets_[i];
+      if (!s.two_pass || s.fan || s.slab_card) continue;
+      SetArgs<T> a = set_args(s, (T)rho[i], (T)gamma[i], flags);
+      const SetScratch scr = scratch_of(s);
+      SampleCtl cf;
+      cf.host_ovf = (int*)hovf_ + i;
+      cf.compact_cap = scr.cap;
+      K<T>::proj_scalars_set(stream_, Gr_, a, 1, s.psf, scr.ptmp, scr.mpart, scr.cbuf, s.Mtrue, cf, hooks());
+      K<T>::proj_dist_set(stream_, Gr_, a, 1, s.psf, fe2_part(i));
+    }
+  }
+
+  // the per-set updates of this rank's sets, in set order; skip_swept: the sweep has updated its sets; lane_now: the lane set is
+  // on its lane (lane_start); own_streams: every set on the stream it was dealt onto (false: all on the engine stream)
+  void update_sets_in_turn(int flags, const double* rho, const double* gamma, bool skip_swept, bool lane_now, bool own_streams) {
+    for (int i = 0; i < p_n_; ++i) {
+      const SetState<T>& s = sets_[i];
+      if (!s.owned || s.dist_ext || (skip_swept && s.in_sweep) || (lane_now && i == lane_set_)) continue;
+      update_one_set(i, flags, rho, gamma, own_streams);
+    }
+  }
+
+  // The per-set update of set i: prox_i of v = x_hat - l / rho -- the threshold / scale search of a two-pass set, or a projector
+  // on the materialised v -- then the fused update of y and l with its sums, and the set's feasibility estimate when asked.
+  void update_one_set(int i, int flags, const double* rho, const double* gamma, bool own_stream) {
+    SetState<T>& s = sets_[i];
+    const bool feas = (flags & SIPX_YL_FEAS) && i < pp_n_;
+    SetArgs<T> a = set_args(s, (T)rho[i], (T)gamma[i], flags);
+    if (mk_) a.x = s.comp == 1 ? x_ : (s.comp == 2 ? x_ + G_.N : w_);
+    double* part = set_part(i);
+    hipStream_t q = (s.st && own_stream) ? s.st : stream_;
+    // slab-decomposed: a feasibility search carries collectives -- those stay on the engine stream, in one order on every rank
+    if (slab_ && feas && s.two_pass) q = stream_;
+    const SetScratch scr = scratch_of(s);
+    if (q != stream_) SIPX_HIP(hipStreamWaitEvent(q, ev_fork_, 0));
+    const YlTarget tgt = aim(s, flags, a);
+    const Grid& gs = s.custom ? s.gm : Gr_;          // (the rank's slab when the whole iteration is slab-decomposed)
+    const Grid& gy = s.custom ? s.gm : Gyl_;
+    if (s.custom) {     // s = A x once, then the identity-shaped kernels on the M entries of s
+      K<T>::csr_spmv(q, s.Mtrue, s.d_rowptr, s.d_colidx, s.d_rval, a.x, s.sbuf);
+      a.x = s.sbuf;
+      a.flags |= F_STORE_DY;
+    }
+    if (s.slab_ext) {   // slab-decomposed, slices of the rank's own planes: nothing crosses the fabric
+      q = stream_;
+      K<T>::store_v(q, Gr_, a, 0, loose_v_);
+      if (r1_ > r0_) {
+        ObsScope obs(KID_EXT, stream_, 0.0);
+        s.ext->project(loose_v_ + r0_, false, scr.ptmp, scr.mpart, scr.cbuf);
+      }
+      a.v = loose_v_;
+      a.vsrc = 2;
+    } else if (s.slab_dft) {   // slab-decomposed transform: every rank its planes, one all-to-all each way, the threshold over all ranks
+      q = stream_;
+      K<T>::store_v(q, Gr_, a, 0, loose_v_);
+      {
+        ObsScope obs(KID_EXT, stream_, 0.0);
+        s.ddft->project(loose_v_ + r0_, false, comm_.get(), &hooks_, part_tmp_, maxpart_, scr_c_, scr_c_len_, (int*)hovf_ + i);
+      }
+      a.v = loose_v_;
+      a.vsrc = 2;
+    } else if (s.fan) { // slab-decomposed, a projector that needs the whole array: its owner has gathered v (fan_begin, in front of
+      q = stream_;      // the per-set updates) and scatters P(v)
+      fan_return(s);
+      a.v = s.fanv;
+      a.vsrc = 2;
+    } else if (s.ext_kind) {   // library-backed projector: materialise v, project it in place, hand y to the fused update
+      K<T>::store_v(q, G_, a, 0, scr_v_);
+      {
+        ObsScope obs(KID_EXT, stream_, 0.0);
+        s.ext->project(scr_v_, false, scr.ptmp, scr.mpart, scr.cbuf);
+      }
+      a.vsrc = 2;
+    }
+    // (a gathered set was projected above; slab-decomposed, a two-pass set but cardinality was searched in lock step with the others)
+    if (s.two_pass && !s.fan && !(slab_ && !s.slab_card)) {   // threshold / scale of prox_i from one pass that produces v on the fly (nothing stored)
+      const bool rescaled = s.rescaled(a.rho);
+      if (rescaled) K<T>::ps_rescale(q, s.ps, s.rescale_factor(a.rho));                      // v rescaled: theta moves like 1/rho
+      K<T>::proj_scalars_set(q, gs, a, 0, s.ps, scr.ptmp, scr.mpart, scr.cbuf, s.Mtrue, search_ctl(i, rescaled, !slab_ && !s.custom), hooks());
+    }
+    if (s.two_pass || s.fan) {
+      s.last_rho = a.rho;
+      s.last_gamma = a.gamma;
+    }
+    K<T>::yl(q, (s.slab_ext || s.slab_dft || (s.fan && s.ident)) ? gs : gy, a, part);      // (no adjoint stencil reads the plane below: nothing to recompute)
+    if (s.custom) K<T>::csc_adj_norm(q, G_.N, s.d_colptr, s.d_rowval, s.d_nzval, s.dy, part + (size_t)SL_ADJ * NB);
+    else if (!s.ident) K<T>::adj_norm(q, gs, a, part + (size_t)SL_ADJ * NB);
+    if (feas && (s.slab_ext || s.slab_dft)) dist_feasibility(s, x_, fe2_part(i), i);
+    else if (feas && s.fan) fan_feasibility(s, a, fe2_part(i));
+    else if (feas && s.ext_kind) ext_feasibility(s, a, fe2_part(i));
+    if (feas && s.two_pass && !s.fan) {
+      // ||P_i(s) - s|| with s = A_i x produced on the fly; its own warm-started scalars (psf)
+      SampleCtl cf;
+      cf.host_ovf = (int*)hovf_ + i;
+      cf.compact_cap = scr.cap;
+      K<T>::proj_scalars_set(q, gs, a, 1, s.psf, scr.ptmp, scr.mpart, scr.cbuf, s.Mtrue, cf, hooks());
+      K<T>::proj_dist_set(q, gs, a, 1, s.psf, fe2_part(i));
+    }
+    rotate(s, tgt);
+  }
+
+  // Sets whose projector is shared by all ranks (slice-wise rank / nuclear norm), in set order on every rank, after the
+  // rank's own sets are queued: the owner materialises v = x_hat - l / rho and scatters it by slab (seven links at once:
+  // 7/8 of N w bytes leave it, a broadcast would move seven times that), every rank projects the slices of its slab, a
+  // gather returns P(v), the owner finishes the update with it.  (Engine stream: the
+  // collectives are ordered against the rank's other work; what runs on the second set stream overlaps.)
+  void update_sets_of_all_ranks(int flags, const double* rho, const double* gamma) {
+    for (int i = 0; i < p_n_; ++i) {
+      SetState<T>& s = sets_[i];
+      if (!s.dist_ext) continue;
+      const int dt = dtype_code();
+      SetArgs<T> a;
+      YlTarget tgt{false, false};
+      if (s.owned) {
+        a = set_args(s, (T)rho[i], (T)gamma[i], flags);
+        tgt = aim(s, flags, a);
+        K<T>::store_v(stream_, G_, a, 0, scr_v_);
+      }
+      comm_->scatter(scr_v_, (size_t)chunk_, dt, s.owner_rank, stream_);
+      if (s.ext) {
+        ObsScope obs(KID_EXT, stream_, 0.0);
+        s.ext->project(scr_v_ + r0_, false, part_tmp_, maxpart_, scr_c_);
+      }
+      comm_->gather(scr_v_, (size_t)chunk_, dt, s.owner_rank, stream_);
+      if (s.owned) {
+        a.vsrc = 2;
+        K<T>::yl(stream_, G_, a, set_part(i));
+        rotate(s, tgt);
+      }
+      if ((flags & SIPX_YL_FEAS) && i < pp_n_) dist_feasibility(s, x_, fe2_part(i));
+    }
+  }
+
+  // the sweep wrote the sum over the sets in front of the first loose one (fuse_rhs_); the rest, in order
+  void rest_of_fused_rhs(const double* rho) {
+    if (!rhs_fused_) return;
+    RhsBatch b(stream_, Gr_, rhs_, true);
+    bool behind = false;
+    for (int i = 0; i < p_n_; ++i) {
+      behind |= !sets_[i].in_sweep;
+      if (behind) b.add(sets_[i], (T)rho[i]);
+    }
+    b.finish();
+  }
+
   // The lane set's y/l update (see sipx_finalize): x is final on the engine stream; store v, project it, update y and l on the
   // lane stream, queued by a host thread (the projector waits for its own stream between its steps).  The pointer rotation of
   // the set happens here, on the caller's thread; the thread only launches.
   void lane_start(int flags, const double* rho, const double* gamma) {
     SetState<T>& s = sets_[lane_set_];
     SetArgs<T> a = set_args(s, (T)rho[lane_set_], (T)gamma[lane_set_], flags);
-    const bool snapshot = (flags & (SIPX_YL_BB | SIPX_YL_FIRST)) != 0;
-    const bool first = (flags & SIPX_YL_FIRST) != 0;
-    const bool to_other = snapshot ? (!first && s.snap != 0) : (s.snap == 0);
-    a.yo = to_other ? s.y0 : s.y;
-    a.lo = to_other ? s.l0 : s.l;
+    const YlTarget tgt = aim(s, flags, a);
     a.v = lane_v_;
     lane_args_ = a;
     SIPX_HIP(hipEventRecord(lane_fork_, stream_));
@@ -1822,17 +1913,15 @@ class Engine : public EngineBase {
       SIPX_HIP(hipEventRecord(stat_event(2 * i), lane_st_));
       lane_sample_ = (long long)i;
     }
-    double* part = part_sets_ + (size_t)lane_set_ * SLOTS * NB;
-    double* ptmp = s.ptmp ? s.ptmp : part_tmp_;
-    T* mpart = s.mpart ? s.mpart : maxpart_;
-    T* cbuf = s.cbuf ? s.cbuf : scr_c_;
+    double* part = set_part(lane_set_);
+    const SetScratch scr = scratch_of(s);
     ExtProj<T>* ext = s.ext.get();
-    lane_thr_ = std::thread([this, a, part, ptmp, mpart, cbuf, ext]() {
+    lane_thr_ = std::thread([this, a, part, scr, ext]() {
       try {
         SIPX_HIP(hipSetDevice(device_));
         K<T>::store_v(lane_st_, slab_ ? Gr_ : G_, a, 0, lane_v_);
-        if (!slab_) ext->project(lane_v_, false, ptmp, mpart, cbuf);
-        else if (r1_ > r0_) ext->project(lane_v_ + r0_, false, ptmp, mpart, cbuf);      // (the slices of the rank's own planes)
+        if (!slab_) ext->project(lane_v_, false, scr.ptmp, scr.mpart, scr.cbuf);
+        else if (r1_ > r0_) ext->project(lane_v_ + r0_, false, scr.ptmp, scr.mpart, scr.cbuf);      // (the slices of the rank's own planes)
         SetArgs<T> a2 = a;
         a2.vsrc = 2;
         K<T>::yl(lane_st_, slab_ ? Gr_ : Gyl_, a2, part);
@@ -1841,9 +1930,7 @@ class Engine : public EngineBase {
         lane_err_ = std::current_exception();
       }
     });
-    if (to_other) { std::swap(s.y, s.y0); std::swap(s.l, s.l0); }     // (y, l) always names the current iterate
-    if (snapshot) s.snap = 0;
-    else if (to_other && s.snap == 0) s.snap = 1;
+    rotate(s, tgt);
   }
   void lane_join(int flags) {
     SetState<T>& s = sets_[lane_set_];
@@ -1860,11 +1947,11 @@ class Engine : public EngineBase {
     }
     SIPX_HIP(hipStreamWaitEvent(stream_, lane_ev_, 0));
     if ((flags & SIPX_YL_FEAS) && lane_set_ < pp_n_) {
-      if (slab_) dist_feasibility(s, x_, part_sets_ + ((size_t)lane_set_ * SLOTS + SL_FE2) * NB, lane_set_);
+      if (slab_) dist_feasibility(s, x_, fe2_part(lane_set_), lane_set_);
       else {
         SetArgs<T> a = lane_args_;
         a.v = scr_v_;
-        ext_feasibility(s, a, part_sets_ + ((size_t)lane_set_ * SLOTS + SL_FE2) * NB);
+        ext_feasibility(s, a, fe2_part(lane_set_));
       }
     }
   }
@@ -2121,14 +2208,30 @@ class Engine : public EngineBase {
            (s.prox == PX_BOUNDS || s.prox == PX_L1 || s.prox == PX_PROX_L1 || s.prox == PX_L2 || s.prox == PX_ANNULUS || s.prox == PX_DIST);
   }
 
-  // Threshold / scale searches of the two-pass sets `tp` of a slab-decomposed grid, all in lock step, through the SPECULATIVE
-  // EXCHANGE (used for the searches of the y/l update, feas_ps = false, and for those of the feasibility estimates, on the sets'
-  // second scalar state and v = A x itself).  gseg[j] / chunk: the set's segment in rank 0's chunk of the full-size exchange
-  // buffer; ctl[j]: the set's pinned words.
-  void spec_exchange_searches(const std::vector<int>& tp, std::vector<SetArgs<T>>& args, std::vector<SampleCtl>& ctl,
-                              const std::vector<T*>& gseg, long long chunk, int v_is_s, bool feas_ps, int it, bool lean_group = false) {
-    const size_t RS = (size_t)(PREP_SLOTS + 1 + 2 * comm_->world);
-    auto PS = [&](int i) { return feas_ps ? sets_[i].psf : sets_[i].ps; };
+  // set j of a lock-step group in the arguments of the two launches that close the first stage of all its searches (sums of the
+  // partial slots + packing; decision + unpacking + solve): fseg: a set's header segment, rank_off: where this rank's segments
+  // start in fbuf_, cap_max: what a final bracket may gather (0: no exchange)
+  void spec_fill(const LockStep& L, size_t j, long long fseg, long long rank_off, double cap_max, SpecPackArgs<T>& pk, SpecFinishArgs<T>& fa) {
+    const SetState<T>& s = sets_[L.tp[j]];
+    ProjScalars<T>* ps = L.feas_ps ? s.psf : s.ps;
+    SpecPackSet<T>& P = pk.s[j];
+    P.ps = ps; P.partials = s.ptmp; P.maxpart = s.mpart; P.compact = s.cbuf;
+    P.seg = fbuf_ + rank_off + (long long)j * fseg;
+    P.is_l1 = s.prox == PX_L1 ? 1 : 0;
+    SpecFinishSet<T>& F = fa.s[j];
+    F.ps = ps;
+    F.da = DecideArgs{L.args[j].prox, (L.args[j].flags & F_NOSPEC) ? 1 : 0, (double)L.args[j].plo, (double)L.args[j].phi, cap_max, s.Mtrue};
+    F.reg = stage_ + j * L.RS;
+    F.fseg0 = fbuf_ + (long long)j * fseg;
+    F.compact = s.cbuf; F.partials = s.ptmp; F.radius = L.args[j].phi;
+    F.host_want = L.ctl[j].host_want; F.verdict = L.ctl[j].verdict;
+  }
+
+  // Threshold / scale searches of the two-pass sets of a lock-step group on a slab-decomposed grid through the SPECULATIVE
+  // EXCHANGE (used for the searches of the y/l update, and -- L.feas_ps, L.v_is_s -- for those of the feasibility estimates, on the
+  // sets' second scalar state and v = A x itself).
+  void spec_exchange_searches(LockStep& L, int it) {
+    const std::vector<int>& tp = L.tp;
     // SPECULATIVE EXCHANGE (kernels_proj.hip, k_spec_pack): first pass of every set, then ONE all-gather carrying every
     // rank's probe sums and the magnitudes it gathered inside the speculative range.  Every rank adds the sums up itself,
     // decides, and -- when the range held theta, the rule once rho and gamma move slowly -- solves from the gathered values:
@@ -2138,20 +2241,10 @@ class Engine : public EngineBase {
     const long long fseg = hooks_.fcap + fast_hdr<T>();
     const long long fchunk = (long long)tp.size() * fseg;
     const unsigned seq = ++spec_seq_ & 0x3fffffffu;
-    // The sets' chains of small kernels (slot sums, packing; decision, unpacking, solve) run side by side on the set
-    // streams -- every set has its own partial slots, gather buffer and segments -- the collective itself on the engine stream.
-    auto fork = [&](hipEvent_t ev) { if (set_streams_) SIPX_HIP(hipEventRecord(ev, stream_)); };
-    auto join = [&]() {
-      for (size_t k = 0; k < pool_.size(); ++k) {
-        if (pool_[k] == stream_) continue;
-        SetState<T>* last = nullptr;
-        for (int i : tp)
-          if (sets_[i].st == pool_[k]) last = &sets_[i];
-        if (!last) continue;
-        SIPX_HIP(hipEventRecord(last->ev, last->st));
-        SIPX_HIP(hipStreamWaitEvent(stream_, last->ev, 0));
-      }
-    };
+    for (size_t j = 0; j < tp.size(); ++j) {
+      L.ctl[j].verdict = (unsigned*)hverd_ + tp[j];
+      L.ctl[j].seq = seq;
+    }
     if ((int)tp.size() <= SPEC_MAX_SETS) {
       // Batched form (the default): every set's first pass on the engine stream, then TWO launches for all sets -- sums of
       // the partial slots + packing, and, after the all-gather, decision + unpacking + solve (one workgroup per set).  A rank's
@@ -2164,71 +2257,53 @@ class Engine : public EngineBase {
       fa.world = comm_->world; fa.fchunk = fchunk; fa.seq = seq;
       // (the lean first passes of the l1 sets in one sweep: everything that prepares a search -- rescaling, sampled prediction --
       //  was queued on this very stream before, so the device-side state a lean pass reads is final when the sweep starts)
-      (void)lean_group;
-      if (!feas_ps && !v_is_s && Gr_.n[0] % 4 == 0) {
+      if (!L.feas_ps && !L.v_is_s && Gr_.n[0] % 4 == 0) {
         LeanMulti<T> lm;
         lm.ns = 0;
         std::vector<size_t> who;
         for (size_t j = 0; j < tp.size() && lm.ns < LEAN_MAX; ++j) {
           SetState<T>& s = sets_[tp[j]];
-          if (s.prox != PX_L1 || (args[j].flags & F_NOSPEC)) continue;
-          LeanSet<T>& L = lm.s[lm.ns++];
-          L.a = args[j]; L.a.ps = s.ps; L.ps = s.ps; L.compact = s.cbuf; L.partials = s.ptmp; L.maxpart = s.mpart;
+          if (s.prox != PX_L1 || (L.args[j].flags & F_NOSPEC)) continue;
+          LeanSet<T>& S = lm.s[lm.ns++];
+          S.a = L.args[j]; S.a.ps = s.ps; S.ps = s.ps; S.compact = s.cbuf; S.partials = s.ptmp; S.maxpart = s.mpart;
           who.push_back(j);
         }
         if (lm.ns >= 2) {
           K<T>::lean_multi(stream_, Gr_, lm);
           for (size_t j : who) {
-            ctl[j].lean_done = 1;
-            ctl[j].lean_known = (hlean_[tp[j]] >> 16) & 1;       // published by the set's last solve: its full first pass need not be launched
+            L.ctl[j].lean_done = 1;
+            L.ctl[j].lean_known = (hlean_[tp[j]] >> 16) & 1;       // published by the set's last solve: its full first pass need not be launched
           }
         }
       }
       for (size_t j = 0; j < tp.size(); ++j) {
-        SetState<T>& s = sets_[tp[j]];
-        ctl[j].verdict = (unsigned*)hverd_ + tp[j];
-        ctl[j].seq = seq;
-        K<T>::proj_scalars_stage(13, stream_, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], &hooks_,
-                                 stage_ + j * RS, gseg[j], chunk);
-        SpecPackSet<T>& P = pk.s[j];
-        P.ps = PS(tp[j]); P.partials = s.ptmp; P.maxpart = s.mpart; P.compact = s.cbuf;
-        P.seg = fbuf_ + (long long)comm_->rank * fchunk + (long long)j * fseg;
-        P.is_l1 = s.prox == PX_L1 ? 1 : 0;
-        SpecFinishSet<T>& F = fa.s[j];
-        F.ps = PS(tp[j]);
-        F.da = DecideArgs{args[j].prox, (args[j].flags & F_NOSPEC) ? 1 : 0, (double)args[j].plo, (double)args[j].phi, (double)hooks_.gcap, s.Mtrue};
-        F.reg = stage_ + j * RS;
-        F.fseg0 = fbuf_ + (long long)j * fseg;
-        F.compact = s.cbuf; F.partials = s.ptmp; F.radius = args[j].phi;
-        F.host_want = ctl[j].host_want; F.verdict = ctl[j].verdict;
+        search_stage(13, stream_, L, j);
+        spec_fill(L, j, fseg, (long long)comm_->rank * fchunk, (double)hooks_.gcap, pk, fa);
       }
       K<T>::spec_sums_pack(stream_, pk);
       comm_->allgather(fbuf_, (size_t)fchunk, dtype_code(), stream_);
       K<T>::spec_finish(stream_, fa);
     } else {
-    fork(ev_fork_);
-    for (size_t j = 0; j < tp.size(); ++j) {
-      SetState<T>& s = sets_[tp[j]];
-      hipStream_t q = (set_streams_ && s.st) ? s.st : stream_;
-      if (q != stream_) SIPX_HIP(hipStreamWaitEvent(q, ev_fork_, 0));
-      ctl[j].verdict = (unsigned*)hverd_ + tp[j];
-      ctl[j].seq = seq;
-      K<T>::proj_scalars_stage(0, q, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], &hooks_,
-                               stage_ + j * RS, gseg[j], chunk);
-      K<T>::proj_scalars_stage(5, q, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], &hooks_,
-                               stage_ + j * RS, fbuf_ + (long long)j * fseg, fchunk);
-    }
-    join();
-    comm_->allgather(fbuf_, (size_t)fchunk, dtype_code(), stream_);
-    fork(ev_fork2_);
-    for (size_t j = 0; j < tp.size(); ++j) {
-      SetState<T>& s = sets_[tp[j]];
-      hipStream_t q = (set_streams_ && s.st) ? s.st : stream_;
-      if (q != stream_) SIPX_HIP(hipStreamWaitEvent(q, ev_fork2_, 0));
-      K<T>::proj_scalars_stage(6, q, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], &hooks_,
-                               stage_ + j * RS, fbuf_ + (long long)j * fseg, fchunk);
-    }
-    join();
+      // The sets' chains of small kernels (slot sums, packing; decision, unpacking, solve) run side by side on the set
+      // streams -- every set has its own partial slots, gather buffer and segments -- the collective itself on the engine stream.
+      auto in_group = [&tp](int i) { return std::binary_search(tp.begin(), tp.end(), i); };
+      auto stream_of = [this](const SetState<T>& s) { return (set_streams_ && s.st) ? s.st : stream_; };
+      if (set_streams_) SIPX_HIP(hipEventRecord(ev_fork_, stream_));
+      for (size_t j = 0; j < tp.size(); ++j) {
+        hipStream_t q = stream_of(sets_[tp[j]]);
+        if (q != stream_) SIPX_HIP(hipStreamWaitEvent(q, ev_fork_, 0));
+        search_stage(0, q, L, j);
+        search_stage(5, q, L, j, stage_ + j * L.RS, fbuf_ + (long long)j * fseg, fchunk);
+      }
+      join_set_streams(in_group);
+      comm_->allgather(fbuf_, (size_t)fchunk, dtype_code(), stream_);
+      if (set_streams_) SIPX_HIP(hipEventRecord(ev_fork2_, stream_));
+      for (size_t j = 0; j < tp.size(); ++j) {
+        hipStream_t q = stream_of(sets_[tp[j]]);
+        if (q != stream_) SIPX_HIP(hipStreamWaitEvent(q, ev_fork2_, 0));
+        search_stage(6, q, L, j, stage_ + j * L.RS, fbuf_ + (long long)j * fseg, fchunk);
+      }
+      join_set_streams(in_group);
     }
     std::vector<size_t> fb;                  // the sets whose search goes on (the same on every rank)
     bool refine = false;
@@ -2241,49 +2316,38 @@ class Engine : public EngineBase {
     spec_fallbacks_ += (long long)fb.size();
     const bool spec_debug = env_knobs().spec_debug;
     if (spec_debug) {
-      for (size_t j : fb) dump_ps(tp[j], stage_ + j * RS);
+      for (size_t j : fb) dump_ps(tp[j], stage_ + j * L.RS);
       std::fprintf(stderr, "[sipx spec] it %d:", it);
       for (size_t j = 0; j < tp.size(); ++j) std::fprintf(stderr, " set %d verdict %u", tp[j], (unsigned)(hverd_[tp[j]] & 3u));
       std::fprintf(stderr, "\n");
     }
-    if (!fb.empty()) {
-      // Fallback (the summed first-pass sums of every set are in its region of stage_, where k_spec_decide left them):
-      // refinement rounds -- gated probe pass, ONE all-reduce, decision -- for as long as some set's bracket holds more than
-      // the exchange segments take (the host reads that from the sets' pinned words after every round: exactly as many
-      // all-reduces as are needed, at most L1_REFINES_SLAB), then the compaction of every final bracket and the full-size
-      // all-gather.  The sets the exchange settled take no part.
-      const int max_rounds = std::max(0, std::min(6, env_knobs().l1_rounds_max));      // SIPX_L1_ROUNDS_MAX (tests): force an overflow
-      for (int rep = 0; refine && rep < max_rounds; ++rep) {
-        const unsigned rseq = ++spec_seq_ & 0x3fffffffu;
-        for (size_t j : fb) {
-          SetState<T>& s = sets_[tp[j]];
-          K<T>::proj_scalars_stage(8, stream_, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], &hooks_,
-                                   stage_ + j * RS, gseg[j], chunk);
-        }
-        comm_->allreduce_sum(stage_, tp.size() * RS, SIPX_F64, stream_);
-        for (size_t j : fb) {
-          SetState<T>& s = sets_[tp[j]];
-          ctl[j].seq = rseq;
-          K<T>::proj_scalars_stage(9, stream_, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], &hooks_,
-                                   stage_ + j * RS, gseg[j], chunk);
-        }
-        refine = false;
-        for (size_t j : fb)
-          if (sets_[tp[j]].prox == PX_L1) refine |= (wait_verdict(hverd_ + tp[j], rseq) & 2u) != 0;
-        spec_rounds_ += 1;
-        if (spec_debug) {
-          std::fprintf(stderr, "[sipx spec]   round %d -> refine %d\n", rep + 1, (int)refine);
-          for (size_t j : fb) dump_ps(tp[j], stage_ + j * RS);
-        }
+    if (fb.empty()) return;
+    // Fallback (the summed first-pass sums of every set are in its region of stage_, where k_spec_decide left them):
+    // refinement rounds -- gated probe pass, ONE all-reduce, decision -- for as long as some set's bracket holds more than
+    // the exchange segments take (the host reads that from the sets' pinned words after every round: exactly as many
+    // all-reduces as are needed, at most L1_REFINES_SLAB), then the compaction of every final bracket and the full-size
+    // all-gather.  The sets the exchange settled take no part.
+    const int max_rounds = std::max(0, std::min(6, env_knobs().l1_rounds_max));      // SIPX_L1_ROUNDS_MAX (tests): force an overflow
+    for (int rep = 0; refine && rep < max_rounds; ++rep) {
+      const unsigned rseq = ++spec_seq_ & 0x3fffffffu;
+      for (size_t j : fb) search_stage(8, stream_, L, j);
+      comm_->allreduce_sum(stage_, tp.size() * L.RS, SIPX_F64, stream_);
+      for (size_t j : fb) {
+        L.ctl[j].seq = rseq;
+        search_stage(9, stream_, L, j);
       }
-      for (int stage : {12, 3}) {
-        for (size_t j : fb) {
-          SetState<T>& s = sets_[tp[j]];
-          K<T>::proj_scalars_stage(stage, stream_, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], &hooks_,
-                                   stage_ + j * RS, gseg[j], chunk);
-        }
-        if (stage == 12) comm_->allgather(gbuf_, (size_t)chunk, dtype_code(), stream_);
+      refine = false;
+      for (size_t j : fb)
+        if (sets_[tp[j]].prox == PX_L1) refine |= (wait_verdict(hverd_ + tp[j], rseq) & 2u) != 0;
+      spec_rounds_ += 1;
+      if (spec_debug) {
+        std::fprintf(stderr, "[sipx spec]   round %d -> refine %d\n", rep + 1, (int)refine);
+        for (size_t j : fb) dump_ps(tp[j], stage_ + j * L.RS);
       }
+    }
+    for (int stage : {12, 3}) {
+      for (size_t j : fb) search_stage(stage, stream_, L, j);
+      if (stage == 12) comm_->allgather(gbuf_, (size_t)L.chunk, dtype_code(), stream_);
     }
   }
 
@@ -2298,111 +2362,106 @@ class Engine : public EngineBase {
   // Per iteration of the headline list: 5 launches instead of 27 on three streams, x read once instead of three times.
   // Same decisions (decide_body with cap_max = 0), same gathered values, same double-double solve: theta bit for bit.
   void batched_searches(int flags, const double* rho, const double* gamma) {
-    std::vector<int> tp;
+    LockStep L;
     for (int i = 0; i < p_n_; ++i)
-      if (sets_[i].two_pass && sets_[i].in_sweep) tp.push_back(i);
-    if (tp.empty()) return;
-    run_batched(tp, false, flags, rho, gamma);
+      if (sets_[i].two_pass && sets_[i].in_sweep) L.tp.push_back(i);
+    if (L.tp.empty()) return;
+    run_batched(L, flags, rho, gamma);
     if (flags & SIPX_YL_FEAS) {               // ||P_i(s) - s|| with s = A_i x itself: the sets' second scalar state
-      std::vector<int> tf;
-      for (int i : tp)
-        if (i < pp_n_) tf.push_back(i);
-      if (!tf.empty()) {
-        run_batched(tf, true, flags, rho, gamma);
-        for (int i : tf) {
+      LockStep F;
+      F.feas_ps = true;
+      for (int i : L.tp)
+        if (i < pp_n_) F.tp.push_back(i);
+      if (!F.tp.empty()) {
+        run_batched(F, flags, rho, gamma);
+        for (int i : F.tp) {
           SetArgs<T> a = set_args(sets_[i], (T)rho[i], (T)gamma[i], flags);
-          K<T>::proj_dist_set(stream_, Gr_, a, 1, sets_[i].psf, part_sets_ + ((size_t)i * SLOTS + SL_FE2) * NB);
+          K<T>::proj_dist_set(stream_, Gr_, a, 1, sets_[i].psf, fe2_part(i));
         }
       }
     }
   }
-  void run_batched(const std::vector<int>& tp, bool feas_ps, int flags, const double* rho, const double* gamma) {
-    const size_t RS = (size_t)(PREP_SLOTS + 1 + 2);
+  // the searches of the sets L.tp (L.feas_ps: those of their feasibility estimates) as one chain; fills the rest of L
+  void run_batched(LockStep& L, int flags, const double* rho, const double* gamma) {
+    const std::vector<int>& tp = L.tp;
+    const bool feas_ps = L.feas_ps;
+    L.RS = (size_t)(PREP_SLOTS + 1 + 2);
+    L.v_is_s = feas_ps ? 1 : 0;
+    L.args.resize(tp.size());
+    L.ctl.resize(tp.size());
     const long long fseg = fast_hdr<T>();
-    const int v_is_s = feas_ps ? 1 : 0;
     const unsigned seq = ++spec_seq_ & 0x3fffffffu;
-    std::vector<SetArgs<T>> args(tp.size());
-    std::vector<SampleCtl> ctl(tp.size());
-    auto PS = [&](int i) { return feas_ps ? sets_[i].psf : sets_[i].ps; };
     const bool vec = Gr_.n[0] % 4 == 0;
     RescaleMulti<T> rs;
     rs.n = 0;
     SampleMulti<T> sm;
     sm.ns = 0;
+    auto sample = [&](size_t j, ProjScalars<T>* ps) {
+      SampleSet<T>& S = sm.s[sm.ns++];
+      S.a = L.args[j]; S.a.ps = ps; S.ps = ps; S.partials = sets_[tp[j]].ptmp; S.reg = nullptr; S.true_len = sets_[tp[j]].Mtrue;
+    };
     for (size_t j = 0; j < tp.size(); ++j) {
       SetState<T>& s = sets_[tp[j]];
-      args[j] = set_args(s, (T)rho[tp[j]], (T)gamma[tp[j]], flags);
-      ctl[j].verdict = (unsigned*)hverd_ + tp[j];
-      ctl[j].seq = seq;
+      L.args[j] = set_args(s, (T)rho[tp[j]], (T)gamma[tp[j]], flags);
+      L.ctl[j].verdict = (unsigned*)hverd_ + tp[j];
+      L.ctl[j].seq = seq;
       if (feas_ps) {
         // the search of a feasibility estimate comes every tenth iteration: its own last theta is ten iterations old and missed
         // the range every time (three fallbacks of two sweeps each per such iteration: 7 % of the 512^3 window) -- a sampled
         // estimate first, whenever the set's last such search asked for one (device side: ProjScalars::want_sample)
-        if (env_knobs().l1_sample && s.prox == PX_L1 && vec) {
-          SampleSet<T>& S = sm.s[sm.ns++];
-          S.a = args[j]; S.a.ps = s.psf; S.ps = s.psf; S.partials = s.ptmp; S.reg = nullptr; S.true_len = s.Mtrue;
-        }
+        if (env_knobs().l1_sample && s.prox == PX_L1 && vec) sample(j, s.psf);
         continue;
       }
-      ctl[j].host_want = (int*)hlean_ + tp[j];
-      ctl[j].runs = env_knobs().l1_sample_runs;
-      const bool l1 = s.prox == PX_L1;
-      const bool rescaled = l1 && s.last_rho > T(0) && s.last_rho != args[j].rho;      // v rescaled: theta moves like 1/rho
-      if (rescaled) { rs.ps[rs.n] = s.ps; rs.factor[rs.n++] = (double)s.last_rho / (double)args[j].rho; }
-      if (env_knobs().l1_sample && l1 && vec && (rescaled || (hlean_[tp[j]] & 0xff) != 0)) {
-        SampleSet<T>& S = sm.s[sm.ns++];
-        S.a = args[j]; S.a.ps = s.ps; S.ps = s.ps; S.partials = s.ptmp; S.reg = nullptr; S.true_len = s.Mtrue;
-      }
-      s.last_rho = args[j].rho;
-      s.last_gamma = args[j].gamma;
+      const bool rescaled = s.rescaled(L.args[j].rho);
+      if (rescaled) { rs.ps[rs.n] = s.ps; rs.factor[rs.n++] = s.rescale_factor(L.args[j].rho); }
+      // (the sampled prediction is a launch of its own for all sets here: of the set's SampleCtl the chain takes the pinned word
+      //  of the prediction and the number of runs, nothing raises an overflow word without an exchange)
+      const SampleCtl c = search_ctl(tp[j], rescaled, vec);
+      L.ctl[j].host_want = c.host_want;
+      L.ctl[j].runs = c.runs;
+      if (c.enable) sample(j, s.ps);
+      s.last_rho = L.args[j].rho;
+      s.last_gamma = L.args[j].gamma;
     }
     K<T>::ps_rescale_multi(stream_, rs);
-    sm.v_is_s = v_is_s;
+    sm.v_is_s = L.v_is_s;
     if (sm.ns > 0) K<T>::sample_multi(10, stream_, Gr_, sm, env_knobs().l1_sample_runs, nullptr);
     // the passes: groups of up to LEAN_MAX sets per launch (x read once per group) -- the lean first passes of the l1 sets whose
     // device-side state asks for one, then the full first passes of everybody else; each kernel returns at once when no set
     // of its group wants it.  (A grid whose lines are no multiple of four points keeps one scalar pass per set.)
     auto group = [&](const std::vector<size_t>& who, size_t from) {
-      LeanMulti<T> L;
-      L.ns = 0;
-      L.v_is_s = v_is_s;
-      for (size_t k = from; k < who.size() && L.ns < LEAN_MAX; ++k) {
+      LeanMulti<T> G;
+      G.ns = 0;
+      G.v_is_s = L.v_is_s;
+      for (size_t k = from; k < who.size() && G.ns < LEAN_MAX; ++k) {
         const size_t j = who[k];
         SetState<T>& s = sets_[tp[j]];
-        LeanSet<T>& S = L.s[L.ns++];
-        S.a = args[j]; S.a.ps = PS(tp[j]); S.ps = PS(tp[j]); S.compact = s.cbuf; S.partials = s.ptmp; S.maxpart = s.mpart;
+        ProjScalars<T>* ps = feas_ps ? s.psf : s.ps;
+        LeanSet<T>& S = G.s[G.ns++];
+        S.a = L.args[j]; S.a.ps = ps; S.ps = ps; S.compact = s.cbuf; S.partials = s.ptmp; S.maxpart = s.mpart;
       }
-      return L;
+      return G;
     };
     std::vector<size_t> all(tp.size());
     for (size_t j = 0; j < tp.size(); ++j) all[j] = j;
+    // the lean first passes of the l1 sets in one sweep (x read once)
+    std::vector<size_t> l1s;
+    for (size_t j = 0; vec && j < tp.size(); ++j)
+      if (sets_[tp[j]].prox == PX_L1 && !(L.args[j].flags & F_NOSPEC)) l1s.push_back(j);
+    for (size_t k = 0; k < l1s.size(); k += LEAN_MAX) K<T>::lean_multi(stream_, Gr_, group(l1s, k));
     // (SIPX_PASS_MULTI=1: the FULL first passes and the fallback passes of a group in one sweep as well -- measured and NOT the
     //  default: eight probes for three sets make that kernel ALU-bound at 161-173 VGPRs, 512^3 first passes 800-1000 us against
     //  3 x 285 us one after the other, refinement 1009 against 3 x 264; 512^3 116.2 against 118.7 it/s.  SIPX_PASS_MULTI=1, tests)
     if (vec && env_knobs().pass_multi) {
-      std::vector<size_t> l1s;
-      for (size_t j = 0; j < tp.size(); ++j)
-        if (sets_[tp[j]].prox == PX_L1 && !(args[j].flags & F_NOSPEC)) l1s.push_back(j);
-      for (size_t k = 0; k < l1s.size(); k += LEAN_MAX) K<T>::lean_multi(stream_, Gr_, group(l1s, k));
-      for (size_t k = 0; k < all.size(); k += LEAN_MAX) K<T>::pass_multi(0, stream_, Gr_, group(all, k), v_is_s);
+      for (size_t k = 0; k < all.size(); k += LEAN_MAX) K<T>::pass_multi(0, stream_, Gr_, group(all, k), L.v_is_s);
     } else {
-      // the lean first passes of the l1 sets in one sweep (x read once), a full first pass per set only where the host does not
-      // know from the set's pinned word that the pass will be a lean one (it returns at once when the device-side state says lean)
-      if (vec) {
-        std::vector<size_t> l1s;
-        for (size_t j = 0; j < tp.size(); ++j)
-          if (sets_[tp[j]].prox == PX_L1 && !(args[j].flags & F_NOSPEC)) l1s.push_back(j);
-        for (size_t k = 0; k < l1s.size(); k += LEAN_MAX) K<T>::lean_multi(stream_, Gr_, group(l1s, k));
-        for (size_t j : l1s) {
-          ctl[j].lean_done = 1;
-          ctl[j].lean_known = feas_ps ? 0 : ((hlean_[tp[j]] >> 16) & 1);      // published by the set's last solve; nothing since can have taken the flag back
-        }
+      // a full first pass per set only where the host does not know from the set's pinned word that the pass will be a lean
+      // one (it returns at once when the device-side state says lean)
+      for (size_t j : l1s) {
+        L.ctl[j].lean_done = 1;
+        L.ctl[j].lean_known = feas_ps ? 0 : ((hlean_[tp[j]] >> 16) & 1);      // published by the set's last solve; nothing since can have taken the flag back
       }
-      for (size_t j = 0; j < tp.size(); ++j) {
-        SetState<T>& s = sets_[tp[j]];
-        K<T>::proj_scalars_stage(13, stream_, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], nullptr,
-                                 stage_ + j * RS, nullptr, 0);
-      }
+      for (size_t j = 0; j < tp.size(); ++j) search_stage(13, stream_, L, j);
     }
     SpecPackArgs<T> pk;
     SpecFinishArgs<T> fa;
@@ -2410,20 +2469,7 @@ class Engine : public EngineBase {
     pk.local = fa.local = 1;
     pk.cap = 0;
     fa.world = 1; fa.fchunk = (long long)tp.size() * fseg; fa.seq = seq;
-    for (size_t j = 0; j < tp.size(); ++j) {
-      SetState<T>& s = sets_[tp[j]];
-      SpecPackSet<T>& P = pk.s[j];
-      P.ps = PS(tp[j]); P.partials = s.ptmp; P.maxpart = s.mpart; P.compact = s.cbuf;
-      P.seg = fbuf_ + (long long)j * fseg;
-      P.is_l1 = s.prox == PX_L1 ? 1 : 0;
-      SpecFinishSet<T>& F = fa.s[j];
-      F.ps = PS(tp[j]);
-      F.da = DecideArgs{args[j].prox, (args[j].flags & F_NOSPEC) ? 1 : 0, (double)args[j].plo, (double)args[j].phi, 0.0, s.Mtrue};
-      F.reg = stage_ + j * RS;
-      F.fseg0 = fbuf_ + (long long)j * fseg;
-      F.compact = s.cbuf; F.partials = s.ptmp; F.radius = args[j].phi;
-      F.host_want = ctl[j].host_want; F.verdict = ctl[j].verdict;
-    }
+    for (size_t j = 0; j < tp.size(); ++j) spec_fill(L, j, fseg, 0, 0.0, pk, fa);
     K<T>::spec_sums_pack(stream_, pk);
     K<T>::spec_finish(stream_, fa);
     // Fallback of the sets whose pinned verdict asks for it (theta left the speculative range, or the range gathered too much):
@@ -2444,31 +2490,26 @@ class Engine : public EngineBase {
     const bool spec_debug = env_knobs().spec_debug;
     if (spec_debug && !feas_ps) {                // (diagnostics: the state every search of the chain ended its first stage with; synchronises)
       std::fprintf(stderr, "[sipx spec] batched chain, search seq %u\n", seq);
-      for (size_t j = 0; j < tp.size(); ++j) dump_ps(tp[j], stage_ + j * RS);
+      for (size_t j = 0; j < tp.size(); ++j) dump_ps(tp[j], stage_ + j * L.RS);
     }
     if (fb.empty()) return;
     auto tail = [&](int stage) {
       for (size_t j : fb) {
         SetState<T>& s = sets_[tp[j]];
-        K<T>::search_tail(stage, stream_, args[j], PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], stage_ + j * RS);
+        K<T>::search_tail(stage, stream_, L.args[j], feas_ps ? s.psf : s.ps, s.ptmp, s.mpart, s.cbuf, s.Mtrue, L.ctl[j], stage_ + j * L.RS);
       }
     };
     if (vec && env_knobs().pass_multi) {
       if (refine) {
-        for (size_t k = 0; k < fb.size(); k += LEAN_MAX) K<T>::pass_multi(1, stream_, Gr_, group(fb, k), v_is_s);
+        for (size_t k = 0; k < fb.size(); k += LEAN_MAX) K<T>::pass_multi(1, stream_, Gr_, group(fb, k), L.v_is_s);
         tail(1);
       }
-      for (size_t k = 0; k < fb.size(); k += LEAN_MAX) K<T>::pass_multi(2, stream_, Gr_, group(fb, k), v_is_s);
+      for (size_t k = 0; k < fb.size(); k += LEAN_MAX) K<T>::pass_multi(2, stream_, Gr_, group(fb, k), L.v_is_s);
       tail(3);
     } else {
-      for (size_t j : fb) {
-        SetState<T>& s = sets_[tp[j]];
-        for (int stage : {1, 2, 3}) {
-          if (stage == 1 && !refine) continue;
-          K<T>::proj_scalars_stage(stage, stream_, Gr_, args[j], v_is_s, PS(tp[j]), s.ptmp, s.mpart, s.cbuf, s.Mtrue, ctl[j], nullptr,
-                                   stage_ + j * RS, nullptr, 0);
-        }
-      }
+      for (size_t j : fb)
+        for (int stage : {1, 2, 3})
+          if (stage != 1 || refine) search_stage(stage, stream_, L, j);
     }
   }
 
@@ -2490,15 +2531,13 @@ class Engine : public EngineBase {
         if (!s.two_pass || !s.in_sweep || s.prox != PX_L1 || s.custom || s.ext_kind) continue;
         SetArgs<T> a = set_args(s, (T)rho[i], (T)gamma[i], flags);
         if (a.flags & F_NOSPEC) continue;
-        const bool rescaled = s.last_rho > T(0) && s.last_rho != a.rho;
-        const bool sampled = env_knobs().l1_sample && (rescaled || (hlean_[i] & 0xff) != 0);
-        if (rescaled || sampled) { ok = false; break; }
+        const bool rescaled = s.rescaled(a.rho);
+        if (rescaled || search_ctl(i, rescaled, true).enable) { ok = false; break; }
         if (lm.ns == LEAN_MAX) break;
-        LeanSet<T>& L = lm.s[lm.ns++];
-        L.a = a; L.a.ps = s.ps; L.ps = s.ps;
-        L.compact = s.cbuf ? s.cbuf : scr_c_;
-        L.partials = s.ptmp ? s.ptmp : part_tmp_;
-        L.maxpart = s.mpart ? s.mpart : maxpart_;
+        const SetScratch scr = scratch_of(s);
+        LeanSet<T>& S = lm.s[lm.ns++];
+        S.a = a; S.a.ps = s.ps; S.ps = s.ps;
+        S.compact = scr.cbuf; S.partials = scr.ptmp; S.maxpart = scr.mpart;
         who.push_back(i);
       }
       bool own = true;                     // every set of the group needs scratch of its own
@@ -2514,39 +2553,24 @@ class Engine : public EngineBase {
       if (!s.two_pass || !s.in_sweep) continue;
       SetArgs<T> a = set_args(s, (T)rho[i], (T)gamma[i], flags);
       hipStream_t q = s.st ? s.st : stream_;
-      double* ptmp = s.ptmp ? s.ptmp : part_tmp_;
-      T* mpart = s.mpart ? s.mpart : maxpart_;
-      T* cbuf = s.cbuf ? s.cbuf : scr_c_;
-      double* part = part_sets_ + (size_t)i * SLOTS * NB;
+      const SetScratch scr = scratch_of(s);
       if (q != stream_) SIPX_HIP(hipStreamWaitEvent(q, ev_fork_, 0));
-      const bool rescaled = a.prox == PX_L1 && s.last_rho > T(0) && s.last_rho != a.rho;
-      if (rescaled) K<T>::ps_rescale(q, s.ps, (double)s.last_rho / (double)a.rho);
-      SampleCtl ctl;
-      ctl.host_want = (int*)hlean_ + i;
-      ctl.host_ovf = (int*)hovf_ + i;
-      ctl.runs = env_knobs().l1_sample_runs;
-      ctl.enable = env_knobs().l1_sample && a.prox == PX_L1 && (rescaled || (hlean_[i] & 0xff) != 0);
+      const bool rescaled = s.rescaled(a.rho);
+      if (rescaled) K<T>::ps_rescale(q, s.ps, s.rescale_factor(a.rho));
+      SampleCtl ctl = search_ctl(i, rescaled, true);
       ctl.lean_done = lean_done[i];
-      K<T>::proj_scalars_set(q, Gr_, a, 0, s.ps, ptmp, mpart, cbuf, s.Mtrue, ctl, nullptr);
+      K<T>::proj_scalars_set(q, Gr_, a, 0, s.ps, scr.ptmp, scr.mpart, scr.cbuf, s.Mtrue, ctl, nullptr);
       s.last_rho = a.rho;
       s.last_gamma = a.gamma;
       if (feas && i < pp_n_) {                 // ||P_i(s) - s|| with s = A_i x produced on the fly; its own warm-started scalars
         SampleCtl cf;                          // (a sampled estimate first, as in the batched chain: run_batched)
         cf.runs = env_knobs().l1_sample_runs;
         cf.enable = env_knobs().l1_sample && a.prox == PX_L1;
-        K<T>::proj_scalars_set(q, Gr_, a, 1, s.psf, ptmp, mpart, cbuf, s.Mtrue, cf, nullptr);
-        K<T>::proj_dist_set(q, Gr_, a, 1, s.psf, part + (size_t)SL_FE2 * NB);
+        K<T>::proj_scalars_set(q, Gr_, a, 1, s.psf, scr.ptmp, scr.mpart, scr.cbuf, s.Mtrue, cf, nullptr);
+        K<T>::proj_dist_set(q, Gr_, a, 1, s.psf, fe2_part(i));
       }
     }
-    for (size_t k = 0; k < pool_.size(); ++k) {                         // join: theta / scale of every set are known
-      if (pool_[k] == stream_) continue;
-      SetState<T>* last = nullptr;
-      for (int i = 0; i < p_n_; ++i)
-        if (sets_[i].two_pass && sets_[i].in_sweep && sets_[i].st == pool_[k]) last = &sets_[i];
-      if (!last) continue;
-      SIPX_HIP(hipEventRecord(last->ev, last->st));
-      SIPX_HIP(hipStreamWaitEvent(stream_, last->ev, 0));
-    }
+    join_set_streams([this](int i) { return sets_[i].two_pass && sets_[i].in_sweep; });      // theta / scale of every set are known
   }
 
   // The y/l update of EVERY set in one sweep over the grid (kernels_multi.hip), on the engine stream, once the threshold /
@@ -2556,7 +2580,8 @@ class Engine : public EngineBase {
   // writes the right-hand side of that iteration.
   // The sweep never updates in place (neighbouring tiles re-read the OLD y, l of a few points): it writes into the pair that
   // holds the old snapshot (BB / first iteration: it is read first), into the free pair, or -- when both other pairs are
-  // taken, i.e. the snapshot must survive and sits in the other pair -- into a third pair, allocated on first need.
+  // taken, i.e. the snapshot must survive and sits in the other pair -- into a third pair, allocated by sipx_finalize.
+  // (The per-set kernels may write in place and have two pairs: their rule is aim / rotate.)
   void sweep_launch(int flags, const double* rho, const double* gamma, MultiArgs<T>& ma) {
     const bool first = (flags & SIPX_YL_FIRST) != 0, bb = (flags & SIPX_YL_BB) != 0 && !first;
     ma.nblk = 0;
@@ -4348,7 +4373,7 @@ class Engine : public EngineBase {
   int p_n_ = 0, pp_n_ = 0;
   std::vector<T> rho_, gamma_;
   std::vector<double> feas_init_;
-  T *x_base_ = nullptr, *p_base_ = nullptr, *m_base_ = nullptr, *r_base_ = nullptr, *p2_base_ = nullptr, *p2_ = nullptr;
+  T *p_base_ = nullptr, *m_base_ = nullptr, *r_base_ = nullptr, *p2_base_ = nullptr, *p2_ = nullptr;
   bool cg_fused_ = false;
   long long halo_ = 0;
   T *x_ = nullptr, *xold_ = nullptr, *rhs_ = nullptr, *m_ = nullptr, *r_ = nullptr, *p_ = nullptr, *Ap_ = nullptr;
