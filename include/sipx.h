@@ -39,7 +39,13 @@ enum { SIPX_F32 = 0, SIPX_F64 = 1 };
  * 2-D grids: D_x = dim 1, D_z = dim 2 (pass n3 = 1); TV = [D_z; D_x] (2-D), [D_z; D_y; D_x] (3-D). */
 enum { SIPX_OP_IDENTITY = 0, SIPX_OP_DX = 1, SIPX_OP_DY = 2, SIPX_OP_DZ = 3, SIPX_OP_TV = 4,
        SIPX_OP_CSC = 5 /* a caller-supplied sparse matrix (constraint.custom_TD_OP[1], setup_constraints.jl:70-72): the
-                          SparseMatrixCSC arrays in sipx_set_desc.csc_*, 0-based; AtA must be passed explicitly in CDS */ };
+                          SparseMatrixCSC arrays in sipx_set_desc.csc_*, 0-based.  Its A'A is passed in CDS when it is banded
+                          (at most 9 bands of the set, 32 of Q), or not at all: with ata_R = NULL the set becomes a MATRIX-FREE
+                          TERM of Q -- no bands are kept for it and every product with Q adds rho_i A_i'(A_i p) through the
+                          operator's own arrays, which is what the reference does when a set is not banded: the AtA stay
+                          sparse (PARSDMM_precompute_distribute.jl:51-59) and CG runs on the sparse Q (argmin_x.jl:42-51).
+                          Needs N, rows and stored entries below 2^31; not available with SIPX_Q_STENCIL, a communicator,
+                          Minkowski components or sipx_warm_start_from */ };
 
 /* Projector descriptor replacing the opaque closure P_sub[i] (src/get_projector.jl:3-103). */
 enum {
@@ -150,6 +156,9 @@ void sipx_destroy(sipx_ctx* ctx);
 /* Adds constraint set i (call in TD_OP order).  ata_R / ata_off / d_i = AtA[i] in CDS (N x d_i,
  * column-major) with set_Prop.AtA_offsets[i] (src/PARSDMM_precompute_distribute.jl:52-59); pass
  * ata_R = NULL to have the bands generated on the device from the operator descriptor.
+ * For SIPX_OP_CSC there is no descriptor to generate bands from: ata_R = NULL makes the set a matrix-free term of Q
+ * (the reference's sparse Q of a set that is not banded, PARSDMM_precompute_distribute.jl:51-59, argmin_x.jl:42-51; see
+ * SIPX_OP_CSC).  sipx_q_terms tells how a finalized context holds Q.
  * RETURN VALUE (unlike every other entry): the 0-based index of the new set (the i of y_i / l_i, of the rho / gamma /
  * r_pri arrays and of sipx_set_rows) on success, -1 on error -- test `rc < 0`, not `rc != 0`. */
 int sipx_add_set(sipx_ctx* ctx, const sipx_set_desc* desc, const void* ata_R, const int64_t* ata_off, int d_i);
@@ -195,7 +204,8 @@ int sipx_update_y_l(sipx_ctx* ctx, int it, int flags, const double* rho, const d
 int sipx_log_scalars(sipx_ctx* ctx, double* obj, double* evol_x);
 /* Barzilai-Borwein rule from the sums gathered by the last sipx_update_y_l(SIPX_YL_BB)  (src/adapt_rho_gamma.jl:55-126) */
 int sipx_adapt_rho_gamma(sipx_ctx* ctx, int adjust_rho, int adjust_gamma, double* rho_io, double* gamma_io);
-/* Q += (rho_new - rho_old) AtA_i for changed sets; rebinds the distance prox  (src/Q_update!.jl:45-48, src/PARSDMM.jl:230-243) */
+/* Q += (rho_new - rho_old) AtA_i for changed sets; rebinds the distance prox  (src/Q_update!.jl:45-48, src/PARSDMM.jl:230-243).
+ * A matrix-free term has no bands to update: its rho_i is replaced by rho_new[i]. */
 int sipx_q_update(sipx_ctx* ctx, const double* rho_new, const double* rho_old);
 /* copy out x, l[i], y[i] (any pointer may be NULL)                     (src/PARSDMM.jl:257) */
 int sipx_download(sipx_ctx* ctx, void* x, void* const* l, void* const* y);
@@ -297,8 +307,12 @@ typedef struct {
 } sipx_observations;
 int sipx_learn_observations(int dtype, const int64_t* n, const double* h, int64_t n_train, const void* m_train,
                             const int64_t* strides, int64_t max_batch, sipx_observations* out, int device);
-/* Q as assembled / updated (N x d column-major) and its offsets */
+/* The BANDED part of Q as assembled / updated (N x d column-major) and its offsets: the sum over the sets that handed over
+ * or generated CDS bands.  Matrix-free terms (SIPX_OP_CSC with ata_R = NULL) are not in it; sipx_apply_Q applies all of Q. */
 int sipx_get_Q(sipx_ctx* ctx, void* Q, int64_t* offsets, int* d);
+/* How the finalized context holds Q = sum_i rho_i A_i'A_i: *bands = bands of the CDS part (what sipx_get_Q returns as d),
+ * *matrix_free = number of sets applied as matrix-free terms.  Either pointer may be NULL. */
+int sipx_q_terms(sipx_ctx* ctx, int* bands, int* matrix_free);
 /* device-side timing of the dominant kernel: runs cds_spmv on Q `reps` times, returns avg ms (HIP events on the engine stream) */
 int sipx_time_spmv(sipx_ctx* ctx, int reps, double* avg_ms);
 /* HIP-event timing of the engine's kernels, bracketed on the stream each launch goes to.  launches / total_ms report what
@@ -418,7 +432,8 @@ int sipx_slab(sipx_ctx* ctx, int64_t* row0, int64_t* row1, int64_t* chunk);
  * (ata_R = NULL).  Results agree with the CDS mode to rounding, not bit for bit.  Call before sipx_finalize. */
 enum { SIPX_Q_CDS = 0, SIPX_Q_STENCIL = 1 };
 int sipx_set_q_mode(sipx_ctx* ctx, int mode);
-/* y = Q x (host TF[N] in and out) through the kernel the x-step uses, in either mode */
+/* y = Q x (host TF[N] in and out) through the kernels the x-step uses, in either mode: the banded (or stencil) product plus
+ * rho_i A_i'(A_i x) of every matrix-free term */
 int sipx_apply_Q(sipx_ctx* ctx, const void* x, void* y);
 
 #ifdef __cplusplus

@@ -279,12 +279,20 @@ function PARSDMM(m         ::Vector{TF},
                             colptr === nothing ? C_NULL : pointer(colptr), rowval === nothing ? C_NULL : pointer(rowval),
                             nzval === nothing ? C_NULL : pointer(nzval), rows,
                             transform, 0)
-            # AtA[i] in CDS (N x d_i) with its offsets; a non-banded Q (sparse / JOLI AtA) is outside libsipx
-            AtA[i] isa Matrix{TF} || error("libsipx needs every AtA in CDS storage (all operators banded)")
-            off = convert(Vector{Int64}, set_Prop.AtA_offsets[i])
-            rc = GC.@preserve keep off ccall((:sipx_add_set, libsipx), Cint,
-                        (Ptr{Cvoid}, Ref{SipxSetDesc}, Ptr{Cvoid}, Ptr{Int64}, Cint),
-                        ctx[], d, AtA[i], off, size(AtA[i], 2))
+            # AtA[i] in CDS (N x d_i) with its offsets.  A custom sparse TD_OP of a set that is not banded
+            # (set_Prop.banded[i] == false: the reference keeps its AtA sparse, PARSDMM_precompute_distribute.jl:51-59) goes
+            # without AtA: libsipx applies it as a matrix-free term of Q.  JOLI / dense AtA stay outside libsipx.
+            if custom && !set_Prop.banded[i]
+                rc = GC.@preserve keep ccall((:sipx_add_set, libsipx), Cint,
+                            (Ptr{Cvoid}, Ref{SipxSetDesc}, Ptr{Cvoid}, Ptr{Int64}, Cint),
+                            ctx[], d, C_NULL, C_NULL, 0)
+            else
+                AtA[i] isa Matrix{TF} || error("libsipx needs the AtA of a banded set in CDS storage")
+                off = convert(Vector{Int64}, set_Prop.AtA_offsets[i])
+                rc = GC.@preserve keep off ccall((:sipx_add_set, libsipx), Cint,
+                            (Ptr{Cvoid}, Ref{SipxSetDesc}, Ptr{Cvoid}, Ptr{Int64}, Cint),
+                            ctx[], d, AtA[i], off, size(AtA[i], 2))
+            end
             rc < 0 && check(1)                                               # sipx_add_set returns the set index, -1 on error
         end
 

@@ -321,6 +321,14 @@ struct SetState {
   long long *d_colptr = nullptr, *d_rowval = nullptr, *d_rowptr = nullptr, *d_colidx = nullptr;
   T *d_nzval = nullptr, *d_rval = nullptr, *sbuf = nullptr;
   Grid gm;                           // the 1-D "grid" of the M rows
+  // Matrix-free term of Q (ata_R = NULL at sipx_add_set): the set hands over no bands of A'A; every product with Q adds
+  // rho_i A_i'(A_i p) through the kernels of kernels_sparse.hip, which also serve the set's own s = A x and A'w (one operator,
+  // one arithmetic).  mf_rho: the set's current rho_i as Q holds it (assemble_Q, q_update); mf_t: A p of a product (M values).
+  bool mfree = false;
+  T mf_rho = T(0);
+  int *mf_colptr = nullptr, *mf_rowidx = nullptr, *mf_rowptr = nullptr, *mf_colidx = nullptr;
+  T* mf_t = nullptr;
+  MfOp<T> mfA, mfAt;                 // CSR copy (t = A p), CSC arrays (A' t)
   int comp = 0;                      // Minkowski component: 0 none, 1 = [A 0], 2 = [0 A], 3 = [A A]
   int dir[3] = {0, 0, 0};
   T ih[3] = {0, 0, 0};
@@ -452,15 +460,20 @@ class Engine : public EngineBase {
     if (d->op == SIPX_OP_CSC) configure_custom(s, d);
     else configure_op(s, d->op);
     configure_proj(s, d);
-    if (s.custom && !ata_R) throw std::runtime_error("a custom sparse operator needs its A'A in CDS (ata_R, ata_off)");
     if (s.custom && (s.comp || s.ext_kind))
-      throw std::runtime_error("custom sparse operators: Minkowski components and library-backed projectors are not available");
+      throw std::runtime_error("custom sparse operators (SIPX_OP_CSC): Minkowski components and library-backed projectors are not available; "
+                               "use one of the built-in operators for such a set");
+    if (s.custom && !ata_R) {              // matrix-free term of Q: no bands, the products go through the operator itself
+      const long long nnz = (long long)s.h_rowval.size();
+      check_mf_index_range(G_.N, s.Mtrue, nnz);
+      s.mfree = true;
+    }
     if (ata_R && s.comp) throw std::runtime_error("Minkowski sets use descriptor-generated AtA (pass ata_R = NULL)");
     if (ata_R) {
       if (d_i < 1 || d_i > 9) throw std::runtime_error("AtA band count out of range (1..9 bands per set)");
       s.ata_off.assign(ata_off, ata_off + d_i);
       s.host_ata.assign((const T*)ata_R, (const T*)ata_R + (size_t)G_.N * d_i);
-    } else {
+    } else if (!s.mfree) {
       s.ata_off = default_ata_offsets(s);
     }
     sets_.push_back(std::move(s));
@@ -595,6 +608,15 @@ class Engine : public EngineBase {
       if (mk_ && !owned_.empty()) throw std::runtime_error("set sharding is not available for Minkowski sets");
       if (mk_)
         for (auto& st : sets_) st.ata_off = default_ata_offsets(st);
+    }
+    for (int i = 0; i < p_n_; ++i) {
+      if (!sets_[i].mfree) continue;
+      const std::string who = "set " + std::to_string(i) + " is a custom sparse operator (SIPX_OP_CSC) passed without its A'A, a matrix-free term of Q: ";
+      if (stencil_q_) throw std::runtime_error(who + "the stencil form of Q has no place for it -- use SIPX_Q_CDS (Q_mode = \"cds\")");
+      if (comm_) throw std::runtime_error(who + "a sharded solve (either decomposition) has no form for it -- solve on one device, or pass the operator's A'A in CDS if it has at most " +
+                                          std::to_string(MAXD) + " bands");
+      if (mk_) throw std::runtime_error(who + "Minkowski components are not available for it -- use the built-in operators for Minkowski sets");
+      ++n_mfree_;
     }
     Nx_ = mk_ ? 2 * G_.N : G_.N;
     if (Nx_ >= (1ll << 31)) throw std::runtime_error("2^31 unknowns or more are not supported");
@@ -838,7 +860,8 @@ class Engine : public EngineBase {
       const bool small = Nx_ <= (1ll << 23);
       // (the z-marching product has a fused form of its own, k_cds_march<MODE 3>: there the fusion also saves traffic -- 8 N w
       //  instead of the 9 of product + p-update -- so it is the default at every size for the matrices the march takes)
-      cg_fused_ = !comm_ && !stencil_q_ && (forced >= 0 ? forced == 1 : (small || cds_.march != 0));
+      // (a matrix-free term of Q has no fused form: the product is followed by the term's two kernels)
+      cg_fused_ = !comm_ && !stencil_q_ && n_mfree_ == 0 && (forced >= 0 ? forced == 1 : (small || cds_.march != 0));
       if (cg_fused_) { p2_base_ = dalloc<T>(Nx_ + 2 * halo_); p2_ = p2_base_ + halo_; }
     }
     const long long c0 = std::max<long long>(0, wlo_), c1 = std::min<long long>(N, whi_);      // (sparse arrays: the rank's share only)
@@ -1141,7 +1164,7 @@ class Engine : public EngineBase {
       SetState<T>& s = sets_[i];
       for (void* b : s.halo_allocs) dzero(b, stream_);
       dzero(s.lh0, stream_); dzero(s.s0, stream_);
-      dzero(s.sbuf, stream_);
+      dzero(s.sbuf, stream_); dzero(s.mf_t, stream_);
       dzero(s.ptmp, stream_); dzero(s.mpart, stream_); dzero(s.cbuf, stream_);
       s.snap = -1;
       s.searches_done = 0;
@@ -1210,7 +1233,7 @@ class Engine : public EngineBase {
         a.x = mm;
         ext_feasibility(s, a, dst);
       } else if (s.custom) {                                   // s = A m materialised, then as for an identity set
-        K<T>::csr_spmv(stream_, s.Mtrue, s.d_rowptr, s.d_colidx, s.d_rval, mm, s.sbuf);
+        custom_fwd(stream_, s, mm, s.sbuf);
         if (s.two_pass) {
           SetArgs<T> a = set_args(s, rho_[i], gamma_[i], 0);
           a.x = s.sbuf;
@@ -1277,8 +1300,7 @@ class Engine : public EngineBase {
     else b.finish();
     for (int i = 0; i < p_n_; ++i) {       // caller-supplied sparse operators: rhs += A_i'(rho_i y_i + l_i), one launch each
       const SetState<T>& s = sets_[i];
-      if (s.owned && s.custom)
-        K<T>::csc_adj_rhs(stream_, G_.N, s.d_colptr, s.d_rowval, s.d_nzval, s.y, s.l, (T)rho[i], rhs_, 1);
+      if (s.owned && s.custom) custom_adj_rhs(stream_, s, (T)rho[i]);
     }
     if (comm_ && !slab_) {
       // the (+) reduction of the partial right-hand sides (rhs_compose.jl:17-20), delivered by z-slab: every rank receives
@@ -1310,6 +1332,8 @@ class Engine : public EngineBase {
     // (x_old is not written: the x-step leaves x_k behind in its own buffer, see the ring of x buffers)
     if (stencil_q_) K<T>::sq_resid(stream_, G_, sq_, x_, rhs_, p_, (T*)nullptr, (T*)nullptr, part_cg_);
     else K<T>::resid(stream_, Nx_, r0, r1, Q_, cds_, x_, rhs_, p_, (T*)nullptr, (T*)nullptr, part_cg_);
+    // matrix-free terms: r_0 -= rho_i A_i'(A_i x); the last launch replaces the partials of ||r_0||^2 (||rhs||^2 stays as it is)
+    mf_terms(x_, p_, /*sign*/ T(-1), /*dot*/ 2, nullptr, nullptr);
     if (comm_) {         // ||r_0||^2, ||rhs||^2 block partials [+ the per-set sums of the y/l update queued just before]; p_1 = r_0 is in p_
       comm_->allreduce_with_halo(part_cg_, (size_t)(2 * NB + merged_nslots_), SIPX_F64, p_ + r0, p_ + r0 - plane_, prev_, p_ + r1 - plane_,
                                  p_ + r1, next_, (size_t)plane_, dt, stream_);
@@ -1347,6 +1371,9 @@ class Engine : public EngineBase {
       CgState<T>* mirror = cg_host_ + (k & 1);
       if (stencil_q_) K<T>::sq_spmv_dot(stream_, G_, sq_, p_, Ap_, part_cg_, cg_dev_);
       else K<T>::spmv_dot(stream_, Nx_, r0, r1, Q_, cds_, p_, Ap_, part_cg_, cg_dev_);
+      // matrix-free terms: Ap += rho_i A_i'(A_i p); the last launch writes the partials of the complete p . Ap where the banded
+      // product put those of its part, so the x / r update reads what it always reads
+      mf_terms(p_, Ap_, T(1), /*dot*/ 1, p_, &cg_dev_->done);
       if (comm_) comm_->allreduce_sum(part_cg_, NB, SIPX_F64, stream_);
       K<T>::cg_update_xr(stream_, nloc, (k == 1 ? x_ : xn) + r0, xn + r0, (k == 1 ? p_ : r_) + r0, r_ + r0, p_ + r0, Ap_ + r0, part_cg_, cg_dev_, mirror, k,
                          (unsigned long long*)ticket_, hlo, hhi);
@@ -1784,7 +1811,7 @@ class Engine : public EngineBase {
     const Grid& gs = s.custom ? s.gm : Gr_;          // (the rank's slab when the whole iteration is slab-decomposed)
     const Grid& gy = s.custom ? s.gm : Gyl_;
     if (s.custom) {     // s = A x once, then the identity-shaped kernels on the M entries of s
-      K<T>::csr_spmv(q, s.Mtrue, s.d_rowptr, s.d_colidx, s.d_rval, a.x, s.sbuf);
+      custom_fwd(q, s, a.x, s.sbuf);
       a.x = s.sbuf;
       a.flags |= F_STORE_DY;
     }
@@ -1830,7 +1857,7 @@ class Engine : public EngineBase {
       s.last_gamma = a.gamma;
     }
     K<T>::yl(q, (s.slab_ext || s.slab_dft || (s.fan && s.ident)) ? gs : gy, a, part);      // (no adjoint stencil reads the plane below: nothing to recompute)
-    if (s.custom) K<T>::csc_adj_norm(q, G_.N, s.d_colptr, s.d_rowval, s.d_nzval, s.dy, part + (size_t)SL_ADJ * NB);
+    if (s.custom) custom_adj_norm(q, s, part + (size_t)SL_ADJ * NB);
     else if (!s.ident) K<T>::adj_norm(q, gs, a, part + (size_t)SL_ADJ * NB);
     if (feas && (s.slab_ext || s.slab_dft)) dist_feasibility(s, x_, fe2_part(i), i);
     else if (feas && s.fan) fan_feasibility(s, a, fe2_part(i));
@@ -2754,6 +2781,7 @@ class Engine : public EngineBase {
     a.nsets = 0;
     for (int i = 0; i < p_n_; ++i) {
       if (rho_new[i] == rho_old[i]) continue;                       // ind_updated, PARSDMM.jl:230
+      if (sets_[i].mfree) { sets_[i].mf_rho = (T)rho_new[i]; continue; }   // a matrix-free term: its rho is all Q holds of it
       push_qset(a, sets_[i], (T)rho_new[i] - (T)rho_old[i]);        // Q_update!.jl:47
     }
     q_apply(a);
@@ -3411,6 +3439,12 @@ class Engine : public EngineBase {
     if (Q) SIPX_HIP(hipMemcpy(Q, Q_, (size_t)Nx_ * cds_.d * sizeof(T), hipMemcpyDeviceToHost));
   }
 
+  void q_terms(int* bands, int* matrix_free) override {
+    need_final();
+    if (bands) *bands = stencil_q_ ? 0 : cds_.d;
+    if (matrix_free) *matrix_free = n_mfree_;
+  }
+
   void apply_Q(const void* x, void* y) override {     // y = Q x through the solver's own kernel (either mode)
     need_final();
     if (comm_ && comm_->world > 1) throw std::runtime_error("a sharded context maintains its slab of Q only");
@@ -3418,6 +3452,7 @@ class Engine : public EngineBase {
     SIPX_HIP(hipMemcpy(p_, x, Nx_ * sizeof(T), hipMemcpyHostToDevice));
     if (stencil_q_) K<T>::sq_spmv(stream_, G_, sq_, p_, Ap_);
     else K<T>::spmv(stream_, G_, Nx_, Q_, cds_, p_, Ap_);
+    mf_terms(p_, Ap_, T(1), 0, nullptr, nullptr);
     SIPX_HIP(hipStreamSynchronize(stream_));
     SIPX_HIP(hipMemcpy(y, Ap_, Nx_ * sizeof(T), hipMemcpyDeviceToHost));
   }
@@ -3430,6 +3465,7 @@ class Engine : public EngineBase {
     auto one = [&]() {
       if (stencil_q_) K<T>::sq_spmv(stream_, G_, sq_, x_, Ap_);
       else K<T>::spmv(stream_, G_, Nx_, Q_, cds_, x_, Ap_);
+      mf_terms(x_, Ap_, T(1), 0, nullptr, nullptr);
     };
     one();   // warm
     SIPX_HIP(hipEventRecord(a, stream_));
@@ -3806,7 +3842,92 @@ class Engine : public EngineBase {
   }
   // device copies: CSC as given, and the CSR view (rows ascending, columns ascending inside a row: a counting sort by row
   // of the column-major entries keeps that order) for s = A x
+  // a matrix-free term addresses its arrays with 32-bit indices: rows, columns and entries all below 2^31
+  static void check_mf_index_range(long long N, long long M, long long nnz) {
+    if (N >= (1ll << 31) || M >= (1ll << 31) || nnz >= (1ll << 31))
+      throw std::runtime_error("custom sparse operator (SIPX_OP_CSC) without its A'A: the matrix-free term of Q uses 32-bit indices and needs "
+                               "fewer than 2^31 columns, rows and stored entries (" + std::to_string(N) + ", " + std::to_string(M) + ", " +
+                               std::to_string(nnz) + " given) -- split the operator into several sets");
+  }
+  // Lanes that share one row of a compressed view: the smallest power of two that covers the mean length of the non-empty rows,
+  // 1 .. 64.  A wave then reads 64 / G rows' runs of values and indices per step; rows longer than the group take further strides,
+  // shorter ones leave lanes idle -- by the mean, as many lanes idle in the short rows as extra strides are walked in the long.
+  static int mf_lanes(const std::vector<int>& ptr) {
+    long long rows = 0;
+    for (size_t r = 0; r + 1 < ptr.size(); ++r) rows += ptr[r + 1] > ptr[r];
+    if (rows == 0) return 1;
+    const double mean = (double)ptr.back() / (double)rows;
+    int g = 1;
+    while (g < 64 && (double)g < mean) g *= 2;
+    return g;
+  }
+  // s = A x, rhs += A'(rho y + l), partials of ||A'(y - y_old)||^2 of a caller-supplied operator: a matrix-free term through the
+  // kernels its term of Q uses, a set that handed over CDS bands through the one-thread-per-row kernels as ever
+  void custom_fwd(hipStream_t q, const SetState<T>& s, const T* x, T* out) {
+    if (s.mfree) K<T>::mf_fwd(q, s.mfA, x, out, nullptr);
+    else K<T>::csr_spmv(q, s.Mtrue, s.d_rowptr, s.d_colidx, s.d_rval, x, out);
+  }
+  void custom_adj_rhs(hipStream_t q, const SetState<T>& s, T rho) {
+    if (!s.mfree) { K<T>::csc_adj_rhs(q, G_.N, s.d_colptr, s.d_rowval, s.d_nzval, s.y, s.l, rho, rhs_, 1); return; }
+    MfAdj<T> a;
+    a.y = s.y; a.l = s.l; a.rho = rho; a.in_mode = 1;
+    a.out = rhs_;
+    K<T>::mf_adj(q, s.mfAt, a);
+  }
+  void custom_adj_norm(hipStream_t q, const SetState<T>& s, double* partials) {
+    if (!s.mfree) { K<T>::csc_adj_norm(q, G_.N, s.d_colptr, s.d_rowval, s.d_nzval, s.dy, partials); return; }
+    MfAdj<T> a;
+    a.y = s.dy;
+    a.dot = 2; a.partials = partials;
+    K<T>::mf_adj(q, s.mfAt, a);
+  }
+  // out += sign * sum_i rho_i A_i'(A_i v) over the matrix-free terms, in set order, on the engine stream.  dot (MfAdj::dot) is
+  // taken by the LAST adjoint launch, on the complete `out`, into slot 0 of the CG partials.
+  void mf_terms(const T* v, T* out, T sign, int dot, const T* p, const int* done) {
+    if (n_mfree_ == 0) return;
+    int left = n_mfree_;
+    for (int i = 0; i < p_n_; ++i) {
+      const SetState<T>& s = sets_[i];
+      if (!s.mfree) continue;
+      K<T>::mf_fwd(stream_, s.mfA, v, s.mf_t, done);
+      MfAdj<T> a;
+      a.y = s.mf_t;
+      a.alpha = sign * s.mf_rho;
+      a.out = out;
+      a.done = done;
+      if (--left == 0 && dot) { a.dot = dot; a.p = p; a.partials = part_cg_; a.slot = 0; }
+      K<T>::mf_adj(stream_, s.mfAt, a);
+    }
+  }
+  void upload_mfree(SetState<T>& s) {
+    const long long N = G_.N, M = s.Mtrue, nnz = (long long)s.h_rowval.size();
+    std::vector<int> colptr(s.h_colptr.begin(), s.h_colptr.end()), rowidx(s.h_rowval.begin(), s.h_rowval.end());
+    std::vector<int> rowptr(M + 1, 0), colidx(nnz);
+    std::vector<T> rval(nnz);
+    for (long long k = 0; k < nnz; ++k) rowptr[rowidx[k] + 1]++;
+    for (long long r = 0; r < M; ++r) rowptr[r + 1] += rowptr[r];
+    std::vector<int> next(rowptr.begin(), rowptr.end() - 1);
+    for (long long j = 0; j < N; ++j)                       // (columns ascend inside a row of the CSR copy, as in upload_custom)
+      for (int k = colptr[j]; k < colptr[j + 1]; ++k) {
+        const int q = next[rowidx[k]]++;
+        colidx[q] = (int)j;
+        rval[q] = s.h_nzval[k];
+      }
+    auto up = [&](auto*& dst, const auto& src) {
+      using E = typename std::remove_reference<decltype(src)>::type::value_type;
+      dst = dalloc<E>(std::max<size_t>(src.size(), 1), false);
+      if (!src.empty()) SIPX_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice));
+    };
+    up(s.mf_colptr, colptr); up(s.mf_rowidx, rowidx); up(s.d_nzval, s.h_nzval);
+    up(s.mf_rowptr, rowptr); up(s.mf_colidx, colidx); up(s.d_rval, rval);
+    s.sbuf = dalloc<T>(M);
+    s.mf_t = dalloc<T>(M);
+    s.mfA.rows = (int)M; s.mfA.nnz = nnz; s.mfA.ptr = s.mf_rowptr; s.mfA.idx = s.mf_colidx; s.mfA.val = s.d_rval; s.mfA.lanes = mf_lanes(rowptr);
+    s.mfAt.rows = (int)N; s.mfAt.nnz = nnz; s.mfAt.ptr = s.mf_colptr; s.mfAt.idx = s.mf_rowidx; s.mfAt.val = s.d_nzval; s.mfAt.lanes = mf_lanes(colptr);
+    s.h_colptr.clear(); s.h_rowval.clear(); s.h_nzval.clear();
+  }
   void upload_custom(SetState<T>& s) {
+    if (s.mfree) { upload_mfree(s); return; }
     const long long N = G_.N, M = s.Mtrue, nnz = (long long)s.h_rowval.size();
     std::vector<long long> rowptr(M + 1, 0), colidx(nnz);
     std::vector<T> rval(nnz);
@@ -3891,11 +4012,16 @@ class Engine : public EngineBase {
       if (std::find(seen.begin(), seen.end(), o) == seen.end()) seen.push_back(o);
     };
     for (auto& s : sets_) {
+      if (s.mfree) continue;               // a matrix-free term contributes no bands
       if (s.ata_off.size() > 999) throw std::runtime_error("more than 999 bands in one set");
       for (long long o : s.ata_off) see(o);
       see(0);
     }
-    if ((int)seen.size() > MAXD) throw std::runtime_error("Q has more bands than this build supports");
+    see(0);                                // (every set matrix-free: Q keeps its -- zero -- diagonal band)
+    if ((int)seen.size() > MAXD)
+      throw std::runtime_error("Q has more bands than this build supports (" + std::to_string(seen.size()) + " > " + std::to_string(MAXD) +
+                               "): a custom sparse operator (SIPX_OP_CSC) can be passed without its A'A (ata_R = NULL) -- it then enters Q "
+                               "as a matrix-free term and contributes no bands");
     cds_.d = (int)seen.size();
     for (int b = 0; b < cds_.d; ++b) cds_.off[b] = seen[b];
     // symmetric read of Q (CdsArgs::sym): every negative band needs its positive partner, at a band index >= 1 so that
@@ -3997,7 +4123,10 @@ class Engine : public EngineBase {
     }
     QArgs<T> a;
     a.nsets = 0;
-    for (int i = 0; i < p_n_; ++i) push_qset(a, sets_[i], rho_[i]);   // Q = 0 + rho_1 AtA_1 + rho_2 AtA_2 + ...
+    for (int i = 0; i < p_n_; ++i) {                                 // Q = 0 + rho_1 AtA_1 + rho_2 AtA_2 + ...
+      if (sets_[i].mfree) sets_[i].mf_rho = rho_[i];                 // (a matrix-free term: no bands; sipx_reset comes through here too)
+      else push_qset(a, sets_[i], rho_[i]);
+    }
     q_apply(a);
   }
 
@@ -4332,7 +4461,8 @@ class Engine : public EngineBase {
     if (s.fan_ev) (void)hipEventDestroy(s.fan_ev);
     dfree(s.fanv);
     for (void* p : {(void*)s.ptmp, (void*)s.mpart, (void*)s.cbuf, (void*)s.d_colptr, (void*)s.d_rowval, (void*)s.d_rowptr,
-                    (void*)s.d_colidx, (void*)s.d_nzval, (void*)s.d_rval, (void*)s.sbuf})
+                    (void*)s.d_colidx, (void*)s.d_nzval, (void*)s.d_rval, (void*)s.sbuf, (void*)s.mf_colptr, (void*)s.mf_rowidx,
+                    (void*)s.mf_rowptr, (void*)s.mf_colidx, (void*)s.mf_t})
       dfree(p);
     for (void* p : s.halo_allocs) dfree(p);
     for (void* p : {(void*)s.lh0, (void*)s.s0, (void*)s.lb, (void*)s.ub, (void*)s.ata,
@@ -4375,6 +4505,7 @@ class Engine : public EngineBase {
   std::vector<double> feas_init_;
   T *p_base_ = nullptr, *m_base_ = nullptr, *r_base_ = nullptr, *p2_base_ = nullptr, *p2_ = nullptr;
   bool cg_fused_ = false;
+  int n_mfree_ = 0;                   // matrix-free terms of Q (custom sparse operators passed without A'A)
   long long halo_ = 0;
   T *x_ = nullptr, *xold_ = nullptr, *rhs_ = nullptr, *m_ = nullptr, *r_ = nullptr, *p_ = nullptr, *Ap_ = nullptr;
   T *Q_ = nullptr, *scr_v_ = nullptr, *scr_c_ = nullptr, *maxpart_ = nullptr;

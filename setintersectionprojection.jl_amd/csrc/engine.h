@@ -48,6 +48,7 @@ struct EngineBase {
   virtual void project(const sipx_set_desc* d, void* v, int64_t len) = 0;
   virtual void get_Q(void* Q, int64_t* offsets, int* d) = 0;
   virtual void apply_Q(const void* x, void* y) = 0;
+  virtual void q_terms(int* bands, int* matrix_free) = 0;
   virtual double time_spmv(int reps) = 0;
   virtual void kernel_stats(int enable, int64_t* launches, double* total_ms) = 0;
   virtual const char* kernel_stats_json(int enable) = 0;

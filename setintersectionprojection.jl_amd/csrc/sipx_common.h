@@ -65,7 +65,7 @@ enum KernelId {
   KID_CDS_SPMV = 0, KID_CDS_DOT, KID_CDS_RESID, KID_CDS_FUSED, KID_SQ_SPMV, KID_SQ_DOT, KID_SQ_RESID, KID_CG_BEGIN, KID_CG_XR, KID_CG_P,
   KID_Q_UPDATE, KID_FIN_SUM, KID_RHS, KID_YL, KID_YL_MULTI, KID_ADJ_NORM, KID_LOG3, KID_PASS_FIRST, KID_PASS_LEAN, KID_PASS_PROBE,
   KID_PASS_COMPACT, KID_PASS_DIST, KID_PASS_STORE, KID_PASS_MULTI, KID_SLOT_SUMS, KID_DECIDE, KID_SAMPLE, KID_L1_SOLVE, KID_GATHER,
-  KID_PS_RESCALE, KID_CARD, KID_EXT, KID_BB_RULE, KID_OTHER, KID_COUNT
+  KID_PS_RESCALE, KID_CARD, KID_EXT, KID_BB_RULE, KID_OTHER, KID_MF_FWD, KID_MF_ADJ, KID_COUNT
 };
 inline const char* kernel_name(int k) {
   static const char* const names[KID_COUNT] = {
@@ -73,7 +73,7 @@ inline const char* kernel_name(int k) {
       "k_cg_update_xr", "k_cg_update_p", "k_q_update", "k_fin_sum", "k_rhs", "k_yl", "k_yl_multi", "k_adj_norm", "k_log3",
       "k_pass<M_FIRST>", "k_pass<M_LEAN>", "k_pass<M_PROBE>", "k_pass<M_COMPACT>", "k_pass<M_DIST>", "k_pass<M_STORE>", "k_pass_multi",
       "k_slot_sums", "k_decide", "k_sample", "k_l1_solve", "k_gather_pack/unpack", "k_ps_rescale", "k_card_*", "ext_proj (library-backed)",
-      "k_bb_rule", "other"};
+      "k_bb_rule", "other", "k_mf_fwd", "k_mf_adj"};
   return (k >= 0 && k < KID_COUNT) ? names[k] : "?";
 }
 struct LaunchObserver {
@@ -453,6 +453,33 @@ struct RhsArgs {
   RhsSet<T> s[MAX_SETS];
 };
 
+// ---- matrix-free term of Q (kernels_sparse.hip): a caller-supplied sparse operator whose A'A is not kept as bands ----------
+// One compressed view of the operator with 32-bit indices: the CSR copy (rows = M, idx = columns) for t = A p, the CSC arrays
+// (rows = N, idx = row numbers) for A' t.  `lanes`: the power-of-two group of lanes (1..64) that shares one row of the view,
+// chosen by the engine from the view's row lengths (mf_lanes).
+template <typename T>
+struct MfOp {
+  int rows = 0;
+  long long nnz = 0;
+  const int* ptr = nullptr;       // rows + 1 entries
+  const int* idx = nullptr;
+  const T* val = nullptr;
+  int lanes = 1;
+};
+// out[j] = out[j] + alpha * (A' w)[j] over the CSC view, w = y (in_mode 0) or rho * y + l (in_mode 1); out == nullptr: nothing
+// is written.  dot: 0 none, 1: partials of p . out, 2: partials of the squares of out (of A' w itself when nothing is written)
+// into slot `slot` of `partials`.  done != nullptr: the launch returns at once when *done is set (CG already stopped).
+template <typename T>
+struct MfAdj {
+  const T *y = nullptr, *l = nullptr;
+  T rho = T(0), alpha = T(1);
+  T* out = nullptr;
+  const T* p = nullptr;
+  double* partials = nullptr;
+  int in_mode = 0, dot = 0, slot = 0;
+  const int* done = nullptr;
+};
+
 // State of one CG solve, device resident (mirrored to pinned host memory by the scalar kernels).
 template <typename T>
 struct CgState {
@@ -524,6 +551,9 @@ struct K {
                           const T* l, T rho, T* out, int accumulate);
   static void csc_adj_norm(hipStream_t s, long long N, const long long* colptr, const long long* row, const T* val, const T* dy,
                            double* partials);
+  // matrix-free term of Q (kernels_sparse.hip): out = A x over the CSR view; the adjoint step over the CSC view (MfAdj)
+  static void mf_fwd(hipStream_t s, const MfOp<T>& A, const T* x, T* out, const int* done);
+  static void mf_adj(hipStream_t s, const MfOp<T>& At, const MfAdj<T>& a);
   static void rows_pack(hipStream_t s, const Grid& g, int dir, long long nrows, const T* pad, T* rows);
   static void rows_unpack(hipStream_t s, const Grid& g, int dir, long long nrows, const T* rows, T* pad);
   static void fin_sum(hipStream_t s, const double* partials, int nslots, double* out_dev, double* out_host, unsigned* ticket = nullptr,

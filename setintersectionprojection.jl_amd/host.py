@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "sipx_kernel_stats_json", "sipx_comm_info", "sipx_device_bytes", "sipx_reset", "sipx_dwt",
     "sipx_learn_observations",
     "sipx_finalize_dev", "sipx_reset_dev", "sipx_download_dev", "sipx_set_caller_stream", "sipx_io_bytes",
+    "sipx_q_terms",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
@@ -48,6 +49,7 @@ TRANSFORMS = {"DCT": 1, "wavelet": 2}
 SPECIAL_OPERATORS = ("DFT", "DCT", "wavelet", "curvelet")     # src/setup_constraints.jl:54
 YL_FEAS, YL_BB, YL_FIRST = 1, 2, 4
 Q_MODES = {"cds": 0, "stencil": 1}
+MAX_Q_BANDS = 32        # bands the engine keeps of Q in CDS form (MAXD, csrc/sipx_common.h)
 
 
 class SipxError(RuntimeError):
@@ -297,12 +299,18 @@ class CustomOperator:
         G.sort_indices()
         N = G.shape[0]
         coo = G.tocoo()
-        offs = np.unique(coo.col.astype(np.int64) - coo.row.astype(np.int64))
+        diag = coo.col.astype(np.int64) - coo.row.astype(np.int64)
+        offs = np.unique(diag)
         R = np.zeros((N, len(offs)), self.TF, order="F")
-        col = {int(o): b for b, o in enumerate(offs)}
-        for r, c, v in zip(coo.row, coo.col, coo.data):
-            R[r, col[int(c) - int(r)]] = v
+        R[coo.row, np.searchsorted(offs, diag)] = coo.data      # (sorted indices, duplicates summed: every (row, band) once)
         return R, offs.astype(np.int64)
+
+    def ata_diagonals(self):
+        """Number of distinct diagonals of TD_OP' * TD_OP, from the sparsity patterns alone."""
+        import scipy.sparse as sp
+        P = sp.csc_matrix((np.ones(self.A.nnz, np.int64), self.A.indices, self.A.indptr), shape=self.A.shape)
+        coo = (P.T @ P).tocoo()
+        return len(np.unique(coo.col.astype(np.int64) - coo.row.astype(np.int64)))
 
 
 class Projector:
@@ -537,7 +545,10 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF):
 
 def PARSDMM_precompute_distribute(TD_OP, set_Prop, comp_grid, options):
     """src/PARSDMM_precompute_distribute.jl:6-77.  AtA[i] = None means "generate the CDS bands of
-    A_i'A_i on the device from the descriptor" (bit-identical to mat2CDS(TD_OP'*TD_OP))."""
+    A_i'A_i on the device from the descriptor" (bit-identical to mat2CDS(TD_OP'*TD_OP)).
+    A custom operator whose set is marked set_Prop.banded[i] = False, or whose A'A has more diagonals than the engine keeps
+    bands (MAX_Q_BANDS), gets AtA[i] = None and empty AtA_offsets[i] too: the engine applies it as a matrix-free term of Q,
+    the reference's sparse Q of a set that is not banded (PARSDMM_precompute_distribute.jl:51-59, argmin_x.jl:42-51)."""
     TF = np.dtype(options.FL).type
     n, _ = _grid(comp_grid)
     if not options.feasibility_only:
@@ -552,7 +563,10 @@ def PARSDMM_precompute_distribute(TD_OP, set_Prop, comp_grid, options):
     for i in range(p):
         kind = TD_OP[i].kind
         if kind == "custom":
-            AtA[i], set_Prop.AtA_offsets[i] = TD_OP[i].ata_cds()
+            if not set_Prop.banded[i] or TD_OP[i].ata_diagonals() > MAX_Q_BANDS:
+                AtA[i], set_Prop.AtA_offsets[i] = None, np.zeros(0, np.int64)
+            else:
+                AtA[i], set_Prop.AtA_offsets[i] = TD_OP[i].ata_cds()
             continue
         dirs = {"identity": [], "D_x": [0], "D_y": [1], "D_z": [len(n) - 1]}.get(kind, list(range(len(n))))
         strides = [int(np.prod(n[:a])) for a in dirs]
@@ -630,9 +644,7 @@ class Context:
         d.component = int(getattr(op, "component", 0))
         if d.component:
             self.Nx = 2 * self.N
-        if op.kind == "custom":
-            if AtA is None:
-                raise SipxError("a custom sparse operator needs its AtA (PARSDMM_precompute_distribute computes it)")
+        if op.kind == "custom":         # AtA = None: a matrix-free term of Q (sipx.h, SIPX_OP_CSC)
             cp = np.ascontiguousarray(op.A.indptr, np.int64); ri = np.ascontiguousarray(op.A.indices, np.int64)
             nz = np.ascontiguousarray(op.A.data, self.TF)
             self._keep += [cp, ri, nz]
@@ -664,6 +676,12 @@ class Context:
         y = np.empty_like(x)
         _chk(lib().sipx_apply_Q(self.h, _ptr(x), _ptr(y)))
         return y
+
+    def q_terms(self):
+        """(bands of the CDS part of Q, number of matrix-free terms) of the finalized context (sipx_q_terms)."""
+        b, f = C.c_int(), C.c_int()
+        _chk(lib().sipx_q_terms(self.h, C.byref(b), C.byref(f)))
+        return int(b.value), int(f.value)
 
     def set_decomp(self, mode: str):
         """"sets": the reference's split by constraint set; "slab": every rank works on its z-slab of every set (sipx.h)."""
