@@ -6,6 +6,7 @@
 #include "dist_dft.h"
 #include "ext_proj.h"
 #include "dwt.h"
+#include "solve_rules.h"
 
 #include <algorithm>
 #include <array>
@@ -249,59 +250,131 @@ inline void dzero(void* p, hipStream_t s) {
 }
 
 
-// Julia maximum(): NaN-propagating
-template <typename It>
-double julia_maximum(It b, It e) {
-  double m = -INFINITY;
-  for (; b != e; ++b) {
-    if (std::isnan(*b)) return NAN;
-    m = std::max(m, (double)*b);
-  }
-  return m;
-}
+// ---- small values of the whole-solve loop ------------------------------------------------------------------------------------
+static_assert(YL_FEAS == SIPX_YL_FEAS && YL_BB == SIPX_YL_BB && YL_FIRST == SIPX_YL_FIRST, "solve_rules.h numbers the flags like sipx.h");
 
-// Barzilai-Borwein scalar rule, reference src/adapt_rho_gamma.jl:55-126, all arithmetic in T.
-template <typename T>
-void bb_rule(T d_dHh_dlh, T n_d_H_hat, T n_d_l_hat, T n_d_l, T n_d_G_hat, T d_dGh_dl, bool adjust_rho,
-             bool adjust_gamma, T& rho, T& gamma) {
-  const T safeguard = sizeof(T) == 8 ? T(1e-10) : T(1e-6);   // :31-35
-  const T eps_correlation = T(0.3);                          // :37
-  bool alpha_reliable = false, beta_reliable = false;
-  T alpha_correlation = 0, beta_correlation = 0;
-  if ((n_d_H_hat * n_d_l_hat) > safeguard && (n_d_H_hat * n_d_H_hat) > safeguard && d_dHh_dlh > safeguard) {
-    alpha_reliable = true;
-    alpha_correlation = d_dHh_dlh / (n_d_H_hat * n_d_l_hat);
+// How one y/l update hands its sums to the host and whether its sweep may write the coming right-hand side: decided once per
+// call (yl_step; the phase entry point sipx_update_y_l takes the default) and passed down to where it is acted on.
+struct YlPlan {
+  enum class Route {
+    ByEvent,        // the host waits on an event recorded behind the reduction
+    ByWord,         // one rank: the host spins on a pinned word the last workgroup of the reduction publishes (k_fin_sum)
+    WithNextHead    // sharded: the all-reduce of the sums rides with the residual sums of the next x-step's head (argmin_x_head)
+  };
+  Route route = Route::ByEvent;
+  bool collect_now = true;           // the update waits for its sums itself; off: the caller collects them later (collect_set_sums)
+  bool fuse_rhs = false;             // rho cannot change before the next iteration: the sweep may write that iteration's rhs
+};
+
+// adds the host time of a scope to a section of log.timing (the host-only sections: bookkeeping, stop rule, rho / gamma rules)
+struct HostSection {
+  double& acc;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  explicit HostSection(double& a) : acc(a) {}
+  ~HostSection() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// Section timing of the whole-solve loop: ONE chain of marks on the engine stream (a record costs the stream about 5 us); the
+// time between two consecutive marks goes to the section named at the later one (-1: a mark that only opens an interval), four
+// marks per step in the common path.  Two sets of marks, by parity of the step: a step never waits for its own timing, the
+// marks of step i are resolved when step i + 2 begins.
+// timing_ms: [0] initialization (host side) [1] rhs [2] argmin x [3] y/l update [4] stop rule [5] rho / gamma rules [6] Q update
+// Grids of up to 2^23 points on one rank: the marks are recorded on iterations 1-4 and on every seventh after them (coprime
+// with the usual rho_update_frequency 2 / 3 and with the feasibility estimate's 10, so that the sample holds plain,
+// Barzilai-Borwein and feasibility iterations in their proportions), what they measure stands for the iterations since the
+// last such one, and the sums of the y/l update are awaited on a pinned word instead of the record behind them (k_fin_sum).
+// A record costs the stream up to 6 us -- two on a plain iteration, five on one that may change rho: 2048^2 2277 -> 2352 it/s,
+// the buckets then estimates (within 12 % of the every-iteration figures over 35 iterations); at 256^3 the same buys 0.4 % and
+// the buckets stay exact.  SIPX_MARK_STRIDE: 1 = every iteration, k = every k-th, whatever the grid.
+// (sharded: every iteration, unless SIPX_MARK_STRIDE says otherwise -- a rank's share of the headline on eight GPUs through RCCL
+//  with a world of one ran at 2215 it/s with the marks sampled and at 2219 without: its collectives leave gaps the records hide
+//  in; the sums then keep an event of their own, ev_sums_, where the marks are left out)
+// (round 5: every iteration by default at every size -- log.timing is a public field and means the same thing for every
+//  caller; the sampling that round 4 switched on by itself for grids of up to 2^23 points is opt-in: SIPX_MARK_STRIDE=7)
+struct SectionMarks {
+  enum { MAXMARK = 12 };
+  hipStream_t stream = nullptr;
+  std::vector<hipEvent_t> ev;          // 2 x MAXMARK
+  hipEvent_t open_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool open_valid[4] = {false, false, false, false};
+  int step[2] = {0, 0};                // the step whose marks sit in a parity's slots
+  double weight[2] = {1.0, 1.0};       // the iterations a timed step stands for
+  int n[2] = {0, 0};
+  int sec[2][MAXMARK];
+  int stride = 1, maxit = 0, last_timed = 0, par = 0;      // of the solve / the step in progress
+  bool timed = false;
+
+  void create(hipStream_t s) {
+    stream = s;
+    for (int k = 0; k < 2 * MAXMARK; ++k) {
+      hipEvent_t e;
+      SIPX_HIP(hipEventCreate(&e));
+      ev.push_back(e);
+    }
   }
-  if ((n_d_G_hat * n_d_l) > safeguard && (n_d_G_hat * n_d_G_hat) > safeguard && d_dGh_dl > safeguard) {
-    beta_reliable = true;
-    beta_correlation = d_dGh_dl / (n_d_G_hat * n_d_l);
+  void destroy() {
+    for (hipEvent_t e : open_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   }
-  bool alpha_comp = false, beta_comp = false;
-  T alpha_hat = 0, beta_hat = 0;
-  if (alpha_reliable && alpha_correlation > eps_correlation) {
-    alpha_comp = true;
-    const T mg = d_dHh_dlh / (n_d_H_hat * n_d_H_hat);
-    const T sd = (n_d_l_hat * n_d_l_hat) / d_dHh_dlh;
-    alpha_hat = (T(2) * mg) > sd ? mg : sd - mg / T(2);
+  void begin_solve(int maxit_) {
+    stride = env_knobs().mark_stride > 0 ? env_knobs().mark_stride : 1;
+    maxit = maxit_;
+    last_timed = 0;
+    for (bool& v : open_valid) v = false;
+    weight[0] = weight[1] = 1.0;
   }
-  if (beta_reliable && beta_correlation > eps_correlation) {
-    beta_comp = true;
-    const T mg = d_dGh_dl / (n_d_G_hat * n_d_G_hat);
-    const T sd = (n_d_l * n_d_l) / d_dGh_dl;
-    beta_hat = (T(2) * mg) > sd ? mg : sd - mg / T(2);
+  void reset() {                       // sipx_reset: whatever a solve that ended in an error left behind
+    begin_solve(0);
+    n[0] = n[1] = 0;
+    step[0] = step[1] = 0;
   }
-  if (adjust_rho) {
-    if (alpha_comp && beta_comp) rho = std::sqrt(alpha_hat * beta_hat);
-    else if (alpha_comp) rho = alpha_hat;
-    else if (beta_comp) rho = beta_hat;
+  bool is_timed(int it) const { return it <= maxit && (stride <= 1 || it <= 4 || it % stride == 0); }
+  void begin_step(int i) {
+    par = i & 1;
+    step[par] = i;
+    timed = is_timed(i);
+    if (timed) {
+      weight[par] = (double)(i - last_timed);
+      last_timed = i;
+    }
   }
-  if (adjust_gamma) {
-    if (alpha_comp && beta_comp) gamma = T(1) + ((T(2) * std::sqrt(alpha_hat * beta_hat)) / (alpha_hat + beta_hat));
-    else if (alpha_comp) gamma = T(1.9);
-    else if (beta_comp) gamma = T(1.1);
-    else gamma = T(1.5);
+  void mark(int section) {
+    if (!timed || n[par] >= MAXMARK) return;
+    SIPX_HIP(hipEventRecord(ev[par * MAXMARK + n[par]], stream));
+    sec[par][n[par]++] = section;
   }
-}
+  // the latest mark of the step in progress (nullptr: it has none)
+  hipEvent_t last_event() const { return timed && n[par] > 0 ? ev[par * MAXMARK + n[par] - 1] : nullptr; }
+  // the event a timed step's first interval starts from (round 4: the first mark of a step used to open nothing when the residual
+  // product had been queued ahead, and the x-step of every such iteration went uncounted -- "argmin x" read 0.21 of 0.5 ms)
+  // (four slots, by step: the opening of step i + 1 is recorded during step i, before the marks of step i - 1 are resolved)
+  void open(int at_step) {
+    if (!is_timed(at_step)) return;
+    const int k = at_step & 3;
+    if (!open_ev[k]) SIPX_HIP(hipEventCreate(&open_ev[k]));
+    SIPX_HIP(hipEventRecord(open_ev[k], stream));
+    open_valid[k] = true;
+  }
+  void resolve(sipx_log* log, int parity) {
+    const int cnt = n[parity];
+    const int slot = step[parity] & 3;
+    if (!cnt) { open_valid[slot] = false; return; }
+    n[parity] = 0;
+    SIPX_HIP(hipEventSynchronize(ev[parity * MAXMARK + cnt - 1]));
+    hipEvent_t prev = open_valid[slot] ? open_ev[slot] : nullptr;
+    open_valid[slot] = false;
+    const double w = weight[parity] > 0 ? weight[parity] : 1.0;
+    for (int k = 0; k < cnt; ++k) {
+      hipEvent_t e = ev[parity * MAXMARK + k];
+      if (sec[parity][k] >= 0 && prev) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, prev, e) == hipSuccess) log->timing_ms[sec[parity][k]] += w * ms;
+        else (void)hipGetLastError();
+      }
+      prev = e;
+    }
+  }
+};
 
 template <typename T>
 struct SetState {
@@ -438,11 +511,10 @@ class Engine : public EngineBase {
     if (cstream_) (void)hipStreamDestroy(cstream_);
     for (auto e : ev_c_) if (e) (void)hipEventDestroy(e);
     if (ev_sums_) (void)hipEventDestroy(ev_sums_);
-    for (hipEvent_t e : open_ev_) if (e) (void)hipEventDestroy(e);
     if (ev_cgb_) (void)hipEventDestroy(ev_cgb_);
     for (const PinnedBlock& b : pinned_blocks()) if (*b.p) (void)hipHostFree(*b.p);
     dfree(sums_ticket_);
-    for (auto e : ev_) (void)hipEventDestroy(e);
+    marks_.destroy();
     for (auto e : stat_ev_) (void)hipEventDestroy(e);
     for (auto e : cg_ev_) if (e) (void)hipEventDestroy(e);
     for (hipStream_t q : pool_) if (q != stream_) (void)hipStreamDestroy(q);
@@ -973,11 +1045,7 @@ class Engine : public EngineBase {
     for (int k = 0; k < 2; ++k) SIPX_HIP(hipEventCreateWithFlags(&cg_ev_[k], hipEventDisableTiming));
     SIPX_HIP(hipEventCreateWithFlags(&ev_cgb_, hipEventDisableTiming));
     SIPX_HIP(hipEventCreateWithFlags(&ev_sums_, hipEventDisableTiming));
-    for (int k = 0; k < 2 * MAXMARK; ++k) {      // two sets of section marks: a step never waits for its own timing
-      hipEvent_t e;
-      SIPX_HIP(hipEventCreate(&e));
-      ev_.push_back(e);
-    }
+    marks_.create(stream_);
   }
 
   // step 6: the device state of set i, its streams and scratch; step 7 for its own vectors: bounds and the warm start of l, y
@@ -1188,14 +1256,11 @@ class Engine : public EngineBase {
     sums_seq_ = 0; cg_seq_ = 0; spec_seq_ = 0;
     spec_searches_ = spec_fallbacks_ = spec_rounds_ = 0;
     batch_searches_ = batch_fallbacks_ = 0;
-    head_done_ = false; rs_pending_ = false; sums_pending_ = false; defer_sums_ = false; merge_sums_ = false; merged_nslots_ = 0;
-    rhs_fused_ = false; fuse_rhs_ = false; have_log_sums_ = false;
+    head_done_ = false; rs_pending_ = false; sums_pending_ = false; merged_nslots_ = 0;
+    rhs_fused_ = false; have_log_sums_ = false;
     obj_ss_ = evo_ss_ = xx_ss_ = 0;
-    sums_flags_ = 0; word_sums_ = false;
-    for (bool& v : open_valid_) v = false;
-    mark_weight_[0] = mark_weight_[1] = 1.0;
-    nmark_[0] = nmark_[1] = 0;
-    mark_step_[0] = mark_step_[1] = 0;
+    sums_flags_ = 0;
+    marks_.reset();
     run_ = Run();
     assemble_Q();
     build_q_table();
@@ -1255,7 +1320,7 @@ class Engine : public EngineBase {
         proj_dist_grid<T>(stream_, G_, s.nblk, s.dir, s.Mpad, scr_v_, s.prox, s.plo, s.phi, s.lb, s.ub, nullptr, dst);
       }
     }
-    reduce_set_sums(p_n_ * SLOTS);
+    reduce_set_sums(p_n_ * SLOTS, YlPlan::Route::ByEvent);
     SIPX_HIP(hipStreamSynchronize(stream_));
     for (int i = 0; i < p_n_ && slab_; ++i)
       if (hovf_[i]) {
@@ -1472,8 +1537,15 @@ class Engine : public EngineBase {
     }
   };
 
+  // the phase entry point: the default plan -- the sums by an event of their own, collected here, nothing fused
   void update_y_l(int it, int flags, const double* rho, const double* gamma, double* r_pri, double* r_dual,
                   double* feas) override {
+    yl_update(it, flags, rho, gamma, YlPlan(), r_pri, r_dual, feas);
+  }
+  // everything of a y/l update queued, the reduction of its sums included; then, unless the plan leaves that to the caller,
+  // the sums collected into r_pri, r_dual, feas (collect_set_sums)
+  void yl_update(int it, int flags, const double* rho, const double* gamma, const YlPlan& plan, double* r_pri = nullptr,
+                 double* r_dual = nullptr, double* feas = nullptr) {
     need_final();
     ObserverGuard og(observer());
     rhs_fused_ = false;
@@ -1493,11 +1565,11 @@ class Engine : public EngineBase {
     switch (regime) {
       case YlRegime::SweepAll:
         one_rank_searches(flags, rho, gamma);
-        sweep_launch(flags, rho, gamma, ma);
+        sweep_launch(flags, rho, gamma, ma, plan.fuse_rhs);
         break;
       case YlRegime::SweepPartial:
         one_rank_searches(flags, rho, gamma);
-        sweep_launch(flags, rho, gamma, ma);
+        sweep_launch(flags, rho, gamma, ma, plan.fuse_rhs);
         update_sets_in_turn(flags, rho, gamma, /*skip_swept*/ true, lane_now, /*own_streams*/ false);
         if (lane_now) lane_join(flags);
         rest_of_fused_rhs(rho);
@@ -1510,7 +1582,7 @@ class Engine : public EngineBase {
           // engine stream, in one order on every rank
           for (int i = 0; i < p_n_; ++i)
             if (sets_[i].two_pass) { sets_[i].last_rho = (T)rho[i]; sets_[i].last_gamma = (T)gamma[i]; }
-          sweep_launch(flags, rho, gamma, ma);
+          sweep_launch(flags, rho, gamma, ma, plan.fuse_rhs);
           if (flags & SIPX_YL_FEAS) slab_feasibility_searches(it, flags, rho, gamma);
         } else if (set_streams_) {
           SIPX_HIP(hipEventRecord(ev_fork_, stream_));      // the searches are done: the updates may start
@@ -1532,13 +1604,13 @@ class Engine : public EngineBase {
     }
     // Minkowski: evol_x runs over all 2N unknowns (PARSDMM.jl:145); the distance-term kernel only saw u + v
     if (mk_) K<T>::log3(stream_, Nx_, x_, (const T*)nullptr, xold_, part_sets_ + (size_t)p_n_ * SLOTS * NB);
-    reduce_set_sums((p_n_ + ((mk_ || comm_) ? 1 : 0)) * SLOTS);
+    reduce_set_sums((p_n_ + ((mk_ || comm_) ? 1 : 0)) * SLOTS, plan.route);
     sums_flags_ = flags;
     sums_pending_ = true;
-    if (!defer_sums_) {
+    if (plan.collect_now) {
       SIPX_HIP(hipEventRecord(ev_sums_, stream_));
       sums_event_ = ev_sums_;
-      collect_set_sums(rho, r_pri, r_dual, feas);
+      collect_set_sums(plan.route, rho, r_pri, r_dual, feas);
     }
   }
 
@@ -1905,7 +1977,7 @@ class Engine : public EngineBase {
     }
   }
 
-  // the sweep wrote the sum over the sets in front of the first loose one (fuse_rhs_); the rest, in order
+  // the sweep wrote the sum over the sets in front of the first loose one (YlPlan::fuse_rhs); the rest, in order
   void rest_of_fused_rhs(const double* rho) {
     if (!rhs_fused_) return;
     RhsBatch b(stream_, Gr_, rhs_, true);
@@ -2603,13 +2675,13 @@ class Engine : public EngineBase {
   // The y/l update of EVERY set in one sweep over the grid (kernels_multi.hip), on the engine stream, once the threshold /
   // scale of every two-pass set is known: one kernel updates all sets, forms the r_pri / r_dual / obj sums -- on
   // Barzilai-Borwein iterations the six BB sums and the snapshot refresh, every tenth iteration the feasibility estimates of
-  // the element-wise sets -- and, when the caller has announced that rho cannot change before the next iteration (fuse_rhs_),
+  // the element-wise sets -- and, when the caller has announced that rho cannot change before the next iteration (YlPlan::fuse_rhs),
   // writes the right-hand side of that iteration.
   // The sweep never updates in place (neighbouring tiles re-read the OLD y, l of a few points): it writes into the pair that
   // holds the old snapshot (BB / first iteration: it is read first), into the free pair, or -- when both other pairs are
   // taken, i.e. the snapshot must survive and sits in the other pair -- into a third pair, allocated by sipx_finalize.
   // (The per-set kernels may write in place and have two pairs: their rule is aim / rotate.)
-  void sweep_launch(int flags, const double* rho, const double* gamma, MultiArgs<T>& ma) {
+  void sweep_launch(int flags, const double* rho, const double* gamma, MultiArgs<T>& ma, bool fuse_rhs) {
     const bool first = (flags & SIPX_YL_FIRST) != 0, bb = (flags & SIPX_YL_BB) != 0 && !first;
     ma.nblk = 0;
     std::vector<int> target(p_n_, 0);          // 0: the other pair (y0, l0); 2: the third pair
@@ -2647,7 +2719,7 @@ class Engine : public EngineBase {
     // the coming x-steps leave its buffer alone (argmin_x)
     ma.x0 = (x0_mode_ && x_snap_ >= 0) ? xr_[x_snap_] : (x0_mode_ ? x_ : nullptr);
     ma.x0w = nullptr;
-    ma.rhs = fuse_rhs_ ? rhs_ : nullptr;
+    ma.rhs = fuse_rhs ? rhs_ : nullptr;
     ma.partials = part_sets_;
     if (!K<T>::yl_multi(stream_, G_, ma)) throw std::runtime_error("internal: the fused y/l sweep refused a block list it was prepared for");
     rhs_fused_ = ma.rhs != nullptr;
@@ -2666,12 +2738,12 @@ class Engine : public EngineBase {
   }
 
   // second half of update_y_l: waits for the reduced sums and turns them into the per-set scalars.  The whole-solve loop
-  // calls it late (defer_sums_), after it has queued the work of the next iteration that cannot depend on them.
-  void collect_set_sums(const double* rho, double* r_pri, double* r_dual, double* feas) {
+  // calls it late (YlPlan::collect_now off), after it has queued the work of the next iteration that cannot depend on them.
+  void collect_set_sums(YlPlan::Route route, const double* rho, double* r_pri, double* r_dual, double* feas) {
     if (!sums_pending_) throw std::runtime_error("no y/l update is pending");
     sums_pending_ = false;
     const int flags = sums_flags_;
-    if (sums_by_word_) wait_word(sums_word_, sums_seq_);
+    if (route == YlPlan::Route::ByWord) wait_word(sums_word_, sums_seq_);
     else SIPX_HIP(hipEventSynchronize(sums_event_));
     have_log_sums_ = false;
     if (slab_) {
@@ -3085,35 +3157,24 @@ class Engine : public EngineBase {
     Run& R = run_;
     R = Run();
     head_done_ = false;
-    for (bool& v : open_valid_) v = false;
-    mark_weight_[0] = mark_weight_[1] = 1.0;
+    marks_.begin_solve(opt->maxit);
     R.log = log;
     R.maxit = opt->maxit;
     const int p = p_n_, pp = pp_n_;
-    R.evol_rel_tol = (T)opt->evol_rel_tol; R.feas_tol = (T)opt->feas_tol; R.obj_tol = (T)opt->obj_tol;   // convert_options!
-    R.adjust_rho = opt->adjust_rho; R.adjust_gamma = opt->adjust_gamma; R.adjust_feas_rho = opt->adjust_feasibility_rho;
-    R.freq = opt->rho_update_frequency;
-    if (any_ncvx_) { R.freq = 3; R.adjust_gamma = false; }            // PARSDMM_initialize.jl:107-114
+    R.tol.evol_rel = (T)opt->evol_rel_tol; R.tol.feas = (T)opt->feas_tol; R.tol.obj = (T)opt->obj_tol;   // convert_options!
+    R.sw.adjust_rho = opt->adjust_rho; R.sw.adjust_gamma = opt->adjust_gamma; R.sw.adjust_feas_rho = opt->adjust_feasibility_rho;
+    R.sw.freq = opt->rho_update_frequency;
+    if (any_ncvx_) { R.sw.freq = 3; R.sw.adjust_gamma = false; }      // PARSDMM_initialize.jl:107-114
+    R.sw.ind_ref = R.maxit;
     std::fill(log->timing_ms, log->timing_ms + 7, 0.0);
     log->stopped_feasible = 0;
     for (int i = 0; i < pp; ++i) log->set_feasibility[i] = feas_init_[i];   // :236
-    const double maxf = julia_maximum(feas_init_.begin(), feas_init_.end());
     R.active = true;
-    if (pp > 0 && maxf < (double)R.feas_tol) {                        // :101-104, PARSDMM.jl:63-82
-      {
-        const long long c0 = slab_local_ ? std::max<long long>(0, wlo_) : 0, c1 = slab_local_ ? std::min<long long>(G_.N, whi_) : G_.N;
-        if (c1 > c0) SIPX_HIP(hipMemcpyAsync(x_ + c0, m_ + c0, (c1 - c0) * sizeof(T), hipMemcpyDeviceToDevice, stream_));
-      }
-      if (mk_) SIPX_HIP(hipMemsetAsync(x_ + G_.N, 0, G_.N * sizeof(T), stream_));      // x = [m; 0]  PARSDMM.jl:64-69
-      SIPX_HIP(hipStreamSynchronize(stream_));
-      log->n_iter = 1;
-      log->n_feas_rows = 1;
-      log->stopped_feasible = 1;
-      R.done = true;
+    if (pp > 0 && julia_maximum(feas_init_.begin(), feas_init_.end()) < (double)R.tol.feas) {     // :101-104
+      already_feasible();
       return;
     }
     R.counter = 2;
-    R.ind_ref = R.maxit;
     R.tol_ref = 1.0;
     R.rho.resize(p); R.gamma.resize(p); R.rho_new.resize(p); R.rpri.resize(p); R.rdual.resize(p);
     R.feas.resize(std::max(pp, 1));
@@ -3122,218 +3183,190 @@ class Engine : public EngineBase {
     log->n_feas_rows = R.counter;
     if (R.maxit < 1) R.done = true;
   }
+  // m lies in every set already: x = m, no iteration (PARSDMM.jl:63-82)
+  void already_feasible() {
+    sipx_log* log = run_.log;
+    {
+      const long long c0 = slab_local_ ? std::max<long long>(0, wlo_) : 0, c1 = slab_local_ ? std::min<long long>(G_.N, whi_) : G_.N;
+      if (c1 > c0) SIPX_HIP(hipMemcpyAsync(x_ + c0, m_ + c0, (c1 - c0) * sizeof(T), hipMemcpyDeviceToDevice, stream_));
+    }
+    if (mk_) SIPX_HIP(hipMemsetAsync(x_ + G_.N, 0, G_.N * sizeof(T), stream_));      // x = [m; 0]  PARSDMM.jl:64-69
+    SIPX_HIP(hipStreamSynchronize(stream_));
+    log->n_iter = 1;
+    log->n_feas_rows = 1;
+    log->stopped_feasible = 1;
+    run_.done = true;
+  }
 
+  // One iteration, PARSDMM.jl:97-254, as a software pipeline: nothing the GPU is given next may depend on the sums the host is
+  // about to read, so the right-hand side and the residual product of iteration i + 1 are queued (queue_ahead) before the
+  // host collects the sums of iteration i and runs the rules on them.
   bool parsdmm_step() override {
     Run& R = run_;
     if (!R.active) throw std::runtime_error("sipx_parsdmm_steps: call sipx_parsdmm_begin first");
     if (R.done) return true;
     ObserverGuard og(observer());
-    sipx_log* log = R.log;
-    const int p = p_n_, pp = pp_n_, maxit = R.maxit;
-    std::vector<double>&rho = R.rho, &gamma = R.gamma, &rho_new = R.rho_new, &rpri = R.rpri, &rdual = R.rdual, &feas = R.feas;
-    int& counter = R.counter;
     const int i = ++R.i;
-    const int par = i & 1;
-    resolve_timing(log, par);            // marks recorded two steps ago have long completed
-    // Grids of up to 2^23 points on one rank: the marks are recorded on iterations 1-4 and on every seventh after them (coprime
-    // with the usual rho_update_frequency 2 / 3 and with the feasibility estimate's 10, so that the sample holds plain,
-    // Barzilai-Borwein and feasibility iterations in their proportions), what they measure stands for the iterations since the
-    // last such one, and the sums of the y/l update are awaited on a pinned word instead of the record behind them (k_fin_sum).
-    // A record costs the stream up to 6 us -- two on a plain iteration, five on one that may change rho: 2048^2 2277 -> 2352 it/s,
-    // the buckets then estimates (within 12 % of the every-iteration figures over 35 iterations); at 256^3 the same buys 0.4 % and
-    // the buckets stay exact.  SIPX_MARK_STRIDE: 1 = every iteration, k = every k-th, whatever the grid.
-    // (sharded: every iteration, unless SIPX_MARK_STRIDE says otherwise -- a rank's share of the headline on eight GPUs through RCCL
-    //  with a world of one ran at 2215 it/s with the marks sampled and at 2219 without: its collectives leave gaps the records hide
-    //  in; the sums then keep an event of their own, ev_sums_, where the marks are left out)
-    // (round 5: every iteration by default at every size -- log.timing is a public field and means the same thing for every
-    //  caller; the sampling that round 4 switched on by itself for grids of up to 2^23 points is opt-in: SIPX_MARK_STRIDE=7)
-    const int stride = env_knobs().mark_stride > 0 ? env_knobs().mark_stride : 1;
-    auto is_timed = [&](int it) { return stride <= 1 || it <= 4 || it % stride == 0; };
-    const bool timed = is_timed(i), next_timed = i < maxit && is_timed(i + 1);
-    mark_step_[par] = i;
-    if (timed) {
-      mark_weight_[par] = (double)(i - R.last_timed);
-      R.last_timed = i;
+    begin_step(i);
+    x_step(i);
+    const YlPlan plan = yl_step(i);
+    queue_ahead(i, plan);
+    collect_set_sums(plan.route, R.rho.data(), R.rpri.data(), R.rdual.data(), R.feas.data());
+    record_log_row(i);
+    if (stop_rule(i)) {
+      finish_solve(i);
+      return true;
     }
-    word_sums_ = stride > 1 && !comm_;
-    struct WordSumsOff { bool& f; ~WordSumsOff() { f = false; } } word_sums_off{word_sums_};      // (the phase entry points keep the event)
-    // Section timing: ONE chain of marks on the engine stream (a record costs the stream about 5 us); the time between two
-    // consecutive marks goes to the section named at the later one (-1: a mark that only opens an interval), four marks per
-    // step in the common path.  The two host-only sections (stop rule, rho / gamma rules) use the host clock.
-    auto mark = [&](int section) {
-      if (!timed || nmark_[par] >= MAXMARK) return;
-      SIPX_HIP(hipEventRecord(ev_[par * MAXMARK + nmark_[par]], stream_));
-      mark_sec_[par][nmark_[par]++] = section;
-    };
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-    // can the rules at the end of iteration `it` change rho?  If not, the right-hand side of iteration it+1 is known as soon
-    // as the y/l kernels of `it` are queued
-    auto rho_may_change = [&](int it) {
-      for (int k = 0; k < p; ++k)          // the clamp to [1e-2, 1e4] runs every iteration (PARSDMM.jl:226): a rho_ini outside it changes at once
-        if ((T)rho[k] != std::max(std::min((T)rho[k], T(1e4)), T(1e-2))) return true;
-      return ((R.adjust_rho || R.adjust_gamma) && it % R.freq == 0) || (R.adjust_feas_rho && it % 10 == 0 && it > 10 && pp > 0);
-    };
-    {
-      // (the x-step's section opens where its residual product is queued: here, or in the step before when that was queued ahead)
-      if (!head_done_ && timed) open_section(i);
-      if (!R.rhs_ready) {
-        rhs_compose(rho.data());
-        mark(1);
-      }
-      R.rhs_ready = false;
-      int64_t cg_it; double relres; int flag;
-      argmin_x(i, &R.tol_ref, &cg_it, &relres, &flag);
-      log->cg_it[i - 1] = cg_it;
-      log->cg_relres[i - 1] = relres;
-      mark(2);
-      int flags = 0;
-      if (i % 10 == 0) flags |= SIPX_YL_FEAS;
-      if (i == 1) flags |= SIPX_YL_FIRST;
-      if ((R.adjust_rho || R.adjust_gamma) && i % R.freq == 0) flags |= SIPX_YL_BB;
-      defer_sums_ = true;                  // queue the kernels and the reduction of their sums, collect them further down
-      const bool rhs_known = i < maxit && !rho_may_change(i);
-      fuse_rhs_ = rhs_known;               // rhs_{i+1} may be formed by the sweep that forms y_{i+1}, l_{i+1}
-      merge_sums_ = rhs_known && comm_ != nullptr;
-      update_y_l(i, flags, rho.data(), gamma.data(), rpri.data(), rdual.data(), feas.data());
-      fuse_rhs_ = false;
-      defer_sums_ = false;
-      merge_sums_ = false;
-      mark(3);                             // also the event the host waits on for the sums (unless they come with the pinned word)
-      if (timed && nmark_[par] > 0) sums_event_ = ev_[par * MAXMARK + nmark_[par] - 1];
-      else if (!word_sums_) {              // (a step without marks whose sums do not come with the pinned word: sharded)
-        SIPX_HIP(hipEventRecord(ev_sums_, stream_));
-        sums_event_ = ev_sums_;
-      }
-      // Software pipeline: nothing the GPU is given next may depend on the sums the host is about to read.  When the rules
-      // below cannot touch rho, rhs_{i+1} = sum_i A_i'(rho_i y_i + l_i) (and, sharded, its reduce-scatter on the
-      // communication stream) is queued now and runs while the host waits for the sums and evaluates the stop rule.  A
-      // stop leaves x, y, l as they are: rhs is scratch.
-      if (rhs_fused_) {
-        R.rhs_ready = true;                  // written by the y/l sweep itself (kernels_multi.hip)
-      } else if (rhs_known) {
-        rhs_compose(rho.data());
-        mark(1);
-        R.rhs_ready = true;
-      }
-      // (round 3 had the product store x_old <- x, which a context without a distance term -- feasibility only -- still had to read
-      //  for evol_x after this point: its logged evol_x was zero.  The product no longer touches x_old: x_k stays behind in its own
-      //  ring buffer when the x-step moves on, tests/test_gpu_round4.py::test_feasibility_only_logs_evol_x...)
-      if (R.rhs_ready) {     // ... and so is the residual product of the coming x-step
-        if (next_timed) open_section(i + 1);         // (the coming step is a timed one: its x-step section opens here)
-        argmin_x_head();
-        if (comm_) {                         // (sharded: the sums arrive with the grouped call of the head)
-          // (an opening mark: the head's time belongs to the coming step's x-step section, which opened in front of it)
-          mark(-1);
-          if (timed && nmark_[par] > 0) sums_event_ = ev_[par * MAXMARK + nmark_[par] - 1];
-          else {
-            SIPX_HIP(hipEventRecord(ev_sums_, stream_));
-            sums_event_ = ev_sums_;
-          }
-        }
-      }
-      collect_set_sums(rho.data(), rpri.data(), rdual.data(), feas.data());
-      auto t_host = clk::now();
-      T sd = (T)rdual[0], sp = (T)rpri[0];
-      for (int k = 0; k < p; ++k) {
-        log->r_pri[(size_t)(i - 1) * p + k] = rpri[k];
-        log->r_dual[(size_t)(i - 1) * p + k] = rdual[k];
-        if (k > 0) { sd = sd + (T)rdual[k]; sp = sp + (T)rpri[k]; }
-        log->rho[(size_t)(i - 1) * p + k] = rho[k];
-        log->gamma[(size_t)(i - 1) * p + k] = gamma[k];
-      }
-      log->r_dual_total[i - 1] = (double)sd;                          // PARSDMM.jl:134
-      log->r_pri_total[i - 1] = (double)sp;                           // :138
-      if (i % 10 == 0) {                                              // update_y_l.jl:90-105
-        for (int k = 0; k < pp; ++k) log->set_feasibility[(size_t)(counter - 1) * pp + k] = feas[k];
-        counter += 1;
-      }
-      log_scalars(&log->obj[i - 1], &log->evol_x[i - 1]);
-      log->timing_ms[3] += ms_since(t_host);                          // bookkeeping of the y/l section
-      t_host = clk::now();
-      // ---- stop_PARSDMM.jl:23-52 ----
-      bool stop = false;
-      if (i > 6 && pp > 0) {
-        const double* row = log->set_feasibility + (size_t)(counter - 2) * pp;
-        if (julia_maximum(row, row + pp) < (double)R.feas_tol) {
-          double mx = -INFINITY; bool nan = false;
-          for (int k = i - 6; k < i; ++k) {
-            const T a = (T)log->obj[k], b = (T)log->obj[k - 1];
-            const T v = std::fabs((a - b) / b);
-            if (std::isnan(v)) nan = true;
-            mx = std::max(mx, (double)v);
-          }
-          if (!nan && mx < (double)R.obj_tol) stop = true;
-        }
-      }
-      if (i > 5 && julia_maximum(log->evol_x + (i - 6), log->evol_x + i) < (double)R.evol_rel_tol) stop = true;
-      if (i > 20 && R.adjust_rho) {
-        const int lo = std::max(i - 50, 1);
-        if (log->r_pri_total[i - 1] > julia_maximum(log->r_pri_total + (lo - 1), log->r_pri_total + (i - 1))) {
-          R.adjust_rho = R.adjust_feas_rho = R.adjust_gamma = false;
-          R.ind_ref = i;
-        }
-      }
-      if (!R.adjust_rho && i > R.ind_ref + 25) {
-        const int lo = std::max(R.ind_ref, std::max(i - 50, 1));
-        if (log->r_pri_total[i - 1] > julia_maximum(log->r_pri_total + (lo - 1), log->r_pri_total + (i - 1))) stop = true;
-      }
-      log->timing_ms[4] += ms_since(t_host);
-      if (stop) {
-        finish_solve(log, i, counter, rho, gamma);
-        return true;
-      }
-      t_host = clk::now();
-      // ---- adjust rho and gamma (PARSDMM.jl:163-227); l_hat / snapshots were fused into update_y_l ----
-      rho_new = rho;
-      if ((R.adjust_rho || R.adjust_gamma) && i % R.freq == 0)
-        adapt_rho_gamma(R.adjust_rho, R.adjust_gamma, rho_new.data(), gamma.data());
-      if (R.adjust_feas_rho && i % 10 == 0 && i > 10 && pp > 0) {       // :213-223
-        const double* row = log->set_feasibility + (size_t)(counter - 2) * pp;
-        int arg = 0;
-        bool found_nan = false;
-        for (int k = 0; k < pp && !found_nan; ++k) {
-          if (std::isnan(row[k])) { arg = k; found_nan = true; }
-          else if (row[k] > row[arg]) arg = k;
-        }
-        rho_new[arg] = (double)(T(2.0) * (T)rho_new[arg]);
-      }
-      for (int k = 0; k < p; ++k)                                      // :226
-        rho_new[k] = (double)std::max(std::min((T)rho_new[k], T(1e4)), T(1e-2));
-      log->timing_ms[5] += ms_since(t_host);
-      if (R.rhs_ready && rho_new != rho) throw std::runtime_error("internal: rho changed under a right-hand side queued ahead");
-      bool changed = false;
-      for (int k = 0; k < p; ++k) changed |= rho_new[k] != rho[k];
-      if ((i < maxit && !R.rhs_ready) || changed) mark(-1);           // the stream sat idle while the host decided
-      if (i < maxit && !R.rhs_ready) {     // rho is final now; queued ahead of the Q update so that, sharded, the
-        rhs_compose(rho_new.data());       // reduce-scatter (communication stream) runs beside it
-        mark(1);
-        R.rhs_ready = true;
-      }
-      if (changed) {
-        q_update(rho_new.data(), rho.data());                          // :230-243
-        mark(6);
-      }
-      rho = rho_new;
-    }
-    if (i == maxit) finish_solve(log, maxit, counter, rho, gamma);
+    next_rho(i);
+    apply_rho(i);
+    if (i == R.maxit) finish_solve(i);
     return R.done;
+  }
+
+  // the marks of step i - 2 (same parity) have long completed: into log.timing; then this step's parity, marks and weight
+  void begin_step(int i) {
+    marks_.resolve(run_.log, i & 1);
+    marks_.begin_step(i);
+  }
+
+  // rhs_i unless it was queued ahead, then x_i (PARSDMM.jl:101-107)
+  void x_step(int i) {
+    Run& R = run_;
+    // (the x-step's section opens where its residual product is queued: here, or in the step before when that was queued ahead)
+    if (!head_done_) marks_.open(i);
+    if (!R.rhs_ready) {
+      rhs_compose(R.rho.data());
+      marks_.mark(1);
+    }
+    R.rhs_ready = false;
+    int64_t cg_it; double relres; int flag;
+    argmin_x(i, &R.tol_ref, &cg_it, &relres, &flag);
+    R.log->cg_it[i - 1] = cg_it;
+    R.log->cg_relres[i - 1] = relres;
+    marks_.mark(2);
+  }
+
+  // y_i, l_i and the reduction of their sums, queued; the sums are collected further down (PARSDMM.jl:133).  Decides the plan:
+  // can the rules at the end of this iteration change rho?  If not, the right-hand side of iteration i + 1 is known as soon as
+  // the y/l kernels are queued, and the sweep that forms y, l may write it.
+  YlPlan yl_step(int i) {
+    Run& R = run_;
+    YlPlan plan;
+    plan.collect_now = false;
+    plan.fuse_rhs = i < R.maxit && !rho_may_change<T>(R.sw, i, pp_n_, R.rho.data(), p_n_);
+    if (comm_) plan.route = plan.fuse_rhs ? YlPlan::Route::WithNextHead : YlPlan::Route::ByEvent;
+    else plan.route = marks_.stride > 1 ? YlPlan::Route::ByWord : YlPlan::Route::ByEvent;
+    yl_update(i, yl_flags(R.sw, i), R.rho.data(), R.gamma.data(), plan);
+    marks_.mark(3);                        // also the event the host waits on for the sums (unless they come with the pinned word)
+    if (plan.route != YlPlan::Route::ByWord) sums_event_here();
+    return plan;
+  }
+  // the sums of the y/l update are complete behind the step's latest mark -- or, on a step without marks, behind ev_sums_, recorded here
+  void sums_event_here() {
+    sums_event_ = marks_.last_event();
+    if (sums_event_) return;
+    SIPX_HIP(hipEventRecord(ev_sums_, stream_));
+    sums_event_ = ev_sums_;
+  }
+
+  // Software pipeline: when the rules cannot touch rho, rhs_{i+1} = sum_i A_i'(rho_i y_i + l_i) (and, sharded, its
+  // reduce-scatter on the communication stream) is queued now and runs while the host waits for the sums and evaluates the
+  // stop rule -- and so is the residual product of the coming x-step.  A stop leaves x, y, l as they are: rhs is scratch.
+  void queue_ahead(int i, const YlPlan& plan) {
+    Run& R = run_;
+    if (rhs_fused_) {
+      R.rhs_ready = true;                  // written by the y/l sweep itself (kernels_multi.hip)
+    } else if (plan.fuse_rhs) {
+      rhs_compose(R.rho.data());
+      marks_.mark(1);
+      R.rhs_ready = true;
+    }
+    // (round 3 had the product store x_old <- x, which a context without a distance term -- feasibility only -- still had to read
+    //  for evol_x after this point: its logged evol_x was zero.  The product no longer touches x_old: x_k stays behind in its own
+    //  ring buffer when the x-step moves on, tests/test_gpu_round4.py::test_feasibility_only_logs_evol_x...)
+    if (!R.rhs_ready) return;
+    marks_.open(i + 1);                    // (if the coming step is a timed one: its x-step section opens here)
+    argmin_x_head();
+    if (comm_) {                           // (sharded: the sums arrive with the grouped call of the head)
+      marks_.mark(-1);                     // (an opening mark: the head's time belongs to the coming step's x-step section, which opened in front of it)
+      sums_event_here();
+    }
+  }
+
+  // row i of the log: residuals, rho, gamma, obj, evol_x; every tenth iteration a row of set_feasibility (PARSDMM.jl:134-147)
+  void record_log_row(int i) {
+    Run& R = run_;
+    sipx_log* log = R.log;
+    const int p = p_n_, pp = pp_n_;
+    HostSection t(log->timing_ms[3]);      // bookkeeping of the y/l section
+    for (int k = 0; k < p; ++k) {
+      log->r_pri[(size_t)(i - 1) * p + k] = R.rpri[k];
+      log->r_dual[(size_t)(i - 1) * p + k] = R.rdual[k];
+      log->rho[(size_t)(i - 1) * p + k] = R.rho[k];
+      log->gamma[(size_t)(i - 1) * p + k] = R.gamma[k];
+    }
+    log->r_dual_total[i - 1] = seq_sum<T>(R.rdual.data(), p);        // PARSDMM.jl:134
+    log->r_pri_total[i - 1] = seq_sum<T>(R.rpri.data(), p);          // :138
+    if (feas_due(i)) {                                               // update_y_l.jl:90-105
+      for (int k = 0; k < pp; ++k) log->set_feasibility[(size_t)(R.counter - 1) * pp + k] = R.feas[k];
+      R.counter += 1;
+    }
+    log_scalars(&log->obj[i - 1], &log->evol_x[i - 1]);
+  }
+
+  // stop_PARSDMM.jl:23-52 on the log so far; may switch the adjust_* rules off for the rest of the solve
+  bool stop_rule(int i) {
+    Run& R = run_;
+    HostSection t(R.log->timing_ms[4]);
+    const LogView view{R.log->set_feasibility, R.log->obj, R.log->evol_x, R.log->r_pri_total};
+    return sipx::stop_rule<T>(view, i, R.counter, pp_n_, R.tol, R.sw);
+  }
+
+  // adjust rho and gamma (PARSDMM.jl:163-227) into rho_new; l_hat / snapshots were fused into update_y_l
+  void next_rho(int i) {
+    Run& R = run_;
+    HostSection t(R.log->timing_ms[5]);
+    R.rho_new = R.rho;
+    if (bb_due(R.sw, i)) adapt_rho_gamma(R.sw.adjust_rho, R.sw.adjust_gamma, R.rho_new.data(), R.gamma.data());
+    const double* latest = R.log->set_feasibility + (size_t)(R.counter - 2) * pp_n_;
+    sipx::next_rho<T>(R.sw, i, pp_n_, latest, R.rho_new.data(), p_n_);
+  }
+
+  // rho_new takes effect: the right-hand side of the coming iteration if it is not queued yet, then the Q update (:230-243)
+  void apply_rho(int i) {
+    Run& R = run_;
+    if (R.rhs_ready && R.rho_new != R.rho) throw std::runtime_error("internal: rho changed under a right-hand side queued ahead");
+    bool changed = false;
+    for (int k = 0; k < p_n_; ++k) changed |= R.rho_new[k] != R.rho[k];
+    const bool rhs_due = i < R.maxit && !R.rhs_ready;
+    if (rhs_due || changed) marks_.mark(-1);     // the stream sat idle while the host decided
+    if (rhs_due) {                         // rho is final now; queued ahead of the Q update so that, sharded, the
+      rhs_compose(R.rho_new.data());       // reduce-scatter (communication stream) runs beside it
+      marks_.mark(1);
+      R.rhs_ready = true;
+    }
+    if (changed) {
+      q_update(R.rho_new.data(), R.rho.data());
+      marks_.mark(6);
+    }
+    R.rho = R.rho_new;
   }
 
   // common exit of the whole solve (stop rule or maxit): timing resolved, logs truncated, and the context left so that a
   // later solve on it continues from here -- Q holds sum_i rho_i AtA_i for exactly these rho
-  void finish_solve(sipx_log* log, int n_iter, int counter, const std::vector<double>& rho, const std::vector<double>& gamma) {
+  void finish_solve(int n_iter) {
+    Run& R = run_;
     if (rs_pending_) {                      // a right-hand side queued ahead: let its exchange finish before anyone touches rhs
       SIPX_HIP(hipStreamWaitEvent(stream_, ev_c_[1], 0));
       rs_pending_ = false;
     }
-    resolve_timing(log, 0);
-    resolve_timing(log, 1);
-    log->n_iter = n_iter;
-    log->n_feas_rows = counter;
-    for (int k = 0; k < p_n_; ++k) { rho_[k] = (T)rho[k]; gamma_[k] = (T)gamma[k]; }
-    run_.rhs_ready = false;
-    run_.done = true;
+    marks_.resolve(R.log, 0);
+    marks_.resolve(R.log, 1);
+    R.log->n_iter = n_iter;
+    R.log->n_feas_rows = R.counter;
+    for (int k = 0; k < p_n_; ++k) { rho_[k] = (T)R.rho[k]; gamma_[k] = (T)R.gamma[k]; }
+    R.rhs_ready = false;
+    R.done = true;
     head_done_ = false;
   }
 
@@ -4322,81 +4355,37 @@ class Engine : public EngineBase {
     dfree(tmp);
   }
 
-  // the event a timed step's first interval starts from (round 4: the first mark of a step used to open nothing when the residual
-  // product had been queued ahead, and the x-step of every such iteration went uncounted -- "argmin x" read 0.21 of 0.5 ms)
-  // (four slots, by step: the opening of step i + 1 is recorded during step i, before the marks of step i - 1 are resolved)
-  void open_section(int step) {
-    const int k = step & 3;
-    if (!open_ev_[k]) SIPX_HIP(hipEventCreate(&open_ev_[k]));
-    SIPX_HIP(hipEventRecord(open_ev_[k], stream_));
-    open_valid_[k] = true;
-  }
-  void resolve_timing(sipx_log* log, int par) {
-    const int n = nmark_[par];
-    const int slot = mark_step_[par] & 3;
-    if (!n) { open_valid_[slot] = false; return; }
-    nmark_[par] = 0;
-    // timing_ms: [0] initialization (host side) [1] rhs [2] argmin x [3] y/l update [4] stop rule [5] rho / gamma rules [6] Q update
-    SIPX_HIP(hipEventSynchronize(ev_[par * MAXMARK + n - 1]));
-    hipEvent_t prev = open_valid_[slot] ? open_ev_[slot] : nullptr;
-    open_valid_[slot] = false;
-    const double w = mark_weight_[par] > 0 ? mark_weight_[par] : 1.0;      // the iterations this timed one stands for
-    for (int k = 0; k < n; ++k) {
-      hipEvent_t e = ev_[par * MAXMARK + k];
-      const int sec = mark_sec_[par][k];
-      if (sec >= 0 && prev) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, prev, e) == hipSuccess) log->timing_ms[sec] += w * ms;
-        else (void)hipGetLastError();
-      }
-      prev = e;
-    }
-  }
-
   int dtype_code() const { return sizeof(T) == 8 ? SIPX_F64 : SIPX_F32; }
 
   // partials of the per-set slots -> hres_ (pinned).  Sharded: summed over the ranks on the way (sets a rank does not own
   // contribute the zeros their slots were allocated with), so every rank reads the sums of every set.
-  void reduce_set_sums(int nslots) {
-    if (comm_ && merge_sums_) {            // their all-reduce rides with the residual sums of the next x-step (argmin_x_head)
+  void reduce_set_sums(int nslots, YlPlan::Route route) {
+    if (comm_ && route == YlPlan::Route::WithNextHead) {
       K<T>::fin_sum(stream_, part_sets_, nslots, dres_, nullptr);
       merged_nslots_ = nslots;
     } else if (comm_) {
       K<T>::fin_sum(stream_, part_sets_, nslots, dres_, nullptr);
       comm_->allreduce_sum(dres_, (size_t)nslots, SIPX_F64, stream_);
       K<T>::copy_f64(stream_, dres_, hres_, nslots);
-    } else if (word_sums_) {
-      // (one rank, whole-solve loop: the host spins on a pinned word the last workgroup publishes, see k_fin_sum)
+    } else if (route == YlPlan::Route::ByWord) {
       K<T>::fin_sum(stream_, part_sets_, nslots, nullptr, hres_, sums_ticket_, (unsigned long long*)sums_word_, ++sums_seq_);
-      sums_by_word_ = true;
-      return;
     } else {
       K<T>::fin_sum(stream_, part_sets_, nslots, nullptr, hres_);
     }
-    sums_by_word_ = false;
   }
 
-  // Verdict of CG iteration `iter` of solve `seq`: spins on the ticket word, which the device publishes as soon as the
-  // verdict is known (and after the state mirror, so that is complete too).  Every enqueued iteration publishes one; should
-  // the stream nevertheless run dry without it (a faulted kernel), the mirror decides.
-  bool wait_ticket(unsigned seq, int iter, const CgState<T>* mirror) {
-    // ticket = (seq << 32) | (iter << 1) | done.  A ticket of a LATER iteration of this solve (small grids queue one
-    // iteration ahead) means that this one did not converge: past `done` no kernel publishes anything.
-    auto verdict = [&](unsigned long long t, bool& done) {
-      if ((unsigned)(t >> 32) != seq) return false;
-      const unsigned ti = (unsigned)(t & 0xffffffffull) >> 1;
-      if (ti < (unsigned)iter) return false;
-      done = ti == (unsigned)iter ? (t & 1ull) != 0 : false;
-      return true;
-    };
-    bool done = false;
+  // The one spin-wait on a pinned word the device publishes.  arrived() loads the word (each caller with its own memory order)
+  // and says whether it holds what is awaited.  Whenever (spins & query_mask) == 0 the stream is queried -- a query costs the
+  // runtime tens of microseconds: rarely -- and should it have run dry without the word (a faulted kernel), ran_dry() decides.
+  template <typename Arrived, typename RanDry>
+  void spin_until(Arrived arrived, unsigned query_mask, RanDry ran_dry) {
     for (unsigned spins = 1;; ++spins) {
-      if (verdict(__atomic_load_n(ticket_, __ATOMIC_ACQUIRE), done)) return done;
-      if ((spins & 0xfff) == 0) {
+      if (arrived()) return;
+      if ((spins & query_mask) == 0) {
         const hipError_t q = hipStreamQuery(stream_);
         if (q == hipSuccess) {
-          if (verdict(__atomic_load_n(ticket_, __ATOMIC_ACQUIRE), done)) return done;
-          return mirror->done != 0;
+          if (!arrived()) ran_dry();
+          return;
         }
         if (q != hipErrorNotReady) SIPX_HIP(q);
         (void)hipGetLastError();        // hipErrorNotReady is not an error: keep it out of the launch checks
@@ -4404,20 +4393,38 @@ class Engine : public EngineBase {
     }
   }
 
+  // Verdict of CG iteration `iter` of solve `seq`: spins on the ticket word, which the device publishes as soon as the
+  // verdict is known (and after the state mirror, so that is complete too).  Every enqueued iteration publishes one; should
+  // the stream nevertheless run dry without it, the mirror decides.
+  bool wait_ticket(unsigned seq, int iter, const CgState<T>* mirror) {
+    // ticket = (seq << 32) | (iter << 1) | done.  A ticket of a LATER iteration of this solve (small grids queue one
+    // iteration ahead) means that this one did not converge: past `done` no kernel publishes anything.
+    bool done = false;
+    spin_until([&] {
+      const unsigned long long t = __atomic_load_n(ticket_, __ATOMIC_ACQUIRE);
+      if ((unsigned)(t >> 32) != seq) return false;
+      const unsigned ti = (unsigned)(t & 0xffffffffull) >> 1;
+      if (ti < (unsigned)iter) return false;
+      done = ti == (unsigned)iter ? (t & 1ull) != 0 : false;
+      return true;
+    }, 0xfff, [&] { done = mirror->done != 0; });
+    return done;
+  }
+
   // the sequence number k_fin_sum publishes behind the sums (pinned; see there)
   void wait_word(volatile unsigned long long* word, unsigned long long seq) {
-    for (unsigned spins = 1;; ++spins) {
-      if (__atomic_load_n((unsigned long long*)word, __ATOMIC_ACQUIRE) == seq) return;
-      if ((spins & 0x3ffff) == 0) {
-        const hipError_t q = hipStreamQuery(stream_);
-        if (q == hipSuccess) {
-          if (__atomic_load_n((unsigned long long*)word, __ATOMIC_ACQUIRE) == seq) return;
-          throw std::runtime_error("internal: the stream ran dry without the sums of the y/l update (a kernel faulted?)");
-        }
-        if (q != hipErrorNotReady) SIPX_HIP(q);
-        (void)hipGetLastError();
-      }
-    }
+    spin_until([&] { return __atomic_load_n((unsigned long long*)word, __ATOMIC_ACQUIRE) == seq; }, 0x3ffff, [] {
+      throw std::runtime_error("internal: the stream ran dry without the sums of the y/l update (a kernel faulted?)");
+    });
+  }
+
+  // the word k_spec_decide publishes for a set: (seq << 2) | verdict bits
+  unsigned wait_verdict(volatile unsigned* word, unsigned seq) {
+    unsigned w = 0;
+    spin_until([&] { return ((w = __atomic_load_n((unsigned*)word, __ATOMIC_ACQUIRE)) >> 2) == seq; }, 0x3ffff, [] {
+      throw std::runtime_error("internal: the stream ran dry without the verdict of a threshold search (a kernel faulted?)");
+    });
+    return w & 3u;
   }
 
   void dump_ps(int set, const double* reg) {       // SIPX_SPEC_DEBUG: the state of a search as the device sees it (synchronises)
@@ -4435,24 +4442,6 @@ class Engine : public EngineBase {
     std::fprintf(stderr, " asum %.6g ovf %.0f\n", r[0], r[PREP_SLOTS]);
     std::fprintf(stderr, "[sipx spec]       theta %.9g theta_prev %.9g hw %.4g sampled %d samp_theta %.9g samp (%.9g, %.9g) samp_c %.0f want_sample %d rescaled %d\n",
                  (double)h.theta, h.theta_prev, h.hw, h.sampled, h.samp_theta, h.samp_lo, h.samp_hi, h.samp_c, h.want_sample, h.rescaled);
-  }
-
-  // the word k_spec_decide publishes for a set: (seq << 2) | verdict bits
-  unsigned wait_verdict(volatile unsigned* word, unsigned seq) {
-    for (unsigned spins = 1;; ++spins) {
-      const unsigned w = __atomic_load_n((unsigned*)word, __ATOMIC_ACQUIRE);
-      if ((w >> 2) == seq) return w & 3u;
-      if ((spins & 0x3ffff) == 0) {          // (a stream query costs the runtime tens of microseconds: rarely)
-        const hipError_t q = hipStreamQuery(stream_);
-        if (q == hipSuccess) {
-          const unsigned w2 = __atomic_load_n((unsigned*)word, __ATOMIC_ACQUIRE);
-          if ((w2 >> 2) == seq) return w2 & 3u;
-          throw std::runtime_error("internal: the stream ran dry without the verdict of a threshold search (a kernel faulted?)");
-        }
-        if (q != hipErrorNotReady) SIPX_HIP(q);
-        (void)hipGetLastError();
-      }
-    }
   }
 
   void free_set(SetState<T>& s) {
@@ -4473,15 +4462,15 @@ class Engine : public EngineBase {
   struct Run {     // state of one whole solve (sipx_parsdmm_begin / _steps)
     bool active = false, done = false;
     sipx_log* log = nullptr;
-    int maxit = 0, freq = 2, counter = 2, ind_ref = 0, i = 0, last_timed = 0;
-    T evol_rel_tol = 0, feas_tol = 0, obj_tol = 0;
-    bool adjust_rho = true, adjust_gamma = true, adjust_feas_rho = true;
+    int maxit = 0, counter = 2, i = 0;
+    Tolerances<T> tol;
+    RuleSwitches sw;               // what the options switch on, as the stop rule has left it
     double tol_ref = 1.0;
     bool rhs_ready = false;        // the right-hand side of the coming iteration is already queued
     std::vector<double> rho, gamma, rho_new, rpri, rdual, feas;
   };
-  enum { MAXMARK = 12 };
   Run run_;
+  SectionMarks marks_;
   int device_ = 0, ndim_ = 2;
   hipStream_t stream_ = nullptr;
   // device-resident boundary: the caller's stream and the two events that order it against the engine stream; whether the call
@@ -4533,7 +4522,6 @@ class Engine : public EngineBase {
   volatile unsigned long long* sums_word_ = nullptr;   // pinned: sequence number of the latest reduction of the set sums (k_fin_sum)
   unsigned* sums_ticket_ = nullptr;
   unsigned long long sums_seq_ = 0;
-  bool sums_by_word_ = false, word_sums_ = false;      // word_sums_: set by the whole-solve loop for the duration of a step (one rank)
   volatile int* hlean_ = nullptr;     // per set: the coming l1 search wants a sampled prediction (written by k_l1_solve)
   volatile int* hovf_ = nullptr;      // per set: the slab-decomposed search overflowed its exchange segments (k_gather_unpack)
   volatile unsigned* hverd_ = nullptr;   // per set: verdict of the speculative exchange of a slab-decomposed search (k_spec_decide)
@@ -4561,16 +4549,8 @@ class Engine : public EngineBase {
   // x0 mode is simply the buffer that held x on the last BB / first iteration (1 N w per BB iteration written before).
   T *xr_base_[3] = {nullptr, nullptr, nullptr}, *xr_[3] = {nullptr, nullptr, nullptr};
   int x_cur_ = 0, x_snap_ = -1;
-  bool fuse_rhs_ = false;             // the whole-solve loop: rho cannot change before the next iteration, so the sweep may write its rhs
-  bool rhs_fused_ = false;            // ... and did
-  std::vector<hipEvent_t> ev_;
-  hipEvent_t open_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool open_valid_[4] = {false, false, false, false};
-  int mark_step_[2] = {0, 0};          // the step whose marks sit in a parity's slots
-  double mark_weight_[2] = {1.0, 1.0};
-  int nmark_[2] = {0, 0};
-  int mark_sec_[2][MAXMARK];
-  hipEvent_t sums_event_ = nullptr;
+  bool rhs_fused_ = false;            // the sweep of the latest y/l update wrote the right-hand side of the coming iteration (YlPlan::fuse_rhs)
+  hipEvent_t sums_event_ = nullptr;   // the event behind which the sums of the latest y/l update are complete (unless they come by word)
   // sharded solve: communicator, this rank's slab [r0_, r1_) of the x-step, rows of Q it maintains
   std::unique_ptr<Comm> comm_;
   CountingComm* counting_ = nullptr;   // comm_ itself, with its call counters
@@ -4581,7 +4561,7 @@ class Engine : public EngineBase {
   bool rs_pending_ = false;
   double* dres_ = nullptr;                  // device copy of the reduced per-set sums (all-reduce buffer)
   hipEvent_t ev_sums_ = nullptr, ev_cgb_ = nullptr;
-  bool sums_pending_ = false, defer_sums_ = false;
+  bool sums_pending_ = false;
   T* qtab_ = nullptr;                   // class table of Q + the check's flag (build_q_table)
   bool q_stale_ = false;                // the stored bands lag the table (ensure_q_bands)
   std::string qtab_reason_ = "not built";   // why the products use the bands ("": they use the table)
@@ -4589,8 +4569,7 @@ class Engine : public EngineBase {
   bool slab_dist_logs_ = false;       // slab-decomposed and a distance term among the sets: obj / evol_x sums come from its y/l update
   bool lean_multi_ = false;           // k_lean_multi for the lean first passes of the l1 searches (finalize: above 2^24 grid points; SIPX_LEAN_MULTI=0/1)
   bool head_done_ = false;            // the residual product of the coming x-step is queued already (argmin_x_head)
-  bool merge_sums_ = false;           // sharded whole-solve loop: the coming reduction of the set sums leaves its all-reduce to argmin_x_head
-  int merged_nslots_ = 0;
+  int merged_nslots_ = 0;             // sums whose all-reduce the coming argmin_x_head carries (YlPlan::Route::WithNextHead)
   int sums_flags_ = 0;
   volatile unsigned long long* ticket_ = nullptr;   // pinned: verdict of the latest CG iteration (publish_ticket)
   unsigned cg_seq_ = 0;
