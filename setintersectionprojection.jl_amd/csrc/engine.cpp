@@ -3432,6 +3432,11 @@ class Engine : public EngineBase {
         st.spec.basis = st.host_basis.empty() ? nullptr : st.host_basis.data();
         ExtProj<T> ext(st.spec, stream_);
         ext.project(dv, false, part, mp, dc);
+        if (st.ext_kind == EXT_RANK) {             // the route of a stand-alone call counts like a set's (rank_route)
+          long long c[4];
+          ext.route_counts(c);
+          for (int q = 0; q < 4; ++q) project_rc_[q] += c[q];
+        }
       } else {                                   // per-fiber bounds, expanded by configure_proj
         lb = dalloc<T>(len); ub = dalloc<T>(len);
         SIPX_HIP(hipMemcpy(lb, st.host_lb.data(), len * sizeof(T), hipMemcpyHostToDevice));
@@ -3526,8 +3531,8 @@ class Engine : public EngineBase {
   }
   // enable = -1: the counters only (slab_searches, rank_route) -- no synchronisation, the collection and its samples stay as they are
   const char* kernel_stats_json(int enable) override {
-    need_final();
     const bool peek = enable < 0;
+    if (!peek) need_final();         // (the counters exist before that: a context that only served sipx_project has its rank_route)
     std::vector<KAgg> agg = peek ? std::vector<KAgg>(KID_COUNT) : aggregate_samples();
     std::string& o = stats_json_;
     o = "{\"mode\": " + std::to_string(stats_mode_) + ", \"event_pair_overhead_ms\": " + std::to_string(stat_pair_ms_) + ", \"kernels\": [";
@@ -3575,7 +3580,7 @@ class Engine : public EngineBase {
     o += std::string(", \"q_table\": {\"on\": ") + (cds_.qtab ? "true" : "false") + ", \"reason\": \"" + qtab_reason_ + "\"}";       // the set updated on a stream of its own (-1: none), lane_start
     o += ", \"batched_searches\": {\"searches\": " + std::to_string(batch_searches_) + ", \"fallbacks\": " + std::to_string(batch_fallbacks_) + "}";
     // slice-rank / matrix-rank sets: which route their projector took since the context was finalised (ext_proj.hip)
-    long long rc[4] = {0, 0, 0, 0};
+    long long rc[4] = {project_rc_[0], project_rc_[1], project_rc_[2], project_rc_[3]};      // stand-alone calls (project)
     for (const auto& st : sets_) {
       if (!st.ext || st.ext_kind != EXT_RANK) continue;
       long long c[4];
@@ -4540,6 +4545,7 @@ class Engine : public EngineBase {
   bool sweep_plain_ = false;          // the sweep takes the plain iterations of this context: every set carries a third y / l pair
   bool search_batch_ = false;         // one rank + sweep: the searches of all sets as one chain of launches (batched_searches; SIPX_SEARCH_BATCH=0: per-set chains on the set streams)
   long long batch_searches_ = 0, batch_fallbacks_ = 0;
+  long long project_rc_[4] = {0, 0, 0, 0};   // route counters of the rank projectors that project() built and dropped
   T* fbuf_ = nullptr;                 // fast segments: world x two-pass sets x (fcap + header)
   bool yl_multi_ = true;              // SIPX_YL_MULTI=0: never take the one-sweep y/l update (A/B switch)
   bool x0_mode_ = false;              // s_0 = A x_0 recomputed from a snapshot of x (see finalize)

@@ -596,6 +596,9 @@ __global__ __launch_bounds__(BLOCK) void k_cheb_step(int k, int b, int g, int r,
     const double* Wl = W + l * b;
     const double a = cheb_floor(Wl, b, g, r);
     const double aj = Wl[j] / CHEB_KAPPA > a ? Wl[j] / CHEB_KAPPA : a;
+    // no positive Ritz value -- a slice of zeros among others: there is no interval, (2 / 0) * 0 would fill the block with NaN that
+    // k_sub_residual never looks at and the final product turns into the slice's output.  The block stays what it is.
+    if (!(aj > 0.0)) { out[e] = first ? Y0[e] : Y1[e]; continue; }
     out[e] = first ? (2.0 / aj) * Z[e] - Y0[e] : (4.0 / aj) * Z[e] - 2.0 * Y1[e] - Y0[e];
   }
 }
@@ -632,6 +635,7 @@ __global__ __launch_bounds__(256) void k_cheb_step_proj(int k, int b, int g, int
     double z = Z[base + i];
     if (m0) z -= x0[i] * c0;
     if (m1) z -= x1[i] * c1;
+    if (!(aj > 0.0)) { out[base + i] = first ? Y0[base + i] : Y1[base + i]; continue; }      // (a slice of zeros: see k_cheb_step)
     out[base + i] = first ? (2.0 / aj) * z - Y0[base + i] : (4.0 / aj) * z - 2.0 * Y1[base + i] - Y0[base + i];
   }
 }

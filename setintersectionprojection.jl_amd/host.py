@@ -325,6 +325,8 @@ class Projector:
         if am[0] not in MODES:
             raise SipxError(f"unknown application mode {am!r}")
         self.mode, self.dir = MODES[am[0]], 0
+        if am == ("slice", "z") and len(comp_grid.n) == 3 and int(comp_grid.n[2]) == 1:
+            self.mode = MODES["matrix"]      # a tensor of one plane is handled as a 2-D grid (_grid): its one z-slice is the array itself
         if self.mode:
             dirs = {"x": 0, "z": len(n) - 1} if len(n) == 2 else {"x": 0, "y": 1, "z": 2}
             if am[1] not in dirs:
