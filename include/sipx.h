@@ -67,9 +67,13 @@ enum {
                                 (projectors/project_histogram_relaxed.jl:9-27) */
   SIPX_PROJ_SUBSPACE    = 11,/* project_subspace!(x, A, orth): whole vector, fibers of a matrix (2-D) or slices of a
                                 tensor (3-D)  (projectors/project_subspace!.jl:10-125); op must be identity */
-  SIPX_PROJ_BOUNDS_DFT  = 12 /* x -> Re(F' (ub .* (F x))), F = unitary DFT: bounds in the Fourier domain with a binary lower
+  SIPX_PROJ_BOUNDS_DFT  = 12,/* x -> Re(F' (ub .* (F x))), F = unitary DFT: bounds in the Fourier domain with a binary lower
                                 bound of zeros and a mask ub TF[N] in the transform's element order
                                 (project_bounds!.jl:27-36 under get_projector.jl:8-9 with TD_OP "DFT"); op must be identity */
+  SIPX_PROJ_CARD_DFT    = 13 /* x -> Re(F' project_cardinality!(F x, k = pmax)), F = unitary DFT: keep the k Fourier coefficients
+                                of largest magnitude, stable order on the column-major index of the spectrum; conjugate pairs count
+                                as exact ties and the lower index wins; k >= N returns x bit for bit; op must be identity, mode WHOLE
+                                (src/get_projector.jl:85-89 with TD_OP "DFT", projectors/project_cardinality!.jl:3-21) */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */

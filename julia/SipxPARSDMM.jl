@@ -84,7 +84,9 @@ function projector_fields(c, TF)
         st == "l1" && return (7, 0.0, Float64(c.max), nothing, nothing, Int32(0))                 # SIPX_PROJ_L1_DFT
         st == "bounds" && vecb && return (12, 0.0, 0.0, nothing, convert(Vector{TF}, c.max), Int32(0))   # SIPX_PROJ_BOUNDS_DFT (mask)
         st in ("l2", "annulus") && return (st == "l2" ? 3 : 4, st == "annulus" ? Float64(c.min) : 0.0, Float64(c.max), nothing, nothing, Int32(0))
-        error("of the DFT-domain sets libsipx builds the l1 ball, masking bounds, the l2 ball and the annulus")
+        st == "cardinality" && c.app_mode[1] in ("matrix", "tensor") &&
+            return (13, 0.0, Float64(convert(Integer, c.max)), nothing, nothing, Int32(0))          # SIPX_PROJ_CARD_DFT
+        error("of the DFT-domain sets libsipx builds the l1 ball, cardinality (matrix / tensor mode), masking bounds, the l2 ball and the annulus")
     elseif op == "wavelet"                           # x -> W' P(W x), periodic db4 (SIPX_TRANSFORM_WAVELET = 2)
         st in ("l2", "annulus") && return (st == "l2" ? 3 : 4, st == "annulus" ? Float64(c.min) : 0.0, Float64(c.max), nothing, nothing, Int32(0))
         st == "l1" && return (2, 0.0, Float64(c.max), nothing, nothing, Int32(2))

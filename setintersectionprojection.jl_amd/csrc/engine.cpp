@@ -3833,6 +3833,13 @@ class Engine : public EngineBase {
         ext(EXT_DFT_MASK);
         s.host_ub.assign((const T*)d->ub, (const T*)d->ub + G_.N);
         break;
+      case SIPX_PROJ_CARD_DFT:
+        if (d->op != SIPX_OP_IDENTITY || mode != SIPX_MODE_WHOLE)
+          throw std::runtime_error("cardinality behind the DFT acts in its own domain: TD_OP must be the identity, mode matrix/tensor");
+        if (d->pmax < 0 || d->pmax != std::floor(d->pmax))
+          throw std::runtime_error("cardinality behind the DFT: k must be a non-negative integer");
+        ext(EXT_CARD_DFT);
+        break;
       case SIPX_PROJ_RANK: ext(EXT_RANK); break;
       case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;
       case SIPX_PROJ_HISTOGRAM:

@@ -117,6 +117,139 @@ __global__ __launch_bounds__(BLOCK) void k_unpack_real(long long N, const T* __r
   if (!ps->need) return;
   for (long long e = (long long)blockIdx.x * BLOCK + threadIdx.x; e < N; e += (long long)gridDim.x * BLOCK) v[e] = w[e] * scale;
 }
+// ------------------------------------------------------------------------------------------------
+// Cardinality behind the DFT (EXT_CARD_DFT): keep the k Fourier coefficients of largest magnitude, x -> Re(F' (K .* F x))
+//     reference: get_projector.jl:85-89 with A = joDFT, project_cardinality! on Complex{TF} (project_cardinality!.jl:3-21).
+// The order is the stable one by descending |Z| on the natural column-major index e = k1 + n1 (k2 + n2 k3) of the full spectrum.
+// For a real model |Z[e]| = |Z[e*]|, e* = the index with every coordinate negated modulo n: the magnitudes are TAKEN as exactly
+// symmetric (max of the two where both are computed) and the tie goes to the lower index, where the reference leaves it to the
+// rounding noise of its FFT.  A pair the cut separates keeps its lower-index member only; Re(F' .) of that is the inverse
+// transform of the pair with weight 1/2 on both members -- in general Re(F'(K .* Z)) = F'(w .* Z), w[e] = (keep[e] + keep[e*]) / 2,
+// which is Hermitian and is what the real transform is handed.  IT: unsigned below 2^31 entries (32-bit divisions), else long long.
+template <typename IT>
+struct DftIdx {
+  IT n1, n2, n3, nh1;              // nh1 = n1/2 + 1: stored planes of the real transform
+};
+template <typename T>
+__device__ __forceinline__ T cplx_abs(T re, T im);
+template <>
+__device__ __forceinline__ float cplx_abs<float>(float re, float im) {      // (the squares of floats are exact in double, their sum cannot overflow)
+  const double r = (double)re, i = (double)im;
+  return (float)sqrt(r * r + i * i);
+}
+template <>
+__device__ __forceinline__ double cplx_abs<double>(double re, double im) { return hypot(re, im); }
+// 16 bytes of spectrum: two Float32 bins or one Float64 bin
+template <typename T> struct alignas(16) BinVec { Cplx<T> b[16 / sizeof(Cplx<T>)]; };
+template <typename T>
+__device__ __forceinline__ bool card_keeps(T m, long long e, T tau, long long cut) { return m > tau || (m == tau && e <= cut); }
+// nothing is dropped (k >= N or k >= the non-zero coefficients, k_card_decide): v stays as it is, bit for bit
+template <typename T>
+__device__ __forceinline__ bool card_identity(const ProjScalars<T>* ps) { return !ps->need && ps->tau == T(0); }
+
+// R2C route, pass 1: the N magnitudes in natural order from the Nh stored bins.  A stored bin (k1, row) writes its own entry and,
+// where its conjugate is not stored (1 <= k1 <= n1 - nh1), the conjugate's; in the planes k1 = 0 and k1 = n1/2 (n1 even) both
+// members of a pair are stored and each takes the larger of the two magnitudes.  Every entry of mag is written exactly once.
+template <typename T, typename IT>
+__global__ __launch_bounds__(BLOCK) void k_card_dft_mag_half(long long Nh, DftIdx<IT> d, const Cplx<T>* __restrict__ z, T* __restrict__ mag) {
+  constexpr int V = 16 / (int)sizeof(Cplx<T>);
+  const IT ndup = d.n1 - d.nh1;
+  const long long nvec = (Nh + V - 1) / V;
+  for (long long p = (long long)blockIdx.x * BLOCK + threadIdx.x; p < nvec; p += (long long)gridDim.x * BLOCK) {
+    const long long h0 = p * V;
+    BinVec<T> bv;
+    if (h0 + V <= Nh) bv = *reinterpret_cast<const BinVec<T>*>(z + h0);
+    else bv.b[0] = z[h0];                                  // (odd Nh in Float32: the last bin alone)
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+      if (h0 + q >= Nh) break;
+      const IT h = (IT)(h0 + q);
+      const IT row = h / d.nh1, k1 = h - row * d.nh1;
+      const IT k3 = row / d.n2, k2 = row - k3 * d.n2;
+      const IT crow = (k2 ? d.n2 - k2 : 0) + d.n2 * (k3 ? d.n3 - k3 : 0);
+      T m = cplx_abs<T>(bv.b[q].re, bv.b[q].im);
+      const long long e = (long long)k1 + (long long)d.n1 * (long long)row;
+      if (k1 >= 1 && k1 <= ndup) {
+        mag[(long long)(d.n1 - k1) + (long long)d.n1 * (long long)crow] = m;
+      } else {
+        const Cplx<T> c = z[(long long)k1 + (long long)d.nh1 * (long long)crow];
+        const T mp = cplx_abs<T>(c.re, c.im);
+        m = mp > m ? mp : m;
+      }
+      mag[e] = m;
+    }
+  }
+}
+// R2C route, pass 2: every stored bin times w = (keep[e] + keep[e*]) / 2 in {0, 1/2, 1}; the partner's decision from the partner's
+// index (mag[e*] == mag[e] by construction).  Partners inside the stored planes get the same weight, self-conjugate bins keep[e].
+template <typename T, typename IT>
+__global__ __launch_bounds__(BLOCK) void k_card_dft_weight_half(long long Nh, DftIdx<IT> d, Cplx<T>* __restrict__ z, const T* __restrict__ mag,
+                                                                const ProjScalars<T>* __restrict__ ps) {
+  if (card_identity(ps)) return;
+  constexpr int V = 16 / (int)sizeof(Cplx<T>);
+  const T tau = ps->tau;
+  const long long cut = ps->quota;
+  const long long nvec = (Nh + V - 1) / V;
+  for (long long p = (long long)blockIdx.x * BLOCK + threadIdx.x; p < nvec; p += (long long)gridDim.x * BLOCK) {
+    const long long h0 = p * V;
+    const bool full = h0 + V <= Nh;
+    BinVec<T> bv;
+    if (full) bv = *reinterpret_cast<const BinVec<T>*>(z + h0);
+    else bv.b[0] = z[h0];
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+      if (h0 + q >= Nh) break;
+      const IT h = (IT)(h0 + q);
+      const IT row = h / d.nh1, k1 = h - row * d.nh1;
+      const IT k3 = row / d.n2, k2 = row - k3 * d.n2;
+      const IT crow = (k2 ? d.n2 - k2 : 0) + d.n2 * (k3 ? d.n3 - k3 : 0);
+      const long long e = (long long)k1 + (long long)d.n1 * (long long)row;
+      const long long ep = (long long)(k1 ? d.n1 - k1 : 0) + (long long)d.n1 * (long long)crow;
+      const T m = mag[e];
+      const T w = T(0.5) * ((card_keeps(m, e, tau, cut) ? T(1) : T(0)) + (card_keeps(m, ep, tau, cut) ? T(1) : T(0)));
+      bv.b[q].re = bv.b[q].re * w;
+      bv.b[q].im = bv.b[q].im * w;
+    }
+    if (full) *reinterpret_cast<BinVec<T>*>(z + h0) = bv;
+    else z[h0] = bv.b[0];
+  }
+}
+// Complex route (SIPX_DFT_REAL=0, n1 < 4), pass 1: mag[e] = max(|Z[e]|, |Z[e*]|) -- both members of a pair compute the same value
+template <typename T, typename IT>
+__global__ __launch_bounds__(BLOCK) void k_card_dft_mag_full(long long N, DftIdx<IT> d, const Cplx<T>* __restrict__ z, T* __restrict__ mag) {
+  for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < N; i += (long long)gridDim.x * BLOCK) {
+    const IT e = (IT)i;
+    const IT row = e / d.n1, k1 = e - row * d.n1;
+    const IT k3 = row / d.n2, k2 = row - k3 * d.n2;
+    const IT crow = (k2 ? d.n2 - k2 : 0) + d.n2 * (k3 ? d.n3 - k3 : 0);
+    const long long ep = (long long)(k1 ? d.n1 - k1 : 0) + (long long)d.n1 * (long long)crow;
+    const Cplx<T> a = z[i], b = z[ep];
+    const T ma = cplx_abs<T>(a.re, a.im), mb = cplx_abs<T>(b.re, b.im);
+    mag[i] = mb > ma ? mb : ma;
+  }
+}
+// Complex route, pass 2: Z[e] <- 0 unless kept, the (tau, index cut) rule on the N bins themselves
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_card_dft_keep_full(long long N, Cplx<T>* __restrict__ z, const T* __restrict__ mag,
+                                                              const ProjScalars<T>* __restrict__ ps) {
+  if (card_identity(ps)) return;
+  const T tau = ps->tau;
+  const long long cut = ps->quota;
+  for (long long e = (long long)blockIdx.x * BLOCK + threadIdx.x; e < N; e += (long long)gridDim.x * BLOCK) {
+    if (card_keeps(mag[e], e, tau, cut)) continue;
+    Cplx<T> c;
+    c.re = T(0);
+    c.im = T(0);
+    z[e] = c;
+  }
+}
+// v <- w * scale (w: N reals with stride `ws` -- the output of C2R, or the real parts of the complex inverse) unless nothing was dropped
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_card_dft_unpack(long long N, const T* __restrict__ w, int ws, T* __restrict__ v, T scale,
+                                                           const ProjScalars<T>* __restrict__ ps) {
+  if (card_identity(ps)) return;
+  for (long long e = (long long)blockIdx.x * BLOCK + threadIdx.x; e < N; e += (long long)gridDim.x * BLOCK) v[e] = w[e * ws] * scale;
+}
 // U[:, j] *= S[j] for the first r columns of every slice
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_scale_cols(int m, int r, int ldu, long long strideU, long long strideS,
@@ -1190,8 +1323,10 @@ ExtProj<T>::ExtProj(const ExtSpec& spec, hipStream_t stream) {
     I.z = I.template alloc<Cplx<T>>(N);
     I.mag = I.template alloc<T>(N);                      // the mask
     SIPX_HIP(hipMemcpy(I.mag, spec.ub, sizeof(T) * N, hipMemcpyHostToDevice));
-  } else if (kind == EXT_L1_DFT) {
-    if (!(spec.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+  } else if (kind == EXT_L1_DFT || kind == EXT_CARD_DFT) {
+    if (kind == EXT_L1_DFT && !(spec.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+    if (kind == EXT_CARD_DFT && (spec.pmax < 0 || spec.pmax != std::floor(spec.pmax)))
+      throw std::runtime_error("cardinality behind the DFT: k must be a non-negative integer");
     I.real_fft = env_knobs().dft_real && G.n[0] >= 4;      // SIPX_DFT_REAL=0: the complex transform of the packed model (A/B switch, tests)
     if (I.real_fft) {
       const hipfftType tf = sizeof(T) == 4 ? HIPFFT_R2C : HIPFFT_D2Z, tb = sizeof(T) == 4 ? HIPFFT_C2R : HIPFFT_Z2D;
@@ -1219,8 +1354,9 @@ ExtProj<T>::ExtProj(const ExtSpec& spec, hipStream_t stream) {
     I.mag = I.template alloc<T>(N);
     I.ps = I.template alloc<ProjScalars<T>>(1);
     I.psf = I.template alloc<ProjScalars<T>>(1);
-    K<T>::ps_init(stream, I.ps, nullptr);
-    K<T>::ps_init(stream, I.psf, nullptr);
+    if (kind == EXT_CARD_DFT) I.cidx = I.template alloc<long long>(N);     // indices of the gathered magnitudes (the tie cut)
+    K<T>::ps_init(stream, I.ps, I.cidx);
+    K<T>::ps_init(stream, I.psf, I.cidx);
     I.radius_raw = (T)(spec.pmax * sqrt((double)N));       // ||F_unitary v||_1 <= b  <=>  ||FFT v||_1 <= b sqrt(N)
   } else if (kind == EXT_RANK || kind == EXT_NUCLEAR) {
     ExtSpec sp = spec;
@@ -1980,6 +2116,41 @@ static bool rank_cheb_route(ExtImpl<T>& I, int w, int k, bool cold = false) {
   return ok;
 }
 
+// Cardinality behind the DFT: transform, the N symmetric magnitudes in natural order, the engine's own cardinality search on them
+// ((tau, index cut) in ps), the weights on the stored bins, inverse transform.  The scale of the transform does not matter to the
+// order, so the raw spectrum is searched; 1/N on the way back.
+template <typename T, typename IT>
+static void card_dft_project(ExtImpl<T>& I, T* v, bool feas, double* partials, T* maxpart, T* compact) {
+  const Grid& G = I.sp.G;
+  const long long N = G.N;
+  hipStream_t s = I.stream;
+  ProjScalars<T>* ps = feas ? I.psf : I.ps;
+  DftIdx<IT> d;
+  d.n1 = (IT)G.n[0]; d.n2 = (IT)G.n[1]; d.n3 = (IT)G.n[2]; d.nh1 = (IT)(G.n[0] / 2 + 1);
+  const T k = (T)I.sp.pmax, scale = (T)(1.0 / (double)N);
+  if (I.real_fft) {
+    if (sizeof(T) == 4) fft_check(hipfftExecR2C(I.plan_r2c, (hipfftReal*)v, (hipfftComplex*)I.z), "forward (real)");
+    else fft_check(hipfftExecD2Z(I.plan_r2c, (hipfftDoubleReal*)v, (hipfftDoubleComplex*)I.z), "forward (real)");
+    hipLaunchKernelGGL((k_card_dft_mag_half<T, IT>), dim3(NB), dim3(BLOCK), 0, s, I.Nh, d, I.z, I.mag);
+    K<T>::proj_scalars_arr(s, N, I.mag, PX_CARD, T(0), k, ps, partials, maxpart, compact, N);
+    hipLaunchKernelGGL((k_card_dft_weight_half<T, IT>), dim3(NB), dim3(BLOCK), 0, s, I.Nh, d, I.z, I.mag, ps);
+    // (as for the l1 ball: the inverse real transform writes into mag, free by now, and v stays untouched when nothing is dropped)
+    if (sizeof(T) == 4) fft_check(hipfftExecC2R(I.plan_c2r, (hipfftComplex*)I.z, (hipfftReal*)I.mag), "inverse (real)");
+    else fft_check(hipfftExecZ2D(I.plan_c2r, (hipfftDoubleComplex*)I.z, (hipfftDoubleReal*)I.mag), "inverse (real)");
+    hipLaunchKernelGGL((k_card_dft_unpack<T>), dim3(NB), dim3(BLOCK), 0, s, N, I.mag, 1, v, scale, ps);
+  } else {
+    hipLaunchKernelGGL((k_pack<T>), dim3(NB), dim3(BLOCK), 0, s, N, v, I.z);
+    if (sizeof(T) == 4) fft_check(hipfftExecC2C(I.plan, (hipfftComplex*)I.z, (hipfftComplex*)I.z, HIPFFT_FORWARD), "forward");
+    else fft_check(hipfftExecZ2Z(I.plan, (hipfftDoubleComplex*)I.z, (hipfftDoubleComplex*)I.z, HIPFFT_FORWARD), "forward");
+    hipLaunchKernelGGL((k_card_dft_mag_full<T, IT>), dim3(NB), dim3(BLOCK), 0, s, N, d, I.z, I.mag);
+    K<T>::proj_scalars_arr(s, N, I.mag, PX_CARD, T(0), k, ps, partials, maxpart, compact, N);
+    hipLaunchKernelGGL((k_card_dft_keep_full<T>), dim3(NB), dim3(BLOCK), 0, s, N, I.z, I.mag, ps);
+    if (sizeof(T) == 4) fft_check(hipfftExecC2C(I.plan, (hipfftComplex*)I.z, (hipfftComplex*)I.z, HIPFFT_BACKWARD), "inverse");
+    else fft_check(hipfftExecZ2Z(I.plan, (hipfftDoubleComplex*)I.z, (hipfftDoubleComplex*)I.z, HIPFFT_BACKWARD), "inverse");
+    hipLaunchKernelGGL((k_card_dft_unpack<T>), dim3(NB), dim3(BLOCK), 0, s, N, (const T*)I.z, 2, v, scale, ps);
+  }
+}
+
 // v <- P(v) in place.  `feas` selects the independent warm-start state used for the feasibility estimate.
 template <typename T>
 void ExtProj<T>::project(T* v, bool feas, double* partials, T* maxpart, T* compact) {
@@ -2018,6 +2189,9 @@ void ExtProj<T>::project(T* v, bool feas, double* partials, T* maxpart, T* compa
     if (sizeof(T) == 4) fft_check(hipfftExecC2C(I.plan, (hipfftComplex*)I.z, (hipfftComplex*)I.z, HIPFFT_BACKWARD), "inverse");
     else fft_check(hipfftExecZ2Z(I.plan, (hipfftDoubleComplex*)I.z, (hipfftDoubleComplex*)I.z, HIPFFT_BACKWARD), "inverse");
     hipLaunchKernelGGL((k_unpack<T>), dim3(NB), dim3(BLOCK), 0, s, N, I.z, v, (T)(1.0 / (double)N), ps);
+  } else if (kind == EXT_CARD_DFT) {
+    if (N < (1ll << 31)) card_dft_project<T, unsigned>(I, v, feas, partials, maxpart, compact);
+    else card_dft_project<T, long long>(I, v, feas, partials, maxpart, compact);
   } else if (kind == EXT_RANK || kind == EXT_NUCLEAR) {
     I.check_status();
     // Batched Jacobi SVD in float64 whatever TF is: rocSOLVER's gesvdj works on A'A (condition number squared), so

@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = [
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
-        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12}
+        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13}
 MODES = {"matrix": 0, "tensor": 0, "fiber": 1, "slice": 2}
 TRANSFORMS = {"DCT": 1, "wavelet": 2}
 SPECIAL_OPERATORS = ("DFT", "DCT", "wavelet", "curvelet")     # src/setup_constraints.jl:54
@@ -388,9 +388,20 @@ class Projector:
                 # P applied to x itself, without the FFT round trip of get_projector.jl:39,47
                 self.kind, self.pmax = st, float(constraint.max)
                 self.pmin = float(constraint.min) if st == "annulus" else 0.0
+            elif constraint.TD_OP == "DFT" and st == "cardinality":
+                # x -> Re(F' project_cardinality!(F x, k)) (get_projector.jl:85-89): the k Fourier coefficients of largest
+                # magnitude, conjugate pairs as exact ties (sipx.h, SIPX_PROJ_CARD_DFT)
+                if self.mode:
+                    raise SipxError("cardinality behind the DFT applies to the whole array (matrix / tensor mode)")
+                k = float(constraint.max)
+                if k != int(k):                          # convert(Integer, constraint.max), get_projector.jl:88
+                    raise SipxError(f"InexactError: Int64({constraint.max!r})")
+                if k < 0:                                # sort_ind[k+1:end] (project_cardinality!.jl:19)
+                    raise SipxError(f"cardinality behind the DFT: k = {int(k)} is negative (BoundsError: sort_ind[{int(k) + 1}:end])")
+                self.kind, self.pmax = "card_dft", k
             else:
-                raise SipxError("of the orthogonal-transform sets only the l1 ball, masking bounds, the l2 ball and the annulus "
-                                "in the DFT domain are built")
+                raise SipxError("of the orthogonal-transform sets only the l1 ball, cardinality (matrix / tensor mode), masking "
+                                "bounds, the l2 ball and the annulus in the DFT domain are built")
         elif st == "rank":
             self.kind, self.pmax = "rank", float(int(constraint.max))
         elif st == "nuclear":
@@ -425,8 +436,8 @@ class Projector:
     def check_rows(self, op: "TDOperator"):
         """Host-side shape checks of the vectors the descriptor points at (the engine reads them unchecked)."""
         n = list(op.n)
-        if op.kind == "custom" and (self.mode or self.transform or self.kind in ("l1_dft", "bounds_dft", "rank", "nuclear",
-                                                                                     "histogram", "subspace")):
+        if op.kind == "custom" and (self.mode or self.transform or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank",
+                                                                                     "nuclear", "histogram", "subspace")):
             raise SipxError("custom sparse operators take the whole-array projectors only")
         if op.kind in ("D_x", "D_y", "D_z"):
             n[{"D_x": 0, "D_y": 1, "D_z": len(n) - 1}[op.kind]] -= 1
@@ -458,7 +469,8 @@ class Projector:
     def __call__(self, v):
         if v.dtype.type != self.TF or not v.flags.c_contiguous:
             raise SipxError("projector input must be a contiguous vector of the working precision")
-        grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "rank", "nuclear", "histogram", "subspace")
+        grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
+                                                                              "subspace")
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
         try:
             if grid_kind:
