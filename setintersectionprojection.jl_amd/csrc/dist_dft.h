@@ -6,7 +6,7 @@
 //   from z-slabs to slabs of k1 rows  ->  1-D transforms along z  ->  the l1 threshold search over the magnitudes of ALL ranks
 //   (the slab collectives of every other search: all-reduced probe sums, all-gathered bracket)  ->  shrinkage  ->  the way back.
 // The model is real: the half spectrum k0 = 0 .. n0/2 is transformed and the magnitudes of the coefficients whose conjugates are
-// not stored count twice, as in the one-GPU projector (ext_proj.hip, k_cabs_half).
+// not stored count twice, as in the one-GPU projector (ext_transform.hip, k_cabs_half).
 #pragma once
 #include <hip/hip_runtime.h>
 

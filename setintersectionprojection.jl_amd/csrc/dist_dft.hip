@@ -50,7 +50,7 @@ __global__ __launch_bounds__(BLOCK) void k_dft_unpack(long long pz, long long n1
 }
 // Magnitudes of the coefficients this rank holds after the transposition -- R[z][j][k0], z < n2, j < m1 of the c1 rows of a block --
 // strung together without the unused rows: mag[(z m1 + j) nh0 + k0]; those of k0 = 1 .. ndup, whose conjugates are not stored, a
-// second time behind them (ext_proj.hip, k_cabs_half): the search sees this rank's share of all N coefficients.
+// second time behind them (ext_transform.hip, k_cabs_half): the search sees this rank's share of all N coefficients.
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_dft_abs(long long n2, long long m1, long long c1, long long nh0, long long ndup,
                                                    const Cx<T>* __restrict__ R, T* __restrict__ mag) {
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(BLOCK) void k_dft_abs(long long n2, long long m1, l
     if (k0 >= 1 && k0 <= ndup) mag[Nh + row * ndup + (k0 - 1)] = m;
   }
 }
-// z <- sign(z) max(|z| - theta, 0)   (project_l1_Duchi!.jl:49 on complex input; ext_proj.hip, k_csoft)
+// z <- sign(z) max(|z| - theta, 0)   (project_l1_Duchi!.jl:49 on complex input; ext_transform.hip, k_csoft)
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_dft_soft(long long n2, long long m1, long long c1, long long nh0, Cx<T>* __restrict__ R,
                                                     const T* __restrict__ mag, const ProjScalars<T>* __restrict__ ps) {
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(BLOCK) void k_dft_soft(long long n2, long long m1, 
     c.im = c.im * f;
   }
 }
-// v <- w / N unless v already lies inside the ball (F'F = I: the round trip would only add rounding noise; ext_proj.hip, k_unpack)
+// v <- w / N unless v already lies inside the ball (F'F = I: the round trip would only add rounding noise; ext_transform.hip, k_unpack)
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_dft_store(long long n, const T* __restrict__ w, T* __restrict__ v, T scale,
                                                      const ProjScalars<T>* __restrict__ ps) {

@@ -1,4 +1,4 @@
-"""Cardinality behind the DFT on the device (sipx.h SIPX_PROJ_CARD_DFT, csrc/ext_proj.hip EXT_CARD_DFT) against the numpy
+"""Cardinality behind the DFT on the device (sipx.h SIPX_PROJ_CARD_DFT, csrc/ext_transform.hip EXT_CARD_DFT) against the numpy
 restatement of its contract (tests/card_dft_ref.py): the projector alone on inputs whose kept set is unambiguous, its properties
 on generic inputs, the learned count DFT_card_095 fed back into it, and whole solves against the oracle with the restatement
 substituted into P_sub (the oracle's own ("cardinality", "DFT") falls through to plain cardinality)."""

@@ -1597,7 +1597,7 @@ def test_named_D_xz_operator(sipx, TF):
 @pytest.mark.parametrize("strict", ["1", "0"])
 def test_rank_projection_subspace_route(sipx, capfd, monkeypatch, strict):
     """Inside a solve the slice-rank projector (Float32, Gram route) restarts a block subspace iteration from the previous
-    call's Ritz vectors and accepts it when the top-r residuals are below its level (ext_proj.hip): strict = 1, the level of
+    call's Ritz vectors and accepts it when the top-r residuals are below its level (ext_rank.hip): strict = 1, the level of
     rounds 3-4 (1e-12 theta_max on the Gram matrix: the two routes then agree to 2e-6); strict = 0, the default since round 5 -- the
     backward error of the reference's own Float32 svd on the slice (project_rank!.jl:26-45), where two correct routes differ like
     two Float32 SVDs do (1e-5 over 16 iterations).  Either way the iterates must agree with the full decomposition of every call
@@ -1644,7 +1644,7 @@ def test_rank_projection_subspace_route(sipx, capfd, monkeypatch, strict):
 @pytest.mark.parametrize("r,strong", [(8, 0), (7, 0), (8, 5)])
 def test_rank_projection_filtered_route_on_flat_spectra(sipx, capfd, monkeypatch, r, strong, strict):
     """Slices that are a constant plus white noise (the synthetic model of BASELINE config 4) have no gap behind any block of
-    singular values: plain subspace iteration never gets there, the Chebyshev-filtered one (ext_proj.hip, rank_cheb_route)
+    singular values: plain subspace iteration never gets there, the Chebyshev-filtered one (ext_rank.hip, rank_cheb_route)
     does, and is accepted on the inertia certificate (one batched Cholesky factorisation of mu I - G + X_r Theta_r X_r').
     r = 7: an odd block (the Jacobi ordering pads it); strong = 5: five more directions far above the noise, of decaying
     weight, so that the projections of the filter take their GEMM form (more than two vectors far above a column).

@@ -1,4 +1,4 @@
-"""The rank projector's subspace routes (csrc/ext_proj.hip: cold ramp, warm-started filtered block iteration, compaction,
+"""The rank projector's subspace routes (csrc/ext_rank.hip: cold ramp, warm-started filtered block iteration, compaction,
 inertia certificate, the two warm states) held call by call to the optimal rank-r truncation.
 
 The criterion is tests/rank_exact.py: the distance of an output to the best rank-r matrix (`excess`) and to rank r

@@ -264,7 +264,7 @@ def test_slab_ranks_hold_their_planes_only(sipx, tmp_path, world, kinds, n):
 
 
 def test_rank_route_packs_the_slices_that_still_need_a_filter(sipx, capfd, monkeypatch):
-    """Filtered subspace route of the slice-rank projector (ext_proj.hip, rank_cheb_route): once three quarters of the batch have
+    """Filtered subspace route of the slice-rank projector (ext_rank.hip, rank_cheb_route): once three quarters of the batch have
     converged, the remaining matrices are packed and the later filters run on those alone.  Fourteen slices with a clear gap behind
     the block and two that are a constant plus white noise: the packed route must be taken, accept on the inertia certificate, and
     end where the whole-batch route (SIPX_RANK_PACK=0) and the full decomposition of every call (SIPX_RANK_CHEB=0) end.
@@ -311,7 +311,7 @@ def test_rank_route_packs_the_slices_that_still_need_a_filter(sipx, capfd, monke
 
 def test_certificate_factorisation_agrees_with_the_library(sipx, capfd, monkeypatch):
     """The inertia certificate of the filtered rank route factors mu I - G + X_r Theta_r X_r' with a blocked Cholesky of its own
-    (ext_proj.hip, rank_cert_factor: k_chol_diag + two batched GEMMs per 64 columns).  SIPX_RANK_CERT_CHECK runs it and rocSOLVER's
+    (ext_rank.hip, rank_cert_factor: k_chol_diag + two batched GEMMs per 64 columns).  SIPX_RANK_CERT_CHECK runs it and rocSOLVER's
     potrf side by side on the certificate's matrices (positive definite when the certificate holds) and on matrices shifted below an
     eigenvalue (never definite): same verdict for every matrix, at 128 x 128 (two blocks) and 160 x 160 (a ragged last block)."""
     TF = np.float32
@@ -409,7 +409,7 @@ def test_bench_headline_survives_a_leg_that_fails_on_one_rank():
 def test_l1_behind_the_dft_through_the_real_transform(sipx, monkeypatch, TF, n):
     """l1 ball on the Fourier coefficients (`A'*project_l1_Duchi!(A*x)` with joDFT, src/get_projector.jl:25-33): the model is real, so
     the engine transforms it with hipFFT's R2C / C2R pair -- half the spectrum, no packing -- and lets the search see all N magnitudes
-    by writing those of the planes whose conjugates are not stored a second time (ext_proj.hip, k_cabs_half).  Against the complex
+    by writing those of the planes whose conjugates are not stored a second time (ext_transform.hip, k_cabs_half).  Against the complex
     transform of the packed model (SIPX_DFT_REAL=0) and the oracle: even and odd leading dimensions, 2-D and 3-D, both precisions;
     a model inside the ball comes back bit for bit."""
     h = (25.0, 25.0, 25.0)[:len(n)]

@@ -160,7 +160,7 @@ def _flat_slices(n, TF, seed):
 def test_slice_rank_projection_is_in_the_class_of_the_float32_svd(sipx, n, r, capfd, monkeypatch):
     """The reference projects a Float32 slice through svd() IN Float32 (src/projectors/project_rank!.jl:26-45: LAPACK's sgesdd).
     Round 5 accepts a Ritz pair of the slice-rank projector at the backward error such an SVD leaves on the slice itself,
-    ||E||_2 <= 2^-23 ||X||_2 = eps(Float32) ||X||_2 (ext_proj.hip, k_sub_residual), instead of 1e-12 theta_max on the Gram matrix in Float64.  Leaf test of
+    ||E||_2 <= 2^-23 ||X||_2 = eps(Float32) ||X||_2 (ext_rank.hip, k_sub_residual), instead of 1e-12 theta_max on the Gram matrix in Float64.  Leaf test of
     that class against the oracle's Float32 LAPACK SVD, on slices without a spectral gap, the projector starting COLD (no previous
     call: the ramp of short filters, no full decomposition):
       * the engine's projection is as close to the exact (Float64 SVD) projection of the same Float32 slices as the reference's

@@ -1,6 +1,6 @@
 """What a Float32 LAPACK SVD -- the arithmetic of the reference's rank projector, src/projectors/project_rank!.jl:26-45: svd() in TF --
 leaves on a slice of BASELINE config 4's model, in the measure the engine's slice-rank projector accepts its Ritz pairs by
-(csrc/ext_proj.hip, k_sub_residual): the backward error of a computed triplet on the slice itself.  CPU only (numpy's svd on a
+(csrc/ext_rank.hip, k_sub_residual): the backward error of a computed triplet on the slice itself.  CPU only (numpy's svd on a
 Float32 array is LAPACK's sgesdd, the routine behind Julia's svd)."""
 import numpy as np
 
