@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "device_memory.h"
 #include "engine.h"
 
 namespace sipx {
@@ -110,20 +111,10 @@ struct DistDftImpl {
   long long sc_len = 0, sg_len = 0;
   ProjScalars<T>*ps = nullptr, *psf = nullptr;
   T radius_raw = 0;
-  long long bytes = 0;
+  DeviceMemory mem;
+  // (zero-filled on the projector's own stream: see DeviceMemory::alloc_zeroed_on)
   template <typename U>
-  U* alloc(long long count) {
-    U* p = nullptr;
-    if (count <= 0) count = 1;
-    SIPX_HIP(hipMalloc((void**)&p, (size_t)count * sizeof(U)));
-    // (on the projector's own stream: a fill on the null stream is not ordered against a non-blocking stream -- the initialisation
-    //  kernel of the search state that follows would race with it, and a rank whose state came out all zero takes other decisions
-    //  than the ranks it shares every collective with)
-    SIPX_HIP(hipMemsetAsync(p, 0, (size_t)count * sizeof(U), stream));
-    bytes += count * (long long)sizeof(U);
-    if (long long* t = alloc_tally()) *t += count * (long long)sizeof(U);
-    return p;
-  }
+  U* alloc(long long count) { return mem.alloc_zeroed_on<U>((size_t)(count > 0 ? count : 1), stream); }
 };
 
 template <typename T>
@@ -132,10 +123,7 @@ static void dist_dft_release(DistDftImpl<T>* impl) {
   if (I.p_fwd2) (void)hipfftDestroy(I.p_fwd2);
   if (I.p_inv2) (void)hipfftDestroy(I.p_inv2);
   if (I.p_z) (void)hipfftDestroy(I.p_z);
-  for (void* p : {(void*)I.A, (void*)I.S, (void*)I.R, (void*)I.X, (void*)I.mag, (void*)I.wr, (void*)I.ps, (void*)I.psf, (void*)I.sp, (void*)I.sm,
-                  (void*)I.sc, (void*)I.sg})
-    if (p) (void)hipFree(p);
-  delete impl;
+  delete impl;      // (its device memory with it)
 }
 template <typename T>
 DistDft<T>::DistDft(const long long n[3], long long z0, long long z1, long long zchunk, int world, int rank, double radius, hipStream_t stream)
@@ -210,7 +198,7 @@ void DistDft<T>::reset() {
 }
 
 template <typename T>
-long long DistDft<T>::device_bytes() const { return impl_->bytes; }
+long long DistDft<T>::device_bytes() const { return impl_->mem.bytes(); }
 
 template <typename T>
 void DistDft<T>::project(T* v, bool feas, Comm* comm, const ChainHooks* hooks, double* partials, T* maxpart, T* compact,

@@ -3,10 +3,13 @@
 // No CPU fallback exists: every numerical step below is a kernel launch.
 #include "engine.h"
 #include "comm.h"
+#include "device_memory.h"
 #include "dist_dft.h"
 #include "ext_proj.h"
+#include "host_prefault.h"
 #include "dwt.h"
 #include "solve_rules.h"
+#include "sparse_granules.h"
 
 #include <algorithm>
 #include <array>
@@ -16,8 +19,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <map>
-#include <mutex>
 #include <thread>
 #include <exception>
 
@@ -33,18 +34,16 @@ EnvKnobs g_env_knobs;
 }
 const EnvKnobs& env_knobs() { return g_env_knobs; }
 void refresh_env_knobs() { g_env_knobs = read_env_knobs(); }
-long long*& alloc_tally() {
-  static thread_local long long* t = nullptr;
-  return t;
-}
 
 namespace {
 
-struct TallyGuard {
-  long long* prev;
-  explicit TallyGuard(long long* t) : prev(alloc_tally()) { alloc_tally() = t; }
-  ~TallyGuard() { alloc_tally() = prev; }
-};
+// every entry point that may be the first to touch the device asks here; returns the number of devices
+int hip_device_count() {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+    throw std::runtime_error("libsipx: no HIP device visible -- this engine has no CPU fallback");
+  return count;
+}
 
 // installs a context's observer for the duration of one entry point (the launchers consult it through launch_observer())
 struct ObserverGuard {
@@ -54,201 +53,6 @@ struct ObserverGuard {
 };
 
 constexpr int SLOTS = SET_SLOTS;      // reduction slots per set: 0..12 k_yl, 13 ||A'dy||^2, 14/15 two-pass feasibility
-
-// what the tally counted for an allocation, so that freeing it while a tally is active takes the bytes back (the temporaries of
-// sipx_finalize -- upload_rows' staging, the whole-size buffer of upload_rows_ranged -- used to stay in device_bytes_per_rank)
-inline std::map<void*, long long>& tally_sizes() {
-  static std::map<void*, long long> m;
-  return m;
-}
-inline std::mutex& tally_mutex() {
-  static std::mutex m;
-  return m;
-}
-inline void tally_add(void* p, long long bytes) {
-  if (long long* t = alloc_tally()) {
-    *t += bytes;
-    std::lock_guard<std::mutex> lk(tally_mutex());
-    tally_sizes()[p] += bytes;
-  }
-}
-inline void tally_release(void* p) {
-  long long* t = alloc_tally();
-  std::lock_guard<std::mutex> lk(tally_mutex());
-  auto it = tally_sizes().find(p);
-  if (it == tally_sizes().end()) return;
-  if (t) *t -= it->second;
-  tally_sizes().erase(it);
-}
-// bytes of every plain allocation (sipx_reset zeroes a context's arrays without knowing each one's length)
-inline std::map<void*, size_t>& alloc_sizes() {
-  static std::map<void*, size_t> m;
-  return m;
-}
-template <typename T>
-T* dalloc(size_t n, bool zero = true) {
-  T* p = nullptr;
-  if (n == 0) return p;
-  SIPX_HIP(hipMalloc(&p, n * sizeof(T)));
-  tally_add(p, (long long)(n * sizeof(T)));
-  {
-    std::lock_guard<std::mutex> lk(tally_mutex());
-    alloc_sizes()[p] = n * sizeof(T);
-  }
-  if (zero) {
-    // hipMemset is queued on the NULL stream; the engine stream is non-blocking, so wait here or the
-    // zero-fill may land after kernels of the engine stream have already written the buffer.
-    SIPX_HIP(hipMemset(p, 0, n * sizeof(T)));
-    SIPX_HIP(hipStreamSynchronize(nullptr));
-  }
-  return p;
-}
-// SPARSE arrays (round 4, slab-decomposed contexts): the array keeps its GLOBAL index space -- the whole range is reserved in the
-// virtual address space, so every kernel indexes it exactly as before -- but only the element ranges a rank touches (its planes,
-// the halo planes around them) are backed by memory (hipMemAddressReserve / hipMemCreate / hipMemMap, 2 MiB granules).  A rank of
-// eight then holds an eighth of every N-vector (plus three planes) instead of all of it: the decomposition grows the problem that
-// fits, not only its speed.  An access outside the mapped ranges faults instead of reading stale data.
-struct SparseBlock {
-  size_t total = 0;
-  std::vector<std::pair<size_t, size_t>> maps;                   // (offset, length) in bytes
-  std::vector<hipMemGenericAllocationHandle_t> handles;
-};
-inline std::map<void*, SparseBlock>& sparse_registry() {
-  static std::map<void*, SparseBlock> reg;
-  return reg;
-}
-inline std::mutex& sparse_mutex() {
-  static std::mutex m;
-  return m;
-}
-constexpr size_t SPARSE_GRAN = 2ull << 20;
-// ranges: [first, last) in BYTES of the array's address space; returns the base of the reservation (zero-filled where mapped)
-inline void* sparse_alloc_bytes(size_t total_bytes, std::vector<std::pair<size_t, size_t>> ranges, int device) {
-  const size_t total = (total_bytes + SPARSE_GRAN - 1) / SPARSE_GRAN * SPARSE_GRAN;
-  for (auto& r : ranges) {
-    r.first = r.first / SPARSE_GRAN * SPARSE_GRAN;
-    r.second = std::min(total, (r.second + SPARSE_GRAN - 1) / SPARSE_GRAN * SPARSE_GRAN);
-  }
-  std::sort(ranges.begin(), ranges.end());
-  std::vector<std::pair<size_t, size_t>> merged;
-  for (const auto& r : ranges) {
-    if (r.second <= r.first) continue;
-    if (!merged.empty() && r.first <= merged.back().second) merged.back().second = std::max(merged.back().second, r.second);
-    else merged.push_back(r);
-  }
-  void* base = nullptr;
-  SIPX_HIP(hipMemAddressReserve(&base, total, SPARSE_GRAN, nullptr, 0));
-  SparseBlock blk;
-  blk.total = total;
-  hipMemAllocationProp prop = {};
-  prop.type = hipMemAllocationTypePinned;
-  prop.location.type = hipMemLocationTypeDevice;
-  prop.location.id = device;
-  hipMemAccessDesc acc = {};
-  acc.location.type = hipMemLocationTypeDevice;
-  acc.location.id = device;
-  acc.flags = hipMemAccessFlagsProtReadWrite;
-  // Every mapping of a reservation has the SAME size, one granule: hipMemSetAccess of this runtime (ROCm 7.2) answers "invalid
-  // argument" for a mapping whose size differs from the others inside one reservation (4 + 4 + 2 MiB fails at the third,
-  // 2 + 4 at the second; uniform sizes are fine -- probed with scratch/vmm_test3).  2 MiB is the native large page.
-  for (const auto& r : merged) {
-    for (size_t off = r.first; off < r.second; off += SPARSE_GRAN) {
-      const size_t len = SPARSE_GRAN;
-      auto chk = [&](hipError_t e, const char* what) {
-        if (e == hipSuccess) return;
-        char msg[256];
-        std::snprintf(msg, sizeof msg, "sparse array: %s failed (%s): reservation %zu bytes at %p, granule at %zu of range [%zu, %zu)", what,
-                      hipGetErrorString(e), total, base, off, r.first, r.second);
-        throw std::runtime_error(msg);
-      };
-      hipMemGenericAllocationHandle_t h;
-      chk(hipMemCreate(&h, len, &prop, 0), "hipMemCreate");
-      chk(hipMemMap((char*)base + off, len, 0, h, 0), "hipMemMap");
-      chk(hipMemSetAccess((char*)base + off, len, &acc, 1), "hipMemSetAccess");
-      blk.maps.push_back({off, len});
-      blk.handles.push_back(h);
-      tally_add(base, (long long)len);
-    }
-    SIPX_HIP(hipMemset((char*)base + r.first, 0, r.second - r.first));
-  }
-  SIPX_HIP(hipStreamSynchronize(nullptr));
-  std::lock_guard<std::mutex> lk(sparse_mutex());
-  sparse_registry()[base] = std::move(blk);
-  return base;
-}
-// A device-to-host copy into memory the caller has just allocated spends most of its time in page faults (one per 4 KiB, taken
-// one after the other by the copy's staging thread: 1 GiB arrives in 68 ms, in 20 ms once the pages exist -- round 5).  The
-// destination of a large download is therefore touched first, by several threads at once: one write per page makes the kernel
-// map it, and the copy that follows overwrites every byte.  (A destination that already has its pages loses a few hundred
-// microseconds per GiB to this.)
-inline void host_prefault(void* p, size_t bytes) {
-  constexpr size_t PAGE = 4096, MIN_BYTES = 8u << 20;
-  int nthreads = env_knobs().prefault_threads;                      // SIPX_PREFAULT_THREADS (0: off)
-  if (nthreads < 0) {
-    const unsigned hc = std::thread::hardware_concurrency();
-    nthreads = (int)std::min<unsigned>(16u, hc > 1 ? hc / 2 : 1u);      // (9 GiB: 0.64 s without, 0.34 / 0.27 s with 4 / 16 threads)
-  }
-  if (!p || bytes < MIN_BYTES || nthreads < 1) return;
-  char* base = static_cast<char*>(p);
-  const size_t first = (PAGE - (reinterpret_cast<uintptr_t>(base) & (PAGE - 1))) & (PAGE - 1);      // first page boundary inside
-  if (first >= bytes) return;
-  const size_t npages = (bytes - first + PAGE - 1) / PAGE;
-  auto touch = [base, first, npages, bytes](size_t a, size_t b) {
-    for (size_t k = a; k < b && k < npages; ++k) {
-      volatile char* q = base + first + k * PAGE;
-      if ((size_t)(q - base) < bytes) *q = 0;
-    }
-  };
-  std::vector<std::thread> th;
-  const size_t per = (npages + (size_t)nthreads - 1) / (size_t)nthreads;
-  for (int t = 1; t < nthreads; ++t) th.emplace_back(touch, (size_t)t * per, (size_t)(t + 1) * per);
-  base[0] = 0;
-  touch(0, per);
-  for (auto& t : th) t.join();
-}
-inline void dfree(void* p) {
-  if (!p) return;
-  tally_release(p);
-  {
-    std::lock_guard<std::mutex> lk(sparse_mutex());
-    auto it = sparse_registry().find(p);
-    if (it != sparse_registry().end()) {
-      for (size_t k = 0; k < it->second.maps.size(); ++k) {
-        (void)hipMemUnmap((char*)p + it->second.maps[k].first, it->second.maps[k].second);
-        (void)hipMemRelease(it->second.handles[k]);
-      }
-      (void)hipMemAddressFree(p, it->second.total);
-      sparse_registry().erase(it);
-      return;
-    }
-  }
-  {
-    std::lock_guard<std::mutex> lk(tally_mutex());
-    alloc_sizes().erase(p);
-  }
-  (void)hipFree(p);
-}
-// zero-fill of an allocation made by dalloc or sparse_alloc_bytes (its mapped granules), queued on `s`
-inline void dzero(void* p, hipStream_t s) {
-  if (!p) return;
-  {
-    std::lock_guard<std::mutex> lk(sparse_mutex());
-    auto it = sparse_registry().find(p);
-    if (it != sparse_registry().end()) {
-      for (const auto& mp : it->second.maps) SIPX_HIP(hipMemsetAsync((char*)p + mp.first, 0, mp.second, s));
-      return;
-    }
-  }
-  size_t bytes = 0;
-  {
-    std::lock_guard<std::mutex> lk(tally_mutex());
-    auto it = alloc_sizes().find(p);
-    if (it == alloc_sizes().end()) throw std::runtime_error("internal: dzero of an allocation the engine did not make");
-    bytes = it->second;
-  }
-  SIPX_HIP(hipMemsetAsync(p, 0, bytes, s));
-}
-
 
 // ---- small values of the whole-solve loop ------------------------------------------------------------------------------------
 static_assert(YL_FEAS == SIPX_YL_FEAS && YL_BB == SIPX_YL_BB && YL_FIRST == SIPX_YL_FIRST, "solve_rules.h numbers the flags like sipx.h");
@@ -418,7 +222,6 @@ struct SetState {
   T *y2 = nullptr, *l2 = nullptr;    // third pair of the one-sweep update (allocated by sipx_finalize, see sweep_launch)
   int snap = -1;                     // -1: no snapshot yet; 0: (y, l) is also the snapshot; 1: (y0, l0) is
   T *lb = nullptr, *ub = nullptr, *ata = nullptr;
-  std::vector<void*> halo_allocs;   // bases of the vectors allocated with a front halo
   int searches_done = 0;             // slab-decomposed l1 searches of this set so far (sizes the refinement rounds)
   int ext_kind = 0;                  // projector acting on a materialised vector (ext_proj.h)
   // Sharded solve: a rank / nuclear-norm set on the slices orthogonal to the last grid dimension is projected by ALL ranks,
@@ -496,24 +299,16 @@ class Engine : public EngineBase {
     if (lane_thr_.joinable()) lane_thr_.join();
     if (lane_st_) { (void)hipStreamSynchronize(lane_st_); (void)hipStreamDestroy(lane_st_); }
     for (hipEvent_t e : {lane_fork_, lane_ev_}) if (e) (void)hipEventDestroy(e);
-    dfree(lane_v_);
     if (fan_st_) { (void)hipStreamSynchronize(fan_st_); (void)hipStreamDestroy(fan_st_); }
     if (fan_fork_) (void)hipEventDestroy(fan_fork_);
-    for (void* p : {(void*)fan_ptmp_, (void*)fan_mpart_, (void*)fan_c_}) dfree(p);
-    if (loose_owned_) { dfree(loose_v_); dfree(loose_w_); }
     (void)hipStreamSynchronize(stream_);
     for (auto& s : sets_) free_set(s);
-    for (void* p : {(void*)xr_base_[0], (void*)xr_base_[1], (void*)xr_base_[2], (void*)w_base_, (void*)rhs_, (void*)m_base_, (void*)r_base_, (void*)p_base_, (void*)p2_base_, (void*)Ap_, (void*)Q_, (void*)qtab_,
-                    (void*)scr_v_, (void*)scr_c_, (void*)scr_i_, (void*)scr_w_, (void*)part_cg_, (void*)part_tmp_, (void*)part_sets_,
-                    (void*)maxpart_, (void*)cg_dev_, (void*)gbuf_, (void*)stage_, (void*)sstage_, (void*)fbuf_, (void*)agree_buf_})
-      dfree(p);
     comm_.reset();
     if (cstream_) (void)hipStreamDestroy(cstream_);
     for (auto e : ev_c_) if (e) (void)hipEventDestroy(e);
     if (ev_sums_) (void)hipEventDestroy(ev_sums_);
     if (ev_cgb_) (void)hipEventDestroy(ev_cgb_);
     for (const PinnedBlock& b : pinned_blocks()) if (*b.p) (void)hipHostFree(*b.p);
-    dfree(sums_ticket_);
     marks_.destroy();
     for (auto e : stat_ev_) (void)hipEventDestroy(e);
     for (auto e : cg_ev_) if (e) (void)hipEventDestroy(e);
@@ -523,7 +318,7 @@ class Engine : public EngineBase {
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_fork2_) (void)hipEventDestroy(ev_fork2_);
     (void)hipStreamDestroy(stream_);
-  }
+  }      // (the device arrays go with mem_, a projector's with the projector)
 
   // ------------------------------------------------------------------------------------------
   int add_set(const sipx_set_desc* d, const void* ata_R, const int64_t* ata_off, int d_i) override {
@@ -592,7 +387,11 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
     size_t fr = 0, tot = 0;
     SIPX_HIP(hipMemGetInfo(&fr, &tot));
-    if (context_bytes) *context_bytes = dev_bytes_;
+    if (context_bytes) {
+      long long b = mem_.bytes();
+      for (const auto& s : sets_) b += (s.ext ? s.ext->device_bytes() : 0) + (s.ddft ? s.ddft->device_bytes() : 0);
+      *context_bytes = b;
+    }
     if (device_used) *device_used = (int64_t)(tot - fr);
     if (device_total) *device_total = (int64_t)tot;
   }
@@ -622,7 +421,6 @@ class Engine : public EngineBase {
     if (finalized_) throw std::runtime_error("sipx_finalize called twice");
     SIPX_HIP(hipSetDevice(device_));
     refresh_env_knobs();                  // the launchers' A/B switches: read once per context, not per launch
-    TallyGuard tally(&dev_bytes_);
     feasibility_only_ = feasibility_only != 0;
     FinalizePlan P;
     plan_sets();
@@ -638,8 +436,8 @@ class Engine : public EngineBase {
       if (search_batch_) {                    // the sets' header segments and decision registers of the batched searches
         int n2 = 0;
         for (auto& s : sets_) n2 += s.two_pass ? 1 : 0;
-        fbuf_ = dalloc<T>((size_t)n2 * fast_hdr<T>());
-        stage_ = dalloc<double>((size_t)n2 * (PREP_SLOTS + 1 + 2));
+        fbuf_ = mem_.alloc<T>((size_t)n2 * fast_hdr<T>(), Mem::State);
+        stage_ = mem_.alloc<double>((size_t)n2 * (PREP_SLOTS + 1 + 2), Mem::State);
       }
       if (dev_io_) {
         import_dev(m, warm ? x0 : nullptr, warm ? l0 : nullptr, warm ? y0 : nullptr);
@@ -915,15 +713,15 @@ class Engine : public EngineBase {
   // step 5a: the vectors of the x-step, and m uploaded
   void alloc_iterate_arrays(const FinalizePlan& P, const void* m) {
     const long long N = G_.N, Npad = P.Npad;
-    for (int k = 0; k < 3; ++k) { xr_base_[k] = galloc(Npad + 2 * halo_, halo_, 1, 0); xr_[k] = xr_base_[k] + halo_; }
+    for (int k = 0; k < 3; ++k) { xr_base_[k] = galloc(Npad + 2 * halo_, halo_, 1, 0, Mem::State); xr_[k] = xr_base_[k] + halo_; }
     x_cur_ = 0; x_snap_ = -1;
     x_ = xr_[0]; xold_ = x_;                // (no x-step yet: x_old names x itself)
-    p_base_ = galloc(Nx_ + 2 * halo_, halo_, 1, 0); p_ = p_base_ + halo_;
-    rhs_ = galloc(Npad, 0, 1, 0);
-    if (mk_) { w_base_ = dalloc<T>(N + 2 * halo_); w_ = w_base_ + halo_; }   // u + v, read through the stencils
+    p_base_ = galloc(Nx_ + 2 * halo_, halo_, 1, 0, Mem::State); p_ = p_base_ + halo_;
+    rhs_ = galloc(Npad, 0, 1, 0, Mem::State);
+    if (mk_) { w_base_ = mem_.alloc<T>(N + 2 * halo_, Mem::State); w_ = w_base_ + halo_; }   // u + v, read through the stencils
     m_base_ = galloc(N + 2 * halo_, halo_, 1, 0); m_ = m_base_ + halo_;   // forward stencils of A m read past the end
-    r_base_ = galloc(Nx_ + 2 * halo_, halo_, 1, 0); r_ = r_base_ + halo_;      // (halo: the fused CG product reads r through the bands)
-    Ap_ = galloc(Nx_, 0, 1, 0);
+    r_base_ = galloc(Nx_ + 2 * halo_, halo_, 1, 0, Mem::State); r_ = r_base_ + halo_;      // (halo: the fused CG product reads r through the bands)
+    Ap_ = galloc(Nx_, 0, 1, 0, Mem::State);
     {
       // CG iterations from the second on as ONE kernel (scalar step + product on p = r + beta p_old formed on the fly,
       // k_cds_fused): one launch and a host round trip less per iteration -- what a launch-bound grid (2048^2) is made of --
@@ -934,7 +732,7 @@ class Engine : public EngineBase {
       //  instead of the 9 of product + p-update -- so it is the default at every size for the matrices the march takes)
       // (a matrix-free term of Q has no fused form: the product is followed by the term's two kernels)
       cg_fused_ = !comm_ && !stencil_q_ && n_mfree_ == 0 && (forced >= 0 ? forced == 1 : (small || cds_.march != 0));
-      if (cg_fused_) { p2_base_ = dalloc<T>(Nx_ + 2 * halo_); p2_ = p2_base_ + halo_; }
+      if (cg_fused_) { p2_base_ = mem_.alloc<T>(Nx_ + 2 * halo_, Mem::State); p2_ = p2_base_ + halo_; }
     }
     const long long c0 = std::max<long long>(0, wlo_), c1 = std::min<long long>(N, whi_);      // (sparse arrays: the rank's share only)
     // (device-resident call: m arrives with the warm start, in the one launch of import_dev)
@@ -995,16 +793,16 @@ class Engine : public EngineBase {
       for (auto& s : sets_) { n2 += s.two_pass ? 1 : 0; nl1 += (s.two_pass && s.prox == PX_L1) ? 1 : 0; }
       // the searches of all sets run in lock step: one staging buffer for their sums (one all-reduce per stage), one exchange
       // buffer with a segment per l1 set and rank (one all-gather)
-      gbuf_ = dalloc<T>((size_t)comm_->world * std::max(nl1, 1) * (hooks_.gcap + GATHER_HDR));
+      gbuf_ = mem_.alloc<T>((size_t)comm_->world * std::max(nl1, 1) * (hooks_.gcap + GATHER_HDR), Mem::State);
       hooks_.gbuf = gbuf_;
       // speculative exchange: a small segment per two-pass set and rank (header with the rank's sums + what its first pass
       // gathered inside the speculative range: a few thousand magnitudes once theta moves slowly)
       // (a rank's share of what the full-size segment holds, times two for uneven shares; at least 16 K values)
       hooks_.fcap = std::min<long long>(hooks_.gcap, std::max<long long>(1ll << 14, (2 * hooks_.gcap / comm_->world + 3) / 4 * 4));
       if (env_knobs().gather_fast_cap >= 4) hooks_.fcap = std::min<long long>(hooks_.gcap, env_knobs().gather_fast_cap / 4 * 4);      // SIPX_GATHER_FAST_CAP (tests)
-      fbuf_ = dalloc<T>((size_t)comm_->world * std::max(n2, 1) * (hooks_.fcap + fast_hdr<T>()));
-      stage_ = dalloc<double>((size_t)std::max(n2, 1) * (PREP_SLOTS + 1 + 2 * comm_->world));
-      sstage_ = dalloc<double>((size_t)std::max(n2, 1) * (2 * SAMPLE_BINS + 3));
+      fbuf_ = mem_.alloc<T>((size_t)comm_->world * std::max(n2, 1) * (hooks_.fcap + fast_hdr<T>()), Mem::State);
+      stage_ = mem_.alloc<double>((size_t)std::max(n2, 1) * (PREP_SLOTS + 1 + 2 * comm_->world), Mem::State);
+      sstage_ = mem_.alloc<double>((size_t)std::max(n2, 1) * (2 * SAMPLE_BINS + 3), Mem::State);
     }
     P.fullpad = maxpad;
     if (slab_local_) {                 // the whole-array scratch is not needed: searches compact at most what the rank's planes hold
@@ -1013,11 +811,11 @@ class Engine : public EngineBase {
       // (... or what the exchange of a search strings together from all ranks: at most gcap magnitudes, by the search's own rule)
       maxpad = std::min<long long>(maxpad, std::max<long long>((long long)nbmax * (whi_ - wlo_), hooks_.gcap + 64));
     }
-    scr_v_ = dalloc<T>(maxpad);
-    scr_c_ = dalloc<T>(maxpad);
+    scr_v_ = mem_.alloc<T>(maxpad, Mem::State);
+    scr_c_ = mem_.alloc<T>(maxpad, Mem::State);
     scr_c_len_ = maxpad;
-    if (need_idx_) scr_i_ = dalloc<long long>(maxpad);
-    if (need_ext_) scr_w_ = dalloc<T>(maxpad);
+    if (need_idx_) scr_i_ = mem_.alloc<long long>(maxpad, Mem::State);
+    if (need_ext_) scr_w_ = mem_.alloc<T>(maxpad, Mem::State);
     // the vectors the materialised sets of a slab-decomposed list are stored into, addressed by GLOBAL index (v, P(v), s = A x and
     // its copy): the engine-wide scratch where that is whole; with sparse arrays a rank that projects a gathered set holds them
     // whole, every other rank its planes only
@@ -1026,18 +824,17 @@ class Engine : public EngineBase {
       bool owner = false;
       for (auto& st : sets_) owner |= st.fan && st.fan_owner == comm_->rank;
       loose_whole_ = owner;
-      loose_v_ = owner ? dalloc<T>(P.fullpad) : loose_alloc(Npad);
-      loose_w_ = owner ? dalloc<T>(P.fullpad) : loose_alloc(Npad);
-      loose_owned_ = true;
+      loose_v_ = owner ? mem_.alloc<T>(P.fullpad) : loose_alloc(Npad);
+      loose_w_ = owner ? mem_.alloc<T>(P.fullpad) : loose_alloc(Npad);
     }
     // (the reduced per-set sums sit right behind the CG partials: sharded, ONE all-reduce can carry both, see argmin_x_head)
-    part_cg_ = dalloc<double>(2 * NB + (size_t)(p_n_ + 1) * SLOTS);
-    part_tmp_ = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-    part_sets_ = dalloc<double>((size_t)(p_n_ + 1) * SLOTS * NB);   // + one group of slots for whole-x sums
-    maxpart_ = dalloc<T>(2 * NB);     // per-block max | per-block smallest non-zero magnitude
-    cg_dev_ = dalloc<CgState<T>>(1);
+    part_cg_ = mem_.alloc<double>(2 * NB + (size_t)(p_n_ + 1) * SLOTS, Mem::State);
+    part_tmp_ = mem_.alloc<double>((size_t)(PREP_SLOTS + 2) * NB, Mem::State);
+    part_sets_ = mem_.alloc<double>((size_t)(p_n_ + 1) * SLOTS * NB, Mem::State);   // + one group of slots for whole-x sums
+    maxpart_ = mem_.alloc<T>(2 * NB, Mem::State);     // per-block max | per-block smallest non-zero magnitude
+    cg_dev_ = mem_.alloc<CgState<T>>(1, Mem::State);
     dres_ = part_cg_ + 2 * NB;
-    sums_ticket_ = dalloc<unsigned>(1);
+    sums_ticket_ = mem_.alloc<unsigned>(1, Mem::State);
     for (const PinnedBlock& b : pinned_blocks()) {
       SIPX_HIP(hipHostMalloc(b.p, b.bytes, hipHostMallocDefault));
       std::memset(*b.p, b.fill, b.bytes);
@@ -1055,7 +852,7 @@ class Engine : public EngineBase {
     // explicit AtA bands are kept on the device (every rank: Q is global); descriptor-generated
     // ones are never stored -- the fused Q update regenerates their values on the fly
     if (!s.host_ata.empty()) {
-      s.ata = dalloc<T>((size_t)N * s.ata_off.size(), false);
+      s.ata = mem_.alloc<T>((size_t)N * s.ata_off.size(), Mem::NoFill);
       SIPX_HIP(hipMemcpy(s.ata, s.host_ata.data(), s.host_ata.size() * sizeof(T), hipMemcpyHostToDevice));
       io_h2d_ += (long long)(s.host_ata.size() * sizeof(T));
       s.host_ata.clear();
@@ -1071,14 +868,10 @@ class Engine : public EngineBase {
     }
     if (!s.owned) return;
     // vectors read through adjoint stencils (w[g - stride]) carry a zero front halo: no bounds checks in the kernels
-    auto halloc = [&](long long n) {
-      T* base = galloc(n + halo_, halo_, s.nblk_or1(), N);
-      s.halo_allocs.push_back(base);
-      return base + halo_;
-    };
+    auto halloc = [&](long long n) { return galloc(n + halo_, halo_, s.nblk_or1(), N, Mem::State) + halo_; };
     s.y = halloc(s.Mpad); s.l = halloc(s.Mpad);
-    s.lh0 = galloc(s.Mpad, 0, s.nblk_or1(), N);
-    if (!x0_mode_) s.s0 = galloc(s.Mpad, 0, s.nblk_or1(), N);
+    s.lh0 = galloc(s.Mpad, 0, s.nblk_or1(), N, Mem::State);
+    if (!x0_mode_) s.s0 = galloc(s.Mpad, 0, s.nblk_or1(), N, Mem::State);
     s.y0 = halloc(s.Mpad); s.l0 = halloc(s.Mpad);       // take turns with y, l as the current iterate: same halo
     if (!s.ident) s.dy = halloc(s.Mpad);
     // the third pair of the one-sweep update (two plain iterations in a row: the snapshot has to survive in the other pair
@@ -1102,27 +895,27 @@ class Engine : public EngineBase {
     if (s.fan) {
       // the gathered sets are collected FIRST in an update (update_y_l), their owners project on a stream of their own while
       // every rank goes on with the sets of its own slab: each such set keeps its own whole-size vector, the fan stream its scratch
-      s.fanv = (s.fan_owner == comm_->rank || !slab_local_) ? dalloc<T>(P.fullpad) : loose_alloc(P.Npad);
+      s.fanv = (s.fan_owner == comm_->rank || !slab_local_) ? mem_.alloc<T>(P.fullpad) : loose_alloc(P.Npad);
       SIPX_HIP(hipEventCreateWithFlags(&s.fan_ev, hipEventDisableTiming));
       if (s.fan_owner == comm_->rank && !fan_st_) {
         SIPX_HIP(hipStreamCreateWithFlags(&fan_st_, hipStreamNonBlocking));
         SIPX_HIP(hipEventCreateWithFlags(&fan_fork_, hipEventDisableTiming));
-        fan_ptmp_ = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-        fan_mpart_ = dalloc<T>(2 * NB);
-        fan_c_ = dalloc<T>(P.fullpad);
+        fan_ptmp_ = mem_.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
+        fan_mpart_ = mem_.alloc<T>(2 * NB);
+        fan_c_ = mem_.alloc<T>(P.fullpad);
       }
     }
     if (s.two_pass) {
-      s.ps = dalloc<ProjScalars<T>>(1);
-      s.psf = dalloc<ProjScalars<T>>(1);
+      s.ps = mem_.alloc<ProjScalars<T>>(1);
+      s.psf = mem_.alloc<ProjScalars<T>>(1);
       K<T>::ps_init(stream_, s.ps, scr_i_);
       K<T>::ps_init(stream_, s.psf, scr_i_);
     }
     if ((slab_ || search_batch_) && s.two_pass) {        // searches in lock step: every set keeps its own partial slots and gather buffer
-      s.ptmp = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-      s.mpart = dalloc<T>(2 * NB);
+      s.ptmp = mem_.alloc<double>((size_t)(PREP_SLOTS + 2) * NB, Mem::State);
+      s.mpart = mem_.alloc<T>(2 * NB, Mem::State);
       s.cbuf_len = slab_local_ ? std::min<long long>(s.Mpad, std::max<long long>((long long)s.nblk_or1() * (whi_ - wlo_), hooks_.gcap + 64)) : s.Mpad;
-      s.cbuf = dalloc<T>(s.cbuf_len);
+      s.cbuf = mem_.alloc<T>(s.cbuf_len, Mem::State);
     }
     const bool had_scratch = s.ptmp != nullptr;
     if (set_streams_ && !s.ext_kind && s.prox != PX_CARD) {     // those two share the engine-wide scratch: main stream
@@ -1142,13 +935,13 @@ class Engine : public EngineBase {
       }
       SIPX_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
       if (s.two_pass && !had_scratch) {
-        s.ptmp = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-        s.mpart = dalloc<T>(2 * NB);
-        s.cbuf = dalloc<T>(s.Mpad);
+        s.ptmp = mem_.alloc<double>((size_t)(PREP_SLOTS + 2) * NB, Mem::State);
+        s.mpart = mem_.alloc<T>(2 * NB, Mem::State);
+        s.cbuf = mem_.alloc<T>(s.Mpad, Mem::State);
       }
     }
     if (s.prox == SIPX_PROJ_BOUNDS_VEC) {
-      s.lb = dalloc<T>(s.Mpad); s.ub = dalloc<T>(s.Mpad);
+      s.lb = mem_.alloc<T>(s.Mpad); s.ub = mem_.alloc<T>(s.Mpad);
       upload_rows(s, s.host_lb.data(), s.lb);
       upload_rows(s, s.host_ub.data(), s.ub);
     }
@@ -1185,8 +978,8 @@ class Engine : public EngineBase {
     SIPX_HIP(hipEventCreateWithFlags(&lane_fork_, hipEventDisableTiming));
     SIPX_HIP(hipEventCreateWithFlags(&lane_ev_, hipEventDisableTiming));
     // (slab-decomposed: a vector of the exchange layout addressed by global index, like loose_v_)
-    if (slab_) lane_v_ = (slab_local_ && !loose_whole_) ? loose_alloc(P.Npad) : dalloc<T>((size_t)std::max<long long>(P.fullpad, sets_[lane_set_].Mpad));
-    else lane_v_ = dalloc<T>((size_t)sets_[lane_set_].Mpad);
+    if (slab_) lane_v_ = (slab_local_ && !loose_whole_) ? loose_alloc(P.Npad) : mem_.alloc<T>((size_t)std::max<long long>(P.fullpad, sets_[lane_set_].Mpad), Mem::State);
+    else lane_v_ = mem_.alloc<T>((size_t)sets_[lane_set_].Mpad, Mem::State);
   }
 
   // ------------------------------------------------------------------------------------------
@@ -1210,15 +1003,7 @@ class Engine : public EngineBase {
     if (cstream_) SIPX_HIP(hipStreamSynchronize(cstream_));
     const long long N = G_.N;
     // ---- arrays
-    for (int k = 0; k < 3; ++k) dzero(xr_base_[k], stream_);
-    dzero(p_base_, stream_); dzero(rhs_, stream_); dzero(r_base_, stream_); dzero(Ap_, stream_);
-    dzero(p2_base_, stream_); dzero(w_base_, stream_);
-    dzero(part_cg_, stream_); dzero(part_tmp_, stream_); dzero(part_sets_, stream_); dzero(maxpart_, stream_);
-    dzero(cg_dev_, stream_); dzero(sums_ticket_, stream_);
-    dzero(fbuf_, stream_); dzero(stage_, stream_); dzero(sstage_, stream_); dzero(gbuf_, stream_);
-    dzero(scr_v_, stream_); dzero(scr_c_, stream_); dzero(scr_w_, stream_);
-    if (scr_i_) dzero(scr_i_, stream_);
-    dzero(lane_v_, stream_);
+    mem_.zero_state(stream_);      // everything allocated as Mem::State: the vectors, partials and scratch of the engine and of its sets
     if (!dev_io_) {
       SIPX_HIP(hipMemcpyAsync(m_, m, N * sizeof(T), hipMemcpyHostToDevice, stream_));
       io_h2d_ += N * (long long)sizeof(T);
@@ -1230,10 +1015,6 @@ class Engine : public EngineBase {
     const bool warm = !zero_ini_guess;
     for (int i = 0; i < p_n_; ++i) {
       SetState<T>& s = sets_[i];
-      for (void* b : s.halo_allocs) dzero(b, stream_);
-      dzero(s.lh0, stream_); dzero(s.s0, stream_);
-      dzero(s.sbuf, stream_); dzero(s.mf_t, stream_);
-      dzero(s.ptmp, stream_); dzero(s.mpart, stream_); dzero(s.cbuf, stream_);
       s.snap = -1;
       s.searches_done = 0;
       std::fill(s.sums, s.sums + SLOTS, 0.0);
@@ -2058,7 +1839,7 @@ class Engine : public EngineBase {
 
   // ---- communicator self-test (round 5) -------------------------------------------------------------------------
   // RcclComm has only ever run with a world of one here (a gpurun box has one GPU), and the slab decomposition hands RCCL halo
-  // planes that live in hipMemMap-backed memory.  Before any array of the context is allocated every rank therefore runs the
+  // planes that live in mapped (sparse-array) memory.  Before any array of the context is allocated every rank therefore runs the
   // communicator's operations once on KNOWN data -- the grouped all-reduce + neighbour exchange, the in-place reduce-scatter and
   // all-gather (the offsets RcclComm computes), the fan scatter / gather, the all-to-all, all on plain memory; then the neighbour exchange once
   // more with its four buffers inside a mapped granule between two unmapped ones -- compares what arrived with what must have
@@ -2069,7 +1850,7 @@ class Engine : public EngineBase {
   void comm_self_test(bool want_mapped, bool want_a2a = false) {
     if (!env_knobs().comm_selftest) {
       selftest_ = "skipped (SIPX_COMM_SELFTEST=0)";
-      if (!agree_buf_) agree_buf_ = dalloc<double>(64);
+      if (!agree_buf_) agree_buf_ = mem_.alloc<double>(64);
       return;
     }
     Comm& c = *comm_;
@@ -2079,10 +1860,11 @@ class Engine : public EngineBase {
     auto val = [](int r, size_t e) { return (double)((r + 1) * 256 + (int)(e & 255)); };
     std::vector<T> h(std::max<size_t>(W * chunk, 4 * hc));
     std::vector<double> hr(64);
-    T* buf = dalloc<T>(W * chunk);
-    T* hal = dalloc<T>(4 * hc);
-    double* red = dalloc<double>(64);
-    T* vm_base = nullptr;
+    DeviceMemory tmp;
+    T* buf = tmp.alloc<T>(W * chunk);
+    T* hal = tmp.alloc<T>(4 * hc);
+    // (the first one is kept: the ranks agree on the outcome of their allocations through it)
+    double* red = agree_buf_ ? tmp.alloc<double>(64) : (agree_buf_ = mem_.alloc<double>(64));
     std::string why;
     auto put = [&](T* dst, size_t n) { SIPX_HIP(hipMemcpy(dst, h.data(), n * sizeof(T), hipMemcpyHostToDevice)); };
     auto get = [&](const T* src, size_t n) {
@@ -2165,7 +1947,7 @@ class Engine : public EngineBase {
     if (ok && want_a2a) {
       T* a2a = nullptr;
       try {
-        a2a = dalloc<T>(3 * W * chunk);
+        a2a = tmp.alloc<T>(3 * W * chunk);
         for (size_t q = 0; q < W * chunk; ++q) h[q] = (T)((R + 1) * 64 + (int)(q / chunk) + (double)(q & 15) / 16.0);
         put(a2a, W * chunk);
         c.alltoall(a2a, a2a + W * chunk, a2a + 2 * W * chunk, chunk, dt, stream_);
@@ -2176,12 +1958,12 @@ class Engine : public EngineBase {
         a2a_ok = false;
         a2a_why_ = ex.what();
       }
-      dfree(a2a);
+      tmp.release(a2a);
     }
-    // E: the neighbour exchange out of / into hipMemMap-backed memory (one mapped granule between two that are not)
+    // E: the neighbour exchange out of / into the memory of a sparse array (one mapped granule between two that are not)
     if (ok && want_mapped) {
       try {
-        vm_base = (T*)sparse_alloc_bytes(3 * SPARSE_GRAN, {{SPARSE_GRAN, 2 * SPARSE_GRAN}}, device_);
+        T* vm_base = (T*)tmp.alloc_sparse(3 * SPARSE_GRAN, {{SPARSE_GRAN, 2 * SPARSE_GRAN}}, device_);
         T* vm = (T*)((char*)vm_base + SPARSE_GRAN) + 64;
         red_fill();
         fill_halo(vm);
@@ -2220,9 +2002,6 @@ class Engine : public EngineBase {
       all_ok = false;
       if (why.empty()) why = std::string("the verdict's all-reduce failed: ") + ex.what();
     }
-    dfree(buf); dfree(hal);
-    if (agree_buf_) dfree(red); else agree_buf_ = red;      // (kept: the ranks agree on the outcome of their allocations through it)
-    if (vm_base) dfree(vm_base);
     if (!all_ok)
       throw std::runtime_error("communicator self-test failed (" + std::string(c.kind()) + ", rank " + std::to_string(R) + " of " + std::to_string(W) +
                                "): " + (why.empty() ? std::string("another rank reports wrong data") : why));
@@ -2240,15 +2019,15 @@ class Engine : public EngineBase {
 
   // An array over the grid: `total` elements, entry g of block q at front + q * bstride + g.  Full size, or (slab_local_) backed
   // by memory for the grid points [wlo_, whi_) of every block only.
-  T* galloc(long long total, long long front, int nblk, long long bstride) {
-    if (!slab_local_) return dalloc<T>((size_t)total);
+  T* galloc(long long total, long long front, int nblk, long long bstride, Mem kind = Mem::Zeroed) {
+    if (!slab_local_) return mem_.alloc<T>((size_t)total, kind);
     std::vector<std::pair<size_t, size_t>> rg;
     for (int q = 0; q < std::max(nblk, 1); ++q) {
       const long long lo = std::max<long long>(0, front + (long long)q * bstride + wlo_);
       const long long hi = std::min<long long>(total, front + (long long)q * bstride + whi_);
       if (hi > lo) rg.push_back({(size_t)lo * sizeof(T), (size_t)hi * sizeof(T)});
     }
-    return (T*)sparse_alloc_bytes((size_t)total * sizeof(T), rg, device_);
+    return (T*)mem_.alloc_sparse((size_t)total * sizeof(T), rg, device_, kind);
   }
 
   // A rank's part of a whole vector of the exchange layout (sparse arrays, a materialised set this rank does not project whole):
@@ -2258,7 +2037,7 @@ class Engine : public EngineBase {
     const long long c0 = (long long)comm_->rank * chunk_, c1 = c0 + chunk_;
     const long long lo = std::min(std::max<long long>(0, wlo_), c0), hi = std::min(Npad, std::max(std::max<long long>(0, whi_), c1));
     std::vector<std::pair<size_t, size_t>> rg{{(size_t)lo * sizeof(T), (size_t)hi * sizeof(T)}};
-    return (T*)sparse_alloc_bytes((size_t)Npad * sizeof(T), rg, device_);
+    return (T*)mem_.alloc_sparse((size_t)Npad * sizeof(T), rg, device_);
   }
 
   // does the sweep take this context / iteration?  (asked before any search is queued; fills the layout part of `ma`)
@@ -2897,7 +2676,7 @@ class Engine : public EngineBase {
       qtab_reason_ = why;
       return;
     }
-    if (!qtab_) qtab_ = dalloc<T>(QT_N + 8);          // (+ the check's flag)
+    if (!qtab_) qtab_ = mem_.alloc<T>(QT_N + 8);          // (+ the check's flag)
     int* ok = (int*)(qtab_ + QT_N);
     K<T>::qtab_build(stream_, Nx_, cds_, Q_, qtab_, ok);
     int h = 0;
@@ -2937,7 +2716,8 @@ class Engine : public EngineBase {
     const long long cpad = c->comm_ ? c->chunk_ * c->comm_->world : Nc;
     int nbmax = 1;
     for (auto& st : c->sets_) nbmax = std::max(nbmax, st.nblk_or1());
-    T* whole = c->slab_ ? dalloc<T>((size_t)nbmax * cpad, false) : nullptr;
+    DeviceMemory tmp;
+    T* whole = c->slab_ ? tmp.alloc<T>((size_t)nbmax * cpad, Mem::NoFill) : nullptr;
     const int dt = dtype_code();
     const long long f0 = slab_local_ ? std::max<long long>(0, wlo_) : 0, f1 = slab_local_ ? std::min<long long>(Nf, whi_) : Nf;
     // (all blocks of a set's coarse vector side by side: a chunk of the reference's row vector may straddle two of them)
@@ -2975,7 +2755,6 @@ class Engine : public EngineBase {
       }
     }
     SIPX_HIP(hipStreamSynchronize(stream_));
-    dfree(whole);
   }
 
   // Slab-decomposed context: completes x and / or the y_i, l_i named on every rank from the ranks' slabs (all-gathers on the
@@ -3004,8 +2783,9 @@ class Engine : public EngineBase {
     const long long N = G_.N, Npad = chunk_ * comm_->world, nloc = r1_ - r0_;
     int nbmax = 1;
     for (auto& s : sets_) nbmax = std::max(nbmax, s.nblk_or1());
-    T* exch = dalloc<T>((size_t)Npad);
-    T* whole = dalloc<T>((size_t)nbmax * N);
+    DeviceMemory tmp;
+    T* exch = tmp.alloc<T>((size_t)Npad);
+    T* whole = tmp.alloc<T>((size_t)nbmax * N);
     auto complete = [&](const T* src) {      // src: a block of a sparse array (global indexing); afterwards exch[0, N) holds all of it
       if (nloc > 0) SIPX_HIP(hipMemcpyAsync(exch + r0_, src + r0_, nloc * sizeof(T), hipMemcpyDeviceToDevice, stream_));
       comm_->allgather(exch, (size_t)chunk_, dt, stream_);
@@ -3029,8 +2809,6 @@ class Engine : public EngineBase {
         download_rows(sets_[i], whole, (T*)dst[i]);
       }
     SIPX_HIP(hipStreamSynchronize(stream_));
-    dfree(exch);
-    dfree(whole);
   }
 
   void download(void* x, void* const* l, void* const* y) override {
@@ -3384,8 +3162,9 @@ class Engine : public EngineBase {
     long long H = 4;
     for (int a = 0; a < 3; ++a) H = std::max<long long>(H, G_.st[a]);
     H = (H + 3) / 4 * 4;
-    T* dxb = dalloc<T>(G_.N + 2 * H);
-    T* dvb = dalloc<T>(s.Mpad + H);
+    DeviceMemory tmp;
+    T* dxb = tmp.alloc<T>(G_.N + 2 * H);
+    T* dvb = tmp.alloc<T>(s.Mpad + H);
     T *dx = dxb + H, *dv = dvb + H;
     if (!adjoint) {
       SIPX_HIP(hipMemcpy(dx, x, G_.N * sizeof(T), hipMemcpyHostToDevice));
@@ -3397,26 +3176,25 @@ class Engine : public EngineBase {
       SIPX_HIP(hipStreamSynchronize(stream_));
       SIPX_HIP(hipMemcpy(out, dx, G_.N * sizeof(T), hipMemcpyDeviceToHost));
     }
-    dfree(dxb);
-    dfree(dvb);
   }
 
   void project(const sipx_set_desc* d, void* v, int64_t len) override {
     SIPX_HIP(hipSetDevice(device_));
     Grid g1;
     g1.n[0] = len; g1.n[1] = 1; g1.n[2] = 1; g1.N = len; g1.st[0] = 1; g1.st[1] = len; g1.st[2] = len;
-    T* dv = dalloc<T>(len);
-    T* dc = dalloc<T>(len);
+    DeviceMemory tmp;
+    T* dv = tmp.alloc<T>(len);
+    T* dc = tmp.alloc<T>(len);
     T *lb = nullptr, *ub = nullptr;
-    double* part = dalloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-    T* mp = dalloc<T>(2 * NB);
-    ProjScalars<T>* ps = dalloc<ProjScalars<T>>(1);
+    double* part = tmp.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
+    T* mp = tmp.alloc<T>(2 * NB);
+    ProjScalars<T>* ps = tmp.alloc<ProjScalars<T>>(1);
     SIPX_HIP(hipMemcpy(dv, v, len * sizeof(T), hipMemcpyHostToDevice));
     const int prox = d->proj;
     const T plo = (T)d->pmin, phi = (T)d->pmax;
     if (prox == SIPX_PROJ_BOUNDS_VEC && d->mode == SIPX_MODE_WHOLE && d->transform == SIPX_TRANSFORM_NONE) {
       if (!d->lb || !d->ub) throw std::runtime_error("per-element bounds need lb and ub");
-      lb = dalloc<T>(len); ub = dalloc<T>(len);
+      lb = tmp.alloc<T>(len); ub = tmp.alloc<T>(len);
       SIPX_HIP(hipMemcpy(lb, d->lb, len * sizeof(T), hipMemcpyHostToDevice));
       SIPX_HIP(hipMemcpy(ub, d->ub, len * sizeof(T), hipMemcpyHostToDevice));
     }
@@ -3438,19 +3216,17 @@ class Engine : public EngineBase {
           for (int q = 0; q < 4; ++q) project_rc_[q] += c[q];
         }
       } else {                                   // per-fiber bounds, expanded by configure_proj
-        lb = dalloc<T>(len); ub = dalloc<T>(len);
+        lb = tmp.alloc<T>(len); ub = tmp.alloc<T>(len);
         SIPX_HIP(hipMemcpy(lb, st.host_lb.data(), len * sizeof(T), hipMemcpyHostToDevice));
         SIPX_HIP(hipMemcpy(ub, st.host_ub.data(), len * sizeof(T), hipMemcpyHostToDevice));
         proj_apply_grid<T>(stream_, g1, 0, nullptr, len, dv, st.prox, st.plo, st.phi, lb, ub, nullptr);
       }
       SIPX_HIP(hipStreamSynchronize(stream_));
       SIPX_HIP(hipMemcpy(v, dv, len * sizeof(T), hipMemcpyDeviceToHost));
-      for (void* q : {(void*)dv, (void*)dc, (void*)part, (void*)mp, (void*)ps, (void*)lb, (void*)ub})
-        if (q) dfree(q);
       return;
     }
     const bool two = prox == SIPX_PROJ_L1 || prox == SIPX_PROJ_L2 || prox == SIPX_PROJ_ANNULUS || prox == SIPX_PROJ_CARDINALITY;
-    long long* di = prox == SIPX_PROJ_CARDINALITY ? dalloc<long long>(len) : nullptr;
+    long long* di = prox == SIPX_PROJ_CARDINALITY ? tmp.alloc<long long>(len) : nullptr;
     if (two) {
       K<T>::ps_init(stream_, ps, di);
       K<T>::proj_scalars_arr(stream_, len, dv, prox, plo, phi, ps, part, mp, dc, len);
@@ -3458,8 +3234,6 @@ class Engine : public EngineBase {
     proj_apply_grid<T>(stream_, g1, 0, nullptr, len, dv, prox, prox == SIPX_PROJ_BOUNDS_VEC ? T(0) : plo, phi, lb, ub, two ? ps : nullptr);
     SIPX_HIP(hipStreamSynchronize(stream_));
     SIPX_HIP(hipMemcpy(v, dv, len * sizeof(T), hipMemcpyDeviceToHost));
-    for (void* q : {(void*)dv, (void*)dc, (void*)lb, (void*)ub, (void*)part, (void*)mp, (void*)ps, (void*)di})
-      dfree(q);
   }
 
   void get_Q(void* Q, int64_t* offsets, int* d) override {
@@ -3960,13 +3734,13 @@ class Engine : public EngineBase {
       }
     auto up = [&](auto*& dst, const auto& src) {
       using E = typename std::remove_reference<decltype(src)>::type::value_type;
-      dst = dalloc<E>(std::max<size_t>(src.size(), 1), false);
+      dst = mem_.alloc<E>(std::max<size_t>(src.size(), 1), Mem::NoFill);
       if (!src.empty()) SIPX_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice));
     };
     up(s.mf_colptr, colptr); up(s.mf_rowidx, rowidx); up(s.d_nzval, s.h_nzval);
     up(s.mf_rowptr, rowptr); up(s.mf_colidx, colidx); up(s.d_rval, rval);
-    s.sbuf = dalloc<T>(M);
-    s.mf_t = dalloc<T>(M);
+    s.sbuf = mem_.alloc<T>(M, Mem::State);
+    s.mf_t = mem_.alloc<T>(M, Mem::State);
     s.mfA.rows = (int)M; s.mfA.nnz = nnz; s.mfA.ptr = s.mf_rowptr; s.mfA.idx = s.mf_colidx; s.mfA.val = s.d_rval; s.mfA.lanes = mf_lanes(rowptr);
     s.mfAt.rows = (int)N; s.mfAt.nnz = nnz; s.mfAt.ptr = s.mf_colptr; s.mfAt.idx = s.mf_rowidx; s.mfAt.val = s.d_nzval; s.mfAt.lanes = mf_lanes(colptr);
     s.h_colptr.clear(); s.h_rowval.clear(); s.h_nzval.clear();
@@ -3987,12 +3761,12 @@ class Engine : public EngineBase {
       }
     auto up = [&](auto*& dst, const auto& src) {
       using E = typename std::remove_reference<decltype(src)>::type::value_type;
-      dst = dalloc<E>(src.size(), false);
+      dst = mem_.alloc<E>(src.size(), Mem::NoFill);
       SIPX_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice));
     };
     up(s.d_colptr, s.h_colptr); up(s.d_rowval, s.h_rowval); up(s.d_nzval, s.h_nzval);
     up(s.d_rowptr, rowptr); up(s.d_colidx, colidx); up(s.d_rval, rval);
-    s.sbuf = dalloc<T>(M);
+    s.sbuf = mem_.alloc<T>(M, Mem::State);
     s.h_colptr.clear(); s.h_rowval.clear(); s.h_nzval.clear();
   }
 
@@ -4145,7 +3919,7 @@ class Engine : public EngineBase {
     }
     // (sparse arrays: the rows of every band that the rank's part of the x-step reads)
     if (Q_) {                       // sipx_reset: the bands are there, zero them and add the sets up again
-      dzero(Q_, stream_);
+      mem_.zero(Q_, stream_);
     } else if (slab_local_) {
       std::vector<std::pair<size_t, size_t>> rg;
       long long maxoff = 0;
@@ -4157,9 +3931,9 @@ class Engine : public EngineBase {
         const long long hi = std::min<long long>((long long)Nx_ * cds_.d, (long long)b * Nx_ + std::max(qr1_, qr0_) + 64);
         if (hi > lo) rg.push_back({(size_t)lo * sizeof(T), (size_t)hi * sizeof(T)});
       }
-      Q_ = (T*)sparse_alloc_bytes((size_t)Nx_ * cds_.d * sizeof(T), rg, device_);
+      Q_ = (T*)mem_.alloc_sparse((size_t)Nx_ * cds_.d * sizeof(T), rg, device_);
     } else {
-      Q_ = dalloc<T>((size_t)Nx_ * cds_.d);
+      Q_ = mem_.alloc<T>((size_t)Nx_ * cds_.d);
     }
     if (mk_) {
       std::vector<T> al(rho_.begin(), rho_.end());
@@ -4326,7 +4100,8 @@ class Engine : public EngineBase {
       SIPX_HIP(hipMemcpy(dev, rows, (size_t)s.Mtrue * sizeof(T), hipMemcpyHostToDevice));
       return;
     }
-    T* tmp = dalloc<T>(s.Mtrue, false);
+    DeviceMemory own;
+    T* tmp = own.alloc<T>(s.Mtrue, Mem::NoFill);
     SIPX_HIP(hipMemcpy(tmp, rows, (size_t)s.Mtrue * sizeof(T), hipMemcpyHostToDevice));
     long long r0 = 0;
     for (int q = 0; q < s.nblk; ++q) {
@@ -4334,18 +4109,17 @@ class Engine : public EngineBase {
       r0 += s.blk_rows[q];
     }
     SIPX_HIP(hipStreamSynchronize(stream_));
-    dfree(tmp);
   }
   // (sparse arrays: through a whole-size temporary, of which the rank's share is kept)
   void upload_rows_ranged(const SetState<T>& s, const T* rows, T* dev) const {
     if (!slab_local_) { upload_rows(s, rows, dev); return; }
-    T* full = dalloc<T>((size_t)s.Mpad);
+    DeviceMemory tmp;
+    T* full = tmp.alloc<T>((size_t)s.Mpad);
     upload_rows(s, rows, full);
     const long long c0 = std::max<long long>(0, wlo_), c1 = std::min<long long>(G_.N, whi_);
     for (int q = 0; q < s.nblk_or1() && c1 > c0; ++q)
       SIPX_HIP(hipMemcpy(dev + (long long)q * G_.N + c0, full + (long long)q * G_.N + c0, (c1 - c0) * sizeof(T), hipMemcpyDeviceToDevice));
     SIPX_HIP(hipDeviceSynchronize());
-    dfree(full);
   }
   void download_rows(const SetState<T>& s, const T* dev, T* rows) const {
     io_d2h_ += s.Mtrue * (long long)sizeof(T);
@@ -4355,7 +4129,8 @@ class Engine : public EngineBase {
       SIPX_HIP(hipMemcpy(rows, dev, (size_t)s.Mtrue * sizeof(T), hipMemcpyDeviceToHost));
       return;
     }
-    T* tmp = dalloc<T>(s.Mtrue, false);
+    DeviceMemory own;
+    T* tmp = own.alloc<T>(s.Mtrue, Mem::NoFill);
     long long r0 = 0;
     for (int q = 0; q < s.nblk; ++q) {
       K<T>::rows_pack(stream_, G_, s.dir[q], s.blk_rows[q], dev + (long long)q * G_.N, tmp + r0);
@@ -4364,7 +4139,6 @@ class Engine : public EngineBase {
     SIPX_HIP(hipStreamSynchronize(stream_));
     host_prefault(rows, (size_t)s.Mtrue * sizeof(T));
     SIPX_HIP(hipMemcpy(rows, tmp, (size_t)s.Mtrue * sizeof(T), hipMemcpyDeviceToHost));
-    dfree(tmp);
   }
 
   int dtype_code() const { return sizeof(T) == 8 ? SIPX_F64 : SIPX_F32; }
@@ -4460,15 +4234,6 @@ class Engine : public EngineBase {
     if (s.st) (void)hipStreamSynchronize(s.st);
     if (s.ev) (void)hipEventDestroy(s.ev);
     if (s.fan_ev) (void)hipEventDestroy(s.fan_ev);
-    dfree(s.fanv);
-    for (void* p : {(void*)s.ptmp, (void*)s.mpart, (void*)s.cbuf, (void*)s.d_colptr, (void*)s.d_rowval, (void*)s.d_rowptr,
-                    (void*)s.d_colidx, (void*)s.d_nzval, (void*)s.d_rval, (void*)s.sbuf, (void*)s.mf_colptr, (void*)s.mf_rowidx,
-                    (void*)s.mf_rowptr, (void*)s.mf_colidx, (void*)s.mf_t})
-      dfree(p);
-    for (void* p : s.halo_allocs) dfree(p);
-    for (void* p : {(void*)s.lh0, (void*)s.s0, (void*)s.lb, (void*)s.ub, (void*)s.ata,
-                    (void*)s.ps, (void*)s.psf})
-      dfree(p);
   }
 
   struct Run {     // state of one whole solve (sipx_parsdmm_begin / _steps)
@@ -4514,7 +4279,7 @@ class Engine : public EngineBase {
   long long scr_c_len_ = 0;
   T* scr_w_ = nullptr;
   T *loose_v_ = nullptr, *loose_w_ = nullptr;    // global-indexed vectors of the materialised sets of a slab-decomposed list (finalize)
-  bool loose_owned_ = false, loose_whole_ = false;
+  bool loose_whole_ = false;
   bool need_idx_ = false, need_ext_ = false;
   CdsArgs cds_;
   bool set_streams_ = true;       // SIPX_SERIAL_SETS=1 keeps every set on the engine stream (A/B measurements)
@@ -4578,7 +4343,7 @@ class Engine : public EngineBase {
   T* qtab_ = nullptr;                   // class table of Q + the check's flag (build_q_table)
   bool q_stale_ = false;                // the stored bands lag the table (ensure_q_bands)
   std::string qtab_reason_ = "not built";   // why the products use the bands ("": they use the table)
-  long long dev_bytes_ = 0;           // device bytes this context allocated (dalloc + the library-backed projectors' own buffers)
+  DeviceMemory mem_;                  // every device array the context keeps (the library-backed projectors own theirs)
   bool slab_dist_logs_ = false;       // slab-decomposed and a distance term among the sets: obj / evol_x sums come from its y/l update
   bool lean_multi_ = false;           // k_lean_multi for the lean first passes of the l1 searches (finalize: above 2^24 grid points; SIPX_LEAN_MULTI=0/1)
   bool head_done_ = false;            // the residual product of the coming x-step is queued already (argmin_x_head)
@@ -4596,7 +4361,7 @@ class Engine : public EngineBase {
   long long fan_exchanges_ = 0;       // gathers + scatters of the gathered sets so far (stats)
   bool slab_loose_ = false;           // slab-decomposed with sets projected on a materialised v (SetState::slab_ext, fan)
   // slab-decomposed with SPARSE arrays: every N-sized array of the context is backed by memory for the rank's planes (and the
-  // halo planes around them) only -- see SparseBlock.  [wlo_, whi_): the grid points whose entries exist on this rank.
+  // halo planes around them) only -- see DeviceMemory::alloc_sparse.  [wlo_, whi_): the grid points whose entries exist on this rank.
   bool slab_full_req_ = false, slab_local_ = false;
   // verdict of the communicator self-test of sipx_finalize ("none" without a communicator)
   std::string selftest_ = "none", mapped_why_;
@@ -4622,9 +4387,7 @@ class Engine : public EngineBase {
 };
 
 EngineBase* make_engine(int dtype, int ndim, const int64_t* n, const double* h, int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    throw std::runtime_error("libsipx: no HIP device visible -- this engine has no CPU fallback");
+  const int count = hip_device_count();
   if (device < 0 || device >= count) throw std::runtime_error("libsipx: device index out of range");
   if (dtype == SIPX_F32) return new Engine<float>(ndim, n, h, device);
   if (dtype == SIPX_F64) return new Engine<double>(ndim, n, h, device);
@@ -4637,10 +4400,11 @@ static void cds_spmv_T(int64_t N, int d, const void* R, const int64_t* off, cons
   long long H = 4;
   for (int b = 0; b < d; ++b) H = std::max<long long>(H, std::llabs((long long)off[b]));
   H = (H + 3) / 4 * 4;
-  T* dR = dalloc<T>((size_t)N * d, false);
-  T* dxb = dalloc<T>(N + 2 * H);          // zero halo on both sides
+  DeviceMemory tmp;
+  T* dR = tmp.alloc<T>((size_t)N * d, Mem::NoFill);
+  T* dxb = tmp.alloc<T>(N + 2 * H);          // zero halo on both sides
   T* dx = dxb + H;
-  T* dy = dalloc<T>(N);
+  T* dy = tmp.alloc<T>(N);
   SIPX_HIP(hipMemcpy(dR, R, (size_t)N * d * sizeof(T), hipMemcpyHostToDevice));
   SIPX_HIP(hipMemcpy(dx, x, N * sizeof(T), hipMemcpyHostToDevice));
   CdsArgs a;
@@ -4651,7 +4415,6 @@ static void cds_spmv_T(int64_t N, int d, const void* R, const int64_t* off, cons
   K<T>::spmv(nullptr, g, N, dR, a, dx, dy);
   SIPX_HIP(hipDeviceSynchronize());
   SIPX_HIP(hipMemcpy(y, dy, N * sizeof(T), hipMemcpyDeviceToHost));
-  dfree(dR); dfree(dxb); dfree(dy);
 }
 
 template <typename T>
@@ -4660,18 +4423,16 @@ static void resample_T(int ndim, const int64_t* nc, const int64_t* nf, const voi
   for (int q = 0; q < ndim && q < 3; ++q) { c[q] = nc[q]; f[q] = nf[q]; }
   const long long Nc = c[0] * c[1] * c[2], Nf = f[0] * f[1] * f[2];
   if (Nc < 1 || Nf < 1) throw std::runtime_error("resample: empty array");
-  T* di = dalloc<T>(Nc, false);
-  T* dout = dalloc<T>(Nf, false);
+  DeviceMemory tmp;
+  T* di = tmp.alloc<T>(Nc, Mem::NoFill);
+  T* dout = tmp.alloc<T>(Nf, Mem::NoFill);
   SIPX_HIP(hipMemcpy(di, in, Nc * sizeof(T), hipMemcpyHostToDevice));
   resample_nn<T>(nullptr, c, f, di, dout);
   SIPX_HIP(hipDeviceSynchronize());
   SIPX_HIP(hipMemcpy(out, dout, Nf * sizeof(T), hipMemcpyDeviceToHost));
-  dfree(di); dfree(dout);
 }
 void resample_nn_host(int dtype, int ndim, const int64_t* nc, const int64_t* nf, const void* in, void* out, int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    throw std::runtime_error("libsipx: no HIP device visible -- this engine has no CPU fallback");
+  hip_device_count();
   if (ndim < 1 || ndim > 3) throw std::runtime_error("resample: ndim must be 1..3");
   SIPX_HIP(hipSetDevice(device));
   if (dtype == SIPX_F32) resample_T<float>(ndim, nc, nf, in, out);
@@ -4682,20 +4443,18 @@ void resample_nn_host(int dtype, int ndim, const int64_t* nc, const int64_t* nf,
 template <typename T>
 static void dwt_T(int ndim, const long long* n, int inverse, const void* in, void* out) {
   const long long N = n[0] * n[1] * n[2];
-  T* di = dalloc<T>(N, false);
-  T* dout = dalloc<T>(N, false);
-  T* ds = dalloc<T>(N, false);
+  DeviceMemory tmp;
+  T* di = tmp.alloc<T>(N, Mem::NoFill);
+  T* dout = tmp.alloc<T>(N, Mem::NoFill);
+  T* ds = tmp.alloc<T>(N, Mem::NoFill);
   SIPX_HIP(hipMemcpy(di, in, N * sizeof(T), hipMemcpyHostToDevice));
   if (inverse) dwt_inverse<T>(nullptr, ndim, n, di, dout, ds);
   else dwt_forward<T>(nullptr, ndim, n, di, dout, ds);
   SIPX_HIP(hipDeviceSynchronize());
   SIPX_HIP(hipMemcpy(out, dout, N * sizeof(T), hipMemcpyDeviceToHost));
-  dfree(di); dfree(dout); dfree(ds);
 }
 void dwt_host(int dtype, int ndim, const int64_t* n, int inverse, const void* in, void* out, int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    throw std::runtime_error("libsipx: no HIP device visible -- this engine has no CPU fallback");
+  hip_device_count();
   if (ndim != 2 && ndim != 3) throw std::runtime_error("wavelet transform: ndim must be 2 or 3");
   long long nn[3] = {1, 1, 1};
   for (int q = 0; q < ndim; ++q) nn[q] = n[q];
@@ -4708,19 +4467,17 @@ void dwt_host(int dtype, int ndim, const int64_t* n, int inverse, const void* in
 
 template <typename T>
 static void prox_l2s_T(int64_t n, void* x, double rho, const void* m) {
-  T* dx = dalloc<T>(n, false);
-  T* dm = dalloc<T>(n, false);
+  DeviceMemory tmp;
+  T* dx = tmp.alloc<T>(n, Mem::NoFill);
+  T* dm = tmp.alloc<T>(n, Mem::NoFill);
   SIPX_HIP(hipMemcpy(dx, x, n * sizeof(T), hipMemcpyHostToDevice));
   SIPX_HIP(hipMemcpy(dm, m, n * sizeof(T), hipMemcpyHostToDevice));
   prox_l2s_dev<T>(nullptr, n, dx, dm, (T)rho);
   SIPX_HIP(hipDeviceSynchronize());
   SIPX_HIP(hipMemcpy(x, dx, n * sizeof(T), hipMemcpyDeviceToHost));
-  dfree(dx); dfree(dm);
 }
 void prox_l2s_host(int dtype, int64_t n, void* x, double rho, const void* m, int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    throw std::runtime_error("libsipx: no HIP device visible -- this engine has no CPU fallback");
+  hip_device_count();
   if (n < 1) return;
   SIPX_HIP(hipSetDevice(device));
   if (dtype == SIPX_F32) prox_l2s_T<float>(n, x, rho, m);
@@ -4729,9 +4486,7 @@ void prox_l2s_host(int dtype, int64_t n, void* x, double rho, const void* m, int
 }
 
 void cds_spmv_host(int dtype, int64_t N, int d, const void* R, const int64_t* off, const void* x, void* y, int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    throw std::runtime_error("libsipx: no HIP device visible -- this engine has no CPU fallback");
+  hip_device_count();
   SIPX_HIP(hipSetDevice(device));
   if (dtype == SIPX_F32) cds_spmv_T<float>(N, d, R, off, x, y);
   else if (dtype == SIPX_F64) cds_spmv_T<double>(N, d, R, off, x, y);

@@ -14,34 +14,19 @@
 #include <vector>
 
 #include "../../include/sipx.h"
+#include "device_memory.h"
 #include "ext_proj.h"
 #include "sipx_device.h"
 
 namespace sipx {
 
-// device allocations of one projector, counted for the context that builds it and freed with the projector
-struct Arena {
-  std::vector<void*> owned;
-  template <typename Q>
-  Q* alloc(size_t count) {
-    void* p = nullptr;
-    SIPX_HIP(hipMalloc(&p, sizeof(Q) * (count ? count : 1)));
-    if (long long* t = alloc_tally()) *t += (long long)(sizeof(Q) * (count ? count : 1));
-    owned.push_back(p);
-    return (Q*)p;
-  }
-  Arena() = default;
-  Arena(const Arena&) = delete;
-  ~Arena() { for (void* p : owned) if (p) (void)hipFree(p); }
-};
-
 // One projector.  A family's constructor that throws halfway releases what it had taken: handles live in members that destroy
-// themselves (BlasHandle, and the like in the units), device memory in the arena.
+// themselves (BlasHandle, and the like in the units), device memory in `mem`, which frees it with the projector.
 template <typename T>
 struct ExtImpl {
   ExtSpec sp;
   hipStream_t stream;
-  Arena mem;
+  DeviceMemory mem;
   ExtImpl(const ExtSpec& spec, hipStream_t s) : sp(spec), stream(s) {}
   virtual ~ExtImpl() {}
   // v <- P(v) in place; feas selects the warm-start state of the feasibility estimate
@@ -50,7 +35,7 @@ struct ExtImpl {
   virtual void reset() {}
   virtual void route_counts(long long out[4]) const { out[0] = out[1] = out[2] = out[3] = 0; }
   template <typename Q>
-  Q* alloc(size_t count) { return mem.template alloc<Q>(count); }
+  Q* alloc(size_t count) { return mem.template alloc<Q>(count ? count : 1, Mem::NoFill); }
 };
 template <typename T> ExtImpl<T>* make_transform_family(const ExtSpec& spec, hipStream_t stream);
 template <typename T> ExtImpl<T>* make_rank_family(const ExtSpec& spec, hipStream_t stream);
@@ -90,10 +75,10 @@ template <typename T>
 struct SearchState {
   ProjScalars<T>*ps = nullptr, *psf = nullptr;
   long long* cidx = nullptr;
-  void build(Arena& mem, hipStream_t s, long long n_idx) {
-    ps = mem.template alloc<ProjScalars<T>>(1);
-    psf = mem.template alloc<ProjScalars<T>>(1);
-    if (n_idx) cidx = mem.template alloc<long long>(n_idx);
+  void build(DeviceMemory& mem, hipStream_t s, long long n_idx) {
+    ps = mem.template alloc<ProjScalars<T>>(1, Mem::NoFill);
+    psf = mem.template alloc<ProjScalars<T>>(1, Mem::NoFill);
+    if (n_idx) cidx = mem.template alloc<long long>(n_idx, Mem::NoFill);
     reinit(s);
   }
   void reinit(hipStream_t s) {       // a projector without a search (never built) has nothing to forget

@@ -42,6 +42,8 @@ class ExtProj {
   void set_stream(hipStream_t s);
   // forget every warm start and counter: the projector behaves like a newly built one (sipx_reset)
   void reset();
+  // device bytes the projector holds
+  long long device_bytes() const;
 
  private:
   ExtImpl<T>* impl_;

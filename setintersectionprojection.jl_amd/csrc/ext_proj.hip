@@ -52,6 +52,8 @@ void ExtProj<T>::set_stream(hipStream_t s) { impl_->set_stream(s); }
 template <typename T>
 void ExtProj<T>::reset() { if (impl_) impl_->reset(); }
 template <typename T>
+long long ExtProj<T>::device_bytes() const { return impl_ ? impl_->mem.bytes() : 0; }
+template <typename T>
 void ExtProj<T>::route_counts(long long out[4]) const {
   out[0] = out[1] = out[2] = out[3] = 0;
   if (impl_) impl_->route_counts(out);

@@ -845,7 +845,8 @@ static int gemm_tune(rocblas_handle h, const GemmShape& key, const double* A, lo
   sols.resize(ns);
   unsigned long long* dh = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (hipMalloc((void**)&dh, sizeof(unsigned long long)) != hipSuccess) return 0;
+  DeviceMemory tmp;
+  try { dh = tmp.alloc<unsigned long long>(1, Mem::NoFill); } catch (const std::exception&) { return 0; }
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   const long long span = sc * (long long)batch;
   struct Res { int sol; unsigned long long hash; float ms; };
@@ -899,7 +900,6 @@ static int gemm_tune(rocblas_handle h, const GemmShape& key, const double* A, lo
   // the call's own result, by the kernel that was chosen (the probes left another candidate's output in C)
   (void)dgemm_ex(h, ta, tb, key.m, key.n, key.k, &one, A, key.lda, sa, B, key.ldb, sb, &zero, C, key.ldc, sc, batch, choice);
   (void)hipStreamSynchronize(s);
-  (void)hipFree(dh);
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
   return choice;
@@ -1351,8 +1351,7 @@ struct RankFamily : ExtImpl<T> {
   }
   void note_status(hipStream_t s, const double* resid = nullptr, const double* S = nullptr, int k = 0) {
     if (!fail) {
-      SIPX_HIP(hipMalloc((void**)&fail, sizeof(int)));
-      this->mem.owned.push_back(fail);
+      fail = this->template alloc<int>(1);
       SIPX_HIP(hipHostMalloc((void**)&fail_host, sizeof(int), hipHostMallocDefault));
       SIPX_HIP(hipEventCreateWithFlags(&fail_ev, hipEventDisableTiming));
     }

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "device_memory.h"
 #include "dwt.h"
 #include "learn.h"
 #include "sipx_common.h"
@@ -324,22 +325,18 @@ void blas_ok(rocblas_status r, const char* what) {
 
 // every device buffer and library handle of one call, released on any exit
 struct Arena {
-  std::vector<void*> bufs;
+  DeviceMemory mem;      // (first: freed after the handles below are gone)
   rocblas_handle blas = nullptr;
   hipfftHandle plan = 0;
   bool has_plan = false;
   template <typename Q>
   Q* get(long long count) {
-    void* p = nullptr;
-    SIPX_HIP(hipMalloc(&p, sizeof(Q) * (size_t)std::max<long long>(count, 1)));
-    bufs.push_back(p);
-    return (Q*)p;
+    return mem.alloc<Q>((size_t)std::max<long long>(count, 1), Mem::NoFill);
   }
   ~Arena() {
     (void)hipDeviceSynchronize();
     if (has_plan) hipfftDestroy(plan);
     if (blas) rocblas_destroy_handle(blas);
-    for (void* p : bufs) (void)hipFree(p);
   }
 };
 

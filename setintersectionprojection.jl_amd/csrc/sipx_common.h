@@ -84,8 +84,6 @@ struct LaunchObserver {
 // the observer of the calling host thread (a context is driven by one thread at a time); nullptr: nothing is recorded
 const LaunchObserver*& launch_observer();
 
-// device bytes allocated on behalf of the context the calling thread is building (nullptr: not counted)
-long long*& alloc_tally();
 struct ObsScope {
   const LaunchObserver* o;
   int kid;
