@@ -61,6 +61,28 @@ def test_parity_every_key(sipx, TF, n, nt):
     check(got, ref, TF, mg)
 
 
+WAVELET_GRID = (200, 200)        # square (wavelet_l1 is 0 otherwise, as in the reference), L = 3, off the powers of two
+
+
+@pytest.mark.parametrize("TF", [np.float32, np.float64])
+def test_wavelet_l1_off_a_power_of_two(sipx, TF):
+    """200 x 200 (L = 3): two levels of axis passes whose half-lengths 100 and 50 are no multiple of the strided run length, the
+    second through the compact boxes, then the one-workgroup kernel on 50 x 50 -- per image, against the float64 restatement of
+    the transform within check()'s bound for this key.  On 200 x 120 the key is 0: the reference observes it on square grids
+    only (constraint_learning_by_observation.jl:67,113), and so does the learner."""
+    from tests import dwt_ref
+    n = WAVELET_GRID
+    m = images(3, n, TF)
+    got = sipx.constraint_learning_by_obseration(sipx.compgrid(H, n), m, keys=["wavelet_l1"])
+    assert set(got) == {"wavelet_l1"} and got["wavelet_l1"].shape == (3,) and got["wavelet_l1"].dtype == TF
+    ref = np.array([np.abs(dwt_ref.dwt_vec(img.reshape(-1, order="F"), n)).sum() for img in m])
+    assert np.all(ref > 0)
+    assert np.allclose(got["wavelet_l1"], ref, rtol=2e-6 if TF == np.float32 else 1e-12, atol=0), (got["wavelet_l1"], ref)
+    n = (200, 120)
+    got = sipx.constraint_learning_by_obseration(sipx.compgrid(H, n), images(3, n, TF), keys=["wavelet_l1"])
+    assert np.array_equal(got["wavelet_l1"], np.zeros(3, TF))
+
+
 def _same(a, b):
     assert set(a) == set(b)
     for k in a:

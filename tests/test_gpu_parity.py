@@ -303,6 +303,34 @@ def test_library_backed_projectors(sipx, TF):
             assert np.linalg.matrix_rank(S.astype(np.float64), tol=1e-3 * np.linalg.norm(S)) <= 3
 
 
+@pytest.mark.parametrize("TF", [np.float32, np.float64])
+@pytest.mark.parametrize("n", [(15, 12, 9), (30, 21), (6, 5), (3, 8), (2, 9), (5, 4, 3)], ids=lambda n: "x".join(map(str, n)))
+def test_l1_ball_behind_the_dft_on_small_and_odd_grids(sipx, monkeypatch, TF, n):
+    """The DFT-folded l1 ball alone where the bookkeeping of the half spectrum changes: odd leading dimensions (no Nyquist plane,
+    another count of self-conjugate bins), n1 = 4 and 5 at the edge of the real route, n1 < 4 (always the complex route).  Through
+    the real transform and, where the real one is the default, through the complex one; against the oracle's projector within
+    the bounds of test_library_backed_projectors.  A model inside the ball comes back bit for bit."""
+    tol = 2e-5 if TF == np.float32 else 1e-10
+    g = sipx.compgrid(tuple(1.0 for _ in n), n)
+    go = O.compgrid(tuple(1.0 for _ in n), n)
+    N = int(np.prod(n))
+    v = np.random.default_rng(31 + N).standard_normal(N).astype(TF)
+    a1 = float(np.abs(np.fft.fftn(v.reshape(n, order="F").astype(np.float64), norm="ortho")).sum())
+    ref = O.get_projector(O.set_definitions("l1", "DFT", 0.0, 0.4 * a1, ("matrix", "")), TF, go)(v.copy()).astype(np.float64)
+    assert np.linalg.norm(ref - v) > 0.1 * np.linalg.norm(v)                         # the set is active
+    for real in ((None, "0") if n[0] >= 4 else (None,)):
+        if real is None:
+            monkeypatch.delenv("SIPX_DFT_REAL", raising=False)
+        else:
+            monkeypatch.setenv("SIPX_DFT_REAL", real)
+        w = sipx.Projector(sipx.set_definitions("l1", "DFT", 0.0, 0.4 * a1, ("matrix", "")), g, TF)(v.copy())
+        err = np.linalg.norm(w.astype(np.float64) - ref) / np.linalg.norm(ref)
+        print(f"l1 DFT n={n} {np.dtype(TF).name} real={real}: rel. l2 error {err:.3e}")
+        assert w.dtype == TF and err <= tol, (n, real, err)
+        inside = sipx.Projector(sipx.set_definitions("l1", "DFT", 0.0, 2.0 * a1, ("matrix", "")), g, TF)(v.copy())
+        assert np.array_equal(inside, v), (n, real)
+
+
 # ---- one phase-level iteration in lock-step with the oracle -------------------------------------
 @pytest.mark.parametrize("TF", [np.float32, np.float64])
 @pytest.mark.parametrize("n,h", GRIDS[:3])

@@ -1,8 +1,10 @@
 """Wavelet-domain sets on the device (TD_OP = "wavelet", sipx.h SIPX_TRANSFORM_WAVELET): the db4 transform of
-kernels_dwt.hip against the float64 numpy restatement (tests/dwt_ref.py, pinned to PyWavelets by tests/test_wavelet_cpu.py),
-the projectors x -> W' P(W x) against the oracle's projectors behind the restatement, and whole solves (single level,
+kernels_dwt.hip against the float64 numpy restatement (tests/dwt_ref.py, pinned to PyWavelets by tests/test_wavelet_cpu.py)
+on powers of two and on EDGE_SHAPES (plan() says which launches a grid takes; tests/test_dwt_passes_cpu.py), the projectors x -> W' P(W x) against the oracle's projectors behind the restatement, and whole solves (single level,
 multilevel, two ranks sharing one GPU, full size) against the oracle with the wavelet closure substituted into P_sub."""
+import functools
 import os
+import re
 
 import numpy as np
 import pytest
@@ -15,30 +17,75 @@ pytestmark = pytest.mark.gpu
 
 FEAS_TOL = 1e-4
 SHAPES = [(16, 8), (32, 24), (128, 128), (8, 8, 4), (16, 16, 8), (9, 7), (64, 64, 32), (256, 128)]
+# grids off the powers of two, every dimension divisible by 2^L: half-lengths that are no multiple of the run lengths RC and RS
+# (the partial last run of a thread), axes shorter than the filter inside a pass kernel, levels >= 2 through the compact boxes,
+# grids on which no level fits the one-workgroup kernel.  tests/test_dwt_passes_cpu.py holds the list to these paths with plan()
+EDGE_SHAPES = [(202, 30), (404, 60), (200, 120), (2, 2050), (2050, 2), (6, 684), (690, 6), (34, 18, 10), (36, 20, 12),
+               (72, 40, 24), (128, 128, 4), (2, 2, 1026)]
+KERNELS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "setintersectionprojection.jl_amd", "csrc",
+                       "kernels_dwt.hip")
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_constants():
+    """RC, RS (outputs per thread along the contiguous / a strided axis) and SMALL (the one-workgroup box), as kernels_dwt.hip
+    defines them."""
+    with open(KERNELS, encoding="utf-8") as f:
+        src = f.read()
+    return {k: int(re.search(r"^constexpr int %s = (\d+);" % k, src, re.M).group(1)) for k in ("RC", "RS", "SMALL")}
+
+
+def plan(n):
+    """The launches dwt_forward / dwt_inverse take on the grid n: per level ("pass" | "small", ((m, h % R), ...)) with, per axis,
+    the length m of the level's box and the remainder of its half-length h = m / 2 by the run length of that axis' pass kernel.
+    A level is "small" from the first box of at most SMALL entries on (first_small)."""
+    k = kernel_constants()
+    b, out = [int(v) for v in n], []
+    for _ in range(R.levels(n)):
+        kind = "small" if int(np.prod(b)) <= k["SMALL"] else "pass"
+        out.append((kind, tuple((m, (m // 2) % (k["RC"] if a == 0 else k["RS"])) for a, m in enumerate(b))))
+        b = [m // 2 for m in b]
+    return out
 
 
 def _tol(TF, scale):
     return (2e-6 if TF == np.float32 else 1e-13) * max(1.0, scale)
 
 
+def _check_transform(sipx, TF, n, x, ref, inv_ref):
+    """forward against the restatement, the inverse of the restatement's coefficients, the round trip, the norm, determinism"""
+    N = int(np.prod(n))
+    c = sipx.dwt(x, n)
+    assert c.dtype == TF and c.shape == (N,)
+    assert np.abs(c - ref).max() <= _tol(TF, np.abs(ref).max()), n
+    xi = sipx.dwt(ref.astype(TF), n, inverse=True)
+    assert np.abs(xi - inv_ref).max() <= _tol(TF, np.abs(x).max()) * 4, n
+    back = sipx.dwt(c, n, inverse=True)
+    assert np.abs(back.astype(np.float64) - x).max() <= _tol(TF, np.abs(x).max()) * 4, n
+    nx, nc = np.linalg.norm(x.astype(np.float64)), np.linalg.norm(c.astype(np.float64))
+    assert abs(nc - nx) <= (1e-6 if TF == np.float32 else 1e-13) * nx, n
+    assert np.array_equal(sipx.dwt(x, n), c), n                        # deterministic: same bits
+    assert np.array_equal(sipx.dwt(c, n, inverse=True), back), n
+
+
 @pytest.mark.parametrize("TF", [np.float32, np.float64])
 def test_dwt_matches_restatement(sipx, TF):
     rng = np.random.default_rng(5)
     for n in SHAPES:
-        N = int(np.prod(n))
-        x = rng.standard_normal(N).astype(TF)
+        x = rng.standard_normal(int(np.prod(n))).astype(TF)
         ref = R.dwt_vec(x, n)
-        c = sipx.dwt(x, n)
-        assert c.dtype == TF and c.shape == (N,)
-        assert np.abs(c - ref).max() <= _tol(TF, np.abs(ref).max()), n
-        xi = sipx.dwt(ref.astype(TF), n, inverse=True)
-        assert np.abs(xi - R.dwt_vec(ref.astype(TF), n, inverse=True)).max() <= _tol(TF, np.abs(x).max()) * 4, n
-        back = sipx.dwt(c, n, inverse=True)
-        assert np.abs(back.astype(np.float64) - x).max() <= _tol(TF, np.abs(x).max()) * 4, n
-        nx, nc = np.linalg.norm(x.astype(np.float64)), np.linalg.norm(c.astype(np.float64))
-        assert abs(nc - nx) <= (1e-6 if TF == np.float32 else 1e-13) * nx, n
-        assert np.array_equal(sipx.dwt(x, n), c), n                        # deterministic: same bits
-        assert np.array_equal(sipx.dwt(c, n, inverse=True), back), n
+        _check_transform(sipx, TF, n, x, ref, R.dwt_vec(ref.astype(TF), n, inverse=True))
+
+
+@pytest.mark.parametrize("TF", [np.float32, np.float64])
+@pytest.mark.parametrize("n", EDGE_SHAPES, ids=lambda n: "x".join(map(str, n)))
+def test_dwt_matches_restatement_on_edge_grids(sipx, TF, n):
+    """The same checks with the same tolerances on EDGE_SHAPES: ragged runs, axes of 2, 4 and 6 inside the pass kernels, compact
+    boxes with strides that differ between source and destination, grids without a one-workgroup level."""
+    assert all(v % (1 << R.levels(n)) == 0 for v in n)
+    x = np.random.default_rng(5 + int(np.prod(n))).standard_normal(int(np.prod(n))).astype(TF)
+    ref = R.dwt_vec(x, n)
+    _check_transform(sipx, TF, n, x, ref, R.dwt_vec(ref.astype(TF), n, inverse=True))
 
 
 def _want(st, lo, hi, v, n):
@@ -56,27 +103,39 @@ def _want(st, lo, hi, v, n):
     return R.dwt_vec(c, n, inverse=True)
 
 
+def _check_projectors(sipx, TF, n, rng):
+    tol = 2e-5 if TF == np.float32 else 1e-11
+    N = int(np.prod(n))
+    g = sipx.compgrid((1.0,) * len(n), n)
+    v = rng.standard_normal(N).astype(TF)
+    c = R.dwt_vec(v, n)
+    a1, a2 = float(np.abs(c).sum()), float(np.linalg.norm(c))
+    for st, lo, hi in [("l1", 0.0, 0.3 * a1), ("bounds", -0.4, 0.6), ("cardinality", 0, N // 5), ("l2", 0.0, 0.5 * a2),
+                       ("annulus", 1.2 * a2, 2.0 * a2)]:
+        want = _want(st, lo, hi, v.astype(np.float64), n)
+        got = sipx.host.Projector(sipx.set_definitions(st, "wavelet", lo, hi, ("matrix", "")), g, TF)(v.copy())
+        if st == "cardinality" and TF == np.float32:
+            # the k-th largest coefficient is decided on TF-rounded coefficients: allow a swap of near-equal entries
+            assert np.linalg.norm(got.astype(np.float64) - want) <= 1e-3 * np.linalg.norm(want), (n, st)
+        else:
+            assert np.abs(got.astype(np.float64) - want).max() <= tol * max(1.0, np.abs(want).max()), (n, st)
+    big = sipx.set_definitions("l1", "wavelet", 0.0, 2.0 * a1, ("matrix", ""))     # inside the ball: v bit for bit
+    assert np.array_equal(sipx.host.Projector(big, g, TF)(v.copy()), v), n
+
+
 @pytest.mark.parametrize("TF", [np.float32, np.float64])
 def test_wavelet_domain_projectors(sipx, TF):
     rng = np.random.default_rng(23)
-    tol = 2e-5 if TF == np.float32 else 1e-11
     for n in ((16, 16, 8), (32, 24), (64, 64, 32), (9, 7)):
-        N = int(np.prod(n))
-        g = sipx.compgrid((1.0,) * len(n), n)
-        v = rng.standard_normal(N).astype(TF)
-        c = R.dwt_vec(v, n)
-        a1, a2 = float(np.abs(c).sum()), float(np.linalg.norm(c))
-        for st, lo, hi in [("l1", 0.0, 0.3 * a1), ("bounds", -0.4, 0.6), ("cardinality", 0, N // 5), ("l2", 0.0, 0.5 * a2),
-                           ("annulus", 1.2 * a2, 2.0 * a2)]:
-            want = _want(st, lo, hi, v.astype(np.float64), n)
-            got = sipx.host.Projector(sipx.set_definitions(st, "wavelet", lo, hi, ("matrix", "")), g, TF)(v.copy())
-            if st == "cardinality" and TF == np.float32:
-                # the k-th largest coefficient is decided on TF-rounded coefficients: allow a swap of near-equal entries
-                assert np.linalg.norm(got.astype(np.float64) - want) <= 1e-3 * np.linalg.norm(want), (n, st)
-            else:
-                assert np.abs(got.astype(np.float64) - want).max() <= tol * max(1.0, np.abs(want).max()), (n, st)
-        big = sipx.set_definitions("l1", "wavelet", 0.0, 2.0 * a1, ("matrix", ""))     # inside the ball: v bit for bit
-        assert np.array_equal(sipx.host.Projector(big, g, TF)(v.copy()), v), n
+        _check_projectors(sipx, TF, n, rng)
+
+
+@pytest.mark.parametrize("TF", [np.float32, np.float64])
+@pytest.mark.parametrize("n", [(200, 120), (72, 40, 24), (34, 18, 10), (2050, 2)], ids=lambda n: "x".join(map(str, n)))
+def test_wavelet_domain_projectors_on_edge_grids(sipx, TF, n):
+    """The five sets behind the transform where its passes take ragged runs; the model inside the l1 ball comes back bit for bit
+    through the gated inverse of those launches."""
+    _check_projectors(sipx, TF, n, np.random.default_rng(23 + int(np.prod(n))))
 
 
 def _wavelet_closure(n, r, TF):
@@ -121,17 +180,19 @@ SEPARATED = {("3d-32x32x16", "f64"): 2e-3}
 
 
 @pytest.mark.parametrize("TF", [np.float32, np.float64])
-@pytest.mark.parametrize("case", ["c1-compass-128", "3d-32x32x16"])
+@pytest.mark.parametrize("case", ["c1-compass-128", "3d-32x32x16", "3d-72x40x24"])
 def test_wavelet_solve_matches_oracle(sipx, TF, case):
-    """BASELINE config 1's compass crop (128^2, L = 7) with {bounds, l1 behind the wavelet at 0.5 ||W m||_1}, and a 3-D grid
-    with {bounds, l1 on D_z, l1 behind the wavelet}: the criteria of test_gpu_parity.py::test_parsdmm_matches_oracle."""
+    """BASELINE config 1's compass crop (128^2, L = 7) with {bounds, l1 behind the wavelet at 0.5 ||W m||_1}, and 3-D grids
+    with {bounds, l1 on D_z, l1 behind the wavelet} -- 32 x 32 x 16, and 72 x 40 x 24 (L = 3: two levels of ragged axis passes,
+    the second through the compact boxes, then the one-workgroup kernel on 18 x 10 x 6): the criteria of
+    test_gpu_parity.py::test_parsdmm_matches_oracle."""
     if case.startswith("c1"):
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "c1_compass_128_m.npy")
         m = np.load(path).astype(TF).reshape(-1, order="F")
         n, h, dz = (128, 128), (25.0, 6.0), False
         assert m.size == 128 * 128
     else:
-        n, h, dz = (32, 32, 16), (25.0, 25.0, 25.0), True
+        n, h, dz = tuple(int(v) for v in case[3:].split("x")), (25.0, 25.0, 25.0), True
         m = model(n, TF, seed=31)
     S, Oq = _problems(sipx, n, h, TF, m, 60, dz)
     gs, os_, Ps, As, props, AtAs = S
