@@ -242,9 +242,44 @@ int sipx_finalize_dev(sipx_ctx* ctx, const void* m, const double* rho_ini, int n
 int sipx_reset_dev(sipx_ctx* ctx, const void* m, const double* rho_ini, int n_rho, double gamma_ini, int zero_ini_guess,
                    const void* x0, const void* const* l0, const void* const* y0, double* feasibility_initial);
 int sipx_download_dev(sipx_ctx* ctx, void* x, void* const* l, void* const* y);
+
+/* ---- new vectors for a set of a context that stays alive ----
+ * The reference's application examples learn their constraints once, build one list of sets and project many images through it;
+ * the last set is a data-fit box LBD <= A x <= UBD around the current image and between images only that projector is replaced:
+ * P_sub[end] = x -> project_bounds!(x, LBD, UBD) (examples/Indonesia_desaturation/image_desaturation_by_constraint_learning.jl:264,
+ * examples/Ecuador_denoising_deblurring_inpainting/denoising_deblurring_inpainting_by_constraint_learning_SA.jl:302).
+ * sipx_set_data replaces lb / ub of set `set` (the index sipx_add_set returned) by host TF vectors, sipx_set_data_dev by TF vectors
+ * in device memory of the context's GPU; a NULL pointer keeps that vector.  Lengths, order and meaning are those of sipx_add_set:
+ *   SIPX_PROJ_BOUNDS_VEC, transform NONE, mode WHOLE:  TF[M_i] in the reference's row order
+ *   SIPX_PROJ_BOUNDS_VEC, transform NONE, mode FIBER:  TF[TD_n[dir]]
+ *   SIPX_PROJ_HISTOGRAM:                               TF[M_i], ascending (unchecked, as in sipx_add_set)
+ * behind every operator sipx_add_set takes for these kinds (SIPX_OP_CSC with banded or matrix-free A'A included; per-fiber bounds
+ * need a built-in operator).
+ * REFUSED, with a message that names the way out (build a new context): every other kind -- scalars, vector bounds behind the DCT,
+ * the DFT mask, subspace bases --, the distance term, an index out of range, and a context with a communicator, a slab
+ * decomposition, set ownership or Minkowski components.  A refused call changes nothing.
+ * WHEN.  From the moment sipx_add_set returned the index.  Before sipx_finalize(_dev) the call replaces what sipx_add_set was given
+ * and finalize uses the latest data, so a first build can take its vectors from device memory (sipx_add_set still wants lb and ub:
+ * placeholders of the right length will do).  On a finalized context the device arrays are overwritten in place: nothing is
+ * allocated, no handle, plan, stream or event is created.
+ * CONTRACT.  sipx_set_data* followed by sipx_reset(_dev) leaves the context in the state sipx_finalize leaves a new context built
+ * with that data; the solve that follows returns the same bits.  (Without the reset the state of a solve in progress is undefined:
+ * the host form stages through scratch of the engine.)
+ * BYTES.  The host form on a finalized context adds the vectors it was given to the host-to-device count of sipx_io_bytes (before
+ * sipx_finalize the upload, and its count, are finalize's); the device form adds nothing.
+ * ORDERING of the device form: as for sipx_reset_dev / sipx_download_dev.  The engine stream waits for an event recorded on the
+ * caller's stream (sipx_set_caller_stream) when the call is made, so work queued there before the call is seen; after the transfer
+ * it records an event the caller's stream waits for, so work queued there afterwards may overwrite the buffers.  The host waits
+ * for nothing.  The host form returns when the caller's arrays have been read.
+ * Both vectors of a call move in one launch of the transfer kernel of the device-resident calls: a whole-mode vector through one
+ * unpack segment per operator block, per-fiber bounds through a broadcast segment (the padded entry of a row takes the bound of its
+ * coordinate along dir) -- bit for bit what sipx_add_set's expansion on the host gives. */
+int sipx_set_data(sipx_ctx* ctx, int set, const void* lb, const void* ub);
+int sipx_set_data_dev(sipx_ctx* ctx, int set, const void* lb, const void* ub);
 /* Bytes of the N-sized transfers between host and device that sipx_finalize, sipx_reset and sipx_download (and their _dev forms)
  * have made on this context since it was created or since the last call with reset != 0: m, x, l_i, y_i, bound vectors and
- * explicit A'A bands.  The _dev forms add nothing for m, x, l_i, y_i.  Either pointer may be NULL. */
+ * explicit A'A bands, and what sipx_set_data uploads.  The _dev forms add nothing for m, x, l_i, y_i, sipx_set_data_dev nothing
+ * at all.  Either pointer may be NULL. */
 int sipx_io_bytes(sipx_ctx* ctx, int64_t* host_to_device, int64_t* device_to_host, int reset);
 
 /* Multilevel (src/PARSDMM_multi_level.jl:61-83, src/interpolate_y_l.jl:16-94): warm start of a finalized context on a finer

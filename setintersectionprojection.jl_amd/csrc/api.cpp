@@ -95,6 +95,8 @@ int sipx_reset_dev(sipx_ctx* c, const void* m, const double* rho_ini, int n_rho,
 }
 int sipx_download_dev(sipx_ctx* c, void* x, void* const* l, void* const* y) { SIPX_TRY(c->e->download_dev(x, l, y)) }
 int sipx_set_caller_stream(sipx_ctx* c, void* stream) { SIPX_TRY(c->e->set_caller_stream(stream)) }
+int sipx_set_data(sipx_ctx* c, int set, const void* lb, const void* ub) { SIPX_TRY(c->e->set_data(set, lb, ub, false)) }
+int sipx_set_data_dev(sipx_ctx* c, int set, const void* lb, const void* ub) { SIPX_TRY(c->e->set_data(set, lb, ub, true)) }
 int sipx_io_bytes(sipx_ctx* c, int64_t* host_to_device, int64_t* device_to_host, int reset) {
   SIPX_TRY(c->e->io_bytes(host_to_device, device_to_host, reset))
 }

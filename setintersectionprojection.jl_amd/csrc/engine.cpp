@@ -222,6 +222,9 @@ struct SetState {
   T *y2 = nullptr, *l2 = nullptr;    // third pair of the one-sweep update (allocated by sipx_finalize, see sweep_launch)
   int snap = -1;                     // -1: no snapshot yet; 0: (y, l) is also the snapshot; 1: (y0, l0) is
   T *lb = nullptr, *ub = nullptr, *ata = nullptr;
+  int bmode = SIPX_MODE_WHOLE, bdir = 0;   // SIPX_PROJ_BOUNDS_VEC: one bound per row (WHOLE) or per coordinate along bdir (FIBER)
+  // vectors sipx_set_data_dev handed over before sipx_finalize, as given (device copies; finalize expands and frees them)
+  T *pend_lb = nullptr, *pend_ub = nullptr;
   int searches_done = 0;             // slab-decomposed l1 searches of this set so far (sizes the refinement rounds)
   int ext_kind = 0;                  // projector acting on a materialised vector (ext_proj.h)
   // Sharded solve: a rank / nuclear-norm set on the slices orthogonal to the last grid dimension is projected by ALL ranks,
@@ -451,9 +454,14 @@ class Engine : public EngineBase {
       assemble_Q();
       build_q_table();
       create_lane(P);
+      if (!comm_ && !ev_io_in_) set_caller_stream((void*)caller_);      // (the events of the device-resident calls: none is created later)
     });
     finalized_ = true;
     initial_feasibility(feasibility_initial);
+    for (auto& s : sets_) {                   // (read by now: the initial feasibility has waited for the engine stream)
+      mem_.release(s.pend_lb); mem_.release(s.pend_ub);
+      s.pend_lb = s.pend_ub = nullptr;
+    }
   }
 
   // step 1: the set list as the solve sees it (the distance term appended), what it allows, which decomposition it gets
@@ -888,7 +896,10 @@ class Engine : public EngineBase {
       s.spec.ub = s.host_ub.empty() ? nullptr : s.host_ub.data();
       s.spec.basis = s.host_basis.empty() ? nullptr : s.host_basis.data();
       s.ext = std::make_shared<ExtProj<T>>(s.spec, stream_);
-      if (s.ext_kind == EXT_HISTOGRAM) { s.host_lb.clear(); s.host_ub.clear(); }
+      if (s.ext_kind == EXT_HISTOGRAM) {
+        s.host_lb.clear(); s.host_ub.clear();
+        if (s.pend_lb || s.pend_ub) s.ext->set_data(s.pend_lb, s.pend_ub, true);
+      }
       s.host_basis.clear();
       s.host_basis.shrink_to_fit();
     }
@@ -942,8 +953,14 @@ class Engine : public EngineBase {
     }
     if (s.prox == SIPX_PROJ_BOUNDS_VEC) {
       s.lb = mem_.alloc<T>(s.Mpad); s.ub = mem_.alloc<T>(s.Mpad);
-      upload_rows(s, s.host_lb.data(), s.lb);
-      upload_rows(s, s.host_ub.data(), s.ub);
+      if (!s.pend_lb) upload_rows(s, s.host_lb.data(), s.lb);
+      if (!s.pend_ub) upload_rows(s, s.host_ub.data(), s.ub);
+      if (s.pend_lb || s.pend_ub) {          // (sipx_set_data_dev before sipx_finalize: the first build takes them from device memory)
+        IoArgs<T> A;
+        if (s.pend_lb) io_add_bounds(A, s, s.pend_lb, s.lb);
+        if (s.pend_ub) io_add_bounds(A, s, s.pend_ub, s.ub);
+        io_rows<T>(stream_, A, false, NB);
+      }
     }
     if (!dev_io_ && l0 && l0[i]) upload_rows_ranged(s, (const T*)l0[i], s.l);
     if (!dev_io_ && y0 && y0[i]) upload_rows_ranged(s, (const T*)y0[i], s.y);
@@ -2926,6 +2943,105 @@ class Engine : public EngineBase {
   }
 
   // ------------------------------------------------------------------------------------------
+  // sipx_set_data / sipx_set_data_dev: new vectors for a set that carries some -- element-wise or per-fiber bounds, the relaxed
+  // histogram -- in a context that stays alive.  The reference's application examples replace one projector of a list between
+  // images, P_sub[end] = x -> project_bounds!(x, LBD, UBD) (examples/Indonesia_desaturation/
+  // image_desaturation_by_constraint_learning.jl:264); here that is one launch of the transfer kernel into the arrays the set
+  // already has.  Before sipx_finalize the call replaces what sipx_add_set was given.  On a finalized context nothing is
+  // allocated and no stream or event is created; the new data holds from the next sipx_reset on (a solve in progress is given
+  // up: the host form stages through the engine's scratch).
+  long long data_len(const SetState<T>& s) const {
+    if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;
+    return G_.n[s.bdir] - ((s.nblk == 1 && s.dir[0] == s.bdir) ? 1 : 0);
+  }
+  // segments that take a bound vector as given (src: device memory) into the padded array of the set
+  void io_add_bounds(IoArgs<T>& A, const SetState<T>& s, const T* src, T* dev) {
+    if (s.bmode != SIPX_MODE_FIBER) { io_add_set(A, false, s, src, dev); return; }
+    if (A.nseg == IO_MAXSEG) {
+      io_rows<T>(stream_, A, false, NB);
+      A.nseg = 0;
+    }
+    io_seg_bcast<T>(A.seg[A.nseg++], G_, s.nblk == 1 ? s.dir[0] : -1, s.bdir, s.Mtrue, src, dev);      // (one block: configure_proj)
+  }
+  void set_data(int set, const void* lb, const void* ub, bool on_device) override {
+    const std::string what = on_device ? "sipx_set_data_dev" : "sipx_set_data";
+    const char* way_out = ": build a new context for that";
+    if (comm_ || slab_req_ || !owned_.empty())
+      throw std::runtime_error(what + " takes single-process contexts only, this one is sharded or slab-decomposed" + way_out);
+    const int nsets = finalized_ ? pp_n_ : (int)sets_.size();
+    if (set == nsets && !(finalized_ && feasibility_only_))
+      throw std::runtime_error(what + ": index " + std::to_string(set) + " is the distance term, which holds no vectors (its data is m: sipx_reset)");
+    if (set < 0 || set >= nsets)
+      throw std::runtime_error(what + ": set index " + std::to_string(set) + " out of range (" + std::to_string(nsets) + " sets)");
+    SetState<T>& s = sets_[set];
+    if (s.comp) throw std::runtime_error(what + " is not available for Minkowski sets" + way_out);
+    const bool bounds = !s.ext_kind && s.prox == SIPX_PROJ_BOUNDS_VEC, hist = s.ext_kind == EXT_HISTOGRAM;
+    if (!bounds && !hist)
+      throw std::runtime_error(what + ": set " + std::to_string(set) + " holds no replaceable vectors -- element-wise and per-fiber bounds "
+                               "(no transform) and the relaxed histogram do; scalars, vector bounds behind the DCT, the DFT mask and "
+                               "subspace bases are fixed at sipx_add_set" + way_out);
+    if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
+      throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
+    if (!lb && !ub) return;
+    SIPX_HIP(hipSetDevice(device_));
+    const T *LB = (const T*)lb, *UB = (const T*)ub;
+    const long long len = data_len(s);
+    const size_t bytes = (size_t)len * sizeof(T);
+    if (!finalized_) {
+      if (on_device) {                       // kept as given until sipx_finalize expands it; the caller may reuse its buffers
+        engine_after_caller();
+        if (LB && !s.pend_lb) s.pend_lb = mem_.alloc<T>((size_t)len, Mem::NoFill);
+        if (UB && !s.pend_ub) s.pend_ub = mem_.alloc<T>((size_t)len, Mem::NoFill);
+        if (LB) SIPX_HIP(hipMemcpyAsync(s.pend_lb, LB, bytes, hipMemcpyDeviceToDevice, stream_));
+        if (UB) SIPX_HIP(hipMemcpyAsync(s.pend_ub, UB, bytes, hipMemcpyDeviceToDevice, stream_));
+        caller_after_engine();
+        return;
+      }
+      auto take = [&](const T* src, std::vector<T>& host, T*& pend) {      // (uploaded, and counted, by sipx_finalize)
+        if (!src) return;
+        mem_.release(pend);
+        pend = nullptr;
+        if (bounds && s.bmode == SIPX_MODE_FIBER) expand_fiber_bounds(s, src, host);
+        else host.assign(src, src + len);
+      };
+      take(LB, s.host_lb, s.pend_lb);
+      take(UB, s.host_ub, s.pend_ub);
+      return;
+    }
+    if (on_device) {
+      // the engine stream behind the caller's and behind the set streams, which may still read the old vectors
+      engine_after_caller();
+      for (auto& o : sets_)
+        if (o.st && o.st != stream_ && o.ev) {
+          SIPX_HIP(hipEventRecord(o.ev, o.st));
+          SIPX_HIP(hipStreamWaitEvent(stream_, o.ev, 0));
+        }
+    } else {
+      if (lane_thr_.joinable()) lane_thr_.join();
+      SIPX_HIP(hipStreamSynchronize(stream_));
+      for (hipStream_t q : pool_) if (q && q != stream_) SIPX_HIP(hipStreamSynchronize(q));
+      if (lane_st_) SIPX_HIP(hipStreamSynchronize(lane_st_));
+      io_h2d_ += (long long)bytes * ((LB ? 1 : 0) + (UB ? 1 : 0));
+    }
+    if (hist) {
+      if (!s.ext) throw std::runtime_error("internal: histogram set without its projector");
+      s.ext->set_stream(stream_);
+      s.ext->set_data(LB, UB, on_device);
+    } else {
+      if (!on_device) {                      // one copy each into the engine's scratch, idle between solves
+        if (LB) { SIPX_HIP(hipMemcpyAsync(scr_v_, LB, bytes, hipMemcpyHostToDevice, stream_)); LB = scr_v_; }
+        if (UB) { SIPX_HIP(hipMemcpyAsync(scr_c_, UB, bytes, hipMemcpyHostToDevice, stream_)); UB = scr_c_; }
+      }
+      IoArgs<T> A;
+      if (LB) io_add_bounds(A, s, LB, s.lb);
+      if (UB) io_add_bounds(A, s, UB, s.ub);
+      io_rows<T>(stream_, A, false, NB);
+    }
+    if (on_device) caller_after_engine();
+    else SIPX_HIP(hipStreamSynchronize(stream_));      // (the caller's arrays have been read)
+  }
+
+  // ------------------------------------------------------------------------------------------
   // Whole solve: src/PARSDMM.jl:63-257 restated (serial path).  begin / step so a caller can advance the
   // solve iteration by iteration (bench warm-up + timed steps); sipx_parsdmm = begin + steps until done.
   void parsdmm_begin(const sipx_options* opt, sipx_log* log) override {
@@ -3484,6 +3600,17 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
   }
 
+  // per-fiber bounds, one per coordinate along s.bdir, as one bound per row of A_i in the reference's row order
+  void expand_fiber_bounds(const SetState<T>& s, const T* per_fiber, std::vector<T>& rows) const {
+    long long dims[3] = {G_.n[0], G_.n[1], G_.n[2]};
+    if (s.nblk == 1) dims[s.dir[0]] -= 1;
+    rows.resize(s.Mtrue);
+    long long r = 0;
+    for (long long k = 0; k < dims[2]; ++k)
+      for (long long j = 0; j < dims[1]; ++j)
+        for (long long i = 0; i < dims[0]; ++i, ++r) rows[r] = per_fiber[s.bdir == 0 ? i : (s.bdir == 1 ? j : k)];
+  }
+
   // projector part of a set descriptor: validation (the reference's error messages) + routing
   void configure_proj(SetState<T>& s, const sipx_set_desc* d) {
     s.prox = d->proj;
@@ -3554,20 +3681,11 @@ class Engine : public EngineBase {
         if (!d->lb || !d->ub) throw std::runtime_error("per-element bounds need lb and ub");
         if (mode == SIPX_MODE_SLICE)
           throw std::runtime_error("bound constraints per slice of a tensor currently not implemented, yet...");   // project_bounds!.jl:83
+        s.bmode = mode;
+        s.bdir = dir;
         if (mode == SIPX_MODE_FIBER) {      // bounds per fiber: expanded to one bound per row of A_i (reference order)
-          long long dims[3] = {G_.n[0], G_.n[1], G_.n[2]};
-          if (s.nblk == 1) dims[s.dir[0]] -= 1;
-          const T *LB = (const T*)d->lb, *UB = (const T*)d->ub;
-          s.host_lb.resize(s.Mtrue);
-          s.host_ub.resize(s.Mtrue);
-          long long r = 0;
-          for (long long k = 0; k < dims[2]; ++k)
-            for (long long j = 0; j < dims[1]; ++j)
-              for (long long i = 0; i < dims[0]; ++i, ++r) {
-                const long long c = dir == 0 ? i : (dir == 1 ? j : k);
-                s.host_lb[r] = LB[c];
-                s.host_ub[r] = UB[c];
-              }
+          expand_fiber_bounds(s, (const T*)d->lb, s.host_lb);
+          expand_fiber_bounds(s, (const T*)d->ub, s.host_ub);
           s.plo = T(1);                       // min(max(x, LB), UB): the fiber methods clip with LB first (project_bounds!.jl:47,65)
         } else {
           s.host_lb.assign((const T*)d->lb, (const T*)d->lb + s.Mtrue);

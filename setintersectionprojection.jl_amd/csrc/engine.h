@@ -40,6 +40,8 @@ struct EngineBase {
                          const void* const* l0, const void* const* y0, double* feasibility_initial) = 0;
   virtual void download_dev(void* x, void* const* l, void* const* y) = 0;
   virtual void set_caller_stream(void* stream) = 0;
+  // new bound / histogram vectors for a set of a context that stays alive (sipx_set_data, sipx_set_data_dev)
+  virtual void set_data(int set, const void* lb, const void* ub, bool on_device) = 0;
   virtual void io_bytes(int64_t* host_to_device, int64_t* device_to_host, int reset) = 0;
   virtual void parsdmm(const sipx_options* opt, sipx_log* log) = 0;
   virtual void parsdmm_begin(const sipx_options* opt, sipx_log* log) = 0;

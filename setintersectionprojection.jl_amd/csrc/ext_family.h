@@ -33,6 +33,8 @@ struct ExtImpl {
   virtual void project(T* v, bool feas, double* partials, T* maxpart, T* compact) = 0;
   virtual void set_stream(hipStream_t s) { stream = s; }
   virtual void reset() {}
+  // sipx_set_data: new lb / ub (nullptr keeps one), host or device memory
+  virtual void set_data(const T*, const T*, bool) { throw std::runtime_error("this projector holds no replaceable vectors (build a new context)"); }
   virtual void route_counts(long long out[4]) const { out[0] = out[1] = out[2] = out[3] = 0; }
   template <typename Q>
   Q* alloc(size_t count) { return mem.template alloc<Q>(count ? count : 1, Mem::NoFill); }

@@ -42,6 +42,9 @@ class ExtProj {
   void set_stream(hipStream_t s);
   // forget every warm start and counter: the projector behaves like a newly built one (sipx_reset)
   void reset();
+  // replaces the vectors the projector was built with (sipx_set_data): lb / ub as in ExtSpec, host or device memory, nullptr keeps
+  // that vector; queued on the projector's stream, nothing is allocated.  Kinds without such vectors throw.
+  void set_data(const T* lb, const T* ub, bool on_device);
   // device bytes the projector holds
   long long device_bytes() const;
 

@@ -52,6 +52,11 @@ void ExtProj<T>::set_stream(hipStream_t s) { impl_->set_stream(s); }
 template <typename T>
 void ExtProj<T>::reset() { if (impl_) impl_->reset(); }
 template <typename T>
+void ExtProj<T>::set_data(const T* lb, const T* ub, bool on_device) {
+  if (!impl_) throw std::runtime_error("this projector holds no replaceable vectors (build a new context)");
+  impl_->set_data(lb, ub, on_device);
+}
+template <typename T>
 long long ExtProj<T>::device_bytes() const { return impl_ ? impl_->mem.bytes() : 0; }
 template <typename T>
 void ExtProj<T>::route_counts(long long out[4]) const {

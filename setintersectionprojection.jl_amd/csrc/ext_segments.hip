@@ -187,6 +187,13 @@ struct HistogramProj : ExtImpl<T> {
     hipLaunchKernelGGL((k_hist_apply<T>), dim3(NB), dim3(BLOCK), 0, s, map, keys_out, idx_out, lb, ub, v);
     SIPX_HIP(hipGetLastError());
   }
+  // new bound vectors into the arrays of the old ones: one copy each, behind whatever the stream still does with them
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const size_t bytes = sizeof(T) * (size_t)map.L;
+    if (new_lb) SIPX_HIP(hipMemcpyAsync(lb, new_lb, bytes, kind, this->stream));
+    if (new_ub) SIPX_HIP(hipMemcpyAsync(ub, new_ub, bytes, kind, this->stream));
+  }
 };
 
 // x .= A*(A'*x)  or  A*((A'*A)\(A'*x))   project_subspace!.jl:15-19

@@ -31,6 +31,29 @@ __device__ __forceinline__ void io_walk(const IoSeg<T>& S, unsigned first, unsig
   }
 }
 
+// Broadcast segment: row r = (i, j, k) of the block takes rows[c], c its coordinate along the segment's direction.  With V = 4 the
+// four entries share j and k (d0 == n0, a multiple of four): along dimension 1 they are four consecutive values of `rows`, one
+// 16-byte load; along the others one value, read once (every lane of a row reads the same address: one request per wave and
+// row) and stored as 16 bytes.
+template <typename T, int V>
+__device__ __forceinline__ void io_walk_bcast(const IoSeg<T>& S, unsigned first, unsigned stride) {
+  const unsigned items = S.nrows / V, bdir = S.bdir - 1u;
+  for (unsigned it = first; it < items; it += stride) {
+    const unsigned r = it * V;
+    const unsigned t = r / S.d0, i = r - t * S.d0, k = t / S.d1, j = t - k * S.d1;
+    const unsigned e = i + S.n0 * (j + S.n1 * k);
+    Vec<T, V> x;
+    if (bdir == 0u) {
+      x = ldv<T, V>(S.rows + i);
+    } else {
+      const T b = S.rows[bdir == 1u ? j : k];
+#pragma unroll
+      for (int q = 0; q < V; ++q) x.v[q] = b;
+    }
+    stv<T, V>(S.pad + e, x);
+  }
+}
+
 template <typename T, bool PACK>
 __global__ __launch_bounds__(BLOCK) void k_io_rows(IoArgs<T> A) {
   int s = 0;                                                    // (uniform over the workgroup)
@@ -38,6 +61,11 @@ __global__ __launch_bounds__(BLOCK) void k_io_rows(IoArgs<T> A) {
   const IoSeg<T> S = A.seg[s];
   const unsigned nb = (s + 1 < A.nseg ? A.seg[s + 1].blk0 : A.nblocks) - S.blk0;
   const unsigned first = (blockIdx.x - S.blk0) * BLOCK + threadIdx.x, stride = nb * BLOCK;
+  if (!PACK && S.bdir) {
+    if (S.vec) io_walk_bcast<T, 4>(S, first, stride);
+    else io_walk_bcast<T, 1>(S, first, stride);
+    return;
+  }
   if (S.vec) io_walk<T, PACK, 4>(S, first, stride);
   else io_walk<T, PACK, 1>(S, first, stride);
 }
@@ -56,6 +84,17 @@ void io_seg_shape(IoSeg<T>& S, const Grid& g, int dir, long long nrows, const T*
   const bool rows_fit = S.linear ? (nrows % 4 == 0) : (S.d0 == S.n0 && S.n0 % 4 == 0);
   S.vec = (rows_fit && aligned16(rows, pad)) ? 1u : 0u;
   S.blk0 = 0;
+  S.bdir = 0;
+}
+
+template <typename T>
+void io_seg_bcast(IoSeg<T>& S, const Grid& g, int dir, int fdir, long long nrows, const T* rows, const T* pad) {
+  if (fdir < 0 || fdir > 2) throw std::runtime_error("internal: broadcast segment along an unknown direction");
+  io_seg_shape<T>(S, g, dir, nrows, rows, pad);
+  S.bdir = 1u + (unsigned)fdir;
+  // four entries of one grid row at a time: the rows of the block are whole grid rows, a multiple of four long (so nrows is one
+  // too); `rows` is then read at multiples of four (fdir == 0) or one value at a time
+  S.vec = (S.d0 == S.n0 && S.n0 % 4 == 0 && aligned16(pad) && (fdir != 0 || aligned16(rows))) ? 1u : 0u;
 }
 
 template <typename T>
@@ -86,6 +125,7 @@ void io_rows(hipStream_t s, IoArgs<T>& A, bool pack, int max_blocks) {
 
 #define SIPX_IO_INST(T)                                                                                   \
   template void io_seg_shape<T>(IoSeg<T>&, const Grid&, int, long long, const T*, const T*);             \
+  template void io_seg_bcast<T>(IoSeg<T>&, const Grid&, int, int, long long, const T*, const T*);        \
   template void io_rows<T>(hipStream_t, IoArgs<T>&, bool, int);
 SIPX_IO_INST(float)
 SIPX_IO_INST(double)

@@ -620,12 +620,14 @@ void resample_nn_padded(hipStream_t s, const long long* nc, const long long* nf,
 // One launch moves every vector of a device-resident call between the caller's buffers (row order) and the padded arrays
 // (kernels_io.hip).  A segment: `nrows` rows of one operator block (extents d0 x d1 x . of the rows, n0 x n1 x . of the grid);
 // linear: both layouts coincide; vec: 16-byte accesses fit; blk0: its first workgroup (io_rows deals them).
+// A BROADCAST segment (bdir = 1 + direction, unpack only; sipx_set_data): `rows` holds one value per coordinate along that
+// direction -- the per-fiber bounds of project_bounds!.jl:38-88 -- and the padded entry of every row takes rows[coordinate].
 constexpr int IO_MAXSEG = 32;     // segments held in the arguments of one launch
 template <typename T>
 struct IoSeg {
   T* rows;
   T* pad;
-  unsigned nrows, d0, d1, n0, n1, blk0, linear, vec;
+  unsigned nrows, d0, d1, n0, n1, blk0, linear, vec, bdir;
 };
 template <typename T>
 struct IoArgs {
@@ -636,6 +638,9 @@ struct IoArgs {
 // dir: direction of the block's difference operator, < 0 for a whole vector (identity, caller-supplied operator, m, x)
 template <typename T>
 void io_seg_shape(IoSeg<T>& S, const Grid& g, int dir, long long nrows, const T* rows, const T* pad);
+// the broadcast segment of one operator block (dir as above): its nrows valid entries take rows[coordinate along fdir]
+template <typename T>
+void io_seg_bcast(IoSeg<T>& S, const Grid& g, int dir, int fdir, long long nrows, const T* rows, const T* pad);
 // pack: rows <- pad; otherwise pad <- rows.  max_blocks: workgroups of the launch (at least one per segment)
 template <typename T>
 void io_rows(hipStream_t s, IoArgs<T>& A, bool pack, int max_blocks);

@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "sipx_kernel_stats_json", "sipx_comm_info", "sipx_device_bytes", "sipx_reset", "sipx_dwt",
     "sipx_learn_observations",
     "sipx_finalize_dev", "sipx_reset_dev", "sipx_download_dev", "sipx_set_caller_stream", "sipx_io_bytes",
-    "sipx_q_terms",
+    "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
@@ -453,6 +453,19 @@ class Projector:
         if self.kind == "histogram" and (self.lb.shape != (rows,) or self.ub.shape != (rows,)):
             raise SipxError(f"histogram bounds need {rows} sorted entries")
 
+    def data_len(self, op) -> Optional[int]:
+        """Entries of each vector sipx_set_data takes for this set behind operator `op`; None: the set holds no replaceable data."""
+        if self.kind == "histogram":
+            return int(op.shape[0])
+        if self.kind != "bounds_vec" or self.transform:
+            return None
+        if self.mode != MODES["fiber"]:
+            return int(op.shape[0])
+        n = list(op.n)
+        if op.kind in ("D_x", "D_y", "D_z"):
+            n[{"D_x": 0, "D_y": 1, "D_z": len(n) - 1}[op.kind]] -= 1
+        return int(n[self.dir])
+
     def desc(self, op: str, ncvx: bool) -> _SetDesc:
         d = _SetDesc()
         d.op, d.proj = OPS[op], PROJ[self.kind]
@@ -638,6 +651,7 @@ class Context:
         ha = (C.c_double * len(n))(*h)
         _chk(lib().sipx_create(C.byref(self.h), _dtype_code(self.TF), len(n), na, ha, device))
         self.rows: List[int] = []
+        self.data_len: List[Optional[int]] = []      # per set: entries of the vectors set_data takes (None: it has none)
         self.p = self.pp = 0
         self._keep = []
 
@@ -676,6 +690,7 @@ class Context:
         r = C.c_int64()
         _chk(lib().sipx_set_rows(self.h, rc, C.byref(r)))
         self.rows.append(int(r.value))
+        self.data_len.append(proj.data_len(op))
         return rc
 
     def set_q_mode(self, mode: str):
@@ -784,6 +799,35 @@ class Context:
         """The stream the caller's tensors are produced and consumed on (a hipStream_t as an integer, e.g.
         torch.cuda.current_stream().cuda_stream; 0 / None: the default stream).  The device-resident calls order themselves against it."""
         _chk(lib().sipx_set_caller_stream(self.h, C.c_void_p(int(stream or 0))))
+
+    def _data_want(self, i):
+        i = int(i)
+        return self.data_len[i] if 0 <= i < len(self.data_len) else None
+
+    def set_data(self, i, lb=None, ub=None):
+        """New bound / histogram vectors for set i from numpy arrays (sipx_set_data): lengths and meaning as at add_set, None keeps a
+        vector.  Before finalize they replace what add_set was given; on a finalized context they hold from the next reset on.
+        A set without such vectors, the distance term and an index out of range are refused by the engine."""
+        want, arrs = self._data_want(i), []
+        for name, a in (("lb", lb), ("ub", ub)):
+            if a is not None:
+                a = _check_array(name, a, self.TF, want)
+            arrs.append(a)
+        _chk(lib().sipx_set_data(self.h, int(i), _ptr(arrs[0]), _ptr(arrs[1])))
+
+    def set_data_dev(self, i, lb=None, ub=None):
+        """set_data with torch tensors on this context's GPU (sipx_set_data_dev), ordered against torch's current stream: what that
+        stream has queued before the call is seen, the tensors may be overwritten by work queued on it afterwards; no host wait."""
+        import torch
+        want, dev = self._data_want(i), None
+        for name, t in (("lb", lb), ("ub", ub)):
+            if t is not None:
+                _check_tensor(name, t, self.TF, t.shape[0] if want is None and t.dim() == 1 else want, dev)
+                dev = t.device
+        if dev is not None:
+            self.set_caller_stream(torch.cuda.current_stream(dev).cuda_stream)
+        _chk(lib().sipx_set_data_dev(self.h, int(i), None if lb is None else C.c_void_p(lb.data_ptr()),
+                                     None if ub is None else C.c_void_p(ub.data_ptr())))
 
     def io_bytes(self, reset=False):
         """(host-to-device, device-to-host) bytes of the N-sized transfers finalize, reset and download have made (sipx_io_bytes)."""
@@ -1190,6 +1234,19 @@ def _check_tensor_list(name, lst, TF, rows, device):
         _check_tensor(f"{name}[{i}]", t, TF, rows[i], device)
 
 
+def _check_array(name, a, TF, length):
+    """A numpy vector of the working precision; returned contiguous."""
+    if not isinstance(a, np.ndarray):
+        raise SipxError(f"{name} must be a numpy array (the device form takes torch tensors), not {type(a).__name__}")
+    if a.dtype.type != np.dtype(TF).type:
+        raise SipxError(f"{name} has dtype {a.dtype}: not the working precision ({np.dtype(TF).name})")
+    if a.ndim != 1:
+        raise SipxError(f"{name} must be 1-D, not of shape {a.shape}")
+    if length is not None and a.shape[0] != length:
+        raise SipxError(f"{name} has {a.shape[0]} entries, {length} are needed")
+    return np.ascontiguousarray(a)
+
+
 _one_runtime_checked = False
 
 
@@ -1288,6 +1345,226 @@ def PARSDMM_device(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x=None, l
         ctx.close()
     log.context_reused = reused
     return xo, log, lo, yo
+
+
+# --------------------------------------------------------------------------------------------------
+# one context, many projections, the data of a set replaced in between
+# --------------------------------------------------------------------------------------------------
+def _is_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+class Solver:
+    """A list of sets kept alive on the GPU: build once, then project model after model through it and replace the vectors of a
+    data-bearing set in between -- the loop of the reference's application examples, which learn their constraints once and give
+    every image its own data-fit box, P_sub[end] = x -> project_bounds!(x, LBD, UBD)
+    (examples/Indonesia_desaturation/image_desaturation_by_constraint_learning.jl:264).
+
+        S = Solver(AtA, TD_OP, set_Prop, P_sub, comp_grid, options, TF, device=None)
+        S.set_data(i, lb=None, ub=None)      # numpy arrays or CUDA tensors; holds until changed; None keeps a vector
+        x, log, l, y = S(m, x=None, l=None, y=None, outputs="all", out=None)
+        S.close()                            # also a context manager
+
+    The arguments are those of PARSDMM.  The first call builds the context (sipx_finalize), every later one is sipx_reset, the
+    solve and the download; data set before the first call goes in before finalize.  With a torch tensor m the call is the
+    device-resident one (PARSDMM_device): every argument is a tensor on m's device, the results are tensors there, torch's
+    current stream is the caller's stream.  set_data takes element-wise or per-fiber bounds (no transform) and the relaxed
+    histogram; a numpy vector is uploaded at every set_data (the array may be changed afterwards), a tensor is read on the device.
+    Every wrong argument raises SipxError before the library is touched.  log.context_reused tells whether the call found its
+    context built.  The Solver owns its context: the caches of PARSDMM / PARSDMM_device and clear_context_cache() do not know it."""
+
+    def __init__(self, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, TF, device=None):
+        self.TF = np.dtype(TF).type
+        _dtype_code(self.TF)
+        pp, p = len(P_sub), len(TD_OP)
+        if (not options.feasibility_only and p != pp + 1) or (options.feasibility_only and p != pp):
+            raise SipxError("TD_OP must hold one operator per set plus the identity of the distance term "
+                            "(output of PARSDMM_precompute_distribute)")
+        for i, P in enumerate(P_sub):
+            if not isinstance(P, Projector):
+                raise SipxError(f"P_sub[{i}] must be a Projector (the output of setup_constraints)")
+            if P.TF != self.TF:
+                raise SipxError(f"P_sub[{i}] was set up in {np.dtype(P.TF).name}, the Solver in {np.dtype(self.TF).name}")
+        if any(int(getattr(A, "component", 0)) for A in TD_OP):
+            raise SipxError("Solver: Minkowski sets are not taken (use PARSDMM)")
+        self.AtA, self.TD_OP, self.set_Prop, self.P_sub = AtA, list(TD_OP), set_Prop, list(P_sub)
+        self.comp_grid, self.options = comp_grid, options
+        self.feasibility_only = bool(options.feasibility_only)
+        n, _ = _grid(comp_grid)
+        self.N = int(np.prod(n))
+        self.rows = [int(A.shape[0]) for A in TD_OP]
+        self.device = None if device is None else int(device)
+        self.ctx: Optional[Context] = None
+        self.built = self.closed = False
+
+    # ---- argument checks (nothing here touches the library)
+    def _device_of(self, t):
+        """Index of the GPU a tensor lives on; refused when the Solver is bound to another one."""
+        idx = t.device.index
+        if idx is None:
+            import torch
+            idx = torch.cuda.current_device()
+        if self.device is not None and idx != self.device:
+            raise SipxError(f"the tensors live on cuda:{idx}, the Solver on cuda:{self.device}")
+        return idx
+
+    def _check_open(self):
+        if self.closed:
+            raise SipxError("this Solver has been closed")
+
+    def _context(self, device):
+        if self.ctx is None:
+            self.device = _default_device if device is None else device
+            ctx = Context(self.comp_grid, self.TF, self.device)
+            try:
+                for i, P in enumerate(self.P_sub):
+                    A = self.AtA[i] if self.AtA is not None else None
+                    ctx.add_set(self.TD_OP[i], P, self.set_Prop.ncvx[i], A, self.set_Prop.AtA_offsets[i] if A is not None else None)
+                ctx.set_q_mode(getattr(self.options, "Q_mode", "cds"))
+            except Exception:
+                ctx.close()
+                raise
+            self.ctx = ctx
+        return self.ctx
+
+    def set_data(self, i, lb=None, ub=None):
+        self._check_open()
+        if not isinstance(i, (int, np.integer)) or isinstance(i, bool):
+            raise SipxError(f"set_data: the set index must be an integer, not {type(i).__name__}")
+        i = int(i)
+        pp = len(self.P_sub)
+        if i == pp and not self.feasibility_only:
+            raise SipxError(f"set_data: index {i} is the distance term, which holds no vectors (its data is m)")
+        if not 0 <= i < pp:
+            raise SipxError(f"set_data: set index {i} out of range ({pp} sets)")
+        want = self.P_sub[i].data_len(self.TD_OP[i])
+        if want is None:
+            raise SipxError(f"set_data: set {i} ({self.set_Prop.tag[i][0]} on {self.set_Prop.tag[i][1]}) holds no replaceable vectors -- "
+                            "element-wise and per-fiber bounds (no transform) and the relaxed histogram do; build a new Solver for "
+                            "other data")
+        given = [(k, a) for k, a in (("lb", lb), ("ub", ub)) if a is not None]
+        if not given:
+            return
+        on_dev = [_is_tensor(a) for _, a in given]
+        if any(on_dev) and not all(on_dev):
+            raise SipxError("set_data: lb and ub must both be numpy arrays or both be tensors on the GPU")
+        if on_dev[0]:
+            for k, t in given:
+                _check_tensor(k, t, self.TF, want, None)
+            if len(given) == 2 and ub.device != lb.device:
+                raise SipxError(f"ub lives on {ub.device}, lb on {lb.device}")
+            device = self._device_of(given[0][1])
+            _check_one_hip_runtime()
+            fn = self._context(device).set_data_dev
+        else:
+            for k, a in given:
+                _check_array(k, a, self.TF, want)
+            fn = self._context(self.device).set_data
+        try:
+            fn(i, lb, ub)
+        except BaseException:
+            self.close()
+            raise
+
+    def __call__(self, m, x=None, l=None, y=None, outputs="all", out=None):
+        import time
+        t0 = time.perf_counter()
+        self._check_open()
+        if outputs not in ("all", "x"):
+            raise SipxError("outputs must be 'all' or 'x'")
+        opt, TF = self.options, self.TF
+        on_dev = _is_tensor(m)
+        if on_dev:
+            if _tensor_TF("m", m) != TF:
+                raise SipxError(f"m has dtype {m.dtype}: not the working precision ({np.dtype(TF).name})")
+            _check_tensor("m", m, TF, self.N, None)
+            dev = m.device
+            if x is not None:
+                _check_tensor("x", x, TF, self.N, dev)
+            for name, lst in (("l", l), ("y", y)):
+                if lst is not None:
+                    _check_tensor_list(name, lst, TF, self.rows, dev)
+            if out is not None:
+                if not isinstance(out, (list, tuple)) or len(out) != 3:
+                    raise SipxError("out must be (x, l, y): the result tensors (l, y may be None with outputs='x')")
+                if out[0] is not None:
+                    _check_tensor("out x", out[0], TF, self.N, dev)
+                for name, lst in (("out l", out[1]), ("out y", out[2])):
+                    if lst is not None and outputs == "all":
+                        _check_tensor_list(name, lst, TF, self.rows, dev)
+            device = self._device_of(m)
+        else:
+            if not isinstance(m, np.ndarray):
+                raise SipxError(f"m must be a numpy array or a torch tensor on a GPU, not {type(m).__name__}")
+            if out is not None:
+                raise SipxError("out takes preallocated tensors: for a numpy m pass x, which is overwritten in place")
+            if not (np.isrealobj(m) and (x is None or np.isrealobj(x))):
+                raise SipxError("input for PARSDMM is not real")                 # src/PARSDMM.jl:50-52
+            _check_array("m", m, TF, self.N)
+            for name, a in (("x", x),):
+                if a is not None and (_is_tensor(a) or np.shape(a) != (self.N,)):
+                    raise SipxError(f"{name} must be a numpy vector of {self.N} entries, like m")
+            for name, lst in (("l", l), ("y", y)):
+                if lst is not None and len(lst) and (len(lst) != len(self.rows) or any(_is_tensor(a) or np.shape(a) != (r,) for a, r in zip(lst, self.rows))):
+                    raise SipxError(f"{name} needs one numpy vector per term (sets plus the distance term) with {self.rows} entries")
+            device = self.device
+        zero = bool(opt.zero_ini_guess)
+        rho_ini = [float(TF(r)) for r in opt.rho_ini]
+        gamma = float(TF(opt.gamma_ini))
+        warm = (None, None, None) if zero else (x, l, y)
+        reused = self.built
+        try:
+            if on_dev:
+                import torch
+                _check_one_hip_runtime()
+                ctx = self._context(device)
+                if reused:
+                    ctx.reset_dev(m, rho_ini, gamma, zero, *warm)
+                else:
+                    ctx.feasibility_initial = ctx.finalize_dev(m, rho_ini, gamma, self.feasibility_only, zero, *warm)
+            else:
+                ctx = self._context(device)
+                if reused:
+                    ctx.reset(m, rho_ini, gamma, zero, *warm)
+                else:
+                    ctx.feasibility_initial = ctx.finalize(m, rho_ini, gamma, self.feasibility_only, zero, *warm)
+            self.built = True
+            t_init = time.perf_counter() - t0
+            log, _ = ctx.parsdmm(opt)
+            log.timing[TIMING_SECTIONS[0]] = t_init          # "initialization": PARSDMM_initialize (src/PARSDMM.jl:40)
+            if on_dev:
+                if out is None and x is not None:
+                    out = (x, None, None)                     # the reference overwrites the x argument in place
+                xo, lo, yo = ctx.download_dev(torch.device("cuda", self.device), want_ly=(outputs == "all"), out=out)
+            else:
+                xo, lo, yo = ctx.download(want_ly=(outputs == "all"), x_out=x)
+                if x is not None and xo is not x and isinstance(x, np.ndarray) and len(x) == len(xo):
+                    x[:] = xo
+                    xo = x
+        except BaseException:
+            self.close()
+            raise
+        log.context_reused = reused
+        return xo, log, lo, yo
+
+    def close(self):
+        self.closed = True
+        if self.ctx is not None:
+            self.ctx.close()
+            self.ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # --------------------------------------------------------------------------------------------------
