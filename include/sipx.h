@@ -52,9 +52,12 @@ enum {
   SIPX_PROJ_BOUNDS      = 0, /* project_bounds!(x, LB, UB) scalar bounds  (projectors/project_bounds!.jl:3-12)  */
   SIPX_PROJ_BOUNDS_VEC  = 1, /* mode WHOLE: per-element bounds lb/ub TF[M_i]           (project_bounds!.jl:14-25);
                                 mode FIBER: per-fiber bounds lb/ub TF[TD_n[dir]]       (project_bounds!.jl:38-88) */
-  SIPX_PROJ_L1          = 2, /* project_l1_Duchi!(x, pmax)                (projectors/project_l1_Duchi!.jl:21-52) */
-  SIPX_PROJ_L2          = 3, /* project_l2!(x, pmax)                      (projectors/project_l2!.jl:3-16) */
-  SIPX_PROJ_ANNULUS     = 4, /* project_annulus!(x, pmin, pmax)           (projectors/project_annulus!.jl:3-21) */
+  /* l1 ball, l2 ball, annulus.  mode WHOLE: the whole vector.  mode FIBER / SLICE (no counterpart in the reference; op identity,
+     D_x, D_y or D_z; no transform): every fiber along dir / slice orthogonal to dir of the array of shape TD_n is projected on
+     its own by the same rule, all segments with the scalar pmin / pmax; a 2-D grid has fibers only. */
+  SIPX_PROJ_L1          = 2, /* project_l1_Duchi!(x, pmax)                (projectors/project_l1_Duchi!.jl:21-52); WHOLE, FIBER, SLICE */
+  SIPX_PROJ_L2          = 3, /* project_l2!(x, pmax)                      (projectors/project_l2!.jl:3-16);        WHOLE, FIBER, SLICE */
+  SIPX_PROJ_ANNULUS     = 4, /* project_annulus!(x, pmin, pmax)           (projectors/project_annulus!.jl:3-21);   WHOLE, FIBER, SLICE */
   SIPX_PROJ_CARDINALITY = 5, /* project_cardinality!(x, k = pmax): whole vector, per fiber or per slice
                                 (projectors/project_cardinality!.jl:3-146) */
   SIPX_PROJ_PROX_L1     = 6, /* prox_l1!(x, pmax)                         (src/prox_l1!.jl:8-10) */

@@ -24,7 +24,7 @@ using SparseArrays
 using TimerOutputs
 import SetIntersectionProjection: log_type_PARSDMM, convert_options!
 
-export PARSDMM, release_contexts, constraint_learning_by_obseration
+export PARSDMM, release_contexts, constraint_learning_by_obseration, setup_constraints
 
 const libsipx = get(ENV, "SIPX_LIBRARY", "libsipx.so")
 
@@ -108,6 +108,39 @@ function projector_fields(c, TF)
     st == "histogram"   && return (10, 0.0, 0.0, convert(Vector{TF}, c.min), convert(Vector{TF}, c.max), Int32(0))
     st == "subspace"    && return (11, 0.0, 0.0, nothing, nothing, Int32(0))
     error("set type $st is not part of libsipx")
+end
+
+"""
+    setup_constraints(constraint, comp_grid, TF; segment_norms=false) -> (P_sub, TD_OP, set_Prop)
+
+The reference's `setup_constraints` (src/setup_constraints.jl:17-102).  With `segment_norms=true` it also takes l1, l2 and annulus
+sets with `app_mode = ("fiber", d)` or `("slice", d)` on the identity, D_x, D_y or D_z: libsipx projects every fiber / slice of the
+array of shape TD_n on its own, all with the scalar min / max (include/sipx.h, SIPX_PROJ_L1).  The reference has no such
+projector ("l1 and l2 constraints only available for matrix or tensor mode, currently"): without the keyword its error stays.
+The reference sets the operators and properties up for the whole-array form of such a set; the application mode is put back
+into the constraint its P_sub[i] captured -- where `PARSDMM` above reads it -- and into set_Prop.tag[i].  Such a P_sub[i] must
+not be called as a Julia function: it would project the whole array.
+"""
+function setup_constraints(constraint, comp_grid, TF; segment_norms::Bool=false)
+    ref = getfield(parentmodule(log_type_PARSDMM), :setup_constraints)
+    segment_norms || return ref(constraint, comp_grid, TF)
+    ndim = (length(comp_grid.n) == 3 && comp_grid.n[3] > 1) ? 3 : 2
+    modes = Dict{Int,Any}()
+    for (i, c) in enumerate(constraint)
+        (c.set_type in ("l1", "l2", "annulus") && c.app_mode[1] in ("fiber", "slice")) || continue
+        c.TD_OP in ("identity", "D_x", "D_y", "D_z") && c.custom_TD_OP[1] == [] ||
+            error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)")
+        ndim == 2 && c.app_mode[1] == "slice" &&
+            error("for 2D models, the mode of application for $(c.set_type) sets needs to be (fiber,x) or (fiber,z), or matrix for the whole array")
+        modes[i] = c.app_mode
+        c.app_mode = (ndim == 3 ? "tensor" : "matrix", "")
+    end
+    (P_sub, TD_OP, set_Prop) = ref(constraint, comp_grid, TF)
+    for (i, am) in modes
+        constraint[i].app_mode = am
+        set_Prop.tag[i] = (set_Prop.tag[i][1], set_Prop.tag[i][2], am[1], am[2])
+    end
+    return P_sub, TD_OP, set_Prop
 end
 
 "log.timing with the reference's seven section names, filled from the engine's accumulators (milliseconds)"

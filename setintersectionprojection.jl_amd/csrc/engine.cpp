@@ -3693,20 +3693,20 @@ class Engine : public EngineBase {
           s.plo = T(0);
         }
         break;
+      // l1, l2, annulus: the whole array through the engine's own two-pass search; per fiber / slice (a gap of the reference,
+      // setup_constraints.jl:65-67 "currently") on the materialised vector, every segment by the same rule (seg_norm.h)
       case SIPX_PROJ_L1:
-        if (mode != SIPX_MODE_WHOLE)
-          throw std::runtime_error("l1 and l2 constraints only available for matrix or tensor mode, currently");   // setup_constraints.jl:65-67
         if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
-        s.two_pass = true;
+        if (mode == SIPX_MODE_WHOLE) s.two_pass = true;
+        else ext(EXT_L1_SEG);
         break;
       case SIPX_PROJ_L2:
-        if (mode != SIPX_MODE_WHOLE)
-          throw std::runtime_error("l1 and l2 constraints only available for matrix or tensor mode, currently");
-        s.two_pass = true;
+        if (mode == SIPX_MODE_WHOLE) s.two_pass = true;
+        else ext(EXT_L2_SEG);
         break;
       case SIPX_PROJ_ANNULUS:
-        if (mode != SIPX_MODE_WHOLE) throw std::runtime_error("annulus constraints apply to the whole array");
-        s.two_pass = true;
+        if (mode == SIPX_MODE_WHOLE) s.two_pass = true;
+        else ext(EXT_ANNULUS_SEG);
         break;
       case SIPX_PROJ_CARDINALITY:
         if (mode == SIPX_MODE_WHOLE) { s.two_pass = true; need_idx_ = true; }

@@ -1,7 +1,7 @@
 // Private to the ext_*.hip units: what ExtProj<T> (ext_proj.h) forwards to, one object per family of projectors --
 //   ext_transform.hip  DFT mask, l1 and cardinality behind the DFT, DCT, DWT
 //   ext_rank.hip       slice / matrix rank, nuclear norm
-//   ext_segments.hip   cardinality per fiber / slice, relaxed histogram, subspace
+//   ext_segments.hip   cardinality, l1, l2 and annulus per fiber / slice (seg_norm.h), relaxed histogram, subspace
 // -- and what more than one family uses.
 #pragma once
 #define ROCBLAS_BETA_FEATURES_API 1
@@ -99,7 +99,7 @@ struct SegMap {
   long long SA, sSa, sSb;            // s -> (s % SA) * sSa + (s / SA) * sSb
   long long LA, LB, sTa, sTb, sTc;   // t = ta + LA * (tb + LB * tc) -> ta * sTa + tb * sTb + tc * sTc
 };
-__device__ __forceinline__ long long seg_addr(const SegMap& m, long long s, long long t) {
+__host__ __device__ __forceinline__ long long seg_addr(const SegMap& m, long long s, long long t) {
   const long long ta = t % m.LA, r = t / m.LA, tb = r % m.LB, tc = r / m.LB;
   return (s % m.SA) * m.sSa + (s / m.SA) * m.sSb + ta * m.sTa + tb * m.sTb + tc * m.sTc;
 }

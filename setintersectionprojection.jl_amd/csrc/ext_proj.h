@@ -5,7 +5,8 @@
 
 namespace sipx {
 
-enum { EXT_L1_DFT = 1, EXT_RANK = 2, EXT_NUCLEAR = 3, EXT_CARD_SEG = 4, EXT_HISTOGRAM = 5, EXT_SUBSPACE = 6, EXT_DFT_MASK = 7, EXT_DCT = 8, EXT_DWT = 9, EXT_CARD_DFT = 10 };
+enum { EXT_L1_DFT = 1, EXT_RANK = 2, EXT_NUCLEAR = 3, EXT_CARD_SEG = 4, EXT_HISTOGRAM = 5, EXT_SUBSPACE = 6, EXT_DFT_MASK = 7, EXT_DCT = 8, EXT_DWT = 9, EXT_CARD_DFT = 10,
+       EXT_L1_SEG = 11, EXT_L2_SEG = 12, EXT_ANNULUS_SEG = 13 /* l1 / l2 / annulus per fiber or slice */ };
 
 // What an ExtProj acts on: the valid extents `dims` (TD_n of the operator) inside the padded grid G (strides G.st),
 // split into segments by the application mode (whole array, fibers along `dir`, slices orthogonal to `dir`).

@@ -1,10 +1,12 @@
 // Projectors on the fibers, the slices or the whole of a materialised vector v that need no transform:
-//   cardinality per fiber / slice (one kernel), the relaxed histogram (hipCUB sort), the subspace projection (rocBLAS).
+//   cardinality per fiber / slice (one kernel), the l1 ball, the l2 ball and the annulus per fiber / slice (one kernel,
+//   seg_norm.h), the relaxed histogram (hipCUB sort), the subspace projection (rocBLAS).
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
 
 #include "ext_family.h"
+#include "seg_norm.h"
 
 namespace sipx {
 
@@ -160,6 +162,36 @@ struct CardSegProj : ExtImpl<T> {
   }
 };
 
+// l1 ball, l2 ball or annulus of every fiber / slice, all segments sharing the scalar min / max (seg_norm.h).  Nothing is kept
+// between calls: the call of the feasibility estimate and the one of the y update are independent, reset() has nothing to forget.
+template <typename T>
+struct NormSegProj : ExtImpl<T> {
+  SegMap map{};
+  SegNormPlan plan{};
+  NormSegProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    if (spec.mode != SIPX_MODE_FIBER && spec.mode != SIPX_MODE_SLICE)
+      throw std::runtime_error("segmented l1 / l2 / annulus sets need a fiber or slice mode");
+    if (spec.ndim == 2 && spec.mode != SIPX_MODE_FIBER)
+      throw std::runtime_error("for 2D models, the mode of application for l1, l2 and annulus sets needs to be (fiber,x) or "
+                               "(fiber,z), or matrix for the whole array");
+    if (spec.kind == EXT_L1_SEG && !((T)spec.pmax > T(0))) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
+    map = make_segmap(spec);
+    if (map.nseg < 1 || map.L < 1 || map.L >= (1ll << 31)) throw std::runtime_error("segmented l1 / l2 / annulus sets: empty or oversize segments");
+    plan = seg_norm_plan(map, (int)sizeof(T));
+  }
+  template <int KIND>
+  void launch(T* v) {
+    hipLaunchKernelGGL((k_seg_norm<T, KIND>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, this->stream, map, plan, v, (T)this->sp.pmin,
+                       (T)this->sp.pmax);
+  }
+  void project(T* v, bool, double*, T*, T*) override {
+    if (this->sp.kind == EXT_L1_SEG) launch<SEGN_L1>(v);
+    else if (this->sp.kind == EXT_L2_SEG) launch<SEGN_L2>(v);
+    else launch<SEGN_ANNULUS>(v);
+    SIPX_HIP(hipGetLastError());
+  }
+};
+
 template <typename T>
 struct HistogramProj : ExtImpl<T> {
   SegMap map{};
@@ -251,6 +283,7 @@ struct SubspaceProj : ExtImpl<T> {
 template <typename T>
 ExtImpl<T>* make_segment_family(const ExtSpec& spec, hipStream_t stream) {
   if (spec.kind == EXT_CARD_SEG) return new CardSegProj<T>(spec, stream);
+  if (spec.kind == EXT_L1_SEG || spec.kind == EXT_L2_SEG || spec.kind == EXT_ANNULUS_SEG) return new NormSegProj<T>(spec, stream);
   if (spec.kind == EXT_HISTOGRAM) return new HistogramProj<T>(spec, stream);
   return new SubspaceProj<T>(spec, stream);
 }

@@ -332,6 +332,13 @@ class Projector:
             if am[1] not in dirs:
                 raise SipxError(f"application mode {am!r}: direction must be one of {sorted(dirs)} on this grid")
             self.dir = dirs[am[1]]
+        if self.mode and st in ("l1", "l2", "annulus"):
+            # l1 / l2 / annulus per fiber or slice (csrc/seg_norm.h): on the array itself or behind D_x / D_y / D_z only
+            if constraint.TD_OP in SPECIAL_OPERATORS or constraint.TD_OP in ("DCT", "wavelet"):
+                raise SipxError(f"{st} sets behind the {constraint.TD_OP} apply to the whole array (matrix / tensor mode)")
+            if len(n) == 2 and self.mode == MODES["slice"]:
+                raise SipxError(f"for 2D models, the mode of application for {st} sets needs to be (fiber,x) or (fiber,z), "
+                                "or matrix for the whole array")
         self.lb = self.ub = self.basis = None
         self.basis_orth = False
         self.pmin = self.pmax = 0.0
@@ -534,8 +541,13 @@ def get_TD_operator(comp_grid, TD_type: str, TF):
     return A, False, False, TD_n, True
 
 
-def setup_constraints(constraint: List[set_definitions], comp_grid, TF):
-    """src/setup_constraints.jl:17-102 -> (P_sub, TD_OP, set_Prop)."""
+def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_norms=False):
+    """src/setup_constraints.jl:17-102 -> (P_sub, TD_OP, set_Prop).
+
+    segment_norms=True takes l1, l2 and annulus sets with app_mode ("fiber", d) / ("slice", d): every fiber along d (slice
+    orthogonal to d) of the array of shape TD_n is projected on its own, all with the scalar min / max, on the identity, D_x, D_y
+    or D_z.  The reference has no such projector ("only available for matrix or tensor mode, currently"); without the keyword its
+    error stays."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -547,8 +559,14 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF):
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
                             "define constraints per slice")
-        if c.set_type in ("l1", "l2") and c.app_mode[0] in ("slice", "fiber"):
+        if c.set_type in ("l1", "l2") and c.app_mode[0] in ("slice", "fiber") and not segment_norms:
             raise SipxError("l1 and l2 constraints only available for matrix or tensor mode, currently")
+        if c.set_type in ("l1", "l2", "annulus") and c.app_mode[0] in ("slice", "fiber"):
+            if not segment_norms:
+                raise SipxError("annulus constraints per fiber or slice need setup_constraints(..., segment_norms=True)")
+            cust0 = c.custom_TD_OP[0]
+            if c.TD_OP in ("TV", "D2D", "D3D", "D_xz") or not (isinstance(cust0, (tuple, list)) and len(cust0) == 0):
+                raise SipxError("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)")
         A, AtA_diag, dense, TD_n, banded = get_TD_operator(comp_grid, c.TD_OP, TF)
         cust = c.custom_TD_OP[0] if c.set_type != "subspace" else ()
         if not (isinstance(cust, (tuple, list)) and len(cust) == 0):          # setup_constraints.jl:70-72
