@@ -54,7 +54,16 @@ enum {
                                 mode FIBER: per-fiber bounds lb/ub TF[TD_n[dir]]       (project_bounds!.jl:38-88) */
   /* l1 ball, l2 ball, annulus.  mode WHOLE: the whole vector.  mode FIBER / SLICE (no counterpart in the reference; op identity,
      D_x, D_y or D_z; no transform): every fiber along dir / slice orthogonal to dir of the array of shape TD_n is projected on
-     its own by the same rule, all segments with the scalar pmin / pmax; a 2-D grid has fibers only. */
+     its own by the same rule; a 2-D grid has fibers only.  RADII: with lb = ub = NULL all segments take the scalar pmin / pmax.  With
+     ub = TF[nseg] segment s takes pmax = ub[s]; the annulus also takes lb = TF[nseg] as pmin of each (one of the two NULL: that side keeps
+     its scalar for every segment).  This needs no kind of its own: the vectors travel in lb / ub like per-fiber bounds.  Segment order:
+     s = sa + SA * sb, the lower remaining dimension fastest -- for a fiber set the array of shape "TD_n without the fiber's axis"
+     flattened column-major, for a slice set the coordinate along dir; nseg and this order are those of sipx_segment_norms.  An entry of
+     an l1 vector that is not > 0 is refused ("Radius of L1 ball is negative") by sipx_add_set and by the host form sipx_set_data.  A vector
+     that arrives from device memory (sipx_set_data_dev) cannot be checked: there a segment whose radius is not > 0 (NaN included) is set
+     to zero, the projection onto the ball of radius 0 -- a rule for device-supplied radii only; the kernel ends for every value.  A
+     vector whose entries are all equal gives the bits of the scalar set.  Contexts with a communicator, a slab decomposition or set
+     ownership refuse vector radii (use a scalar radius, or a single process). */
   SIPX_PROJ_L1          = 2, /* project_l1_Duchi!(x, pmax)                (projectors/project_l1_Duchi!.jl:21-52); WHOLE, FIBER, SLICE */
   SIPX_PROJ_L2          = 3, /* project_l2!(x, pmax)                      (projectors/project_l2!.jl:3-16);        WHOLE, FIBER, SLICE */
   SIPX_PROJ_ANNULUS     = 4, /* project_annulus!(x, pmin, pmax)           (projectors/project_annulus!.jl:3-21);   WHOLE, FIBER, SLICE */
@@ -97,7 +106,8 @@ typedef struct {
   int32_t op;        /* SIPX_OP_*   */
   int32_t proj;      /* SIPX_PROJ_* */
   double pmin, pmax; /* constraint[i].min / .max (set_definitions, src/SetIntersectionProjection.jl:142-149) */
-  const void* lb;    /* BOUNDS_VEC / HISTOGRAM: host TF vectors (see the kinds above), else NULL */
+  const void* lb;    /* BOUNDS_VEC / HISTOGRAM: host TF vectors (see the kinds above); L1 / L2 / ANNULUS in mode FIBER / SLICE: NULL or
+                        the radii per segment, TF[nseg]; else NULL */
   const void* ub;
   int32_t ncvx;      /* set_Prop.ncvx[i] (src/setup_constraints.jl:89-97) */
   int32_t reserved;  /* 0 */
@@ -256,6 +266,11 @@ int sipx_download_dev(sipx_ctx* ctx, void* x, void* const* l, void* const* y);
  *   SIPX_PROJ_BOUNDS_VEC, transform NONE, mode WHOLE:  TF[M_i] in the reference's row order
  *   SIPX_PROJ_BOUNDS_VEC, transform NONE, mode FIBER:  TF[TD_n[dir]]
  *   SIPX_PROJ_HISTOGRAM:                               TF[M_i], ascending (unchecked, as in sipx_add_set)
+ *   SIPX_PROJ_L1 / L2 / ANNULUS, mode FIBER / SLICE, built with a vector of radii:  TF[nseg]; ub = the radii (pmax of each segment),
+ *                                                      lb = the annulus' inner radii (refused for l1 / l2).  One copy per vector on the
+ *                                                      set's stream into the arrays the projector was built with.  The host form refuses
+ *                                                      an l1 radius that is not > 0; for the device form see SIPX_PROJ_L1.  A set built
+ *                                                      with scalars holds no replaceable vectors.
  * behind every operator sipx_add_set takes for these kinds (SIPX_OP_CSC with banded or matrix-free A'A included; per-fiber bounds
  * need a built-in operator).
  * REFUSED, with a message that names the way out (build a new context): every other kind -- scalars, vector bounds behind the DCT,
@@ -308,6 +323,19 @@ int sipx_apply_op(sipx_ctx* ctx, int op, const void* x, void* s);
 int sipx_apply_op_adj(sipx_ctx* ctx, int op, const void* v, void* t);
 /* in-place projector on a host vector of length len (src/projectors/project_X.jl) */
 int sipx_project(sipx_ctx* ctx, const sipx_set_desc* desc, void* v, int64_t len);
+/* The norms of the fibers / slices of A x: out[s] = ||segment s of A x||_1 (norm = 0) or _2 (norm = 1), TF[nseg], for op = identity, D_x,
+ * D_y or D_z, mode = SIPX_MODE_FIBER / SLICE and dir as in sipx_set_desc, on the 2-D or 3-D grid of the context (which needs no sets and no
+ * finalize).  nseg and the order of the segments are those of the per-segment radii (SIPX_PROJ_L1): what this call returns can be
+ * passed as ub / lb of such a set.  *nseg receives the count (may be NULL); with x = NULL or out = NULL only the count is returned.  The
+ * operator / mode combinations the sets refuse are refused here with the same messages.  A x comes from the engine's operator product
+ * into scratch of the call; one kernel then reads it once, with the tile mapping and the first-pass reduction of the projector -- float64
+ * sums in a fixed order, rounded to TF once, sqrt in float64 for l2.  CONTRACT: the numbers are the ones the projector compares with
+ * its radii, so radii observed on x make A x a point the projector does not write (l1, l2, annulus with lb = ub = observed); an all-zero
+ * segment gives exactly 0 (as an l1 radius that is refused: give such a segment any positive radius).  x, out: host memory; the _dev
+ * form takes both in device memory of the context's GPU, ordered like sipx_download_dev against the caller's stream (sipx_set_caller_stream),
+ * and nothing crosses PCIe.  Learning from several arrays is a loop with an element-wise maximum / minimum over the results. */
+int sipx_segment_norms(sipx_ctx* ctx, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg);
+int sipx_segment_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg);
 /* nearest-neighbour resampling of an array of shape nc to shape nf, the grid transfer of PARSDMM_multi_level:
  * out[k] = in[round(1 + (k-1)(nc-1)/(nf-1))] per axis (Interpolations.BSpline(Constant()) evaluated on
  * range(1, stop=nc, length=nf); src/PARSDMM_multi_level.jl:41-45,61-65, src/interpolate_y_l.jl:32-88) */

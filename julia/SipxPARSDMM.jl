@@ -98,6 +98,15 @@ function projector_fields(c, TF)
     end
     st == "bounds"      && !vecb && return (0, Float64(c.min), Float64(c.max), nothing, nothing, Int32(0))
     st == "bounds"      && return (1, 0.0, 0.0, convert(Vector{TF}, c.min), convert(Vector{TF}, c.max), Int32(0))
+    # l1 / l2 / annulus per fiber or slice with one radius per segment (setup_constraints(...; segment_norms=true)): the vectors travel
+    # in lb / ub like per-fiber bounds (include/sipx.h, SIPX_PROJ_L1); a scalar beside a vector is repeated
+    if st in ("l1", "l2", "annulus") && c.app_mode[1] in ("fiber", "slice") && (c.max isa AbstractVector || (st == "annulus" && c.min isa AbstractVector))
+        nseg = c.max isa AbstractVector ? length(c.max) : length(c.min)
+        ub = c.max isa AbstractVector ? convert(Vector{TF}, c.max) : fill(TF(c.max), nseg)
+        lb = st != "annulus" ? nothing : (c.min isa AbstractVector ? convert(Vector{TF}, c.min) : fill(TF(c.min), nseg))
+        st == "l1" && !all(ub .> 0) && error("Radius of L1 ball is negative")
+        return (st == "l1" ? 2 : st == "l2" ? 3 : 4, lb === nothing ? 0.0 : Float64(minimum(lb)), Float64(maximum(ub)), lb, ub, Int32(0))
+    end
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "l2"          && return (3, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "annulus"     && return (4, Float64(c.min), Float64(c.max), nothing_[3:5]...)
@@ -115,7 +124,8 @@ end
 
 The reference's `setup_constraints` (src/setup_constraints.jl:17-102).  With `segment_norms=true` it also takes l1, l2 and annulus
 sets with `app_mode = ("fiber", d)` or `("slice", d)` on the identity, D_x, D_y or D_z: libsipx projects every fiber / slice of the
-array of shape TD_n on its own, all with the scalar min / max (include/sipx.h, SIPX_PROJ_L1).  The reference has no such
+array of shape TD_n on its own, all with the scalar min / max, or each with its own: `max` (for the annulus `min` and / or `max`) a
+vector of nseg entries in the segment order of include/sipx.h (SIPX_PROJ_L1), a scalar beside a vector repeated.  The reference has no such
 projector ("l1 and l2 constraints only available for matrix or tensor mode, currently"): without the keyword its error stays.
 The reference sets the operators and properties up for the whole-array form of such a set; the application mode is put back
 into the constraint its P_sub[i] captured -- where `PARSDMM` above reads it -- and into set_Prop.tag[i].  Such a P_sub[i] must
@@ -132,12 +142,16 @@ function setup_constraints(constraint, comp_grid, TF; segment_norms::Bool=false)
             error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)")
         ndim == 2 && c.app_mode[1] == "slice" &&
             error("for 2D models, the mode of application for $(c.set_type) sets needs to be (fiber,x) or (fiber,z), or matrix for the whole array")
-        modes[i] = c.app_mode
+        modes[i] = (c.app_mode, c.min, c.max)
         c.app_mode = (ndim == 3 ? "tensor" : "matrix", "")
+        c.max isa AbstractVector && (c.max = maximum(c.max))      # the reference sets the whole-array form up with scalars
+        c.min isa AbstractVector && (c.min = minimum(c.min))
     end
     (P_sub, TD_OP, set_Prop) = ref(constraint, comp_grid, TF)
-    for (i, am) in modes
+    for (i, (am, mn, mx)) in modes
         constraint[i].app_mode = am
+        constraint[i].min = mn isa AbstractVector ? convert(Vector{TF}, mn) : constraint[i].min
+        constraint[i].max = mx isa AbstractVector ? convert(Vector{TF}, mx) : constraint[i].max
         set_Prop.tag[i] = (set_Prop.tag[i][1], set_Prop.tag[i][2], am[1], am[2])
     end
     return P_sub, TD_OP, set_Prop

@@ -132,6 +132,12 @@ int sipx_learn_observations(int dtype, const int64_t* n, const double* h, int64_
 int sipx_apply_op(sipx_ctx* c, int op, const void* x, void* s) { SIPX_TRY(c->e->apply_op(op, x, s, false)) }
 int sipx_apply_op_adj(sipx_ctx* c, int op, const void* v, void* t) { SIPX_TRY(c->e->apply_op(op, v, t, true)) }
 int sipx_project(sipx_ctx* c, const sipx_set_desc* d, void* v, int64_t len) { SIPX_TRY(sipx::refresh_env_knobs(); c->e->project(d, v, len)) }
+int sipx_segment_norms(sipx_ctx* c, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->segment_norms(op, mode, dir, norm, x, out, nseg, false))
+}
+int sipx_segment_norms_dev(sipx_ctx* c, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->segment_norms(op, mode, dir, norm, x, out, nseg, true))
+}
 int sipx_get_Q(sipx_ctx* c, void* Q, int64_t* offsets, int* d) { SIPX_TRY(c->e->get_Q(Q, offsets, d)) }
 int sipx_q_terms(sipx_ctx* c, int* bands, int* matrix_free) { SIPX_TRY(c->e->q_terms(bands, matrix_free)) }
 int sipx_time_spmv(sipx_ctx* c, int reps, double* avg_ms) { SIPX_TRY(*avg_ms = c->e->time_spmv(reps)) }

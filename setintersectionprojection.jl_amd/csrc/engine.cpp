@@ -227,6 +227,7 @@ struct SetState {
   T *pend_lb = nullptr, *pend_ub = nullptr;
   int searches_done = 0;             // slab-decomposed l1 searches of this set so far (sizes the refinement rounds)
   int ext_kind = 0;                  // projector acting on a materialised vector (ext_proj.h)
+  bool seg_radii = false;            // EXT_L1_SEG / L2_SEG / ANNULUS_SEG built with one radius per segment (host_lb / host_ub, then the projector's)
   // Sharded solve: a rank / nuclear-norm set on the slices orthogonal to the last grid dimension is projected by ALL ranks,
   // each factorising the slices of its z-slab (`ext` is then built for the slab on every rank, owner or not)
   bool dist_ext = false;
@@ -425,6 +426,8 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
     refresh_env_knobs();                  // the launchers' A/B switches: read once per context, not per launch
     feasibility_only_ = feasibility_only != 0;
+    for (const auto& s : sets_)
+      if (s.seg_radii) refuse_sharded_radii();
     FinalizePlan P;
     plan_sets();
     init_rho_gamma(rho_ini, n_rho, gamma_ini);
@@ -896,7 +899,7 @@ class Engine : public EngineBase {
       s.spec.ub = s.host_ub.empty() ? nullptr : s.host_ub.data();
       s.spec.basis = s.host_basis.empty() ? nullptr : s.host_basis.data();
       s.ext = std::make_shared<ExtProj<T>>(s.spec, stream_);
-      if (s.ext_kind == EXT_HISTOGRAM) {
+      if (s.ext_kind == EXT_HISTOGRAM || s.seg_radii) {
         s.host_lb.clear(); s.host_ub.clear();
         if (s.pend_lb || s.pend_ub) s.ext->set_data(s.pend_lb, s.pend_ub, true);
       }
@@ -2951,6 +2954,7 @@ class Engine : public EngineBase {
   // allocated and no stream or event is created; the new data holds from the next sipx_reset on (a solve in progress is given
   // up: the host form stages through the engine's scratch).
   long long data_len(const SetState<T>& s) const {
+    if (s.seg_radii) return seg_count(s.spec);
     if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;
     return G_.n[s.bdir] - ((s.nblk == 1 && s.dir[0] == s.bdir) ? 1 : 0);
   }
@@ -2975,11 +2979,15 @@ class Engine : public EngineBase {
       throw std::runtime_error(what + ": set index " + std::to_string(set) + " out of range (" + std::to_string(nsets) + " sets)");
     SetState<T>& s = sets_[set];
     if (s.comp) throw std::runtime_error(what + " is not available for Minkowski sets" + way_out);
-    const bool bounds = !s.ext_kind && s.prox == SIPX_PROJ_BOUNDS_VEC, hist = s.ext_kind == EXT_HISTOGRAM;
+    const bool bounds = !s.ext_kind && s.prox == SIPX_PROJ_BOUNDS_VEC, hist = s.ext_kind == EXT_HISTOGRAM || s.seg_radii;
     if (!bounds && !hist)
       throw std::runtime_error(what + ": set " + std::to_string(set) + " holds no replaceable vectors -- element-wise and per-fiber bounds "
-                               "(no transform) and the relaxed histogram do; scalars, vector bounds behind the DCT, the DFT mask and "
+                               "(no transform), the relaxed histogram and per-fiber / per-slice l1, l2 and annulus sets built with a "
+                               "vector of radii do; scalars, vector bounds behind the DCT, the DFT mask and "
                                "subspace bases are fixed at sipx_add_set" + way_out);
+    if (s.seg_radii && lb && s.ext_kind != EXT_ANNULUS_SEG)
+      throw std::runtime_error(what + ": only the annulus has inner radii (lb); the radii of an l1 / l2 set are its ub");
+    if (s.seg_radii && s.ext_kind == EXT_L1_SEG && ub && !on_device) check_l1_radii((const T*)ub, seg_count(s.spec));
     if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
       throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
     if (!lb && !ub) return;
@@ -3024,7 +3032,7 @@ class Engine : public EngineBase {
       io_h2d_ += (long long)bytes * ((LB ? 1 : 0) + (UB ? 1 : 0));
     }
     if (hist) {
-      if (!s.ext) throw std::runtime_error("internal: histogram set without its projector");
+      if (!s.ext) throw std::runtime_error("internal: histogram / segment-radii set without its projector");
       s.ext->set_stream(stream_);
       s.ext->set_data(LB, UB, on_device);
     } else {
@@ -3352,6 +3360,55 @@ class Engine : public EngineBase {
     SIPX_HIP(hipMemcpy(v, dv, len * sizeof(T), hipMemcpyDeviceToHost));
   }
 
+  // sipx_segment_norms(_dev): the l1 / l2 norms of the fibers / slices of A x, in the order of the per-segment radii.  A x through the
+  // operator product of apply_op into scratch of the call, one launch of k_seg_observe (seg_norm.h) on it.
+  void segment_norms(int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg, bool on_device) override {
+    SIPX_HIP(hipSetDevice(device_));
+    if (norm != 0 && norm != 1) throw std::runtime_error("segment norms: norm must be 0 (l1) or 1 (l2)");
+    if (op != SIPX_OP_IDENTITY && op != SIPX_OP_DX && op != SIPX_OP_DY && op != SIPX_OP_DZ)
+      throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
+    SetState<T> s;
+    configure_op(s, op);
+    sipx_set_desc d{};
+    d.op = op; d.proj = SIPX_PROJ_L2; d.mode = mode; d.dir = dir;
+    if (mode == SIPX_MODE_WHOLE) throw std::runtime_error("segment norms need a fiber or slice mode");
+    configure_proj(s, &d);                     // the refusals, and the ExtSpec, of the sets
+    const long long ns = seg_count(s.spec);
+    if (nseg) *nseg = ns;
+    if (!x || !out) return;                    // (a query of the length)
+    long long H = 4;
+    for (int a = 0; a < 3; ++a) H = std::max<long long>(H, G_.st[a]);
+    H = (H + 3) / 4 * 4;
+    DeviceMemory tmp;
+    T* dxb = on_device && !s.nblk ? nullptr : tmp.alloc<T>(G_.N + 2 * H);
+    T* dvb = s.nblk ? tmp.alloc<T>(s.Mpad + H) : nullptr;
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(ns);
+    const T* dx = (const T*)x;
+    if (on_device) engine_after_caller();
+    if (dxb) {
+      const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+      SIPX_HIP(hipMemcpyAsync(dxb + H, x, G_.N * sizeof(T), kind, stream_));
+      dx = dxb + H;
+    }
+    const T* dv = dx;                          // the identity: x itself
+    if (s.nblk) {
+      K<T>::fwd(stream_, G_, s.nblk, s.dir, s.ih, dx, dvb + H);
+      dv = dvb + H;
+    }
+    {
+      ObserverGuard og(observer());            // (sipx_kernel_stats mode 2 times the launch: the row of the materialised projectors)
+      ObsScope obs(KID_EXT, stream_, (double)s.Mtrue * sizeof(T));
+      seg_observe<T>(s.spec, norm, dv, dout, stream_);
+    }
+    if (on_device) {
+      caller_after_engine();
+      SIPX_HIP(hipStreamSynchronize(stream_));      // (the scratch of this call goes when it returns)
+    } else {
+      SIPX_HIP(hipStreamSynchronize(stream_));
+      SIPX_HIP(hipMemcpy(out, dout, ns * sizeof(T), hipMemcpyDeviceToHost));
+    }
+  }
+
   void get_Q(void* Q, int64_t* offsets, int* d) override {
     need_final();
     SIPX_HIP(hipStreamSynchronize(stream_));
@@ -3611,6 +3668,18 @@ class Engine : public EngineBase {
         for (long long i = 0; i < dims[0]; ++i, ++r) rows[r] = per_fiber[s.bdir == 0 ? i : (s.bdir == 1 ? j : k)];
   }
 
+  // vector radii live in the one projector of a single process: a rank of a sharded solve would each need its share of them
+  void refuse_sharded_radii() const {
+    if (comm_ || slab_req_ || !owned_.empty())
+      throw std::runtime_error("per-fiber / per-slice l1, l2 and annulus sets with one radius per segment take single-process contexts only, this "
+                               "one has a communicator, a slab decomposition or set ownership: use a scalar radius, or a single process");
+  }
+  // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
+  static void check_l1_radii(const T* r, long long n) {
+    for (long long k = 0; k < n; ++k)
+      if (!(r[k] > T(0))) throw std::runtime_error("Radius of L1 ball is negative (segment " + std::to_string(k) + ")");
+  }
+
   // projector part of a set descriptor: validation (the reference's error messages) + routing
   void configure_proj(SetState<T>& s, const sipx_set_desc* d) {
     s.prox = d->proj;
@@ -3640,6 +3709,23 @@ class Engine : public EngineBase {
       s.spec.pmax = d->pmax;
       s.prox = PX_EXT;
       need_ext_ = true;
+    };
+    // l1 / l2 / annulus per fiber or slice: the scalars, or one radius per segment in ub (and lb: the annulus' inner radii)
+    auto seg_norm = [&](int kind) {
+      const bool vec = d->ub || (kind == EXT_ANNULUS_SEG && d->lb);
+      if (kind == EXT_L1_SEG && !vec && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
+      ext(kind);
+      if (!vec) return;
+      refuse_sharded_radii();
+      const long long nseg = seg_count(s.spec);
+      s.seg_radii = true;
+      if (d->ub) s.host_ub.assign((const T*)d->ub, (const T*)d->ub + nseg);
+      else s.host_ub.assign((size_t)nseg, (T)d->pmax);
+      if (kind == EXT_ANNULUS_SEG) {
+        if (d->lb) s.host_lb.assign((const T*)d->lb, (const T*)d->lb + nseg);
+        else s.host_lb.assign((size_t)nseg, (T)d->pmin);
+      }
+      if (kind == EXT_L1_SEG) check_l1_radii(s.host_ub.data(), nseg);
     };
     if (d->transform == SIPX_TRANSFORM_DCT) {      // x -> C' P(C x): P acts on the DCT coefficients (ext_proj.hip)
       if (d->op != SIPX_OP_IDENTITY || mode != SIPX_MODE_WHOLE)
@@ -3696,17 +3782,18 @@ class Engine : public EngineBase {
       // l1, l2, annulus: the whole array through the engine's own two-pass search; per fiber / slice (a gap of the reference,
       // setup_constraints.jl:65-67 "currently") on the materialised vector, every segment by the same rule (seg_norm.h)
       case SIPX_PROJ_L1:
-        if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
-        if (mode == SIPX_MODE_WHOLE) s.two_pass = true;
-        else ext(EXT_L1_SEG);
+        if (mode == SIPX_MODE_WHOLE) {
+          if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
+          s.two_pass = true;
+        } else seg_norm(EXT_L1_SEG);
         break;
       case SIPX_PROJ_L2:
         if (mode == SIPX_MODE_WHOLE) s.two_pass = true;
-        else ext(EXT_L2_SEG);
+        else seg_norm(EXT_L2_SEG);
         break;
       case SIPX_PROJ_ANNULUS:
         if (mode == SIPX_MODE_WHOLE) s.two_pass = true;
-        else ext(EXT_ANNULUS_SEG);
+        else seg_norm(EXT_ANNULUS_SEG);
         break;
       case SIPX_PROJ_CARDINALITY:
         if (mode == SIPX_MODE_WHOLE) { s.two_pass = true; need_idx_ = true; }

@@ -18,7 +18,8 @@ struct ExtSpec {
   int mode = 0, dir = 2;          // SIPX_MODE_*, 0-based direction
   double pmin = 0, pmax = 0;
   int inner = 0;                  // EXT_DCT / EXT_DWT: the SIPX_PROJ_* kind applied to the transform coefficients
-  const void* lb = nullptr;       // EXT_HISTOGRAM: host TF[prod(dims)], ascending
+  const void* lb = nullptr;       // EXT_HISTOGRAM: host TF[prod(dims)], ascending; EXT_L1_SEG / L2_SEG / ANNULUS_SEG: host TF[nseg]
+                                  // radii per segment (ub: pmax of each, lb: the annulus' pmin of each), or nullptr: the scalars
   const void* ub = nullptr;
   const void* basis = nullptr;    // EXT_SUBSPACE: host TF[basis_rows x basis_cols], column-major
   long long basis_rows = 0;
@@ -52,6 +53,12 @@ class ExtProj {
  private:
   ExtImpl<T>* impl_;
 };
+
+// out[s] <- the l1 (norm_l2 = 0) or l2 norm of segment s of v (padded layout, spec.mode FIBER / SLICE), seg_count(spec) entries in the
+// order of the per-segment radii (seg_norm.h: k_seg_observe)
+template <typename T>
+void seg_observe(const ExtSpec& spec, int norm_l2, const T* v, T* out, hipStream_t stream);
+long long seg_count(const ExtSpec& spec);
 
 // sum (projected - original)^2 and sum original^2 into partial slots dst[0..NB), dst[NB..2NB)
 template <typename T>

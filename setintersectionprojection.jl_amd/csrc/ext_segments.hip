@@ -162,27 +162,48 @@ struct CardSegProj : ExtImpl<T> {
   }
 };
 
-// l1 ball, l2 ball or annulus of every fiber / slice, all segments sharing the scalar min / max (seg_norm.h).  Nothing is kept
-// between calls: the call of the feasibility estimate and the one of the y update are independent, reset() has nothing to forget.
+// l1 ball, l2 ball or annulus of every fiber / slice (seg_norm.h): all segments share the scalar min / max, or -- built with
+// ExtSpec::lb / ub -- each has its own (rmin / rmax, nseg entries in SegMap's order; one vector given for an annulus, the other one
+// repeats its scalar).  Nothing is kept between calls: the call of the feasibility estimate and the one of the y update are
+// independent, reset() has nothing to forget.
 template <typename T>
 struct NormSegProj : ExtImpl<T> {
   SegMap map{};
   SegNormPlan plan{};
+  T *rmin = nullptr, *rmax = nullptr;
   NormSegProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
     if (spec.mode != SIPX_MODE_FIBER && spec.mode != SIPX_MODE_SLICE)
       throw std::runtime_error("segmented l1 / l2 / annulus sets need a fiber or slice mode");
     if (spec.ndim == 2 && spec.mode != SIPX_MODE_FIBER)
       throw std::runtime_error("for 2D models, the mode of application for l1, l2 and annulus sets needs to be (fiber,x) or "
                                "(fiber,z), or matrix for the whole array");
-    if (spec.kind == EXT_L1_SEG && !((T)spec.pmax > T(0))) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
+    const bool vec = spec.ub || (spec.kind == EXT_ANNULUS_SEG && spec.lb);
+    if (spec.kind == EXT_L1_SEG && !vec && !((T)spec.pmax > T(0))) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
     map = make_segmap(spec);
     if (map.nseg < 1 || map.L < 1 || map.L >= (1ll << 31)) throw std::runtime_error("segmented l1 / l2 / annulus sets: empty or oversize segments");
     plan = seg_norm_plan(map, (int)sizeof(T));
+    if (!vec) return;
+    auto fill = [&](const void* host, double scalar) {
+      std::vector<T> h((size_t)map.nseg, (T)scalar);
+      if (host) h.assign((const T*)host, (const T*)host + map.nseg);
+      if (spec.kind == EXT_L1_SEG)
+        for (T r : h)
+          if (!(r > T(0))) throw std::runtime_error("Radius of L1 ball is negative");
+      T* d = this->template alloc<T>((size_t)map.nseg);
+      SIPX_HIP(hipMemcpy(d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+      return d;
+    };
+    rmax = fill(spec.ub, spec.pmax);
+    if (spec.kind == EXT_ANNULUS_SEG) rmin = fill(spec.lb, spec.pmin);
   }
   template <int KIND>
   void launch(T* v) {
-    hipLaunchKernelGGL((k_seg_norm<T, KIND>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, this->stream, map, plan, v, (T)this->sp.pmin,
-                       (T)this->sp.pmax);
+    if (rmax)
+      hipLaunchKernelGGL((k_seg_norm<T, KIND, true>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, this->stream, map, plan, v,
+                         (T)this->sp.pmin, (T)this->sp.pmax, rmin, rmax);
+    else
+      hipLaunchKernelGGL((k_seg_norm<T, KIND, false>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, this->stream, map, plan, v,
+                         (T)this->sp.pmin, (T)this->sp.pmax, (const T*)nullptr, (const T*)nullptr);
   }
   void project(T* v, bool, double*, T*, T*) override {
     if (this->sp.kind == EXT_L1_SEG) launch<SEGN_L1>(v);
@@ -190,7 +211,37 @@ struct NormSegProj : ExtImpl<T> {
     else launch<SEGN_ANNULUS>(v);
     SIPX_HIP(hipGetLastError());
   }
+  // new radii into the arrays of the old ones: one copy each on the set's stream (lb: the annulus' inner radii)
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    if (!rmax) ExtImpl<T>::set_data(new_lb, new_ub, on_device);
+    if (new_lb && !rmin) throw std::runtime_error("only the annulus has inner radii: pass the radii of this set as ub");
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const size_t bytes = sizeof(T) * (size_t)map.nseg;
+    if (new_lb) SIPX_HIP(hipMemcpyAsync(rmin, new_lb, bytes, kind, this->stream));
+    if (new_ub) SIPX_HIP(hipMemcpyAsync(rmax, new_ub, bytes, kind, this->stream));
+  }
 };
+
+// The norms of the fibers / slices of a materialised vector (sipx_segment_norms): one launch of k_seg_observe with the projector's
+// own tile mapping, nothing resident.
+template <typename T>
+void seg_observe(const ExtSpec& spec, int norm_l2, const T* v, T* out, hipStream_t stream) {
+  if (spec.mode != SIPX_MODE_FIBER && spec.mode != SIPX_MODE_SLICE) throw std::runtime_error("segment norms need a fiber or slice mode");
+  if (spec.ndim == 2 && spec.mode != SIPX_MODE_FIBER)
+    throw std::runtime_error("for 2D models, the mode of application for l1, l2 and annulus sets needs to be (fiber,x) or "
+                             "(fiber,z), or matrix for the whole array");
+  const SegMap map = make_segmap(spec);
+  if (map.nseg < 1 || map.L < 1 || map.L >= (1ll << 31)) throw std::runtime_error("segment norms: empty or oversize segments");
+  SegNormPlan plan = seg_norm_plan(map, (int)sizeof(T));
+  plan.lds = 0;
+  plan.lds_bytes = 0;
+  if (norm_l2) hipLaunchKernelGGL((k_seg_observe<T, SEGN_L2>), dim3(plan.grid), dim3(BLOCK), 0, stream, map, plan, v, out);
+  else hipLaunchKernelGGL((k_seg_observe<T, SEGN_L1>), dim3(plan.grid), dim3(BLOCK), 0, stream, map, plan, v, out);
+  SIPX_HIP(hipGetLastError());
+}
+template void seg_observe<float>(const ExtSpec&, int, const float*, float*, hipStream_t);
+template void seg_observe<double>(const ExtSpec&, int, const double*, double*, hipStream_t);
+long long seg_count(const ExtSpec& spec) { return make_segmap(spec).nseg; }
 
 template <typename T>
 struct HistogramProj : ExtImpl<T> {

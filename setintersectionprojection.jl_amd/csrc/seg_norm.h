@@ -19,6 +19,12 @@
 // thread re-reads its own entries only: no barrier guards them); otherwise every pass re-reads global memory.
 // REDUCTIONS are fixed trees: serial per thread in t order, a butterfly over the lanes of a wave that share a segment, the four
 // waves' totals added in wave order.  No floating-point atomics, no state between calls: two calls give the same bits.
+// RADII.  All segments share the scalar pmin / pmax, or every segment has its own: rmin[s] / rmax[s], s = seg_tile_index (SegMap's
+// order, s = sa + SA * sb).  The lanes of a segment load one address, the F segments of a tile F consecutive ones, once per tile into a
+// register.  An l1 radius that is not > 0 can only arrive from device memory (every host path refuses it): the ball is {0} or empty,
+// and a segment that is not all zero is set to zero.  The loops end for every radius, NaN included.
+// OBSERVATION.  k_seg_observe is pass 1 on its own (segn_pass1, shared with the projector): segment s writes (T)asum or
+// (T)sqrt(sumsq), the very numbers k_seg_norm compares with the radii -- radii observed on v make v a point the projector does not write.
 #pragma once
 #include "ext_family.h"
 
@@ -68,6 +74,12 @@ __host__ __device__ inline bool seg_tile_base(const SegMap& m, const SegNormPlan
   const long long ia = tile % p.ntA, sb = tile / p.ntA, sa = ia * p.F + f;
   base = sa * m.sSa + sb * m.sSb;
   return sa < m.SA;
+}
+
+// index of that segment in SegMap's order (what rmin / rmax and the observed norms are indexed by), -1 for a lane of the ragged end
+__host__ __device__ inline long long seg_tile_index(const SegMap& m, const SegNormPlan& p, long long tile, int f) {
+  const long long ia = tile % p.ntA, sb = tile / p.ntA, sa = ia * p.F + f;
+  return sa < m.SA ? sa + m.SA * sb : -1;
 }
 
 // Michelot's iteration of one segment.  theta only ever grows, so the active count C(theta) = #{|v| > theta} only shrinks: the
@@ -147,8 +159,29 @@ __device__ __forceinline__ double segn_min(double a, int F, double* red) {
   return a;
 }
 
-template <typename T, int KIND>
-__global__ __launch_bounds__(BLOCK) void k_seg_norm(SegMap m, SegNormPlan p, T* __restrict__ v, T pmin, T pmax) {
+// pass 1 of one tile: the sums of segment f over its lanes, returned to each of them; the values go to `sm` when the plan keeps them
+template <typename T>
+__device__ __forceinline__ void segn_pass1(const SegMap& m, const SegNormPlan& p, const T* vs, T* sm, bool live, int f, int r, int G,
+                                           double* red, double& asum, double& sumsq, double& vmin) {
+  const int F = p.F;
+  const long long L = m.L;
+  asum = 0; sumsq = 0; vmin = (double)INFINITY;
+  if (live)
+    for (long long t = r; t < L; t += G) {
+      const T x = vs[seg_toff(m, t)];
+      if (p.lds) sm[t * F + f] = x;
+      const double a = (double)fabs(x);
+      asum += a;
+      sumsq += (double)x * (double)x;
+      vmin = a < vmin ? a : vmin;
+    }
+  segn_sum2(asum, sumsq, F, red);
+}
+
+// VEC: rmin / rmax hold one radius per segment (rmin is read by the annulus only); otherwise every segment takes pmin / pmax
+template <typename T, int KIND, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_seg_norm(SegMap m, SegNormPlan p, T* __restrict__ v, T pmin, T pmax, const T* __restrict__ rmin,
+                                                    const T* __restrict__ rmax) {
   static_assert(BLOCK == 256, "four waves: segn_sum2 adds four wave totals");
   extern __shared__ __align__(16) unsigned char segn_lds[];
   __shared__ double red[2 * BLOCK];
@@ -160,24 +193,23 @@ __global__ __launch_bounds__(BLOCK) void k_seg_norm(SegMap m, SegNormPlan p, T* 
     long long base;
     const bool live = seg_tile_base(m, p, tile, f, base);
     T* const vs = v + base;
-    // pass 1: the sums; the values go to LDS when they fit
-    double asum = 0, sumsq = 0, vmin = (double)INFINITY;
-    if (live)
-      for (long long t = r; t < L; t += G) {
-        const T x = vs[seg_toff(m, t)];
-        if (p.lds) sm[t * F + f] = x;
-        const double a = (double)fabs(x);
-        asum += a;
-        sumsq += (double)x * (double)x;
-        vmin = a < vmin ? a : vmin;
+    if constexpr (VEC) {
+      if (live) {
+        const long long s = seg_tile_index(m, p, tile, f);
+        pmax = rmax[s];
+        if constexpr (KIND == SEGN_ANNULUS) pmin = rmin[s];
       }
-    segn_sum2(asum, sumsq, F, red);
-    int act = 0;                        // 0: inside the set, 1: soft threshold / multiply, 2: fill
+    }
+    // pass 1: the sums; the values go to LDS when they fit
+    double asum, sumsq, vmin;
+    segn_pass1<T>(m, p, vs, sm, live, f, r, G, red, asum, sumsq, vmin);
+    int act = 0;                        // 0: inside the set, 1: soft threshold / multiply, 2: fill, 3: zero
     T par = T(0);                       // theta or the scale
     if constexpr (KIND == SEGN_L1) {
       vmin = segn_min(vmin, F, red);
       const double b = (double)pmax;
-      const bool need = live && !((T)asum <= pmax);          // norm(v,1) <= b && return v   project_l1_Duchi!.jl:23
+      const bool ball = !VEC || pmax > T(0);                  // a radius from device memory: <= 0 or NaN leaves {0} at most
+      const bool need = live && ball && !((T)asum <= pmax);   // norm(v,1) <= b && return v   project_l1_Duchi!.jl:23
       L1SegState st = l1_seg_start(asum, b, L);
       st.done = need ? 0 : 1;
       for (long long it = 0; it <= L + 1; ++it) {
@@ -194,6 +226,8 @@ __global__ __launch_bounds__(BLOCK) void k_seg_norm(SegMap m, SegNormPlan p, T* 
       if (need) {
         act = 1;
         par = (T)l1_seg_finish(st, asum, vmin, b, L);
+      } else if (VEC && live && !ball && asum > 0) {
+        act = 3;
       }
     } else {
       if (live) act = l2_seg_rule<T>(KIND, sumsq, pmin, pmax, L, par);
@@ -203,8 +237,26 @@ __global__ __launch_bounds__(BLOCK) void k_seg_norm(SegMap m, SegNormPlan p, T* 
       for (long long t = r; t < L; t += G) {
         const long long o = seg_toff(m, t);
         const T x = p.lds ? sm[t * F + f] : vs[o];
-        vs[o] = KIND == SEGN_L1 ? soft_thr(x, par) : (act == 2 ? par : x * par);
+        if constexpr (KIND == SEGN_L1) vs[o] = VEC && act == 3 ? T(0) : soft_thr(x, par);
+        else vs[o] = act == 2 ? par : x * par;
       }
+  }
+}
+
+// The norms of all segments: out[s] = (T)||segment s||_1 (NORM == SEGN_L1) or (T)sqrt(sum of squares) (SEGN_L2), s in SegMap's order.
+// `p` is the projector's plan with lds = 0: one read pass, nothing kept.
+template <typename T, int NORM>
+__global__ __launch_bounds__(BLOCK) void k_seg_observe(SegMap m, SegNormPlan p, const T* __restrict__ v, T* __restrict__ out) {
+  static_assert(BLOCK == 256, "four waves: segn_sum2 adds four wave totals");
+  __shared__ double red[2 * BLOCK];
+  const int F = p.F, G = BLOCK >> p.logF;
+  const int f = (int)threadIdx.x & (F - 1), r = (int)threadIdx.x >> p.logF;
+  for (long long tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
+    long long base;
+    const bool live = seg_tile_base(m, p, tile, f, base);
+    double asum, sumsq, vmin;
+    segn_pass1<T>(m, p, v + base, (T*)nullptr, live, f, r, G, red, asum, sumsq, vmin);
+    if (live && r == 0) out[seg_tile_index(m, p, tile, f)] = NORM == SEGN_L1 ? (T)asum : (T)sqrt(sumsq);
   }
 }
 #endif

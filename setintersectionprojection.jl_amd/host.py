@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "sipx_kernel_stats_json", "sipx_comm_info", "sipx_device_bytes", "sipx_reset", "sipx_dwt",
     "sipx_learn_observations",
     "sipx_finalize_dev", "sipx_reset_dev", "sipx_download_dev", "sipx_set_caller_stream", "sipx_io_bytes",
-    "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev",
+    "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev", "sipx_segment_norms", "sipx_segment_norms_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
@@ -343,6 +343,7 @@ class Projector:
         self.basis_orth = False
         self.pmin = self.pmax = 0.0
         self.transform = 0
+        self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
         if constraint.TD_OP == "DCT":
             # x -> C' P(C x) with the orthonormal DCT-II (get_projector.jl, special_operator_list branches); the l2 ball and
             # the annulus commute with an orthogonal transform and are applied to x itself
@@ -431,6 +432,8 @@ class Projector:
             if self.basis.ndim != 2:
                 raise SipxError("subspace constraints need a matrix A in custom_TD_OP[0]")
             self.basis_orth = bool(orth)
+        elif self.mode and st in ("l1", "l2", "annulus") and (np.ndim(constraint.max) or (st == "annulus" and np.ndim(constraint.min))):
+            self._segment_radii(st, constraint)
         elif st in ("l1", "l2", "prox_l1"):
             self.kind, self.pmax = st, float(constraint.max)
         elif st == "annulus":
@@ -439,6 +442,35 @@ class Projector:
             self.kind, self.pmax = st, float(int(constraint.max))
         else:
             raise SipxError(f"set type {st!r} is not part of this engine")
+
+    def _segment_radii(self, st, constraint):
+        """One radius per segment (csrc/seg_norm.h): max -- and for the annulus min and / or max -- a vector of nseg entries in the order of
+        segment_norms(); a scalar beside a vector is repeated.  The length is checked against the operator in check_rows."""
+        vec = {}
+        for name, a in (("min", constraint.min), ("max", constraint.max)):
+            if name == "min" and st != "annulus":
+                continue
+            if np.ndim(a) > 1:
+                raise SipxError(f"{st} radii per segment: {name} must be a scalar or a 1-D vector, not of shape {np.shape(a)}")
+            vec[name] = np.ascontiguousarray(a, self.TF) if np.ndim(a) == 1 else None
+        length = max(len(v) for v in vec.values() if v is not None)
+        for name, a in (("min", constraint.min), ("max", constraint.max)):
+            if name in vec and vec[name] is None:
+                vec[name] = np.full(length, self.TF(a), self.TF)
+        self.kind, self.seg_radii = st, True
+        self.ub, self.lb = vec["max"], vec.get("min")
+        _check_l1_radii(st, self.ub)
+        self.pmax = float(self.ub.max()) if len(self.ub) else 0.0
+        self.pmin = float(self.lb.min()) if self.lb is not None and len(self.lb) else 0.0
+
+    def nseg(self, op) -> int:
+        """Fibers / slices of the array of shape TD_n this set splits behind operator `op` (0: a whole-array set)."""
+        if not self.mode:
+            return 0
+        n = list(op.n)
+        if op.kind in ("D_x", "D_y", "D_z"):
+            n[{"D_x": 0, "D_y": 1, "D_z": len(n) - 1}[op.kind]] -= 1
+        return int(np.prod(n)) // int(n[self.dir]) if self.mode == MODES["fiber"] else int(n[self.dir])
 
     def check_rows(self, op: "TDOperator"):
         """Host-side shape checks of the vectors the descriptor points at (the engine reads them unchecked)."""
@@ -455,6 +487,13 @@ class Projector:
             want = n[self.dir] if self.mode == MODES["fiber"] else rows
             if self.lb.shape != (want,) or self.ub.shape != (want,):
                 raise SipxError(f"bounds vectors need {want} entries for this operator / application mode")
+        if self.seg_radii:
+            want = self.nseg(op)
+            for name, a in (("min", self.lb), ("max", self.ub)):
+                if a is not None and a.shape != (want,):
+                    what = "fiber along" if self.mode == MODES["fiber"] else "slice orthogonal to"
+                    raise SipxError(f"{self.kind} radii per segment: {name} has {a.shape[0]} entries, nseg = {want} are needed -- one per "
+                                    f"segment, a segment being a {what} dimension {self.dir + 1} of the array of shape {tuple(n)} (TD_n)")
         if self.kind == "bounds_dft" and self.ub.shape != (rows,):
             raise SipxError(f"the DFT-domain mask needs {rows} entries")
         if self.kind == "histogram" and (self.lb.shape != (rows,) or self.ub.shape != (rows,)):
@@ -464,6 +503,8 @@ class Projector:
         """Entries of each vector sipx_set_data takes for this set behind operator `op`; None: the set holds no replaceable data."""
         if self.kind == "histogram":
             return int(op.shape[0])
+        if self.seg_radii:
+            return self.nseg(op)
         if self.kind != "bounds_vec" or self.transform:
             return None
         if self.mode != MODES["fiber"]:
@@ -545,13 +586,17 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
     """src/setup_constraints.jl:17-102 -> (P_sub, TD_OP, set_Prop).
 
     segment_norms=True takes l1, l2 and annulus sets with app_mode ("fiber", d) / ("slice", d): every fiber along d (slice
-    orthogonal to d) of the array of shape TD_n is projected on its own, all with the scalar min / max, on the identity, D_x, D_y
-    or D_z.  The reference has no such projector ("only available for matrix or tensor mode, currently"); without the keyword its
+    orthogonal to d) of the array of shape TD_n is projected on its own, on the identity, D_x, D_y or D_z -- all with the scalar
+    min / max, or each with its own: max (for the annulus min and / or max) a vector of nseg entries in the order segment_norms()
+    returns them, a scalar beside a vector repeated.  The reference has no such projector ("only available for matrix or tensor mode, currently"); without the keyword its
     error stays."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
-        if np.ndim(c.min) == 0:
+        seg = segment_norms and c.set_type in ("l1", "l2", "annulus") and c.app_mode[0] in ("slice", "fiber")
+        if seg and np.ndim(c.min) != np.ndim(c.max):      # radii per segment: a scalar beside a vector, each converted on its own
+            c.min, c.max = [np.asarray(a, TF) if np.ndim(a) else (TF(a) if isinstance(a, (float, np.floating)) else a) for a in (c.min, c.max)]
+        elif np.ndim(c.min) == 0:
             if isinstance(c.min, (float, np.floating)):
                 c.min, c.max = TF(c.min), TF(c.max)
         else:
@@ -574,6 +619,8 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             AtA_diag, dense = False, False
         banded = True       # the engine keeps Q in CDS: a DFT set contributes the identity band like any orthogonal op
         P_sub.append(Projector(c, comp_grid, TF))
+        if P_sub[-1].seg_radii:
+            P_sub[-1].check_rows(A)           # nseg depends on the operator
         TD_OP.append(A)
         prop.AtA_diag.append(AtA_diag); prop.dense.append(dense); prop.TD_n.append(TD_n)
         prop.banded.append(banded); prop.AtA_offsets.append(None)
@@ -672,6 +719,7 @@ class Context:
         self.data_len: List[Optional[int]] = []      # per set: entries of the vectors set_data takes (None: it has none)
         self.p = self.pp = 0
         self._keep = []
+        self._keep_proj: List[Projector] = []        # per set: its descriptor
 
     def close(self):
         if self.h:
@@ -709,6 +757,7 @@ class Context:
         _chk(lib().sipx_set_rows(self.h, rc, C.byref(r)))
         self.rows.append(int(r.value))
         self.data_len.append(proj.data_len(op))
+        self._keep_proj.append(proj)
         return rc
 
     def set_q_mode(self, mode: str):
@@ -831,6 +880,9 @@ class Context:
             if a is not None:
                 a = _check_array(name, a, self.TF, want)
             arrs.append(a)
+        P = self._keep_proj[int(i)] if 0 <= int(i) < len(self._keep_proj) else None
+        if P is not None and P.seg_radii and arrs[1] is not None:
+            _check_l1_radii(P.kind, arrs[1])
         _chk(lib().sipx_set_data(self.h, int(i), _ptr(arrs[0]), _ptr(arrs[1])))
 
     def set_data_dev(self, i, lb=None, ub=None):
@@ -1265,6 +1317,13 @@ def _check_array(name, a, TF, length):
     return np.ascontiguousarray(a)
 
 
+def _check_l1_radii(kind, r):
+    """project_l1_Duchi!.jl:22 for every segment: no host path hands the device an l1 radius that is not > 0."""
+    if kind == "l1" and not np.all(np.asarray(r) > 0):
+        bad = int(np.flatnonzero(~(np.asarray(r) > 0))[0])
+        raise SipxError(f"Radius of L1 ball is negative (segment {bad}: {np.asarray(r)[bad]!r})")
+
+
 _one_runtime_checked = False
 
 
@@ -1386,8 +1445,9 @@ class Solver:
     The arguments are those of PARSDMM.  The first call builds the context (sipx_finalize), every later one is sipx_reset, the
     solve and the download; data set before the first call goes in before finalize.  With a torch tensor m the call is the
     device-resident one (PARSDMM_device): every argument is a tensor on m's device, the results are tensors there, torch's
-    current stream is the caller's stream.  set_data takes element-wise or per-fiber bounds (no transform) and the relaxed
-    histogram; a numpy vector is uploaded at every set_data (the array may be changed afterwards), a tensor is read on the device.
+    current stream is the caller's stream.  set_data takes element-wise or per-fiber bounds (no transform), the relaxed
+    histogram and the radii of a per-fiber / per-slice l1, l2 or annulus set that was built with a vector of them (ub: the radii,
+    lb: the annulus' inner radii; nseg entries); a numpy vector is uploaded at every set_data (the array may be changed afterwards), a tensor is read on the device.
     Every wrong argument raises SipxError before the library is touched.  log.context_reused tells whether the call found its
     context built.  The Solver owns its context: the caches of PARSDMM / PARSDMM_device and clear_context_cache() do not know it."""
 
@@ -1458,8 +1518,10 @@ class Solver:
         want = self.P_sub[i].data_len(self.TD_OP[i])
         if want is None:
             raise SipxError(f"set_data: set {i} ({self.set_Prop.tag[i][0]} on {self.set_Prop.tag[i][1]}) holds no replaceable vectors -- "
-                            "element-wise and per-fiber bounds (no transform) and the relaxed histogram do; build a new Solver for "
-                            "other data")
+                            "element-wise and per-fiber bounds (no transform), the relaxed histogram and per-fiber / per-slice l1, l2 "
+                            "and annulus sets built with a vector of radii do; build a new Solver for other data")
+        if self.P_sub[i].seg_radii and lb is not None and self.P_sub[i].kind != "annulus":
+            raise SipxError(f"set_data: set {i} is an {self.P_sub[i].kind} set: its radii are ub, only the annulus has inner radii (lb)")
         given = [(k, a) for k, a in (("lb", lb), ("ub", ub)) if a is not None]
         if not given:
             return
@@ -1477,6 +1539,8 @@ class Solver:
         else:
             for k, a in given:
                 _check_array(k, a, self.TF, want)
+            if self.P_sub[i].seg_radii and ub is not None:
+                _check_l1_radii(self.P_sub[i].kind, ub)
             fn = self._context(self.device).set_data
         try:
             fn(i, lb, ub)
@@ -1623,6 +1687,59 @@ def resample_nn(a, nc, nf, device=None):
     out = np.empty(int(np.prod(nf)), TF)
     _chk(lib().sipx_resample_nn(_dtype_code(TF), len(nc), (C.c_int64 * len(nc))(*nc), (C.c_int64 * len(nf))(*nf),
                                 _ptr(a), _ptr(out), device))
+    return out
+
+
+def segment_norms(x, comp_grid, TD_OP: str, app_mode, norm: str):
+    """The l1 or l2 norm of every fiber / slice of A x, A = TD_OP in ("identity", "D_x", "D_y", "D_z"), app_mode = ("fiber" | "slice", d),
+    norm in ("l1", "l2"), on a 2-D or 3-D grid: nseg numbers of the working precision (that of x) in the order the per-segment radii of
+    setup_constraints(..., segment_norms=True) are read -- a fiber set: the array of shape "TD_n without the fiber's axis", flattened
+    in Fortran order; a slice set: the coordinate along d.  Computed by the projector's own first pass (sipx_segment_norms): used as
+    radii they leave A x untouched.  x: a numpy vector (a numpy result) or a 1-D torch tensor on a GPU (a tensor there; nothing
+    crosses PCIe, the call orders itself against torch's current stream).  Radii for several training arrays: np.maximum / np.minimum
+    over the results."""
+    if norm not in ("l1", "l2"):
+        raise SipxError(f"segment_norms: norm must be 'l1' or 'l2', not {norm!r}")
+    if TD_OP not in ("identity", "D_x", "D_y", "D_z"):
+        raise SipxError("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)")
+    am = tuple(app_mode)
+    if len(am) != 2 or am[0] not in ("fiber", "slice"):
+        raise SipxError(f"segment_norms: app_mode must be ('fiber', d) or ('slice', d), not {app_mode!r}")
+    on_dev = _is_tensor(x)
+    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("segment_norms: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    n, _ = _grid(comp_grid)
+    if TD_OP == "D_y" and len(n) == 2:
+        raise SipxError("provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options")
+    P = Projector(set_definitions("l2", TD_OP, 0.0, 1.0, am), comp_grid, TF)      # mode, direction and their refusals
+    nseg = P.nseg(TDOperator(TD_OP, comp_grid, TF))
+    N = int(np.prod(n))
+    if on_dev:
+        import torch
+        _check_tensor("x", x, TF, N, None)
+        _check_one_hip_runtime()
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        out = torch.empty(nseg, dtype=x.dtype, device=torch.device("cuda", device))
+        xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
+        fn = lib().sipx_segment_norms_dev
+    else:
+        x = _check_array("x", x, TF, N)
+        device = None
+        out = np.empty(nseg, TF)
+        xp, op_ = _ptr(x), _ptr(out)
+        fn = lib().sipx_segment_norms
+    ctx = Context(comp_grid, TF, device)
+    try:
+        if on_dev:
+            ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        cnt = C.c_int64()
+        _chk(fn(ctx.h, OPS[TD_OP], P.mode, P.dir, 0 if norm == "l1" else 1, None, None, C.byref(cnt)))      # the count only
+        if cnt.value != nseg:
+            raise SipxError(f"internal: the engine counts {cnt.value} segments, the host {nseg}")
+        _chk(fn(ctx.h, OPS[TD_OP], P.mode, P.dir, 0 if norm == "l1" else 1, xp, op_, C.byref(cnt)))
+    finally:
+        ctx.close()
     return out
 
 
