@@ -82,10 +82,19 @@ enum {
   SIPX_PROJ_BOUNDS_DFT  = 12,/* x -> Re(F' (ub .* (F x))), F = unitary DFT: bounds in the Fourier domain with a binary lower
                                 bound of zeros and a mask ub TF[N] in the transform's element order
                                 (project_bounds!.jl:27-36 under get_projector.jl:8-9 with TD_OP "DFT"); op must be identity */
-  SIPX_PROJ_CARD_DFT    = 13 /* x -> Re(F' project_cardinality!(F x, k = pmax)), F = unitary DFT: keep the k Fourier coefficients
+  SIPX_PROJ_CARD_DFT    = 13,/* x -> Re(F' project_cardinality!(F x, k = pmax)), F = unitary DFT: keep the k Fourier coefficients
                                 of largest magnitude, stable order on the column-major index of the spectrum; conjugate pairs count
                                 as exact ties and the lower index wins; k >= N returns x bit for bit; op must be identity, mode WHOLE
                                 (src/get_projector.jl:85-89 with TD_OP "DFT", projectors/project_cardinality!.jl:3-21) */
+  SIPX_PROJ_L21         = 14 /* isotropic total variation (no counterpart in the reference): the l2,1 ball
+                                { v : sum_p ||v_p||_2 <= pmax } on the range of the TV operator, the group of grid point p being the
+                                forward differences that start at p (0 to ndim members).  op must be SIPX_OP_TV, mode WHOLE, transform
+                                NONE, pmax = tau > 0.  Group norms from a float64 sum of squares rounded once to TF, the threshold of
+                                SIPX_PROJ_L1 on the N group norms, every member scaled by max(g - theta, 0) / g; an input inside the
+                                ball is not written (csrc/l21.h).  Holds no replaceable vectors (sipx_set_data refuses).  Contexts
+                                with a communicator, a slab decomposition or set ownership refuse it.  sipx_project takes the
+                                M-vector of the TV range in the reference's row order on the context's grid; sipx_l21_norm observes
+                                the norm */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -336,6 +345,13 @@ int sipx_project(sipx_ctx* ctx, const sipx_set_desc* desc, void* v, int64_t len)
  * and nothing crosses PCIe.  Learning from several arrays is a loop with an element-wise maximum / minimum over the results. */
 int sipx_segment_norms(sipx_ctx* ctx, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg);
 int sipx_segment_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg);
+/* The isotropic total variation of x: *out = ||TV x||_2,1 as one TF, x TF[N] on the 2-D or 3-D grid of the context (which needs no sets
+ * and no finalize).  TV x comes from the engine's operator product into scratch of the call; the group norms are formed by the kernel of
+ * SIPX_PROJ_L21 and summed by the first pass of its threshold search.  CONTRACT: the value is the very number the projector compares
+ * with pmax, so a radius observed on x makes TV x a point the projector does not write.  x, out: host memory; the _dev form takes both
+ * in device memory of the context's GPU, ordered like sipx_download_dev against the caller's stream. */
+int sipx_l21_norm(sipx_ctx* ctx, const void* x, void* out);
+int sipx_l21_norm_dev(sipx_ctx* ctx, const void* x, void* out);
 /* nearest-neighbour resampling of an array of shape nc to shape nf, the grid transfer of PARSDMM_multi_level:
  * out[k] = in[round(1 + (k-1)(nc-1)/(nf-1))] per axis (Interpolations.BSpline(Constant()) evaluated on
  * range(1, stop=nc, length=nf); src/PARSDMM_multi_level.jl:41-45,61-65, src/interpolate_y_l.jl:32-88) */

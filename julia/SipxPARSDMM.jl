@@ -107,6 +107,13 @@ function projector_fields(c, TF)
         st == "l1" && !all(ub .> 0) && error("Radius of L1 ball is negative")
         return (st == "l1" ? 2 : st == "l2" ? 3 : 4, lb === nothing ? 0.0 : Float64(minimum(lb)), Float64(maximum(ub)), lb, ub, Int32(0))
     end
+    # isotropic total variation: the l2,1 ball on the range of the TV operator (include/sipx.h, SIPX_PROJ_L21; not a set of the reference)
+    if st == "l21"
+        op in ("TV", "D2D", "D3D") && c.custom_TD_OP[1] == [] || error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)")
+        c.app_mode[1] in ("matrix", "tensor") || error("the l2,1 ball applies to the whole array (mode matrix/tensor)")
+        c.max > 0 || error("Radius of L1 ball is negative")
+        return (14, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "l2"          && return (3, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "annulus"     && return (4, Float64(c.min), Float64(c.max), nothing_[3:5]...)
@@ -130,8 +137,33 @@ projector ("l1 and l2 constraints only available for matrix or tensor mode, curr
 The reference sets the operators and properties up for the whole-array form of such a set; the application mode is put back
 into the constraint its P_sub[i] captured -- where `PARSDMM` above reads it -- and into set_Prop.tag[i].  Such a P_sub[i] must
 not be called as a Julia function: it would project the whole array.
+
+`("l21", "TV")` in matrix / tensor mode -- isotropic total variation, the l2,1 ball of radius `max` on the TV range (include/sipx.h,
+SIPX_PROJ_L21) -- is libsipx's own as well and needs no keyword.  The reference sets such a set up as the anisotropic `("l1", "TV")`
+(same operator, same properties); the set type is put back into the captured constraint and the tag.  Its P_sub[i] must not be
+called as a Julia function either: it would project onto the l1 ball.
 """
 function setup_constraints(constraint, comp_grid, TF; segment_norms::Bool=false)
+    iso = [i for (i, c) in enumerate(constraint) if c.set_type == "l21"]
+    for i in iso
+        projector_fields(constraint[i], TF)                 # the refusals
+        constraint[i].set_type = "l1"
+    end
+    out = try
+        setup_constraints_segments(constraint, comp_grid, TF, segment_norms)
+    finally
+        for i in iso
+            constraint[i].set_type = "l21"
+        end
+    end
+    for i in iso
+        t = out[3].tag[i]
+        out[3].tag[i] = ("l21", t[2], t[3], t[4])
+    end
+    return out
+end
+
+function setup_constraints_segments(constraint, comp_grid, TF, segment_norms::Bool)
     ref = getfield(parentmodule(log_type_PARSDMM), :setup_constraints)
     segment_norms || return ref(constraint, comp_grid, TF)
     ndim = (length(comp_grid.n) == 3 && comp_grid.n[3] > 1) ? 3 : 2

@@ -426,8 +426,10 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
     refresh_env_knobs();                  // the launchers' A/B switches: read once per context, not per launch
     feasibility_only_ = feasibility_only != 0;
-    for (const auto& s : sets_)
+    for (const auto& s : sets_) {
       if (s.seg_radii) refuse_sharded_radii();
+      if (s.ext_kind == EXT_L21) refuse_sharded_l21();
+    }
     FinalizePlan P;
     plan_sets();
     init_rho_gamma(rho_ini, n_rho, gamma_ini);
@@ -3302,8 +3304,69 @@ class Engine : public EngineBase {
     }
   }
 
+  // SIPX_PROJ_L21 of sipx_project: the M-vector of the TV range in the reference's row order, through the packing of a TV set's y / l
+  void project_l21(const sipx_set_desc* d, void* v, int64_t len) {
+    SetState<T> st;
+    if (d->op != SIPX_OP_TV) throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
+    configure_op(st, SIPX_OP_TV);
+    configure_proj(st, d);
+    if (len != st.Mtrue)
+      throw std::runtime_error("the l2,1 ball projects a vector of the TV range: " + std::to_string(st.Mtrue) + " entries on this grid, " +
+                               std::to_string((long long)len) + " given");
+    DeviceMemory tmp;
+    T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
+    T* dc = tmp.alloc<T>(G_.N);
+    double* part = tmp.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
+    T* mp = tmp.alloc<T>(2 * NB);
+    upload_rows(st, (const T*)v, dv);
+    {
+      ExtProj<T> ext(st.spec, stream_);
+      ext.project(dv, false, part, mp, dc);
+      download_rows(st, dv, (T*)v);               // (synchronises the stream)
+    }
+  }
+
+  // sipx_l21_norm(_dev): ||TV x||_2,1 by the group-norm kernel of the projector and the first pass of its search (ext_group.hip)
+  void l21_norm(const void* x, void* out, bool on_device) override {
+    SIPX_HIP(hipSetDevice(device_));
+    if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed");
+    SetState<T> s;
+    configure_op(s, SIPX_OP_TV);
+    sipx_set_desc d{};
+    d.op = SIPX_OP_TV; d.proj = SIPX_PROJ_L21; d.mode = SIPX_MODE_WHOLE; d.pmax = 1.0;
+    configure_proj(s, &d);                     // the refusals, and the ExtSpec, of the set
+    long long H = 4;
+    for (int a = 0; a < 3; ++a) H = std::max<long long>(H, G_.st[a]);
+    H = (H + 3) / 4 * 4;
+    DeviceMemory tmp;
+    T* dxb = tmp.alloc<T>(G_.N + 2 * H);
+    T* dvb = tmp.alloc<T>(s.Mpad + H);
+    T* g = tmp.alloc<T>(G_.N);
+    T* dc = tmp.alloc<T>(G_.N);
+    double* part = tmp.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
+    T* mp = tmp.alloc<T>(2 * NB);
+    ProjScalars<T>* ps = tmp.alloc<ProjScalars<T>>(1);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
+    if (on_device) engine_after_caller();
+    SIPX_HIP(hipMemcpyAsync(dxb + H, x, G_.N * sizeof(T), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    K<T>::fwd(stream_, G_, s.nblk, s.dir, s.ih, dxb + H, dvb + H);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 1) * G_.N * sizeof(T));
+      l21_observe<T>(s.spec, dvb + H, g, ps, part, mp, dc, dout, stream_);
+    }
+    if (on_device) {
+      caller_after_engine();
+      SIPX_HIP(hipStreamSynchronize(stream_));      // (the scratch of this call goes when it returns)
+    } else {
+      SIPX_HIP(hipStreamSynchronize(stream_));
+      SIPX_HIP(hipMemcpy(out, dout, sizeof(T), hipMemcpyDeviceToHost));
+    }
+  }
+
   void project(const sipx_set_desc* d, void* v, int64_t len) override {
     SIPX_HIP(hipSetDevice(device_));
+    if (d->proj == SIPX_PROJ_L21) { project_l21(d, v, len); return; }
     Grid g1;
     g1.n[0] = len; g1.n[1] = 1; g1.n[2] = 1; g1.N = len; g1.st[0] = 1; g1.st[1] = len; g1.st[2] = len;
     DeviceMemory tmp;
@@ -3674,6 +3737,12 @@ class Engine : public EngineBase {
       throw std::runtime_error("per-fiber / per-slice l1, l2 and annulus sets with one radius per segment take single-process contexts only, this "
                                "one has a communicator, a slab decomposition or set ownership: use a scalar radius, or a single process");
   }
+  // the groups of the l2,1 ball span the blocks of the TV operator: the gather route of a slab-decomposed solve is single-block
+  void refuse_sharded_l21() const {
+    if (comm_ || slab_req_ || !owned_.empty())
+      throw std::runtime_error("the l2,1 ball on the TV operator (isotropic total variation) takes single-process contexts only, this one "
+                               "has a communicator, a slab decomposition or set ownership: use the l1 ball on TV, or a single process");
+  }
   // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
   static void check_l1_radii(const T* r, long long n) {
     for (long long k = 0; k < n; ++k)
@@ -3696,7 +3765,7 @@ class Engine : public EngineBase {
       if (s.nblk > 1) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
     }
     auto ext = [&](int kind) {
-      if (s.nblk > 1) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
+      if (s.nblk > 1 && kind != EXT_L21) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
       s.ext_kind = kind;
       s.spec.kind = kind;
       s.spec.ndim = ndim_;
@@ -3707,6 +3776,9 @@ class Engine : public EngineBase {
       s.spec.dir = dir;
       s.spec.pmin = d->pmin;
       s.spec.pmax = d->pmax;
+      s.spec.nblk = s.nblk;                                  // EXT_L21: the blocks side by side, full padded grids
+      s.spec.bstride = G_.N;
+      for (int q = 0; q < 3; ++q) s.spec.bdir[q] = q < s.nblk ? s.dir[q] : 0;
       s.prox = PX_EXT;
       need_ext_ = true;
     };
@@ -3818,6 +3890,15 @@ class Engine : public EngineBase {
         if (d->pmax < 0 || d->pmax != std::floor(d->pmax))
           throw std::runtime_error("cardinality behind the DFT: k must be a non-negative integer");
         ext(EXT_CARD_DFT);
+        break;
+      case SIPX_PROJ_L21:        // isotropic TV: groups across the blocks of the TV operator (l21.h), on the materialised vector
+        if (d->op != SIPX_OP_TV) throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
+        if (mode != SIPX_MODE_WHOLE) throw std::runtime_error("the l2,1 ball applies to the whole array (mode matrix/tensor)");
+        if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+        if (s.comp) throw std::runtime_error("the l2,1 ball takes no Minkowski component");
+        if (G_.N >= (1ll << 31)) throw std::runtime_error("the l2,1 ball: the grid needs fewer than 2^31 points");
+        refuse_sharded_l21();
+        ext(EXT_L21);
         break;
       case SIPX_PROJ_RANK: ext(EXT_RANK); break;
       case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;

@@ -2,6 +2,7 @@
 //   ext_transform.hip  DFT mask, l1 and cardinality behind the DFT, DCT, DWT
 //   ext_rank.hip       slice / matrix rank, nuclear norm
 //   ext_segments.hip   cardinality, l1, l2 and annulus per fiber / slice (seg_norm.h), relaxed histogram, subspace
+//   ext_group.hip      the l2,1 ball across the blocks of the TV operator (l21.h)
 // -- and what more than one family uses.
 #pragma once
 #define ROCBLAS_BETA_FEATURES_API 1
@@ -42,6 +43,7 @@ struct ExtImpl {
 template <typename T> ExtImpl<T>* make_transform_family(const ExtSpec& spec, hipStream_t stream);
 template <typename T> ExtImpl<T>* make_rank_family(const ExtSpec& spec, hipStream_t stream);
 template <typename T> ExtImpl<T>* make_segment_family(const ExtSpec& spec, hipStream_t stream);
+template <typename T> ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream);
 
 inline void fft_check(hipfftResult r, const char* what) {
   if (r != HIPFFT_SUCCESS) throw std::runtime_error(std::string("hipFFT: ") + what + " failed (" + std::to_string((int)r) + ")");

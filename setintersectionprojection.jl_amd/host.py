@@ -38,12 +38,17 @@ EXPORTED_SYMBOLS = [
     "sipx_learn_observations",
     "sipx_finalize_dev", "sipx_reset_dev", "sipx_download_dev", "sipx_set_caller_stream", "sipx_io_bytes",
     "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev", "sipx_segment_norms", "sipx_segment_norms_dev",
+    "sipx_l21_norm", "sipx_l21_norm_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
-        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13}
+        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14}
+TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
+# the engine's refusals of the l2,1 ball (csrc/engine.cpp, configure_proj), word for word
+L21_NEEDS_TV = "the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)"
+L21_WHOLE_ONLY = "the l2,1 ball applies to the whole array (mode matrix/tensor)"
 MODES = {"matrix": 0, "tensor": 0, "fiber": 1, "slice": 2}
 TRANSFORMS = {"DCT": 1, "wavelet": 2}
 SPECIAL_OPERATORS = ("DFT", "DCT", "wavelet", "curvelet")     # src/setup_constraints.jl:54
@@ -344,6 +349,20 @@ class Projector:
         self.pmin = self.pmax = 0.0
         self.transform = 0
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
+        self.op = None               # the operator a stand-alone call of the projector acts behind (l21: the TV range), None: the identity
+        if st == "l21":
+            # isotropic total variation: the l2,1 ball on the range of the TV operator (csrc/l21.h); max is the radius
+            cust = constraint.custom_TD_OP[0]
+            if constraint.TD_OP not in TV_OPERATORS or not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+                raise SipxError(L21_NEEDS_TV)
+            if self.mode:
+                raise SipxError(L21_WHOLE_ONLY)
+            if np.ndim(constraint.max) != 0:
+                raise SipxError("the l2,1 ball takes one radius (constraint.max a scalar)")
+            if not float(constraint.max) > 0:
+                raise SipxError("Radius of L1 ball is negative")
+            self.kind, self.pmax, self.op = "l21", float(constraint.max), "TV"
+            return
         if constraint.TD_OP == "DCT":
             # x -> C' P(C x) with the orthonormal DCT-II (get_projector.jl, special_operator_list branches); the l2 ball and
             # the annulus commute with an orthogonal transform and are applied to x itself
@@ -475,6 +494,8 @@ class Projector:
     def check_rows(self, op: "TDOperator"):
         """Host-side shape checks of the vectors the descriptor points at (the engine reads them unchecked)."""
         n = list(op.n)
+        if self.kind == "l21" and op.kind not in TV_OPERATORS:
+            raise SipxError(L21_NEEDS_TV)
         if op.kind == "custom" and (self.mode or self.transform or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank",
                                                                                      "nuclear", "histogram", "subspace")):
             raise SipxError("custom sparse operators take the whole-array projectors only")
@@ -531,9 +552,17 @@ class Projector:
         if v.dtype.type != self.TF or not v.flags.c_contiguous:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
-                                                                              "subspace")
+                                                                              "subspace", "l21")
+        if self.kind == "l21":       # the M-vector of the TV range in the reference's row order, on the grid
+            rows = TDOperator(self.op, self.comp_grid, self.TF).shape[0]
+            if v.shape != (rows,):
+                raise SipxError(f"the l2,1 ball projects a vector of the TV range: {rows} entries on this grid, {v.size} given")
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
         try:
+            if self.kind == "l21":
+                d = self.desc(self.op, False)
+                _chk(lib().sipx_project(ctx.h, C.byref(d), _ptr(v), C.c_int64(len(v))))
+                return v
             if grid_kind:
                 self.check_rows(TDOperator("identity", self.comp_grid, self.TF))
             elif self.kind == "bounds_vec" and (self.lb.shape != v.shape or self.ub.shape != v.shape):
@@ -589,7 +618,10 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
     orthogonal to d) of the array of shape TD_n is projected on its own, on the identity, D_x, D_y or D_z -- all with the scalar
     min / max, or each with its own: max (for the annulus min and / or max) a vector of nseg entries in the order segment_norms()
     returns them, a scalar beside a vector repeated.  The reference has no such projector ("only available for matrix or tensor mode, currently"); without the keyword its
-    error stays."""
+    error stays.
+
+    ("l21", "TV") in matrix / tensor mode -- isotropic total variation, the l2,1 ball of radius max on the TV range (csrc/l21.h) --
+    is the engine's own too and needs no keyword: the reference has no error to preserve there."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -601,6 +633,8 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
                 c.min, c.max = TF(c.min), TF(c.max)
         else:
             c.min, c.max = np.asarray(c.min, TF), np.asarray(c.max, TF)
+        if c.set_type == "l21":
+            Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
                             "define constraints per slice")
@@ -1741,6 +1775,44 @@ def segment_norms(x, comp_grid, TD_OP: str, app_mode, norm: str):
     finally:
         ctx.close()
     return out
+
+
+def l21_norm(x, comp_grid, TD_OP: str = "TV"):
+    """||TV x||_2,1, the isotropic total variation of x on a 2-D or 3-D grid: sum over the grid points of the l2 norm of the forward
+    differences that start there, one number of the working precision (that of x).  Computed by the kernel and the first-pass sum of
+    the ("l21", "TV") projector (sipx_l21_norm): used as the radius it leaves TV x untouched.  x: a numpy vector (a numpy scalar
+    comes back) or a 1-D torch tensor on a GPU (a tensor of one entry there; nothing crosses PCIe, the call orders itself against
+    torch's current stream)."""
+    if TD_OP not in TV_OPERATORS:
+        raise SipxError(L21_NEEDS_TV)
+    on_dev = _is_tensor(x)
+    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("l21_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    n, _ = _grid(comp_grid)
+    N = int(np.prod(n))
+    if on_dev:
+        import torch
+        _check_tensor("x", x, TF, N, None)
+        _check_one_hip_runtime()
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        out = torch.empty(1, dtype=x.dtype, device=torch.device("cuda", device))
+        xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
+        fn = lib().sipx_l21_norm_dev
+    else:
+        x = _check_array("x", x, TF, N)
+        device = None
+        out = np.empty(1, TF)
+        xp, op_ = _ptr(x), _ptr(out)
+        fn = lib().sipx_l21_norm
+    ctx = Context(comp_grid, TF, device)
+    try:
+        if on_dev:
+            ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        _chk(fn(ctx.h, xp, op_))
+    finally:
+        ctx.close()
+    return out if on_dev else out[0]
 
 
 def _dwt_check_grid(n):

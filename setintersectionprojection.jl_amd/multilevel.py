@@ -30,7 +30,7 @@ def constraint2coarse(constraint, comp_grid, cf):
             c.max = min(c.max, min(n))
         if c.set_type == "cardinality":
             c.max = min(c.max, int(np.prod(n)))
-        if c.set_type == "l1":
+        if c.set_type in ("l1", "l21"):      # (the l2,1 ball on TV sums one norm per grid point: it scales like the l1 ball)
             c.max = c.max / (cf ** 3 if dim3 else cf ** 2)
         if c.set_type == "l2":
             c.max = c.max / (math.sqrt(cf ** 3) if dim3 else cf)
