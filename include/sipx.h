@@ -36,7 +36,7 @@ enum { SIPX_F32 = 0, SIPX_F64 = 1 };
 /* Transform-domain operator A_i, matrix-free.  Replaces the SparseMatrixCSC TD_OP[i] built by
  * get_TD_operator / get_discrete_Grad (src/get_TD_operator.jl:12-95, src/get_discrete_Grad.jl:16-76);
  * the shim maps set_Prop.tag[i][2] ("identity","D_x","D_y","D_z","TV") + comp_grid.n/.d to it.
- * 2-D grids: D_x = dim 1, D_z = dim 2 (pass n3 = 1); TV = [D_z; D_x] (2-D), [D_z; D_y; D_x] (3-D). */
+ * 2-D grids: D_x = dim 1, D_z = dim 2 (pass n3 = 1); TV = [D_z; D_x] (2-D), [D_z; D_y; D_x] (3-D); TV_xy = [D_y; D_x] (3-D only). */
 enum { SIPX_OP_IDENTITY = 0, SIPX_OP_DX = 1, SIPX_OP_DY = 2, SIPX_OP_DZ = 3, SIPX_OP_TV = 4,
        SIPX_OP_CSC = 5 /* a caller-supplied sparse matrix (constraint.custom_TD_OP[1], setup_constraints.jl:70-72): the
                           SparseMatrixCSC arrays in sipx_set_desc.csc_*, 0-based.  Its A'A is passed in CDS when it is banded
@@ -45,7 +45,13 @@ enum { SIPX_OP_IDENTITY = 0, SIPX_OP_DX = 1, SIPX_OP_DY = 2, SIPX_OP_DZ = 3, SIP
                           operator's own arrays, which is what the reference does when a set is not banded: the AtA stay
                           sparse (PARSDMM_precompute_distribute.jl:51-59) and CG runs on the sparse Q (argmin_x.jl:42-51).
                           Needs N, rows and stored entries below 2^31; not available with SIPX_Q_STENCIL, a communicator,
-                          Minkowski components or sipx_warm_start_from */ };
+                          Minkowski components or sipx_warm_start_from */,
+       SIPX_OP_TV_XY = 6 /* the in-plane gradient of a 3-D grid, [D_y; D_x] (no counterpart in the reference): the rows of D_y
+                          first, column-major over (n1, n2-1, n3), then those of D_x over (n1-1, n2, n3), entries -+fl(1/h) as in
+                          D_y / D_x; A'A has the offsets {0, +-1, +-n1}.  It takes every set SIPX_OP_TV takes in mode WHOLE, and
+                          SIPX_PROJ_L21 per z-slice.  A 2-D grid refuses it (there SIPX_OP_TV is in-plane already), and so do
+                          contexts with a communicator, a slab decomposition or set ownership, Minkowski components and
+                          sipx_warm_start_from */ };
 
 /* Projector descriptor replacing the opaque closure P_sub[i] (src/get_projector.jl:3-103). */
 enum {
@@ -94,7 +100,15 @@ enum {
                                 ball is not written (csrc/l21.h).  Holds no replaceable vectors (sipx_set_data refuses).  Contexts
                                 with a communicator, a slab decomposition or set ownership refuse it.  sipx_project takes the
                                 M-vector of the TV range in the reference's row order on the context's grid; sipx_l21_norm observes
-                                the norm */
+                                the norm.
+                                op SIPX_OP_TV_XY (3-D grids): mode WHOLE is the same ball on the in-plane gradient (groups of 0 to 2
+                                members).  Mode SLICE with dir = 2 is the ball PER FRAME, { v : sum_{p in frame k} ||v_p||_2 <= tau_k
+                                for every k }, frame k the grid points (., ., k): the l1 rule of a slice set (SIPX_PROJ_L1, mode SLICE)
+                                on the n1 n2 group norms of every frame, a frame inside its ball is not written (csrc/l21_seg.h).
+                                Radii as for the per-segment l1 ball: ub = NULL gives every frame pmax, ub = TF[n3] frame k its own,
+                                replaceable through sipx_set_data(_dev); an entry that is not > 0 is refused by every host path,
+                                from device memory it zeroes a frame that is not all zero.  Other fiber / slice modes are refused:
+                                frames run along z.  sipx_l21_norms observes the norms */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -352,6 +366,12 @@ int sipx_segment_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, int norm, c
  * in device memory of the context's GPU, ordered like sipx_download_dev against the caller's stream. */
 int sipx_l21_norm(sipx_ctx* ctx, const void* x, void* out);
 int sipx_l21_norm_dev(sipx_ctx* ctx, const void* x, void* out);
+/* The same behind an operator and per application mode of SIPX_PROJ_L21: op SIPX_OP_TV or SIPX_OP_TV_XY with mode WHOLE writes one TF,
+ * op SIPX_OP_TV_XY with mode SLICE, dir = 2 writes the n3 numbers (TF)asum_k, the sums of the group norms of every frame -- the very
+ * values the per-frame projector compares with its radii, so radii observed on x leave [D_y; D_x] x unwritten.  *nseg (if not NULL)
+ * receives the number of values; x = out = NULL only asks for it.  Every other combination is refused as sipx_add_set refuses it. */
+int sipx_l21_norms(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
+int sipx_l21_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
 /* nearest-neighbour resampling of an array of shape nc to shape nf, the grid transfer of PARSDMM_multi_level:
  * out[k] = in[round(1 + (k-1)(nc-1)/(nf-1))] per axis (Interpolations.BSpline(Constant()) evaluated on
  * range(1, stop=nc, length=nf); src/PARSDMM_multi_level.jl:41-45,61-65, src/interpolate_y_l.jl:32-88) */

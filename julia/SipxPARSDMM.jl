@@ -57,6 +57,9 @@ mutable struct SipxLog                 # sipx_log: flat row-major arrays the cal
 end
 
 const OPS  = Dict("identity" => 0, "D_x" => 1, "D_y" => 2, "D_z" => 3, "TV" => 4, "D2D" => 4, "D3D" => 4)
+# SIPX_OP_TV_XY (include/sipx.h): the in-plane gradient [D_y; D_x] of a 3-D grid, libsipx's own.  The reference's get_TD_operator has no
+# such name, so setup_constraints of this shim cannot build the set; the code is mirrored for callers of the C ABI.
+const SIPX_OP_TV_XY = 6
 const MODE = Dict("matrix" => 0, "tensor" => 0, "fiber" => 1, "slice" => 2)
 const SPECIAL = ("DFT", "DCT", "wavelet", "curvelet")          # src/setup_constraints.jl:54
 # the seven @timeit sections of src/PARSDMM.jl:40,100,105,113,152,163,229

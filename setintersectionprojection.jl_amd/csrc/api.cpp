@@ -144,6 +144,12 @@ int sipx_l21_norm(sipx_ctx* c, const void* x, void* out) {
 int sipx_l21_norm_dev(sipx_ctx* c, const void* x, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norm(x, out, true))
 }
+int sipx_l21_norms(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(op, mode, dir, x, out, nseg, false))
+}
+int sipx_l21_norms_dev(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(op, mode, dir, x, out, nseg, true))
+}
 int sipx_get_Q(sipx_ctx* c, void* Q, int64_t* offsets, int* d) { SIPX_TRY(c->e->get_Q(Q, offsets, d)) }
 int sipx_q_terms(sipx_ctx* c, int* bands, int* matrix_free) { SIPX_TRY(c->e->q_terms(bands, matrix_free)) }
 int sipx_time_spmv(sipx_ctx* c, int reps, double* avg_ms) { SIPX_TRY(*avg_ms = c->e->time_spmv(reps)) }

@@ -330,6 +330,10 @@ class Engine : public EngineBase {
     SetState<T> s;
     if (d->op == SIPX_OP_CSC) configure_custom(s, d);
     else configure_op(s, d->op);
+    if (s.op == SIPX_OP_TV_XY) {
+      refuse_sharded_tv_xy();
+      if (d->component) throw std::runtime_error("the TV_xy operator takes no Minkowski component");
+    }
     configure_proj(s, d);
     if (s.custom && (s.comp || s.ext_kind))
       throw std::runtime_error("custom sparse operators (SIPX_OP_CSC): Minkowski components and library-backed projectors are not available; "
@@ -428,7 +432,8 @@ class Engine : public EngineBase {
     feasibility_only_ = feasibility_only != 0;
     for (const auto& s : sets_) {
       if (s.seg_radii) refuse_sharded_radii();
-      if (s.ext_kind == EXT_L21) refuse_sharded_l21();
+      if (s.op == SIPX_OP_TV_XY) refuse_sharded_tv_xy();
+      if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG) refuse_sharded_l21();
     }
     FinalizePlan P;
     plan_sets();
@@ -2759,6 +2764,7 @@ class Engine : public EngineBase {
     for (int i = 0; i < p_n_; ++i) {
       SetState<T>&f = sets_[i], &g = c->sets_[i];
       if (f.custom || g.custom || f.nblk != g.nblk) throw std::runtime_error("warm start: operator kinds differ between the levels");
+      if (f.op == SIPX_OP_TV_XY || g.op == SIPX_OP_TV_XY) throw std::runtime_error("warm start: the TV_xy operator is not built for multilevel solves");
       for (int q = 0; q < f.nblk; ++q)
         if (f.dir[q] != g.dir[q]) throw std::runtime_error("warm start: operator kinds differ between the levels");
       if (!f.owned || !g.owned) continue;
@@ -2956,7 +2962,7 @@ class Engine : public EngineBase {
   // allocated and no stream or event is created; the new data holds from the next sipx_reset on (a solve in progress is given
   // up: the host form stages through the engine's scratch).
   long long data_len(const SetState<T>& s) const {
-    if (s.seg_radii) return seg_count(s.spec);
+    if (s.seg_radii) return s.ext_kind == EXT_L21_SEG ? G_.n[2] : seg_count(s.spec);
     if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;
     return G_.n[s.bdir] - ((s.nblk == 1 && s.dir[0] == s.bdir) ? 1 : 0);
   }
@@ -2989,7 +2995,7 @@ class Engine : public EngineBase {
                                "subspace bases are fixed at sipx_add_set" + way_out);
     if (s.seg_radii && lb && s.ext_kind != EXT_ANNULUS_SEG)
       throw std::runtime_error(what + ": only the annulus has inner radii (lb); the radii of an l1 / l2 set are its ub");
-    if (s.seg_radii && s.ext_kind == EXT_L1_SEG && ub && !on_device) check_l1_radii((const T*)ub, seg_count(s.spec));
+    if (s.seg_radii && (s.ext_kind == EXT_L1_SEG || s.ext_kind == EXT_L21_SEG) && ub && !on_device) check_l1_radii((const T*)ub, data_len(s));
     if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
       throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
     if (!lb && !ub) return;
@@ -3307,12 +3313,14 @@ class Engine : public EngineBase {
   // SIPX_PROJ_L21 of sipx_project: the M-vector of the TV range in the reference's row order, through the packing of a TV set's y / l
   void project_l21(const sipx_set_desc* d, void* v, int64_t len) {
     SetState<T> st;
-    if (d->op != SIPX_OP_TV) throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
-    configure_op(st, SIPX_OP_TV);
+    if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY)
+      throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
+    configure_op(st, d->op);
     configure_proj(st, d);
     if (len != st.Mtrue)
-      throw std::runtime_error("the l2,1 ball projects a vector of the TV range: " + std::to_string(st.Mtrue) + " entries on this grid, " +
-                               std::to_string((long long)len) + " given");
+      throw std::runtime_error(std::string("the l2,1 ball projects a vector of the ") + (d->op == SIPX_OP_TV ? "TV" : "TV_xy") + " range: " +
+                               std::to_string(st.Mtrue) + " entries on this grid, " + std::to_string((long long)len) + " given");
+    st.spec.ub = st.host_ub.empty() ? nullptr : st.host_ub.data();      // (per frame: one radius each)
     DeviceMemory tmp;
     T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
     T* dc = tmp.alloc<T>(G_.N);
@@ -3328,13 +3336,26 @@ class Engine : public EngineBase {
 
   // sipx_l21_norm(_dev): ||TV x||_2,1 by the group-norm kernel of the projector and the first pass of its search (ext_group.hip)
   void l21_norm(const void* x, void* out, bool on_device) override {
-    SIPX_HIP(hipSetDevice(device_));
     if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed");
+    l21_norms(SIPX_OP_TV, SIPX_MODE_WHOLE, 0, x, out, nullptr, on_device);
+  }
+  // sipx_l21_norms(_dev): the same behind TV or TV_xy, and per z-slice of TV_xy: the n3 sums the per-frame projector compares with
+  // its radii (k_l21_frames, pass 1)
+  void l21_norms(int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device) override {
+    SIPX_HIP(hipSetDevice(device_));
+    if (op != SIPX_OP_TV && op != SIPX_OP_TV_XY)
+      throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
     SetState<T> s;
-    configure_op(s, SIPX_OP_TV);
+    configure_op(s, op);
+    if (op == SIPX_OP_TV_XY) refuse_sharded_tv_xy();
     sipx_set_desc d{};
-    d.op = SIPX_OP_TV; d.proj = SIPX_PROJ_L21; d.mode = SIPX_MODE_WHOLE; d.pmax = 1.0;
+    d.op = op; d.proj = SIPX_PROJ_L21; d.mode = mode; d.dir = dir; d.pmax = 1.0;
     configure_proj(s, &d);                     // the refusals, and the ExtSpec, of the set
+    const bool frames = s.ext_kind == EXT_L21_SEG;
+    const long long nout = frames ? G_.n[2] : 1;
+    if (nseg) *nseg = nout;
+    if (!x && !out) return;                    // (a query of the length)
+    if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed");
     long long H = 4;
     for (int a = 0; a < 3; ++a) H = std::max<long long>(H, G_.st[a]);
     H = (H + 3) / 4 * 4;
@@ -3346,21 +3367,22 @@ class Engine : public EngineBase {
     double* part = tmp.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
     T* mp = tmp.alloc<T>(2 * NB);
     ProjScalars<T>* ps = tmp.alloc<ProjScalars<T>>(1);
-    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(nout);
     if (on_device) engine_after_caller();
     SIPX_HIP(hipMemcpyAsync(dxb + H, x, G_.N * sizeof(T), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
     K<T>::fwd(stream_, G_, s.nblk, s.dir, s.ih, dxb + H, dvb + H);
     {
       ObserverGuard og(observer());
       ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 1) * G_.N * sizeof(T));
-      l21_observe<T>(s.spec, dvb + H, g, ps, part, mp, dc, dout, stream_);
+      if (frames) l21_seg_observe<T>(s.spec, dvb + H, g, dout, stream_);
+      else l21_observe<T>(s.spec, dvb + H, g, ps, part, mp, dc, dout, stream_);
     }
     if (on_device) {
       caller_after_engine();
       SIPX_HIP(hipStreamSynchronize(stream_));      // (the scratch of this call goes when it returns)
     } else {
       SIPX_HIP(hipStreamSynchronize(stream_));
-      SIPX_HIP(hipMemcpy(out, dout, sizeof(T), hipMemcpyDeviceToHost));
+      SIPX_HIP(hipMemcpy(out, dout, nout * sizeof(T), hipMemcpyDeviceToHost));
     }
   }
 
@@ -3598,7 +3620,17 @@ class Engine : public EngineBase {
       for (int q = 0; q < 4; ++q) rc[q] += c[q];
     }
     o += ", \"rank_route\": {\"calls\": " + std::to_string(rc[0]) + ", \"warm_started_subspace\": " + std::to_string(rc[1]) +
-         ", \"full_decomposition\": " + std::to_string(rc[2]) + ", \"products_with_gram\": " + std::to_string(rc[3]) + "}}";
+         ", \"full_decomposition\": " + std::to_string(rc[2]) + ", \"products_with_gram\": " + std::to_string(rc[3]) + "}";
+    // per-frame l2,1 sets: Michelot's passes of the last projection (total over the frames, most in one frame, frames)
+    long long fc[4] = {0, 0, 0, 0};
+    for (const auto& st : sets_) {
+      if (!st.ext || st.ext_kind != EXT_L21_SEG) continue;
+      long long c[4];
+      st.ext->route_counts(c);
+      fc[0] += c[0]; fc[1] = std::max(fc[1], c[1]); fc[3] += c[3];
+    }
+    o += ", \"l21_frames\": {\"passes_total\": " + std::to_string(fc[0]) + ", \"passes_max\": " + std::to_string(fc[1]) +
+         ", \"frames\": " + std::to_string(fc[3]) + "}}";
     if (!peek) start_stats(enable);
     return o.c_str();
   }
@@ -3743,6 +3775,12 @@ class Engine : public EngineBase {
       throw std::runtime_error("the l2,1 ball on the TV operator (isotropic total variation) takes single-process contexts only, this one "
                                "has a communicator, a slab decomposition or set ownership: use the l1 ball on TV, or a single process");
   }
+  // TV_xy is an operator of single-process contexts: the slab routes know TV's one block per dimension only
+  void refuse_sharded_tv_xy() const {
+    if (comm_ || slab_req_ || !owned_.empty())
+      throw std::runtime_error("the TV_xy operator takes single-process contexts only, this one has a communicator, a slab decomposition "
+                               "or set ownership: use D_x and D_y sets, or a single process");
+  }
   // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
   static void check_l1_radii(const T* r, long long n) {
     for (long long k = 0; k < n; ++k)
@@ -3762,10 +3800,14 @@ class Engine : public EngineBase {
       throw std::runtime_error("unknown application mode");
     if (mode != SIPX_MODE_WHOLE) {
       if (dir < 0 || dir >= ndim_) throw std::runtime_error("application mode: direction out of range for this grid");
-      if (s.nblk > 1) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
+      // the one multi-block set with a mode of its own: the l2,1 ball per z-slice on TV_xy (l21_seg.h)
+      const bool frames = d->proj == SIPX_PROJ_L21 && s.op == SIPX_OP_TV_XY && d->transform == SIPX_TRANSFORM_NONE;
+      if (frames && !(mode == SIPX_MODE_SLICE && dir == 2))
+        throw std::runtime_error("the l2,1 ball on TV_xy: frames run along z -- the mode must be (slice, z), or tensor for the whole array");
+      if (s.nblk > 1 && !frames) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
     }
     auto ext = [&](int kind) {
-      if (s.nblk > 1 && kind != EXT_L21) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
+      if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
       s.ext_kind = kind;
       s.spec.kind = kind;
       s.spec.ndim = ndim_;
@@ -3892,13 +3934,24 @@ class Engine : public EngineBase {
         ext(EXT_CARD_DFT);
         break;
       case SIPX_PROJ_L21:        // isotropic TV: groups across the blocks of the TV operator (l21.h), on the materialised vector
-        if (d->op != SIPX_OP_TV) throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
-        if (mode != SIPX_MODE_WHOLE) throw std::runtime_error("the l2,1 ball applies to the whole array (mode matrix/tensor)");
-        if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+        if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY)
+          throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
+        if (mode != SIPX_MODE_WHOLE && d->op == SIPX_OP_TV) throw std::runtime_error("the l2,1 ball applies to the whole array (mode matrix/tensor)");
         if (s.comp) throw std::runtime_error("the l2,1 ball takes no Minkowski component");
         if (G_.N >= (1ll << 31)) throw std::runtime_error("the l2,1 ball: the grid needs fewer than 2^31 points");
         refuse_sharded_l21();
-        ext(EXT_L21);
+        if (mode == SIPX_MODE_WHOLE) {
+          if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+          ext(EXT_L21);
+        } else {                 // per frame on TV_xy (checked above): the scalar, or one radius per frame in ub
+          if (!d->ub && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+          ext(EXT_L21_SEG);
+          if (d->ub) {
+            s.seg_radii = true;
+            s.host_ub.assign((const T*)d->ub, (const T*)d->ub + G_.n[2]);
+            check_l1_radii(s.host_ub.data(), G_.n[2]);
+          }
+        }
         break;
       case SIPX_PROJ_RANK: ext(EXT_RANK); break;
       case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;
@@ -4069,6 +4122,12 @@ class Engine : public EngineBase {
       case SIPX_OP_TV:                                   // vcat(D_z[,D_y],D_x): get_discrete_Grad.jl:31-33,69-72
         if (ndim_ == 2) { s.nblk = 2; s.dir[0] = 1; s.dir[1] = 0; }
         else { s.nblk = 3; s.dir[0] = 2; s.dir[1] = 1; s.dir[2] = 0; }
+        break;
+      case SIPX_OP_TV_XY:                                // vcat(D_y,D_x) on a 3-D grid: the in-plane part of TV
+        if (ndim_ == 2)
+          throw std::runtime_error("provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) "
+                                   "for options (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)");
+        s.nblk = 2; s.dir[0] = 1; s.dir[1] = 0;
         break;
       default: throw std::runtime_error("unknown operator kind");
     }

@@ -12,6 +12,7 @@
 // are 16-byte aligned and the VW points lie on one grid line), one point otherwise.  g lives in the projector's own memory.
 #include "ext_family.h"
 #include "l21.h"
+#include "l21_seg.h"
 
 namespace sipx {
 
@@ -57,15 +58,28 @@ __global__ __launch_bounds__(BLOCK) void k_l21_norms(L21Args a, const T* __restr
   }
 }
 
-template <typename T, int NBLK, int VW>
+// FRAMES (EXT_L21_SEG, l21_seg.h): every z-slice has its own threshold and decision, theta[k] / need[k] of k_l21_frames at the z
+// coordinate of the VW points (one grid line: one frame); a frame with need == 0 is skipped without a store, need == 3 is zeroed
+template <typename T, int NBLK, int VW, bool FRAMES>
 __global__ __launch_bounds__(BLOCK) void k_l21_scale(L21Args a, T* __restrict__ v, const T* __restrict__ g,
-                                                     const ProjScalars<T>* __restrict__ ps, const T* __restrict__ theta) {
-  if (!ps->need) return;
-  const T th = theta ? theta[0] : ps->theta;          // (Float64: the threshold k_l21_theta_final left)
+                                                     const ProjScalars<T>* __restrict__ ps, const T* __restrict__ theta,
+                                                     const int* __restrict__ need) {
+  T th = T(0);
+  if constexpr (!FRAMES) {
+    if (!ps->need) return;
+    th = theta ? theta[0] : ps->theta;                // (Float64: the threshold k_l21_theta_final left)
+  }
   const unsigned nvec = (unsigned)(a.G.N / VW), step = gridDim.x * BLOCK;
   for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
     const unsigned p = vi * VW;
     const Coord c = coords(a.G, (long long)p);
+    bool zero = false;
+    if constexpr (FRAMES) {
+      const int act = need[c.k];
+      if (!act) continue;
+      th = theta[c.k];
+      zero = act == 3;
+    }
     const Vec<T, VW> gv = ldv<T, VW>(g + p);
     T f[VW];
 #pragma unroll
@@ -77,7 +91,7 @@ __global__ __launch_bounds__(BLOCK) void k_l21_scale(L21Args a, T* __restrict__ 
       T* vq = v + (size_t)q * (size_t)a.bstride + p;
       Vec<T, VW> x = ldv<T, VW>(vq);
 #pragma unroll
-      for (int k = 0; k < VW; ++k) x.v[k] = x.v[k] * f[k];
+      for (int k = 0; k < VW; ++k) x.v[k] = FRAMES && zero ? T(0) : x.v[k] * f[k];
       bool all = true;
 #pragma unroll
       for (int k = 0; k < VW; ++k) all = all && mem[k];
@@ -153,8 +167,11 @@ __global__ void k_l21_pick(const ProjScalars<T>* __restrict__ ps, T* __restrict_
 }
 
 static void l21_check_spec(const ExtSpec& sp) {
-  if (sp.nblk != 2 && sp.nblk != 3) throw std::runtime_error("the l2,1 ball needs the 2 or 3 blocks of the TV operator");
-  if (sp.nblk != sp.ndim) throw std::runtime_error("the l2,1 ball: one block per grid dimension");
+  if (sp.nblk != 2 && sp.nblk != 3) throw std::runtime_error("the l2,1 ball needs the 2 or 3 blocks of the TV or TV_xy operator");
+  if (sp.nblk > sp.ndim) throw std::runtime_error("the l2,1 ball: more blocks than grid dimensions");
+  for (int q = 0; q < sp.nblk; ++q)
+    for (int r = 0; r < q; ++r)
+      if (sp.bdir[q] == sp.bdir[r]) throw std::runtime_error("the l2,1 ball: two blocks along one direction");
   if (sp.G.N >= (1ll << 31)) throw std::runtime_error("the l2,1 ball: the grid needs fewer than 2^31 points");
   if (sp.bstride < sp.G.N) throw std::runtime_error("the l2,1 ball: the blocks overlap");
   for (int q = 0; q < sp.nblk; ++q)
@@ -179,6 +196,7 @@ static void l21_norms(hipStream_t s, const ExtSpec& sp, const T* v, T* g) {
   const L21Args a = l21_args(sp);
   const bool wide = l21_wide(sp, v, g);
   const int grid = fit_grid(sp.G.N / (wide ? W : 1), NB);
+  ObsScope obs(KID_L21_NORMS, s, (double)(sp.nblk + 1) * sp.G.N * sizeof(T));
   if (sp.nblk == 2 && wide) hipLaunchKernelGGL((k_l21_norms<T, 2, W>), dim3(grid), dim3(BLOCK), 0, s, a, v, g);
   else if (sp.nblk == 2) hipLaunchKernelGGL((k_l21_norms<T, 2, 1>), dim3(grid), dim3(BLOCK), 0, s, a, v, g);
   else if (wide) hipLaunchKernelGGL((k_l21_norms<T, 3, W>), dim3(grid), dim3(BLOCK), 0, s, a, v, g);
@@ -191,10 +209,25 @@ static void l21_scale(hipStream_t s, const ExtSpec& sp, T* v, const T* g, const 
   const L21Args a = l21_args(sp);
   const bool wide = l21_wide(sp, v, g);
   const int grid = fit_grid(sp.G.N / (wide ? W : 1), NB);
-  if (sp.nblk == 2 && wide) hipLaunchKernelGGL((k_l21_scale<T, 2, W>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta);
-  else if (sp.nblk == 2) hipLaunchKernelGGL((k_l21_scale<T, 2, 1>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta);
-  else if (wide) hipLaunchKernelGGL((k_l21_scale<T, 3, W>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta);
-  else hipLaunchKernelGGL((k_l21_scale<T, 3, 1>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta);
+  const int* none = nullptr;
+  ObsScope obs(KID_L21_SCALE, s, (double)(2 * sp.nblk + 1) * sp.G.N * sizeof(T));
+  if (sp.nblk == 2 && wide) hipLaunchKernelGGL((k_l21_scale<T, 2, W, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
+  else if (sp.nblk == 2) hipLaunchKernelGGL((k_l21_scale<T, 2, 1, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
+  else if (wide) hipLaunchKernelGGL((k_l21_scale<T, 3, W, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
+  else hipLaunchKernelGGL((k_l21_scale<T, 3, 1, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
+  SIPX_HIP(hipGetLastError());
+}
+// the per-frame form: two blocks on a 3-D grid (l21_seg_check_spec)
+template <typename T>
+static void l21_scale_frames(hipStream_t s, const ExtSpec& sp, T* v, const T* g, const T* theta, const int* need) {
+  constexpr int W = l21_vec_width<T>();
+  const L21Args a = l21_args(sp);
+  const bool wide = l21_wide(sp, v, g);
+  const int grid = fit_grid(sp.G.N / (wide ? W : 1), NB);
+  const ProjScalars<T>* none = nullptr;
+  ObsScope obs(KID_L21_SCALE, s, (double)(2 * sp.nblk + 1) * sp.G.N * sizeof(T));
+  if (wide) hipLaunchKernelGGL((k_l21_scale<T, 2, W, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, none, theta, need);
+  else hipLaunchKernelGGL((k_l21_scale<T, 2, 1, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, none, theta, need);
   SIPX_HIP(hipGetLastError());
 }
 
@@ -232,11 +265,98 @@ struct GroupProj : ExtImpl<T> {
   }
 };
 
+// ---- EXT_L21_SEG: the l2,1 ball of every z-slice on the range of TV_xy (l21_seg.h) -------------------------------------------------------
+//     k_l21_norms     as above, two blocks on the 3-D grid                                    reads 2 N words, writes N
+//     k_l21_frames    one workgroup per frame on g alone: asum, the decision, Michelot's passes  reads N (LDS) or passes * N
+//     k_l21_scale     the per-frame form; frames inside their ball are skipped without a store  reads up to 3 N, writes up to 2 N
+static void l21_seg_check_spec(const ExtSpec& sp) {
+  l21_check_spec(sp);
+  if (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0)
+    throw std::runtime_error("the l2,1 ball per frame needs the blocks (D_y, D_x) of the TV_xy operator on a 3-D grid");
+  if (sp.mode != SIPX_MODE_SLICE || sp.dir != 2) throw std::runtime_error("the l2,1 ball on TV_xy: frames run along z, the mode is (slice, z)");
+}
+template <typename T, bool OBSERVE>
+static void l21_frames(hipStream_t s, const ExtSpec& sp, const T* g, T tau, const T* rmax, T* theta, int* need, T* asum, int* passes) {
+  const long long L = sp.G.n[0] * sp.G.n[1], nf = sp.G.n[2];
+  L21SegPlan plan = l21_seg_plan(L, nf, (int)sizeof(T));
+  if (OBSERVE) { plan.lds = 0; plan.lds_bytes = 0; }
+  ObsScope obs(KID_L21_FRAMES, s, (double)sp.G.N * sizeof(T));
+  if (rmax)
+    hipLaunchKernelGGL((k_l21_frames<T, true, OBSERVE>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, s, plan, (unsigned)L, (unsigned)nf, g, tau,
+                       rmax, theta, need, asum, passes);
+  else
+    hipLaunchKernelGGL((k_l21_frames<T, false, OBSERVE>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, s, plan, (unsigned)L, (unsigned)nf, g, tau,
+                       rmax, theta, need, asum, passes);
+  SIPX_HIP(hipGetLastError());
+}
+
+// Nothing is kept between calls: the call of the feasibility estimate and the one of the y update are independent, reset() has
+// nothing to forget.  Built with ExtSpec::ub every frame has its own radius (rmax, n3 entries), sipx_set_data replaces them.
+template <typename T>
+struct FrameProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  T *g = nullptr, *theta = nullptr, *asum = nullptr, *rmax = nullptr;
+  int *need = nullptr, *passes = nullptr;
+  long long nf = 0;
+  FrameProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    l21_seg_check_spec(sp);
+    nf = sp.G.n[2];
+    if (!sp.ub && !((T)sp.pmax > T(0))) throw std::runtime_error("Radius of L1 ball is negative");
+    if (sp.ub) {
+      const T* h = (const T*)sp.ub;
+      for (long long k = 0; k < nf; ++k)
+        if (!(h[k] > T(0))) throw std::runtime_error("Radius of L1 ball is negative");
+    }
+    g = this->template alloc<T>(sp.G.N);
+    theta = this->template alloc<T>(nf);
+    asum = this->template alloc<T>(nf);
+    need = this->template alloc<int>(2 * nf);
+    passes = need + nf;
+    SIPX_HIP(hipMemset(need, 0, sizeof(int) * 2 * (size_t)nf));      // (route_counts may be asked before the first projection)
+    if (sp.ub) {
+      rmax = this->template alloc<T>(nf);
+      SIPX_HIP(hipMemcpy(rmax, sp.ub, sizeof(T) * (size_t)nf, hipMemcpyHostToDevice));
+    }
+  }
+  void project(T* v, bool, double*, T*, T*) override {
+    l21_norms<T>(stream, sp, v, g);
+    l21_frames<T, false>(stream, sp, g, (T)sp.pmax, rmax, theta, need, asum, passes);
+    l21_scale_frames<T>(stream, sp, v, g, theta, need);
+  }
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    if (!rmax) ExtImpl<T>::set_data(new_lb, new_ub, on_device);
+    if (new_lb) throw std::runtime_error("only the annulus has inner radii: pass the radii of this set as ub");
+    if (new_ub)
+      SIPX_HIP(hipMemcpyAsync(rmax, new_ub, sizeof(T) * (size_t)nf, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  }
+  // the Michelot passes of the last call, per frame (tools/l21_frames_bench.py)
+  void route_counts(long long out[4]) const override {
+    std::vector<int> h((size_t)nf);
+    SIPX_HIP(hipStreamSynchronize(stream));
+    SIPX_HIP(hipMemcpy(h.data(), passes, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
+    out[0] = out[1] = out[2] = 0; out[3] = nf;
+    for (int x : h) { out[0] += x; out[1] = std::max<long long>(out[1], x); }
+  }
+};
+
 template <typename T>
 ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
+  if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);
   if (spec.kind != EXT_L21) throw std::runtime_error("unknown external projector");
   return new GroupProj<T>(spec, stream);
 }
+
+// out[k] (device, n3 entries) <- (T)asum_k of the frames of a materialised vector in the layout of an EXT_L21_SEG spec: k_l21_norms
+// into g (N entries), then pass 1 of k_l21_frames -- the numbers the projector compares with the radii
+template <typename T>
+void l21_seg_observe(const ExtSpec& spec, const T* v, T* g, T* out, hipStream_t stream) {
+  l21_seg_check_spec(spec);
+  l21_norms<T>(stream, spec, v, g);
+  l21_frames<T, true>(stream, spec, g, T(0), (const T*)nullptr, (T*)nullptr, (int*)nullptr, out, (int*)nullptr);
+}
+template void l21_seg_observe<float>(const ExtSpec&, const float*, float*, float*, hipStream_t);
+template void l21_seg_observe<double>(const ExtSpec&, const double*, double*, double*, hipStream_t);
 
 // out[0] (device) <- ||v||_2,1 of a materialised vector in the layout of spec: k_l21_norms into g (N entries), then the first pass
 // of a search with a new state and an infinite radius -- the sum, and the rounding to T, of the projector's own decision

@@ -1,6 +1,6 @@
 // Projectors that act on a materialised vector v (one block of the padded layout): library transforms
-// (hipFFT / rocSOLVER / rocBLAS / hipCUB sort) and the per-fiber / per-slice selections; see ext_proj.hip.  EXT_L21 alone acts on
-// the nblk blocks of the TV operator at once (ext_group.hip).
+// (hipFFT / rocSOLVER / rocBLAS / hipCUB sort) and the per-fiber / per-slice selections; see ext_proj.hip.  EXT_L21 and EXT_L21_SEG alone
+// act on the nblk blocks of the TV / TV_xy operator at once (ext_group.hip).
 #pragma once
 #include "sipx_common.h"
 
@@ -8,7 +8,8 @@ namespace sipx {
 
 enum { EXT_L1_DFT = 1, EXT_RANK = 2, EXT_NUCLEAR = 3, EXT_CARD_SEG = 4, EXT_HISTOGRAM = 5, EXT_SUBSPACE = 6, EXT_DFT_MASK = 7, EXT_DCT = 8, EXT_DWT = 9, EXT_CARD_DFT = 10,
        EXT_L1_SEG = 11, EXT_L2_SEG = 12, EXT_ANNULUS_SEG = 13 /* l1 / l2 / annulus per fiber or slice */,
-       EXT_L21 = 14 /* the l2,1 ball across the blocks of the TV operator (l21.h) */ };
+       EXT_L21 = 14 /* the l2,1 ball across the blocks of the TV / TV_xy operator (l21.h) */,
+       EXT_L21_SEG = 15 /* the l2,1 ball of every z-slice across the blocks of TV_xy (l21_seg.h) */ };
 
 // What an ExtProj acts on: the valid extents `dims` (TD_n of the operator) inside the padded grid G (strides G.st),
 // split into segments by the application mode (whole array, fibers along `dir`, slices orthogonal to `dir`).
@@ -26,7 +27,7 @@ struct ExtSpec {
   const void* basis = nullptr;    // EXT_SUBSPACE: host TF[basis_rows x basis_cols], column-major
   long long basis_rows = 0;
   int basis_cols = 0, basis_orth = 0;
-  int nblk = 0;                   // EXT_L21: blocks of the operator (2 or 3), block q at v + q * bstride holding the differences along bdir[q]
+  int nblk = 0;                   // EXT_L21(_SEG): blocks of the operator (2 or 3), block q at v + q * bstride holding the differences along bdir[q]
   long long bstride = 0;
   int bdir[3] = {0, 0, 0};
 };
@@ -70,6 +71,11 @@ long long seg_count(const ExtSpec& spec);
 template <typename T>
 void l21_observe(const ExtSpec& spec, const T* v, T* g, ProjScalars<T>* ps, double* partials, T* maxpart, T* compact, T* out,
                  hipStream_t stream);
+
+// out[k] (device, n3 entries) <- the sum of the group norms of frame k, as the per-frame projector's decision sums and rounds it
+// (ext_group.hip, EXT_L21_SEG); g: N entries of scratch
+template <typename T>
+void l21_seg_observe(const ExtSpec& spec, const T* v, T* g, T* out, hipStream_t stream);
 
 // sum (projected - original)^2 and sum original^2 into partial slots dst[0..NB), dst[NB..2NB)
 template <typename T>

@@ -38,17 +38,23 @@ EXPORTED_SYMBOLS = [
     "sipx_learn_observations",
     "sipx_finalize_dev", "sipx_reset_dev", "sipx_download_dev", "sipx_set_caller_stream", "sipx_io_bytes",
     "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev", "sipx_segment_norms", "sipx_segment_norms_dev",
-    "sipx_l21_norm", "sipx_l21_norm_dev",
+    "sipx_l21_norm", "sipx_l21_norm_dev", "sipx_l21_norms", "sipx_l21_norms_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
-OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5}
+OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusals of the l2,1 ball (csrc/engine.cpp, configure_proj), word for word
 L21_NEEDS_TV = "the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)"
 L21_WHOLE_ONLY = "the l2,1 ball applies to the whole array (mode matrix/tensor)"
+# TV_xy = vcat(D_y, D_x), the in-plane gradient of a 3-D grid (include/sipx.h, SIPX_OP_TV_XY): the engine's own, with its refusals
+L21_FRAMES_Z = "the l2,1 ball on TV_xy: frames run along z -- the mode must be (slice, z), or tensor for the whole array"
+UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
+TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
+TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
+TV_XY_NO_MULTILEVEL = "the TV_xy operator is not built for PARSDMM_multi_level: solve on one level"
 MODES = {"matrix": 0, "tensor": 0, "fiber": 1, "slice": 2}
 TRANSFORMS = {"DCT": 1, "wavelet": 2}
 SPECIAL_OPERATORS = ("DFT", "DCT", "wavelet", "curvelet")     # src/setup_constraints.jl:54
@@ -231,12 +237,16 @@ class TDOperator:
         self.kind, self.comp_grid, self.TF, self.adjoint = kind, comp_grid, np.dtype(TF).type, adjoint
         n, _ = _grid(comp_grid)
         self.n = n
+        if kind == "TV_xy" and len(n) != 3:
+            raise SipxError(TV_XY_NEEDS_3D)
+        if kind == "TV_xy" and component:
+            raise SipxError(TV_XY_NO_MINKOWSKI)
         N = int(np.prod(n))
         if kind == "identity":
             rows = N
         else:
             dirs = {"D_x": [0], "D_y": [1], "D_z": [len(n) - 1], "TV": list(range(len(n))), "D2D": list(range(len(n))),
-                    "D3D": list(range(len(n)))}[kind]
+                    "D3D": list(range(len(n))), "TV_xy": [0, 1]}[kind]
             rows = sum(N // n[a] * (n[a] - 1) for a in dirs)
         # Minkowski block rows [A 0] (1), [0 A] (2), [A A] (3) act on [u; v]  (PARSDMM_precompute_distribute_Minkowski.jl:91-103)
         self.component = int(component)
@@ -353,8 +363,28 @@ class Projector:
         if st == "l21":
             # isotropic total variation: the l2,1 ball on the range of the TV operator (csrc/l21.h); max is the radius
             cust = constraint.custom_TD_OP[0]
-            if constraint.TD_OP not in TV_OPERATORS or not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+            if constraint.TD_OP not in TV_OPERATORS + ("TV_xy",) or not (isinstance(cust, (tuple, list)) and len(cust) == 0):
                 raise SipxError(L21_NEEDS_TV)
+            if constraint.TD_OP == "TV_xy":
+                # on the in-plane gradient of a 3-D grid: the whole array, or every z-slice on its own (csrc/l21_seg.h) with one
+                # radius for all frames or a vector of n3
+                if len(n) != 3:
+                    raise SipxError(TV_XY_NEEDS_3D)
+                if self.mode and (self.mode, self.dir) != (MODES["slice"], 2):
+                    raise SipxError(L21_FRAMES_Z)
+                if np.ndim(constraint.max) > (1 if self.mode else 0):
+                    raise SipxError("the l2,1 ball on TV_xy takes one radius, or per frame a vector of n3 (constraint.max)")
+                self.kind, self.op = "l21", "TV_xy"
+                if np.ndim(constraint.max) == 1:
+                    self.seg_radii = True
+                    self.ub = np.ascontiguousarray(constraint.max, self.TF)
+                    _check_l1_radii("l1", self.ub)
+                    self.pmax = float(self.ub.max()) if len(self.ub) else 0.0
+                else:
+                    if not float(constraint.max) > 0:
+                        raise SipxError("Radius of L1 ball is negative")
+                    self.pmax = float(constraint.max)
+                return
             if self.mode:
                 raise SipxError(L21_WHOLE_ONLY)
             if np.ndim(constraint.max) != 0:
@@ -487,6 +517,8 @@ class Projector:
         if not self.mode:
             return 0
         n = list(op.n)
+        if self.kind == "l21":          # frames of the grid itself
+            return int(n[2])
         if op.kind in ("D_x", "D_y", "D_z"):
             n[{"D_x": 0, "D_y": 1, "D_z": len(n) - 1}[op.kind]] -= 1
         return int(np.prod(n)) // int(n[self.dir]) if self.mode == MODES["fiber"] else int(n[self.dir])
@@ -494,7 +526,7 @@ class Projector:
     def check_rows(self, op: "TDOperator"):
         """Host-side shape checks of the vectors the descriptor points at (the engine reads them unchecked)."""
         n = list(op.n)
-        if self.kind == "l21" and op.kind not in TV_OPERATORS:
+        if self.kind == "l21" and (op.kind != "TV_xy" if self.op == "TV_xy" else op.kind not in TV_OPERATORS):
             raise SipxError(L21_NEEDS_TV)
         if op.kind == "custom" and (self.mode or self.transform or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank",
                                                                                      "nuclear", "histogram", "subspace")):
@@ -508,7 +540,11 @@ class Projector:
             want = n[self.dir] if self.mode == MODES["fiber"] else rows
             if self.lb.shape != (want,) or self.ub.shape != (want,):
                 raise SipxError(f"bounds vectors need {want} entries for this operator / application mode")
-        if self.seg_radii:
+        if self.seg_radii and self.kind == "l21":
+            if self.ub.shape != (n[2],):
+                raise SipxError(f"l21 radii per frame: max has {self.ub.shape[0]} entries, n3 = {n[2]} are needed -- one per z-slice "
+                                f"of the grid of shape {tuple(n)}")
+        elif self.seg_radii:
             want = self.nseg(op)
             for name, a in (("min", self.lb), ("max", self.ub)):
                 if a is not None and a.shape != (want,):
@@ -554,9 +590,11 @@ class Projector:
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
                                                                               "subspace", "l21")
         if self.kind == "l21":       # the M-vector of the TV range in the reference's row order, on the grid
-            rows = TDOperator(self.op, self.comp_grid, self.TF).shape[0]
+            op = TDOperator(self.op, self.comp_grid, self.TF)
+            rows = op.shape[0]
             if v.shape != (rows,):
-                raise SipxError(f"the l2,1 ball projects a vector of the TV range: {rows} entries on this grid, {v.size} given")
+                raise SipxError(f"the l2,1 ball projects a vector of the {self.op} range: {rows} entries on this grid, {v.size} given")
+            self.check_rows(op)
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
         try:
             if self.kind == "l21":
@@ -597,6 +635,8 @@ def get_TD_operator(comp_grid, TD_type: str, TF):
         Dx = sp.kron(sp.identity(n2, dtype=TFt, format="csc"), fwd(n1, h[0]), format="csc")            # on (n1, n2)
         Dz = sp.kron(fwd(n2, h[1]), sp.identity(n1 - 1, dtype=TFt, format="csc"), format="csc")        # on (n1-1, n2)
         return CustomOperator((Dz @ Dx).astype(TFt), comp_grid, TF), False, False, (n1 - 1, n2 - 1), True
+    if TD_type == "TV_xy" and len(n) != 3:
+        raise SipxError(TV_XY_NEEDS_3D)
     A = TDOperator(TD_type, comp_grid, TF)
     if TD_type == "identity":
         return A, True, False, n, True
@@ -607,7 +647,8 @@ def get_TD_operator(comp_grid, TD_type: str, TF):
     else:
         n1, n2, n3 = n
         TD_n = {"TV": (3 * n1 - 1, 3 * n2 - 1, 3 * n3 - 1), "D3D": (3 * n1 - 1, 3 * n2 - 1, 3 * n3 - 1),
-                "D_z": (n1, n2, n3 - 1), "D_y": (n1, n2 - 1, n3), "D_x": (n1 - 1, n2, n3)}[TD_type]
+                "D_z": (n1, n2, n3 - 1), "D_y": (n1, n2 - 1, n3), "D_x": (n1 - 1, n2, n3),
+                "TV_xy": (2 * n1 - 1, 2 * n2 - 1, n3)}[TD_type]      # (bookkeeping only, as the TV entries are)
     return A, False, False, TD_n, True
 
 
@@ -628,11 +669,15 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
         seg = segment_norms and c.set_type in ("l1", "l2", "annulus") and c.app_mode[0] in ("slice", "fiber")
         if seg and np.ndim(c.min) != np.ndim(c.max):      # radii per segment: a scalar beside a vector, each converted on its own
             c.min, c.max = [np.asarray(a, TF) if np.ndim(a) else (TF(a) if isinstance(a, (float, np.floating)) else a) for a in (c.min, c.max)]
+        elif c.set_type == "l21" and np.ndim(c.max):
+            pass                                       # (radii per frame: converted below)
         elif np.ndim(c.min) == 0:
             if isinstance(c.min, (float, np.floating)):
                 c.min, c.max = TF(c.min), TF(c.max)
         else:
             c.min, c.max = np.asarray(c.min, TF), np.asarray(c.max, TF)
+        if c.set_type == "l21" and np.ndim(c.max) == 1:      # one radius per frame (TV_xy, ("slice", "z"))
+            c.max = np.asarray(c.max, TF)
         if c.set_type == "l21":
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
@@ -644,7 +689,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             if not segment_norms:
                 raise SipxError("annulus constraints per fiber or slice need setup_constraints(..., segment_norms=True)")
             cust0 = c.custom_TD_OP[0]
-            if c.TD_OP in ("TV", "D2D", "D3D", "D_xz") or not (isinstance(cust0, (tuple, list)) and len(cust0) == 0):
+            if c.TD_OP in ("TV", "D2D", "D3D", "D_xz", "TV_xy") or not (isinstance(cust0, (tuple, list)) and len(cust0) == 0):
                 raise SipxError("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)")
         A, AtA_diag, dense, TD_n, banded = get_TD_operator(comp_grid, c.TD_OP, TF)
         cust = c.custom_TD_OP[0] if c.set_type != "subspace" else ()
@@ -694,7 +739,7 @@ def PARSDMM_precompute_distribute(TD_OP, set_Prop, comp_grid, options):
             else:
                 AtA[i], set_Prop.AtA_offsets[i] = TD_OP[i].ata_cds()
             continue
-        dirs = {"identity": [], "D_x": [0], "D_y": [1], "D_z": [len(n) - 1]}.get(kind, list(range(len(n))))
+        dirs = {"identity": [], "D_x": [0], "D_y": [1], "D_z": [len(n) - 1], "TV_xy": [0, 1]}.get(kind, list(range(len(n))))
         strides = [int(np.prod(n[:a])) for a in dirs]
         set_Prop.AtA_offsets[i] = np.array(sorted({0} | {s for s in strides} | {-s for s in strides}), np.int64)
     del st
@@ -712,6 +757,8 @@ def PARSDMM_precompute_distribute_Minkowski(TD_OP_c1, TD_OP_c2, TD_OP_sum, set_P
     TF = np.dtype(options.FL).type
     n, _ = _grid(comp_grid)
     groups = ((TD_OP_c1, 1), (TD_OP_c2, 2), (TD_OP_sum, 3))
+    if any(A.kind == "TV_xy" for ops, _ in groups for A in ops):
+        raise SipxError(TV_XY_NO_MINKOWSKI)
     TD_OP = [TDOperator(A.kind, comp_grid, TF, component=c) for ops, c in groups for A in ops]
     prop = copy.deepcopy(set_Prop_c1)
     for other in (set_Prop_c2, set_Prop_sum):
@@ -726,7 +773,7 @@ def PARSDMM_precompute_distribute_Minkowski(TD_OP_c1, TD_OP_c2, TD_OP_sum, set_P
     N = int(np.prod(n))
     for i in range(s):
         kind, comp = TD_OP[i].kind, TD_OP[i].component
-        dirs = {"identity": [], "D_x": [0], "D_y": [1], "D_z": [len(n) - 1]}.get(kind, list(range(len(n))))
+        dirs = {"identity": [], "D_x": [0], "D_y": [1], "D_z": [len(n) - 1], "TV_xy": [0, 1]}.get(kind, list(range(len(n))))
         base = sorted({0} | {int(np.prod(n[:a])) for a in dirs} | {-int(np.prod(n[:a])) for a in dirs})
         off = sorted({o + sh for o in base for sh in (-N, 0, N)}) if comp == 3 else base
         prop.AtA_offsets[i] = np.array(off, np.int64)
@@ -916,7 +963,7 @@ class Context:
             arrs.append(a)
         P = self._keep_proj[int(i)] if 0 <= int(i) < len(self._keep_proj) else None
         if P is not None and P.seg_radii and arrs[1] is not None:
-            _check_l1_radii(P.kind, arrs[1])
+            _check_l1_radii("l1" if P.kind == "l21" else P.kind, arrs[1])
         _chk(lib().sipx_set_data(self.h, int(i), _ptr(arrs[0]), _ptr(arrs[1])))
 
     def set_data_dev(self, i, lb=None, ub=None):
@@ -1574,7 +1621,7 @@ class Solver:
             for k, a in given:
                 _check_array(k, a, self.TF, want)
             if self.P_sub[i].seg_radii and ub is not None:
-                _check_l1_radii(self.P_sub[i].kind, ub)
+                _check_l1_radii("l1" if self.P_sub[i].kind == "l21" else self.P_sub[i].kind, ub)
             fn = self._context(self.device).set_data
         try:
             fn(i, lb, ub)
@@ -1777,42 +1824,56 @@ def segment_norms(x, comp_grid, TD_OP: str, app_mode, norm: str):
     return out
 
 
-def l21_norm(x, comp_grid, TD_OP: str = "TV"):
+def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None):
     """||TV x||_2,1, the isotropic total variation of x on a 2-D or 3-D grid: sum over the grid points of the l2 norm of the forward
     differences that start there, one number of the working precision (that of x).  Computed by the kernel and the first-pass sum of
     the ("l21", "TV") projector (sipx_l21_norm): used as the radius it leaves TV x untouched.  x: a numpy vector (a numpy scalar
     comes back) or a 1-D torch tensor on a GPU (a tensor of one entry there; nothing crosses PCIe, the call orders itself against
-    torch's current stream)."""
-    if TD_OP not in TV_OPERATORS:
+    torch's current stream).
+
+    TD_OP = "TV_xy" (3-D grids) observes the in-plane gradient vcat(D_y, D_x) instead.  With app_mode = ("slice", "z") the n3 per-frame
+    norms come back (an array / a tensor of n3 entries): the sums of the group norms of every z-slice as the per-frame projector
+    ("l21", "TV_xy", ("slice", "z")) compares them with its radii (sipx_l21_norms), so radii observed on x leave TV_xy x unwritten."""
+    if TD_OP not in TV_OPERATORS + ("TV_xy",):
         raise SipxError(L21_NEEDS_TV)
+    mode, dirn = 0, 0
+    if app_mode is not None and tuple(app_mode)[0] not in ("matrix", "tensor"):
+        if TD_OP != "TV_xy":
+            raise SipxError(L21_WHOLE_ONLY)
+        if tuple(app_mode) != ("slice", "z"):
+            raise SipxError(L21_FRAMES_Z)
+        mode, dirn = MODES["slice"], 2
     on_dev = _is_tensor(x)
     TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
     if TF not in (np.float32, np.float64):
         raise SipxError("l21_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
     n, _ = _grid(comp_grid)
     N = int(np.prod(n))
+    if TD_OP == "TV_xy" and len(n) != 3:
+        raise SipxError(TV_XY_NEEDS_3D)
+    nout = int(n[2]) if mode else 1
     if on_dev:
         import torch
         _check_tensor("x", x, TF, N, None)
         _check_one_hip_runtime()
         device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        out = torch.empty(1, dtype=x.dtype, device=torch.device("cuda", device))
+        out = torch.empty(nout, dtype=x.dtype, device=torch.device("cuda", device))
         xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
-        fn = lib().sipx_l21_norm_dev
+        fn = lib().sipx_l21_norms_dev
     else:
         x = _check_array("x", x, TF, N)
         device = None
-        out = np.empty(1, TF)
+        out = np.empty(nout, TF)
         xp, op_ = _ptr(x), _ptr(out)
-        fn = lib().sipx_l21_norm
+        fn = lib().sipx_l21_norms
     ctx = Context(comp_grid, TF, device)
     try:
         if on_dev:
             ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
-        _chk(fn(ctx.h, xp, op_))
+        _chk(fn(ctx.h, OPS[TD_OP], mode, dirn, xp, op_, None))
     finally:
         ctx.close()
-    return out if on_dev else out[0]
+    return out if (on_dev or mode) else out[0]
 
 
 def _dwt_check_grid(n):

@@ -42,6 +42,8 @@ def constraint2coarse(constraint, comp_grid, cf):
 def setup_multi_level_PARSDMM(m, n_levels, coarsening_factor, comp_grid, constraint, options):
     TF = m.dtype.type
     cf = coarsening_factor
+    if any(c.TD_OP == "TV_xy" for c in constraint):
+        raise host.SipxError(host.TV_XY_NO_MULTILEVEL)
     P_sub, TD_OP, prop = host.setup_constraints(copy.deepcopy(constraint), comp_grid, TF)
     TD_OP, AtA, l, y = host.PARSDMM_precompute_distribute(TD_OP, prop, comp_grid, options)
     TD_OP_levels, AtA_levels, P_sub_levels, prop_levels, grid_levels = [TD_OP], [AtA], [P_sub], [prop], [comp_grid]
@@ -141,6 +143,8 @@ def PARSDMM_multi_level(m, TD_OP_levels, AtA_levels, P_sub_levels, set_Prop_leve
     alone does not wait for their copies: 8 of the 9 vectors of the {bounds, l1 TV} list)."""
     if outputs not in ("all", "x"):
         raise host.SipxError(f"outputs must be 'all' or 'x', not {outputs!r}")
+    if any(getattr(A, "kind", None) == "TV_xy" for ops in TD_OP_levels for A in ops):
+        raise host.SipxError(host.TV_XY_NO_MULTILEVEL)
     import time
     attach = None
     keep = []

@@ -1,0 +1,112 @@
+"""Time of one projection onto the per-frame l2,1 ball on TV_xy (csrc/l21_seg.h, csrc/ext_group.hip) next to the anisotropic per-frame
+pair and the whole-array l2,1 ball on the same operator, same build, same run.
+
+    python tools/l21_frames_bench.py [--size 256,256,64] [--steps 10] [--rounds 3] [--out FILE]
+
+Float32.  Three contexts, each inside a PARSDMM solve of {bounds, the set(s)} so that the projector sees the vectors a user's solve
+hands it; radii: half of each frame's (or the array's) own norm of A m.
+    frames   ("l21", "TV_xy", ("slice", "z")) with one radius per frame
+    aniso    ("l1", "D_x", ("slice", "z")) and ("l1", "D_y", ("slice", "z")) with one radius per frame each
+    whole    ("l21", "TV_xy", ("tensor", "")): the engine's threshold search on all N group norms in place of the per-frame thresholds
+After a warm-up window the contexts are measured in alternating windows of `steps` iterations with the engine's device events around
+every launch (sipx_kernel_stats mode 2); per figure the median over the windows with the spread.
+
+The row "ext_proj (library-backed)" is a whole materialised projector in the y/l update (for `aniso`: one launch per set, two per
+iteration) and "k_pass<M_STORE>" the pass that materialises v in front of it; ms_per_projection is their sum per launch.  The rows
+k_l21_norms / k_l21_frames / k_l21_scale are the three kernels on their own, recorded inside the ext_proj row (and by the feasibility
+estimate, which runs the same projector): ms per launch, and GB/s over the bytes the launcher books -- (nblk + 1) N w, N w,
+(2 nblk + 1) N w, w = 4; k_l21_scale moves less where frames are inside their balls.  michelot_passes: evaluations of (S, C) in the last
+projection of the run, total over the frames and the most in one frame.  Needs a GPU."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ROW, STORE = "ext_proj (library-backed)", "k_pass<M_STORE>"
+KERNELS = ("k_l21_norms", "k_l21_frames", "k_l21_scale")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", default="256,256,64")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    from __graft_entry__ import load_package
+    sipx = load_package()
+    TF = np.float32
+    n = tuple(int(v) for v in a.size.split(","))
+    N = int(np.prod(n))
+    rng = np.random.default_rng(0)
+    z = np.linspace(0, 1, n[-1]).reshape((1, 1, -1))
+    m = (1500 + 2500 * z + 150 * rng.standard_normal(n)).astype(TF).reshape(-1, order="F")
+    g = sipx.compgrid((25.0,) * 3, n)
+    opt = sipx.PARSDMM_options(FL=TF, maxit=a.steps * (a.rounds + 1), evol_rel_tol=0.0, feas_tol=0.0, obj_tol=0.0)
+    half = lambda r: (0.5 * np.asarray(r, np.float64)).astype(TF)
+    bounds = sipx.set_definitions("bounds", "identity", 1600.0, 3900.0, ("tensor", ""))
+    sets = {
+        "frames": [sipx.set_definitions("l21", "TV_xy", 0.0, half(sipx.l21_norm(m, g, "TV_xy", ("slice", "z"))), ("slice", "z"))],
+        "aniso": [sipx.set_definitions("l1", op, 0.0, half(sipx.segment_norms(m, g, op, ("slice", "z"), "l1")), ("slice", "z"))
+                  for op in ("D_x", "D_y")],
+        "whole": [sipx.set_definitions("l21", "TV_xy", 0.0, 0.5 * float(sipx.l21_norm(m, g, "TV_xy")), ("tensor", ""))],
+    }
+    ctxs = {}
+    fig = {name: {"ms": [], **{k: [] for k in KERNELS}} for name in sets}
+    gbs = {k: [] for k in KERNELS}
+    passes = None
+    try:
+        for name, c in sets.items():
+            P, A, prop = sipx.setup_constraints([bounds] + c, g, TF, segment_norms=True)
+            A, AtA, _, _ = sipx.PARSDMM_precompute_distribute(A, prop, g, opt)
+            ctx = ctxs[name] = sipx.host.build_context(m, AtA, A, prop, P, g, opt)
+            ctx.parsdmm_begin(opt)
+            ctx.parsdmm_steps(a.steps)                      # warm-up
+        for _ in range(a.rounds):
+            for name, ctx in ctxs.items():
+                ctx.kernel_stats(2)
+                ctx.parsdmm_steps(a.steps)
+                st = ctx.kernel_stats_all(0)
+                ks = {k["name"]: k for k in st["kernels"]}
+                ext, store = ks.get(ROW), ks.get(STORE)
+                if not ext or not ext["launches"] or not store or not store["launches"]:
+                    raise RuntimeError("no projector call was recorded")
+                fig[name]["ms"].append(ext["total_ms"] / ext["launches"] + store["total_ms"] / store["launches"])
+                for k in KERNELS:
+                    if k in ks and ks[k]["launches"]:
+                        per = ks[k]["total_ms"] / ks[k]["launches"]
+                        fig[name][k].append(per)
+                        if name == "frames":
+                            gbs[k].append(ks[k]["bytes_survey"] / ks[k]["launches"] / (per * 1e-3) / 1e9)
+                if name == "frames":
+                    passes = st.get("l21_frames")
+    finally:
+        for ctx in ctxs.values():
+            ctx.close()
+
+    def stat(v, nd=4):
+        return {"median": round(float(np.median(v)), nd), "min": round(float(min(v)), nd), "max": round(float(max(v)), nd)} if v else None
+    res = {"n": list(n), "dtype": "float32", "steps_per_window": a.steps, "windows": a.rounds, "michelot_passes": passes}
+    for name in sets:
+        res[name + "_ms_per_projection"] = stat(fig[name]["ms"])
+        for k in KERNELS:
+            if fig[name][k]:
+                res[f"{name}_{k}_ms"] = stat(fig[name][k])
+    for k in KERNELS:
+        res[f"frames_{k}_GB_per_s"] = stat(gbs[k], 1)
+    f, t = res["frames_ms_per_projection"]["median"], res.get("frames_k_l21_frames_ms", {}).get("median")
+    res["frames_threshold_share"] = round(t / f, 3) if t else None
+    txt = json.dumps(res)
+    print(txt)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(txt + "\n")
+
+
+if __name__ == "__main__":
+    main()
