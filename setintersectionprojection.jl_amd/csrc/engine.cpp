@@ -7,7 +7,7 @@
 #include "dist_dft.h"
 #include "ext_proj.h"
 #include "host_prefault.h"
-#include "dwt.h"
+#include "set_config.h"
 #include "solve_rules.h"
 #include "sparse_granules.h"
 
@@ -180,39 +180,24 @@ struct SectionMarks {
   }
 };
 
+// A set of a context: what its descriptor fixed (SetConfig, set_config.h) and, below, what finalize and the solve own -- device
+// arrays, the decomposition's routing, streams, events and warm starts.
 template <typename T>
-struct SetState {
-  int op = 0, prox = 0, nblk = 0, ncvx = 0;
-  int nblk_or1() const { return nblk > 0 ? nblk : 1; }
-  bool rank_like() const { return ext_kind == EXT_RANK || ext_kind == EXT_NUCLEAR; }
-  // a slice-wise rank / nuclear set on the last grid dimension of the identity: every rank can project the slices of its own z-slab
-  bool sliced_on_last_dim(int ndim) const { return rank_like() && spec.mode == SIPX_MODE_SLICE && spec.dir == ndim - 1 && ident; }
+struct SetState : SetConfig<T> {
+  SetState() = default;
+  explicit SetState(SetConfig<T>&& c) : SetConfig<T>(std::move(c)) {}
   // rho changed since this set's last l1 search: v is rescaled and theta moves like 1/rho -- by rescale_factor
-  bool rescaled(T rho) const { return prox == PX_L1 && last_rho > T(0) && last_rho != rho; }
+  bool rescaled(T rho) const { return this->prox == PX_L1 && last_rho > T(0) && last_rho != rho; }
   double rescale_factor(T rho) const { return (double)last_rho / (double)rho; }
-  // caller-supplied sparse operator (SIPX_OP_CSC): CSC for the adjoint, a CSR copy for the forward product; s = A x is
-  // materialised in sbuf and every set kernel then runs in its identity shape on a 1-D grid of M entries
-  bool custom = false;
-  std::vector<long long> h_colptr, h_rowval;
-  std::vector<T> h_nzval;
+  // device copies of a caller-supplied sparse operator (SIPX_OP_CSC): CSC, the CSR copy, and s = A x
   long long *d_colptr = nullptr, *d_rowval = nullptr, *d_rowptr = nullptr, *d_colidx = nullptr;
   T *d_nzval = nullptr, *d_rval = nullptr, *sbuf = nullptr;
-  Grid gm;                           // the 1-D "grid" of the M rows
-  // Matrix-free term of Q (ata_R = NULL at sipx_add_set): the set hands over no bands of A'A; every product with Q adds
-  // rho_i A_i'(A_i p) through the kernels of kernels_sparse.hip, which also serve the set's own s = A x and A'w (one operator,
-  // one arithmetic).  mf_rho: the set's current rho_i as Q holds it (assemble_Q, q_update); mf_t: A p of a product (M values).
-  bool mfree = false;
+  // a matrix-free term of Q.  mf_rho: the set's current rho_i as Q holds it (assemble_Q, q_update); mf_t: A p of a product (M values).
   T mf_rho = T(0);
   int *mf_colptr = nullptr, *mf_rowidx = nullptr, *mf_rowptr = nullptr, *mf_colidx = nullptr;
   T* mf_t = nullptr;
   MfOp<T> mfA, mfAt;                 // CSR copy (t = A p), CSC arrays (A' t)
-  int comp = 0;                      // Minkowski component: 0 none, 1 = [A 0], 2 = [0 A], 3 = [A A]
-  int dir[3] = {0, 0, 0};
-  T ih[3] = {0, 0, 0};
-  long long Mtrue = 0, Mpad = 0;
-  long long blk_rows[3] = {0, 0, 0};
-  T plo = 0, phi = 0;
-  bool ident = true, two_pass = false, is_dist = false, owned = true;
+  bool is_dist = false, owned = true;
   bool in_sweep = false;             // the one-sweep update (k_yl_multi) takes this set; the others keep their per-set kernels
   // y, l: the arrays holding the current iterate; y0, l0: the other pair.  The snapshot (y_0, l_0) of the BB rule lives
   // in whichever pair `snap` names: on a snapshot iteration the update is written over the old snapshot (after it has
@@ -222,12 +207,9 @@ struct SetState {
   T *y2 = nullptr, *l2 = nullptr;    // third pair of the one-sweep update (allocated by sipx_finalize, see sweep_launch)
   int snap = -1;                     // -1: no snapshot yet; 0: (y, l) is also the snapshot; 1: (y0, l0) is
   T *lb = nullptr, *ub = nullptr, *ata = nullptr;
-  int bmode = SIPX_MODE_WHOLE, bdir = 0;   // SIPX_PROJ_BOUNDS_VEC: one bound per row (WHOLE) or per coordinate along bdir (FIBER)
   // vectors sipx_set_data_dev handed over before sipx_finalize, as given (device copies; finalize expands and frees them)
   T *pend_lb = nullptr, *pend_ub = nullptr;
   int searches_done = 0;             // slab-decomposed l1 searches of this set so far (sizes the refinement rounds)
-  int ext_kind = 0;                  // projector acting on a materialised vector (ext_proj.h)
-  bool seg_radii = false;            // EXT_L1_SEG / L2_SEG / ANNULUS_SEG built with one radius per segment (host_lb / host_ub, then the projector's)
   // Sharded solve: a rank / nuclear-norm set on the slices orthogonal to the last grid dimension is projected by ALL ranks,
   // each factorising the slices of its z-slab (`ext` is then built for the slab on every rank, owner or not)
   bool dist_ext = false;
@@ -248,13 +230,9 @@ struct SetState {
   bool fan_on_side = false;          // this update's projection was queued on the fan stream
   T* fanv = nullptr;                 // a gathered set's own whole-size vector (v, then P(v)): its owner projects it on the fan stream
   hipEvent_t fan_ev = nullptr;       // ... and records this when P(v) is ready
-  ExtSpec spec;
-  std::vector<T> host_basis;
   std::shared_ptr<ExtProj<T>> ext;
   ProjScalars<T>* ps = nullptr;    // scalars of prox_i (warm-started across iterations)
   ProjScalars<T>* psf = nullptr;   // scalars of the feasibility estimate P_i(A_i x)
-  std::vector<long long> ata_off;
-  std::vector<T> host_lb, host_ub, host_ata;
   double sums[SLOTS] = {0};
   bool bb_valid = false;
   T last_rho = T(-1), last_gamma = T(-1);   // parameters of the previous y/l update (speculation of the l1 search)
@@ -274,29 +252,19 @@ template <typename T>
 class Engine : public EngineBase {
  public:
   Engine(int ndim, const int64_t* n, const double* h, int device) : device_(device) {
-    if (ndim != 2 && ndim != 3) throw std::runtime_error("ndim must be 2 or 3");
+    const ConfigCtx grid = grid_ctx<T>(ndim, n, h);      // (refuses a grid before anything is created for it)
+    ndim_ = grid.ndim;
+    G_ = grid.G;
+    for (int a = 0; a < 3; ++a) ih_[a] = (T)grid.ih[a];
     SIPX_HIP(hipSetDevice(device));
     SIPX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     SIPX_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
     SIPX_HIP(hipEventCreateWithFlags(&ev_fork2_, hipEventDisableTiming));
     set_streams_ = env_knobs().serial_sets != 1;
-    ndim_ = ndim;
-    for (int a = 0; a < 3; ++a) {
-      G_.n[a] = a < ndim ? n[a] : 1;
-      if (G_.n[a] < 1) throw std::runtime_error("grid size must be positive");
-      ih_[a] = a < ndim ? T(1) / T(h[a]) : T(0);   // entries +-1/h of get_discrete_Grad.jl:22-23,58-60
-    }
-    if (ndim == 3 && G_.n[2] == 1) ndim_ = 2;      // get_TD_operator.jl:30
-    G_.N = G_.n[0] * G_.n[1] * G_.n[2];
     // Up to 2^22 grid points the kernels of the searches are too short for a second stream to hide anything: the cross-stream
     // dependencies (an event wait costs 15-25 us on this stack) outweigh the overlap.  2048^2, C2: 2130 -> 2300 it/s on one
     // stream; 256^3 gains 6 % from its three.  SIPX_SERIAL_SETS=0 keeps the streams whatever the size.
     if (G_.N <= (1ll << 22) && env_knobs().serial_sets < 0) set_streams_ = false;
-    G_.st[0] = 1;
-    G_.st[1] = G_.n[0];
-    G_.st[2] = G_.n[0] * G_.n[1];
-    if (G_.N >= (1ll << 31)) throw std::runtime_error("grids of 2^31 points or more are not supported");
-    G_.set_fast_div();
   }
   ~Engine() override {
     (void)hipSetDevice(device_);
@@ -327,32 +295,14 @@ class Engine : public EngineBase {
   // ------------------------------------------------------------------------------------------
   int add_set(const sipx_set_desc* d, const void* ata_R, const int64_t* ata_off, int d_i) override {
     if (finalized_) throw std::runtime_error("sipx_add_set after sipx_finalize");
-    SetState<T> s;
-    if (d->op == SIPX_OP_CSC) configure_custom(s, d);
-    else configure_op(s, d->op);
-    if (s.op == SIPX_OP_TV_XY) {
-      refuse_sharded_tv_xy();
-      if (d->component) throw std::runtime_error("the TV_xy operator takes no Minkowski component");
-    }
-    configure_proj(s, d);
-    if (s.custom && (s.comp || s.ext_kind))
-      throw std::runtime_error("custom sparse operators (SIPX_OP_CSC): Minkowski components and library-backed projectors are not available; "
-                               "use one of the built-in operators for such a set");
-    if (s.custom && !ata_R) {              // matrix-free term of Q: no bands, the products go through the operator itself
-      const long long nnz = (long long)s.h_rowval.size();
-      check_mf_index_range(G_.N, s.Mtrue, nnz);
-      s.mfree = true;
-    }
-    if (ata_R && s.comp) throw std::runtime_error("Minkowski sets use descriptor-generated AtA (pass ata_R = NULL)");
-    if (ata_R) {
-      if (d_i < 1 || d_i > 9) throw std::runtime_error("AtA band count out of range (1..9 bands per set)");
-      s.ata_off.assign(ata_off, ata_off + d_i);
-      s.host_ata.assign((const T*)ata_R, (const T*)ata_R + (size_t)G_.N * d_i);
-    } else if (!s.mfree) {
-      s.ata_off = default_ata_offsets(s);
-    }
-    sets_.push_back(std::move(s));
+    sets_.emplace_back(configure_set<T>(config_ctx(), d, ata_R, ata_off, d_i));
+    need_ext_ |= sets_.back().needs_ext_scratch;       // the context's scratch is decided by the sets it was given
+    need_idx_ |= sets_.back().needs_index_scratch;
     return (int)sets_.size() - 1;
+  }
+  // what the descriptor rules (set_config.h) read from this context, as it stands now
+  ConfigCtx config_ctx() const {
+    return ConfigCtx{ndim_, G_, {(double)ih_[0], (double)ih_[1], (double)ih_[2]}, !(comm_ || slab_req_ || !owned_.empty())};
   }
 
   int64_t set_rows(int set) override {
@@ -430,10 +380,11 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
     refresh_env_knobs();                  // the launchers' A/B switches: read once per context, not per launch
     feasibility_only_ = feasibility_only != 0;
+    const ConfigCtx ctx = config_ctx();     // (a communicator, a decomposition or ownership may have come after the sets)
     for (const auto& s : sets_) {
-      if (s.seg_radii) refuse_sharded_radii();
-      if (s.op == SIPX_OP_TV_XY) refuse_sharded_tv_xy();
-      if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG) refuse_sharded_l21();
+      if (s.seg_radii) refuse_sharded(ctx, Sharded::RADII);
+      if (s.op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
+      if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG) refuse_sharded(ctx, Sharded::L21);
     }
     FinalizePlan P;
     plan_sets();
@@ -479,7 +430,7 @@ class Engine : public EngineBase {
     pp_n_ = (int)sets_.size();
     if (!feasibility_only_) {             // PARSDMM_precompute_distribute.jl:17-26: identity operator for 1/2||x-m||^2
       SetState<T> s;
-      configure_op(s, SIPX_OP_IDENTITY);
+      configure_op(config_ctx(), s, SIPX_OP_IDENTITY);
       s.prox = PX_DIST;
       s.is_dist = true;
       s.ata_off = {0};
@@ -495,7 +446,7 @@ class Engine : public EngineBase {
       if (mk_ && stencil_q_) throw std::runtime_error("the stencil form of Q is not available for Minkowski sets");
       if (mk_ && !owned_.empty()) throw std::runtime_error("set sharding is not available for Minkowski sets");
       if (mk_)
-        for (auto& st : sets_) st.ata_off = default_ata_offsets(st);
+        for (auto& st : sets_) st.ata_off = default_ata_offsets(config_ctx(), st);
     }
     for (int i = 0; i < p_n_; ++i) {
       if (!sets_[i].mfree) continue;
@@ -2961,11 +2912,6 @@ class Engine : public EngineBase {
   // already has.  Before sipx_finalize the call replaces what sipx_add_set was given.  On a finalized context nothing is
   // allocated and no stream or event is created; the new data holds from the next sipx_reset on (a solve in progress is given
   // up: the host form stages through the engine's scratch).
-  long long data_len(const SetState<T>& s) const {
-    if (s.seg_radii) return s.ext_kind == EXT_L21_SEG ? G_.n[2] : seg_count(s.spec);
-    if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;
-    return G_.n[s.bdir] - ((s.nblk == 1 && s.dir[0] == s.bdir) ? 1 : 0);
-  }
   // segments that take a bound vector as given (src: device memory) into the padded array of the set
   void io_add_bounds(IoArgs<T>& A, const SetState<T>& s, const T* src, T* dev) {
     if (s.bmode != SIPX_MODE_FIBER) { io_add_set(A, false, s, src, dev); return; }
@@ -2995,13 +2941,14 @@ class Engine : public EngineBase {
                                "subspace bases are fixed at sipx_add_set" + way_out);
     if (s.seg_radii && lb && s.ext_kind != EXT_ANNULUS_SEG)
       throw std::runtime_error(what + ": only the annulus has inner radii (lb); the radii of an l1 / l2 set are its ub");
-    if (s.seg_radii && (s.ext_kind == EXT_L1_SEG || s.ext_kind == EXT_L21_SEG) && ub && !on_device) check_l1_radii((const T*)ub, data_len(s));
+    const ConfigCtx ctx = config_ctx();
+    const long long len = data_len(ctx, s);
+    if (s.seg_radii && (s.ext_kind == EXT_L1_SEG || s.ext_kind == EXT_L21_SEG) && ub && !on_device) check_l1_radii((const T*)ub, len);
     if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
       throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
     if (!lb && !ub) return;
     SIPX_HIP(hipSetDevice(device_));
     const T *LB = (const T*)lb, *UB = (const T*)ub;
-    const long long len = data_len(s);
     const size_t bytes = (size_t)len * sizeof(T);
     if (!finalized_) {
       if (on_device) {                       // kept as given until sipx_finalize expands it; the caller may reuse its buffers
@@ -3017,7 +2964,7 @@ class Engine : public EngineBase {
         if (!src) return;
         mem_.release(pend);
         pend = nullptr;
-        if (bounds && s.bmode == SIPX_MODE_FIBER) expand_fiber_bounds(s, src, host);
+        if (bounds && s.bmode == SIPX_MODE_FIBER) expand_fiber_bounds(ctx, s, src, host);
         else host.assign(src, src + len);
       };
       take(LB, s.host_lb, s.pend_lb);
@@ -3287,49 +3234,90 @@ class Engine : public EngineBase {
   }
 
   // ------------------------------------------------------------------------------------------
+  // The stand-alone calls (sipx_apply_op, sipx_project, sipx_l21_norms, sipx_segment_norms) configure a throw-away set like
+  // sipx_add_set does and work in scratch of the call.  What they share:
+  // x behind the halo the difference kernels read across (dx) and the padded blocks of A x (dv), each only where wanted
+  struct OpScratch {
+    T *dx = nullptr, *dv = nullptr;
+    OpScratch(DeviceMemory& tmp, const Grid& G, long long Mpad, bool want_x, bool want_v) {
+      long long H = 4;
+      for (int a = 0; a < 3; ++a) H = std::max<long long>(H, G.st[a]);
+      H = (H + 3) / 4 * 4;
+      if (want_x) dx = tmp.alloc<T>(G.N + 2 * H) + H;
+      if (want_v) dv = tmp.alloc<T>(Mpad + H) + H;
+    }
+  };
+  // ... for A x of host or device x: device x of the identity is read where it lies
+  OpScratch forward_scratch(DeviceMemory& tmp, const SetConfig<T>& s, bool on_device) const {
+    return OpScratch(tmp, G_, s.Mpad, !(on_device && !s.nblk), s.nblk > 0);
+  }
+  // A x (x itself for the identity) queued on the engine stream, behind the caller's stream for device x
+  const T* queue_forward(const OpScratch& w, const SetConfig<T>& s, const void* x, bool on_device) {
+    if (on_device) engine_after_caller();
+    if (w.dx) SIPX_HIP(hipMemcpyAsync(w.dx, x, G_.N * sizeof(T), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    const T* dx = w.dx ? w.dx : (const T*)x;
+    if (s.nblk) K<T>::fwd(stream_, G_, s.nblk, s.dir, s.ih, dx, w.dv);
+    return s.nblk ? w.dv : dx;
+  }
+  // the scratch of a threshold search over n entries (ps: where the engine's own two-pass search runs)
+  struct SearchScratch {
+    T *dc = nullptr, *mp = nullptr;
+    double* part = nullptr;
+    ProjScalars<T>* ps = nullptr;
+    SearchScratch(DeviceMemory& tmp, long long n, bool with_ps) {
+      dc = tmp.alloc<T>(n);
+      part = tmp.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
+      mp = tmp.alloc<T>(2 * NB);
+      if (with_ps) ps = tmp.alloc<ProjScalars<T>>(1);
+    }
+  };
+  // the result of a call: left in the caller's device memory behind the caller's stream, or copied to the host
+  void finish_call(bool on_device, void* out, const T* dout, long long n) {
+    if (on_device) {
+      caller_after_engine();
+      SIPX_HIP(hipStreamSynchronize(stream_));      // (the scratch of this call goes when it returns)
+    } else {
+      SIPX_HIP(hipStreamSynchronize(stream_));
+      SIPX_HIP(hipMemcpy(out, dout, n * sizeof(T), hipMemcpyDeviceToHost));
+    }
+  }
+
   void apply_op(int op, const void* x, void* out, bool adjoint) override {
     SIPX_HIP(hipSetDevice(device_));
-    SetState<T> s;
-    configure_op(s, op);
-    long long H = 4;
-    for (int a = 0; a < 3; ++a) H = std::max<long long>(H, G_.st[a]);
-    H = (H + 3) / 4 * 4;
+    SetConfig<T> s;
+    configure_op(config_ctx(), s, op);
     DeviceMemory tmp;
-    T* dxb = tmp.alloc<T>(G_.N + 2 * H);
-    T* dvb = tmp.alloc<T>(s.Mpad + H);
-    T *dx = dxb + H, *dv = dvb + H;
+    const OpScratch w(tmp, G_, s.Mpad, true, true);
     if (!adjoint) {
-      SIPX_HIP(hipMemcpy(dx, x, G_.N * sizeof(T), hipMemcpyHostToDevice));
-      K<T>::fwd(stream_, G_, s.nblk, s.dir, s.ih, dx, dv);
-      download_rows(s, dv, (T*)out);
+      SIPX_HIP(hipMemcpy(w.dx, x, G_.N * sizeof(T), hipMemcpyHostToDevice));
+      K<T>::fwd(stream_, G_, s.nblk, s.dir, s.ih, w.dx, w.dv);
+      download_rows(s, w.dv, (T*)out);
     } else {
-      upload_rows(s, (const T*)x, dv);
-      K<T>::adj(stream_, G_, s.nblk, s.dir, s.ih, dv, dx);
-      SIPX_HIP(hipStreamSynchronize(stream_));
-      SIPX_HIP(hipMemcpy(out, dx, G_.N * sizeof(T), hipMemcpyDeviceToHost));
+      upload_rows(s, (const T*)x, w.dv);
+      K<T>::adj(stream_, G_, s.nblk, s.dir, s.ih, w.dv, w.dx);
+      finish_call(false, out, w.dx, G_.N);
     }
   }
 
   // SIPX_PROJ_L21 of sipx_project: the M-vector of the TV range in the reference's row order, through the packing of a TV set's y / l
   void project_l21(const sipx_set_desc* d, void* v, int64_t len) {
-    SetState<T> st;
+    SetConfig<T> st;
     if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY)
       throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
-    configure_op(st, d->op);
-    configure_proj(st, d);
+    const ConfigCtx ctx = config_ctx();
+    configure_op(ctx, st, d->op);
+    configure_proj(ctx, st, d);
     if (len != st.Mtrue)
       throw std::runtime_error(std::string("the l2,1 ball projects a vector of the ") + (d->op == SIPX_OP_TV ? "TV" : "TV_xy") + " range: " +
                                std::to_string(st.Mtrue) + " entries on this grid, " + std::to_string((long long)len) + " given");
     st.spec.ub = st.host_ub.empty() ? nullptr : st.host_ub.data();      // (per frame: one radius each)
     DeviceMemory tmp;
     T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
-    T* dc = tmp.alloc<T>(G_.N);
-    double* part = tmp.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-    T* mp = tmp.alloc<T>(2 * NB);
+    const SearchScratch q(tmp, G_.N, false);
     upload_rows(st, (const T*)v, dv);
     {
       ExtProj<T> ext(st.spec, stream_);
-      ext.project(dv, false, part, mp, dc);
+      ext.project(dv, false, q.part, q.mp, q.dc);
       download_rows(st, dv, (T*)v);               // (synchronises the stream)
     }
   }
@@ -3345,45 +3333,31 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
     if (op != SIPX_OP_TV && op != SIPX_OP_TV_XY)
       throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
-    SetState<T> s;
-    configure_op(s, op);
-    if (op == SIPX_OP_TV_XY) refuse_sharded_tv_xy();
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, op);
+    if (op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
     sipx_set_desc d{};
     d.op = op; d.proj = SIPX_PROJ_L21; d.mode = mode; d.dir = dir; d.pmax = 1.0;
-    configure_proj(s, &d);                     // the refusals, and the ExtSpec, of the set
+    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the set
     const bool frames = s.ext_kind == EXT_L21_SEG;
     const long long nout = frames ? G_.n[2] : 1;
     if (nseg) *nseg = nout;
     if (!x && !out) return;                    // (a query of the length)
     if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed");
-    long long H = 4;
-    for (int a = 0; a < 3; ++a) H = std::max<long long>(H, G_.st[a]);
-    H = (H + 3) / 4 * 4;
     DeviceMemory tmp;
-    T* dxb = tmp.alloc<T>(G_.N + 2 * H);
-    T* dvb = tmp.alloc<T>(s.Mpad + H);
+    const OpScratch w = forward_scratch(tmp, s, on_device);
     T* g = tmp.alloc<T>(G_.N);
-    T* dc = tmp.alloc<T>(G_.N);
-    double* part = tmp.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-    T* mp = tmp.alloc<T>(2 * NB);
-    ProjScalars<T>* ps = tmp.alloc<ProjScalars<T>>(1);
+    const SearchScratch q(tmp, G_.N, true);
     T* dout = on_device ? (T*)out : tmp.alloc<T>(nout);
-    if (on_device) engine_after_caller();
-    SIPX_HIP(hipMemcpyAsync(dxb + H, x, G_.N * sizeof(T), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
-    K<T>::fwd(stream_, G_, s.nblk, s.dir, s.ih, dxb + H, dvb + H);
+    const T* dv = queue_forward(w, s, x, on_device);
     {
       ObserverGuard og(observer());
       ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 1) * G_.N * sizeof(T));
-      if (frames) l21_seg_observe<T>(s.spec, dvb + H, g, dout, stream_);
-      else l21_observe<T>(s.spec, dvb + H, g, ps, part, mp, dc, dout, stream_);
+      if (frames) l21_seg_observe<T>(s.spec, dv, g, dout, stream_);
+      else l21_observe<T>(s.spec, dv, g, q.ps, q.part, q.mp, q.dc, dout, stream_);
     }
-    if (on_device) {
-      caller_after_engine();
-      SIPX_HIP(hipStreamSynchronize(stream_));      // (the scratch of this call goes when it returns)
-    } else {
-      SIPX_HIP(hipStreamSynchronize(stream_));
-      SIPX_HIP(hipMemcpy(out, dout, nout * sizeof(T), hipMemcpyDeviceToHost));
-    }
+    finish_call(on_device, out, dout, nout);
   }
 
   void project(const sipx_set_desc* d, void* v, int64_t len) override {
@@ -3393,11 +3367,8 @@ class Engine : public EngineBase {
     g1.n[0] = len; g1.n[1] = 1; g1.n[2] = 1; g1.N = len; g1.st[0] = 1; g1.st[1] = len; g1.st[2] = len;
     DeviceMemory tmp;
     T* dv = tmp.alloc<T>(len);
-    T* dc = tmp.alloc<T>(len);
+    const SearchScratch q(tmp, len, true);
     T *lb = nullptr, *ub = nullptr;
-    double* part = tmp.alloc<double>((size_t)(PREP_SLOTS + 2) * NB);
-    T* mp = tmp.alloc<T>(2 * NB);
-    ProjScalars<T>* ps = tmp.alloc<ProjScalars<T>>(1);
     SIPX_HIP(hipMemcpy(dv, v, len * sizeof(T), hipMemcpyHostToDevice));
     const int prox = d->proj;
     const T plo = (T)d->pmin, phi = (T)d->pmax;
@@ -3410,39 +3381,38 @@ class Engine : public EngineBase {
     if (prox == SIPX_PROJ_L1 && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
     if (d->mode != SIPX_MODE_WHOLE || d->transform != SIPX_TRANSFORM_NONE || prox == SIPX_PROJ_L1_DFT || prox >= SIPX_PROJ_RANK) {   // incl. SIPX_PROJ_BOUNDS_DFT   // acts on the context grid
       if (len != G_.N) throw std::runtime_error("this projector / application mode needs a vector of the grid size");
-      SetState<T> st;
-      configure_op(st, SIPX_OP_IDENTITY);
-      configure_proj(st, d);
+      const ConfigCtx ctx = config_ctx();
+      SetConfig<T> st;
+      configure_op(ctx, st, SIPX_OP_IDENTITY);
+      configure_proj(ctx, st, d);
       if (st.ext_kind) {
         st.spec.lb = st.host_lb.empty() ? nullptr : st.host_lb.data();
         st.spec.ub = st.host_ub.empty() ? nullptr : st.host_ub.data();
         st.spec.basis = st.host_basis.empty() ? nullptr : st.host_basis.data();
         ExtProj<T> ext(st.spec, stream_);
-        ext.project(dv, false, part, mp, dc);
+        ext.project(dv, false, q.part, q.mp, q.dc);
         if (st.ext_kind == EXT_RANK) {             // the route of a stand-alone call counts like a set's (rank_route)
           long long c[4];
           ext.route_counts(c);
           for (int q = 0; q < 4; ++q) project_rc_[q] += c[q];
         }
-      } else {                                   // per-fiber bounds, expanded by configure_proj
+      } else {                                   // per-fiber bounds, expanded by configure_proj (set_config.h)
         lb = tmp.alloc<T>(len); ub = tmp.alloc<T>(len);
         SIPX_HIP(hipMemcpy(lb, st.host_lb.data(), len * sizeof(T), hipMemcpyHostToDevice));
         SIPX_HIP(hipMemcpy(ub, st.host_ub.data(), len * sizeof(T), hipMemcpyHostToDevice));
         proj_apply_grid<T>(stream_, g1, 0, nullptr, len, dv, st.prox, st.plo, st.phi, lb, ub, nullptr);
       }
-      SIPX_HIP(hipStreamSynchronize(stream_));
-      SIPX_HIP(hipMemcpy(v, dv, len * sizeof(T), hipMemcpyDeviceToHost));
+      finish_call(false, v, dv, len);
       return;
     }
     const bool two = prox == SIPX_PROJ_L1 || prox == SIPX_PROJ_L2 || prox == SIPX_PROJ_ANNULUS || prox == SIPX_PROJ_CARDINALITY;
     long long* di = prox == SIPX_PROJ_CARDINALITY ? tmp.alloc<long long>(len) : nullptr;
     if (two) {
-      K<T>::ps_init(stream_, ps, di);
-      K<T>::proj_scalars_arr(stream_, len, dv, prox, plo, phi, ps, part, mp, dc, len);
+      K<T>::ps_init(stream_, q.ps, di);
+      K<T>::proj_scalars_arr(stream_, len, dv, prox, plo, phi, q.ps, q.part, q.mp, q.dc, len);
     }
-    proj_apply_grid<T>(stream_, g1, 0, nullptr, len, dv, prox, prox == SIPX_PROJ_BOUNDS_VEC ? T(0) : plo, phi, lb, ub, two ? ps : nullptr);
-    SIPX_HIP(hipStreamSynchronize(stream_));
-    SIPX_HIP(hipMemcpy(v, dv, len * sizeof(T), hipMemcpyDeviceToHost));
+    proj_apply_grid<T>(stream_, g1, 0, nullptr, len, dv, prox, prox == SIPX_PROJ_BOUNDS_VEC ? T(0) : plo, phi, lb, ub, two ? q.ps : nullptr);
+    finish_call(false, v, dv, len);
   }
 
   // sipx_segment_norms(_dev): the l1 / l2 norms of the fibers / slices of A x, in the order of the per-segment radii.  A x through the
@@ -3452,46 +3422,26 @@ class Engine : public EngineBase {
     if (norm != 0 && norm != 1) throw std::runtime_error("segment norms: norm must be 0 (l1) or 1 (l2)");
     if (op != SIPX_OP_IDENTITY && op != SIPX_OP_DX && op != SIPX_OP_DY && op != SIPX_OP_DZ)
       throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
-    SetState<T> s;
-    configure_op(s, op);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, op);
     sipx_set_desc d{};
     d.op = op; d.proj = SIPX_PROJ_L2; d.mode = mode; d.dir = dir;
     if (mode == SIPX_MODE_WHOLE) throw std::runtime_error("segment norms need a fiber or slice mode");
-    configure_proj(s, &d);                     // the refusals, and the ExtSpec, of the sets
+    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the sets
     const long long ns = seg_count(s.spec);
     if (nseg) *nseg = ns;
     if (!x || !out) return;                    // (a query of the length)
-    long long H = 4;
-    for (int a = 0; a < 3; ++a) H = std::max<long long>(H, G_.st[a]);
-    H = (H + 3) / 4 * 4;
     DeviceMemory tmp;
-    T* dxb = on_device && !s.nblk ? nullptr : tmp.alloc<T>(G_.N + 2 * H);
-    T* dvb = s.nblk ? tmp.alloc<T>(s.Mpad + H) : nullptr;
+    const OpScratch w = forward_scratch(tmp, s, on_device);
     T* dout = on_device ? (T*)out : tmp.alloc<T>(ns);
-    const T* dx = (const T*)x;
-    if (on_device) engine_after_caller();
-    if (dxb) {
-      const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-      SIPX_HIP(hipMemcpyAsync(dxb + H, x, G_.N * sizeof(T), kind, stream_));
-      dx = dxb + H;
-    }
-    const T* dv = dx;                          // the identity: x itself
-    if (s.nblk) {
-      K<T>::fwd(stream_, G_, s.nblk, s.dir, s.ih, dx, dvb + H);
-      dv = dvb + H;
-    }
+    const T* dv = queue_forward(w, s, x, on_device);
     {
       ObserverGuard og(observer());            // (sipx_kernel_stats mode 2 times the launch: the row of the materialised projectors)
       ObsScope obs(KID_EXT, stream_, (double)s.Mtrue * sizeof(T));
       seg_observe<T>(s.spec, norm, dv, dout, stream_);
     }
-    if (on_device) {
-      caller_after_engine();
-      SIPX_HIP(hipStreamSynchronize(stream_));      // (the scratch of this call goes when it returns)
-    } else {
-      SIPX_HIP(hipStreamSynchronize(stream_));
-      SIPX_HIP(hipMemcpy(out, dout, ns * sizeof(T), hipMemcpyDeviceToHost));
-    }
+    finish_call(on_device, out, dout, ns);
   }
 
   void get_Q(void* Q, int64_t* offsets, int* d) override {
@@ -3752,261 +3702,6 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
   }
 
-  // per-fiber bounds, one per coordinate along s.bdir, as one bound per row of A_i in the reference's row order
-  void expand_fiber_bounds(const SetState<T>& s, const T* per_fiber, std::vector<T>& rows) const {
-    long long dims[3] = {G_.n[0], G_.n[1], G_.n[2]};
-    if (s.nblk == 1) dims[s.dir[0]] -= 1;
-    rows.resize(s.Mtrue);
-    long long r = 0;
-    for (long long k = 0; k < dims[2]; ++k)
-      for (long long j = 0; j < dims[1]; ++j)
-        for (long long i = 0; i < dims[0]; ++i, ++r) rows[r] = per_fiber[s.bdir == 0 ? i : (s.bdir == 1 ? j : k)];
-  }
-
-  // vector radii live in the one projector of a single process: a rank of a sharded solve would each need its share of them
-  void refuse_sharded_radii() const {
-    if (comm_ || slab_req_ || !owned_.empty())
-      throw std::runtime_error("per-fiber / per-slice l1, l2 and annulus sets with one radius per segment take single-process contexts only, this "
-                               "one has a communicator, a slab decomposition or set ownership: use a scalar radius, or a single process");
-  }
-  // the groups of the l2,1 ball span the blocks of the TV operator: the gather route of a slab-decomposed solve is single-block
-  void refuse_sharded_l21() const {
-    if (comm_ || slab_req_ || !owned_.empty())
-      throw std::runtime_error("the l2,1 ball on the TV operator (isotropic total variation) takes single-process contexts only, this one "
-                               "has a communicator, a slab decomposition or set ownership: use the l1 ball on TV, or a single process");
-  }
-  // TV_xy is an operator of single-process contexts: the slab routes know TV's one block per dimension only
-  void refuse_sharded_tv_xy() const {
-    if (comm_ || slab_req_ || !owned_.empty())
-      throw std::runtime_error("the TV_xy operator takes single-process contexts only, this one has a communicator, a slab decomposition "
-                               "or set ownership: use D_x and D_y sets, or a single process");
-  }
-  // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
-  static void check_l1_radii(const T* r, long long n) {
-    for (long long k = 0; k < n; ++k)
-      if (!(r[k] > T(0))) throw std::runtime_error("Radius of L1 ball is negative (segment " + std::to_string(k) + ")");
-  }
-
-  // projector part of a set descriptor: validation (the reference's error messages) + routing
-  void configure_proj(SetState<T>& s, const sipx_set_desc* d) {
-    s.prox = d->proj;
-    s.ncvx = d->ncvx;
-    s.plo = (T)d->pmin;
-    s.phi = (T)d->pmax;
-    if (d->component < 0 || d->component > 3) throw std::runtime_error("Minkowski component must be 0, 1, 2 or 3");
-    s.comp = d->component;
-    const int mode = d->mode, dir = d->dir;
-    if (mode != SIPX_MODE_WHOLE && mode != SIPX_MODE_FIBER && mode != SIPX_MODE_SLICE)
-      throw std::runtime_error("unknown application mode");
-    if (mode != SIPX_MODE_WHOLE) {
-      if (dir < 0 || dir >= ndim_) throw std::runtime_error("application mode: direction out of range for this grid");
-      // the one multi-block set with a mode of its own: the l2,1 ball per z-slice on TV_xy (l21_seg.h)
-      const bool frames = d->proj == SIPX_PROJ_L21 && s.op == SIPX_OP_TV_XY && d->transform == SIPX_TRANSFORM_NONE;
-      if (frames && !(mode == SIPX_MODE_SLICE && dir == 2))
-        throw std::runtime_error("the l2,1 ball on TV_xy: frames run along z -- the mode must be (slice, z), or tensor for the whole array");
-      if (s.nblk > 1 && !frames) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
-    }
-    auto ext = [&](int kind) {
-      if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
-      s.ext_kind = kind;
-      s.spec.kind = kind;
-      s.spec.ndim = ndim_;
-      s.spec.G = G_;
-      for (int a = 0; a < 3; ++a) s.spec.dims[a] = G_.n[a];
-      if (s.nblk == 1) s.spec.dims[s.dir[0]] -= 1;           // TD_n of a difference operator (get_TD_operator.jl)
-      s.spec.mode = mode;
-      s.spec.dir = dir;
-      s.spec.pmin = d->pmin;
-      s.spec.pmax = d->pmax;
-      s.spec.nblk = s.nblk;                                  // EXT_L21: the blocks side by side, full padded grids
-      s.spec.bstride = G_.N;
-      for (int q = 0; q < 3; ++q) s.spec.bdir[q] = q < s.nblk ? s.dir[q] : 0;
-      s.prox = PX_EXT;
-      need_ext_ = true;
-    };
-    // l1 / l2 / annulus per fiber or slice: the scalars, or one radius per segment in ub (and lb: the annulus' inner radii)
-    auto seg_norm = [&](int kind) {
-      const bool vec = d->ub || (kind == EXT_ANNULUS_SEG && d->lb);
-      if (kind == EXT_L1_SEG && !vec && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
-      ext(kind);
-      if (!vec) return;
-      refuse_sharded_radii();
-      const long long nseg = seg_count(s.spec);
-      s.seg_radii = true;
-      if (d->ub) s.host_ub.assign((const T*)d->ub, (const T*)d->ub + nseg);
-      else s.host_ub.assign((size_t)nseg, (T)d->pmax);
-      if (kind == EXT_ANNULUS_SEG) {
-        if (d->lb) s.host_lb.assign((const T*)d->lb, (const T*)d->lb + nseg);
-        else s.host_lb.assign((size_t)nseg, (T)d->pmin);
-      }
-      if (kind == EXT_L1_SEG) check_l1_radii(s.host_ub.data(), nseg);
-    };
-    if (d->transform == SIPX_TRANSFORM_DCT) {      // x -> C' P(C x): P acts on the DCT coefficients (ext_proj.hip)
-      if (d->op != SIPX_OP_IDENTITY || mode != SIPX_MODE_WHOLE)
-        throw std::runtime_error("sets behind the DCT act in their own domain: TD_OP must be the identity, mode matrix/tensor");
-      if (d->proj != SIPX_PROJ_BOUNDS && d->proj != SIPX_PROJ_BOUNDS_VEC && d->proj != SIPX_PROJ_L1 &&
-          d->proj != SIPX_PROJ_CARDINALITY)
-        throw std::runtime_error("behind the DCT: bounds, the l1 ball and cardinality are built (l2 / annulus commute with it)");
-      if (d->proj == SIPX_PROJ_L1 && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-      if (d->proj == SIPX_PROJ_BOUNDS_VEC) {
-        if (!d->lb || !d->ub) throw std::runtime_error("per-element bounds need lb and ub");
-        s.host_lb.assign((const T*)d->lb, (const T*)d->lb + G_.N);
-        s.host_ub.assign((const T*)d->ub, (const T*)d->ub + G_.N);
-      }
-      ext(EXT_DCT);
-      s.spec.inner = d->proj;
-      return;
-    } else if (d->transform == SIPX_TRANSFORM_WAVELET) {      // x -> W' P(W x): P acts on the db4 wavelet coefficients (kernels_dwt.hip)
-      if (d->op != SIPX_OP_IDENTITY || mode != SIPX_MODE_WHOLE)
-        throw std::runtime_error("sets behind the wavelet transform act in their own domain: TD_OP must be the identity, mode matrix/tensor");
-      if (d->proj != SIPX_PROJ_BOUNDS && d->proj != SIPX_PROJ_L1 && d->proj != SIPX_PROJ_CARDINALITY)
-        throw std::runtime_error("behind the wavelet transform: scalar bounds, the l1 ball and cardinality are built (l2 / annulus commute "
-                                 "with it; per-element bounds would depend on the coefficient layout)");
-      if (d->proj == SIPX_PROJ_L1 && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-      dwt_check_grid(ndim_, G_.n);
-      ext(EXT_DWT);
-      s.spec.inner = d->proj;
-      return;
-    } else if (d->transform != SIPX_TRANSFORM_NONE) {
-      throw std::runtime_error("unknown transform");
-    }
-    switch (d->proj) {
-      case SIPX_PROJ_BOUNDS:
-        if (mode != SIPX_MODE_WHOLE) throw std::runtime_error("scalar bounds apply to the whole array (use per-fiber vectors)");
-        break;
-      case SIPX_PROJ_PROX_L1:
-        if (mode != SIPX_MODE_WHOLE) throw std::runtime_error("prox_l1 applies to the whole array");
-        break;
-      case SIPX_PROJ_BOUNDS_VEC:
-        if (!d->lb || !d->ub) throw std::runtime_error("per-element bounds need lb and ub");
-        if (mode == SIPX_MODE_SLICE)
-          throw std::runtime_error("bound constraints per slice of a tensor currently not implemented, yet...");   // project_bounds!.jl:83
-        s.bmode = mode;
-        s.bdir = dir;
-        if (mode == SIPX_MODE_FIBER) {      // bounds per fiber: expanded to one bound per row of A_i (reference order)
-          expand_fiber_bounds(s, (const T*)d->lb, s.host_lb);
-          expand_fiber_bounds(s, (const T*)d->ub, s.host_ub);
-          s.plo = T(1);                       // min(max(x, LB), UB): the fiber methods clip with LB first (project_bounds!.jl:47,65)
-        } else {
-          s.host_lb.assign((const T*)d->lb, (const T*)d->lb + s.Mtrue);
-          s.host_ub.assign((const T*)d->ub, (const T*)d->ub + s.Mtrue);
-          s.plo = T(0);
-        }
-        break;
-      // l1, l2, annulus: the whole array through the engine's own two-pass search; per fiber / slice (a gap of the reference,
-      // setup_constraints.jl:65-67 "currently") on the materialised vector, every segment by the same rule (seg_norm.h)
-      case SIPX_PROJ_L1:
-        if (mode == SIPX_MODE_WHOLE) {
-          if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");   // project_l1_Duchi!.jl:22
-          s.two_pass = true;
-        } else seg_norm(EXT_L1_SEG);
-        break;
-      case SIPX_PROJ_L2:
-        if (mode == SIPX_MODE_WHOLE) s.two_pass = true;
-        else seg_norm(EXT_L2_SEG);
-        break;
-      case SIPX_PROJ_ANNULUS:
-        if (mode == SIPX_MODE_WHOLE) s.two_pass = true;
-        else seg_norm(EXT_ANNULUS_SEG);
-        break;
-      case SIPX_PROJ_CARDINALITY:
-        if (mode == SIPX_MODE_WHOLE) { s.two_pass = true; need_idx_ = true; }
-        else ext(EXT_CARD_SEG);
-        break;
-      case SIPX_PROJ_L1_DFT:
-        if (d->op != SIPX_OP_IDENTITY || mode != SIPX_MODE_WHOLE)
-          throw std::runtime_error("the DFT-l1 projector acts in its own domain: TD_OP must be the identity, mode matrix/tensor");
-        if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-        ext(EXT_L1_DFT);
-        break;
-      case SIPX_PROJ_BOUNDS_DFT:
-        if (d->op != SIPX_OP_IDENTITY || mode != SIPX_MODE_WHOLE)
-          throw std::runtime_error("bounds in the DFT domain act in their own domain: TD_OP must be the identity, mode matrix/tensor");
-        if (!d->ub) throw std::runtime_error("bounds in the DFT domain need the mask vector (constraint.max)");
-        ext(EXT_DFT_MASK);
-        s.host_ub.assign((const T*)d->ub, (const T*)d->ub + G_.N);
-        break;
-      case SIPX_PROJ_CARD_DFT:
-        if (d->op != SIPX_OP_IDENTITY || mode != SIPX_MODE_WHOLE)
-          throw std::runtime_error("cardinality behind the DFT acts in its own domain: TD_OP must be the identity, mode matrix/tensor");
-        if (d->pmax < 0 || d->pmax != std::floor(d->pmax))
-          throw std::runtime_error("cardinality behind the DFT: k must be a non-negative integer");
-        ext(EXT_CARD_DFT);
-        break;
-      case SIPX_PROJ_L21:        // isotropic TV: groups across the blocks of the TV operator (l21.h), on the materialised vector
-        if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY)
-          throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
-        if (mode != SIPX_MODE_WHOLE && d->op == SIPX_OP_TV) throw std::runtime_error("the l2,1 ball applies to the whole array (mode matrix/tensor)");
-        if (s.comp) throw std::runtime_error("the l2,1 ball takes no Minkowski component");
-        if (G_.N >= (1ll << 31)) throw std::runtime_error("the l2,1 ball: the grid needs fewer than 2^31 points");
-        refuse_sharded_l21();
-        if (mode == SIPX_MODE_WHOLE) {
-          if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-          ext(EXT_L21);
-        } else {                 // per frame on TV_xy (checked above): the scalar, or one radius per frame in ub
-          if (!d->ub && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-          ext(EXT_L21_SEG);
-          if (d->ub) {
-            s.seg_radii = true;
-            s.host_ub.assign((const T*)d->ub, (const T*)d->ub + G_.n[2]);
-            check_l1_radii(s.host_ub.data(), G_.n[2]);
-          }
-        }
-        break;
-      case SIPX_PROJ_RANK: ext(EXT_RANK); break;
-      case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;
-      case SIPX_PROJ_HISTOGRAM:
-        if (!d->lb || !d->ub) throw std::runtime_error("histogram constraints need sorted lb and ub vectors");
-        ext(EXT_HISTOGRAM);
-        s.host_lb.assign((const T*)d->lb, (const T*)d->lb + s.Mtrue);     // kept on the host until the ExtProj is built
-        s.host_ub.assign((const T*)d->ub, (const T*)d->ub + s.Mtrue);
-        break;
-      case SIPX_PROJ_SUBSPACE:
-        if (d->op != SIPX_OP_IDENTITY) throw std::runtime_error("subspace constraints act on the model itself: TD_OP must be the identity");
-        if (!d->basis || d->basis_cols < 1 || d->basis_rows < 1) throw std::runtime_error("subspace constraints need the matrix A");
-        ext(EXT_SUBSPACE);
-        s.host_basis.assign((const T*)d->basis, (const T*)d->basis + (size_t)d->basis_rows * d->basis_cols);
-        s.spec.basis_rows = d->basis_rows;
-        s.spec.basis_cols = d->basis_cols;
-        s.spec.basis_orth = d->basis_orth;
-        break;
-      default: throw std::runtime_error("unknown projector kind");
-    }
-  }
-
-  // SIPX_OP_CSC: validate the SparseMatrixCSC arrays and keep host copies until sipx_finalize
-  void configure_custom(SetState<T>& s, const sipx_set_desc* d) const {
-    const long long N = G_.N, M = d->csc_rows;
-    if (!d->csc_colptr || !d->csc_rowval || !d->csc_nzval || M < 1) throw std::runtime_error("custom operator: CSC arrays missing");
-    const long long nnz = d->csc_colptr[N];
-    if (d->csc_colptr[0] != 0 || nnz < 0) throw std::runtime_error("custom operator: colptr must start at 0 (0-based arrays)");
-    for (long long j = 0; j < N; ++j) {
-      if (d->csc_colptr[j + 1] < d->csc_colptr[j]) throw std::runtime_error("custom operator: colptr must be non-decreasing");
-      for (long long k = d->csc_colptr[j]; k < d->csc_colptr[j + 1]; ++k) {
-        const long long r = d->csc_rowval[k];
-        if (r < 0 || r >= M) throw std::runtime_error("custom operator: row index out of range");
-        if (k > d->csc_colptr[j] && r <= d->csc_rowval[k - 1]) throw std::runtime_error("custom operator: rows must ascend inside a column");
-      }
-    }
-    s.op = SIPX_OP_CSC;
-    s.custom = true;
-    s.nblk = 0;                       // the set kernels see an identity over M entries
-    s.ident = false;
-    s.Mtrue = s.Mpad = M;
-    s.h_colptr.assign(d->csc_colptr, d->csc_colptr + N + 1);
-    s.h_rowval.assign(d->csc_rowval, d->csc_rowval + nnz);
-    s.h_nzval.assign((const T*)d->csc_nzval, (const T*)d->csc_nzval + nnz);
-    s.gm.n[0] = M; s.gm.n[1] = 1; s.gm.n[2] = 1; s.gm.N = M; s.gm.st[0] = 1; s.gm.st[1] = M; s.gm.st[2] = M;
-  }
-  // device copies: CSC as given, and the CSR view (rows ascending, columns ascending inside a row: a counting sort by row
-  // of the column-major entries keeps that order) for s = A x
-  // a matrix-free term addresses its arrays with 32-bit indices: rows, columns and entries all below 2^31
-  static void check_mf_index_range(long long N, long long M, long long nnz) {
-    if (N >= (1ll << 31) || M >= (1ll << 31) || nnz >= (1ll << 31))
-      throw std::runtime_error("custom sparse operator (SIPX_OP_CSC) without its A'A: the matrix-free term of Q uses 32-bit indices and needs "
-                               "fewer than 2^31 columns, rows and stored entries (" + std::to_string(N) + ", " + std::to_string(M) + ", " +
-                               std::to_string(nnz) + " given) -- split the operator into several sets");
-  }
   // Lanes that share one row of a compressed view: the smallest power of two that covers the mean length of the non-empty rows,
   // 1 .. 64.  A wave then reads 64 / G rows' runs of values and indices per step; rows longer than the group take further strides,
   // shorter ones leave lanes idle -- by the mean, as many lanes idle in the short rows as extra strides are walked in the long.
@@ -4084,6 +3779,8 @@ class Engine : public EngineBase {
     s.mfAt.rows = (int)N; s.mfAt.nnz = nnz; s.mfAt.ptr = s.mf_colptr; s.mfAt.idx = s.mf_rowidx; s.mfAt.val = s.d_nzval; s.mfAt.lanes = mf_lanes(colptr);
     s.h_colptr.clear(); s.h_rowval.clear(); s.h_nzval.clear();
   }
+  // device copies: CSC as given, and the CSR view (rows ascending, columns ascending inside a row: a counting sort by row
+  // of the column-major entries keeps that order) for s = A x
   void upload_custom(SetState<T>& s) {
     if (s.mfree) { upload_mfree(s); return; }
     const long long N = G_.N, M = s.Mtrue, nnz = (long long)s.h_rowval.size();
@@ -4107,60 +3804,6 @@ class Engine : public EngineBase {
     up(s.d_rowptr, rowptr); up(s.d_colidx, colidx); up(s.d_rval, rval);
     s.sbuf = mem_.alloc<T>(M, Mem::State);
     s.h_colptr.clear(); s.h_rowval.clear(); s.h_nzval.clear();
-  }
-
-  void configure_op(SetState<T>& s, int op) const {
-    s.op = op;
-    const int zdir = ndim_ == 2 ? 1 : 2;
-    switch (op) {
-      case SIPX_OP_IDENTITY: s.nblk = 0; break;
-      case SIPX_OP_DX: s.nblk = 1; s.dir[0] = 0; break;
-      case SIPX_OP_DY:
-        if (ndim_ == 2) throw std::runtime_error("D_y needs a 3-D grid");
-        s.nblk = 1; s.dir[0] = 1; break;
-      case SIPX_OP_DZ: s.nblk = 1; s.dir[0] = zdir; break;
-      case SIPX_OP_TV:                                   // vcat(D_z[,D_y],D_x): get_discrete_Grad.jl:31-33,69-72
-        if (ndim_ == 2) { s.nblk = 2; s.dir[0] = 1; s.dir[1] = 0; }
-        else { s.nblk = 3; s.dir[0] = 2; s.dir[1] = 1; s.dir[2] = 0; }
-        break;
-      case SIPX_OP_TV_XY:                                // vcat(D_y,D_x) on a 3-D grid: the in-plane part of TV
-        if (ndim_ == 2)
-          throw std::runtime_error("provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) "
-                                   "for options (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)");
-        s.nblk = 2; s.dir[0] = 1; s.dir[1] = 0;
-        break;
-      default: throw std::runtime_error("unknown operator kind");
-    }
-    s.ident = s.nblk == 0;
-    s.Mtrue = 0;
-    for (int q = 0; q < s.nblk; ++q) {
-      const int a = s.dir[q];
-      if (G_.n[a] < 2) throw std::runtime_error("difference operator along a dimension of size 1");
-      s.ih[q] = ih_[a];
-      s.blk_rows[q] = G_.N / G_.n[a] * (G_.n[a] - 1);
-      s.Mtrue += s.blk_rows[q];
-    }
-    if (s.ident) s.Mtrue = G_.N;
-    s.Mpad = s.ident ? G_.N : (long long)s.nblk * G_.N;
-  }
-
-  std::vector<long long> default_ata_offsets(const SetState<T>& s) const {   // mat2CDS: ascending (mat2CDS.jl:9-13)
-    std::vector<long long> o = {0};
-    for (int q = 0; q < s.nblk; ++q) {
-      o.push_back(G_.st[s.dir[q]]);
-      o.push_back(-G_.st[s.dir[q]]);
-    }
-    std::sort(o.begin(), o.end());
-    o.erase(std::unique(o.begin(), o.end()), o.end());
-    if (s.comp == 3) {     // [B B; B B]: every diagonal of B also shifted by -N and +N (mat2CDS of the 2N x 2N block matrix)
-      std::vector<long long> all;
-      for (long long sh : {-G_.N, 0ll, G_.N})
-        for (long long v : o) all.push_back(v + sh);
-      std::sort(all.begin(), all.end());
-      all.erase(std::unique(all.begin(), all.end()), all.end());
-      return all;
-    }
-    return o;
   }
 
   int q_col(long long off) const {
@@ -4439,7 +4082,7 @@ class Engine : public EngineBase {
 
   // Import / export between the reference's row order (host) and the padded layout (device): one contiguous PCIe
   // copy plus a device gather / scatter per operator block (the pads keep the zeros they were allocated with).
-  void upload_rows(const SetState<T>& s, const T* rows, T* dev) const {
+  void upload_rows(const SetConfig<T>& s, const T* rows, T* dev) const {
     io_h2d_ += s.Mtrue * (long long)sizeof(T);
     if (s.ident || s.custom) {
       SIPX_HIP(hipMemcpy(dev, rows, (size_t)s.Mtrue * sizeof(T), hipMemcpyHostToDevice));
@@ -4466,7 +4109,7 @@ class Engine : public EngineBase {
       SIPX_HIP(hipMemcpy(dev + (long long)q * G_.N + c0, full + (long long)q * G_.N + c0, (c1 - c0) * sizeof(T), hipMemcpyDeviceToDevice));
     SIPX_HIP(hipDeviceSynchronize());
   }
-  void download_rows(const SetState<T>& s, const T* dev, T* rows) const {
+  void download_rows(const SetConfig<T>& s, const T* dev, T* rows) const {
     io_d2h_ += s.Mtrue * (long long)sizeof(T);
     SIPX_HIP(hipStreamSynchronize(stream_));
     if (s.ident || s.custom) {

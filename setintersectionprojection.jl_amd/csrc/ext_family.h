@@ -129,6 +129,8 @@ inline SegMap make_segmap(const ExtSpec& sp) {
   }
   return m;
 }
+// segments of a spec: the entries of seg_observe's output and of a vector of per-segment radii
+inline long long seg_count(const ExtSpec& spec) { return make_segmap(spec).nseg; }
 
 // dense[s * L + t] <- v[seg_addr(s, t)] and back (U = double for the SVD path, T otherwise).  `flag` (optional):
 // segments with flag[s] == 0 are left untouched by the scatter.

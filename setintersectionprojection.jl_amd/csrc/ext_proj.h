@@ -60,11 +60,10 @@ class ExtProj {
   ExtImpl<T>* impl_;
 };
 
-// out[s] <- the l1 (norm_l2 = 0) or l2 norm of segment s of v (padded layout, spec.mode FIBER / SLICE), seg_count(spec) entries in the
-// order of the per-segment radii (seg_norm.h: k_seg_observe)
+// out[s] <- the l1 (norm_l2 = 0) or l2 norm of segment s of v (padded layout, spec.mode FIBER / SLICE), seg_count(spec) entries
+// (ext_family.h) in the order of the per-segment radii (seg_norm.h: k_seg_observe)
 template <typename T>
 void seg_observe(const ExtSpec& spec, int norm_l2, const T* v, T* out, hipStream_t stream);
-long long seg_count(const ExtSpec& spec);
 
 // out[0] (device) <- ||v||_2,1 of a materialised vector in the layout of an EXT_L21 spec, as the projector's own decision sums and
 // rounds it (ext_group.hip); g: N entries of scratch, ps / partials / maxpart / compact: those of a threshold search over N entries

@@ -241,7 +241,6 @@ void seg_observe(const ExtSpec& spec, int norm_l2, const T* v, T* out, hipStream
 }
 template void seg_observe<float>(const ExtSpec&, int, const float*, float*, hipStream_t);
 template void seg_observe<double>(const ExtSpec&, int, const double*, double*, hipStream_t);
-long long seg_count(const ExtSpec& spec) { return make_segmap(spec).nseg; }
 
 template <typename T>
 struct HistogramProj : ExtImpl<T> {

@@ -249,21 +249,12 @@ struct Shape {
 };
 
 Shape shape_of(int ndim, const long long* n) {
-  if (ndim != 2 && ndim != 3) throw std::runtime_error("wavelet transform: 2-D and 3-D grids only");
+  dwt_check_grid(ndim, n);
   Shape sh;
   sh.ndim = ndim;
   sh.n[0] = n[0]; sh.n[1] = n[1]; sh.n[2] = ndim == 3 ? n[2] : 1;
   sh.N = sh.n[0] * sh.n[1] * sh.n[2];
-  if (sh.n[0] < 1 || sh.n[1] < 1 || sh.n[2] < 1) throw std::runtime_error("wavelet transform: empty grid");
-  if (sh.N >= (1LL << 31)) throw std::runtime_error("wavelet transform: grids of 2^31 points and more are not supported");
   sh.L = dwt_levels(ndim, n);
-  for (int a = 0; a < ndim; ++a)
-    if (sh.n[a] % (1LL << sh.L) != 0) {
-      std::string g = std::to_string(sh.n[0]);
-      for (int q = 1; q < ndim; ++q) g += " x " + std::to_string(sh.n[q]);
-      throw std::runtime_error("wavelet transform: the grid " + g + " has " + std::to_string(sh.L) + " levels (2^L divides the smallest "
-                               "dimension) but dimension " + std::to_string(a + 1) + " is not divisible by 2^" + std::to_string(sh.L));
-    }
   return sh;
 }
 
@@ -288,16 +279,6 @@ void level_box(const Shape& sh, int l, long long* b) {
 }
 
 }  // namespace
-
-void dwt_check_grid(int ndim, const long long* n) { (void)shape_of(ndim, n); }
-
-int dwt_levels(int ndim, const long long* n) {
-  long long m = n[0];
-  for (int a = 1; a < ndim; ++a) m = n[a] < m ? n[a] : m;
-  int L = 0;
-  while (m > 0 && m % 2 == 0) { m /= 2; ++L; }
-  return L;
-}
 
 template <typename T>
 void dwt_forward(hipStream_t s, int ndim, const long long* n, const T* in, T* out, T* scratch) {

@@ -46,7 +46,8 @@ OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4,
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
-# the engine's refusals of the l2,1 ball (csrc/engine.cpp, configure_proj), word for word
+# the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
+# engine refuses as it does for every multi-block operator, the front end in words of the set's own
 L21_NEEDS_TV = "the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)"
 L21_WHOLE_ONLY = "the l2,1 ball applies to the whole array (mode matrix/tensor)"
 # TV_xy = vcat(D_y, D_x), the in-plane gradient of a 3-D grid (include/sipx.h, SIPX_OP_TV_XY): the engine's own, with its refusals
