@@ -1084,7 +1084,8 @@ class Engine : public EngineBase {
     for (int i = 0; i < p_n_ && slab_; ++i)
       if (hovf_[i]) {
         hovf_[i] = 0;
-        throw std::runtime_error("initial feasibility of set " + std::to_string(i) + ": the magnitudes inside the final bracket of the l1 search, gathered over all ranks, exceed the exchange segment of " +
+        throw std::runtime_error("initial feasibility of set " + std::to_string(i) + ": the magnitudes inside the final bracket of the " + std::string(sets_[i].prox == PX_CARD ? "cardinality" : "l1") +
+                                 " search, gathered over all ranks, exceed the exchange segment of " +
                                  std::to_string(hooks_.gcap) + " values per rank (slab decomposition) -- use the set decomposition for this problem");
       }
     for (int i = 0; i < pp_n_; ++i) {
@@ -2521,7 +2522,7 @@ class Engine : public EngineBase {
                               d == sets_[i].ps ? "y/l update" : "feasibility estimate", h.lo, h.hi, h.rounds_used, h.asum, (double)sets_[i].phi, h.spec_lo, h.spec_hi);
         }
         dbg[at] = 0;
-        throw std::runtime_error("l1 threshold search of set " + std::to_string(i) + ": the magnitudes inside the final bracket, gathered over all "
+        throw std::runtime_error(std::string(sets_[i].prox == PX_CARD ? "cardinality search" : "l1 threshold search") + " of set " + std::to_string(i) + ": the magnitudes inside the final bracket, gathered over all "
                                  "ranks, exceed the exchange segment of " + std::to_string(hooks_.gcap) + " values per rank "
                                  "(slab decomposition) after the refinement rounds of the search; the iterate of this step is not valid -- "
                                  "use the set decomposition for this problem" + std::string(dbg));

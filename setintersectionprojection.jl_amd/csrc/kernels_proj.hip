@@ -1606,7 +1606,9 @@ __global__ __launch_bounds__(SIPX_SOLVE_NT) void k_l1_solve(ProjScalars<T>* ps, 
 
 // ---------------------------------------------------------------------------------------------
 // Cardinality: tau = k-th largest magnitude.  Bracket (lo, hi] with C(lo) >= k > C(hi) from the probe counts,
-// refined by gated probe passes until it holds at most CARD_CAP magnitudes (or the passes run out).
+// refined by gated probe passes until it holds at most CARD_CAP magnitudes (or the passes run out).  When they run out
+// (a tie group larger than the cap at the k-th place, an outlier that stretches the axis) everything still inside the bracket
+// is gathered: `compact` and `cidx` hold a full vector, and the selection works on however many pairs there are.
 constexpr double CARD_CAP = 8192.0;
 constexpr int CARD_REFINES = 5;
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import parsdmm_oracle as O
+from tests import card_exact as XC
 from tests import l1_exact as X
 
 pytestmark = pytest.mark.gpu
@@ -151,6 +152,7 @@ HITS = plan((1, 1, "cold"), (1, G, "hit"), (1, G, "lean"), (1, S, "lean-miss"), 
 FAR = plan((1, 1, "cold"), (1, 1, "beyond"), (1, G, "hit"), (1, G, "lean"), (2, G, "lean"), (1, G, "lean"), (1, G, "lean"))
 FEAS = plan((1, 1, "cold"), (1, G, "hit"), (16, 1, "feasible"), (1, -31, "stale"), (1, G, "hit"), (16, 1, "feasible"), (1, -31, "stale"))
 SHORT = plan((1, 1, "cold"), (1, G, "hit"), (1, G, "lean"))
+CARD3 = plan(*[(1, 1, "card")] * 3)
 ALLACT = plan((1, 1, "cold"), (1, G, "hit"), (1, G, "hit"))      # (every entry active: the solve never announces a lean pass)
 
 CASES = {
@@ -207,6 +209,19 @@ CASES = {
     "card-dz": dict(n=(36, 20, 9), x="integers", sets=[("bounds",), ("l1", "D_x", "heavy", 0.3, SHORT), ("card", "D_z", plan(*[(1, 1, "card")] * 3))]),
     "cardf-dy": dict(n=(36, 20, 9), x="integers", sets=[("bounds",), ("l1", "D_z", "heavy", 0.3, SHORT),
                                                          ("cardf", "D_y", ("slice", "z"), plan(*[(1, 1, "card")] * 3))]),
+    # the whole-vector search on its hostile inputs (tests/test_gpu_card_exact.py drives and checks these)
+    # |D_z x| in {0, 1}: 23040 rows, about 11500 ones -- one tie group above CARD_CAP; n1 % 4 == 0: the vector kernel
+    "card-dz-big-vec": dict(n=(48, 32, 16), x="binary", sets=[("bounds",), ("card", "D_z", CARD3)]),
+    "card-dz-big-odd": dict(n=(45, 32, 17), x="binary", sets=[("bounds",), ("card", "D_z", CARD3)]),          # the scalar kernel
+    # three padded blocks (two in 2-D), M != N: the index order across blocks and pads decides who survives
+    "card-tv-3d": dict(n=(36, 20, 9), x="integers", sets=[("bounds",), ("card", "TV", CARD3)]),
+    "card-tv-2d": dict(n=(33, 27), x="integers", sets=[("bounds",), ("card", "TV", CARD3)]),
+    # the outlier stretches (0, vmax]: the five passes of the cold search run out with everything but the outlier in the bracket
+    "card-id-outlier": dict(n=(120, 100), x="outlier", sets=[("bounds",), ("card", "identity", CARD3)]),
+    # call 2, gamma = 3 (an extrapolation, as after a feasible call of an l1 set): the dropped entries come back four times as
+    # large, tau more than doubles -- the warm bracket (2 tau_prev, vmax]; call 3, rho * 16: the multiplier term all but
+    # vanishes, v is s = A x again and tau the first call's, less than half of the second's -- the warm bracket (0, tau_prev / 2]
+    "card-moves": dict(n=(48, 32, 16), x="heavy", sets=[("bounds",), ("card", "D_z", plan((1, 1, "card"), (1, 3, "card"), (16, 1, "card")))]),
 }
 
 
@@ -220,6 +235,14 @@ def make_x(kind, n, TF, rng):
         return cluster_vector(rng, int(np.prod(n)), TF)
     if kind == "integers":
         return rng.integers(0, 6, n).astype(TF).reshape(-1, order="F")
+    if kind == "binary":                     # layers of equal jumps: |D_z x| is 0 or 1
+        return rng.integers(0, 2, n).astype(TF).reshape(-1, order="F")
+    if kind == "outlier":                    # magnitudes in [1, 2] and one entry of 1e9 (tests/card_exact.py, `outlier`)
+        x = ((1.0 + rng.random(n)) * np.sign(rng.standard_normal(n))).astype(TF).reshape(-1, order="F")
+        x[len(x) // 3] = TF(1e9)
+        return x
+    if kind == "heavy":
+        return heavy(rng, int(np.prod(n)), TF)
     z = np.linspace(0, 1, n[-1]).reshape((1,) * (len(n) - 1) + (-1,))
     return (2.0 * z + rng.standard_normal(n)).astype(TF).reshape(-1, order="F")
 
@@ -244,9 +267,12 @@ def build(mod, n, TF, sets, radii, cards):
 
 
 class Chain:
-    """One context, x fixed; step() makes one ctx.update_y_l and replays it in the oracle from the engine's own state."""
+    """One context, x fixed; step() makes one ctx.update_y_l and replays it in the oracle from the engine's own state.
+    sipx = None: no engine at all -- oracle_step() advances the same chain in the oracle alone (what the ranks of a
+    slab-decomposed context are held to by a parent that has no context of its own)."""
 
-    def __init__(self, sipx, case, TF, rho0=8.0, stats=True):
+    def __init__(self, sipx, case, TF, rho0=8.0, stats=True, **ctx_kw):
+        """ctx_kw: device, owned, attach of host.build_context (a rank of a slab-decomposed context)."""
         self.sipx, self.TF, self.stats = sipx, TF, stats
         n, sets = case["n"], case["sets"]
         rng = np.random.default_rng(len(n) * 1000 + n[0])
@@ -286,7 +312,7 @@ class Chain:
                     radii[i] = float(TF(s[3] * float(np.abs(w.astype(np.float64)).sum())))
                 self.b[i] = radii[i]
             elif s[0] == "card":
-                cards[i] = int(0.3 * M)
+                cards[i] = int(case.get("card_frac", 0.3) * M)
             else:
                 ax = {"x": 0, "y": 1, "z": len(n) - 1}[s[2][1]]
                 cards[i] = max(1, int(0.3 * (int(np.prod(tdn)) // tdn[ax])))
@@ -296,17 +322,44 @@ class Chain:
         y0.append(self.x.copy())
         self.cards = cards
         self.go, self.oo, self.Po, self.Ao, self.propo, _ = build(O, n, TF, sets, radii, cards)
-        gs, os_, Ps, As, props, AtAs = build(sipx, n, TF, sets, radii, cards)
-        os_.zero_ini_guess = False
-        os_.rho_ini = [float(r) for r in self.rho]
-        self.ctx = sipx.host.build_context(self.m, AtAs, As, props, Ps, gs, os_, x=self.x, l=l0, y=y0)
+        self.ctx = None
+        if sipx is not None:
+            gs, os_, Ps, As, props, AtAs = build(sipx, n, TF, sets, radii, cards)
+            os_.zero_ini_guess = False
+            os_.rho_ini = [float(r) for r in self.rho]
+            self.ctx = sipx.host.build_context(self.m, AtAs, As, props, Ps, gs, os_, x=self.x, l=l0, y=y0, **ctx_kw)
         self.y, self.l = [v.copy() for v in y0], [v.copy() for v in l0]
         self.diag = {i: None for i in self.l1}
         self.batched = None
         self.calls = 0
 
     def close(self):
-        self.ctx.close()
+        if self.ctx is not None:
+            self.ctx.close()
+
+    def oracle_step(self, factors, gamma):
+        """The same call in the oracle alone.  Returns {cardinality set: dict(v, y, l)} and advances y, l."""
+        TF, p = self.TF, self.p
+        self.rho = self.rho * np.asarray(factors, np.float64)
+        rho, gam = self.rho.astype(TF), np.asarray(gamma, np.float64).astype(TF)
+        seen = {}
+
+        def card_prox(i):
+            def f(v):
+                seen[i] = v.copy()
+                return self.Po[i](v)
+            return f
+        prox = [card_prox(i) if i in self.card else self.Po[i] for i in range(p - 1)]
+        prox.append(lambda v: O.prox_l2s(v, rho[p - 1], self.m))
+        z = lambda: [np.zeros(self.Ao[i].shape[0], TF) for i in range(p)]
+
+        class L:
+            pass
+        log = L()
+        log.r_pri = np.zeros((1, p)); log.r_dual = np.zeros((1, p)); log.set_feasibility = np.zeros((1, p - 1))
+        O.update_y_l(self.x.copy(), p, 1, self.y, z(), self.l, z(), rho, gam, prox, self.Ao, log, self.Po, 1, z(), z(), z())
+        self.calls += 1
+        return {i: dict(v=seen[i], y=self.y[i].copy(), l=self.l[i].copy()) for i in self.card}
 
     def step(self, factors, gamma, flags=0, it=1):
         """One call.  Returns {set: record}; every l1 / cardinality set has been checked when it returns."""
@@ -323,6 +376,7 @@ class Chain:
         self.batched = (c1["searches"] - c0["searches"], c1["fallbacks"] - c0["fallbacks"])
         _, le, ye = ctx.download()
         dg = {i: ctx.debug_proj(i, 0) for i in self.l1}
+        dgc = {i: ctx.debug_proj(i, 0) for i in self.card}      # need, lo, hi, vmax, gathered (n_compact at the selection), refine
         # the oracle from the state the engine had before the call; the l1 prox thresholds with the ENGINE's theta
         seen = {}
 
@@ -366,7 +420,12 @@ class Chain:
         for i in self.card:
             assert X.same_bits(ye[i], y[i]), f"call {self.calls + 1}, cardinality set {i}: y is not the oracle's bit for bit"
             assert X.same_bits(le[i], l[i]), f"call {self.calls + 1}, cardinality set {i}: l"
-            out[i] = dict(v=seen[i], y=ye[i])
+            if self.sets[i][0] == "card":
+                try:
+                    XC.check_card_output(seen[i], ye[i], self.cards[i])
+                except AssertionError as e:
+                    raise AssertionError(f"call {self.calls + 1}, cardinality set {i}: {e}; diagnostics {dgc[i]}") from None
+            out[i] = dict(v=seen[i], y=ye[i], d=dgc[i])
         self.y, self.l = ye, le
         self.diag = dg
         self.calls += 1
