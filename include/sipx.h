@@ -108,7 +108,22 @@ enum {
                                 Radii as for the per-segment l1 ball: ub = NULL gives every frame pmax, ub = TF[n3] frame k its own,
                                 replaceable through sipx_set_data(_dev); an entry that is not > 0 is refused by every host path,
                                 from device memory it zeroes a frame that is not all zero.  Other fiber / slice modes are refused:
-                                frames run along z.  sipx_l21_norms observes the norms */
+                                frames run along z.  sipx_l21_norms observes the norms */,
+  SIPX_PROJ_L21_JOINT   = 15 /* joint (vectorial) isotropic total variation across frames (no counterpart in the reference): the
+                                l2,1 ball { v : sum_{(i,j)} g_ij <= pmax } on the range of SIPX_OP_TV_XY, with ONE group per pixel
+                                (i, j) that spans the frames: for every k the D_y difference that starts at (i, j, k) if j < n2 - 1
+                                and the D_x difference if i < n1 - 1 -- 0 to 2 n3 members, so the frames share their edges.  op must
+                                be SIPX_OP_TV_XY (a 3-D grid), mode WHOLE, transform NONE, no custom operator, pmax = tau > 0
+                                ("Radius of L1 ball is negative" otherwise, NaN included); any other combination is refused with
+                                "the joint l2,1 ball groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor".  g_ij from a
+                                float64 sum of squares in a fixed order (frames ascending, D_y then D_x; the z range possibly in
+                                chunks that depend on the grid and TF alone) rounded once to TF, the threshold of SIPX_PROJ_L1 on
+                                the n1 n2 numbers g, every member of group (i, j) in every frame scaled by max(g - theta, 0) / g;
+                                an input inside the ball is not written, -0.0 included; no floating-point atomics: two calls give
+                                the same bits (csrc/l21_joint.h).  Holds no replaceable vectors (sipx_set_data refuses).  Contexts
+                                with a communicator, a slab decomposition or set ownership refuse it, as they refuse the
+                                operator.  sipx_project takes the M-vector of the TV_xy range in the row order of SIPX_OP_TV_XY
+                                and refuses any other length with both lengths; sipx_l21_joint_norm observes the norm */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -372,6 +387,13 @@ int sipx_l21_norm_dev(sipx_ctx* ctx, const void* x, void* out);
  * receives the number of values; x = out = NULL only asks for it.  Every other combination is refused as sipx_add_set refuses it. */
 int sipx_l21_norms(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
 int sipx_l21_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
+/* The joint total variation of the frames of x: *out = one TF, the sum over the pixels (i, j) of the group norms g_ij of SIPX_PROJ_L21_JOINT
+ * on [D_y; D_x] x, x TF[N] on the 3-D grid of the context.  The norms come from the z-march of the projector, the sum from the first
+ * pass of its threshold search.  CONTRACT: the value is the very number the projector compares with pmax, so a radius observed on x
+ * leaves [D_y; D_x] x unwritten.  x, out: host memory; the _dev form takes both in device memory of the context's GPU, ordered like
+ * sipx_l21_norm_dev against the caller's stream.  Refused where the set is refused (2-D grids, sharded contexts). */
+int sipx_l21_joint_norm(sipx_ctx* ctx, const void* x, void* out);
+int sipx_l21_joint_norm_dev(sipx_ctx* ctx, const void* x, void* out);
 /* nearest-neighbour resampling of an array of shape nc to shape nf, the grid transfer of PARSDMM_multi_level:
  * out[k] = in[round(1 + (k-1)(nc-1)/(nf-1))] per axis (Interpolations.BSpline(Constant()) evaluated on
  * range(1, stop=nc, length=nf); src/PARSDMM_multi_level.jl:41-45,61-65, src/interpolate_y_l.jl:32-88) */

@@ -56,7 +56,8 @@ mutable struct SipxLog                 # sipx_log: flat row-major arrays the cal
     n_iter::Int32; n_feas_rows::Int32; stopped_feasible::Int32
 end
 
-const OPS  = Dict("identity" => 0, "D_x" => 1, "D_y" => 2, "D_z" => 3, "TV" => 4, "D2D" => 4, "D3D" => 4)
+const OPS  = Dict("identity" => 0, "D_x" => 1, "D_y" => 2, "D_z" => 3, "TV" => 4, "D2D" => 4, "D3D" => 4,
+                 "TV_xy" => 6)      # (libsipx's own in-plane gradient of a 3-D grid: SIPX_OP_TV_XY)
 # SIPX_OP_TV_XY (include/sipx.h): the in-plane gradient [D_y; D_x] of a 3-D grid, libsipx's own.  The reference's get_TD_operator has no
 # such name, so setup_constraints of this shim cannot build the set; the code is mirrored for callers of the C ABI.
 const SIPX_OP_TV_XY = 6
@@ -116,6 +117,15 @@ function projector_fields(c, TF)
         c.app_mode[1] in ("matrix", "tensor") || error("the l2,1 ball applies to the whole array (mode matrix/tensor)")
         c.max > 0 || error("Radius of L1 ball is negative")
         return (14, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
+    # joint (vectorial) total variation across frames: one group per pixel on the range of TV_xy (include/sipx.h, SIPX_PROJ_L21_JOINT;
+    # neither the set nor the operator is the reference's: its setup_constraints cannot build TD_OP = "TV_xy", so this tag reaches
+    # libsipx only from a caller that assembles the descriptor list itself, with OPS["TV_xy"])
+    if st == "l21_joint"
+        op == "TV_xy" && c.custom_TD_OP[1] == [] && c.app_mode[1] in ("matrix", "tensor") ||
+            error("the joint l2,1 ball groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor")
+        c.max > 0 || error("Radius of L1 ball is negative")
+        return (15, 0.0, Float64(c.max), nothing_[3:5]...)
     end
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "l2"          && return (3, 0.0, Float64(c.max), nothing_[3:5]...)

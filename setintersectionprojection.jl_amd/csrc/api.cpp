@@ -150,6 +150,12 @@ int sipx_l21_norms(sipx_ctx* c, int op, int mode, int dir, const void* x, void* 
 int sipx_l21_norms_dev(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(op, mode, dir, x, out, nseg, true))
 }
+int sipx_l21_joint_norm(sipx_ctx* c, const void* x, void* out) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_joint_norm(x, out, false))
+}
+int sipx_l21_joint_norm_dev(sipx_ctx* c, const void* x, void* out) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_joint_norm(x, out, true))
+}
 int sipx_get_Q(sipx_ctx* c, void* Q, int64_t* offsets, int* d) { SIPX_TRY(c->e->get_Q(Q, offsets, d)) }
 int sipx_q_terms(sipx_ctx* c, int* bands, int* matrix_free) { SIPX_TRY(c->e->q_terms(bands, matrix_free)) }
 int sipx_time_spmv(sipx_ctx* c, int reps, double* avg_ms) { SIPX_TRY(*avg_ms = c->e->time_spmv(reps)) }

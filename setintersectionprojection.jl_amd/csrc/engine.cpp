@@ -7,6 +7,7 @@
 #include "dist_dft.h"
 #include "ext_proj.h"
 #include "host_prefault.h"
+#include "l21_joint.h"
 #include "set_config.h"
 #include "solve_rules.h"
 #include "sparse_granules.h"
@@ -384,7 +385,7 @@ class Engine : public EngineBase {
     for (const auto& s : sets_) {
       if (s.seg_radii) refuse_sharded(ctx, Sharded::RADII);
       if (s.op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
-      if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG) refuse_sharded(ctx, Sharded::L21);
+      if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG || s.ext_kind == EXT_L21_JOINT) refuse_sharded(ctx, Sharded::L21);
     }
     FinalizePlan P;
     plan_sets();
@@ -3303,6 +3304,8 @@ class Engine : public EngineBase {
   // SIPX_PROJ_L21 of sipx_project: the M-vector of the TV range in the reference's row order, through the packing of a TV set's y / l
   void project_l21(const sipx_set_desc* d, void* v, int64_t len) {
     SetConfig<T> st;
+    if (d->proj == SIPX_PROJ_L21_JOINT && d->op != SIPX_OP_TV_XY)
+      throw std::runtime_error(L21_JOINT_ROUTE);
     if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY)
       throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
     const ConfigCtx ctx = config_ctx();
@@ -3361,9 +3364,38 @@ class Engine : public EngineBase {
     finish_call(on_device, out, dout, nout);
   }
 
+  // sipx_l21_joint_norm(_dev): the sum of the n1 n2 group norms of TV_xy x, the groups spanning the frames, by the z-march of the joint
+  // projector and the first pass of its search (ext_group.hip)
+  void l21_joint_norm(const void* x, void* out, bool on_device) override {
+    SIPX_HIP(hipSetDevice(device_));
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, SIPX_OP_TV_XY);
+    refuse_sharded(ctx, Sharded::TV_XY);
+    sipx_set_desc d{};
+    d.op = SIPX_OP_TV_XY; d.proj = SIPX_PROJ_L21_JOINT; d.mode = SIPX_MODE_WHOLE; d.pmax = 1.0;
+    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the set
+    if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed");
+    const long long L = G_.st[2];
+    const L21JointPlan plan = l21_joint_plan(L, G_.n[2], (int)sizeof(T));
+    DeviceMemory tmp;
+    const OpScratch w = forward_scratch(tmp, s, on_device);
+    T* g = tmp.alloc<T>(L);
+    double* part = plan.nchunk > 1 ? tmp.alloc<double>((size_t)plan.nchunk * L) : nullptr;
+    const SearchScratch q(tmp, L, true);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
+    const T* dv = queue_forward(w, s, x, on_device);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 1) * G_.N * sizeof(T));
+      l21_joint_observe<T>(s.spec, dv, g, part, q.ps, q.part, q.mp, q.dc, dout, stream_);
+    }
+    finish_call(on_device, out, dout, 1);
+  }
+
   void project(const sipx_set_desc* d, void* v, int64_t len) override {
     SIPX_HIP(hipSetDevice(device_));
-    if (d->proj == SIPX_PROJ_L21) { project_l21(d, v, len); return; }
+    if (d->proj == SIPX_PROJ_L21 || d->proj == SIPX_PROJ_L21_JOINT) { project_l21(d, v, len); return; }
     Grid g1;
     g1.n[0] = len; g1.n[1] = 1; g1.n[2] = 1; g1.N = len; g1.st[0] = 1; g1.st[1] = len; g1.st[2] = len;
     DeviceMemory tmp;

@@ -2,7 +2,7 @@
 //   ext_transform.hip  DFT mask, l1 and cardinality behind the DFT, DCT, DWT
 //   ext_rank.hip       slice / matrix rank, nuclear norm
 //   ext_segments.hip   cardinality, l1, l2 and annulus per fiber / slice (seg_norm.h), relaxed histogram, subspace
-//   ext_group.hip      the l2,1 ball across the blocks of the TV / TV_xy operator (l21.h), per z-slice (l21_seg.h)
+//   ext_group.hip      the l2,1 ball across the blocks of the TV / TV_xy operator (l21.h), per z-slice (l21_seg.h), across the frames (l21_joint.h)
 // -- and what more than one family uses.
 #pragma once
 #define ROCBLAS_BETA_FEATURES_API 1

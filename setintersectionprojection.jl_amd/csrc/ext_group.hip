@@ -10,8 +10,11 @@
 // Both kernels are grid-stride over the N grid points with 32-bit index arithmetic (N < 2^31 is checked when the projector is
 // built), use no LDS, and take VW points per thread: 16 bytes of every array when n1 % 4 == 0 (then N and every block base
 // are 16-byte aligned and the VW points lie on one grid line), one point otherwise.  g lives in the projector's own memory.
+// Further down: the ball of every z-slice of TV_xy (EXT_L21_SEG, l21_seg.h) and the ball whose groups span the frames (EXT_L21_JOINT,
+// l21_joint.h), each with the kernels it adds.
 #include "ext_family.h"
 #include "l21.h"
+#include "l21_joint.h"
 #include "l21_seg.h"
 
 namespace sipx {
@@ -60,7 +63,8 @@ __global__ __launch_bounds__(BLOCK) void k_l21_norms(L21Args a, const T* __restr
 
 // FRAMES (EXT_L21_SEG, l21_seg.h): every z-slice has its own threshold and decision, theta[k] / need[k] of k_l21_frames at the z
 // coordinate of the VW points (one grid line: one frame); a frame with need == 0 is skipped without a store, need == 3 is zeroed
-template <typename T, int NBLK, int VW, bool FRAMES>
+// JOINT (EXT_L21_JOINT, l21_joint.h): g holds one norm per pixel, the weight of grid point p is read at its pixel index p - k L
+template <typename T, int NBLK, int VW, bool FRAMES, bool JOINT = false>
 __global__ __launch_bounds__(BLOCK) void k_l21_scale(L21Args a, T* __restrict__ v, const T* __restrict__ g,
                                                      const ProjScalars<T>* __restrict__ ps, const T* __restrict__ theta,
                                                      const int* __restrict__ need) {
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(BLOCK) void k_l21_scale(L21Args a, T* __restrict__ 
       th = theta[c.k];
       zero = act == 3;
     }
-    const Vec<T, VW> gv = ldv<T, VW>(g + p);
+    const Vec<T, VW> gv = ldv<T, VW>(g + (JOINT ? p - (unsigned)c.k * (unsigned)a.G.st[2] : p));
     T f[VW];
 #pragma unroll
     for (int k = 0; k < VW; ++k) f[k] = l21_weight<T>(gv.v[k], th);
@@ -340,8 +344,161 @@ struct FrameProj : ExtImpl<T> {
   }
 };
 
+// ---- EXT_L21_JOINT: the l2,1 ball whose groups span the frames, on the range of TV_xy (l21_joint.h) ---------------------------------------
+//     k_l21j_norms    the z-march: g[pixel] or the chunk sums part[c L + pixel]               reads 2 N words, writes L (or nchunk L doubles)
+//     k_l21j_finish   more than one chunk: g[pixel] from the chunk sums, ascending c           reads nchunk L doubles, writes L
+//     the engine's l1 threshold search on the L numbers g (and the Float64 refinement above)   its passes over L words
+//     k_l21_scale     the JOINT form: the weight of grid point p from g[p - k L]               reads 2 N + L words, writes 2 N
+struct L21JArgs {
+  Grid G;
+  long long bstride;
+  L21JointPlan plan;
+};
+// frames a thread loads before it uses the first: 2 L21J_BATCH loads of 16 bytes (or one entry) in flight per lane, as l21_seg_each
+// keeps L21_SEG_LOADS -- a thread's walk is a chain of n3 / L21J_BATCH exposed memory latencies, not n3
+constexpr int L21J_BATCH = L21_SEG_LOADS / 2;
+
+// A thread owns the VW consecutive pixels p .. p + VW - 1 (one grid line of the frame) in one chunk and walks the chunk's frames with
+// stride L; PART: the float64 chunk sums go to part[c L + p] (k_l21j_finish adds them), otherwise the chunk is the whole z range and
+// g is written.  Grid-stride over the nchunk L / VW items; every index stays below N < 2^31.
+template <typename T, int VW, bool PART>
+__global__ __launch_bounds__(BLOCK) void k_l21j_norms(L21JArgs a, const T* __restrict__ v, T* __restrict__ g, double* __restrict__ part) {
+  const unsigned L = (unsigned)a.G.st[2], n3 = (unsigned)a.G.n[2], nvec = L / VW;
+  const unsigned items = nvec * (PART ? (unsigned)a.plan.nchunk : 1u), step = gridDim.x * BLOCK;
+  const T* const vx = v + (size_t)a.bstride;
+  for (unsigned it = blockIdx.x * BLOCK + threadIdx.x; it < items; it += step) {
+    const unsigned c = PART ? it / nvec : 0u, p = (it - c * nvec) * VW;
+    const Coord cd = coords(a.G, (long long)p);                 // (p < L: the pixel's i, j)
+    const bool my = l21_member(cd.j, (int)a.G.n[1]);
+    bool mx[VW];
+#pragma unroll
+    for (int w = 0; w < VW; ++w) mx[w] = l21_member(cd.i + w, (int)a.G.n[0]);
+    const unsigned z0 = PART ? (unsigned)a.plan.z0((int)c) : 0u, z1 = PART ? (unsigned)a.plan.z1((int)c, (int)n3) : n3;
+    double ss[VW];
+#pragma unroll
+    for (int w = 0; w < VW; ++w) ss[w] = 0.0;
+    unsigned k = z0, off = z0 * L + p;
+    for (; k + L21J_BATCH <= z1; k += L21J_BATCH, off += L21J_BATCH * L) {
+      Vec<T, VW> y[L21J_BATCH], x[L21J_BATCH];
+#pragma unroll
+      for (int u = 0; u < L21J_BATCH; ++u) {
+        y[u] = ldv<T, VW>(v + off + u * L);
+        x[u] = ldv<T, VW>(vx + off + u * L);
+      }
+#pragma unroll
+      for (int u = 0; u < L21J_BATCH; ++u)
+#pragma unroll
+        for (int w = 0; w < VW; ++w) l21_joint_add<T>(ss[w], y[u].v[w], x[u].v[w], my, mx[w]);
+    }
+    for (; k < z1; ++k, off += L) {
+      const Vec<T, VW> y = ldv<T, VW>(v + off), x = ldv<T, VW>(vx + off);
+#pragma unroll
+      for (int w = 0; w < VW; ++w) l21_joint_add<T>(ss[w], y.v[w], x.v[w], my, mx[w]);
+    }
+    if constexpr (PART) {
+      double* const dst = part + (size_t)c * L + p;
+#pragma unroll
+      for (int w = 0; w < VW; ++w) dst[w] = ss[w];
+    } else {
+      Vec<T, VW> out;
+#pragma unroll
+      for (int w = 0; w < VW; ++w) out.v[w] = l21_norm_of<T>(ss[w]);
+      stv<T, VW>(g + p, out);
+    }
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_l21j_finish(unsigned L, int nchunk, const double* __restrict__ part, T* __restrict__ g) {
+  for (unsigned p = blockIdx.x * BLOCK + threadIdx.x; p < L; p += gridDim.x * BLOCK)
+    g[p] = l21_norm_of<T>(l21_joint_total(part, (long long)L, (long long)p, nchunk));
+}
+
+static void l21_joint_check_spec(const ExtSpec& sp) {
+  l21_check_spec(sp);
+  if (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0 || sp.mode != SIPX_MODE_WHOLE)
+    throw std::runtime_error(L21_JOINT_ROUTE);
+}
+// g (L entries) <- the group norms of v; part: nchunk L doubles when the plan chunks, not looked at otherwise
+template <typename T>
+static void l21_joint_norms(hipStream_t s, const ExtSpec& sp, const L21JointPlan& plan, const T* v, T* g, double* part) {
+  constexpr int W = l21_vec_width<T>();
+  L21JArgs a;
+  a.G = sp.G;
+  a.G.set_fast_div();
+  a.bstride = sp.bstride;
+  a.plan = plan;
+  const long long L = sp.G.st[2];
+  const bool wide = l21_wide(sp, v, g), chunks = plan.nchunk > 1;
+  const int grid = fit_grid(L / (wide ? W : 1) * plan.nchunk, NB);
+  {
+    ObsScope obs(KID_L21J_NORMS, s, (double)(2 * sp.G.N + L) * sizeof(T));
+    if (chunks && wide) hipLaunchKernelGGL((k_l21j_norms<T, W, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, part);
+    else if (chunks) hipLaunchKernelGGL((k_l21j_norms<T, 1, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, part);
+    else if (wide) hipLaunchKernelGGL((k_l21j_norms<T, W, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, part);
+    else hipLaunchKernelGGL((k_l21j_norms<T, 1, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, part);
+    SIPX_HIP(hipGetLastError());
+  }
+  if (chunks) {
+    ObsScope obs(KID_L21J_FINISH, s, (double)L * (plan.nchunk * sizeof(double) + sizeof(T)));
+    hipLaunchKernelGGL((k_l21j_finish<T>), dim3(fit_grid(L, NB)), dim3(BLOCK), 0, s, (unsigned)L, plan.nchunk, part, g);
+    SIPX_HIP(hipGetLastError());
+  }
+}
+template <typename T>
+static void l21_joint_scale(hipStream_t s, const ExtSpec& sp, T* v, const T* g, const ProjScalars<T>* ps, const T* theta) {
+  constexpr int W = l21_vec_width<T>();
+  const L21Args a = l21_args(sp);
+  const bool wide = l21_wide(sp, v, g);
+  const int grid = fit_grid(sp.G.N / (wide ? W : 1), NB);
+  const int* none = nullptr;
+  ObsScope obs(KID_L21J_SCALE, s, (double)(4 * sp.G.N + sp.G.st[2]) * sizeof(T));
+  if (wide) hipLaunchKernelGGL((k_l21_scale<T, 2, W, false, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
+  else hipLaunchKernelGGL((k_l21_scale<T, 2, 1, false, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
+  SIPX_HIP(hipGetLastError());
+}
+
+template <typename T>
+struct JointProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  L21JointPlan plan;
+  long long L = 0;
+  T* g = nullptr;                      // the group norms, L entries
+  double* part = nullptr;              // the chunk sums, nchunk L entries, when the plan chunks
+  double* tpart = nullptr;             // Float64: the partial sums of k_l21_theta_part
+  T* theta = nullptr;                  // Float64: the threshold k_l21_scale applies
+  SearchState<T> search;
+  void reset() override { search.reinit(stream); }
+  JointProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    l21_joint_check_spec(sp);
+    if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+    L = sp.G.st[2];
+    plan = l21_joint_plan(L, sp.G.n[2], (int)sizeof(T));
+    g = this->template alloc<T>(L);
+    if (plan.nchunk > 1) part = this->template alloc<double>((size_t)plan.nchunk * L);
+    if (sizeof(T) == 8) {
+      tpart = this->template alloc<double>(3 * L21_THETA_GRID);
+      theta = this->template alloc<T>(1);
+    }
+    search.build(this->mem, s, 0);
+  }
+  void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
+    ProjScalars<T>* ps = search.pick(feas);
+    l21_joint_norms<T>(stream, sp, plan, v, g, part);
+    K<T>::proj_scalars_arr(stream, L, g, PX_L1, T(0), (T)sp.pmax, ps, partials, maxpart, compact, L);
+    if constexpr (sizeof(T) == 8) {
+      const int grid = fit_grid(L, L21_THETA_GRID);
+      hipLaunchKernelGGL(k_l21_theta_part, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)L, g, ps, tpart);
+      hipLaunchKernelGGL(k_l21_theta_final, dim3(1), dim3(BLOCK), 0, stream, grid, (unsigned)L, (double)sp.pmax, tpart, ps, theta);
+      SIPX_HIP(hipGetLastError());
+    }
+    l21_joint_scale<T>(stream, sp, v, g, ps, theta);
+  }
+};
+
 template <typename T>
 ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
+  if (spec.kind == EXT_L21_JOINT) return new JointProj<T>(spec, stream);
   if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);
   if (spec.kind != EXT_L21) throw std::runtime_error("unknown external projector");
   return new GroupProj<T>(spec, stream);
@@ -371,6 +528,25 @@ void l21_observe(const ExtSpec& spec, const T* v, T* g, ProjScalars<T>* ps, doub
   hipLaunchKernelGGL((k_l21_pick<T>), dim3(1), dim3(64), 0, stream, ps, out);
   SIPX_HIP(hipGetLastError());
 }
+
+// out[0] (device) <- the sum of the L group norms of a materialised vector in the layout of an EXT_L21_JOINT spec: the z-march into g
+// (L entries; part: the chunk sums of l21_joint_plan, nchunk L doubles, when it chunks), then the first pass of a search with a new
+// state and an infinite radius -- the sum, and the rounding to T, of the projector's own decision
+template <typename T>
+void l21_joint_observe(const ExtSpec& spec, const T* v, T* g, double* part, ProjScalars<T>* ps, double* partials, T* maxpart, T* compact,
+                       T* out, hipStream_t stream) {
+  l21_joint_check_spec(spec);
+  const long long L = spec.G.st[2];
+  l21_joint_norms<T>(stream, spec, l21_joint_plan(L, spec.G.n[2], (int)sizeof(T)), v, g, part);
+  K<T>::ps_init(stream, ps, nullptr);
+  K<T>::proj_scalars_arr(stream, L, g, PX_L1, T(0), (T)INFINITY, ps, partials, maxpart, compact, L);
+  hipLaunchKernelGGL((k_l21_pick<T>), dim3(1), dim3(64), 0, stream, ps, out);
+  SIPX_HIP(hipGetLastError());
+}
+template void l21_joint_observe<float>(const ExtSpec&, const float*, float*, double*, ProjScalars<float>*, double*, float*, float*, float*,
+                                       hipStream_t);
+template void l21_joint_observe<double>(const ExtSpec&, const double*, double*, double*, ProjScalars<double>*, double*, double*, double*,
+                                        double*, hipStream_t);
 
 template ExtImpl<float>* make_group_family<float>(const ExtSpec&, hipStream_t);
 template ExtImpl<double>* make_group_family<double>(const ExtSpec&, hipStream_t);

@@ -1,5 +1,5 @@
 // Projectors that act on a materialised vector v (one block of the padded layout): library transforms
-// (hipFFT / rocSOLVER / rocBLAS / hipCUB sort) and the per-fiber / per-slice selections; see ext_proj.hip.  EXT_L21 and EXT_L21_SEG alone
+// (hipFFT / rocSOLVER / rocBLAS / hipCUB sort) and the per-fiber / per-slice selections; see ext_proj.hip.  EXT_L21, EXT_L21_SEG and EXT_L21_JOINT alone
 // act on the nblk blocks of the TV / TV_xy operator at once (ext_group.hip).
 #pragma once
 #include "sipx_common.h"
@@ -9,7 +9,12 @@ namespace sipx {
 enum { EXT_L1_DFT = 1, EXT_RANK = 2, EXT_NUCLEAR = 3, EXT_CARD_SEG = 4, EXT_HISTOGRAM = 5, EXT_SUBSPACE = 6, EXT_DFT_MASK = 7, EXT_DCT = 8, EXT_DWT = 9, EXT_CARD_DFT = 10,
        EXT_L1_SEG = 11, EXT_L2_SEG = 12, EXT_ANNULUS_SEG = 13 /* l1 / l2 / annulus per fiber or slice */,
        EXT_L21 = 14 /* the l2,1 ball across the blocks of the TV / TV_xy operator (l21.h) */,
-       EXT_L21_SEG = 15 /* the l2,1 ball of every z-slice across the blocks of TV_xy (l21_seg.h) */ };
+       EXT_L21_SEG = 15 /* the l2,1 ball of every z-slice across the blocks of TV_xy (l21_seg.h) */,
+       EXT_L21_JOINT = 16 /* the l2,1 ball whose groups span the blocks of TV_xy and the frames (l21_joint.h) */ };
+
+// The refusal of an EXT_L21_JOINT set off its operator or mode, worded once: set_config.h (sipx_add_set), the stand-alone calls of the
+// engine and the projector's own check throw this text (its cases: tests/test_l21_joint_cpu.py, tests/test_gpu_l21_joint.py)
+constexpr const char* L21_JOINT_ROUTE = "the joint l2,1 ball groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor";
 
 // What an ExtProj acts on: the valid extents `dims` (TD_n of the operator) inside the padded grid G (strides G.st),
 // split into segments by the application mode (whole array, fibers along `dir`, slices orthogonal to `dir`).
@@ -75,6 +80,13 @@ void l21_observe(const ExtSpec& spec, const T* v, T* g, ProjScalars<T>* ps, doub
 // (ext_group.hip, EXT_L21_SEG); g: N entries of scratch
 template <typename T>
 void l21_seg_observe(const ExtSpec& spec, const T* v, T* g, T* out, hipStream_t stream);
+
+// out[0] (device) <- the sum of the n1 n2 group norms of a materialised vector in the layout of an EXT_L21_JOINT spec, as the joint
+// projector's decision sums and rounds it (ext_group.hip); g: n1 n2 entries of scratch, part: nchunk n1 n2 doubles when l21_joint_plan
+// (l21_joint.h) chunks, ps / partials / maxpart / compact: those of a threshold search over n1 n2 entries
+template <typename T>
+void l21_joint_observe(const ExtSpec& spec, const T* v, T* g, double* part, ProjScalars<T>* ps, double* partials, T* maxpart, T* compact,
+                       T* out, hipStream_t stream);
 
 // sum (projected - original)^2 and sum original^2 into partial slots dst[0..NB), dst[NB..2NB)
 template <typename T>

@@ -199,6 +199,9 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
   const int mode = d->mode, dir = d->dir;
   if (mode != SIPX_MODE_WHOLE && mode != SIPX_MODE_FIBER && mode != SIPX_MODE_SLICE)
     throw std::runtime_error("unknown application mode");
+  // the joint l2,1 ball (l21_joint.h) is one set on one operator: its refusal names the way out before any general one
+  if (d->proj == SIPX_PROJ_L21_JOINT && (s.op != SIPX_OP_TV_XY || mode != SIPX_MODE_WHOLE || d->transform != SIPX_TRANSFORM_NONE))
+    throw std::runtime_error(L21_JOINT_ROUTE);
   if (mode != SIPX_MODE_WHOLE) {
     if (dir < 0 || dir >= c.ndim) throw std::runtime_error("application mode: direction out of range for this grid");
     // the one multi-block set with a mode of its own: the l2,1 ball per z-slice on TV_xy (l21_seg.h)
@@ -208,7 +211,7 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (s.nblk > 1 && !frames) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
   }
   auto ext = [&](int kind) {
-    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
+    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
     s.ext_kind = kind;
     s.spec.kind = kind;
     s.spec.ndim = c.ndim;
@@ -352,6 +355,12 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
           check_l1_radii(s.host_ub.data(), G.n[2]);
         }
       }
+      break;
+    case SIPX_PROJ_L21_JOINT:  // vectorial TV: one group per pixel across the blocks of TV_xy and all frames (op, mode, transform: above)
+      if (s.comp) throw std::runtime_error("the l2,1 ball takes no Minkowski component");
+      refuse_sharded(c, Sharded::L21);
+      if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+      ext(EXT_L21_JOINT);
       break;
     case SIPX_PROJ_RANK: ext(EXT_RANK); break;
     case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;

@@ -65,7 +65,8 @@ enum KernelId {
   KID_CDS_SPMV = 0, KID_CDS_DOT, KID_CDS_RESID, KID_CDS_FUSED, KID_SQ_SPMV, KID_SQ_DOT, KID_SQ_RESID, KID_CG_BEGIN, KID_CG_XR, KID_CG_P,
   KID_Q_UPDATE, KID_FIN_SUM, KID_RHS, KID_YL, KID_YL_MULTI, KID_ADJ_NORM, KID_LOG3, KID_PASS_FIRST, KID_PASS_LEAN, KID_PASS_PROBE,
   KID_PASS_COMPACT, KID_PASS_DIST, KID_PASS_STORE, KID_PASS_MULTI, KID_SLOT_SUMS, KID_DECIDE, KID_SAMPLE, KID_L1_SOLVE, KID_GATHER,
-  KID_PS_RESCALE, KID_CARD, KID_EXT, KID_BB_RULE, KID_OTHER, KID_MF_FWD, KID_MF_ADJ, KID_L21_NORMS, KID_L21_FRAMES, KID_L21_SCALE, KID_COUNT
+  KID_PS_RESCALE, KID_CARD, KID_EXT, KID_BB_RULE, KID_OTHER, KID_MF_FWD, KID_MF_ADJ, KID_L21_NORMS, KID_L21_FRAMES, KID_L21_SCALE,
+  KID_L21J_NORMS, KID_L21J_FINISH, KID_L21J_SCALE, KID_COUNT
 };
 inline const char* kernel_name(int k) {
   static const char* const names[KID_COUNT] = {
@@ -73,7 +74,8 @@ inline const char* kernel_name(int k) {
       "k_cg_update_xr", "k_cg_update_p", "k_q_update", "k_fin_sum", "k_rhs", "k_yl", "k_yl_multi", "k_adj_norm", "k_log3",
       "k_pass<M_FIRST>", "k_pass<M_LEAN>", "k_pass<M_PROBE>", "k_pass<M_COMPACT>", "k_pass<M_DIST>", "k_pass<M_STORE>", "k_pass_multi",
       "k_slot_sums", "k_decide", "k_sample", "k_l1_solve", "k_gather_pack/unpack", "k_ps_rescale", "k_card_*", "ext_proj (library-backed)",
-      "k_bb_rule", "other", "k_mf_fwd", "k_mf_adj", "k_l21_norms", "k_l21_frames", "k_l21_scale"};      // (the last three: inside ext_proj)
+      "k_bb_rule", "other", "k_mf_fwd", "k_mf_adj", "k_l21_norms", "k_l21_frames", "k_l21_scale",
+      "k_l21j_norms", "k_l21j_finish", "k_l21j_scale"};      // (the last six: inside ext_proj)
   return (k >= 0 && k < KID_COUNT) ? names[k] : "?";
 }
 struct LaunchObserver {

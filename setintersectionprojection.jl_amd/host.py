@@ -39,12 +39,13 @@ EXPORTED_SYMBOLS = [
     "sipx_finalize_dev", "sipx_reset_dev", "sipx_download_dev", "sipx_set_caller_stream", "sipx_io_bytes",
     "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev", "sipx_segment_norms", "sipx_segment_norms_dev",
     "sipx_l21_norm", "sipx_l21_norm_dev", "sipx_l21_norms", "sipx_l21_norms_dev",
+    "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
-        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14}
+        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -52,6 +53,8 @@ L21_NEEDS_TV = "the l2,1 ball acts on the range of the TV operator: TD_OP must b
 L21_WHOLE_ONLY = "the l2,1 ball applies to the whole array (mode matrix/tensor)"
 # TV_xy = vcat(D_y, D_x), the in-plane gradient of a 3-D grid (include/sipx.h, SIPX_OP_TV_XY): the engine's own, with its refusals
 L21_FRAMES_Z = "the l2,1 ball on TV_xy: frames run along z -- the mode must be (slice, z), or tensor for the whole array"
+# the joint l2,1 ball (csrc/l21_joint.h): one group per pixel across the frames of TV_xy; the engine's refusal, word for word
+L21_JOINT_NEEDS_TV_XY = "the joint l2,1 ball groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor"
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
 TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
 TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
@@ -361,6 +364,21 @@ class Projector:
         self.transform = 0
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
         self.op = None               # the operator a stand-alone call of the projector acts behind (l21: the TV range), None: the identity
+        if st == "l21_joint":
+            # joint (vectorial) total variation: one group per pixel across the frames of TV_xy (csrc/l21_joint.h); max is the radius
+            cust = constraint.custom_TD_OP[0]
+            if constraint.TD_OP != "TV_xy" or not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+                raise SipxError(L21_JOINT_NEEDS_TV_XY)
+            if len(n) != 3:
+                raise SipxError(TV_XY_NEEDS_3D)
+            if self.mode:
+                raise SipxError(L21_JOINT_NEEDS_TV_XY)
+            if np.ndim(constraint.max) != 0:
+                raise SipxError("the joint l2,1 ball takes one radius (constraint.max a scalar)")
+            if not float(constraint.max) > 0:
+                raise SipxError("Radius of L1 ball is negative")
+            self.kind, self.pmax, self.op = "l21_joint", float(constraint.max), "TV_xy"
+            return
         if st == "l21":
             # isotropic total variation: the l2,1 ball on the range of the TV operator (csrc/l21.h); max is the radius
             cust = constraint.custom_TD_OP[0]
@@ -529,6 +547,8 @@ class Projector:
         n = list(op.n)
         if self.kind == "l21" and (op.kind != "TV_xy" if self.op == "TV_xy" else op.kind not in TV_OPERATORS):
             raise SipxError(L21_NEEDS_TV)
+        if self.kind == "l21_joint" and op.kind != "TV_xy":
+            raise SipxError(L21_JOINT_NEEDS_TV_XY)
         if op.kind == "custom" and (self.mode or self.transform or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank",
                                                                                      "nuclear", "histogram", "subspace")):
             raise SipxError("custom sparse operators take the whole-array projectors only")
@@ -589,8 +609,9 @@ class Projector:
         if v.dtype.type != self.TF or not v.flags.c_contiguous:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
-                                                                              "subspace", "l21")
-        if self.kind == "l21":       # the M-vector of the TV range in the reference's row order, on the grid
+                                                                              "subspace", "l21", "l21_joint")
+        l21 = self.kind in ("l21", "l21_joint")
+        if l21:                      # the M-vector of the TV range in the reference's row order, on the grid
             op = TDOperator(self.op, self.comp_grid, self.TF)
             rows = op.shape[0]
             if v.shape != (rows,):
@@ -598,7 +619,7 @@ class Projector:
             self.check_rows(op)
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
         try:
-            if self.kind == "l21":
+            if l21:
                 d = self.desc(self.op, False)
                 _chk(lib().sipx_project(ctx.h, C.byref(d), _ptr(v), C.c_int64(len(v))))
                 return v
@@ -663,7 +684,10 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
     error stays.
 
     ("l21", "TV") in matrix / tensor mode -- isotropic total variation, the l2,1 ball of radius max on the TV range (csrc/l21.h) --
-    is the engine's own too and needs no keyword: the reference has no error to preserve there."""
+    is the engine's own too and needs no keyword: the reference has no error to preserve there.  So are ("l21", "TV_xy") on the
+    in-plane gradient of a 3-D grid -- the whole array or per z-slice (csrc/l21_seg.h) -- and ("l21_joint", "TV_xy") in tensor mode,
+    the ball whose groups span the frames: one budget on the sum over pixels of the l2 norm of all in-plane differences at that
+    pixel in all frames (vectorial total variation, csrc/l21_joint.h)."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -679,7 +703,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.min, c.max = np.asarray(c.min, TF), np.asarray(c.max, TF)
         if c.set_type == "l21" and np.ndim(c.max) == 1:      # one radius per frame (TV_xy, ("slice", "z"))
             c.max = np.asarray(c.max, TF)
-        if c.set_type == "l21":
+        if c.set_type in ("l21", "l21_joint"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -1875,6 +1899,44 @@ def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None):
     finally:
         ctx.close()
     return out if (on_dev or mode) else out[0]
+
+
+def l21_joint_norm(x, comp_grid):
+    """The joint (vectorial) total variation of the frames of x on a 3-D grid: the sum over the pixels (i, j) of the l2 norm of all
+    in-plane differences that start at that pixel in any frame, one number of the working precision (that of x).  Computed by the
+    z-march and the first-pass sum of the ("l21_joint", "TV_xy") projector (sipx_l21_joint_norm): used as the radius it leaves TV_xy x
+    unwritten.  x: a numpy vector (a numpy scalar comes back) or a 1-D torch tensor on a GPU (a tensor of one entry there; nothing
+    crosses PCIe, the call orders itself against torch's current stream)."""
+    on_dev = _is_tensor(x)
+    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("l21_joint_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    n, _ = _grid(comp_grid)
+    N = int(np.prod(n))
+    if len(n) != 3:
+        raise SipxError(TV_XY_NEEDS_3D)
+    if on_dev:
+        import torch
+        _check_tensor("x", x, TF, N, None)
+        _check_one_hip_runtime()
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        out = torch.empty(1, dtype=x.dtype, device=torch.device("cuda", device))
+        xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
+        fn = lib().sipx_l21_joint_norm_dev
+    else:
+        x = _check_array("x", x, TF, N)
+        device = None
+        out = np.empty(1, TF)
+        xp, op_ = _ptr(x), _ptr(out)
+        fn = lib().sipx_l21_joint_norm
+    ctx = Context(comp_grid, TF, device)
+    try:
+        if on_dev:
+            ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        _chk(fn(ctx.h, xp, op_))
+    finally:
+        ctx.close()
+    return out if on_dev else out[0]
 
 
 def _dwt_check_grid(n):
