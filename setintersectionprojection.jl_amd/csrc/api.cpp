@@ -139,22 +139,22 @@ int sipx_segment_norms_dev(sipx_ctx* c, int op, int mode, int dir, int norm, con
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->segment_norms(op, mode, dir, norm, x, out, nseg, true))
 }
 int sipx_l21_norm(sipx_ctx* c, const void* x, void* out) {
-  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norm(x, out, false))
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21, SIPX_OP_TV, SIPX_MODE_WHOLE, 0, x, out, nullptr, false, false))
 }
 int sipx_l21_norm_dev(sipx_ctx* c, const void* x, void* out) {
-  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norm(x, out, true))
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21, SIPX_OP_TV, SIPX_MODE_WHOLE, 0, x, out, nullptr, true, false))
 }
 int sipx_l21_norms(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
-  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(op, mode, dir, x, out, nseg, false))
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21, op, mode, dir, x, out, nseg, false, true))
 }
 int sipx_l21_norms_dev(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
-  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(op, mode, dir, x, out, nseg, true))
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21, op, mode, dir, x, out, nseg, true, true))
 }
 int sipx_l21_joint_norm(sipx_ctx* c, const void* x, void* out) {
-  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_joint_norm(x, out, false))
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21_JOINT, SIPX_OP_TV_XY, SIPX_MODE_WHOLE, 0, x, out, nullptr, false, false))
 }
 int sipx_l21_joint_norm_dev(sipx_ctx* c, const void* x, void* out) {
-  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_joint_norm(x, out, true))
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21_JOINT, SIPX_OP_TV_XY, SIPX_MODE_WHOLE, 0, x, out, nullptr, true, false))
 }
 int sipx_get_Q(sipx_ctx* c, void* Q, int64_t* offsets, int* d) { SIPX_TRY(c->e->get_Q(Q, offsets, d)) }
 int sipx_q_terms(sipx_ctx* c, int* bands, int* matrix_free) { SIPX_TRY(c->e->q_terms(bands, matrix_free)) }

@@ -7,7 +7,6 @@
 #include "dist_dft.h"
 #include "ext_proj.h"
 #include "host_prefault.h"
-#include "l21_joint.h"
 #include "set_config.h"
 #include "solve_rules.h"
 #include "sparse_granules.h"
@@ -3326,14 +3325,12 @@ class Engine : public EngineBase {
     }
   }
 
-  // sipx_l21_norm(_dev): ||TV x||_2,1 by the group-norm kernel of the projector and the first pass of its search (ext_group.hip)
-  void l21_norm(const void* x, void* out, bool on_device) override {
-    if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed");
-    l21_norms(SIPX_OP_TV, SIPX_MODE_WHOLE, 0, x, out, nullptr, on_device);
-  }
-  // sipx_l21_norms(_dev): the same behind TV or TV_xy, and per z-slice of TV_xy: the n3 sums the per-frame projector compares with
-  // its radii (k_l21_frames, pass 1)
-  void l21_norms(int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device) override {
+  // sipx_l21_norm(s)(_dev), sipx_l21_joint_norm(_dev): what the (proj, op, mode) set compares with its radius on A x -- ||TV x||_2,1 or
+  // its TV_xy form, the n3 per-frame sums of TV_xy with (slice, z), the sum over the pixels of the joint set -- by the observe() of a
+  // throw-away projector of that set (ext_group.hip): the launches and the sums of its project()
+  void l21_norms(int proj, int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device, bool query) override {
+    auto need_x_out = [&] { if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed"); };
+    if (proj == SIPX_PROJ_L21 && !query) need_x_out();    // (sipx_l21_norm refuses a null pointer before the context is looked at)
     SIPX_HIP(hipSetDevice(device_));
     if (op != SIPX_OP_TV && op != SIPX_OP_TV_XY)
       throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
@@ -3342,55 +3339,24 @@ class Engine : public EngineBase {
     configure_op(ctx, s, op);
     if (op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
     sipx_set_desc d{};
-    d.op = op; d.proj = SIPX_PROJ_L21; d.mode = mode; d.dir = dir; d.pmax = 1.0;
+    d.op = op; d.proj = proj; d.mode = mode; d.dir = dir; d.pmax = 1.0;
     configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the set
-    const bool frames = s.ext_kind == EXT_L21_SEG;
-    const long long nout = frames ? G_.n[2] : 1;
+    const long long nout = s.ext_kind == EXT_L21_SEG ? G_.n[2] : 1;
     if (nseg) *nseg = nout;
-    if (!x && !out) return;                    // (a query of the length)
-    if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed");
+    if (query && !x && !out) return;           // (sipx_l21_norms: a query of the length)
+    need_x_out();
     DeviceMemory tmp;
     const OpScratch w = forward_scratch(tmp, s, on_device);
-    T* g = tmp.alloc<T>(G_.N);
-    const SearchScratch q(tmp, G_.N, true);
+    const SearchScratch q(tmp, s.ext_kind == EXT_L21_JOINT ? G_.st[2] : G_.N, false);
     T* dout = on_device ? (T*)out : tmp.alloc<T>(nout);
+    ExtProj<T> ext(s.spec, stream_);
     const T* dv = queue_forward(w, s, x, on_device);
     {
       ObserverGuard og(observer());
       ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 1) * G_.N * sizeof(T));
-      if (frames) l21_seg_observe<T>(s.spec, dv, g, dout, stream_);
-      else l21_observe<T>(s.spec, dv, g, q.ps, q.part, q.mp, q.dc, dout, stream_);
+      ext.observe(dv, dout, q.part, q.mp, q.dc);
     }
     finish_call(on_device, out, dout, nout);
-  }
-
-  // sipx_l21_joint_norm(_dev): the sum of the n1 n2 group norms of TV_xy x, the groups spanning the frames, by the z-march of the joint
-  // projector and the first pass of its search (ext_group.hip)
-  void l21_joint_norm(const void* x, void* out, bool on_device) override {
-    SIPX_HIP(hipSetDevice(device_));
-    const ConfigCtx ctx = config_ctx();
-    SetConfig<T> s;
-    configure_op(ctx, s, SIPX_OP_TV_XY);
-    refuse_sharded(ctx, Sharded::TV_XY);
-    sipx_set_desc d{};
-    d.op = SIPX_OP_TV_XY; d.proj = SIPX_PROJ_L21_JOINT; d.mode = SIPX_MODE_WHOLE; d.pmax = 1.0;
-    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the set
-    if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed");
-    const long long L = G_.st[2];
-    const L21JointPlan plan = l21_joint_plan(L, G_.n[2], (int)sizeof(T));
-    DeviceMemory tmp;
-    const OpScratch w = forward_scratch(tmp, s, on_device);
-    T* g = tmp.alloc<T>(L);
-    double* part = plan.nchunk > 1 ? tmp.alloc<double>((size_t)plan.nchunk * L) : nullptr;
-    const SearchScratch q(tmp, L, true);
-    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
-    const T* dv = queue_forward(w, s, x, on_device);
-    {
-      ObserverGuard og(observer());
-      ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 1) * G_.N * sizeof(T));
-      l21_joint_observe<T>(s.spec, dv, g, part, q.ps, q.part, q.mp, q.dc, dout, stream_);
-    }
-    finish_call(on_device, out, dout, 1);
   }
 
   void project(const sipx_set_desc* d, void* v, int64_t len) override {

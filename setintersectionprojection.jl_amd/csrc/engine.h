@@ -49,9 +49,8 @@ struct EngineBase {
   virtual void apply_op(int op, const void* x, void* s, bool adjoint) = 0;
   virtual void project(const sipx_set_desc* d, void* v, int64_t len) = 0;
   virtual void segment_norms(int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg, bool on_device) = 0;
-  virtual void l21_norm(const void* x, void* out, bool on_device) = 0;
-  virtual void l21_norms(int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device) = 0;
-  virtual void l21_joint_norm(const void* x, void* out, bool on_device) = 0;
+  // the six sipx_l21_*norm* calls: proj SIPX_PROJ_L21 or SIPX_PROJ_L21_JOINT; query: x and out both null ask for *nseg alone
+  virtual void l21_norms(int proj, int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device, bool query) = 0;
   virtual void get_Q(void* Q, int64_t* offsets, int* d) = 0;
   virtual void apply_Q(const void* x, void* y) = 0;
   virtual void q_terms(int* bands, int* matrix_free) = 0;

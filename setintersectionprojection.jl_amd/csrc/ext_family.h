@@ -2,7 +2,8 @@
 //   ext_transform.hip  DFT mask, l1 and cardinality behind the DFT, DCT, DWT
 //   ext_rank.hip       slice / matrix rank, nuclear norm
 //   ext_segments.hip   cardinality, l1, l2 and annulus per fiber / slice (seg_norm.h), relaxed histogram, subspace
-//   ext_group.hip      the l2,1 ball across the blocks of the TV / TV_xy operator (l21.h), per z-slice (l21_seg.h), across the frames (l21_joint.h)
+//   ext_group.hip      the l2,1 ball across the blocks of the TV / TV_xy operator: BallProj on the whole array (l21.h) or with groups
+//                      across the frames (l21_joint.h), FrameProj per z-slice (l21_seg.h)
 // -- and what more than one family uses.
 #pragma once
 #define ROCBLAS_BETA_FEATURES_API 1
@@ -37,6 +38,8 @@ struct ExtImpl {
   // sipx_set_data: new lb / ub (nullptr keeps one), host or device memory
   virtual void set_data(const T*, const T*, bool) { throw std::runtime_error("this projector holds no replaceable vectors (build a new context)"); }
   virtual void route_counts(long long out[4]) const { out[0] = out[1] = out[2] = out[3] = 0; }
+  // out (device) <- the number(s) project(v, ...) would compare with the radius; v is not written (ext_proj.h)
+  virtual void observe(const T*, T*, double*, T*, T*) { throw std::runtime_error("this projector has no observer"); }
   template <typename Q>
   Q* alloc(size_t count) { return mem.template alloc<Q>(count ? count : 1, Mem::NoFill); }
 };

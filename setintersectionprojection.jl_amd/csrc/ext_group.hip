@@ -1,6 +1,6 @@
 // Group norms across the blocks of a multi-block operator: the l2,1 ball on the range of the TV operator (isotropic total
-// variation, EXT_L21).  The rule is written down in l21.h; here are the two streaming kernels and the projector
-//     k_l21_norms     g[p] <- the l2 norm of the group of grid point p              reads nblk N words, writes N
+// variation, EXT_L21).  The rule is written down in l21.h; here are the two streaming kernels and the projector (BallProj)
+//     k_l21_norms    g[p] <- the l2 norm of the group of grid point p              reads nblk N words, writes N
 //     the engine's l1 threshold search on the array g (K<T>::proj_scalars_arr)     its passes over N words
 //     k_l21_scale     v_q[p] <- v_q[p] * f_p unless the search found v inside     reads (nblk + 1) N words, writes nblk N
 // -- (2 nblk + 2) N words plus the search per projection outside the set.  The reference package has no such projector.
@@ -10,8 +10,10 @@
 // Both kernels are grid-stride over the N grid points with 32-bit index arithmetic (N < 2^31 is checked when the projector is
 // built), use no LDS, and take VW points per thread: 16 bytes of every array when n1 % 4 == 0 (then N and every block base
 // are 16-byte aligned and the VW points lie on one grid line), one point otherwise.  g lives in the projector's own memory.
-// Further down: the ball of every z-slice of TV_xy (EXT_L21_SEG, l21_seg.h) and the ball whose groups span the frames (EXT_L21_JOINT,
-// l21_joint.h), each with the kernels it adds.
+// The ball whose groups span the frames (EXT_L21_JOINT, l21_joint.h) is the same projector with norms kernels of its own and L = n1 n2
+// entries of g; the ball of every z-slice of TV_xy (EXT_L21_SEG, l21_seg.h, FrameProj) has k_l21_frames in place of the search.
+// Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the two projectors.
+// A projector's observe() runs the norms launch and the first sum of its own project(): what it reports is what project() decides on.
 #include "ext_family.h"
 #include "l21.h"
 #include "l21_joint.h"
@@ -118,7 +120,7 @@ constexpr int L21_THETA_GRID = 512;
 __global__ __launch_bounds__(BLOCK) void k_l21_theta_part(unsigned N, const double* __restrict__ g, const ProjScalars<double>* __restrict__ ps,
                                                           double* __restrict__ part) {
   if (!ps->need) return;
-  __shared__ double sh[BLOCK], sl[BLOCK], sc[BLOCK];
+  __shared__ double red[3 * BLOCK];
   const double th = ps->theta;
   L21Sum acc{0.0, 0.0};
   double cnt = 0.0;
@@ -126,21 +128,12 @@ __global__ __launch_bounds__(BLOCK) void k_l21_theta_part(unsigned N, const doub
     const double a = g[p];
     if (a > th) { l21_sum_add(acc, a); cnt += 1.0; }
   }
-  sh[threadIdx.x] = acc.hi; sl[threadIdx.x] = acc.lo; sc[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int w = BLOCK / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      L21Sum a{sh[threadIdx.x], sl[threadIdx.x]};
-      l21_sum_merge(a, L21Sum{sh[threadIdx.x + w], sl[threadIdx.x + w]});
-      sh[threadIdx.x] = a.hi; sl[threadIdx.x] = a.lo; sc[threadIdx.x] += sc[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { part[3 * blockIdx.x] = sh[0]; part[3 * blockIdx.x + 1] = sl[0]; part[3 * blockIdx.x + 2] = sc[0]; }
+  l21_tree_merge<BLOCK>(acc, cnt, red);
+  if (threadIdx.x == 0) { part[3 * blockIdx.x] = acc.hi; part[3 * blockIdx.x + 1] = acc.lo; part[3 * blockIdx.x + 2] = cnt; }
 }
 __global__ __launch_bounds__(BLOCK) void k_l21_theta_final(int nparts, unsigned N, double tau, const double* __restrict__ part,
                                                            const ProjScalars<double>* __restrict__ ps, double* __restrict__ theta) {
-  __shared__ double sh[BLOCK], sl[BLOCK], sc[BLOCK];
+  __shared__ double red[3 * BLOCK];
   if (!ps->need) {
     if (threadIdx.x == 0) theta[0] = ps->theta;
     return;
@@ -151,17 +144,8 @@ __global__ __launch_bounds__(BLOCK) void k_l21_theta_final(int nparts, unsigned 
     l21_sum_merge(acc, L21Sum{part[3 * b], part[3 * b + 1]});
     cnt += part[3 * b + 2];
   }
-  sh[threadIdx.x] = acc.hi; sl[threadIdx.x] = acc.lo; sc[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int w = BLOCK / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      L21Sum a{sh[threadIdx.x], sl[threadIdx.x]};
-      l21_sum_merge(a, L21Sum{sh[threadIdx.x + w], sl[threadIdx.x + w]});
-      sh[threadIdx.x] = a.hi; sl[threadIdx.x] = a.lo; sc[threadIdx.x] += sc[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) theta[0] = l21_theta_refined(L21Sum{sh[0], sl[0]}, sc[0], tau, (double)N, ps->theta);
+  l21_tree_merge<BLOCK>(acc, cnt, red);
+  if (threadIdx.x == 0) theta[0] = l21_theta_refined(acc, cnt, tau, (double)N, ps->theta);
 }
 
 // out[0] <- (T) ||g||_1 as the search's first pass summed it: the number its decision compares with the radius
@@ -169,180 +153,6 @@ template <typename T>
 __global__ void k_l21_pick(const ProjScalars<T>* __restrict__ ps, T* __restrict__ out) {
   if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = (T)ps->asum;
 }
-
-static void l21_check_spec(const ExtSpec& sp) {
-  if (sp.nblk != 2 && sp.nblk != 3) throw std::runtime_error("the l2,1 ball needs the 2 or 3 blocks of the TV or TV_xy operator");
-  if (sp.nblk > sp.ndim) throw std::runtime_error("the l2,1 ball: more blocks than grid dimensions");
-  for (int q = 0; q < sp.nblk; ++q)
-    for (int r = 0; r < q; ++r)
-      if (sp.bdir[q] == sp.bdir[r]) throw std::runtime_error("the l2,1 ball: two blocks along one direction");
-  if (sp.G.N >= (1ll << 31)) throw std::runtime_error("the l2,1 ball: the grid needs fewer than 2^31 points");
-  if (sp.bstride < sp.G.N) throw std::runtime_error("the l2,1 ball: the blocks overlap");
-  for (int q = 0; q < sp.nblk; ++q)
-    if (sp.bdir[q] < 0 || sp.bdir[q] >= sp.ndim) throw std::runtime_error("the l2,1 ball: block direction out of range");
-}
-static L21Args l21_args(const ExtSpec& sp) {
-  L21Args a;
-  a.G = sp.G;
-  a.G.set_fast_div();
-  for (int q = 0; q < 3; ++q) a.dir[q] = q < sp.nblk ? sp.bdir[q] : 0;
-  a.bstride = sp.bstride;
-  return a;
-}
-// 16-byte accesses: n1 % 4 == 0 (N and every block base then are multiples of 4 entries) and 16-byte aligned arrays
-template <typename T>
-static bool l21_wide(const ExtSpec& sp, const T* v, const T* g) {
-  return sp.G.n[0] % 4 == 0 && sp.bstride % 4 == 0 && aligned16(v, g);
-}
-template <typename T>
-static void l21_norms(hipStream_t s, const ExtSpec& sp, const T* v, T* g) {
-  constexpr int W = l21_vec_width<T>();
-  const L21Args a = l21_args(sp);
-  const bool wide = l21_wide(sp, v, g);
-  const int grid = fit_grid(sp.G.N / (wide ? W : 1), NB);
-  ObsScope obs(KID_L21_NORMS, s, (double)(sp.nblk + 1) * sp.G.N * sizeof(T));
-  if (sp.nblk == 2 && wide) hipLaunchKernelGGL((k_l21_norms<T, 2, W>), dim3(grid), dim3(BLOCK), 0, s, a, v, g);
-  else if (sp.nblk == 2) hipLaunchKernelGGL((k_l21_norms<T, 2, 1>), dim3(grid), dim3(BLOCK), 0, s, a, v, g);
-  else if (wide) hipLaunchKernelGGL((k_l21_norms<T, 3, W>), dim3(grid), dim3(BLOCK), 0, s, a, v, g);
-  else hipLaunchKernelGGL((k_l21_norms<T, 3, 1>), dim3(grid), dim3(BLOCK), 0, s, a, v, g);
-  SIPX_HIP(hipGetLastError());
-}
-template <typename T>
-static void l21_scale(hipStream_t s, const ExtSpec& sp, T* v, const T* g, const ProjScalars<T>* ps, const T* theta) {
-  constexpr int W = l21_vec_width<T>();
-  const L21Args a = l21_args(sp);
-  const bool wide = l21_wide(sp, v, g);
-  const int grid = fit_grid(sp.G.N / (wide ? W : 1), NB);
-  const int* none = nullptr;
-  ObsScope obs(KID_L21_SCALE, s, (double)(2 * sp.nblk + 1) * sp.G.N * sizeof(T));
-  if (sp.nblk == 2 && wide) hipLaunchKernelGGL((k_l21_scale<T, 2, W, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
-  else if (sp.nblk == 2) hipLaunchKernelGGL((k_l21_scale<T, 2, 1, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
-  else if (wide) hipLaunchKernelGGL((k_l21_scale<T, 3, W, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
-  else hipLaunchKernelGGL((k_l21_scale<T, 3, 1, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
-  SIPX_HIP(hipGetLastError());
-}
-// the per-frame form: two blocks on a 3-D grid (l21_seg_check_spec)
-template <typename T>
-static void l21_scale_frames(hipStream_t s, const ExtSpec& sp, T* v, const T* g, const T* theta, const int* need) {
-  constexpr int W = l21_vec_width<T>();
-  const L21Args a = l21_args(sp);
-  const bool wide = l21_wide(sp, v, g);
-  const int grid = fit_grid(sp.G.N / (wide ? W : 1), NB);
-  const ProjScalars<T>* none = nullptr;
-  ObsScope obs(KID_L21_SCALE, s, (double)(2 * sp.nblk + 1) * sp.G.N * sizeof(T));
-  if (wide) hipLaunchKernelGGL((k_l21_scale<T, 2, W, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, none, theta, need);
-  else hipLaunchKernelGGL((k_l21_scale<T, 2, 1, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, none, theta, need);
-  SIPX_HIP(hipGetLastError());
-}
-
-template <typename T>
-struct GroupProj : ExtImpl<T> {
-  using ExtImpl<T>::sp;
-  using ExtImpl<T>::stream;
-  T* g = nullptr;                      // the group norms, N entries
-  double* tpart = nullptr;             // Float64: the partial sums of k_l21_theta_part
-  T* theta = nullptr;                  // Float64: the threshold k_l21_scale applies
-  SearchState<T> search;
-  void reset() override { search.reinit(stream); }
-  GroupProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
-    l21_check_spec(sp);
-    if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-    g = this->template alloc<T>(sp.G.N);
-    if (sizeof(T) == 8) {
-      tpart = this->template alloc<double>(3 * L21_THETA_GRID);
-      theta = this->template alloc<T>(1);
-    }
-    search.build(this->mem, s, 0);
-  }
-  void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
-    const long long N = sp.G.N;
-    ProjScalars<T>* ps = search.pick(feas);
-    l21_norms<T>(stream, sp, v, g);
-    K<T>::proj_scalars_arr(stream, N, g, PX_L1, T(0), (T)sp.pmax, ps, partials, maxpart, compact, N);
-    if constexpr (sizeof(T) == 8) {
-      const int grid = fit_grid(N, L21_THETA_GRID);
-      hipLaunchKernelGGL(k_l21_theta_part, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)N, g, ps, tpart);
-      hipLaunchKernelGGL(k_l21_theta_final, dim3(1), dim3(BLOCK), 0, stream, grid, (unsigned)N, (double)sp.pmax, tpart, ps, theta);
-      SIPX_HIP(hipGetLastError());
-    }
-    l21_scale<T>(stream, sp, v, g, ps, theta);
-  }
-};
-
-// ---- EXT_L21_SEG: the l2,1 ball of every z-slice on the range of TV_xy (l21_seg.h) -------------------------------------------------------
-//     k_l21_norms     as above, two blocks on the 3-D grid                                    reads 2 N words, writes N
-//     k_l21_frames    one workgroup per frame on g alone: asum, the decision, Michelot's passes  reads N (LDS) or passes * N
-//     k_l21_scale     the per-frame form; frames inside their ball are skipped without a store  reads up to 3 N, writes up to 2 N
-static void l21_seg_check_spec(const ExtSpec& sp) {
-  l21_check_spec(sp);
-  if (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0)
-    throw std::runtime_error("the l2,1 ball per frame needs the blocks (D_y, D_x) of the TV_xy operator on a 3-D grid");
-  if (sp.mode != SIPX_MODE_SLICE || sp.dir != 2) throw std::runtime_error("the l2,1 ball on TV_xy: frames run along z, the mode is (slice, z)");
-}
-template <typename T, bool OBSERVE>
-static void l21_frames(hipStream_t s, const ExtSpec& sp, const T* g, T tau, const T* rmax, T* theta, int* need, T* asum, int* passes) {
-  const long long L = sp.G.n[0] * sp.G.n[1], nf = sp.G.n[2];
-  L21SegPlan plan = l21_seg_plan(L, nf, (int)sizeof(T));
-  if (OBSERVE) { plan.lds = 0; plan.lds_bytes = 0; }
-  ObsScope obs(KID_L21_FRAMES, s, (double)sp.G.N * sizeof(T));
-  if (rmax)
-    hipLaunchKernelGGL((k_l21_frames<T, true, OBSERVE>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, s, plan, (unsigned)L, (unsigned)nf, g, tau,
-                       rmax, theta, need, asum, passes);
-  else
-    hipLaunchKernelGGL((k_l21_frames<T, false, OBSERVE>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, s, plan, (unsigned)L, (unsigned)nf, g, tau,
-                       rmax, theta, need, asum, passes);
-  SIPX_HIP(hipGetLastError());
-}
-
-// Nothing is kept between calls: the call of the feasibility estimate and the one of the y update are independent, reset() has
-// nothing to forget.  Built with ExtSpec::ub every frame has its own radius (rmax, n3 entries), sipx_set_data replaces them.
-template <typename T>
-struct FrameProj : ExtImpl<T> {
-  using ExtImpl<T>::sp;
-  using ExtImpl<T>::stream;
-  T *g = nullptr, *theta = nullptr, *asum = nullptr, *rmax = nullptr;
-  int *need = nullptr, *passes = nullptr;
-  long long nf = 0;
-  FrameProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
-    l21_seg_check_spec(sp);
-    nf = sp.G.n[2];
-    if (!sp.ub && !((T)sp.pmax > T(0))) throw std::runtime_error("Radius of L1 ball is negative");
-    if (sp.ub) {
-      const T* h = (const T*)sp.ub;
-      for (long long k = 0; k < nf; ++k)
-        if (!(h[k] > T(0))) throw std::runtime_error("Radius of L1 ball is negative");
-    }
-    g = this->template alloc<T>(sp.G.N);
-    theta = this->template alloc<T>(nf);
-    asum = this->template alloc<T>(nf);
-    need = this->template alloc<int>(2 * nf);
-    passes = need + nf;
-    SIPX_HIP(hipMemset(need, 0, sizeof(int) * 2 * (size_t)nf));      // (route_counts may be asked before the first projection)
-    if (sp.ub) {
-      rmax = this->template alloc<T>(nf);
-      SIPX_HIP(hipMemcpy(rmax, sp.ub, sizeof(T) * (size_t)nf, hipMemcpyHostToDevice));
-    }
-  }
-  void project(T* v, bool, double*, T*, T*) override {
-    l21_norms<T>(stream, sp, v, g);
-    l21_frames<T, false>(stream, sp, g, (T)sp.pmax, rmax, theta, need, asum, passes);
-    l21_scale_frames<T>(stream, sp, v, g, theta, need);
-  }
-  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
-    if (!rmax) ExtImpl<T>::set_data(new_lb, new_ub, on_device);
-    if (new_lb) throw std::runtime_error("only the annulus has inner radii: pass the radii of this set as ub");
-    if (new_ub)
-      SIPX_HIP(hipMemcpyAsync(rmax, new_ub, sizeof(T) * (size_t)nf, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-  }
-  // the Michelot passes of the last call, per frame (tools/l21_frames_bench.py)
-  void route_counts(long long out[4]) const override {
-    std::vector<int> h((size_t)nf);
-    SIPX_HIP(hipStreamSynchronize(stream));
-    SIPX_HIP(hipMemcpy(h.data(), passes, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
-    out[0] = out[1] = out[2] = 0; out[3] = nf;
-    for (int x : h) { out[0] += x; out[1] = std::max<long long>(out[1], x); }
-  }
-};
 
 // ---- EXT_L21_JOINT: the l2,1 ball whose groups span the frames, on the range of TV_xy (l21_joint.h) ---------------------------------------
 //     k_l21j_norms    the z-march: g[pixel] or the chunk sums part[c L + pixel]               reads 2 N words, writes L (or nchunk L doubles)
@@ -413,145 +223,233 @@ __global__ __launch_bounds__(BLOCK) void k_l21j_finish(unsigned L, int nchunk, c
     g[p] = l21_norm_of<T>(l21_joint_total(part, (long long)L, (long long)p, nchunk));
 }
 
+static void l21_check_spec(const ExtSpec& sp) {
+  if (sp.nblk != 2 && sp.nblk != 3) throw std::runtime_error("the l2,1 ball needs the 2 or 3 blocks of the TV or TV_xy operator");
+  if (sp.nblk > sp.ndim) throw std::runtime_error("the l2,1 ball: more blocks than grid dimensions");
+  for (int q = 0; q < sp.nblk; ++q)
+    for (int r = 0; r < q; ++r)
+      if (sp.bdir[q] == sp.bdir[r]) throw std::runtime_error("the l2,1 ball: two blocks along one direction");
+  if (sp.G.N >= (1ll << 31)) throw std::runtime_error("the l2,1 ball: the grid needs fewer than 2^31 points");
+  if (sp.bstride < sp.G.N) throw std::runtime_error("the l2,1 ball: the blocks overlap");
+  for (int q = 0; q < sp.nblk; ++q)
+    if (sp.bdir[q] < 0 || sp.bdir[q] >= sp.ndim) throw std::runtime_error("the l2,1 ball: block direction out of range");
+}
+static void l21_seg_check_spec(const ExtSpec& sp) {
+  l21_check_spec(sp);
+  if (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0)
+    throw std::runtime_error("the l2,1 ball per frame needs the blocks (D_y, D_x) of the TV_xy operator on a 3-D grid");
+  if (sp.mode != SIPX_MODE_SLICE || sp.dir != 2) throw std::runtime_error("the l2,1 ball on TV_xy: frames run along z, the mode is (slice, z)");
+}
 static void l21_joint_check_spec(const ExtSpec& sp) {
   l21_check_spec(sp);
   if (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0 || sp.mode != SIPX_MODE_WHOLE)
     throw std::runtime_error(L21_JOINT_ROUTE);
 }
-// g (L entries) <- the group norms of v; part: nchunk L doubles when the plan chunks, not looked at otherwise
+static L21Args l21_args(const ExtSpec& sp) {
+  L21Args a;
+  a.G = sp.G;
+  a.G.set_fast_div();
+  for (int q = 0; q < 3; ++q) a.dir[q] = q < sp.nblk ? sp.bdir[q] : 0;
+  a.bstride = sp.bstride;
+  return a;
+}
+// 16-byte accesses: n1 % 4 == 0 (N and every block base then are multiples of 4 entries) and 16-byte aligned arrays
 template <typename T>
-static void l21_joint_norms(hipStream_t s, const ExtSpec& sp, const L21JointPlan& plan, const T* v, T* g, double* part) {
+static bool l21_wide(const ExtSpec& sp, const T* v, const T* g) {
+  return sp.G.n[0] % 4 == 0 && sp.bstride % 4 == 0 && aligned16(v, g);
+}
+
+// g <- the group norms of v, for every set of the family: N entries by k_l21_norms, or the L entries of EXT_L21_JOINT by the z-march
+// (part: the nchunk L doubles of l21_joint_plan when it chunks, not looked at otherwise)
+template <typename T>
+static void l21_norms(hipStream_t s, const ExtSpec& sp, const T* v, T* g, double* part = nullptr) {
   constexpr int W = l21_vec_width<T>();
+  const bool wide = l21_wide(sp, v, g);
+  const long long N = sp.G.N, L = sp.G.st[2];
+  if (sp.kind != EXT_L21_JOINT) {
+    void (*const k)(L21Args, const T*, T*) = sp.nblk == 2 ? (wide ? k_l21_norms<T, 2, W> : k_l21_norms<T, 2, 1>)
+                                                          : (wide ? k_l21_norms<T, 3, W> : k_l21_norms<T, 3, 1>);
+    ObsScope obs(KID_L21_NORMS, s, (double)(sp.nblk + 1) * N * sizeof(T));
+    hipLaunchKernelGGL(k, dim3(fit_grid(N / (wide ? W : 1), NB)), dim3(BLOCK), 0, s, l21_args(sp), v, g);
+    SIPX_HIP(hipGetLastError());
+    return;
+  }
   L21JArgs a;
   a.G = sp.G;
   a.G.set_fast_div();
   a.bstride = sp.bstride;
-  a.plan = plan;
-  const long long L = sp.G.st[2];
-  const bool wide = l21_wide(sp, v, g), chunks = plan.nchunk > 1;
-  const int grid = fit_grid(L / (wide ? W : 1) * plan.nchunk, NB);
+  a.plan = l21_joint_plan(L, sp.G.n[2], (int)sizeof(T));
+  const bool chunks = a.plan.nchunk > 1;
   {
-    ObsScope obs(KID_L21J_NORMS, s, (double)(2 * sp.G.N + L) * sizeof(T));
-    if (chunks && wide) hipLaunchKernelGGL((k_l21j_norms<T, W, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, part);
-    else if (chunks) hipLaunchKernelGGL((k_l21j_norms<T, 1, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, part);
-    else if (wide) hipLaunchKernelGGL((k_l21j_norms<T, W, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, part);
-    else hipLaunchKernelGGL((k_l21j_norms<T, 1, false>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, part);
+    void (*const k)(L21JArgs, const T*, T*, double*) = chunks ? (wide ? k_l21j_norms<T, W, true> : k_l21j_norms<T, 1, true>)
+                                                              : (wide ? k_l21j_norms<T, W, false> : k_l21j_norms<T, 1, false>);
+    ObsScope obs(KID_L21J_NORMS, s, (double)(2 * N + L) * sizeof(T));
+    hipLaunchKernelGGL(k, dim3(fit_grid(L / (wide ? W : 1) * a.plan.nchunk, NB)), dim3(BLOCK), 0, s, a, v, g, part);
     SIPX_HIP(hipGetLastError());
   }
   if (chunks) {
-    ObsScope obs(KID_L21J_FINISH, s, (double)L * (plan.nchunk * sizeof(double) + sizeof(T)));
-    hipLaunchKernelGGL((k_l21j_finish<T>), dim3(fit_grid(L, NB)), dim3(BLOCK), 0, s, (unsigned)L, plan.nchunk, part, g);
+    ObsScope obs(KID_L21J_FINISH, s, (double)L * (a.plan.nchunk * sizeof(double) + sizeof(T)));
+    hipLaunchKernelGGL((k_l21j_finish<T>), dim3(fit_grid(L, NB)), dim3(BLOCK), 0, s, (unsigned)L, a.plan.nchunk, part, g);
     SIPX_HIP(hipGetLastError());
   }
 }
+// v <- v scaled by the weights of g, for every set of the family: (ps, theta) the search's decision and the Float64 threshold, or
+// EXT_L21_SEG's (theta, need) per frame; kid / bytes: the row of sipx_kernel_stats the launch is booked on
 template <typename T>
-static void l21_joint_scale(hipStream_t s, const ExtSpec& sp, T* v, const T* g, const ProjScalars<T>* ps, const T* theta) {
+static void l21_scale(hipStream_t s, const ExtSpec& sp, int kid, double bytes, T* v, const T* g, const ProjScalars<T>* ps, const T* theta,
+                      const int* need) {
   constexpr int W = l21_vec_width<T>();
-  const L21Args a = l21_args(sp);
   const bool wide = l21_wide(sp, v, g);
-  const int grid = fit_grid(sp.G.N / (wide ? W : 1), NB);
-  const int* none = nullptr;
-  ObsScope obs(KID_L21J_SCALE, s, (double)(4 * sp.G.N + sp.G.st[2]) * sizeof(T));
-  if (wide) hipLaunchKernelGGL((k_l21_scale<T, 2, W, false, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
-  else hipLaunchKernelGGL((k_l21_scale<T, 2, 1, false, true>), dim3(grid), dim3(BLOCK), 0, s, a, v, g, ps, theta, none);
+  void (*const k)(L21Args, T*, const T*, const ProjScalars<T>*, const T*, const int*) =
+      sp.kind == EXT_L21_SEG     ? (wide ? k_l21_scale<T, 2, W, true> : k_l21_scale<T, 2, 1, true>)
+      : sp.kind == EXT_L21_JOINT ? (wide ? k_l21_scale<T, 2, W, false, true> : k_l21_scale<T, 2, 1, false, true>)
+      : sp.nblk == 2             ? (wide ? k_l21_scale<T, 2, W, false> : k_l21_scale<T, 2, 1, false>)
+                                 : (wide ? k_l21_scale<T, 3, W, false> : k_l21_scale<T, 3, 1, false>);
+  ObsScope obs(kid, s, bytes);
+  hipLaunchKernelGGL(k, dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, s, l21_args(sp), v, g, ps, theta, need);
+  SIPX_HIP(hipGetLastError());
+}
+template <typename T, bool OBSERVE>
+static void l21_frames(hipStream_t s, const ExtSpec& sp, const T* g, T tau, const T* rmax, T* theta, int* need, T* asum, int* passes) {
+  const long long L = sp.G.n[0] * sp.G.n[1], nf = sp.G.n[2];
+  L21SegPlan plan = l21_seg_plan(L, nf, (int)sizeof(T));
+  if (OBSERVE) { plan.lds = 0; plan.lds_bytes = 0; }
+  ObsScope obs(KID_L21_FRAMES, s, (double)sp.G.N * sizeof(T));
+  if (rmax)
+    hipLaunchKernelGGL((k_l21_frames<T, true, OBSERVE>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, s, plan, (unsigned)L, (unsigned)nf, g, tau,
+                       rmax, theta, need, asum, passes);
+  else
+    hipLaunchKernelGGL((k_l21_frames<T, false, OBSERVE>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, s, plan, (unsigned)L, (unsigned)nf, g, tau,
+                       rmax, theta, need, asum, passes);
   SIPX_HIP(hipGetLastError());
 }
 
+// ---- EXT_L21, EXT_L21_JOINT: one ball on the whole array -- the norms, the engine's search on g, Float64: the refinement, the scale ----
+// The two sets differ in what a group is, hence in the norms launch and in the length of g: the N grid points, or the L pixels.
 template <typename T>
-struct JointProj : ExtImpl<T> {
+struct BallProj : ExtImpl<T> {
   using ExtImpl<T>::sp;
   using ExtImpl<T>::stream;
-  L21JointPlan plan;
-  long long L = 0;
-  T* g = nullptr;                      // the group norms, L entries
-  double* part = nullptr;              // the chunk sums, nchunk L entries, when the plan chunks
+  const bool joint;
+  long long n = 0;                     // groups: the entries of g, the length of the search
+  T* g = nullptr;                      // the group norms
+  double* part = nullptr;              // EXT_L21_JOINT: the chunk sums, nchunk L entries, when the plan chunks
   double* tpart = nullptr;             // Float64: the partial sums of k_l21_theta_part
   T* theta = nullptr;                  // Float64: the threshold k_l21_scale applies
   SearchState<T> search;
+  ProjScalars<T>* ps_obs = nullptr;    // the state of observe's search, taken at its first call
   void reset() override { search.reinit(stream); }
-  JointProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
-    l21_joint_check_spec(sp);
+  BallProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s), joint(spec.kind == EXT_L21_JOINT) {
+    if (joint) l21_joint_check_spec(sp);
+    else l21_check_spec(sp);
     if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-    L = sp.G.st[2];
-    plan = l21_joint_plan(L, sp.G.n[2], (int)sizeof(T));
-    g = this->template alloc<T>(L);
-    if (plan.nchunk > 1) part = this->template alloc<double>((size_t)plan.nchunk * L);
+    n = joint ? sp.G.st[2] : sp.G.N;
+    g = this->template alloc<T>(n);
+    const int nchunk = joint ? l21_joint_plan(n, sp.G.n[2], (int)sizeof(T)).nchunk : 1;
+    if (nchunk > 1) part = this->template alloc<double>((size_t)nchunk * n);
     if (sizeof(T) == 8) {
       tpart = this->template alloc<double>(3 * L21_THETA_GRID);
       theta = this->template alloc<T>(1);
     }
     search.build(this->mem, s, 0);
   }
-  void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
-    ProjScalars<T>* ps = search.pick(feas);
-    l21_joint_norms<T>(stream, sp, plan, v, g, part);
-    K<T>::proj_scalars_arr(stream, L, g, PX_L1, T(0), (T)sp.pmax, ps, partials, maxpart, compact, L);
+  // the search on g; Float64: then the threshold of its active set in twice the working precision, left in theta[0]
+  void threshold(ProjScalars<T>* ps, double* partials, T* maxpart, T* compact) {
+    K<T>::proj_scalars_arr(stream, n, g, PX_L1, T(0), (T)sp.pmax, ps, partials, maxpart, compact, n);
     if constexpr (sizeof(T) == 8) {
-      const int grid = fit_grid(L, L21_THETA_GRID);
-      hipLaunchKernelGGL(k_l21_theta_part, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)L, g, ps, tpart);
-      hipLaunchKernelGGL(k_l21_theta_final, dim3(1), dim3(BLOCK), 0, stream, grid, (unsigned)L, (double)sp.pmax, tpart, ps, theta);
+      const int grid = fit_grid(n, L21_THETA_GRID);
+      hipLaunchKernelGGL(k_l21_theta_part, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)n, g, ps, tpart);
+      hipLaunchKernelGGL(k_l21_theta_final, dim3(1), dim3(BLOCK), 0, stream, grid, (unsigned)n, (double)sp.pmax, tpart, ps, theta);
       SIPX_HIP(hipGetLastError());
     }
-    l21_joint_scale<T>(stream, sp, v, g, ps, theta);
+  }
+  void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
+    const double N = (double)sp.G.N;
+    ProjScalars<T>* ps = search.pick(feas);
+    l21_norms<T>(stream, sp, v, g, part);
+    threshold(ps, partials, maxpart, compact);
+    if (joint) l21_scale<T>(stream, sp, KID_L21J_SCALE, (4 * N + n) * sizeof(T), v, g, ps, theta, nullptr);
+    else l21_scale<T>(stream, sp, KID_L21_SCALE, (2 * sp.nblk + 1) * N * sizeof(T), v, g, ps, theta, nullptr);
+  }
+  // out[0] <- the sum of the group norms as project decides on it: its norms launch into its g, then the first pass of a search with
+  // a new state and an infinite radius -- the sum, and the rounding to T, that project compares with the radius.  The warm starts stay.
+  void observe(const T* v, T* out, double* partials, T* maxpart, T* compact) override {
+    if (!ps_obs) ps_obs = this->template alloc<ProjScalars<T>>(1);
+    l21_norms<T>(stream, sp, v, g, part);
+    K<T>::ps_init(stream, ps_obs, nullptr);
+    K<T>::proj_scalars_arr(stream, n, g, PX_L1, T(0), (T)INFINITY, ps_obs, partials, maxpart, compact, n);
+    hipLaunchKernelGGL((k_l21_pick<T>), dim3(1), dim3(64), 0, stream, ps_obs, out);
+    SIPX_HIP(hipGetLastError());
+  }
+};
+
+// ---- EXT_L21_SEG: the l2,1 ball of every z-slice on the range of TV_xy (l21_seg.h) -------------------------------------------------------
+//     k_l21_norms     as above, two blocks on the 3-D grid                                    reads 2 N words, writes N
+//     k_l21_frames    one workgroup per frame on g alone: asum, the decision, Michelot's passes  reads N (LDS) or passes * N
+//     k_l21_scale     the per-frame form; frames inside their ball are skipped without a store  reads up to 3 N, writes up to 2 N
+// Nothing is kept between calls: the call of the feasibility estimate and the one of the y update are independent, reset() has
+// nothing to forget.  Built with ExtSpec::ub every frame has its own radius (rmax, n3 entries), sipx_set_data replaces them.
+template <typename T>
+struct FrameProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  T *g = nullptr, *theta = nullptr, *asum = nullptr, *rmax = nullptr;
+  int *need = nullptr, *passes = nullptr;
+  long long nf = 0;
+  FrameProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    l21_seg_check_spec(sp);
+    nf = sp.G.n[2];
+    if (!sp.ub && !((T)sp.pmax > T(0))) throw std::runtime_error("Radius of L1 ball is negative");
+    if (sp.ub) {
+      const T* h = (const T*)sp.ub;
+      for (long long k = 0; k < nf; ++k)
+        if (!(h[k] > T(0))) throw std::runtime_error("Radius of L1 ball is negative");
+    }
+    g = this->template alloc<T>(sp.G.N);
+    theta = this->template alloc<T>(nf);
+    asum = this->template alloc<T>(nf);
+    need = this->template alloc<int>(2 * nf);
+    passes = need + nf;
+    SIPX_HIP(hipMemset(need, 0, sizeof(int) * 2 * (size_t)nf));      // (route_counts may be asked before the first projection)
+    if (sp.ub) {
+      rmax = this->template alloc<T>(nf);
+      SIPX_HIP(hipMemcpy(rmax, sp.ub, sizeof(T) * (size_t)nf, hipMemcpyHostToDevice));
+    }
+  }
+  void project(T* v, bool, double*, T*, T*) override {
+    l21_norms<T>(stream, sp, v, g);
+    l21_frames<T, false>(stream, sp, g, (T)sp.pmax, rmax, theta, need, asum, passes);
+    l21_scale<T>(stream, sp, KID_L21_SCALE, (2 * sp.nblk + 1) * (double)sp.G.N * sizeof(T), v, g, nullptr, theta, need);
+  }
+  // out[k] (n3 entries) <- (T)asum_k of the frames as project decides on them: its norms launch into its g, then pass 1 of k_l21_frames
+  void observe(const T* v, T* out, double*, T*, T*) override {
+    l21_norms<T>(stream, sp, v, g);
+    l21_frames<T, true>(stream, sp, g, T(0), (const T*)nullptr, (T*)nullptr, (int*)nullptr, out, (int*)nullptr);
+  }
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    if (!rmax) ExtImpl<T>::set_data(new_lb, new_ub, on_device);
+    if (new_lb) throw std::runtime_error("only the annulus has inner radii: pass the radii of this set as ub");
+    if (new_ub)
+      SIPX_HIP(hipMemcpyAsync(rmax, new_ub, sizeof(T) * (size_t)nf, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  }
+  // the Michelot passes of the last call, per frame (tools/l21_frames_bench.py)
+  void route_counts(long long out[4]) const override {
+    std::vector<int> h((size_t)nf);
+    SIPX_HIP(hipStreamSynchronize(stream));
+    SIPX_HIP(hipMemcpy(h.data(), passes, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
+    out[0] = out[1] = out[2] = 0; out[3] = nf;
+    for (int x : h) { out[0] += x; out[1] = std::max<long long>(out[1], x); }
   }
 };
 
 template <typename T>
 ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
-  if (spec.kind == EXT_L21_JOINT) return new JointProj<T>(spec, stream);
   if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);
-  if (spec.kind != EXT_L21) throw std::runtime_error("unknown external projector");
-  return new GroupProj<T>(spec, stream);
+  if (spec.kind != EXT_L21 && spec.kind != EXT_L21_JOINT) throw std::runtime_error("unknown external projector");
+  return new BallProj<T>(spec, stream);
 }
-
-// out[k] (device, n3 entries) <- (T)asum_k of the frames of a materialised vector in the layout of an EXT_L21_SEG spec: k_l21_norms
-// into g (N entries), then pass 1 of k_l21_frames -- the numbers the projector compares with the radii
-template <typename T>
-void l21_seg_observe(const ExtSpec& spec, const T* v, T* g, T* out, hipStream_t stream) {
-  l21_seg_check_spec(spec);
-  l21_norms<T>(stream, spec, v, g);
-  l21_frames<T, true>(stream, spec, g, T(0), (const T*)nullptr, (T*)nullptr, (int*)nullptr, out, (int*)nullptr);
-}
-template void l21_seg_observe<float>(const ExtSpec&, const float*, float*, float*, hipStream_t);
-template void l21_seg_observe<double>(const ExtSpec&, const double*, double*, double*, hipStream_t);
-
-// out[0] (device) <- ||v||_2,1 of a materialised vector in the layout of spec: k_l21_norms into g (N entries), then the first pass
-// of a search with a new state and an infinite radius -- the sum, and the rounding to T, of the projector's own decision
-template <typename T>
-void l21_observe(const ExtSpec& spec, const T* v, T* g, ProjScalars<T>* ps, double* partials, T* maxpart, T* compact, T* out,
-                 hipStream_t stream) {
-  l21_check_spec(spec);
-  const long long N = spec.G.N;
-  l21_norms<T>(stream, spec, v, g);
-  K<T>::ps_init(stream, ps, nullptr);
-  K<T>::proj_scalars_arr(stream, N, g, PX_L1, T(0), (T)INFINITY, ps, partials, maxpart, compact, N);
-  hipLaunchKernelGGL((k_l21_pick<T>), dim3(1), dim3(64), 0, stream, ps, out);
-  SIPX_HIP(hipGetLastError());
-}
-
-// out[0] (device) <- the sum of the L group norms of a materialised vector in the layout of an EXT_L21_JOINT spec: the z-march into g
-// (L entries; part: the chunk sums of l21_joint_plan, nchunk L doubles, when it chunks), then the first pass of a search with a new
-// state and an infinite radius -- the sum, and the rounding to T, of the projector's own decision
-template <typename T>
-void l21_joint_observe(const ExtSpec& spec, const T* v, T* g, double* part, ProjScalars<T>* ps, double* partials, T* maxpart, T* compact,
-                       T* out, hipStream_t stream) {
-  l21_joint_check_spec(spec);
-  const long long L = spec.G.st[2];
-  l21_joint_norms<T>(stream, spec, l21_joint_plan(L, spec.G.n[2], (int)sizeof(T)), v, g, part);
-  K<T>::ps_init(stream, ps, nullptr);
-  K<T>::proj_scalars_arr(stream, L, g, PX_L1, T(0), (T)INFINITY, ps, partials, maxpart, compact, L);
-  hipLaunchKernelGGL((k_l21_pick<T>), dim3(1), dim3(64), 0, stream, ps, out);
-  SIPX_HIP(hipGetLastError());
-}
-template void l21_joint_observe<float>(const ExtSpec&, const float*, float*, double*, ProjScalars<float>*, double*, float*, float*, float*,
-                                       hipStream_t);
-template void l21_joint_observe<double>(const ExtSpec&, const double*, double*, double*, ProjScalars<double>*, double*, double*, double*,
-                                        double*, hipStream_t);
 
 template ExtImpl<float>* make_group_family<float>(const ExtSpec&, hipStream_t);
 template ExtImpl<double>* make_group_family<double>(const ExtSpec&, hipStream_t);
-template void l21_observe<float>(const ExtSpec&, const float*, float*, ProjScalars<float>*, double*, float*, float*, float*, hipStream_t);
-template void l21_observe<double>(const ExtSpec&, const double*, double*, ProjScalars<double>*, double*, double*, double*, double*,
-                                  hipStream_t);
 
 }  // namespace sipx

@@ -48,6 +48,10 @@ class ExtProj {
   ExtProj(const ExtProj&) = delete;
   // v <- P(v) in place (padded layout, G.N entries); feas selects the warm-start state of the feasibility estimate
   void project(T* v, bool feas, double* partials, T* maxpart, T* compact);
+  // the l2,1 sets (ext_group.hip): out (device) <- what project(v, ...) would compare with the radius, summed and rounded by the
+  // projector's own launches -- ||v||_2,1 for EXT_L21, the sum of the n1 n2 group norms for EXT_L21_JOINT, one sum per z-slice (n3
+  // entries) for EXT_L21_SEG.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
+  void observe(const T* v, T* out, double* partials, T* maxpart, T* compact);
   // rank projector: calls since construction, calls served by the warm-started subspace route, calls that decomposed fully,
   // products with the Gram matrices the subspace route spent (all zero for the other kinds)
   void route_counts(long long out[4]) const;
@@ -69,24 +73,6 @@ class ExtProj {
 // (ext_family.h) in the order of the per-segment radii (seg_norm.h: k_seg_observe)
 template <typename T>
 void seg_observe(const ExtSpec& spec, int norm_l2, const T* v, T* out, hipStream_t stream);
-
-// out[0] (device) <- ||v||_2,1 of a materialised vector in the layout of an EXT_L21 spec, as the projector's own decision sums and
-// rounds it (ext_group.hip); g: N entries of scratch, ps / partials / maxpart / compact: those of a threshold search over N entries
-template <typename T>
-void l21_observe(const ExtSpec& spec, const T* v, T* g, ProjScalars<T>* ps, double* partials, T* maxpart, T* compact, T* out,
-                 hipStream_t stream);
-
-// out[k] (device, n3 entries) <- the sum of the group norms of frame k, as the per-frame projector's decision sums and rounds it
-// (ext_group.hip, EXT_L21_SEG); g: N entries of scratch
-template <typename T>
-void l21_seg_observe(const ExtSpec& spec, const T* v, T* g, T* out, hipStream_t stream);
-
-// out[0] (device) <- the sum of the n1 n2 group norms of a materialised vector in the layout of an EXT_L21_JOINT spec, as the joint
-// projector's decision sums and rounds it (ext_group.hip); g: n1 n2 entries of scratch, part: nchunk n1 n2 doubles when l21_joint_plan
-// (l21_joint.h) chunks, ps / partials / maxpart / compact: those of a threshold search over n1 n2 entries
-template <typename T>
-void l21_joint_observe(const ExtSpec& spec, const T* v, T* g, double* part, ProjScalars<T>* ps, double* partials, T* maxpart, T* compact,
-                       T* out, hipStream_t stream);
 
 // sum (projected - original)^2 and sum original^2 into partial slots dst[0..NB), dst[NB..2NB)
 template <typename T>

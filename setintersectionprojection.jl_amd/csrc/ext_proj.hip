@@ -49,6 +49,10 @@ void ExtProj<T>::project(T* v, bool feas, double* partials, T* maxpart, T* compa
   impl_->project(v, feas, partials, maxpart, compact);
 }
 template <typename T>
+void ExtProj<T>::observe(const T* v, T* out, double* partials, T* maxpart, T* compact) {
+  impl_->observe(v, out, partials, maxpart, compact);
+}
+template <typename T>
 void ExtProj<T>::set_stream(hipStream_t s) { impl_->set_stream(s); }
 // Back to the state of a freshly built projector (sipx_reset): no warm start of any kind, no pending status, counters at zero.
 // A reused context then walks through exactly the calls of a new one -- same bits -- without its allocations, plans and handles.

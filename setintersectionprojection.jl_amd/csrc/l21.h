@@ -1,5 +1,5 @@
 // Isotropic total variation: the l2,1 ball { v : sum_p ||v_p||_2 <= tau } on the range of the TV operator (ext_group.hip,
-// GroupProj).  The rule of one group as __host__ __device__ functions (tests/l21/rule_driver.cpp runs them on the CPU); the
+// BallProj).  The rule of one group as __host__ __device__ functions (tests/l21/rule_driver.cpp runs them on the CPU); the
 // kernels in ext_group.hip call nothing else for the arithmetic.
 //
 // GROUPS.  The TV operator lays its nblk = 2 (2-D) or 3 (3-D) difference blocks side by side as full padded grids with block
@@ -93,5 +93,28 @@ __host__ __device__ inline double l21_theta_refined(const L21Sum& S, double C, d
   const double th = (d + (e + S.lo)) / C;
   return th > 0.0 ? th : 0.0;
 }
+
+#if defined(__HIPCC__)
+// The fixed tree of the sums in twice the working precision, across the NT threads of a workgroup: the four-wave layout of segn_sum2
+// does not apply to a pair that is merged, not added, so the pairs are merged in halves -- thread t merges (sh[t], sl[t]) with
+// (sh[t + w], sl[t + w]) for w = NT / 2 .. 1, the counts are added alongside.  `red`: 3 * NT doubles of LDS.  Returned to every thread.
+// Every Float64 threshold (k_l21_theta_part, k_l21_theta_final, k_l21_frames) goes through this one order.
+template <int NT>
+__device__ __forceinline__ void l21_tree_merge(L21Sum& a, double& c, double* red) {
+  double *sh = red, *sl = red + NT, *sc = red + 2 * NT;
+  sh[threadIdx.x] = a.hi; sl[threadIdx.x] = a.lo; sc[threadIdx.x] = c;
+  __syncthreads();
+  for (int w = NT / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      L21Sum x{sh[threadIdx.x], sl[threadIdx.x]};
+      l21_sum_merge(x, L21Sum{sh[threadIdx.x + w], sl[threadIdx.x + w]});
+      sh[threadIdx.x] = x.hi; sl[threadIdx.x] = x.lo; sc[threadIdx.x] += sc[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  a.hi = sh[0]; a.lo = sl[0]; c = sc[0];
+  __syncthreads();
+}
+#endif
 
 }  // namespace sipx

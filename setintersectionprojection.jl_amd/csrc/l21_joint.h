@@ -1,5 +1,5 @@
 // Joint (vectorial) isotropic total variation: the l2,1 ball whose groups span the frames, on the range of the in-plane gradient
-// TV_xy = vcat(D_y, D_x) of a 3-D grid, { v : sum_{(i,j)} g_ij <= tau } (ext_group.hip, JointProj).  The launch plan of the z-march
+// TV_xy = vcat(D_y, D_x) of a 3-D grid, { v : sum_{(i,j)} g_ij <= tau } (ext_group.hip, BallProj).  The launch plan of the z-march
 // and the rule of one pixel as __host__ __device__ functions (tests/l21_joint/rule_driver.cpp runs them on the CPU); the kernels in
 // ext_group.hip call nothing else for the arithmetic.
 //

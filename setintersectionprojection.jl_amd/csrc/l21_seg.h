@@ -98,24 +98,6 @@ __host__ __device__ inline int l21_seg_frame(const T* g, long long L, T tau, boo
 }
 
 #if defined(__HIPCC__)
-// The fixed tree of the sums in twice the working precision: the four-wave layout of segn_sum2 does not apply to a pair that is
-// merged, not added, so the workgroup's BLOCK pairs are merged in halves.  `red`: 3 * BLOCK doubles.  Returned to every thread.
-__device__ __forceinline__ void l21_seg_merge(L21Sum& a, double& c, double* red) {
-  double *sh = red, *sl = red + BLOCK, *sc = red + 2 * BLOCK;
-  sh[threadIdx.x] = a.hi; sl[threadIdx.x] = a.lo; sc[threadIdx.x] = c;
-  __syncthreads();
-  for (int w = BLOCK / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      L21Sum x{sh[threadIdx.x], sl[threadIdx.x]};
-      l21_sum_merge(x, L21Sum{sh[threadIdx.x + w], sl[threadIdx.x + w]});
-      sh[threadIdx.x] = x.hi; sl[threadIdx.x] = x.lo; sc[threadIdx.x] += sc[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  a.hi = sh[0]; a.lo = sl[0]; c = sc[0];
-  __syncthreads();
-}
-
 // f(t, src[t]) for the thread's entries t = tid, tid + BLOCK, ... in that order, L21_SEG_LOADS loads issued before the first is used:
 // one workgroup streams a whole frame, and with one load in flight per lane a pass is a chain of L / BLOCK exposed memory latencies
 // (the weak case of k_seg_norm).  The order of the visits, hence every sum, is that of the plain loop.
@@ -185,7 +167,7 @@ __global__ __launch_bounds__(BLOCK) void k_l21_frames(L21SegPlan p, unsigned L, 
           const double a = (double)x;
           if (a > (double)th) { l21_sum_add(S, a); C += 1.0; }
         });
-        l21_seg_merge(S, C, red);
+        l21_tree_merge<BLOCK>(S, C, red);
         th = (T)l21_seg_theta_final((double)th, S, C, (double)tau, (long long)L);
       }
     }

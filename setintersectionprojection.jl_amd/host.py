@@ -1849,6 +1849,41 @@ def segment_norms(x, comp_grid, TD_OP: str, app_mode, norm: str):
     return out
 
 
+def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after):
+    """What l21_norm and l21_joint_norm share: x, a numpy vector or a 1-D torch tensor on a GPU, goes through the library call
+    fn(ctx, *before, x, out, *after) -- its _dev form for a tensor, ordered against torch's current stream -- in a context of its
+    own.  out: n3 entries (per_frame) or one, of the kind and precision of x.  Returns (out, x is a tensor)."""
+    on_dev = _is_tensor(x)
+    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError(f"{name}: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    n, _ = _grid(comp_grid)
+    N = int(np.prod(n))
+    if needs_3d and len(n) != 3:
+        raise SipxError(TV_XY_NEEDS_3D)
+    nout = int(n[2]) if per_frame else 1
+    if on_dev:
+        import torch
+        _check_tensor("x", x, TF, N, None)
+        _check_one_hip_runtime()
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        out = torch.empty(nout, dtype=x.dtype, device=torch.device("cuda", device))
+        xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
+    else:
+        x = _check_array("x", x, TF, N)
+        device = None
+        out = np.empty(nout, TF)
+        xp, op_ = _ptr(x), _ptr(out)
+    ctx = Context(comp_grid, TF, device)
+    try:
+        if on_dev:
+            ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        _chk(getattr(lib(), fn + ("_dev" if on_dev else ""))(ctx.h, *before, xp, op_, *after))
+    finally:
+        ctx.close()
+    return out, on_dev
+
+
 def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None):
     """||TV x||_2,1, the isotropic total variation of x on a 2-D or 3-D grid: sum over the grid points of the l2 norm of the forward
     differences that start there, one number of the working precision (that of x).  Computed by the kernel and the first-pass sum of
@@ -1868,36 +1903,7 @@ def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None):
         if tuple(app_mode) != ("slice", "z"):
             raise SipxError(L21_FRAMES_Z)
         mode, dirn = MODES["slice"], 2
-    on_dev = _is_tensor(x)
-    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
-    if TF not in (np.float32, np.float64):
-        raise SipxError("l21_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
-    n, _ = _grid(comp_grid)
-    N = int(np.prod(n))
-    if TD_OP == "TV_xy" and len(n) != 3:
-        raise SipxError(TV_XY_NEEDS_3D)
-    nout = int(n[2]) if mode else 1
-    if on_dev:
-        import torch
-        _check_tensor("x", x, TF, N, None)
-        _check_one_hip_runtime()
-        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        out = torch.empty(nout, dtype=x.dtype, device=torch.device("cuda", device))
-        xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
-        fn = lib().sipx_l21_norms_dev
-    else:
-        x = _check_array("x", x, TF, N)
-        device = None
-        out = np.empty(nout, TF)
-        xp, op_ = _ptr(x), _ptr(out)
-        fn = lib().sipx_l21_norms
-    ctx = Context(comp_grid, TF, device)
-    try:
-        if on_dev:
-            ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
-        _chk(fn(ctx.h, OPS[TD_OP], mode, dirn, xp, op_, None))
-    finally:
-        ctx.close()
+    out, on_dev = _l21_observe("l21_norm", x, comp_grid, TD_OP == "TV_xy", bool(mode), "sipx_l21_norms", (OPS[TD_OP], mode, dirn), (None,))
     return out if (on_dev or mode) else out[0]
 
 
@@ -1907,35 +1913,7 @@ def l21_joint_norm(x, comp_grid):
     z-march and the first-pass sum of the ("l21_joint", "TV_xy") projector (sipx_l21_joint_norm): used as the radius it leaves TV_xy x
     unwritten.  x: a numpy vector (a numpy scalar comes back) or a 1-D torch tensor on a GPU (a tensor of one entry there; nothing
     crosses PCIe, the call orders itself against torch's current stream)."""
-    on_dev = _is_tensor(x)
-    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
-    if TF not in (np.float32, np.float64):
-        raise SipxError("l21_joint_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
-    n, _ = _grid(comp_grid)
-    N = int(np.prod(n))
-    if len(n) != 3:
-        raise SipxError(TV_XY_NEEDS_3D)
-    if on_dev:
-        import torch
-        _check_tensor("x", x, TF, N, None)
-        _check_one_hip_runtime()
-        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        out = torch.empty(1, dtype=x.dtype, device=torch.device("cuda", device))
-        xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
-        fn = lib().sipx_l21_joint_norm_dev
-    else:
-        x = _check_array("x", x, TF, N)
-        device = None
-        out = np.empty(1, TF)
-        xp, op_ = _ptr(x), _ptr(out)
-        fn = lib().sipx_l21_joint_norm
-    ctx = Context(comp_grid, TF, device)
-    try:
-        if on_dev:
-            ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
-        _chk(fn(ctx.h, xp, op_))
-    finally:
-        ctx.close()
+    out, on_dev = _l21_observe("l21_joint_norm", x, comp_grid, True, False, "sipx_l21_joint_norm", (), ())
     return out if on_dev else out[0]
 
 

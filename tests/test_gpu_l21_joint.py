@@ -1,5 +1,5 @@
 """Joint (vectorial) isotropic total variation across frames on the GPU: the ("l21_joint", "TV_xy") set (csrc/l21_joint.h,
-csrc/ext_group.hip, JointProj) against tests/l21_joint_ref.py: the projector at four radii, inputs it must not write, exact ties, the
+csrc/ext_group.hip, BallProj) against tests/l21_joint_ref.py: the projector at four radii, inputs it must not write, exact ties, the
 whole-array set on an input with one non-zero frame, observed radii (sipx.l21_joint_norm), whole solves against the oracle on the same
 operator given as custom_TD_OP with its projector swapped for the reference, and the engine's refusals through the C ABI.
 
