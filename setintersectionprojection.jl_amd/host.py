@@ -138,7 +138,18 @@ def _dtype_code(TF):
 
 
 def _ptr(a):
+    """The data of a numpy array as a void pointer (None: the null pointer)."""
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _tensor_ptr(t):
+    """The same for a torch tensor."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _ptr_array(lst, ptr=_ptr):
+    """A C array of void pointers, one per vector of the list (None: the null pointer).  The caller keeps the vectors alive."""
+    return None if lst is None else (C.c_void_p * len(lst))(*[ptr(a) for a in lst])
 
 
 # --------------------------------------------------------------------------------------------------
@@ -810,6 +821,19 @@ def PARSDMM_precompute_distribute_Minkowski(TD_OP_c1, TD_OP_c2, TD_OP_sum, set_P
 # --------------------------------------------------------------------------------------------------
 # engine handle (phase-level API, include/sipx.h section A)
 # --------------------------------------------------------------------------------------------------
+def _warm_start_arrays(lst, TF, rows):
+    """l or y of a warm start as contiguous vectors of the working precision, one per term."""
+    if len(lst) != len(rows):
+        raise SipxError("warm start: l and y need one vector per term (sets plus the distance term)")
+    out = []
+    for i, a in enumerate(lst):
+        a = np.ascontiguousarray(a, TF)
+        if a.shape != (rows[i],):
+            raise SipxError(f"warm start: vector {i} has {a.shape} entries, operator {i} has {rows[i]} rows")
+        out.append(a)
+    return out
+
+
 class Context:
     def __init__(self, comp_grid, TF, device: Optional[int] = None):
         device = _default_device if device is None else device
@@ -854,7 +878,7 @@ class Context:
         if AtA is not None:
             R = np.asfortranarray(AtA, dtype=self.TF)
             off = np.ascontiguousarray(AtA_offsets, np.int64)
-            rc = lib().sipx_add_set(self.h, C.byref(d), _ptr(R), off.ctypes.data_as(C.c_void_p), int(R.shape[1]))
+            rc = lib().sipx_add_set(self.h, C.byref(d), _ptr(R), _ptr(off), int(R.shape[1]))
         else:
             rc = lib().sipx_add_set(self.h, C.byref(d), None, None, 0)
         if rc < 0:
@@ -895,75 +919,57 @@ class Context:
     def set_owned(self, owned: Sequence[int]):
         a = np.zeros(len(self.rows) + 1, np.int32)       # constraint sets + the distance term
         a[:len(owned)] = np.asarray(owned, np.int32)[:len(a)]
-        _chk(lib().sipx_set_owned(self.h, a.ctypes.data_as(C.c_void_p)))
+        _chk(lib().sipx_set_owned(self.h, _ptr(a)))
 
     def finalize(self, m, rho_ini, gamma_ini, feasibility_only=False, zero_ini_guess=True, x0=None, l0=None, y0=None):
-        m = np.ascontiguousarray(m, self.TF)
-        if m.shape != (self.N,):
-            raise SipxError("length of m does not match the grid")
-        rho = np.ascontiguousarray(rho_ini, np.float64)
-        npp = len(self.rows)
-        feas = np.zeros(max(npp, 1))
-        keep = []
-
-        rows_all = list(self.rows) + ([] if feasibility_only else [self.N])
-
-        def arr_list(lst):
-            if lst is None or len(lst) == 0:
-                return None
-            if len(lst) != len(rows_all):
-                raise SipxError("warm start: l and y need one vector per term (sets plus the distance term)")
-            ptrs = (C.c_void_p * len(lst))()
-            for i, a in enumerate(lst):
-                a = np.ascontiguousarray(a, self.TF)
-                if a.shape != (rows_all[i],):
-                    raise SipxError(f"warm start: vector {i} has {a.shape} entries, operator {i} has {rows_all[i]} rows")
-                keep.append(a)
-                ptrs[i] = a.ctypes.data
-            return ptrs
-        x0a = None if x0 is None else np.ascontiguousarray(x0, self.TF)
-        if x0a is not None and x0a.shape != (self.Nx,):
-            raise SipxError("length of x does not match the grid")
-        _chk(lib().sipx_finalize(self.h, _ptr(m), rho.ctypes.data_as(C.c_void_p), len(rho), C.c_double(gamma_ini),
-                                 int(feasibility_only), int(zero_ini_guess), _ptr(x0a), arr_list(l0), arr_list(y0),
-                                 feas.ctypes.data_as(C.c_void_p)))
-        p, pp = C.c_int(), C.c_int()
-        _chk(lib().sipx_num_terms(self.h, C.byref(p), C.byref(pp)))
-        self.p, self.pp = p.value, pp.value
-        if self.p > npp:
-            self.rows.append(self.N)
-        return feas[:npp]
+        return self._start(False, False, m, rho_ini, gamma_ini, feasibility_only, zero_ini_guess, x0, l0, y0)
 
     def reset(self, m, rho_ini, gamma_ini, zero_ini_guess=True, x0=None, l0=None, y0=None):
         """The same sets on the same grid, once more (sipx_reset): a new model m -- and, optionally, a new warm start and rho_ini --
         on this finalised context, without any allocation.  Returns the initial feasibilities.  A solve that follows gives the
         bits a newly built context gives."""
-        m = np.ascontiguousarray(m, self.TF)
-        if m.shape != (self.N,):
-            raise SipxError("length of m does not match the grid")
-        rho = np.ascontiguousarray(rho_ini, np.float64)
-        npp = self.pp
-        feas = np.zeros(max(npp, 1))
-        keep = []
+        return self._start(False, True, m, rho_ini, gamma_ini, False, zero_ini_guess, x0, l0, y0)
 
-        def arr_list(lst):
-            if lst is None or len(lst) == 0:
-                return None
-            if len(lst) != len(self.rows):
-                raise SipxError("warm start: l and y need one vector per term (sets plus the distance term)")
-            ptrs = (C.c_void_p * len(lst))()
-            for i, a in enumerate(lst):
-                a = np.ascontiguousarray(a, self.TF)
-                if a.shape != (self.rows[i],):
-                    raise SipxError(f"warm start: vector {i} has {a.shape} entries, operator {i} has {self.rows[i]} rows")
-                keep.append(a)
-                ptrs[i] = a.ctypes.data
-            return ptrs
-        x0a = None if x0 is None else np.ascontiguousarray(x0, self.TF)
-        if x0a is not None and x0a.shape != (self.Nx,):
-            raise SipxError("length of x does not match the grid")
-        _chk(lib().sipx_reset(self.h, _ptr(m), rho.ctypes.data_as(C.c_void_p), len(rho), C.c_double(gamma_ini),
-                              int(zero_ini_guess), _ptr(x0a), arr_list(l0), arr_list(y0), feas.ctypes.data_as(C.c_void_p)))
+    def _start(self, on_dev, again, m, rho_ini, gamma_ini, feasibility_only, zero_ini_guess, x0, l0, y0):
+        """What finalize, reset and their _dev forms are: m and the warm start checked against the grid and the rows of the terms,
+        handed to sipx_finalize / sipx_reset (first call / again) or their _dev forms (on_dev: torch tensors on this context's GPU
+        instead of numpy arrays).  Stores and returns the initial feasibilities."""
+        TF = self.TF
+        rows = self.rows if again else list(self.rows) + ([] if feasibility_only else [self.N])
+        npp = self.pp if again else len(self.rows)
+        l0, y0 = [None if lst is None or len(lst) == 0 else lst for lst in (l0, y0)]
+        if on_dev:
+            dev, ptr = m.device, _tensor_ptr
+            _check_tensor("m", m, TF, self.N, dev)
+            if x0 is not None:
+                _check_tensor("x", x0, TF, self.Nx, dev)
+            for name, lst in (("l", l0), ("y", y0)):
+                if lst is not None:
+                    _check_tensor_list(name, lst, TF, rows, dev)
+            import torch
+            self.set_caller_stream(torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            ptr = _ptr
+            m = np.ascontiguousarray(m, TF)
+            if m.shape != (self.N,):
+                raise SipxError("length of m does not match the grid")
+            if x0 is not None:
+                x0 = np.ascontiguousarray(x0, TF)
+                if x0.shape != (self.Nx,):
+                    raise SipxError("length of x does not match the grid")
+            l0, y0 = [None if lst is None else _warm_start_arrays(lst, TF, rows) for lst in (l0, y0)]
+        rho = np.ascontiguousarray(rho_ini, np.float64)
+        feas = np.zeros(max(npp, 1))
+        # (m, x0, l0, y0 -- the converted copies among them -- live until this frame is left: across the call)
+        fn = getattr(lib(), ("sipx_reset" if again else "sipx_finalize") + ("_dev" if on_dev else ""))
+        _chk(fn(self.h, ptr(m), _ptr(rho), len(rho), C.c_double(gamma_ini), *(() if again else (int(feasibility_only),)),
+                int(zero_ini_guess), ptr(x0), _ptr_array(l0, ptr), _ptr_array(y0, ptr), _ptr(feas)))
+        if not again:
+            p, pp = C.c_int(), C.c_int()
+            _chk(lib().sipx_num_terms(self.h, C.byref(p), C.byref(pp)))
+            self.p, self.pp = p.value, pp.value
+            if self.p > npp:
+                self.rows.append(self.N)         # the distance term
         self.feasibility_initial = feas[:npp]
         return self.feasibility_initial
 
@@ -1002,8 +1008,7 @@ class Context:
                 dev = t.device
         if dev is not None:
             self.set_caller_stream(torch.cuda.current_stream(dev).cuda_stream)
-        _chk(lib().sipx_set_data_dev(self.h, int(i), None if lb is None else C.c_void_p(lb.data_ptr()),
-                                     None if ub is None else C.c_void_p(ub.data_ptr())))
+        _chk(lib().sipx_set_data_dev(self.h, int(i), _tensor_ptr(lb), _tensor_ptr(ub)))
 
     def io_bytes(self, reset=False):
         """(host-to-device, device-to-host) bytes of the N-sized transfers finalize, reset and download have made (sipx_io_bytes)."""
@@ -1011,49 +1016,13 @@ class Context:
         _chk(lib().sipx_io_bytes(self.h, C.byref(a), C.byref(b), int(bool(reset))))
         return a.value, b.value
 
-    def _dev_args(self, m, x0, l0, y0, rows_all):
-        import torch
-        dev = m.device
-        _check_tensor("m", m, self.TF, self.N, dev)
-        if x0 is not None:
-            _check_tensor("x", x0, self.TF, self.Nx, dev)
-        keep = [m, x0]
-
-        def ptr_list(name, lst):
-            if lst is None or len(lst) == 0:
-                return None
-            _check_tensor_list(name, lst, self.TF, rows_all, dev)
-            keep.extend(lst)
-            return (C.c_void_p * len(lst))(*[t.data_ptr() for t in lst])
-        self.set_caller_stream(torch.cuda.current_stream(dev).cuda_stream)
-        return (C.c_void_p(m.data_ptr()), None if x0 is None else C.c_void_p(x0.data_ptr()), ptr_list("l", l0), ptr_list("y", y0), keep)
-
     def finalize_dev(self, m, rho_ini, gamma_ini, feasibility_only=False, zero_ini_guess=True, x0=None, l0=None, y0=None):
         """finalize with m and the warm start as torch tensors on this context's GPU, ordered against torch's current stream."""
-        rho = np.ascontiguousarray(rho_ini, np.float64)
-        npp = len(self.rows)
-        feas = np.zeros(max(npp, 1))
-        rows_all = list(self.rows) + ([] if feasibility_only else [self.N])
-        mp, xp, lp, yp, keep = self._dev_args(m, x0, l0, y0, rows_all)
-        _chk(lib().sipx_finalize_dev(self.h, mp, rho.ctypes.data_as(C.c_void_p), len(rho), C.c_double(gamma_ini),
-                                     int(feasibility_only), int(zero_ini_guess), xp, lp, yp, feas.ctypes.data_as(C.c_void_p)))
-        p, pp = C.c_int(), C.c_int()
-        _chk(lib().sipx_num_terms(self.h, C.byref(p), C.byref(pp)))
-        self.p, self.pp = p.value, pp.value
-        if self.p > npp:
-            self.rows.append(self.N)
-        return feas[:npp]
+        return self._start(True, False, m, rho_ini, gamma_ini, feasibility_only, zero_ini_guess, x0, l0, y0)
 
     def reset_dev(self, m, rho_ini, gamma_ini, zero_ini_guess=True, x0=None, l0=None, y0=None):
         """reset with m and the warm start as torch tensors on this context's GPU, ordered against torch's current stream."""
-        rho = np.ascontiguousarray(rho_ini, np.float64)
-        npp = self.pp
-        feas = np.zeros(max(npp, 1))
-        mp, xp, lp, yp, keep = self._dev_args(m, x0, l0, y0, list(self.rows))
-        _chk(lib().sipx_reset_dev(self.h, mp, rho.ctypes.data_as(C.c_void_p), len(rho), C.c_double(gamma_ini),
-                                  int(zero_ini_guess), xp, lp, yp, feas.ctypes.data_as(C.c_void_p)))
-        self.feasibility_initial = feas[:npp]
-        return self.feasibility_initial
+        return self._start(True, True, m, rho_ini, gamma_ini, False, zero_ini_guess, x0, l0, y0)
 
     def download_dev(self, device, want_ly=True, out=None):
         """x, l, y as torch tensors on `device` (this context's GPU), written on the engine stream; torch's current stream waits
@@ -1075,17 +1044,14 @@ class Context:
                 _check_tensor_list(name, lst, self.TF, self.rows, device)
                 res.append(lst)
         x, l, y = res
-
-        def ptrs(lst):
-            return None if lst is None else (C.c_void_p * len(lst))(*[t.data_ptr() for t in lst])
         self.set_caller_stream(torch.cuda.current_stream(device).cuda_stream)
-        _chk(lib().sipx_download_dev(self.h, C.c_void_p(x.data_ptr()), ptrs(l), ptrs(y)))
+        _chk(lib().sipx_download_dev(self.h, _tensor_ptr(x), _ptr_array(l, _tensor_ptr), _ptr_array(y, _tensor_ptr)))
         return x, l, y
 
     # ---- phases ----
     def rhs_compose(self, rho):
         rho = np.ascontiguousarray(rho, np.float64)
-        _chk(lib().sipx_rhs_compose(self.h, rho.ctypes.data_as(C.c_void_p)))
+        _chk(lib().sipx_rhs_compose(self.h, _ptr(rho)))
 
     def argmin_x(self, it, tol_ref):
         t, ci, rr, fl = C.c_double(tol_ref), C.c_int64(), C.c_double(), C.c_int()
@@ -1095,9 +1061,7 @@ class Context:
     def update_y_l(self, it, flags, rho, gamma):
         rho = np.ascontiguousarray(rho, np.float64); gamma = np.ascontiguousarray(gamma, np.float64)
         rp, rd, fe = np.zeros(self.p), np.zeros(self.p), np.zeros(max(self.pp, 1))
-        _chk(lib().sipx_update_y_l(self.h, int(it), int(flags), rho.ctypes.data_as(C.c_void_p),
-                                   gamma.ctypes.data_as(C.c_void_p), rp.ctypes.data_as(C.c_void_p),
-                                   rd.ctypes.data_as(C.c_void_p), fe.ctypes.data_as(C.c_void_p)))
+        _chk(lib().sipx_update_y_l(self.h, int(it), int(flags), _ptr(rho), _ptr(gamma), _ptr(rp), _ptr(rd), _ptr(fe)))
         return rp, rd, fe[:self.pp]
 
     def log_scalars(self):
@@ -1107,13 +1071,12 @@ class Context:
 
     def adapt_rho_gamma(self, adjust_rho, adjust_gamma, rho, gamma):
         rho = np.array(rho, np.float64); gamma = np.array(gamma, np.float64)
-        _chk(lib().sipx_adapt_rho_gamma(self.h, int(adjust_rho), int(adjust_gamma), rho.ctypes.data_as(C.c_void_p),
-                                        gamma.ctypes.data_as(C.c_void_p)))
+        _chk(lib().sipx_adapt_rho_gamma(self.h, int(adjust_rho), int(adjust_gamma), _ptr(rho), _ptr(gamma)))
         return rho, gamma
 
     def q_update(self, rho_new, rho_old):
         a = np.ascontiguousarray(rho_new, np.float64); b = np.ascontiguousarray(rho_old, np.float64)
-        _chk(lib().sipx_q_update(self.h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        _chk(lib().sipx_q_update(self.h, _ptr(a), _ptr(b)))
 
     def download(self, want_ly=True, x_out=None):
         # the reference overwrites the x argument in place (cg.jl:95, PARSDMM.jl:64): a caller's array of the right kind is the
@@ -1125,15 +1088,7 @@ class Context:
             x = np.empty(self.Nx, self.TF)
         l = [np.zeros(r, self.TF) for r in self.rows] if want_ly else None
         y = [np.zeros(r, self.TF) for r in self.rows] if want_ly else None
-
-        def ptrs(lst):
-            if lst is None:
-                return None
-            a = (C.c_void_p * len(lst))()
-            for i, v in enumerate(lst):
-                a[i] = v.ctypes.data
-            return a
-        _chk(lib().sipx_download(self.h, _ptr(x), ptrs(l), ptrs(y)))
+        _chk(lib().sipx_download(self.h, _ptr(x), _ptr_array(l), _ptr_array(y)))
         return x, l, y
 
     def warm_start_from(self, coarse: "Context"):
@@ -1155,9 +1110,9 @@ class Context:
     def get_Q(self):
         d = C.c_int()
         offs = np.zeros(32, np.int64)
-        _chk(lib().sipx_get_Q(self.h, None, offs.ctypes.data_as(C.c_void_p), C.byref(d)))
+        _chk(lib().sipx_get_Q(self.h, None, _ptr(offs), C.byref(d)))
         Q = np.empty((self.Nx, d.value), self.TF, order="F")
-        _chk(lib().sipx_get_Q(self.h, _ptr(Q), offs.ctypes.data_as(C.c_void_p), C.byref(d)))
+        _chk(lib().sipx_get_Q(self.h, _ptr(Q), _ptr(offs), C.byref(d)))
         return Q, offs[:d.value].copy()
 
     def time_spmv(self, reps=20):
@@ -1167,7 +1122,7 @@ class Context:
 
     def debug_proj(self, set_index: int, which: int = 0):
         out = np.zeros(16)
-        _chk(lib().sipx_debug_proj(self.h, int(set_index), int(which), out.ctypes.data_as(C.c_void_p)))
+        _chk(lib().sipx_debug_proj(self.h, int(set_index), int(which), _ptr(out)))
         keys = ("need", "theta", "theta_prev", "hw", "spec_lo", "spec_hi", "lo", "hi", "asum", "vmax", "gathered",
                 "overflow", "spec_ok", "michelot_its", "refine", "lean")
         d = dict(zip(keys, out))
@@ -1248,6 +1203,32 @@ class Context:
         return self._log_result(lg, arrs)
 
 
+def _check_term_count(TD_OP, P_sub, options):
+    if len(TD_OP) != len(P_sub) + (0 if options.feasibility_only else 1):
+        raise SipxError("TD_OP must hold one operator per set plus the identity of the distance term "
+                        "(output of PARSDMM_precompute_distribute)")
+
+
+def _populate(ctx, AtA, TD_OP, set_Prop, P_sub, options) -> Context:
+    """The sets and the Q mode of a new context, which is closed when one of them is refused.  What is left is finalize."""
+    try:
+        for i, P in enumerate(P_sub):
+            A = AtA[i] if AtA is not None else None
+            ctx.add_set(TD_OP[i], P, set_Prop.ncvx[i], A, set_Prop.AtA_offsets[i] if A is not None else None)
+        ctx.set_q_mode(getattr(options, "Q_mode", "cds"))
+    except Exception:
+        ctx.close()
+        raise
+    return ctx
+
+
+def _start_values(options, TF, x=None, l=None, y=None):
+    """(rho_ini, gamma_ini, zero_ini_guess, warm start) as finalize and reset take them: the options in the working precision
+    (convert_options!.jl:6-15); with zero_ini_guess x, l, y are zero-filled (PARSDMM_initialize.jl:304-313) and not passed on."""
+    zero = bool(options.zero_ini_guess)
+    return [float(TF(r)) for r in options.rho_ini], float(TF(options.gamma_ini)), zero, (None, None, None) if zero else (x, l, y)
+
+
 def build_context(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x=None, l=None, y=None, device=None,
                   owned=None, attach=None) -> Context:
     """Everything PARSDMM_initialize allocates (src/PARSDMM_initialize.jl:117-230), on the device.  `attach(ctx)` is called
@@ -1255,30 +1236,42 @@ def build_context(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x=None, l=
     TF = np.dtype(m.dtype).type
     if not (np.isrealobj(m) and (x is None or np.isrealobj(x))):
         raise SipxError("input for PARSDMM is not real")                 # src/PARSDMM.jl:50-52
-    pp = len(P_sub)
-    p = len(TD_OP)
-    if (not options.feasibility_only and p != pp + 1) or (options.feasibility_only and p != pp):
-        raise SipxError("TD_OP must hold one operator per set plus the identity of the distance term "
-                        "(output of PARSDMM_precompute_distribute)")
-    ctx = Context(comp_grid, TF, device)
+    _check_term_count(TD_OP, P_sub, options)
+    ctx = _populate(Context(comp_grid, TF, device), AtA, TD_OP, set_Prop, P_sub, options)
     try:
-        for i in range(pp):
-            A = AtA[i] if AtA is not None else None
-            ctx.add_set(TD_OP[i], P_sub[i], set_Prop.ncvx[i], A, set_Prop.AtA_offsets[i] if A is not None else None)
         if owned is not None:
             ctx.set_owned(owned)
         if attach is not None:
             attach(ctx)
-        ctx.set_q_mode(getattr(options, "Q_mode", "cds"))
-        rho_ini = [float(TF(r)) for r in options.rho_ini]                # convert_options!.jl:6-15
-        zero = bool(options.zero_ini_guess)                               # x, l, y are zero-filled then (PARSDMM_initialize.jl:304-313)
-        feas0 = ctx.finalize(m, rho_ini, float(TF(options.gamma_ini)), options.feasibility_only,
-                             zero, None if zero else x, None if zero else l, None if zero else y)
-        ctx.feasibility_initial = feas0
+        rho_ini, gamma_ini, zero, warm = _start_values(options, TF, x, l, y)
+        ctx.finalize(m, rho_ini, gamma_ini, options.feasibility_only, zero, *warm)
     except Exception:
         ctx.close()
         raise
     return ctx
+
+
+def _solve(ctx, again, t0, m, options, x, l, y, outputs, out=None, dev=None):
+    """The whole solve on a populated context, for every front end: start (finalize, or reset when the context has been through
+    one: `again`), the native loop, the download -> (x, log, l, y).  dev = None: the host form (numpy arrays); a torch.device:
+    the device-resident form, tensors on that GPU and `out` the preallocated results.  t0: the clock at entry of the caller."""
+    import time
+    rho_ini, gamma_ini, zero, warm = _start_values(options, ctx.TF, x, l, y)
+    ctx._start(dev is not None, again, m, rho_ini, gamma_ini, options.feasibility_only, zero, *warm)
+    t_init = time.perf_counter() - t0
+    log, _ = ctx.parsdmm(options)
+    log.timing[TIMING_SECTIONS[0]] = t_init          # "initialization": PARSDMM_initialize (src/PARSDMM.jl:40)
+    want_ly = outputs == "all"
+    # the reference overwrites the x argument in place (PARSDMM.jl:64)
+    if dev is not None:
+        xo, lo, yo = ctx.download_dev(dev, want_ly, (x, None, None) if out is None and x is not None else out)
+    else:
+        xo, lo, yo = ctx.download(want_ly, x_out=x)
+        if isinstance(x, np.ndarray) and xo is not x and len(x) == len(xo):
+            x[:] = xo
+            xo = x
+    log.context_reused = again
+    return xo, log, lo, yo
 
 
 # Contexts kept between calls of PARSDMM (round 5).  The reference's callers wrap PARSDMM as a projector and call it again and again
@@ -1331,6 +1324,37 @@ def _context_key(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, device):
     return (dev, np.dtype(m.dtype).str, tuple(n), tuple(h), bool(options.feasibility_only), getattr(options, "Q_mode", "cds"), tuple(sig), env)
 
 
+class _CachedContext:
+    """The context of one call of a cached front end, `with _CachedContext(m, <the problem>, device) as slot`: slot.ctx is the
+    entry of _ctx_cache for this problem, taken out for the call (slot.reused), or a context built and populated now (m gives
+    the precision only).  When the body raises, the context is closed and forgotten.  Otherwise it goes (back) into the cache,
+    whose oldest entries make room for it; a problem that is not cached (no key) has its context closed."""
+
+    def __init__(self, m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, device):
+        self.limit = _cache_limit()
+        self.key = _context_key(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, device) if self.limit > 0 else None
+        self.ctx = _ctx_cache.pop(self.key, None) if self.key is not None else None
+        self.reused = self.ctx is not None
+        if not self.reused:
+            _check_term_count(TD_OP, P_sub, options)
+            self.ctx = _populate(Context(comp_grid, np.dtype(m.dtype).type, device), AtA, TD_OP, set_Prop, P_sub, options)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, etype, exc, tb):
+        if etype is not None:
+            if issubclass(etype, Exception):
+                self.ctx.close()
+        elif self.key is not None:
+            while len(_ctx_cache) >= self.limit:                 # the oldest entry goes (dicts keep insertion order)
+                _ctx_cache.pop(next(iter(_ctx_cache))).close()
+            _ctx_cache[self.key] = self.ctx
+        else:
+            self.ctx.close()
+        return False
+
+
 def PARSDMM(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x=None, l=None, y=None, device=None, outputs="all"):
     """Drop-in for src/PARSDMM.jl:25-258 (serial path): returns (x, log_PARSDMM, l, y).
     outputs="x": l and y are not copied back (returned as None) -- a caller that uses PARSDMM as a projector reads x only
@@ -1341,37 +1365,8 @@ def PARSDMM(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x=None, l=None, 
         raise SipxError("outputs must be 'all' or 'x'")
     if not (np.isrealobj(m) and (x is None or np.isrealobj(x))):
         raise SipxError("input for PARSDMM is not real")                 # src/PARSDMM.jl:50-52
-    limit = _cache_limit()
-    key = _context_key(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, device) if limit > 0 else None
-    ctx = _ctx_cache.pop(key, None) if key is not None else None
-    reused = ctx is not None
-    try:
-        if reused:
-            TF = np.dtype(m.dtype).type
-            zero = bool(options.zero_ini_guess)
-            rho_ini = [float(TF(r)) for r in options.rho_ini]
-            ctx.reset(m, rho_ini, float(TF(options.gamma_ini)), zero, None if zero else x, None if zero else l, None if zero else y)
-        else:
-            ctx = build_context(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x, l, y, device)
-        t_init = time.perf_counter() - t0
-        log, _ = ctx.parsdmm(options)
-        log.timing[TIMING_SECTIONS[0]] = t_init          # "initialization": PARSDMM_initialize (src/PARSDMM.jl:40)
-        xo, lo, yo = ctx.download(want_ly=(outputs == "all"), x_out=x)
-    except Exception:
-        if ctx is not None:
-            ctx.close()
-        raise
-    if key is not None:
-        while len(_ctx_cache) >= limit:                 # the oldest entry goes (dicts keep insertion order)
-            _ctx_cache.pop(next(iter(_ctx_cache))).close()
-        _ctx_cache[key] = ctx
-    else:
-        ctx.close()
-    log.context_reused = reused
-    if x is not None and xo is not x and len(x) == len(xo):
-        x[:] = xo                         # the reference overwrites the x argument in place
-        xo = x
-    return xo, log, lo, yo
+    with _CachedContext(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, device) as slot:
+        return _solve(slot.ctx, slot.reused, t0, m, options, x, l, y, outputs)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1408,6 +1403,26 @@ def _check_tensor_list(name, lst, TF, rows, device):
                         f"{len(lst) if isinstance(lst, (list, tuple)) else type(lst).__name__}")
     for i, t in enumerate(lst):
         _check_tensor(f"{name}[{i}]", t, TF, rows[i], device)
+
+
+def _check_device_args(m, x, l, y, out, TF, N, Nx, rows, outputs):
+    """The tensor arguments of a device-form solve: everything that can be wrong with them, before the library is touched or a
+    pointer is taken.  m names the device, the others live there."""
+    _check_tensor("m", m, TF, N, None)
+    dev = m.device
+    if x is not None:
+        _check_tensor("x", x, TF, Nx, dev)
+    for name, lst in (("l", l), ("y", y)):
+        if lst is not None:
+            _check_tensor_list(name, lst, TF, rows, dev)
+    if out is not None:
+        if not isinstance(out, (list, tuple)) or len(out) != 3:
+            raise SipxError("out must be (x, l, y): the result tensors (l, y may be None with outputs='x')")
+        if out[0] is not None:
+            _check_tensor("out x", out[0], TF, Nx, dev)
+        for name, lst in (("out l", out[1]), ("out y", out[2])):
+            if lst is not None and outputs == "all":
+                _check_tensor_list(name, lst, TF, rows, dev)
 
 
 def _check_array(name, a, TF, length):
@@ -1468,66 +1483,15 @@ def PARSDMM_device(m, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, x=None, l
     TF = _tensor_TF("m", m)
     n, _ = _grid(comp_grid)
     N = int(np.prod(n))
-    pp, p = len(P_sub), len(TD_OP)
-    if (not options.feasibility_only and p != pp + 1) or (options.feasibility_only and p != pp):
-        raise SipxError("TD_OP must hold one operator per set plus the identity of the distance term "
-                        "(output of PARSDMM_precompute_distribute)")
+    _check_term_count(TD_OP, P_sub, options)
     Nx = 2 * N if any(int(getattr(A, "component", 0)) for A in TD_OP) else N
-    rows = [int(A.shape[0]) for A in TD_OP]
-    dev = m.device
-    _check_tensor("m", m, TF, N, None)
-    if x is not None:
-        _check_tensor("x", x, TF, Nx, dev)
-    for name, lst in (("l", l), ("y", y)):
-        if lst is not None:
-            _check_tensor_list(name, lst, TF, rows, dev)
-    if out is not None:
-        if not isinstance(out, (list, tuple)) or len(out) != 3:
-            raise SipxError("out must be (x, l, y): the result tensors (l, y may be None with outputs='x')")
-        if out[0] is not None:
-            _check_tensor("out x", out[0], TF, Nx, dev)
-        for name, lst in (("out l", out[1]), ("out y", out[2])):
-            if lst is not None and outputs == "all":
-                _check_tensor_list(name, lst, TF, rows, dev)
+    _check_device_args(m, x, l, y, out, TF, N, Nx, [int(A.shape[0]) for A in TD_OP], outputs)
     import torch
     _check_one_hip_runtime()
-    device = dev.index if dev.index is not None else torch.cuda.current_device()
-    dev = torch.device("cuda", device)
-    limit = _cache_limit()
-    key = _context_key(np.empty(0, TF), AtA, TD_OP, set_Prop, P_sub, comp_grid, options, device) if limit > 0 else None
-    ctx = _ctx_cache.pop(key, None) if key is not None else None
-    reused = ctx is not None
-    zero = bool(options.zero_ini_guess)
-    rho_ini = [float(TF(r)) for r in options.rho_ini]
-    warm = (None, None, None) if zero else (x, l, y)
-    try:
-        if reused:
-            ctx.reset_dev(m, rho_ini, float(TF(options.gamma_ini)), zero, *warm)
-        else:
-            ctx = Context(comp_grid, TF, device)
-            for i in range(pp):
-                A = AtA[i] if AtA is not None else None
-                ctx.add_set(TD_OP[i], P_sub[i], set_Prop.ncvx[i], A, set_Prop.AtA_offsets[i] if A is not None else None)
-            ctx.set_q_mode(getattr(options, "Q_mode", "cds"))
-            ctx.feasibility_initial = ctx.finalize_dev(m, rho_ini, float(TF(options.gamma_ini)), options.feasibility_only, zero, *warm)
-        t_init = time.perf_counter() - t0
-        log, _ = ctx.parsdmm(options)
-        log.timing[TIMING_SECTIONS[0]] = t_init
-        if out is None and x is not None:
-            out = (x, None, None)                     # the reference overwrites the x argument in place
-        xo, lo, yo = ctx.download_dev(dev, want_ly=(outputs == "all"), out=out)
-    except Exception:
-        if ctx is not None:
-            ctx.close()
-        raise
-    if key is not None:
-        while len(_ctx_cache) >= limit:
-            _ctx_cache.pop(next(iter(_ctx_cache))).close()
-        _ctx_cache[key] = ctx
-    else:
-        ctx.close()
-    log.context_reused = reused
-    return xo, log, lo, yo
+    device = m.device.index if m.device.index is not None else torch.cuda.current_device()
+    # (the key of the host form: m stands in by its precision)
+    with _CachedContext(np.empty(0, TF), AtA, TD_OP, set_Prop, P_sub, comp_grid, options, device) as slot:
+        return _solve(slot.ctx, slot.reused, t0, m, options, x, l, y, outputs, out, torch.device("cuda", device))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1560,10 +1524,7 @@ class Solver:
     def __init__(self, AtA, TD_OP, set_Prop, P_sub, comp_grid, options, TF, device=None):
         self.TF = np.dtype(TF).type
         _dtype_code(self.TF)
-        pp, p = len(P_sub), len(TD_OP)
-        if (not options.feasibility_only and p != pp + 1) or (options.feasibility_only and p != pp):
-            raise SipxError("TD_OP must hold one operator per set plus the identity of the distance term "
-                            "(output of PARSDMM_precompute_distribute)")
+        _check_term_count(TD_OP, P_sub, options)
         for i, P in enumerate(P_sub):
             if not isinstance(P, Projector):
                 raise SipxError(f"P_sub[{i}] must be a Projector (the output of setup_constraints)")
@@ -1599,16 +1560,8 @@ class Solver:
     def _context(self, device):
         if self.ctx is None:
             self.device = _default_device if device is None else device
-            ctx = Context(self.comp_grid, self.TF, self.device)
-            try:
-                for i, P in enumerate(self.P_sub):
-                    A = self.AtA[i] if self.AtA is not None else None
-                    ctx.add_set(self.TD_OP[i], P, self.set_Prop.ncvx[i], A, self.set_Prop.AtA_offsets[i] if A is not None else None)
-                ctx.set_q_mode(getattr(self.options, "Q_mode", "cds"))
-            except Exception:
-                ctx.close()
-                raise
-            self.ctx = ctx
+            self.ctx = _populate(Context(self.comp_grid, self.TF, self.device), self.AtA, self.TD_OP, self.set_Prop, self.P_sub,
+                                 self.options)
         return self.ctx
 
     def set_data(self, i, lb=None, ub=None):
@@ -1663,23 +1616,7 @@ class Solver:
         opt, TF = self.options, self.TF
         on_dev = _is_tensor(m)
         if on_dev:
-            if _tensor_TF("m", m) != TF:
-                raise SipxError(f"m has dtype {m.dtype}: not the working precision ({np.dtype(TF).name})")
-            _check_tensor("m", m, TF, self.N, None)
-            dev = m.device
-            if x is not None:
-                _check_tensor("x", x, TF, self.N, dev)
-            for name, lst in (("l", l), ("y", y)):
-                if lst is not None:
-                    _check_tensor_list(name, lst, TF, self.rows, dev)
-            if out is not None:
-                if not isinstance(out, (list, tuple)) or len(out) != 3:
-                    raise SipxError("out must be (x, l, y): the result tensors (l, y may be None with outputs='x')")
-                if out[0] is not None:
-                    _check_tensor("out x", out[0], TF, self.N, dev)
-                for name, lst in (("out l", out[1]), ("out y", out[2])):
-                    if lst is not None and outputs == "all":
-                        _check_tensor_list(name, lst, TF, self.rows, dev)
+            _check_device_args(m, x, l, y, out, TF, self.N, self.N, self.rows, outputs)
             device = self._device_of(m)
         else:
             if not isinstance(m, np.ndarray):
@@ -1696,44 +1633,18 @@ class Solver:
                 if lst is not None and len(lst) and (len(lst) != len(self.rows) or any(_is_tensor(a) or np.shape(a) != (r,) for a, r in zip(lst, self.rows))):
                     raise SipxError(f"{name} needs one numpy vector per term (sets plus the distance term) with {self.rows} entries")
             device = self.device
-        zero = bool(opt.zero_ini_guess)
-        rho_ini = [float(TF(r)) for r in opt.rho_ini]
-        gamma = float(TF(opt.gamma_ini))
-        warm = (None, None, None) if zero else (x, l, y)
-        reused = self.built
         try:
+            dev = None
             if on_dev:
                 import torch
                 _check_one_hip_runtime()
-                ctx = self._context(device)
-                if reused:
-                    ctx.reset_dev(m, rho_ini, gamma, zero, *warm)
-                else:
-                    ctx.feasibility_initial = ctx.finalize_dev(m, rho_ini, gamma, self.feasibility_only, zero, *warm)
-            else:
-                ctx = self._context(device)
-                if reused:
-                    ctx.reset(m, rho_ini, gamma, zero, *warm)
-                else:
-                    ctx.feasibility_initial = ctx.finalize(m, rho_ini, gamma, self.feasibility_only, zero, *warm)
+                dev = torch.device("cuda", device)
+            res = _solve(self._context(device), self.built, t0, m, opt, x, l, y, outputs, out, dev)
             self.built = True
-            t_init = time.perf_counter() - t0
-            log, _ = ctx.parsdmm(opt)
-            log.timing[TIMING_SECTIONS[0]] = t_init          # "initialization": PARSDMM_initialize (src/PARSDMM.jl:40)
-            if on_dev:
-                if out is None and x is not None:
-                    out = (x, None, None)                     # the reference overwrites the x argument in place
-                xo, lo, yo = ctx.download_dev(torch.device("cuda", self.device), want_ly=(outputs == "all"), out=out)
-            else:
-                xo, lo, yo = ctx.download(want_ly=(outputs == "all"), x_out=x)
-                if x is not None and xo is not x and isinstance(x, np.ndarray) and len(x) == len(xo):
-                    x[:] = xo
-                    xo = x
         except BaseException:
             self.close()
             raise
-        log.context_reused = reused
-        return xo, log, lo, yo
+        return res
 
     def close(self):
         self.closed = True
@@ -1766,8 +1677,8 @@ def cds_spmv(R, offsets, x, device=None):
     off = np.ascontiguousarray(offsets, np.int64)
     x = np.ascontiguousarray(x)
     y = np.empty_like(x)
-    _chk(lib().sipx_cds_spmv(_dtype_code(TF), C.c_int64(R.shape[0]), int(R.shape[1]), _ptr(R),
-                             off.ctypes.data_as(C.c_void_p), _ptr(x), _ptr(y), device))
+    _chk(lib().sipx_cds_spmv(_dtype_code(TF), C.c_int64(R.shape[0]), int(R.shape[1]), _ptr(R), _ptr(off),
+                             _ptr(x), _ptr(y), device))
     return y
 
 

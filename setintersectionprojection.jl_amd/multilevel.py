@@ -193,8 +193,8 @@ def PARSDMM_multi_level(m, TD_OP_levels, AtA_levels, P_sub_levels, set_Prop_leve
                 options.zero_ini_guess = False
             if cached is not None:
                 ctx = cached[i]
-                TF = np.dtype(m.dtype).type
-                ctx.reset(m_levels[i], [float(TF(r)) for r in options.rho_ini], float(TF(options.gamma_ini)), True)
+                rho_ini, gamma_ini = host._start_values(options, np.dtype(m.dtype).type)[:2]
+                ctx.reset(m_levels[i], rho_ini, gamma_ini, True)
             else:
                 ctx = host.build_context(m_levels[i], AtA_levels[i], TD_OP_levels[i], set_Prop_levels[i], P_sub_levels[i],
                                          comp_grid_levels[i], options, x if host_transfers else None, l if host_transfers else None,
