@@ -97,7 +97,14 @@ enum {
                                 forward differences that start at p (0 to ndim members).  op must be SIPX_OP_TV, mode WHOLE, transform
                                 NONE, pmax = tau > 0.  Group norms from a float64 sum of squares rounded once to TF, the threshold of
                                 SIPX_PROJ_L1 on the N group norms, every member scaled by max(g - theta, 0) / g; an input inside the
-                                ball is not written (csrc/l21.h).  Holds no replaceable vectors (sipx_set_data refuses).  Contexts
+                                ball is not written (csrc/l21.h).  Holds no replaceable vectors (sipx_set_data refuses).
+                                WEIGHTS (mode WHOLE, op TV or TV_XY; SIPX_PROJ_L21_JOINT alike): lb = TF[groups] (N grid points in
+                                column-major order; the joint set: n1 n2 pixels), reserved = their number, ub = NULL, makes the set
+                                { v : sum_p w_p ||v_p||_2 <= pmax }: group p is shrunk by theta w_p, theta from a weighted Michelot
+                                iteration of its own; w_p = 0 leaves group p unconstrained and unwritten; a weight that is negative,
+                                NaN or infinite is refused by every host path and counts as 0 from device memory
+                                (csrc/l21_weighted.h).  sipx_set_data(_dev) replaces the weights (lb; ub refused);
+                                sipx_l21_weighted_norm observes the weighted norm.  The per-frame mode takes no weights.  Contexts
                                 with a communicator, a slab decomposition or set ownership refuse it.  sipx_project takes the
                                 M-vector of the TV range in the reference's row order on the context's grid; sipx_l21_norm observes
                                 the norm.
@@ -145,10 +152,11 @@ typedef struct {
   int32_t proj;      /* SIPX_PROJ_* */
   double pmin, pmax; /* constraint[i].min / .max (set_definitions, src/SetIntersectionProjection.jl:142-149) */
   const void* lb;    /* BOUNDS_VEC / HISTOGRAM: host TF vectors (see the kinds above); L1 / L2 / ANNULUS in mode FIBER / SLICE: NULL or
-                        the radii per segment, TF[nseg]; else NULL */
+                        the radii per segment, TF[nseg]; L21 in mode WHOLE / L21_JOINT: NULL or one weight per group (lb alone, and
+                        `reserved` holds their number); else NULL */
   const void* ub;
   int32_t ncvx;      /* set_Prop.ncvx[i] (src/setup_constraints.jl:89-97) */
-  int32_t reserved;  /* 0 */
+  int32_t reserved;  /* 0; a weighted L21 / L21_JOINT set: the entries of lb, refused unless it is the group count */
   int32_t mode;      /* SIPX_MODE_* */
   int32_t dir;       /* direction of the fibers / normal of the slices */
   const void* basis; /* SUBSPACE: host TF[basis_rows x basis_cols], column-major (constraint.custom_TD_OP[1]) */
@@ -394,6 +402,14 @@ int sipx_l21_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, 
  * sipx_l21_norm_dev against the caller's stream.  Refused where the set is refused (2-D grids, sharded contexts). */
 int sipx_l21_joint_norm(sipx_ctx* ctx, const void* x, void* out);
 int sipx_l21_joint_norm_dev(sipx_ctx* ctx, const void* x, void* out);
+/* The weighted total variation of x: *out = one TF, (TF) sum_p w_p g_p over the groups of SIPX_PROJ_L21 behind op (SIPX_OP_TV or
+ * SIPX_OP_TV_XY; joint = 0, w TF[N] in the grid's column-major point order) or of SIPX_PROJ_L21_JOINT (joint != 0, op SIPX_OP_TV_XY, w
+ * TF[n1 n2] in pixel order), summed by the first pass of the weighted projector (csrc/l21_weighted.h).  CONTRACT: the value is the
+ * very number that projector compares with pmax, so a radius observed on x leaves A x unwritten.  x, w, out: host memory, a weight
+ * that is negative, NaN or infinite is refused; the _dev form takes all three in device memory of the context's GPU, ordered like
+ * sipx_l21_norm_dev against the caller's stream, and there such a weight counts as 0.  Refused where the set is refused. */
+int sipx_l21_weighted_norm(sipx_ctx* ctx, int op, int joint, const void* x, const void* w, void* out);
+int sipx_l21_weighted_norm_dev(sipx_ctx* ctx, int op, int joint, const void* x, const void* w, void* out);
 /* nearest-neighbour resampling of an array of shape nc to shape nf, the grid transfer of PARSDMM_multi_level:
  * out[k] = in[round(1 + (k-1)(nc-1)/(nf-1))] per axis (Interpolations.BSpline(Constant()) evaluated on
  * range(1, stop=nc, length=nf); src/PARSDMM_multi_level.jl:41-45,61-65, src/interpolate_y_l.jl:32-88) */

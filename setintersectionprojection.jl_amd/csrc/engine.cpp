@@ -857,7 +857,7 @@ class Engine : public EngineBase {
       s.spec.ub = s.host_ub.empty() ? nullptr : s.host_ub.data();
       s.spec.basis = s.host_basis.empty() ? nullptr : s.host_basis.data();
       s.ext = std::make_shared<ExtProj<T>>(s.spec, stream_);
-      if (s.ext_kind == EXT_HISTOGRAM || s.seg_radii) {
+      if (s.ext_kind == EXT_HISTOGRAM || s.seg_radii || s.weighted) {
         s.host_lb.clear(); s.host_ub.clear();
         if (s.pend_lb || s.pend_ub) s.ext->set_data(s.pend_lb, s.pend_ub, true);
       }
@@ -2934,16 +2934,19 @@ class Engine : public EngineBase {
       throw std::runtime_error(what + ": set index " + std::to_string(set) + " out of range (" + std::to_string(nsets) + " sets)");
     SetState<T>& s = sets_[set];
     if (s.comp) throw std::runtime_error(what + " is not available for Minkowski sets" + way_out);
-    const bool bounds = !s.ext_kind && s.prox == SIPX_PROJ_BOUNDS_VEC, hist = s.ext_kind == EXT_HISTOGRAM || s.seg_radii;
+    const bool bounds = !s.ext_kind && s.prox == SIPX_PROJ_BOUNDS_VEC, hist = s.ext_kind == EXT_HISTOGRAM || s.seg_radii || s.weighted;
     if (!bounds && !hist)
       throw std::runtime_error(what + ": set " + std::to_string(set) + " holds no replaceable vectors -- element-wise and per-fiber bounds "
                                "(no transform), the relaxed histogram and per-fiber / per-slice l1, l2 and annulus sets built with a "
-                               "vector of radii do; scalars, vector bounds behind the DCT, the DFT mask and "
+                               "vector of radii do, and the l2,1 sets built with weights; scalars, vector bounds behind the DCT, the DFT mask and "
                                "subspace bases are fixed at sipx_add_set" + way_out);
     if (s.seg_radii && lb && s.ext_kind != EXT_ANNULUS_SEG)
       throw std::runtime_error(what + ": only the annulus has inner radii (lb); the radii of an l1 / l2 set are its ub");
+    if (s.weighted && ub)
+      throw std::runtime_error(what + ": the weights of an l2,1 set are its lb; it has no ub (the radius is fixed at sipx_add_set)");
     const ConfigCtx ctx = config_ctx();
     const long long len = data_len(ctx, s);
+    if (s.weighted && lb && !on_device) check_l21_weights((const T*)lb, len, s.ext_kind == EXT_L21_JOINT ? "l21_joint" : "l21");
     if (s.seg_radii && (s.ext_kind == EXT_L1_SEG || s.ext_kind == EXT_L21_SEG) && ub && !on_device) check_l1_radii((const T*)ub, len);
     if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
       throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
@@ -3314,6 +3317,7 @@ class Engine : public EngineBase {
       throw std::runtime_error(std::string("the l2,1 ball projects a vector of the ") + (d->op == SIPX_OP_TV ? "TV" : "TV_xy") + " range: " +
                                std::to_string(st.Mtrue) + " entries on this grid, " + std::to_string((long long)len) + " given");
     st.spec.ub = st.host_ub.empty() ? nullptr : st.host_ub.data();      // (per frame: one radius each)
+    st.spec.lb = st.weighted ? st.host_lb.data() : nullptr;             // (weighted: one weight per group)
     DeviceMemory tmp;
     T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
     const SearchScratch q(tmp, G_.N, false);
@@ -3357,6 +3361,39 @@ class Engine : public EngineBase {
       ext.observe(dv, dout, q.part, q.mp, q.dc);
     }
     finish_call(on_device, out, dout, nout);
+  }
+
+  // sipx_l21_weighted_norm(_dev): (T) sum_p w_p g_p of the weighted (op, joint) set on A x, by the observe() of a throw-away projector
+  // of that set: its norms launch and the first pass of its iteration (l21_weighted.h)
+  void l21_weighted_norm(int op, bool joint, const void* x, const void* w, void* out, bool on_device) override {
+    if (!x || !w || !out) throw std::runtime_error("weighted l2,1 norm: x, w and out are needed");
+    SIPX_HIP(hipSetDevice(device_));
+    if (joint && op != SIPX_OP_TV_XY) throw std::runtime_error(L21_JOINT_ROUTE);
+    if (op != SIPX_OP_TV && op != SIPX_OP_TV_XY)
+      throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, op);
+    if (op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
+    sipx_set_desc d{};
+    d.op = op; d.proj = joint ? SIPX_PROJ_L21_JOINT : SIPX_PROJ_L21; d.mode = SIPX_MODE_WHOLE; d.pmax = 1.0;
+    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the unweighted set
+    const long long ng = l21_groups(ctx, s.ext_kind);
+    if (!on_device) check_l21_weights((const T*)w, ng, joint ? "l21_joint" : "l21");
+    s.spec.weighted = 1;
+    s.spec.lb = on_device ? nullptr : w;
+    DeviceMemory tmp;
+    const OpScratch ws = forward_scratch(tmp, s, on_device);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
+    ExtProj<T> ext(s.spec, stream_);
+    const T* dv = queue_forward(ws, s, x, on_device);     // (device x, w: the engine stream is behind the caller's from here on)
+    if (on_device) ext.set_data((const T*)w, nullptr, true);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 1) * G_.N * sizeof(T));
+      ext.observe(dv, dout, nullptr, nullptr, nullptr);
+    }
+    finish_call(on_device, out, dout, 1);
   }
 
   void project(const sipx_set_desc* d, void* v, int64_t len) override {
@@ -3579,7 +3616,17 @@ class Engine : public EngineBase {
       fc[0] += c[0]; fc[1] = std::max(fc[1], c[1]); fc[3] += c[3];
     }
     o += ", \"l21_frames\": {\"passes_total\": " + std::to_string(fc[0]) + ", \"passes_max\": " + std::to_string(fc[1]) +
-         ", \"frames\": " + std::to_string(fc[3]) + "}}";
+         ", \"frames\": " + std::to_string(fc[3]) + "}";
+    // weighted l2,1 sets: the Michelot passes and the flag reads of the last projection (summed over such sets), their calls and groups
+    long long wc[4] = {0, 0, 0, 0};
+    for (const auto& st : sets_) {
+      if (!st.ext || !st.weighted) continue;
+      long long c[4];
+      st.ext->route_counts(c);
+      for (int q = 0; q < 4; ++q) wc[q] += c[q];
+    }
+    o += ", \"l21_weighted\": {\"passes\": " + std::to_string(wc[0]) + ", \"flag_reads\": " + std::to_string(wc[1]) +
+         ", \"calls\": " + std::to_string(wc[2]) + ", \"groups\": " + std::to_string(wc[3]) + "}}";
     if (!peek) start_stats(enable);
     return o.c_str();
   }

@@ -12,12 +12,15 @@
 // are 16-byte aligned and the VW points lie on one grid line), one point otherwise.  g lives in the projector's own memory.
 // The ball whose groups span the frames (EXT_L21_JOINT, l21_joint.h) is the same projector with norms kernels of its own and L = n1 n2
 // entries of g; the ball of every z-slice of TV_xy (EXT_L21_SEG, l21_seg.h, FrameProj) has k_l21_frames in place of the search.
+// Built with one weight per group (ExtSpec::weighted, l21_weighted.h) BallProj takes a route of its own after the norms launch: Michelot
+// passes k_l21w_part / k_l21w_finish in batches gated on a device flag, then k_l21w_scale; without weights not one launch differs.
 // Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the two projectors.
 // A projector's observe() runs the norms launch and the first sum of its own project(): what it reports is what project() decides on.
 #include "ext_family.h"
 #include "l21.h"
 #include "l21_joint.h"
 #include "l21_seg.h"
+#include "l21_weighted.h"
 
 namespace sipx {
 
@@ -152,6 +155,130 @@ __global__ __launch_bounds__(BLOCK) void k_l21_theta_final(int nparts, unsigned 
 template <typename T>
 __global__ void k_l21_pick(const ProjScalars<T>* __restrict__ ps, T* __restrict__ out) {
   if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = (T)ps->asum;
+}
+
+// ---- the weighted ball (l21_weighted.h): one weight per group, EXT_L21 and EXT_L21_JOINT built with ExtSpec::weighted ---------------------
+//     k_l21w_part     one Michelot pass: the sums (S, C, count) of the groups in A_k, one partial per workgroup   reads 2 n words
+//     k_l21w_finish   one workgroup: the partials in the same tree, then l21w_start / l21w_step on the device state
+//     k_l21w_scale    k_l21_scale with w read alongside g; groups of weight 0 are skipped without a load or a store of v
+// Both pass kernels return at once when the state says done, so the host enqueues them in batches and reads one word per batch
+// (BallProj::weighted_search).  FIRST: the pass over every group, which also gives asum and the decision; the state is not read.
+constexpr int L21W_GRID = 1024;        // most workgroups of a pass: four per compute unit, 5 doubles of partials each
+constexpr int L21W_LOADS = 4;          // loads of g and of w a lane issues before it uses the first (16 bytes or one entry each)
+constexpr int L21W_BATCH = 8;          // passes enqueued per read of the flag
+// entries one sweep of the pass kernel's unrolled loop covers at full grid: beyond it a thread takes a second round
+template <typename T>
+constexpr long long l21w_sweep(bool wide) { return (long long)L21W_GRID * BLOCK * L21W_LOADS * (wide ? l21_vec_width<T>() : 1); }
+
+template <typename T, int VW, bool FIRST>
+__global__ __launch_bounds__(BLOCK) void k_l21w_part(unsigned n, const T* __restrict__ g, const T* __restrict__ w,
+                                                     const L21WState* __restrict__ st, double* __restrict__ part) {
+  if (!FIRST && st->done) return;
+  __shared__ double red[5 * BLOCK];
+  const double th = FIRST ? 0.0 : st->theta;
+  const unsigned nvec = n / VW, step = gridDim.x * BLOCK;
+  L21WSums a;
+  auto take = [&](const Vec<T, VW>& gv, const Vec<T, VW>& wv) {
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      const T wk = l21w_clean<T>(wv.v[k]);
+      if (FIRST || l21w_active<T>(gv.v[k], wk, th)) l21w_add<T>(a, gv.v[k], wk);
+    }
+  };
+  unsigned vi = blockIdx.x * BLOCK + threadIdx.x;
+  for (; vi + (L21W_LOADS - 1) * step < nvec; vi += L21W_LOADS * step) {
+    Vec<T, VW> gv[L21W_LOADS], wv[L21W_LOADS];
+#pragma unroll
+    for (int u = 0; u < L21W_LOADS; ++u) {
+      gv[u] = ldv<T, VW>(g + (size_t)(vi + u * step) * VW);
+      wv[u] = ldv<T, VW>(w + (size_t)(vi + u * step) * VW);
+    }
+#pragma unroll
+    for (int u = 0; u < L21W_LOADS; ++u) take(gv[u], wv[u]);
+  }
+  for (; vi < nvec; vi += step) take(ldv<T, VW>(g + (size_t)vi * VW), ldv<T, VW>(w + (size_t)vi * VW));
+  l21w_tree<BLOCK>(a, red);
+  if (threadIdx.x == 0) {
+    double* o = part + 5 * (size_t)blockIdx.x;
+    o[0] = a.S.hi; o[1] = a.S.lo; o[2] = a.C.hi; o[3] = a.C.lo; o[4] = a.cnt;
+  }
+}
+// flag[0] <- the passes so far once the iteration is done, 0 before: the one word the host reads
+template <typename T, bool FIRST>
+__global__ __launch_bounds__(BLOCK) void k_l21w_finish(int nparts, T tau, const double* __restrict__ part, L21WState* __restrict__ st,
+                                                       T* __restrict__ theta, int* __restrict__ flag) {
+  if (!FIRST && st->done) return;
+  __shared__ double red[5 * BLOCK];
+  L21WSums a;
+  for (int b = threadIdx.x; b < nparts; b += BLOCK) {
+    const double* o = part + 5 * (size_t)b;
+    L21WSums x;
+    x.S = L21Sum{o[0], o[1]}; x.C = L21Sum{o[2], o[3]}; x.cnt = o[4];
+    l21w_merge(a, x);
+  }
+  l21w_tree<BLOCK>(a, red);
+  if (threadIdx.x == 0) {
+    L21WState s{};
+    T th = T(0);
+    if constexpr (FIRST) {
+      l21w_start<T>(s, th, a, tau);
+    } else {
+      s = *st;
+      l21w_step<T>(s, th, a, tau);
+    }
+    *st = s;
+    if (s.done) theta[0] = th;
+    flag[0] = s.done ? s.passes : 0;
+  }
+}
+template <typename T>
+__global__ void k_l21w_pick(const L21WState* __restrict__ st, T* __restrict__ out) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = (T)st->asum;
+}
+template <typename T, int NBLK, int VW, bool JOINT>
+__global__ __launch_bounds__(BLOCK) void k_l21w_scale(L21Args a, T* __restrict__ v, const T* __restrict__ g, const T* __restrict__ w,
+                                                      const L21WState* __restrict__ st, const T* __restrict__ theta) {
+  if (!st->need) return;
+  const T th = theta[0];
+  const unsigned nvec = (unsigned)(a.G.N / VW), step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    const Coord c = coords(a.G, (long long)p);
+    const unsigned gi = JOINT ? p - (unsigned)c.k * (unsigned)a.G.st[2] : p;
+    const Vec<T, VW> wv = ldv<T, VW>(w + gi);
+    T wk[VW];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      wk[k] = l21w_clean<T>(wv.v[k]);
+      any = any || wk[k] > T(0);
+    }
+    if (!any) continue;                // groups of weight 0: f = 1, nothing to do
+    const Vec<T, VW> gv = ldv<T, VW>(g + gi);
+    T f[VW];
+#pragma unroll
+    for (int k = 0; k < VW; ++k) f[k] = l21w_factor<T>(gv.v[k], wk[k], th);
+#pragma unroll
+    for (int q = 0; q < NBLK; ++q) {
+      bool mem[VW];
+      l21_members<VW>(a, c, q, mem);
+      T* vq = v + (size_t)q * (size_t)a.bstride + p;
+      Vec<T, VW> x = ldv<T, VW>(vq);
+      bool all = true;
+#pragma unroll
+      for (int k = 0; k < VW; ++k) {
+        x.v[k] = wk[k] > T(0) ? x.v[k] * f[k] : x.v[k];      // (weight 0 beside a weighted neighbour: its own bits are stored back)
+        all = all && mem[k];
+      }
+      if (all) {
+        stv<T, VW>(vq, x);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VW; ++k)
+          if (mem[k] && wk[k] > T(0)) vq[k] = x.v[k];
+      }
+    }
+  }
 }
 
 // ---- EXT_L21_JOINT: the l2,1 ball whose groups span the frames, on the range of TV_xy (l21_joint.h) ---------------------------------------
@@ -338,7 +465,16 @@ struct BallProj : ExtImpl<T> {
   T* theta = nullptr;                  // Float64: the threshold k_l21_scale applies
   SearchState<T> search;
   ProjScalars<T>* ps_obs = nullptr;    // the state of observe's search, taken at its first call
+  // the weighted route (l21_weighted.h), taken when the spec carries weights: none of the members above but g and part is used
+  T* w = nullptr;                      // one weight per group
+  L21WState* wst = nullptr;            // the state of the iteration
+  double* wpart = nullptr;             // the partials of a pass, 5 per workgroup
+  T* wtheta = nullptr;                 // theta in T, written when the iteration is done
+  int* wflag = nullptr;                // device: 0, or the passes once done
+  int* h_flag = nullptr;               // pinned: where the host reads it
+  long long last_passes = 0, last_reads = 0, calls = 0;
   void reset() override { search.reinit(stream); }
+  ~BallProj() override { if (h_flag) (void)hipHostFree(h_flag); }
   BallProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s), joint(spec.kind == EXT_L21_JOINT) {
     if (joint) l21_joint_check_spec(sp);
     else l21_check_spec(sp);
@@ -347,6 +483,17 @@ struct BallProj : ExtImpl<T> {
     g = this->template alloc<T>(n);
     const int nchunk = joint ? l21_joint_plan(n, sp.G.n[2], (int)sizeof(T)).nchunk : 1;
     if (nchunk > 1) part = this->template alloc<double>((size_t)nchunk * n);
+    if (sp.weighted) {
+      w = this->template alloc<T>(n);
+      wst = this->template alloc<L21WState>(1);
+      wpart = this->template alloc<double>(5 * L21W_GRID);
+      wtheta = this->template alloc<T>(1);
+      wflag = this->template alloc<int>(1);
+      SIPX_HIP(hipHostMalloc((void**)&h_flag, sizeof(int), hipHostMallocDefault));
+      if (sp.lb) SIPX_HIP(hipMemcpy(w, sp.lb, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+      else SIPX_HIP(hipMemsetAsync(w, 0, sizeof(T) * (size_t)n, s));      // (set_data brings them; until then no group is constrained)
+      return;
+    }
     if (sizeof(T) == 8) {
       tpart = this->template alloc<double>(3 * L21_THETA_GRID);
       theta = this->template alloc<T>(1);
@@ -363,8 +510,68 @@ struct BallProj : ExtImpl<T> {
       SIPX_HIP(hipGetLastError());
     }
   }
+  // ---- the weighted route ----
+  // one pass: the partial kernel and the one-workgroup finish (both return at once when the state says done)
+  template <bool FIRST>
+  void weighted_pass(T tau) {
+    constexpr int W = l21_vec_width<T>();
+    const bool wide = sp.G.n[0] % 4 == 0 && aligned16(g, w);
+    const int grid = fit_grid((n / (wide ? W : 1) + L21W_LOADS - 1) / L21W_LOADS, L21W_GRID);
+    void (*const k)(unsigned, const T*, const T*, const L21WState*, double*) = wide ? k_l21w_part<T, W, FIRST> : k_l21w_part<T, 1, FIRST>;
+    {
+      ObsScope obs(KID_L21W_PASS, stream, 2.0 * n * sizeof(T));
+      hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)n, g, w, wst, wpart);
+    }
+    hipLaunchKernelGGL((k_l21w_finish<T, FIRST>), dim3(1), dim3(BLOCK), 0, stream, grid, tau, wpart, wst, wtheta, wflag);
+    SIPX_HIP(hipGetLastError());
+  }
+  // the iteration on (g, w): passes in batches of L21W_BATCH, one 4-byte read of the flag per batch; more than n + 1 passes is an error
+  void weighted_search(T tau) {
+    weighted_pass<true>(tau);
+    long long queued = 1;
+    last_reads = 0;
+    for (;;) {
+      for (; queued % L21W_BATCH != 0; ++queued) weighted_pass<false>(tau);
+      SIPX_HIP(hipMemcpyAsync(h_flag, wflag, sizeof(int), hipMemcpyDeviceToHost, stream));
+      SIPX_HIP(hipStreamSynchronize(stream));
+      ++last_reads;
+      if (*h_flag) break;
+      if (queued > n + 1) throw std::runtime_error("the weighted l2,1 ball: the threshold iteration did not end within n + 1 passes");
+      weighted_pass<false>(tau);
+      ++queued;
+    }
+    last_passes = *h_flag;
+    ++calls;
+  }
+  void weighted_scale(T* v) {
+    constexpr int W = l21_vec_width<T>();
+    const bool wide = l21_wide(sp, v, g) && aligned16(w);
+    void (*const k)(L21Args, T*, const T*, const T*, const L21WState*, const T*) =
+        joint           ? (wide ? k_l21w_scale<T, 2, W, true> : k_l21w_scale<T, 2, 1, true>)
+        : sp.nblk == 2  ? (wide ? k_l21w_scale<T, 2, W, false> : k_l21w_scale<T, 2, 1, false>)
+                        : (wide ? k_l21w_scale<T, 3, W, false> : k_l21w_scale<T, 3, 1, false>);
+    ObsScope obs(KID_L21W_SCALE, stream, (2.0 * sp.nblk * sp.G.N + 2.0 * n) * sizeof(T));
+    hipLaunchKernelGGL(k, dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream, l21_args(sp), v, g, w, wst, wtheta);
+    SIPX_HIP(hipGetLastError());
+  }
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    if (!w) ExtImpl<T>::set_data(new_lb, new_ub, on_device);
+    if (new_ub) throw std::runtime_error("the weighted l2,1 ball: the weights are its lb, it has no ub (the radius is fixed at sipx_add_set)");
+    if (new_lb) SIPX_HIP(hipMemcpyAsync(w, new_lb, sizeof(T) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  }
+  // the passes of the last call (the first included), the reads of the flag it took, the calls so far, the groups
+  void route_counts(long long out[4]) const override {
+    out[0] = last_passes; out[1] = last_reads; out[2] = calls; out[3] = w ? n : 0;
+  }
+
   void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
     const double N = (double)sp.G.N;
+    if (w) {
+      l21_norms<T>(stream, sp, v, g, part);
+      weighted_search((T)sp.pmax);
+      weighted_scale(v);
+      return;
+    }
     ProjScalars<T>* ps = search.pick(feas);
     l21_norms<T>(stream, sp, v, g, part);
     threshold(ps, partials, maxpart, compact);
@@ -374,6 +581,13 @@ struct BallProj : ExtImpl<T> {
   // out[0] <- the sum of the group norms as project decides on it: its norms launch into its g, then the first pass of a search with
   // a new state and an infinite radius -- the sum, and the rounding to T, that project compares with the radius.  The warm starts stay.
   void observe(const T* v, T* out, double* partials, T* maxpart, T* compact) override {
+    if (w) {                // the weighted norm: the norms launch and the first pass of project(), (T)asum as that pass compares it
+      l21_norms<T>(stream, sp, v, g, part);
+      weighted_pass<true>((T)INFINITY);
+      hipLaunchKernelGGL((k_l21w_pick<T>), dim3(1), dim3(64), 0, stream, wst, out);
+      SIPX_HIP(hipGetLastError());
+      return;
+    }
     if (!ps_obs) ps_obs = this->template alloc<ProjScalars<T>>(1);
     l21_norms<T>(stream, sp, v, g, part);
     K<T>::ps_init(stream, ps_obs, nullptr);

@@ -35,6 +35,8 @@ struct ExtSpec {
   int nblk = 0;                   // EXT_L21(_SEG): blocks of the operator (2 or 3), block q at v + q * bstride holding the differences along bdir[q]
   long long bstride = 0;
   int bdir[3] = {0, 0, 0};
+  int weighted = 0;               // EXT_L21 (whole array) / EXT_L21_JOINT: 1: one weight per group (l21_weighted.h) -- lb: host TF[groups], or
+                                  // nullptr: set_data brings them before the first projection
 };
 
 template <typename T>

@@ -9,6 +9,7 @@
 
 #include "dwt.h"
 #include "ext_family.h"      // (sipx.h, sipx_common.h, ext_proj.h; make_segmap / seg_count)
+#include "l21_weighted.h"    // (the host checks of the weighted l2,1 sets)
 
 namespace sipx {
 
@@ -70,6 +71,7 @@ struct SetConfig {
   int bmode = SIPX_MODE_WHOLE, bdir = 0;   // SIPX_PROJ_BOUNDS_VEC: one bound per row (WHOLE) or per coordinate along bdir (FIBER)
   int ext_kind = 0;                  // projector acting on a materialised vector (ext_proj.h)
   bool seg_radii = false;            // EXT_L1_SEG / L2_SEG / ANNULUS_SEG built with one radius per segment (host_lb / host_ub, then the projector's)
+  bool weighted = false;             // EXT_L21 (whole array) / EXT_L21_JOINT built with one weight per group in lb (host_lb, then the projector's)
   ExtSpec spec;
   std::vector<T> host_basis;
   std::vector<long long> ata_off;
@@ -115,6 +117,9 @@ void check_l1_radii(const T* r, long long n) {
   for (long long k = 0; k < n; ++k)
     if (!(r[k] > T(0))) throw std::runtime_error("Radius of L1 ball is negative (segment " + std::to_string(k) + ")");
 }
+
+// the groups of a weighted l2,1 set (l21_weighted.h): the grid points of EXT_L21, the pixels of EXT_L21_JOINT
+inline long long l21_groups(const ConfigCtx& c, int ext_kind) { return ext_kind == EXT_L21_JOINT ? c.G.st[2] : c.G.N; }
 
 template <typename T>
 void configure_op(const ConfigCtx& c, SetConfig<T>& s, int op) {
@@ -274,6 +279,17 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
   } else if (d->transform != SIPX_TRANSFORM_NONE) {
     throw std::runtime_error("unknown transform");
   }
+  // one weight per group in lb (l21_weighted.h): EXT_L21 on the whole array and EXT_L21_JOINT
+  // (the refusals of the weighted sets are worded in l21_weighted.h, beside the rule)
+  auto weights = [&](const char* set) {
+    const long long n = l21_groups(c, s.ext_kind);
+    l21w_check_desc(set, d->lb != nullptr, d->ub != nullptr, d->reserved, n, s.ext_kind == EXT_L21_JOINT);      // (reserved: the entries lb holds)
+    if (!d->lb) return;
+    check_l21_weights((const T*)d->lb, n, set);
+    s.weighted = true;
+    s.spec.weighted = 1;
+    s.host_lb.assign((const T*)d->lb, (const T*)d->lb + n);
+  };
   switch (d->proj) {
     case SIPX_PROJ_BOUNDS:
       if (mode != SIPX_MODE_WHOLE) throw std::runtime_error("scalar bounds apply to the whole array (use per-fiber vectors)");
@@ -346,7 +362,9 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       if (mode == SIPX_MODE_WHOLE) {
         if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
         ext(EXT_L21);
-      } else {                 // per frame on TV_xy (checked above): the scalar, or one radius per frame in ub
+        weights("l21");
+      } else {
+        if (d->lb) l21w_refuse_frames();                 // per frame on TV_xy (checked above): the scalar, or one radius per frame in ub
         if (!d->ub && !(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
         ext(EXT_L21_SEG);
         if (d->ub) {
@@ -361,6 +379,7 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       refuse_sharded(c, Sharded::L21);
       if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
       ext(EXT_L21_JOINT);
+      weights("l21_joint");
       break;
     case SIPX_PROJ_RANK: ext(EXT_RANK); break;
     case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;
@@ -407,6 +426,7 @@ std::vector<long long> default_ata_offsets(const ConfigCtx& c, const SetConfig<T
 // entries of the vectors a set takes (sipx_add_set, sipx_set_data): radii per segment, bounds per fiber coordinate, or one per row
 template <typename T>
 long long data_len(const ConfigCtx& c, const SetConfig<T>& s) {
+  if (s.weighted) return l21_groups(c, s.ext_kind);
   if (s.seg_radii) return s.ext_kind == EXT_L21_SEG ? c.G.n[2] : seg_count(s.spec);
   if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;
   return c.G.n[s.bdir] - ((s.nblk == 1 && s.dir[0] == s.bdir) ? 1 : 0);

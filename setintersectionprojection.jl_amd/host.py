@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = [
     "sipx_finalize_dev", "sipx_reset_dev", "sipx_download_dev", "sipx_set_caller_stream", "sipx_io_bytes",
     "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev", "sipx_segment_norms", "sipx_segment_norms_dev",
     "sipx_l21_norm", "sipx_l21_norm_dev", "sipx_l21_norms", "sipx_l21_norms_dev",
-    "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev",
+    "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev", "sipx_l21_weighted_norm", "sipx_l21_weighted_norm_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
@@ -55,6 +55,13 @@ L21_WHOLE_ONLY = "the l2,1 ball applies to the whole array (mode matrix/tensor)"
 L21_FRAMES_Z = "the l2,1 ball on TV_xy: frames run along z -- the mode must be (slice, z), or tensor for the whole array"
 # the joint l2,1 ball (csrc/l21_joint.h): one group per pixel across the frames of TV_xy; the engine's refusal, word for word
 L21_JOINT_NEEDS_TV_XY = "the joint l2,1 ball groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor"
+# one weight per group (csrc/l21_weighted.h): what takes them, and what to do where they are refused
+L21_WEIGHTS_WHERE = ("weights belong to the l2,1 sets on the whole array -- (\"l21\", \"TV\"), (\"l21\", \"TV_xy\") in tensor mode and "
+                     "(\"l21_joint\", \"TV_xy\"): drop them, or use one of these sets")
+L21_WEIGHTS_NO_FRAMES = ("the l2,1 ball per frame takes no weights: use (\"l21\", \"TV_xy\") in tensor mode or (\"l21_joint\", \"TV_xy\"), "
+                         "which take one weight per group")
+L21_WEIGHTS_NO_COARSE = ("multilevel: a weighted l2,1 set has no rule that takes its weights to a coarser grid yet -- solve on one level, "
+                         "or drop the weights")
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
 TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
 TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
@@ -199,6 +206,7 @@ class set_definitions:
     max: Any
     app_mode: Tuple[str, str]
     custom_TD_OP: Tuple[Any, bool] = ((), False)
+    weights: Any = None      # the l2,1 sets on the whole array: one weight >= 0 per group (csrc/l21_weighted.h), None: the plain ball
 
 
 @dataclass
@@ -373,6 +381,9 @@ class Projector:
         self.basis_orth = False
         self.pmin = self.pmax = 0.0
         self.transform = 0
+        self.weighted = False        # an l2,1 set built with one weight per group (in lb)
+        if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint"):
+            raise SipxError(f"set type {st!r} takes no weights: " + L21_WEIGHTS_WHERE)
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
         self.op = None               # the operator a stand-alone call of the projector acts behind (l21: the TV range), None: the identity
         if st == "l21_joint":
@@ -389,6 +400,7 @@ class Projector:
             if not float(constraint.max) > 0:
                 raise SipxError("Radius of L1 ball is negative")
             self.kind, self.pmax, self.op = "l21_joint", float(constraint.max), "TV_xy"
+            self._take_weights(constraint, int(n[0]) * int(n[1]), "pixel (n1 n2, pixel order)")
             return
         if st == "l21":
             # isotropic total variation: the l2,1 ball on the range of the TV operator (csrc/l21.h); max is the radius
@@ -405,6 +417,10 @@ class Projector:
                 if np.ndim(constraint.max) > (1 if self.mode else 0):
                     raise SipxError("the l2,1 ball on TV_xy takes one radius, or per frame a vector of n3 (constraint.max)")
                 self.kind, self.op = "l21", "TV_xy"
+                if self.mode and getattr(constraint, "weights", None) is not None:
+                    raise SipxError(L21_WEIGHTS_NO_FRAMES)
+                if not self.mode:
+                    self._take_weights(constraint, int(np.prod(n)), "grid point (column-major order)")
                 if np.ndim(constraint.max) == 1:
                     self.seg_radii = True
                     self.ub = np.ascontiguousarray(constraint.max, self.TF)
@@ -422,6 +438,7 @@ class Projector:
             if not float(constraint.max) > 0:
                 raise SipxError("Radius of L1 ball is negative")
             self.kind, self.pmax, self.op = "l21", float(constraint.max), "TV"
+            self._take_weights(constraint, int(np.prod(n)), "grid point (column-major order)")
             return
         if constraint.TD_OP == "DCT":
             # x -> C' P(C x) with the orthonormal DCT-II (get_projector.jl, special_operator_list branches); the l2 ball and
@@ -522,6 +539,22 @@ class Projector:
         else:
             raise SipxError(f"set type {st!r} is not part of this engine")
 
+    def _take_weights(self, constraint, groups, what):
+        """constraint.weights of an l2,1 set on the whole array: a 1-D numpy vector of the working precision with one finite weight >= 0
+        per group, kept as lb (csrc/l21_weighted.h).  None: the plain ball."""
+        w = getattr(constraint, "weights", None)
+        if w is None:
+            return
+        name = f"{constraint.set_type} weights"
+        if not isinstance(w, np.ndarray):
+            raise SipxError(f"{name} must be a numpy array, not {type(w).__name__}")
+        if w.dtype.type != self.TF:
+            raise SipxError(f"{name} have dtype {w.dtype}: not the working precision ({np.dtype(self.TF).name})")
+        if w.shape != (groups,):
+            raise SipxError(f"{name} have shape {w.shape}: ({groups},) is needed -- one per {what}")
+        _check_l21_weights(constraint.set_type, w)
+        self.lb, self.weighted = np.ascontiguousarray(w), True
+
     def _segment_radii(self, st, constraint):
         """One radius per segment (csrc/seg_norm.h): max -- and for the annulus min and / or max -- a vector of nseg entries in the order of
         segment_norms(); a scalar beside a vector is repeated.  The length is checked against the operator in check_rows."""
@@ -592,6 +625,8 @@ class Projector:
         """Entries of each vector sipx_set_data takes for this set behind operator `op`; None: the set holds no replaceable data."""
         if self.kind == "histogram":
             return int(op.shape[0])
+        if self.weighted:
+            return int(self.lb.shape[0])
         if self.seg_radii:
             return self.nseg(op)
         if self.kind != "bounds_vec" or self.transform:
@@ -608,7 +643,7 @@ class Projector:
         d.op, d.proj = OPS[op], PROJ[self.kind]
         d.pmin, d.pmax = self.pmin, self.pmax
         d.lb, d.ub = _ptr(self.lb), _ptr(self.ub)
-        d.ncvx, d.reserved = int(bool(ncvx)), 0
+        d.ncvx, d.reserved = int(bool(ncvx)), (int(self.lb.shape[0]) if self.weighted else 0)
         d.mode, d.dir = self.mode, self.dir
         d.transform = self.transform
         if self.basis is not None:
@@ -714,6 +749,8 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.min, c.max = np.asarray(c.min, TF), np.asarray(c.max, TF)
         if c.set_type == "l21" and np.ndim(c.max) == 1:      # one radius per frame (TV_xy, ("slice", "z"))
             c.max = np.asarray(c.max, TF)
+        if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
+            c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
         if c.set_type in ("l21", "l21_joint"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
@@ -995,6 +1032,11 @@ class Context:
         P = self._keep_proj[int(i)] if 0 <= int(i) < len(self._keep_proj) else None
         if P is not None and P.seg_radii and arrs[1] is not None:
             _check_l1_radii("l1" if P.kind == "l21" else P.kind, arrs[1])
+        if P is not None and P.weighted:
+            if arrs[1] is not None:
+                raise SipxError(L21_WEIGHTS_ARE_LB)
+            if arrs[0] is not None:
+                _check_l21_weights(P.kind, arrs[0])
         _chk(lib().sipx_set_data(self.h, int(i), _ptr(arrs[0]), _ptr(arrs[1])))
 
     def set_data_dev(self, i, lb=None, ub=None):
@@ -1438,6 +1480,19 @@ def _check_array(name, a, TF, length):
     return np.ascontiguousarray(a)
 
 
+L21_WEIGHTS_ARE_LB = "set_data: the weights of an l2,1 set are its lb; it has no ub (the radius is fixed when the set is built)"
+
+
+def _check_l21_weights(kind, w):
+    """No host path hands the device a weight of the weighted l2,1 ball that is negative, NaN or infinite (csrc/l21_weighted.h)."""
+    w = np.asarray(w)
+    ok = np.isfinite(w) & (w >= 0)
+    if not np.all(ok):
+        bad = int(np.flatnonzero(~ok)[0])
+        raise SipxError(f"the weighted l2,1 ball ({kind}): weight {bad} is negative, NaN or infinite ({w[bad]!r}) -- every weight must be "
+                        "finite and >= 0 (0 leaves its group unconstrained)")
+
+
 def _check_l1_radii(kind, r):
     """project_l1_Duchi!.jl:22 for every segment: no host path hands the device an l1 radius that is not > 0."""
     if kind == "l1" and not np.all(np.asarray(r) > 0):
@@ -1578,7 +1633,10 @@ class Solver:
         if want is None:
             raise SipxError(f"set_data: set {i} ({self.set_Prop.tag[i][0]} on {self.set_Prop.tag[i][1]}) holds no replaceable vectors -- "
                             "element-wise and per-fiber bounds (no transform), the relaxed histogram and per-fiber / per-slice l1, l2 "
-                            "and annulus sets built with a vector of radii do; build a new Solver for other data")
+                            "and annulus sets built with a vector of radii do, and the l2,1 sets built with weights; build a new "
+                            "Solver for other data")
+        if self.P_sub[i].weighted and ub is not None:
+            raise SipxError(L21_WEIGHTS_ARE_LB)
         if self.P_sub[i].seg_radii and lb is not None and self.P_sub[i].kind != "annulus":
             raise SipxError(f"set_data: set {i} is an {self.P_sub[i].kind} set: its radii are ub, only the annulus has inner radii (lb)")
         given = [(k, a) for k, a in (("lb", lb), ("ub", ub)) if a is not None]
@@ -1600,6 +1658,8 @@ class Solver:
                 _check_array(k, a, self.TF, want)
             if self.P_sub[i].seg_radii and ub is not None:
                 _check_l1_radii("l1" if self.P_sub[i].kind == "l21" else self.P_sub[i].kind, ub)
+            if self.P_sub[i].weighted and lb is not None:
+                _check_l21_weights(self.P_sub[i].kind, lb)
             fn = self._context(self.device).set_data
         try:
             fn(i, lb, ub)
@@ -1760,10 +1820,11 @@ def segment_norms(x, comp_grid, TD_OP: str, app_mode, norm: str):
     return out
 
 
-def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after):
+def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after, weights=None, groups=0):
     """What l21_norm and l21_joint_norm share: x, a numpy vector or a 1-D torch tensor on a GPU, goes through the library call
     fn(ctx, *before, x, out, *after) -- its _dev form for a tensor, ordered against torch's current stream -- in a context of its
-    own.  out: n3 entries (per_frame) or one, of the kind and precision of x.  Returns (out, x is a tensor)."""
+    own.  out: n3 entries (per_frame) or one, of the kind and precision of x.  weights (`groups` entries, of the kind and precision of
+    x) go between x and out: fn(ctx, *before, x, weights, out).  Returns (out, x is a tensor)."""
     on_dev = _is_tensor(x)
     TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
     if TF not in (np.float32, np.float64):
@@ -1780,22 +1841,33 @@ def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after):
         device = x.device.index if x.device.index is not None else torch.cuda.current_device()
         out = torch.empty(nout, dtype=x.dtype, device=torch.device("cuda", device))
         xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
+        if weights is not None:
+            if not _is_tensor(weights):
+                raise SipxError(f"{name}: x is a tensor on the GPU, the weights must be one too")
+            _check_tensor("weights", weights, TF, groups, x.device)
+            mid = (C.c_void_p(weights.data_ptr()),)
     else:
         x = _check_array("x", x, TF, N)
         device = None
         out = np.empty(nout, TF)
         xp, op_ = _ptr(x), _ptr(out)
+        if weights is not None:
+            weights = _check_array("weights", weights, TF, groups)
+            _check_l21_weights(name, weights)
+            mid = (_ptr(weights),)
+    if weights is None:
+        mid = ()
     ctx = Context(comp_grid, TF, device)
     try:
         if on_dev:
             ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
-        _chk(getattr(lib(), fn + ("_dev" if on_dev else ""))(ctx.h, *before, xp, op_, *after))
+        _chk(getattr(lib(), fn + ("_dev" if on_dev else ""))(ctx.h, *before, xp, *mid, op_, *after))
     finally:
         ctx.close()
     return out, on_dev
 
 
-def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None):
+def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None, weights=None):
     """||TV x||_2,1, the isotropic total variation of x on a 2-D or 3-D grid: sum over the grid points of the l2 norm of the forward
     differences that start there, one number of the working precision (that of x).  Computed by the kernel and the first-pass sum of
     the ("l21", "TV") projector (sipx_l21_norm): used as the radius it leaves TV x untouched.  x: a numpy vector (a numpy scalar
@@ -1804,7 +1876,10 @@ def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None):
 
     TD_OP = "TV_xy" (3-D grids) observes the in-plane gradient vcat(D_y, D_x) instead.  With app_mode = ("slice", "z") the n3 per-frame
     norms come back (an array / a tensor of n3 entries): the sums of the group norms of every z-slice as the per-frame projector
-    ("l21", "TV_xy", ("slice", "z")) compares them with its radii (sipx_l21_norms), so radii observed on x leave TV_xy x unwritten."""
+    ("l21", "TV_xy", ("slice", "z")) compares them with its radii (sipx_l21_norms), so radii observed on x leave TV_xy x unwritten.
+
+    weights (whole array only): one weight >= 0 per grid point in column-major order, of the kind and precision of x -- the weighted
+    norm sum_p w_p g_p as the first pass of the weighted projector sums it (sipx_l21_weighted_norm, csrc/l21_weighted.h)."""
     if TD_OP not in TV_OPERATORS + ("TV_xy",):
         raise SipxError(L21_NEEDS_TV)
     mode, dirn = 0, 0
@@ -1814,16 +1889,30 @@ def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None):
         if tuple(app_mode) != ("slice", "z"):
             raise SipxError(L21_FRAMES_Z)
         mode, dirn = MODES["slice"], 2
+    if weights is not None:
+        if mode:
+            raise SipxError(L21_WEIGHTS_NO_FRAMES)
+        out, on_dev = _l21_observe("l21_norm", x, comp_grid, TD_OP == "TV_xy", False, "sipx_l21_weighted_norm", (OPS[TD_OP], 0), (),
+                                   weights, int(np.prod(_grid(comp_grid)[0])))
+        return out if on_dev else out[0]
     out, on_dev = _l21_observe("l21_norm", x, comp_grid, TD_OP == "TV_xy", bool(mode), "sipx_l21_norms", (OPS[TD_OP], mode, dirn), (None,))
     return out if (on_dev or mode) else out[0]
 
 
-def l21_joint_norm(x, comp_grid):
+def l21_joint_norm(x, comp_grid, weights=None):
     """The joint (vectorial) total variation of the frames of x on a 3-D grid: the sum over the pixels (i, j) of the l2 norm of all
     in-plane differences that start at that pixel in any frame, one number of the working precision (that of x).  Computed by the
     z-march and the first-pass sum of the ("l21_joint", "TV_xy") projector (sipx_l21_joint_norm): used as the radius it leaves TV_xy x
     unwritten.  x: a numpy vector (a numpy scalar comes back) or a 1-D torch tensor on a GPU (a tensor of one entry there; nothing
-    crosses PCIe, the call orders itself against torch's current stream)."""
+    crosses PCIe, the call orders itself against torch's current stream).  weights: one weight >= 0 per pixel (n1 n2 entries, pixel
+    order), of the kind and precision of x -- the weighted norm as the weighted projector sums it (sipx_l21_weighted_norm)."""
+    if weights is not None:
+        n, _ = _grid(comp_grid)
+        if len(n) != 3:
+            raise SipxError(TV_XY_NEEDS_3D)
+        out, on_dev = _l21_observe("l21_joint_norm", x, comp_grid, True, False, "sipx_l21_weighted_norm", (OPS["TV_xy"], 1), (),
+                                   weights, int(n[0]) * int(n[1]))
+        return out if on_dev else out[0]
     out, on_dev = _l21_observe("l21_joint_norm", x, comp_grid, True, False, "sipx_l21_joint_norm", (), ())
     return out if on_dev else out[0]
 
