@@ -1015,6 +1015,7 @@ class Engine : public EngineBase {
     sums_seq_ = 0; cg_seq_ = 0; spec_seq_ = 0;
     spec_searches_ = spec_fallbacks_ = spec_rounds_ = 0;
     batch_searches_ = batch_fallbacks_ = 0;
+    for (long long& c : routes_) c = 0;
     head_done_ = false; rs_pending_ = false; sums_pending_ = false; merged_nslots_ = 0;
     rhs_fused_ = false; have_log_sums_ = false;
     obj_ss_ = evo_ss_ = xx_ss_ = 0;
@@ -3506,6 +3507,7 @@ class Engine : public EngineBase {
     if (comm_ && comm_->world > 1) throw std::runtime_error("a sharded context maintains its slab of Q only");
     SIPX_HIP(hipStreamSynchronize(stream_));
     SIPX_HIP(hipMemcpy(p_, x, Nx_ * sizeof(T), hipMemcpyHostToDevice));
+    ObserverGuard og(observer());
     if (stencil_q_) K<T>::sq_spmv(stream_, G_, sq_, p_, Ap_);
     else K<T>::spmv(stream_, G_, Nx_, Q_, cds_, p_, Ap_);
     mf_terms(p_, Ap_, T(1), 0, nullptr, nullptr);
@@ -3597,6 +3599,10 @@ class Engine : public EngineBase {
     o += ", \"lane_set\": " + std::to_string(lane_set_);
     o += std::string(", \"q_table\": {\"on\": ") + (cds_.qtab ? "true" : "false") + ", \"reason\": \"" + qtab_reason_ + "\"}";       // the set updated on a stream of its own (-1: none), lane_start
     o += ", \"batched_searches\": {\"searches\": " + std::to_string(batch_searches_) + ", \"fallbacks\": " + std::to_string(batch_fallbacks_) + "}";
+    // launches per route since the context was finalised, where one observer name covers two kernels (RouteId)
+    o += ", \"routes\": {";
+    for (int r = 0; r < RT_COUNT; ++r) o += std::string(r ? ", \"" : "\"") + route_name(r) + "\": " + std::to_string(routes_[r]);
+    o += "}";
     // slice-rank / matrix-rank sets: which route their projector took since the context was finalised (ext_proj.hip)
     long long rc[4] = {project_rc_[0], project_rc_[1], project_rc_[2], project_rc_[3]};      // stand-alone calls (project)
     for (const auto& st : sets_) {
@@ -3685,6 +3691,9 @@ class Engine : public EngineBase {
     e->open_.pop_back();
     if (i < e->samples_.size()) SIPX_HIP(hipEventRecord(e->stat_event(2 * i + 1), s));
   }
+  static void obs_route(void* user, int route) {
+    if (route >= 0 && route < RT_COUNT) static_cast<Engine<T>*>(user)->routes_[route] += 1;
+  }
   void drop_samples_from(size_t n) {
     if (n < samples_.size()) samples_.resize(n);
     open_.clear();
@@ -3741,7 +3750,8 @@ class Engine : public EngineBase {
     }
     stats_mode_ = mode;
   }
-  const LaunchObserver* observer() const { return stats_mode_ ? &obs_ : nullptr; }
+  // always installed: the route counters run whether or not statistics are collected (obs_begin / obs_end return at once then)
+  const LaunchObserver* observer() const { return &obs_; }
 
   void need_final() const {
     if (!finalized_) throw std::runtime_error("call sipx_finalize first");
@@ -4351,6 +4361,7 @@ class Engine : public EngineBase {
   bool sweep_plain_ = false;          // the sweep takes the plain iterations of this context: every set carries a third y / l pair
   bool search_batch_ = false;         // one rank + sweep: the searches of all sets as one chain of launches (batched_searches; SIPX_SEARCH_BATCH=0: per-set chains on the set streams)
   long long batch_searches_ = 0, batch_fallbacks_ = 0;
+  long long routes_[RT_COUNT] = {};     // launches per route since finalize (RouteId; obs_route)
   long long project_rc_[4] = {0, 0, 0, 0};   // route counters of the rank projectors that project() built and dropped
   T* fbuf_ = nullptr;                 // fast segments: world x two-pass sets x (fcap + header)
   bool yl_multi_ = true;              // SIPX_YL_MULTI=0: never take the one-sweep y/l update (A/B switch)
@@ -4415,7 +4426,7 @@ class Engine : public EngineBase {
   std::vector<KSample> samples_;
   std::vector<size_t> open_;              // samples whose closing record is still to come (launch scopes may nest)
   int stats_mode_ = 0;
-  LaunchObserver obs_{this, &Engine<T>::obs_begin, &Engine<T>::obs_end};
+  LaunchObserver obs_{this, &Engine<T>::obs_begin, &Engine<T>::obs_end, &Engine<T>::obs_route};
   std::string stats_json_;
   double stat_pair_ms_ = 0;       // elapsed time between two adjacent event records (median of 16 on the idle stream)
 };

@@ -503,10 +503,12 @@ static void launch_cds(hipStream_t s, long long N, long long r0, long long r1, c
   const double moved_extra = (MODE == 2 && !xold) ? 3.0 : extra;      // (x_old kept by buffer rotation: not written)
   ObsScope obs(MODE == 0 ? KID_CDS_SPMV : (MODE == 1 ? KID_CDS_DOT : KID_CDS_RESID), s, (a.d + extra) * rw, (read_bands + moved_extra) * rw);
   if (try_march<T, MODE>(s, N, r0, r1, R, a, x, y, b, pout, xold, partials, done)) {
+    obs.route((a.qtab ? RT_CDS_MARCH_TABLE : RT_CDS_MARCH_BANDS) + MODE);
     SIPX_HIP(hipGetLastError());
     return;
   }
   if (a.qtab) throw std::runtime_error("internal: Q's class table is in use but the z-marching product does not apply");
+  obs.route(RT_CDS_FLAT + MODE);
 #define SIPX_CDS(V, D) \
   hipLaunchKernelGGL((k_cds<T, V, D, MODE>), dim3(fit_grid((r1 - r0) / V, SIPX_CG_GRID)), dim3(BLOCK), 0, s, N, r0, r1, R, a, x, y, b, pout, xold, partials, done)
   // 16 bytes per thread and band: four floats or two doubles (four doubles leave the 7-band kernel 3 waves per SIMD)
@@ -1307,10 +1309,12 @@ void K<T>::spmv_fused(hipStream_t s, long long N, const T* R, const CdsArgs& a, 
   if (a.qtab) read_bands = 0;
   ObsScope obs(KID_CDS_FUSED, s, (a.d + 4.0) * (double)N * sizeof(T), (read_bands + 4.0) * (double)N * sizeof(T));   // r, p_k read; p_k+1, Ap written
   if (try_march<T, 3>(s, N, 0, N, R, a, r, Ap, p_old, p_new, nullptr, partials, nullptr, st, host, ticket)) {
+    obs.route((a.qtab ? RT_CDS_MARCH_TABLE : RT_CDS_MARCH_BANDS) + 3);
     SIPX_HIP(hipGetLastError());
     return;
   }
   if (a.qtab) throw std::runtime_error("internal: Q's class table is in use but the z-marching product does not apply");
+  obs.route(RT_CDS_FUSED_FLAT);
 #define SIPX_CDSF(V, D) \
   hipLaunchKernelGGL((k_cds_fused<T, V, D>), dim3(fit_grid(N / V, SIPX_CG_GRID)), dim3(BLOCK), 0, s, N, R, a, r, p_old, p_new, Ap, partials, st, host, ticket)
   constexpr int VW = sizeof(T) == 8 ? SIPX_F64_VEC : 4;

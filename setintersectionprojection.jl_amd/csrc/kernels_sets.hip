@@ -257,9 +257,11 @@ void K<T>::rhs_compose(hipStream_t s, const Grid& g, const RhsArgs<T>& a, T* rhs
   for (int i = 0; i < a.nsets; ++i) vecs += 2.0 * (a.s[i].nblk > 0 ? a.s[i].nblk : 1);
   ObsScope obs(KID_RHS, s, vecs * (double)range_len(g) * sizeof(T));
   if (!accumulate && try_rhs_march<T>(s, g, a, rhs)) {
+    obs.route(RT_RHS_MARCH);
     SIPX_HIP(hipGetLastError());
     return;
   }
+  obs.route(RT_RHS_FLAT);
   if (g.n[0] % 4 == 0)
     hipLaunchKernelGGL((k_rhs<T, 4>), dim3(fit_grid(range_len(g) / 4, NB)), dim3(BLOCK), 0, s, g, a, rhs, accumulate);
   else

@@ -78,10 +78,30 @@ inline const char* kernel_name(int k) {
       "k_l21j_norms", "k_l21j_finish", "k_l21j_scale", "k_l21w_part", "k_l21w_scale"};      // (the last eight: inside ext_proj)
   return (k >= 0 && k < KID_COUNT) ? names[k] : "?";
 }
+// Which kernel served a launch where one observer name covers two of them (the z-marching product and right-hand side run
+// under the names of the flat kernels): counted per context since finalize, whether or not statistics are collected, and
+// reported as `routes` by sipx_kernel_stats_json -- the tests that force a route prove it there.
+enum RouteId {
+  RT_CDS_MARCH_BANDS = 0,      // + MODE 0..3: k_cds_march on the stored bands (MODE 3: the fused iteration)
+  RT_CDS_MARCH_TABLE = 4,      // + MODE 0..3: k_cds_march on the class table of Q
+  RT_CDS_FLAT = 8,             // + MODE 0..2: k_cds
+  RT_CDS_FUSED_FLAT = 11,      // k_cds_fused
+  RT_RHS_MARCH = 12,           // k_rhs_march
+  RT_RHS_FLAT = 13,            // k_rhs
+  RT_COUNT = 14
+};
+inline const char* route_name(int r) {
+  static const char* const names[RT_COUNT] = {
+      "k_cds_march<MODE=0>/bands", "k_cds_march<MODE=1>/bands", "k_cds_march<MODE=2>/bands", "k_cds_march<MODE=3>/bands",
+      "k_cds_march<MODE=0>/table", "k_cds_march<MODE=1>/table", "k_cds_march<MODE=2>/table", "k_cds_march<MODE=3>/table",
+      "k_cds<MODE=0>", "k_cds<MODE=1>", "k_cds<MODE=2>", "k_cds_fused", "k_rhs_march", "k_rhs"};
+  return (r >= 0 && r < RT_COUNT) ? names[r] : "?";
+}
 struct LaunchObserver {
   void* user;
   void (*begin)(void* user, int kid, hipStream_t s, double bytes_survey, double bytes_moved);
   void (*end)(void* user, int kid, hipStream_t s);
+  void (*route)(void* user, int route);
 };
 // the observer of the calling host thread (a context is driven by one thread at a time); nullptr: nothing is recorded
 const LaunchObserver*& launch_observer();
@@ -101,6 +121,7 @@ struct ObsScope {
       fprintf(stderr, "[sipx trace]   done\n");
     }
   }
+  void route(int r) const { if (o && o->route) o->route(o->user, r); }      // the kernel this launch went to (RouteId)
   ObsScope(const ObsScope&) = delete;
   ObsScope& operator=(const ObsScope&) = delete;
 };

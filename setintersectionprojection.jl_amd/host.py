@@ -1181,8 +1181,11 @@ class Context:
 
     def kernel_stats_all(self, enable):
         """Per-kernel statistics gathered since the last call, as a dict (sipx_kernel_stats_json); `enable` as above.
-        enable = -1: the engine's counters only (`slab_searches`, `rank_route`) -- nothing is synchronised, a running
-        collection and its samples stay as they are."""
+        enable = -1: the engine's counters only (`slab_searches`, `rank_route`, `routes`) -- nothing is synchronised, a
+        running collection and its samples stay as they are.  `routes` counts, since finalize, the launches of the Q
+        products and of the right-hand side per kernel that served them -- `k_cds_march<MODE=m>/bands` and `/table` (m = 3:
+        the fused iteration), `k_cds<MODE=m>`, `k_cds_fused`, `k_rhs_march`, `k_rhs` -- where the entries of `kernels`
+        name the marched and the flat kernel alike."""
         import json
         txt = lib().sipx_kernel_stats_json(self.h, int(enable))
         if txt is None:

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import parsdmm_oracle as O      # checker only
+from tests import march_geometry as MG
 from tests.test_gpu_parity import _problem, model
 
 pytestmark = pytest.mark.gpu
@@ -49,6 +50,7 @@ def test_table_products_keep_the_bits_of_the_bands(sipx, monkeypatch, TF, n, kin
         ctx = sipx.host.build_context(m, AtAs, As, props, Ps, gs, os_)
         try:
             state = _q_table(ctx)
+            before = MG.routes(ctx)
             y0 = ctx.apply_Q(x)
             rho2 = [r * (1.5 if i % 2 else 0.75) for i, r in enumerate(rho)]
             ctx.q_update(rho2, rho)
@@ -59,12 +61,19 @@ def test_table_products_keep_the_bits_of_the_bands(sipx, monkeypatch, TF, n, kin
             ctx.q_update(rho4, rho3)
             Q4, _ = ctx.get_Q()
             y4 = ctx.apply_Q(x)
+            took_q = MG.ran(MG.routes(ctx), before)
             ctx.close()
             ctx = sipx.host.build_context(m, AtAs, As, props, Ps, gs, os_)
+            before = MG.routes(ctx)
             log, _ = ctx.parsdmm(os_)
+            took = MG.ran(MG.routes(ctx), before)
             xs, ls, ys = ctx.download()
         finally:
             ctx.close()
+        # the products ran marched, on the table / on the bands as switched: the engine's own count of launches per route
+        form, other = ("/table", "/bands") if tab == "1" else ("/bands", "/table")
+        assert took_q == {"k_cds_march<MODE=0>" + form: 3}, f"SIPX_Q_TABLE={tab}: apply_Q did not take the march on {form[1:]} three times: {took_q}"
+        MG.assert_route(took, [f"k_cds_march<MODE={k}>{form}" for k in (1, 2, 3)], MG.MARCH_ONLY + [other], f"SIPX_Q_TABLE={tab}")
         out[tab] = (state, y0, y1, Q4, y4, log, xs, ls, ys)
     on, off = out["1"], out["0"]
     assert on[0]["on"] is True and on[0]["reason"] == "", on[0]

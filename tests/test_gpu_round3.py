@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import parsdmm_oracle as O      # checker only
+from tests import march_geometry as MG
 from tests.test_gpu_parity import _problem, model
 
 pytestmark = pytest.mark.gpu
@@ -294,15 +295,25 @@ def test_z_marching_product_is_bit_identical(sipx, monkeypatch, TF, n, kinds):
         gs, os_, Ps, As, props, AtAs = _problem(sipx, n, h, TF, kinds, m, dict(maxit=25))
         os_.rho_ini = rho
         ctx = sipx.host.build_context(m, AtAs, As, props, Ps, gs, os_)
+        before = MG.routes(ctx)
         y0 = ctx.apply_Q(x)
         rho2 = [r * (1.5 if i % 2 else 0.75) for i, r in enumerate(rho)]
         ctx.q_update(rho2, rho)
         y1 = ctx.apply_Q(x)
+        took_q = MG.ran(MG.routes(ctx), before)
         ctx.kernel_stats(2)
         log, _ = ctx.parsdmm(os_)
-        names = {k["name"] for k in ctx.kernel_stats_all(0)["kernels"]}
+        took = MG.ran(MG.routes(ctx), before)
         xs, _, _ = ctx.download()
         ctx.close()
+        # the route each switch forces, by the engine's own count of launches: the flat kernels alone / the march alone (the
+        # class table is on by default wherever the march applies), apply_Q, the start residual and the CG products among them
+        if sw == "0":
+            assert took_q == {"k_cds<MODE=0>": 2}, f"SIPX_CDS_MARCH={sw}: apply_Q did not take the flat product twice: {took_q}"
+            MG.assert_route(took, ["k_cds<MODE=0>", "k_cds<MODE=1>", "k_cds<MODE=2>"], MG.FLAT_ONLY, f"SIPX_CDS_MARCH={sw}")
+        else:
+            assert took_q == {"k_cds_march<MODE=0>/table": 2}, f"SIPX_CDS_MARCH={sw}: apply_Q did not take the marched product twice: {took_q}"
+            MG.assert_route(took, [f"k_cds_march<MODE={k}>/table" for k in (0, 1, 2)], MG.MARCH_ONLY + ["/bands"], f"SIPX_CDS_MARCH={sw}")
         out[sw] = (y0, y1, xs, log)
     assert np.array_equal(out["0"][0], want) and np.array_equal(out["2"][0], want)
     assert np.array_equal(out["0"][1], out["2"][1])
@@ -374,7 +385,19 @@ def test_fused_z_marching_cg_iteration_is_bit_identical(sipx, monkeypatch, TF, n
     out = {}
     for tag in ("0", "1"):
         monkeypatch.setenv("SIPX_CG_FUSED", tag)
-        x, log, l, y = sipx.PARSDMM(m.copy(), AtA, A, prop, P, g, opt)
+        ctx = sipx.host.build_context(m.copy(), AtA, A, prop, P, g, opt)      # (what sipx.PARSDMM does, with the context in hand)
+        try:
+            before = MG.routes(ctx)
+            log, _ = ctx.parsdmm(opt)
+            took = MG.ran(MG.routes(ctx), before)
+            x, _, _ = ctx.download()
+        finally:
+            ctx.close()
+        # the march ran, and its fused form exactly where it is switched on
+        fused = [k for k in took if "MODE=3" in k or k == "k_cds_fused"]
+        MG.assert_route(took, ["k_cds_march<MODE=1>/table", "k_cds_march<MODE=2>/table"] + (["k_cds_march<MODE=3>/table"] if tag == "1" else []),
+                        MG.MARCH_ONLY + ["/bands"], f"SIPX_CG_FUSED={tag}")
+        assert bool(fused) == (tag == "1"), (tag, took)
         out[tag] = (x, log)
     (x0, l0), (x1, l1) = out["0"], out["1"]
     assert l0.cg_it.sum() > len(l0.cg_it)                       # iterations beyond the first did run
@@ -459,14 +482,24 @@ def test_z_marching_rhs_is_bit_identical(sipx, monkeypatch, TF, n, kinds):
     ctx = sipx.host.build_context(m, AtAs, As, props, Ps, gs, os_)
     ctx.parsdmm_begin(os_)
     ctx.parsdmm_steps(9)
+    x9, l9, y9 = ctx.download()
+    ctx.close()
     rho = [0.7 + 0.9 * i for i in range(len(Ps) + 1)]
+    os_.zero_ini_guess = False
     out = {}
     for tag in ("0", "2"):
+        # (a context reads its switches when it is built: one context per route, started from the state of the solve)
         monkeypatch.setenv("SIPX_RHS_MARCH", tag)
         monkeypatch.setenv("SIPX_RHS_MARCH_ZCHUNK", "5")
-        ctx.rhs_compose(rho)
-        out[tag] = ctx.get_rhs()
-    ctx.close()
+        ctx = sipx.host.build_context(m, AtAs, As, props, Ps, gs, os_, x=x9, l=l9, y=y9)
+        try:
+            before = MG.routes(ctx)
+            ctx.rhs_compose(rho)
+            out[tag] = ctx.get_rhs()
+            took = MG.ran(MG.routes(ctx), before)
+        finally:
+            ctx.close()
+        assert took == ({"k_rhs": 1} if tag == "0" else {"k_rhs_march": 1}), f"SIPX_RHS_MARCH={tag}: the forced route was not taken: {took}"
     assert np.isfinite(out["0"]).all() and np.abs(out["0"]).max() > 0
     assert np.array_equal(out["0"], out["2"])
 
