@@ -130,7 +130,25 @@ enum {
                                 the same bits (csrc/l21_joint.h).  Holds no replaceable vectors (sipx_set_data refuses).  Contexts
                                 with a communicator, a slab decomposition or set ownership refuse it, as they refuse the
                                 operator.  sipx_project takes the M-vector of the TV_xy range in the row order of SIPX_OP_TV_XY
-                                and refuses any other length with both lengths; sipx_l21_joint_norm observes the norm */
+                                and refuses any other length with both lengths; sipx_l21_joint_norm observes the norm */,
+  SIPX_PROJ_L21_GROUPS  = 16 /* group sparsity over fibers or slices (no counterpart in the reference): the l2,1 ball
+                                { v = A x : sum_s w_s ||v[segment s]||_2 <= pmax } on the range of a one-block operator (op IDENTITY, DX,
+                                DY or DZ), the groups being the fibers along dir (mode FIBER) or the slices orthogonal to it (mode SLICE,
+                                3-D grids) of the array of shape TD_n -- nseg segments in the order of sipx_segment_norms.  Segments
+                                compete for ONE budget (SIPX_PROJ_L2 per segment gives every segment its own).  pmax = tau > 0
+                                ("Radius of L1 ball is negative" otherwise, NaN included).  lb = NULL (every weight 1) or TF[nseg]
+                                finite weights >= 0 with reserved = nseg (0 leaves its segment unconstrained and unwritten), ub =
+                                NULL.  g_s from a float64 sum of squares in a fixed order rounded once to TF (fibers: the bits of
+                                sipx_segment_norms with norm 1; slices: chunks of the element index, one workgroup each), the weighted
+                                Michelot threshold of the weighted SIPX_PROJ_L21 on the nseg pairs (g, w) -- exact for any active set,
+                                all segments active included -- every entry of segment s scaled by max(g_s - theta w_s, 0) / g_s; an
+                                input inside the ball is not written, -0.0 included; pads of the layout are neither read into a sum
+                                nor written; no floating-point atomics, no state: two calls give the same bits, and no weights give the
+                                bits of a vector of ones (csrc/l21_groups.h).  Mode WHOLE (one group: use SIPX_PROJ_L2), multi-block
+                                and custom operators, transforms, Minkowski components and contexts with a communicator, a slab
+                                decomposition or set ownership are refused, each in words of its own.  sipx_set_data(_dev) replaces
+                                the weights of a set built with weights (lb, nseg entries; ub refused).  sipx_project takes the
+                                M-vector of the operator's range in the reference's row order; sipx_l21_groups_norm observes the norm */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -152,11 +170,11 @@ typedef struct {
   int32_t proj;      /* SIPX_PROJ_* */
   double pmin, pmax; /* constraint[i].min / .max (set_definitions, src/SetIntersectionProjection.jl:142-149) */
   const void* lb;    /* BOUNDS_VEC / HISTOGRAM: host TF vectors (see the kinds above); L1 / L2 / ANNULUS in mode FIBER / SLICE: NULL or
-                        the radii per segment, TF[nseg]; L21 in mode WHOLE / L21_JOINT: NULL or one weight per group (lb alone, and
-                        `reserved` holds their number); else NULL */
+                        the radii per segment, TF[nseg]; L21 in mode WHOLE / L21_JOINT / L21_GROUPS: NULL or one weight per group
+                        (lb alone, and `reserved` holds their number); else NULL */
   const void* ub;
   int32_t ncvx;      /* set_Prop.ncvx[i] (src/setup_constraints.jl:89-97) */
-  int32_t reserved;  /* 0; a weighted L21 / L21_JOINT set: the entries of lb, refused unless it is the group count */
+  int32_t reserved;  /* 0; a weighted L21 / L21_JOINT / L21_GROUPS set: the entries of lb, refused unless it is the group count */
   int32_t mode;      /* SIPX_MODE_* */
   int32_t dir;       /* direction of the fibers / normal of the slices */
   const void* basis; /* SUBSPACE: host TF[basis_rows x basis_cols], column-major (constraint.custom_TD_OP[1]) */
@@ -410,6 +428,14 @@ int sipx_l21_joint_norm_dev(sipx_ctx* ctx, const void* x, void* out);
  * sipx_l21_norm_dev against the caller's stream, and there such a weight counts as 0.  Refused where the set is refused. */
 int sipx_l21_weighted_norm(sipx_ctx* ctx, int op, int joint, const void* x, const void* w, void* out);
 int sipx_l21_weighted_norm_dev(sipx_ctx* ctx, int op, int joint, const void* x, const void* w, void* out);
+/* The group norm of x over fibers or slices: *out = one TF, (TF) sum_s w_s g_s over the segments of SIPX_PROJ_L21_GROUPS behind op
+ * (IDENTITY, DX, DY, DZ) with (mode, dir); w = TF[nseg] in the order of sipx_segment_norms, or NULL: every weight 1.  Summed by the norms
+ * launch and the first pass of the projector (csrc/l21_groups.h).  CONTRACT: the value is the very number the projector compares with
+ * pmax, so a set built with pmax = *out leaves A x unwritten.  A negative, NaN or infinite weight is refused on the host path; _dev: x,
+ * w and out device pointers, ordered like sipx_l21_norm_dev against the caller's stream, and there such a weight counts as 0.  Refused
+ * where the set is refused. */
+int sipx_l21_groups_norm(sipx_ctx* ctx, int op, int mode, int dir, const void* x, const void* w, void* out);
+int sipx_l21_groups_norm_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, const void* w, void* out);
 /* nearest-neighbour resampling of an array of shape nc to shape nf, the grid transfer of PARSDMM_multi_level:
  * out[k] = in[round(1 + (k-1)(nc-1)/(nf-1))] per axis (Interpolations.BSpline(Constant()) evaluated on
  * range(1, stop=nc, length=nf); src/PARSDMM_multi_level.jl:41-45,61-65, src/interpolate_y_l.jl:32-88) */

@@ -127,6 +127,16 @@ function projector_fields(c, TF)
         c.max > 0 || error("Radius of L1 ball is negative")
         return (15, 0.0, Float64(c.max), nothing_[3:5]...)
     end
+    # group sparsity: the l2,1 ball whose groups are the fibers / slices of the range of a one-block operator (include/sipx.h,
+    # SIPX_PROJ_L21_GROUPS; not a set of the reference).  Without weights: the binding does not carry them yet.
+    if st == "l21_groups"
+        op in ("identity", "D_x", "D_y", "D_z") && c.custom_TD_OP[1] == [] ||
+            error("the l2,1 ball over fibers or slices (l21_groups) groups the range of a one-block operator: TD_OP must be the identity, D_x, D_y or D_z (on TV use the l21 sets, whose groups are the grid points)")
+        c.app_mode[1] in ("fiber", "slice") ||
+            error("the l2,1 ball over fibers or slices (l21_groups) needs a fiber or slice mode: on the whole array it has one group and is the l2 ball -- use the l2 set")
+        c.max > 0 || error("Radius of L1 ball is negative")
+        return (16, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "l2"          && return (3, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "annulus"     && return (4, Float64(c.min), Float64(c.max), nothing_[3:5]...)

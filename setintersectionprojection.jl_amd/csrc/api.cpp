@@ -162,6 +162,12 @@ int sipx_l21_weighted_norm(sipx_ctx* c, int op, int joint, const void* x, const 
 int sipx_l21_weighted_norm_dev(sipx_ctx* c, int op, int joint, const void* x, const void* w, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_weighted_norm(op, joint != 0, x, w, out, true))
 }
+int sipx_l21_groups_norm(sipx_ctx* c, int op, int mode, int dir, const void* x, const void* w, void* out) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_groups_norm(op, mode, dir, x, w, out, false))
+}
+int sipx_l21_groups_norm_dev(sipx_ctx* c, int op, int mode, int dir, const void* x, const void* w, void* out) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_groups_norm(op, mode, dir, x, w, out, true))
+}
 int sipx_get_Q(sipx_ctx* c, void* Q, int64_t* offsets, int* d) { SIPX_TRY(c->e->get_Q(Q, offsets, d)) }
 int sipx_q_terms(sipx_ctx* c, int* bands, int* matrix_free) { SIPX_TRY(c->e->q_terms(bands, matrix_free)) }
 int sipx_time_spmv(sipx_ctx* c, int reps, double* avg_ms) { SIPX_TRY(*avg_ms = c->e->time_spmv(reps)) }

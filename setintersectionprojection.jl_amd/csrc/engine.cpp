@@ -385,6 +385,7 @@ class Engine : public EngineBase {
       if (s.seg_radii) refuse_sharded(ctx, Sharded::RADII);
       if (s.op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
       if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG || s.ext_kind == EXT_L21_JOINT) refuse_sharded(ctx, Sharded::L21);
+      if (s.ext_kind == EXT_L21_GROUPS) refuse_sharded(ctx, Sharded::L21_GROUPS);
     }
     FinalizePlan P;
     plan_sets();
@@ -2947,7 +2948,7 @@ class Engine : public EngineBase {
       throw std::runtime_error(what + ": the weights of an l2,1 set are its lb; it has no ub (the radius is fixed at sipx_add_set)");
     const ConfigCtx ctx = config_ctx();
     const long long len = data_len(ctx, s);
-    if (s.weighted && lb && !on_device) check_l21_weights((const T*)lb, len, s.ext_kind == EXT_L21_JOINT ? "l21_joint" : "l21");
+    if (s.weighted && lb && !on_device) check_l21_weights((const T*)lb, len, s.ext_kind == EXT_L21_JOINT ? "l21_joint" : (s.ext_kind == EXT_L21_GROUPS ? "l21_groups" : "l21"));
     if (s.seg_radii && (s.ext_kind == EXT_L1_SEG || s.ext_kind == EXT_L21_SEG) && ub && !on_device) check_l1_radii((const T*)ub, len);
     if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
       throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
@@ -3304,18 +3305,23 @@ class Engine : public EngineBase {
     }
   }
 
-  // SIPX_PROJ_L21 of sipx_project: the M-vector of the TV range in the reference's row order, through the packing of a TV set's y / l
+  // SIPX_PROJ_L21 of sipx_project: the M-vector of the TV range in the reference's row order, through the packing of a TV set's y / l;
+  // SIPX_PROJ_L21_GROUPS alike on the range of its one-block operator
   void project_l21(const sipx_set_desc* d, void* v, int64_t len) {
     SetConfig<T> st;
+    const bool groups = d->proj == SIPX_PROJ_L21_GROUPS;
     if (d->proj == SIPX_PROJ_L21_JOINT && d->op != SIPX_OP_TV_XY)
       throw std::runtime_error(L21_JOINT_ROUTE);
-    if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY)
+    if (groups && d->op != SIPX_OP_IDENTITY && d->op != SIPX_OP_DX && d->op != SIPX_OP_DY && d->op != SIPX_OP_DZ)
+      throw std::runtime_error(L21G_ONE_BLOCK);
+    if (!groups && d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY)
       throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
     const ConfigCtx ctx = config_ctx();
     configure_op(ctx, st, d->op);
     configure_proj(ctx, st, d);
     if (len != st.Mtrue)
-      throw std::runtime_error(std::string("the l2,1 ball projects a vector of the ") + (d->op == SIPX_OP_TV ? "TV" : "TV_xy") + " range: " +
+      throw std::runtime_error(std::string("the l2,1 ball projects a vector of the ") +
+                               (groups ? "operator's" : (d->op == SIPX_OP_TV ? "TV" : "TV_xy")) + " range: " +
                                std::to_string(st.Mtrue) + " entries on this grid, " + std::to_string((long long)len) + " given");
     st.spec.ub = st.host_ub.empty() ? nullptr : st.host_ub.data();      // (per frame: one radius each)
     st.spec.lb = st.weighted ? st.host_lb.data() : nullptr;             // (weighted: one weight per group)
@@ -3397,9 +3403,38 @@ class Engine : public EngineBase {
     finish_call(on_device, out, dout, 1);
   }
 
+  // sipx_l21_groups_norm(_dev): (T) sum_s w_s g_s over the segments of the (op, mode, dir) set on A x (w NULL: every weight 1), by the
+  // observe() of a throw-away projector of that set: its norms launch and the first pass of its iteration (l21_groups.h)
+  void l21_groups_norm(int op, int mode, int dir, const void* x, const void* w, void* out, bool on_device) override {
+    if (!x || !out) throw std::runtime_error("l2,1 norm over fibers or slices: x and out are needed");
+    SIPX_HIP(hipSetDevice(device_));
+    if (op != SIPX_OP_IDENTITY && op != SIPX_OP_DX && op != SIPX_OP_DY && op != SIPX_OP_DZ) throw std::runtime_error(L21G_ONE_BLOCK);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, op);
+    sipx_set_desc d{};
+    d.op = op; d.proj = SIPX_PROJ_L21_GROUPS; d.mode = mode; d.dir = dir; d.pmax = 1.0;
+    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the set without weights
+    if (w && !on_device) check_l21_weights((const T*)w, seg_count(s.spec), "l21_groups");
+    s.spec.weighted = w ? 1 : 0;
+    s.spec.lb = on_device ? nullptr : w;
+    DeviceMemory tmp;
+    const OpScratch ws = forward_scratch(tmp, s, on_device);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
+    ExtProj<T> ext(s.spec, stream_);
+    const T* dv = queue_forward(ws, s, x, on_device);     // (device x, w: the engine stream is behind the caller's from here on)
+    if (on_device && w) ext.set_data((const T*)w, nullptr, true);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)s.Mtrue * sizeof(T));
+      ext.observe(dv, dout, nullptr, nullptr, nullptr);
+    }
+    finish_call(on_device, out, dout, 1);
+  }
+
   void project(const sipx_set_desc* d, void* v, int64_t len) override {
     SIPX_HIP(hipSetDevice(device_));
-    if (d->proj == SIPX_PROJ_L21 || d->proj == SIPX_PROJ_L21_JOINT) { project_l21(d, v, len); return; }
+    if (d->proj == SIPX_PROJ_L21 || d->proj == SIPX_PROJ_L21_JOINT || d->proj == SIPX_PROJ_L21_GROUPS) { project_l21(d, v, len); return; }
     Grid g1;
     g1.n[0] = len; g1.n[1] = 1; g1.n[2] = 1; g1.N = len; g1.st[0] = 1; g1.st[1] = len; g1.st[2] = len;
     DeviceMemory tmp;
@@ -3626,13 +3661,23 @@ class Engine : public EngineBase {
     // weighted l2,1 sets: the Michelot passes and the flag reads of the last projection (summed over such sets), their calls and groups
     long long wc[4] = {0, 0, 0, 0};
     for (const auto& st : sets_) {
-      if (!st.ext || !st.weighted) continue;
+      if (!st.ext || !st.weighted || st.ext_kind == EXT_L21_GROUPS) continue;
       long long c[4];
       st.ext->route_counts(c);
       for (int q = 0; q < 4; ++q) wc[q] += c[q];
     }
     o += ", \"l21_weighted\": {\"passes\": " + std::to_string(wc[0]) + ", \"flag_reads\": " + std::to_string(wc[1]) +
-         ", \"calls\": " + std::to_string(wc[2]) + ", \"groups\": " + std::to_string(wc[3]) + "}}";
+         ", \"calls\": " + std::to_string(wc[2]) + ", \"groups\": " + std::to_string(wc[3]) + "}";
+    // l2,1 sets over fibers / slices, with or without weights: the same counts, and their segments
+    long long gc[4] = {0, 0, 0, 0};
+    for (const auto& st : sets_) {
+      if (!st.ext || st.ext_kind != EXT_L21_GROUPS) continue;
+      long long c[4];
+      st.ext->route_counts(c);
+      for (int q = 0; q < 4; ++q) gc[q] += c[q];
+    }
+    o += ", \"l21_groups\": {\"passes\": " + std::to_string(gc[0]) + ", \"flag_reads\": " + std::to_string(gc[1]) +
+         ", \"calls\": " + std::to_string(gc[2]) + ", \"nseg\": " + std::to_string(gc[3]) + "}}";
     if (!peek) start_stats(enable);
     return o.c_str();
   }

@@ -52,6 +52,8 @@ struct EngineBase {
   // the six sipx_l21_*norm* calls: proj SIPX_PROJ_L21 or SIPX_PROJ_L21_JOINT; query: x and out both null ask for *nseg alone
   virtual void l21_norms(int proj, int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device, bool query) = 0;
   virtual void l21_weighted_norm(int op, bool joint, const void* x, const void* w, void* out, bool on_device) = 0;
+  // sipx_l21_groups_norm(_dev): w null: every weight 1
+  virtual void l21_groups_norm(int op, int mode, int dir, const void* x, const void* w, void* out, bool on_device) = 0;
   virtual void get_Q(void* Q, int64_t* offsets, int* d) = 0;
   virtual void apply_Q(const void* x, void* y) = 0;
   virtual void q_terms(int* bands, int* matrix_free) = 0;

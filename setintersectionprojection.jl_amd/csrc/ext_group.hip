@@ -14,12 +14,15 @@
 // entries of g; the ball of every z-slice of TV_xy (EXT_L21_SEG, l21_seg.h, FrameProj) has k_l21_frames in place of the search.
 // Built with one weight per group (ExtSpec::weighted, l21_weighted.h) BallProj takes a route of its own after the norms launch: Michelot
 // passes k_l21w_part / k_l21w_finish in batches gated on a device flag, then k_l21w_scale; without weights not one launch differs.
+// The ball whose groups are the fibers or slices of a one-block operator's range (EXT_L21_GROUPS, l21_groups.h, GroupsProj) shares only the
+// weighted iteration (L21WSearch): its norms and its scale kernel are its own.
 // Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the two projectors.
 // A projector's observe() runs the norms launch and the first sum of its own project(): what it reports is what project() decides on.
 #include "ext_family.h"
 #include "l21.h"
 #include "l21_joint.h"
 #include "l21_seg.h"
+#include "l21_groups.h"
 #include "l21_weighted.h"
 
 namespace sipx {
@@ -162,7 +165,7 @@ __global__ void k_l21_pick(const ProjScalars<T>* __restrict__ ps, T* __restrict_
 //     k_l21w_finish   one workgroup: the partials in the same tree, then l21w_start / l21w_step on the device state
 //     k_l21w_scale    k_l21_scale with w read alongside g; groups of weight 0 are skipped without a load or a store of v
 // Both pass kernels return at once when the state says done, so the host enqueues them in batches and reads one word per batch
-// (BallProj::weighted_search).  FIRST: the pass over every group, which also gives asum and the decision; the state is not read.
+// (L21WSearch::run).  FIRST: the pass over every group, which also gives asum and the decision; the state is not read.
 constexpr int L21W_GRID = 1024;        // most workgroups of a pass: four per compute unit, 5 doubles of partials each
 constexpr int L21W_LOADS = 4;          // loads of g and of w a lane issues before it uses the first (16 bytes or one entry each)
 constexpr int L21W_BATCH = 8;          // passes enqueued per read of the flag
@@ -350,6 +353,110 @@ __global__ __launch_bounds__(BLOCK) void k_l21j_finish(unsigned L, int nchunk, c
     g[p] = l21_norm_of<T>(l21_joint_total(part, (long long)L, (long long)p, nchunk));
 }
 
+// ---- EXT_L21_GROUPS: the l2,1 ball whose groups are the fibers or slices of a one-block operator's range (l21_groups.h) ----------------------
+//     fibers: k_seg_observe<T, SEGN_L2> (seg_norm.h)      g[s] in segn_pass1's order                     reads N words, writes nseg
+//     slices: k_l21g_part                                  one (tile, chunk) per workgroup: its partial    reads N words, writes 2 ntA F nchunk doubles
+//             k_l21g_finish                                g[s] from a slice's partials, ascending chunk   reads 2 nseg nchunk doubles, writes nseg
+//     k_l21w_part / k_l21w_finish on (g, w), n = nseg      the passes of l21_weighted.h                     passes * 2 nseg words
+//     k_l21g_scale                                         coords -> segment -> f_s -> multiply             reads N + up to 2 N words, writes N
+struct L21GArgs {
+  Grid G;
+  int d[3];                   // the valid extents TD_n
+  int cs[3];                  // s = i cs[0] + j cs[1] + k cs[2]: the segment of grid point (i, j, k), all six geometries
+};
+
+// VW: consecutive element indices a thread takes before it strides (plan.vw); WIDE: they are one 16-byte load (VW > 1, the valid extent
+// along x a multiple of VW, 16-byte aligned rows), otherwise VW scalar loads of the same entries in the same order
+template <typename T, int VW, bool WIDE>
+__global__ __launch_bounds__(BLOCK) void k_l21g_part(SegMap m, L21GroupsPlan p, const T* __restrict__ v, double* __restrict__ part) {
+  __shared__ double red[2 * BLOCK];
+  const int F = p.F, G = BLOCK >> p.logF;
+  const int f = (int)threadIdx.x & (F - 1), r = (int)threadIdx.x >> p.logF;
+  const long long c = (long long)blockIdx.x % p.nchunk, tile = (long long)blockIdx.x / p.nchunk;
+  const long long sa = tile * F + f;
+  const bool live = sa < m.nseg;
+  const T* const vs = v + sa * m.sSa;
+  const long long t1 = p.t1(c, m.L);
+  L21Sum acc{0.0, 0.0};
+  if (live)
+    for (long long t = p.t0(c) + (long long)r * VW; t < t1; t += (long long)G * VW) {
+      if constexpr (WIDE) {
+        const Vec<T, VW> x = ldv<T, VW>(vs + seg_toff(m, t));
+#pragma unroll
+        for (int k = 0; k < VW; ++k) l21g_add_square<T>(acc, x.v[k]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VW; ++k)
+          if (t + k < t1) l21g_add_square<T>(acc, vs[seg_toff(m, t + k)]);
+      }
+    }
+  // the halving tree over the lanes of one slice: thread t merges with t + w, w = BLOCK / 2 .. F (t and t + w share f)
+  double *sh = red, *sl = red + BLOCK;
+  sh[threadIdx.x] = acc.hi; sl[threadIdx.x] = acc.lo;
+  __syncthreads();
+  for (int w = BLOCK / 2; w >= F; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      L21Sum x{sh[threadIdx.x], sl[threadIdx.x]};
+      l21_sum_merge(x, L21Sum{sh[threadIdx.x + w], sl[threadIdx.x + w]});
+      sh[threadIdx.x] = x.hi; sl[threadIdx.x] = x.lo;
+    }
+    __syncthreads();
+  }
+  if ((int)threadIdx.x < F && live) {
+    double* const o = part + 2 * (sa * p.nchunk + c);
+    o[0] = sh[threadIdx.x]; o[1] = sl[threadIdx.x];
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_l21g_finish(long long nseg, long long nchunk, const double* __restrict__ part, T* __restrict__ g) {
+  for (long long s = (long long)blockIdx.x * BLOCK + threadIdx.x; s < nseg; s += (long long)gridDim.x * BLOCK) {
+    L21Sum a{0.0, 0.0};
+    for (long long c = 0; c < nchunk; ++c) l21_sum_merge(a, L21Sum{part[2 * (s * nchunk + c)], part[2 * (s * nchunk + c) + 1]});
+    g[s] = l21g_norm_of<T>(a);
+  }
+}
+// Grid-stride over the padded grid, VW points of one grid line per thread.  A point outside the valid extents, or in a segment of weight
+// 0, is neither multiplied nor stored; nothing at all is read when the search found v inside the ball.
+template <typename T, int VW>
+__global__ __launch_bounds__(BLOCK) void k_l21g_scale(L21GArgs a, T* __restrict__ v, const T* __restrict__ g, const T* __restrict__ w,
+                                                      const L21WState* __restrict__ st, const T* __restrict__ theta) {
+  if (!st->need) return;
+  const T th = theta[0];
+  const unsigned nvec = (unsigned)(a.G.N / VW), step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    const Coord c = coords(a.G, (long long)p);
+    if (c.j >= a.d[1] || c.k >= a.d[2]) continue;
+    const int sb = c.j * a.cs[1] + c.k * a.cs[2];
+    T f[VW];
+    bool wr[VW], any = false, all = true;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      wr[k] = false;
+      f[k] = T(1);
+      const int i = c.i + k;
+      if (i < a.d[0]) {
+        const int s = sb + i * a.cs[0];
+        const T wk = l21w_clean<T>(w[s]);
+        if (wk > T(0)) { f[k] = l21w_factor<T>(g[s], wk, th); wr[k] = true; }
+      }
+      any = any || wr[k];
+      all = all && wr[k];
+    }
+    if (!any) continue;
+    Vec<T, VW> x = ldv<T, VW>(v + p);
+#pragma unroll
+    for (int k = 0; k < VW; ++k) x.v[k] = wr[k] ? x.v[k] * f[k] : x.v[k];
+    if (all) {
+      stv<T, VW>(v + p, x);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VW; ++k)
+        if (wr[k]) v[p + k] = x.v[k];
+    }
+  }
+}
+
 static void l21_check_spec(const ExtSpec& sp) {
   if (sp.nblk != 2 && sp.nblk != 3) throw std::runtime_error("the l2,1 ball needs the 2 or 3 blocks of the TV or TV_xy operator");
   if (sp.nblk > sp.ndim) throw std::runtime_error("the l2,1 ball: more blocks than grid dimensions");
@@ -451,6 +558,64 @@ static void l21_frames(hipStream_t s, const ExtSpec& sp, const T* g, T tau, cons
   SIPX_HIP(hipGetLastError());
 }
 
+// ---- the weighted Michelot iteration on n entries (g, w) (l21_weighted.h): the device state and the launches, for BallProj's weighted
+// route and for GroupsProj.  wide: 16-byte loads of g and w (n a multiple of 16 bytes' worth of entries, both arrays aligned).
+template <typename T>
+struct L21WSearch {
+  L21WState* st = nullptr;             // the state of the iteration
+  double* part = nullptr;              // the partials of a pass, 5 per workgroup
+  T* theta = nullptr;                  // theta in T, written when the iteration is done
+  int* flag = nullptr;                 // device: 0, or the passes once done
+  int* h_flag = nullptr;               // pinned: where the host reads it
+  long long last_passes = 0, last_reads = 0, calls = 0;
+  L21WSearch() = default;
+  L21WSearch(const L21WSearch&) = delete;
+  ~L21WSearch() { if (h_flag) (void)hipHostFree(h_flag); }
+  void build(ExtImpl<T>& owner) {
+    st = owner.template alloc<L21WState>(1);
+    part = owner.template alloc<double>(5 * L21W_GRID);
+    theta = owner.template alloc<T>(1);
+    flag = owner.template alloc<int>(1);
+    SIPX_HIP(hipHostMalloc((void**)&h_flag, sizeof(int), hipHostMallocDefault));
+  }
+  // one pass: the partial kernel and the one-workgroup finish (both return at once when the state says done)
+  template <bool FIRST>
+  void pass(hipStream_t stream, long long n, const T* g, const T* w, bool wide, T tau) {
+    constexpr int W = l21_vec_width<T>();
+    const int grid = fit_grid((n / (wide ? W : 1) + L21W_LOADS - 1) / L21W_LOADS, L21W_GRID);
+    void (*const k)(unsigned, const T*, const T*, const L21WState*, double*) = wide ? k_l21w_part<T, W, FIRST> : k_l21w_part<T, 1, FIRST>;
+    {
+      ObsScope obs(KID_L21W_PASS, stream, 2.0 * n * sizeof(T));
+      hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)n, g, w, st, part);
+    }
+    hipLaunchKernelGGL((k_l21w_finish<T, FIRST>), dim3(1), dim3(BLOCK), 0, stream, grid, tau, part, st, theta, flag);
+    SIPX_HIP(hipGetLastError());
+  }
+  // the iteration: passes in batches of L21W_BATCH, one 4-byte read of the flag per batch; more than n + 1 passes is an error
+  void run(hipStream_t stream, long long n, const T* g, const T* w, bool wide, T tau) {
+    pass<true>(stream, n, g, w, wide, tau);
+    long long queued = 1;
+    last_reads = 0;
+    for (;;) {
+      for (; queued % L21W_BATCH != 0; ++queued) pass<false>(stream, n, g, w, wide, tau);
+      SIPX_HIP(hipMemcpyAsync(h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, stream));
+      SIPX_HIP(hipStreamSynchronize(stream));
+      ++last_reads;
+      if (*h_flag) break;
+      if (queued > n + 1) throw std::runtime_error("the weighted l2,1 ball: the threshold iteration did not end within n + 1 passes");
+      pass<false>(stream, n, g, w, wide, tau);
+      ++queued;
+    }
+    last_passes = *h_flag;
+    ++calls;
+  }
+  // out[0] <- (T)asum of the last first pass
+  void pick(hipStream_t stream, T* out) {
+    hipLaunchKernelGGL((k_l21w_pick<T>), dim3(1), dim3(64), 0, stream, st, out);
+    SIPX_HIP(hipGetLastError());
+  }
+};
+
 // ---- EXT_L21, EXT_L21_JOINT: one ball on the whole array -- the norms, the engine's search on g, Float64: the refinement, the scale ----
 // The two sets differ in what a group is, hence in the norms launch and in the length of g: the N grid points, or the L pixels.
 template <typename T>
@@ -467,14 +632,8 @@ struct BallProj : ExtImpl<T> {
   ProjScalars<T>* ps_obs = nullptr;    // the state of observe's search, taken at its first call
   // the weighted route (l21_weighted.h), taken when the spec carries weights: none of the members above but g and part is used
   T* w = nullptr;                      // one weight per group
-  L21WState* wst = nullptr;            // the state of the iteration
-  double* wpart = nullptr;             // the partials of a pass, 5 per workgroup
-  T* wtheta = nullptr;                 // theta in T, written when the iteration is done
-  int* wflag = nullptr;                // device: 0, or the passes once done
-  int* h_flag = nullptr;               // pinned: where the host reads it
-  long long last_passes = 0, last_reads = 0, calls = 0;
+  L21WSearch<T> ws;                    // the iteration on (g, w)
   void reset() override { search.reinit(stream); }
-  ~BallProj() override { if (h_flag) (void)hipHostFree(h_flag); }
   BallProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s), joint(spec.kind == EXT_L21_JOINT) {
     if (joint) l21_joint_check_spec(sp);
     else l21_check_spec(sp);
@@ -485,11 +644,7 @@ struct BallProj : ExtImpl<T> {
     if (nchunk > 1) part = this->template alloc<double>((size_t)nchunk * n);
     if (sp.weighted) {
       w = this->template alloc<T>(n);
-      wst = this->template alloc<L21WState>(1);
-      wpart = this->template alloc<double>(5 * L21W_GRID);
-      wtheta = this->template alloc<T>(1);
-      wflag = this->template alloc<int>(1);
-      SIPX_HIP(hipHostMalloc((void**)&h_flag, sizeof(int), hipHostMallocDefault));
+      ws.build(*this);
       if (sp.lb) SIPX_HIP(hipMemcpy(w, sp.lb, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
       else SIPX_HIP(hipMemsetAsync(w, 0, sizeof(T) * (size_t)n, s));      // (set_data brings them; until then no group is constrained)
       return;
@@ -511,38 +666,7 @@ struct BallProj : ExtImpl<T> {
     }
   }
   // ---- the weighted route ----
-  // one pass: the partial kernel and the one-workgroup finish (both return at once when the state says done)
-  template <bool FIRST>
-  void weighted_pass(T tau) {
-    constexpr int W = l21_vec_width<T>();
-    const bool wide = sp.G.n[0] % 4 == 0 && aligned16(g, w);
-    const int grid = fit_grid((n / (wide ? W : 1) + L21W_LOADS - 1) / L21W_LOADS, L21W_GRID);
-    void (*const k)(unsigned, const T*, const T*, const L21WState*, double*) = wide ? k_l21w_part<T, W, FIRST> : k_l21w_part<T, 1, FIRST>;
-    {
-      ObsScope obs(KID_L21W_PASS, stream, 2.0 * n * sizeof(T));
-      hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)n, g, w, wst, wpart);
-    }
-    hipLaunchKernelGGL((k_l21w_finish<T, FIRST>), dim3(1), dim3(BLOCK), 0, stream, grid, tau, wpart, wst, wtheta, wflag);
-    SIPX_HIP(hipGetLastError());
-  }
-  // the iteration on (g, w): passes in batches of L21W_BATCH, one 4-byte read of the flag per batch; more than n + 1 passes is an error
-  void weighted_search(T tau) {
-    weighted_pass<true>(tau);
-    long long queued = 1;
-    last_reads = 0;
-    for (;;) {
-      for (; queued % L21W_BATCH != 0; ++queued) weighted_pass<false>(tau);
-      SIPX_HIP(hipMemcpyAsync(h_flag, wflag, sizeof(int), hipMemcpyDeviceToHost, stream));
-      SIPX_HIP(hipStreamSynchronize(stream));
-      ++last_reads;
-      if (*h_flag) break;
-      if (queued > n + 1) throw std::runtime_error("the weighted l2,1 ball: the threshold iteration did not end within n + 1 passes");
-      weighted_pass<false>(tau);
-      ++queued;
-    }
-    last_passes = *h_flag;
-    ++calls;
-  }
+  bool weighted_wide() const { return sp.G.n[0] % 4 == 0 && aligned16(g, w); }
   void weighted_scale(T* v) {
     constexpr int W = l21_vec_width<T>();
     const bool wide = l21_wide(sp, v, g) && aligned16(w);
@@ -551,7 +675,7 @@ struct BallProj : ExtImpl<T> {
         : sp.nblk == 2  ? (wide ? k_l21w_scale<T, 2, W, false> : k_l21w_scale<T, 2, 1, false>)
                         : (wide ? k_l21w_scale<T, 3, W, false> : k_l21w_scale<T, 3, 1, false>);
     ObsScope obs(KID_L21W_SCALE, stream, (2.0 * sp.nblk * sp.G.N + 2.0 * n) * sizeof(T));
-    hipLaunchKernelGGL(k, dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream, l21_args(sp), v, g, w, wst, wtheta);
+    hipLaunchKernelGGL(k, dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream, l21_args(sp), v, g, w, ws.st, ws.theta);
     SIPX_HIP(hipGetLastError());
   }
   void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
@@ -561,14 +685,14 @@ struct BallProj : ExtImpl<T> {
   }
   // the passes of the last call (the first included), the reads of the flag it took, the calls so far, the groups
   void route_counts(long long out[4]) const override {
-    out[0] = last_passes; out[1] = last_reads; out[2] = calls; out[3] = w ? n : 0;
+    out[0] = ws.last_passes; out[1] = ws.last_reads; out[2] = ws.calls; out[3] = w ? n : 0;
   }
 
   void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
     const double N = (double)sp.G.N;
     if (w) {
       l21_norms<T>(stream, sp, v, g, part);
-      weighted_search((T)sp.pmax);
+      ws.run(stream, n, g, w, weighted_wide(), (T)sp.pmax);
       weighted_scale(v);
       return;
     }
@@ -583,9 +707,8 @@ struct BallProj : ExtImpl<T> {
   void observe(const T* v, T* out, double* partials, T* maxpart, T* compact) override {
     if (w) {                // the weighted norm: the norms launch and the first pass of project(), (T)asum as that pass compares it
       l21_norms<T>(stream, sp, v, g, part);
-      weighted_pass<true>((T)INFINITY);
-      hipLaunchKernelGGL((k_l21w_pick<T>), dim3(1), dim3(64), 0, stream, wst, out);
-      SIPX_HIP(hipGetLastError());
+      ws.template pass<true>(stream, n, g, w, weighted_wide(), (T)INFINITY);
+      ws.pick(stream, out);
       return;
     }
     if (!ps_obs) ps_obs = this->template alloc<ProjScalars<T>>(1);
@@ -656,8 +779,112 @@ struct FrameProj : ExtImpl<T> {
   }
 };
 
+// ---- EXT_L21_GROUPS: one ball whose groups are the fibers or slices of the valid block (l21_groups.h) ---------------------------------------
+// The norms by the plan of l21_groups.h, the iteration of the weighted route on the nseg pairs (g, w), k_l21g_scale.  Built without weights
+// w is a vector of ones: not one launch, and not one bit, differs from the set built with np.ones(nseg).  Nothing is kept between calls.
+static void l21g_check_spec(const ExtSpec& sp) {
+  if (sp.nblk > 1) throw std::runtime_error(L21G_ONE_BLOCK);
+  if (sp.mode != SIPX_MODE_FIBER && sp.mode != SIPX_MODE_SLICE) throw std::runtime_error(L21G_NEEDS_MODE);
+  if (sp.ndim == 2 && sp.mode == SIPX_MODE_SLICE) throw std::runtime_error(L21G_2D_SLICE);
+  if (sp.G.N >= (1ll << 31)) throw std::runtime_error("the l2,1 ball over fibers or slices: the grid needs fewer than 2^31 points");
+}
+template <typename T>
+struct GroupsProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  SegMap map{};
+  L21GroupsPlan plan{};
+  long long n = 0;                     // segments: the entries of g and w, the length of the search
+  T *g = nullptr, *w = nullptr;
+  double* part = nullptr;              // slices: the chunk partials, 2 per (slice, chunk)
+  L21WSearch<T> ws;
+  GroupsProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    l21g_check_spec(sp);
+    if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+    map = make_segmap(sp);
+    if (map.nseg < 1 || map.L < 1) throw std::runtime_error("the l2,1 ball over fibers or slices: empty segments");
+    plan = l21_groups_plan(map, sp.mode, (int)sizeof(T));
+    n = map.nseg;
+    g = this->template alloc<T>(n);
+    w = this->template alloc<T>(n);
+    if (plan.slices) part = this->template alloc<double>(2 * (size_t)(plan.ntA * plan.F * plan.nchunk));
+    ws.build(*this);
+    if (sp.lb) {
+      SIPX_HIP(hipMemcpy(w, sp.lb, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+    } else if (sp.weighted) {
+      SIPX_HIP(hipMemsetAsync(w, 0, sizeof(T) * (size_t)n, s));      // (set_data brings them; until then no segment is constrained)
+    } else {
+      const std::vector<T> ones((size_t)n, T(1));
+      SIPX_HIP(hipMemcpy(w, ones.data(), sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+    }
+  }
+  bool search_wide() const { return n % 4 == 0 && aligned16(g, w); }
+  void norms(const T* v) {
+    if (!plan.slices) {                // k_seg_observe with the tile mapping of seg_norm.h: the bits of sipx_segment_norms
+      ObsScope obs(KID_L21G_NORMS, stream, (double)(map.nseg * map.L + n) * sizeof(T));
+      hipLaunchKernelGGL((k_seg_observe<T, SEGN_L2>), dim3(plan.fiber.grid), dim3(BLOCK), 0, stream, map, plan.fiber, v, g);
+      SIPX_HIP(hipGetLastError());
+      return;
+    }
+    constexpr int W = l21_vec_width<T>();
+    // 16-byte loads: a thread's VW entries lie in one row of the slice (LA % VW) whose start is 16-byte aligned (every stride % VW)
+    const bool wide = plan.vw == W && map.LA % W == 0 && sp.G.n[0] % 4 == 0 && aligned16(v);
+    void (*const k)(SegMap, L21GroupsPlan, const T*, double*) =
+        plan.vw == 1 ? k_l21g_part<T, 1, false> : (wide ? k_l21g_part<T, W, true> : k_l21g_part<T, W, false>);
+    {
+      ObsScope obs(KID_L21G_NORMS, stream, (double)(map.nseg * map.L) * sizeof(T) + 16.0 * plan.grid);
+      hipLaunchKernelGGL(k, dim3((unsigned)plan.grid), dim3(BLOCK), 0, stream, map, plan, v, part);
+    }
+    {
+      ObsScope obs(KID_L21G_FINISH, stream, (double)n * (16.0 * plan.nchunk + sizeof(T)));
+      hipLaunchKernelGGL((k_l21g_finish<T>), dim3(fit_grid(n, NB)), dim3(BLOCK), 0, stream, n, plan.nchunk, part, g);
+    }
+    SIPX_HIP(hipGetLastError());
+  }
+  void scale(T* v) {
+    constexpr int W = l21_vec_width<T>();
+    const bool wide = sp.G.n[0] % 4 == 0 && aligned16(v);
+    L21GArgs a;
+    a.G = sp.G;
+    a.G.set_fast_div();
+    for (int q = 0; q < 3; ++q) { a.d[q] = (int)sp.dims[q]; a.cs[q] = 0; }
+    if (sp.mode == SIPX_MODE_SLICE) {
+      a.cs[sp.dir] = 1;
+    } else {                           // make_segmap: s = c_a + d_a c_b over the two other axes a < b
+      const int ax = sp.dir == 0 ? 1 : 0, bx = sp.dir == 2 ? 1 : 2;
+      a.cs[ax] = 1;
+      a.cs[bx] = (int)sp.dims[ax];
+    }
+    ObsScope obs(KID_L21G_SCALE, stream, (2.0 * sp.G.N + 2.0 * n) * sizeof(T));
+    hipLaunchKernelGGL((wide ? k_l21g_scale<T, W> : k_l21g_scale<T, 1>), dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream, a,
+                       v, g, w, ws.st, ws.theta);
+    SIPX_HIP(hipGetLastError());
+  }
+  void project(T* v, bool, double*, T*, T*) override {
+    norms(v);
+    ws.run(stream, n, g, w, search_wide(), (T)sp.pmax);
+    scale(v);
+  }
+  // out[0] <- (T)asum as project decides on it: its norms launch into its g, then the first pass of its iteration
+  void observe(const T* v, T* out, double*, T*, T*) override {
+    norms(v);
+    ws.template pass<true>(stream, n, g, w, search_wide(), (T)INFINITY);
+    ws.pick(stream, out);
+  }
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    if (!sp.weighted) ExtImpl<T>::set_data(new_lb, new_ub, on_device);
+    if (new_ub) throw std::runtime_error("the weighted l2,1 ball: the weights are its lb, it has no ub (the radius is fixed at sipx_add_set)");
+    if (new_lb) SIPX_HIP(hipMemcpyAsync(w, new_lb, sizeof(T) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  }
+  // the passes of the last call (the first included), the reads of the flag it took, the calls so far, the segments
+  void route_counts(long long out[4]) const override {
+    out[0] = ws.last_passes; out[1] = ws.last_reads; out[2] = ws.calls; out[3] = n;
+  }
+};
+
 template <typename T>
 ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
+  if (spec.kind == EXT_L21_GROUPS) return new GroupsProj<T>(spec, stream);
   if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);
   if (spec.kind != EXT_L21 && spec.kind != EXT_L21_JOINT) throw std::runtime_error("unknown external projector");
   return new BallProj<T>(spec, stream);

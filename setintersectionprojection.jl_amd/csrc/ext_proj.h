@@ -10,7 +10,8 @@ enum { EXT_L1_DFT = 1, EXT_RANK = 2, EXT_NUCLEAR = 3, EXT_CARD_SEG = 4, EXT_HIST
        EXT_L1_SEG = 11, EXT_L2_SEG = 12, EXT_ANNULUS_SEG = 13 /* l1 / l2 / annulus per fiber or slice */,
        EXT_L21 = 14 /* the l2,1 ball across the blocks of the TV / TV_xy operator (l21.h) */,
        EXT_L21_SEG = 15 /* the l2,1 ball of every z-slice across the blocks of TV_xy (l21_seg.h) */,
-       EXT_L21_JOINT = 16 /* the l2,1 ball whose groups span the blocks of TV_xy and the frames (l21_joint.h) */ };
+       EXT_L21_JOINT = 16 /* the l2,1 ball whose groups span the blocks of TV_xy and the frames (l21_joint.h) */,
+       EXT_L21_GROUPS = 17 /* the l2,1 ball whose groups are the fibers or slices of a one-block operator's range (l21_groups.h) */ };
 
 // The refusal of an EXT_L21_JOINT set off its operator or mode, worded once: set_config.h (sipx_add_set), the stand-alone calls of the
 // engine and the projector's own check throw this text (its cases: tests/test_l21_joint_cpu.py, tests/test_gpu_l21_joint.py)
@@ -35,7 +36,7 @@ struct ExtSpec {
   int nblk = 0;                   // EXT_L21(_SEG): blocks of the operator (2 or 3), block q at v + q * bstride holding the differences along bdir[q]
   long long bstride = 0;
   int bdir[3] = {0, 0, 0};
-  int weighted = 0;               // EXT_L21 (whole array) / EXT_L21_JOINT: 1: one weight per group (l21_weighted.h) -- lb: host TF[groups], or
+  int weighted = 0;               // EXT_L21 (whole array) / EXT_L21_JOINT / EXT_L21_GROUPS: 1: one weight per group (l21_weighted.h) -- lb: host TF[groups], or
                                   // nullptr: set_data brings them before the first projection
 };
 
@@ -52,7 +53,7 @@ class ExtProj {
   void project(T* v, bool feas, double* partials, T* maxpart, T* compact);
   // the l2,1 sets (ext_group.hip): out (device) <- what project(v, ...) would compare with the radius, summed and rounded by the
   // projector's own launches -- ||v||_2,1 for EXT_L21, the sum of the n1 n2 group norms for EXT_L21_JOINT, one sum per z-slice (n3
-  // entries) for EXT_L21_SEG.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
+  // entries) for EXT_L21_SEG, the weighted sum of the segment norms for EXT_L21_GROUPS.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
   void observe(const T* v, T* out, double* partials, T* maxpart, T* compact);
   // rank projector: calls since construction, calls served by the warm-started subspace route, calls that decomposed fully,
   // products with the Gram matrices the subspace route spent (all zero for the other kinds)

@@ -9,6 +9,7 @@
 
 #include "dwt.h"
 #include "ext_family.h"      // (sipx.h, sipx_common.h, ext_proj.h; make_segmap / seg_count)
+#include "l21_groups.h"      // (the refusals and the descriptor check of the l2,1 ball over fibers / slices)
 #include "l21_weighted.h"    // (the host checks of the weighted l2,1 sets)
 
 namespace sipx {
@@ -71,7 +72,7 @@ struct SetConfig {
   int bmode = SIPX_MODE_WHOLE, bdir = 0;   // SIPX_PROJ_BOUNDS_VEC: one bound per row (WHOLE) or per coordinate along bdir (FIBER)
   int ext_kind = 0;                  // projector acting on a materialised vector (ext_proj.h)
   bool seg_radii = false;            // EXT_L1_SEG / L2_SEG / ANNULUS_SEG built with one radius per segment (host_lb / host_ub, then the projector's)
-  bool weighted = false;             // EXT_L21 (whole array) / EXT_L21_JOINT built with one weight per group in lb (host_lb, then the projector's)
+  bool weighted = false;             // EXT_L21 (whole array) / EXT_L21_JOINT / EXT_L21_GROUPS built with one weight per group in lb (host_lb, then the projector's)
   ExtSpec spec;
   std::vector<T> host_basis;
   std::vector<long long> ata_off;
@@ -95,8 +96,9 @@ void expand_fiber_bounds(const ConfigCtx& c, const SetConfig<T>& s, const T* per
 
 // What only single-process contexts take.  RADII: vector radii live in the one projector of a single process, a rank of a sharded
 // solve would each need its share of them.  L21: the groups of the l2,1 ball span the blocks of the TV operator, the gather route
-// of a slab-decomposed solve is single-block.  TV_XY: the slab routes know TV's one block per dimension only.
-enum class Sharded { RADII, L21, TV_XY };
+// of a slab-decomposed solve is single-block.  TV_XY: the slab routes know TV's one block per dimension only.  L21_GROUPS: the segments
+// of the l2,1 ball over fibers / slices share one budget, a rank would see its slab's segments (or its part of every slice) only.
+enum class Sharded { RADII, L21, TV_XY, L21_GROUPS };
 inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
   if (c.single_process) return;
   switch (which) {
@@ -109,6 +111,8 @@ inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
     case Sharded::TV_XY:
       throw std::runtime_error("the TV_xy operator takes single-process contexts only, this one has a communicator, a slab decomposition "
                                "or set ownership: use D_x and D_y sets, or a single process");
+    case Sharded::L21_GROUPS:
+      throw std::runtime_error(L21G_SHARDED);
   }
 }
 // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
@@ -118,7 +122,8 @@ void check_l1_radii(const T* r, long long n) {
     if (!(r[k] > T(0))) throw std::runtime_error("Radius of L1 ball is negative (segment " + std::to_string(k) + ")");
 }
 
-// the groups of a weighted l2,1 set (l21_weighted.h): the grid points of EXT_L21, the pixels of EXT_L21_JOINT
+// the groups of a weighted l2,1 set on TV / TV_xy (l21_weighted.h): the grid points of EXT_L21, the pixels of EXT_L21_JOINT
+// (EXT_L21_GROUPS: the segments of its spec, seg_count)
 inline long long l21_groups(const ConfigCtx& c, int ext_kind) { return ext_kind == EXT_L21_JOINT ? c.G.st[2] : c.G.N; }
 
 template <typename T>
@@ -207,6 +212,13 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
   // the joint l2,1 ball (l21_joint.h) is one set on one operator: its refusal names the way out before any general one
   if (d->proj == SIPX_PROJ_L21_JOINT && (s.op != SIPX_OP_TV_XY || mode != SIPX_MODE_WHOLE || d->transform != SIPX_TRANSFORM_NONE))
     throw std::runtime_error(L21_JOINT_ROUTE);
+  // so is the l2,1 ball over fibers or slices (l21_groups.h): a one-block operator, no transform, no component, a mode
+  if (d->proj == SIPX_PROJ_L21_GROUPS) {
+    if (s.custom || s.nblk > 1) throw std::runtime_error(L21G_ONE_BLOCK);
+    if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(L21G_NO_TRANSFORM);
+    if (s.comp) throw std::runtime_error(L21G_NO_MINKOWSKI);
+    if (mode == SIPX_MODE_WHOLE) throw std::runtime_error(L21G_NEEDS_MODE);
+  }
   if (mode != SIPX_MODE_WHOLE) {
     if (dir < 0 || dir >= c.ndim) throw std::runtime_error("application mode: direction out of range for this grid");
     // the one multi-block set with a mode of its own: the l2,1 ball per z-slice on TV_xy (l21_seg.h)
@@ -381,6 +393,21 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       ext(EXT_L21_JOINT);
       weights("l21_joint");
       break;
+    case SIPX_PROJ_L21_GROUPS: {  // group sparsity: one group per fiber or slice of the valid block (op, transform, component, mode: above)
+      if (c.ndim == 2 && mode == SIPX_MODE_SLICE) throw std::runtime_error(L21G_2D_SLICE);
+      refuse_sharded(c, Sharded::L21_GROUPS);
+      if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+      ext(EXT_L21_GROUPS);
+      const long long nseg = seg_count(s.spec);
+      l21g_check_desc(d->lb != nullptr, d->ub != nullptr, d->reserved, nseg, mode == SIPX_MODE_FIBER, dir, s.spec.dims);   // (reserved: the entries lb holds)
+      if (d->lb) {
+        check_l21_weights((const T*)d->lb, nseg, "l21_groups");
+        s.weighted = true;
+        s.spec.weighted = 1;
+        s.host_lb.assign((const T*)d->lb, (const T*)d->lb + nseg);
+      }
+      break;
+    }
     case SIPX_PROJ_RANK: ext(EXT_RANK); break;
     case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;
     case SIPX_PROJ_HISTOGRAM:
@@ -426,7 +453,7 @@ std::vector<long long> default_ata_offsets(const ConfigCtx& c, const SetConfig<T
 // entries of the vectors a set takes (sipx_add_set, sipx_set_data): radii per segment, bounds per fiber coordinate, or one per row
 template <typename T>
 long long data_len(const ConfigCtx& c, const SetConfig<T>& s) {
-  if (s.weighted) return l21_groups(c, s.ext_kind);
+  if (s.weighted) return s.ext_kind == EXT_L21_GROUPS ? seg_count(s.spec) : l21_groups(c, s.ext_kind);
   if (s.seg_radii) return s.ext_kind == EXT_L21_SEG ? c.G.n[2] : seg_count(s.spec);
   if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;
   return c.G.n[s.bdir] - ((s.nblk == 1 && s.dir[0] == s.bdir) ? 1 : 0);

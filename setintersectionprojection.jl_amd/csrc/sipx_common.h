@@ -66,7 +66,8 @@ enum KernelId {
   KID_Q_UPDATE, KID_FIN_SUM, KID_RHS, KID_YL, KID_YL_MULTI, KID_ADJ_NORM, KID_LOG3, KID_PASS_FIRST, KID_PASS_LEAN, KID_PASS_PROBE,
   KID_PASS_COMPACT, KID_PASS_DIST, KID_PASS_STORE, KID_PASS_MULTI, KID_SLOT_SUMS, KID_DECIDE, KID_SAMPLE, KID_L1_SOLVE, KID_GATHER,
   KID_PS_RESCALE, KID_CARD, KID_EXT, KID_BB_RULE, KID_OTHER, KID_MF_FWD, KID_MF_ADJ, KID_L21_NORMS, KID_L21_FRAMES, KID_L21_SCALE,
-  KID_L21J_NORMS, KID_L21J_FINISH, KID_L21J_SCALE, KID_L21W_PASS, KID_L21W_SCALE, KID_COUNT
+  KID_L21J_NORMS, KID_L21J_FINISH, KID_L21J_SCALE, KID_L21W_PASS, KID_L21W_SCALE,
+  KID_L21G_NORMS, KID_L21G_FINISH, KID_L21G_SCALE, KID_COUNT
 };
 inline const char* kernel_name(int k) {
   static const char* const names[KID_COUNT] = {
@@ -75,7 +76,8 @@ inline const char* kernel_name(int k) {
       "k_pass<M_FIRST>", "k_pass<M_LEAN>", "k_pass<M_PROBE>", "k_pass<M_COMPACT>", "k_pass<M_DIST>", "k_pass<M_STORE>", "k_pass_multi",
       "k_slot_sums", "k_decide", "k_sample", "k_l1_solve", "k_gather_pack/unpack", "k_ps_rescale", "k_card_*", "ext_proj (library-backed)",
       "k_bb_rule", "other", "k_mf_fwd", "k_mf_adj", "k_l21_norms", "k_l21_frames", "k_l21_scale",
-      "k_l21j_norms", "k_l21j_finish", "k_l21j_scale", "k_l21w_part", "k_l21w_scale"};      // (the last eight: inside ext_proj)
+      "k_l21j_norms", "k_l21j_finish", "k_l21j_scale", "k_l21w_part", "k_l21w_scale",
+      "k_l21g_norms", "k_l21g_finish", "k_l21g_scale"};      // (the last eleven: inside ext_proj)
   return (k >= 0 && k < KID_COUNT) ? names[k] : "?";
 }
 // Which kernel served a launch where one observer name covers two of them (the z-marching product and right-hand side run

@@ -40,12 +40,13 @@ EXPORTED_SYMBOLS = [
     "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev", "sipx_segment_norms", "sipx_segment_norms_dev",
     "sipx_l21_norm", "sipx_l21_norm_dev", "sipx_l21_norms", "sipx_l21_norms_dev",
     "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev", "sipx_l21_weighted_norm", "sipx_l21_weighted_norm_dev",
+    "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
-        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15}
+        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -62,6 +63,20 @@ L21_WEIGHTS_NO_FRAMES = ("the l2,1 ball per frame takes no weights: use (\"l21\"
                          "which take one weight per group")
 L21_WEIGHTS_NO_COARSE = ("multilevel: a weighted l2,1 set has no rule that takes its weights to a coarser grid yet -- solve on one level, "
                          "or drop the weights")
+# group sparsity over fibers or slices (csrc/l21_groups.h): one l2,1 ball whose groups are the fibers / slices of a one-block operator's
+# range; the engine's refusals, word for word, and the front end's own
+ONE_BLOCK_OPERATORS = ("identity", "D_x", "D_y", "D_z")
+L21G_ONE_BLOCK = ("the l2,1 ball over fibers or slices (l21_groups) groups the range of a one-block operator: TD_OP must "
+                  "be the identity, D_x, D_y or D_z (on TV use the l21 sets, whose groups are the grid points)")
+L21G_NEEDS_MODE = ("the l2,1 ball over fibers or slices (l21_groups) needs a fiber or slice mode: on the whole array it has "
+                   "one group and is the l2 ball -- use the l2 set")
+L21G_2D_SLICE = "for 2D models, the mode of application for l21_groups sets needs to be (fiber,x) or (fiber,z)"
+L21G_NO_TRANSFORM = "the l2,1 ball over fibers or slices (l21_groups) takes no transform: it acts on A x itself"
+L21G_NO_MINKOWSKI = "the l2,1 ball over fibers or slices (l21_groups) takes no Minkowski component"
+L21G_NO_CUSTOM = ("the l2,1 ball over fibers or slices (l21_groups) takes no custom operator: its segments are the fibers / slices of a "
+                  "grid-shaped range -- TD_OP must be the identity, D_x, D_y or D_z")
+L21G_NO_COARSE = ("multilevel: the l2,1 ball over fibers or slices (l21_groups) has no rule that takes its radius to a coarser grid yet -- "
+                  "solve on one level")
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
 TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
 TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
@@ -206,7 +221,8 @@ class set_definitions:
     max: Any
     app_mode: Tuple[str, str]
     custom_TD_OP: Tuple[Any, bool] = ((), False)
-    weights: Any = None      # the l2,1 sets on the whole array: one weight >= 0 per group (csrc/l21_weighted.h), None: the plain ball
+    weights: Any = None      # the l2,1 sets on the whole array: one weight >= 0 per group (csrc/l21_weighted.h), None: the plain ball;
+                             # l21_groups: one per fiber / slice, in the order of segment_norms (csrc/l21_groups.h)
 
 
 @dataclass
@@ -382,10 +398,39 @@ class Projector:
         self.pmin = self.pmax = 0.0
         self.transform = 0
         self.weighted = False        # an l2,1 set built with one weight per group (in lb)
-        if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint"):
+        if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint", "l21_groups"):
             raise SipxError(f"set type {st!r} takes no weights: " + L21_WEIGHTS_WHERE)
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
         self.op = None               # the operator a stand-alone call of the projector acts behind (l21: the TV range), None: the identity
+        if st == "l21_groups":
+            # group sparsity: one l2,1 ball whose groups are the fibers / slices of the range of a one-block operator (csrc/l21_groups.h);
+            # max is the radius, weights one per segment in the order of segment_norms()
+            cust = constraint.custom_TD_OP[0]
+            if not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+                raise SipxError(L21G_NO_CUSTOM)
+            if constraint.TD_OP in SPECIAL_OPERATORS:
+                raise SipxError(L21G_NO_TRANSFORM)
+            if constraint.TD_OP not in ONE_BLOCK_OPERATORS:
+                raise SipxError(L21G_ONE_BLOCK)
+            if constraint.TD_OP == "D_y" and len(n) == 2:
+                raise SipxError(UNKNOWN_OPERATOR)
+            if not self.mode:
+                raise SipxError(L21G_NEEDS_MODE)
+            if len(n) == 2 and self.mode == MODES["slice"]:
+                raise SipxError(L21G_2D_SLICE)
+            if np.ndim(constraint.max) != 0:
+                raise SipxError("the l2,1 ball over fibers or slices takes one radius (constraint.max a scalar): its segments share it")
+            if not float(constraint.max) > 0:
+                raise SipxError("Radius of L1 ball is negative")
+            self.kind, self.pmax, self.op = "l21_groups", float(constraint.max), constraint.TD_OP
+            tdn = list(n)
+            if constraint.TD_OP != "identity":
+                tdn[{"D_x": 0, "D_y": 1, "D_z": len(n) - 1}[constraint.TD_OP]] -= 1
+            nseg = int(np.prod(tdn)) // int(tdn[self.dir]) if self.mode == MODES["fiber"] else int(tdn[self.dir])
+            what = "fiber along" if self.mode == MODES["fiber"] else "slice orthogonal to"
+            self._take_weights(constraint, nseg, f"segment, a segment being a {what} dimension {self.dir + 1} of the array of shape "
+                                                 f"{tuple(tdn)} (TD_n), in the order of segment_norms()")
+            return
         if st == "l21_joint":
             # joint (vectorial) total variation: one group per pixel across the frames of TV_xy (csrc/l21_joint.h); max is the radius
             cust = constraint.custom_TD_OP[0]
@@ -593,6 +638,13 @@ class Projector:
             raise SipxError(L21_NEEDS_TV)
         if self.kind == "l21_joint" and op.kind != "TV_xy":
             raise SipxError(L21_JOINT_NEEDS_TV_XY)
+        if self.kind == "l21_groups":
+            if op.kind == "custom":
+                raise SipxError(L21G_NO_CUSTOM)
+            if op.kind != self.op:
+                raise SipxError(L21G_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
+            if getattr(op, "component", 0):
+                raise SipxError(L21G_NO_MINKOWSKI)
         if op.kind == "custom" and (self.mode or self.transform or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank",
                                                                                      "nuclear", "histogram", "subspace")):
             raise SipxError("custom sparse operators take the whole-array projectors only")
@@ -655,9 +707,9 @@ class Projector:
         if v.dtype.type != self.TF or not v.flags.c_contiguous:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
-                                                                              "subspace", "l21", "l21_joint")
-        l21 = self.kind in ("l21", "l21_joint")
-        if l21:                      # the M-vector of the TV range in the reference's row order, on the grid
+                                                                              "subspace", "l21", "l21_joint", "l21_groups")
+        l21 = self.kind in ("l21", "l21_joint", "l21_groups")
+        if l21:                      # the M-vector of the TV range (l21_groups: of its operator's) in the reference's row order, on the grid
             op = TDOperator(self.op, self.comp_grid, self.TF)
             rows = op.shape[0]
             if v.shape != (rows,):
@@ -733,7 +785,11 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
     is the engine's own too and needs no keyword: the reference has no error to preserve there.  So are ("l21", "TV_xy") on the
     in-plane gradient of a 3-D grid -- the whole array or per z-slice (csrc/l21_seg.h) -- and ("l21_joint", "TV_xy") in tensor mode,
     the ball whose groups span the frames: one budget on the sum over pixels of the l2 norm of all in-plane differences at that
-    pixel in all frames (vectorial total variation, csrc/l21_joint.h)."""
+    pixel in all frames (vectorial total variation, csrc/l21_joint.h).
+
+    ("l21_groups", op, ("fiber", d) / ("slice", d)) on the identity, D_x, D_y or D_z is group sparsity (csrc/l21_groups.h): ONE ball of
+    radius max on the sum over the fibers / slices of the array of shape TD_n of their l2 norms, optionally with one weight per segment
+    (weights, in the order of segment_norms()).  ("l2", op, same mode) gives every segment a ball of its own instead."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -751,7 +807,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.max = np.asarray(c.max, TF)
         if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
             c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
-        if c.set_type in ("l21", "l21_joint"):
+        if c.set_type in ("l21", "l21_joint", "l21_groups"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -1823,11 +1879,12 @@ def segment_norms(x, comp_grid, TD_OP: str, app_mode, norm: str):
     return out
 
 
-def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after, weights=None, groups=0):
+def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after, weights=None, groups=0, no_weights=()):
     """What l21_norm and l21_joint_norm share: x, a numpy vector or a 1-D torch tensor on a GPU, goes through the library call
     fn(ctx, *before, x, out, *after) -- its _dev form for a tensor, ordered against torch's current stream -- in a context of its
     own.  out: n3 entries (per_frame) or one, of the kind and precision of x.  weights (`groups` entries, of the kind and precision of
-    x) go between x and out: fn(ctx, *before, x, weights, out).  Returns (out, x is a tensor)."""
+    x) go between x and out: fn(ctx, *before, x, weights, out); no_weights: what takes their place when there are none (a call whose
+    weights argument may be NULL passes (None,)).  Returns (out, x is a tensor)."""
     on_dev = _is_tensor(x)
     TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
     if TF not in (np.float32, np.float64):
@@ -1859,7 +1916,7 @@ def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after, wei
             _check_l21_weights(name, weights)
             mid = (_ptr(weights),)
     if weights is None:
-        mid = ()
+        mid = tuple(no_weights)
     ctx = Context(comp_grid, TF, device)
     try:
         if on_dev:
@@ -1900,6 +1957,26 @@ def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None, weights=None):
         return out if on_dev else out[0]
     out, on_dev = _l21_observe("l21_norm", x, comp_grid, TD_OP == "TV_xy", bool(mode), "sipx_l21_norms", (OPS[TD_OP], mode, dirn), (None,))
     return out if (on_dev or mode) else out[0]
+
+
+def l21_groups_norm(x, comp_grid, TD_OP: str, app_mode, weights=None):
+    """sum_s w_s ||(A x)[segment s]||_2 over the fibers / slices of A x, A = TD_OP one of identity, D_x, D_y, D_z: one number of the
+    working precision (that of x), (T)asum as the norms launch and the first pass of the ("l21_groups", TD_OP, app_mode) projector sum
+    and compare it (sipx_l21_groups_norm, csrc/l21_groups.h) -- used as the radius it leaves A x unwritten.  x: a numpy vector (a numpy
+    scalar comes back) or a 1-D torch tensor on a GPU (a tensor of one entry there; nothing crosses PCIe, the call orders itself
+    against torch's current stream).  weights: one finite weight >= 0 per segment in the order of segment_norms(), of the kind and
+    precision of x; None: every weight 1."""
+    TF = _tensor_TF("x", x) if _is_tensor(x) else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("l21_groups_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    P = Projector(set_definitions("l21_groups", TD_OP, 0.0, 1.0, tuple(app_mode)), comp_grid, TF)      # mode, direction and the refusals
+    nseg = P.nseg(TDOperator(TD_OP, comp_grid, TF))
+    fn = "sipx_l21_groups_norm"
+    if weights is None:
+        out, on_dev = _l21_observe("l21_groups_norm", x, comp_grid, False, False, fn, (OPS[TD_OP], P.mode, P.dir), (), None, 0, (None,))
+    else:
+        out, on_dev = _l21_observe("l21_groups_norm", x, comp_grid, False, False, fn, (OPS[TD_OP], P.mode, P.dir), (), weights, nseg)
+    return out if on_dev else out[0]
 
 
 def l21_joint_norm(x, comp_grid, weights=None):

@@ -26,6 +26,8 @@ def constraint2coarse(constraint, comp_grid, cf):
     n = tuple(int(v) for v in comp_grid.n)
     dim3 = len(n) == 3 and n[2] > 1
     for c in constraint:
+        if c.set_type == "l21_groups":
+            raise host.SipxError(host.L21G_NO_COARSE)
         if getattr(c, "weights", None) is not None:
             raise host.SipxError(host.L21_WEIGHTS_NO_COARSE)
         if c.set_type == "rank":
