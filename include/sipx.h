@@ -148,7 +148,25 @@ enum {
                                 and custom operators, transforms, Minkowski components and contexts with a communicator, a slab
                                 decomposition or set ownership are refused, each in words of its own.  sipx_set_data(_dev) replaces
                                 the weights of a set built with weights (lb, nseg entries; ub refused).  sipx_project takes the
-                                M-vector of the operator's range in the reference's row order; sipx_l21_groups_norm observes the norm */
+                                M-vector of the operator's range in the reference's row order; sipx_l21_groups_norm observes the norm */,
+  SIPX_PROJ_TNV         = 17 /* total nuclear variation (no counterpart in the reference): the nuclear-norm ball
+                                { v : sum_{(i,j)} ||J_ij||_* <= pmax } on the range of SIPX_OP_TV_XY, J_ij the 2 x n3 matrix whose column
+                                k is the (D_y, D_x) pair of pixel (i, j) in frame k -- the groups, members and pads of
+                                SIPX_PROJ_L21_JOINT, whose ball is the Frobenius member of the same family; here the frames share
+                                the DIRECTION of their gradients, not only where the edges are.  op must be SIPX_OP_TV_XY (a 3-D
+                                grid), mode WHOLE, transform NONE, no custom operator: anything else is refused with "total nuclear
+                                variation couples the frames of TV_xy: TD_OP must be TV_xy, mode tensor, no transform"; lb = ub =
+                                NULL (vectors are refused with a text that names SIPX_PROJ_L21_JOINT as the weighted set); pmax =
+                                tau > 0 ("Radius of L1 ball is negative" otherwise, NaN included).  Per pixel the Gram matrix
+                                J J' from float64 sums in the fixed order of SIPX_PROJ_L21_JOINT (Float64: in twice the working
+                                precision), its two singular values sigma1 >= sigma2 rounded once to TF and the left singular
+                                vector of sigma1; the threshold of SIPX_PROJ_L1 on the 2 n1 n2 numbers sigma; every frame's pair
+                                multiplied by f2 I + (f1 - f2) u1 u1', f_i = max(sigma_i - theta, 0) / sigma_i; an input inside
+                                the ball is not written, -0.0 included; rows a block does not have are neither used nor written;
+                                no floating-point atomics: two calls give the same bits (csrc/tnv.h).  Holds no replaceable
+                                vectors.  Contexts with a communicator, a slab decomposition or set ownership refuse it, as they
+                                refuse the operator.  sipx_project takes the M-vector of the TV_xy range in the row order of
+                                SIPX_OP_TV_XY; sipx_tnv_norm observes the norm */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -420,6 +438,13 @@ int sipx_l21_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, 
  * sipx_l21_norm_dev against the caller's stream.  Refused where the set is refused (2-D grids, sharded contexts). */
 int sipx_l21_joint_norm(sipx_ctx* ctx, const void* x, void* out);
 int sipx_l21_joint_norm_dev(sipx_ctx* ctx, const void* x, void* out);
+/* The total nuclear variation of the frames of x: *out = one TF, the sum over the pixels of the two singular values of SIPX_PROJ_TNV on
+ * [D_y; D_x] x, x TF[N] on the 3-D grid of the context: the Gram march and the decomposition of the projector, the sum from the first
+ * pass of its threshold search.  CONTRACT: the value is the very number the projector compares with pmax, so a radius observed on x
+ * leaves [D_y; D_x] x unwritten.  x, out: host memory; the _dev form takes both in device memory of the context's GPU, ordered like
+ * sipx_l21_norm_dev against the caller's stream.  Refused where the set is refused (2-D grids, sharded contexts). */
+int sipx_tnv_norm(sipx_ctx* ctx, const void* x, void* out);
+int sipx_tnv_norm_dev(sipx_ctx* ctx, const void* x, void* out);
 /* The weighted total variation of x: *out = one TF, (TF) sum_p w_p g_p over the groups of SIPX_PROJ_L21 behind op (SIPX_OP_TV or
  * SIPX_OP_TV_XY; joint = 0, w TF[N] in the grid's column-major point order) or of SIPX_PROJ_L21_JOINT (joint != 0, op SIPX_OP_TV_XY, w
  * TF[n1 n2] in pixel order), summed by the first pass of the weighted projector (csrc/l21_weighted.h).  CONTRACT: the value is the

@@ -61,6 +61,7 @@ const OPS  = Dict("identity" => 0, "D_x" => 1, "D_y" => 2, "D_z" => 3, "TV" => 4
 # SIPX_OP_TV_XY (include/sipx.h): the in-plane gradient [D_y; D_x] of a 3-D grid, libsipx's own.  The reference's get_TD_operator has no
 # such name, so setup_constraints of this shim cannot build the set; the code is mirrored for callers of the C ABI.
 const SIPX_OP_TV_XY = 6
+const SIPX_PROJ_TNV = 17     # total nuclear variation on the range of TV_xy (include/sipx.h), set_type = "tnv"
 const MODE = Dict("matrix" => 0, "tensor" => 0, "fiber" => 1, "slice" => 2)
 const SPECIAL = ("DFT", "DCT", "wavelet", "curvelet")          # src/setup_constraints.jl:54
 # the seven @timeit sections of src/PARSDMM.jl:40,100,105,113,152,163,229
@@ -126,6 +127,14 @@ function projector_fields(c, TF)
             error("the joint l2,1 ball groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor")
         c.max > 0 || error("Radius of L1 ball is negative")
         return (15, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
+    # total nuclear variation: the nuclear-norm ball on the 2 x n3 Jacobians of the pixels of TV_xy (include/sipx.h, SIPX_PROJ_TNV; as for
+    # "l21_joint", the tag reaches libsipx only from a caller that assembles the descriptor list itself, with OPS["TV_xy"]); no weights
+    if st == "tnv"
+        op == "TV_xy" && c.custom_TD_OP[1] == [] && c.app_mode[1] in ("matrix", "tensor") ||
+            error("total nuclear variation couples the frames of TV_xy: TD_OP must be TV_xy, mode tensor, no transform")
+        c.max > 0 || error("Radius of L1 ball is negative")
+        return (SIPX_PROJ_TNV, 0.0, Float64(c.max), nothing_[3:5]...)
     end
     # group sparsity: the l2,1 ball whose groups are the fibers / slices of the range of a one-block operator (include/sipx.h,
     # SIPX_PROJ_L21_GROUPS; not a set of the reference).  Without weights: the binding does not carry them yet.

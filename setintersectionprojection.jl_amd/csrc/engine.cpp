@@ -384,7 +384,7 @@ class Engine : public EngineBase {
     for (const auto& s : sets_) {
       if (s.seg_radii) refuse_sharded(ctx, Sharded::RADII);
       if (s.op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
-      if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG || s.ext_kind == EXT_L21_JOINT) refuse_sharded(ctx, Sharded::L21);
+      if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG || s.ext_kind == EXT_L21_JOINT || s.ext_kind == EXT_TNV) refuse_sharded(ctx, Sharded::L21);
       if (s.ext_kind == EXT_L21_GROUPS) refuse_sharded(ctx, Sharded::L21_GROUPS);
     }
     FinalizePlan P;
@@ -3312,6 +3312,7 @@ class Engine : public EngineBase {
     const bool groups = d->proj == SIPX_PROJ_L21_GROUPS;
     if (d->proj == SIPX_PROJ_L21_JOINT && d->op != SIPX_OP_TV_XY)
       throw std::runtime_error(L21_JOINT_ROUTE);
+    if (d->proj == SIPX_PROJ_TNV && d->op != SIPX_OP_TV_XY) throw std::runtime_error(TNV_ROUTE);
     if (groups && d->op != SIPX_OP_IDENTITY && d->op != SIPX_OP_DX && d->op != SIPX_OP_DY && d->op != SIPX_OP_DZ)
       throw std::runtime_error(L21G_ONE_BLOCK);
     if (!groups && d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY)
@@ -3337,12 +3338,14 @@ class Engine : public EngineBase {
   }
 
   // sipx_l21_norm(s)(_dev), sipx_l21_joint_norm(_dev): what the (proj, op, mode) set compares with its radius on A x -- ||TV x||_2,1 or
-  // its TV_xy form, the n3 per-frame sums of TV_xy with (slice, z), the sum over the pixels of the joint set -- by the observe() of a
+  // its TV_xy form, the n3 per-frame sums of TV_xy with (slice, z), the sum over the pixels of the joint set or of the singular values of
+  // SIPX_PROJ_TNV (sipx_tnv_norm) -- by the observe() of a
   // throw-away projector of that set (ext_group.hip): the launches and the sums of its project()
   void l21_norms(int proj, int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device, bool query) override {
     auto need_x_out = [&] { if (!x || !out) throw std::runtime_error("l2,1 norm: x and out are needed"); };
     if (proj == SIPX_PROJ_L21 && !query) need_x_out();    // (sipx_l21_norm refuses a null pointer before the context is looked at)
     SIPX_HIP(hipSetDevice(device_));
+    if (proj == SIPX_PROJ_TNV && op != SIPX_OP_TV_XY) throw std::runtime_error(TNV_ROUTE);
     if (op != SIPX_OP_TV && op != SIPX_OP_TV_XY)
       throw std::runtime_error("the l2,1 ball acts on the range of the TV operator: TD_OP must be TV (D2D, D3D)");
     const ConfigCtx ctx = config_ctx();
@@ -3434,7 +3437,10 @@ class Engine : public EngineBase {
 
   void project(const sipx_set_desc* d, void* v, int64_t len) override {
     SIPX_HIP(hipSetDevice(device_));
-    if (d->proj == SIPX_PROJ_L21 || d->proj == SIPX_PROJ_L21_JOINT || d->proj == SIPX_PROJ_L21_GROUPS) { project_l21(d, v, len); return; }
+    if (d->proj == SIPX_PROJ_L21 || d->proj == SIPX_PROJ_L21_JOINT || d->proj == SIPX_PROJ_L21_GROUPS || d->proj == SIPX_PROJ_TNV) {
+      project_l21(d, v, len);
+      return;
+    }
     Grid g1;
     g1.n[0] = len; g1.n[1] = 1; g1.n[2] = 1; g1.N = len; g1.st[0] = 1; g1.st[1] = len; g1.st[2] = len;
     DeviceMemory tmp;

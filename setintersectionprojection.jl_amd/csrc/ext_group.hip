@@ -16,6 +16,8 @@
 // passes k_l21w_part / k_l21w_finish in batches gated on a device flag, then k_l21w_scale; without weights not one launch differs.
 // The ball whose groups are the fibers or slices of a one-block operator's range (EXT_L21_GROUPS, l21_groups.h, GroupsProj) shares only the
 // weighted iteration (L21WSearch): its norms and its scale kernel are its own.
+// Total nuclear variation (EXT_TNV, tnv.h, TnvProj) has the groups and the z-march of the joint ball, two numbers per pixel in the search
+// and a 2 x 2 matrix per pixel in place of the weight.
 // Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the two projectors.
 // A projector's observe() runs the norms launch and the first sum of its own project(): what it reports is what project() decides on.
 #include "ext_family.h"
@@ -24,6 +26,7 @@
 #include "l21_seg.h"
 #include "l21_groups.h"
 #include "l21_weighted.h"
+#include "tnv.h"
 
 namespace sipx {
 
@@ -353,6 +356,120 @@ __global__ __launch_bounds__(BLOCK) void k_l21j_finish(unsigned L, int nchunk, c
     g[p] = l21_norm_of<T>(l21_joint_total(part, (long long)L, (long long)p, nchunk));
 }
 
+// ---- EXT_TNV: the nuclear-norm ball on the 2 x n3 Jacobians of the pixels, on the range of TV_xy (tnv.h) ------------------------------------
+//     k_tnv_gram      the z-march of k_l21j_norms with three sums per pixel: (s, rot) of the pixel,   reads 2 N words, writes 4 L
+//                     or the chunk sums part[(c W + word) L + pixel], W = 3 (Float64: 6)              (or nchunk W L doubles)
+//     k_tnv_finish    more than one chunk: (s, rot) from the chunk sums, ascending c                  reads nchunk W L doubles, writes 4 L
+//     the engine's l1 threshold search on the 2 L numbers s (and the Float64 refinement above)         its passes over 2 L words
+//     k_tnv_apply     M_p from (s, rot, theta) at the pixel of grid point p, (vy, vx) <- M_p (vy, vx)  reads 2 N + 4 L words, writes 2 N
+template <typename T, int VW, bool PART>
+__global__ __launch_bounds__(BLOCK) void k_tnv_gram(L21JArgs a, const T* __restrict__ v, T* __restrict__ s, T* __restrict__ rot,
+                                                    double* __restrict__ part) {
+  const unsigned L = (unsigned)a.G.st[2], n3 = (unsigned)a.G.n[2], nvec = L / VW;
+  const unsigned items = nvec * (PART ? (unsigned)a.plan.nchunk : 1u), step = gridDim.x * BLOCK;
+  const T* const vx = v + (size_t)a.bstride;
+  for (unsigned it = blockIdx.x * BLOCK + threadIdx.x; it < items; it += step) {
+    const unsigned c = PART ? it / nvec : 0u, p = (it - c * nvec) * VW;
+    const Coord cd = coords(a.G, (long long)p);                 // (p < L: the pixel's i, j)
+    const bool my = l21_member(cd.j, (int)a.G.n[1]);
+    bool mx[VW];
+#pragma unroll
+    for (int w = 0; w < VW; ++w) mx[w] = l21_member(cd.i + w, (int)a.G.n[0]);
+    const unsigned z0 = PART ? (unsigned)a.plan.z0((int)c) : 0u, z1 = PART ? (unsigned)a.plan.z1((int)c, (int)n3) : n3;
+    TnvGram acc[VW];
+#pragma unroll
+    for (int w = 0; w < VW; ++w) acc[w] = TnvGram{};
+    unsigned k = z0, off = z0 * L + p;
+    for (; k + L21J_BATCH <= z1; k += L21J_BATCH, off += L21J_BATCH * L) {
+      Vec<T, VW> y[L21J_BATCH], x[L21J_BATCH];
+#pragma unroll
+      for (int u = 0; u < L21J_BATCH; ++u) {
+        y[u] = ldv<T, VW>(v + off + u * L);
+        x[u] = ldv<T, VW>(vx + off + u * L);
+      }
+#pragma unroll
+      for (int u = 0; u < L21J_BATCH; ++u)
+#pragma unroll
+        for (int w = 0; w < VW; ++w) tnv_gram_add<T>(acc[w], y[u].v[w], x[u].v[w], my, mx[w]);
+    }
+    for (; k < z1; ++k, off += L) {
+      const Vec<T, VW> y = ldv<T, VW>(v + off), x = ldv<T, VW>(vx + off);
+#pragma unroll
+      for (int w = 0; w < VW; ++w) tnv_gram_add<T>(acc[w], y.v[w], x.v[w], my, mx[w]);
+    }
+    if constexpr (PART) {
+#pragma unroll
+      for (int w = 0; w < VW; ++w) tnv_gram_store<T>(acc[w], part, (long long)L, (long long)(p + w), (int)c);
+    } else {
+      Vec<T, VW> s1, s2, cs, sn;
+#pragma unroll
+      for (int w = 0; w < VW; ++w) {
+        const TnvPixel<T> o = tnv_decompose<T>(acc[w]);
+        s1.v[w] = o.s1; s2.v[w] = o.s2; cs.v[w] = o.cs; sn.v[w] = o.sn;
+      }
+      stv<T, VW>(s + p, s1);
+      stv<T, VW>(s + L + p, s2);
+      stv<T, VW>(rot + p, cs);
+      stv<T, VW>(rot + L + p, sn);
+    }
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_tnv_finish(unsigned L, int nchunk, const double* __restrict__ part, T* __restrict__ s,
+                                                      T* __restrict__ rot) {
+  for (unsigned p = blockIdx.x * BLOCK + threadIdx.x; p < L; p += gridDim.x * BLOCK) {
+    const TnvPixel<T> o = tnv_decompose<T>(tnv_gram_total<T>(part, (long long)L, (long long)p, nchunk));
+    s[p] = o.s1; s[L + p] = o.s2; rot[p] = o.cs; rot[L + p] = o.sn;
+  }
+}
+// Grid-stride over the N grid points as k_l21_scale, VW points of one grid line (one frame) per thread: the thread builds M_p of its VW
+// pixels once and multiplies the pair (vy, vx) of each; nothing at all is read when the search found v inside the ball.  Rows a block
+// does not have enter as zeros and are not written.
+template <typename T, int VW>
+__global__ __launch_bounds__(BLOCK) void k_tnv_apply(L21Args a, T* __restrict__ v, const T* __restrict__ s, const T* __restrict__ rot,
+                                                     const ProjScalars<T>* __restrict__ ps, const T* __restrict__ theta) {
+  if (!ps->need) return;
+  const T th = theta ? theta[0] : ps->theta;                // (Float64: the threshold k_l21_theta_final left)
+  const unsigned L = (unsigned)a.G.st[2], nvec = (unsigned)(a.G.N / VW), step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    const Coord c = coords(a.G, (long long)p);
+    const unsigned px = p - (unsigned)c.k * L;
+    const Vec<T, VW> s1 = ldv<T, VW>(s + px), s2 = ldv<T, VW>(s + L + px), cs = ldv<T, VW>(rot + px), sn = ldv<T, VW>(rot + L + px);
+    bool my[VW], mx[VW];
+    l21_members<VW>(a, c, 0, my);
+    l21_members<VW>(a, c, 1, mx);
+    T* const py = v + p;
+    T* const pxx = v + (size_t)a.bstride + p;
+    Vec<T, VW> y = ldv<T, VW>(py), x = ldv<T, VW>(pxx);
+    bool ally = true, allx = true;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      double m00, m01, m11;
+      tnv_matrix<T>(s1.v[k], s2.v[k], cs.v[k], sn.v[k], th, m00, m01, m11);
+      T oy, ox;
+      tnv_apply_pair<T>(m00, m01, m11, y.v[k], x.v[k], my[k], mx[k], oy, ox);
+      y.v[k] = oy; x.v[k] = ox;
+      ally = ally && my[k];
+      allx = allx && mx[k];
+    }
+    if (ally) {
+      stv<T, VW>(py, y);
+    } else {              // the far face along y: rows the block does not have are not written
+#pragma unroll
+      for (int k = 0; k < VW; ++k)
+        if (my[k]) py[k] = y.v[k];
+    }
+    if (allx) {
+      stv<T, VW>(pxx, x);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VW; ++k)
+        if (mx[k]) pxx[k] = x.v[k];
+    }
+  }
+}
+
 // ---- EXT_L21_GROUPS: the l2,1 ball whose groups are the fibers or slices of a one-block operator's range (l21_groups.h) ----------------------
 //     fibers: k_seg_observe<T, SEGN_L2> (seg_norm.h)      g[s] in segn_pass1's order                     reads N words, writes nseg
 //     slices: k_l21g_part                                  one (tile, chunk) per workgroup: its partial    reads N words, writes 2 ntA F nchunk doubles
@@ -478,6 +595,11 @@ static void l21_joint_check_spec(const ExtSpec& sp) {
   l21_check_spec(sp);
   if (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0 || sp.mode != SIPX_MODE_WHOLE)
     throw std::runtime_error(L21_JOINT_ROUTE);
+}
+static void tnv_check_spec(const ExtSpec& sp) {
+  l21_check_spec(sp);
+  if (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0 || sp.mode != SIPX_MODE_WHOLE) throw std::runtime_error(TNV_ROUTE);
+  if (sp.weighted || sp.lb || sp.ub) throw std::runtime_error(TNV_NO_WEIGHTS);
 }
 static L21Args l21_args(const ExtSpec& sp) {
   L21Args a;
@@ -779,6 +901,89 @@ struct FrameProj : ExtImpl<T> {
   }
 };
 
+// ---- EXT_TNV: the nuclear-norm ball on the pixels' Jacobians (tnv.h) -- the Gram march, the engine's search on the 2 L singular values,
+// Float64: the refinement, the 2 x 2 matrices.  BallProj's sequence with s in place of g; the search runs on 2 L entries, which the scratch
+// every caller hands over (N entries at least) holds: a 3-D grid has n3 >= 2 frames, so 2 L <= N -- checked when the projector is built.
+template <typename T>
+struct TnvProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  L21JointPlan plan{};
+  long long L = 0;                     // pixels
+  T* s = nullptr;                      // [sigma1; sigma2], 2 L entries: the array of the search
+  T* rot = nullptr;                    // [cs; sn], 2 L entries
+  double* part = nullptr;              // the chunk sums, nchunk tnv_words L entries, when the plan chunks
+  double* tpart = nullptr;             // Float64: the partial sums of k_l21_theta_part
+  T* theta = nullptr;                  // Float64: the threshold k_tnv_apply applies
+  SearchState<T> search;
+  ProjScalars<T>* ps_obs = nullptr;    // the state of observe's search, taken at its first call
+  void reset() override { search.reinit(stream); }
+  TnvProj(const ExtSpec& spec, hipStream_t st) : ExtImpl<T>(spec, st) {
+    tnv_check_spec(sp);
+    if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+    L = sp.G.st[2];
+    if (2 * L > sp.G.N) throw std::runtime_error("total nuclear variation: the search over 2 n1 n2 singular values needs a grid of at least 2 frames");
+    plan = l21_joint_plan(L, sp.G.n[2], (int)sizeof(T));
+    s = this->template alloc<T>(2 * L);
+    rot = this->template alloc<T>(2 * L);
+    if (plan.nchunk > 1) part = this->template alloc<double>((size_t)plan.nchunk * tnv_words<T>() * L);
+    if (sizeof(T) == 8) {
+      tpart = this->template alloc<double>(3 * L21_THETA_GRID);
+      theta = this->template alloc<T>(1);
+    }
+    search.build(this->mem, st, 0);
+  }
+  // (s, rot) <- the singular values and rotations of the pixels of v
+  void gram(const T* v) {
+    constexpr int W = l21_vec_width<T>();
+    const bool wide = l21_wide(sp, v, s) && aligned16(rot), chunks = plan.nchunk > 1;
+    L21JArgs a;
+    a.G = sp.G;
+    a.G.set_fast_div();
+    a.bstride = sp.bstride;
+    a.plan = plan;
+    {
+      void (*const k)(L21JArgs, const T*, T*, T*, double*) = chunks ? (wide ? k_tnv_gram<T, W, true> : k_tnv_gram<T, 1, true>)
+                                                                    : (wide ? k_tnv_gram<T, W, false> : k_tnv_gram<T, 1, false>);
+      ObsScope obs(KID_TNV_GRAM, stream, (double)(2 * sp.G.N + 4 * L) * sizeof(T));
+      hipLaunchKernelGGL(k, dim3(fit_grid(L / (wide ? W : 1) * plan.nchunk, NB)), dim3(BLOCK), 0, stream, a, v, s, rot, part);
+      SIPX_HIP(hipGetLastError());
+    }
+    if (chunks) {
+      ObsScope obs(KID_TNV_FINISH, stream, (double)L * (plan.nchunk * tnv_words<T>() * sizeof(double) + 4 * sizeof(T)));
+      hipLaunchKernelGGL((k_tnv_finish<T>), dim3(fit_grid(L, NB)), dim3(BLOCK), 0, stream, (unsigned)L, plan.nchunk, part, s, rot);
+      SIPX_HIP(hipGetLastError());
+    }
+  }
+  void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
+    constexpr int W = l21_vec_width<T>();
+    ProjScalars<T>* ps = search.pick(feas);
+    gram(v);
+    K<T>::proj_scalars_arr(stream, 2 * L, s, PX_L1, T(0), (T)sp.pmax, ps, partials, maxpart, compact, 2 * L);
+    if constexpr (sizeof(T) == 8) {
+      const int grid = fit_grid(2 * L, L21_THETA_GRID);
+      hipLaunchKernelGGL(k_l21_theta_part, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)(2 * L), s, ps, tpart);
+      hipLaunchKernelGGL(k_l21_theta_final, dim3(1), dim3(BLOCK), 0, stream, grid, (unsigned)(2 * L), (double)sp.pmax, tpart, ps, theta);
+      SIPX_HIP(hipGetLastError());
+    }
+    const bool wide = l21_wide(sp, v, s) && aligned16(rot);
+    ObsScope obs(KID_TNV_APPLY, stream, (double)(4 * sp.G.N + 4 * L) * sizeof(T));
+    hipLaunchKernelGGL((wide ? k_tnv_apply<T, W> : k_tnv_apply<T, 1>), dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream,
+                       l21_args(sp), v, s, rot, ps, theta);
+    SIPX_HIP(hipGetLastError());
+  }
+  // out[0] <- ||s||_1 as project compares it: its Gram launch into its s, then the first pass of a search with a new state and an
+  // infinite radius -- the sum, and the rounding to T, of project's decision.  The warm starts stay.
+  void observe(const T* v, T* out, double* partials, T* maxpart, T* compact) override {
+    if (!ps_obs) ps_obs = this->template alloc<ProjScalars<T>>(1);
+    gram(v);
+    K<T>::ps_init(stream, ps_obs, nullptr);
+    K<T>::proj_scalars_arr(stream, 2 * L, s, PX_L1, T(0), (T)INFINITY, ps_obs, partials, maxpart, compact, 2 * L);
+    hipLaunchKernelGGL((k_l21_pick<T>), dim3(1), dim3(64), 0, stream, ps_obs, out);
+    SIPX_HIP(hipGetLastError());
+  }
+};
+
 // ---- EXT_L21_GROUPS: one ball whose groups are the fibers or slices of the valid block (l21_groups.h) ---------------------------------------
 // The norms by the plan of l21_groups.h, the iteration of the weighted route on the nseg pairs (g, w), k_l21g_scale.  Built without weights
 // w is a vector of ones: not one launch, and not one bit, differs from the set built with np.ones(nseg).  Nothing is kept between calls.
@@ -885,6 +1090,7 @@ struct GroupsProj : ExtImpl<T> {
 template <typename T>
 ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
   if (spec.kind == EXT_L21_GROUPS) return new GroupsProj<T>(spec, stream);
+  if (spec.kind == EXT_TNV) return new TnvProj<T>(spec, stream);
   if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);
   if (spec.kind != EXT_L21 && spec.kind != EXT_L21_JOINT) throw std::runtime_error("unknown external projector");
   return new BallProj<T>(spec, stream);

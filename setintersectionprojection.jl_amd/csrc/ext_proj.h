@@ -11,11 +11,17 @@ enum { EXT_L1_DFT = 1, EXT_RANK = 2, EXT_NUCLEAR = 3, EXT_CARD_SEG = 4, EXT_HIST
        EXT_L21 = 14 /* the l2,1 ball across the blocks of the TV / TV_xy operator (l21.h) */,
        EXT_L21_SEG = 15 /* the l2,1 ball of every z-slice across the blocks of TV_xy (l21_seg.h) */,
        EXT_L21_JOINT = 16 /* the l2,1 ball whose groups span the blocks of TV_xy and the frames (l21_joint.h) */,
-       EXT_L21_GROUPS = 17 /* the l2,1 ball whose groups are the fibers or slices of a one-block operator's range (l21_groups.h) */ };
+       EXT_L21_GROUPS = 17 /* the l2,1 ball whose groups are the fibers or slices of a one-block operator's range (l21_groups.h) */,
+       EXT_TNV = 18 /* total nuclear variation: the nuclear-norm ball on the 2 x n3 Jacobians of the pixels of TV_xy (tnv.h) */ };
 
 // The refusal of an EXT_L21_JOINT set off its operator or mode, worded once: set_config.h (sipx_add_set), the stand-alone calls of the
 // engine and the projector's own check throw this text (its cases: tests/test_l21_joint_cpu.py, tests/test_gpu_l21_joint.py)
 constexpr const char* L21_JOINT_ROUTE = "the joint l2,1 ball groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor";
+// The refusals of an EXT_TNV set, worded once in the same way (their cases: tests/test_tnv_cpu.py, tests/test_gpu_tnv.py): off its operator
+// or mode or behind a transform, and with vectors in lb / ub
+constexpr const char* TNV_ROUTE = "total nuclear variation couples the frames of TV_xy: TD_OP must be TV_xy, mode tensor, no transform";
+constexpr const char* TNV_NO_WEIGHTS = "total nuclear variation (tnv) takes no weights or vectors (lb, ub): the weighted set across the frames is "
+                                       "(\"l21_joint\", \"TV_xy\")";
 
 // What an ExtProj acts on: the valid extents `dims` (TD_n of the operator) inside the padded grid G (strides G.st),
 // split into segments by the application mode (whole array, fibers along `dir`, slices orthogonal to `dir`).
@@ -53,7 +59,7 @@ class ExtProj {
   void project(T* v, bool feas, double* partials, T* maxpart, T* compact);
   // the l2,1 sets (ext_group.hip): out (device) <- what project(v, ...) would compare with the radius, summed and rounded by the
   // projector's own launches -- ||v||_2,1 for EXT_L21, the sum of the n1 n2 group norms for EXT_L21_JOINT, one sum per z-slice (n3
-  // entries) for EXT_L21_SEG, the weighted sum of the segment norms for EXT_L21_GROUPS.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
+  // entries) for EXT_L21_SEG, the weighted sum of the segment norms for EXT_L21_GROUPS, the sum of the 2 n1 n2 singular values for EXT_TNV.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
   void observe(const T* v, T* out, double* partials, T* maxpart, T* compact);
   // rank projector: calls since construction, calls served by the warm-started subspace route, calls that decomposed fully,
   // products with the Gram matrices the subspace route spent (all zero for the other kinds)

@@ -212,6 +212,11 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
   // the joint l2,1 ball (l21_joint.h) is one set on one operator: its refusal names the way out before any general one
   if (d->proj == SIPX_PROJ_L21_JOINT && (s.op != SIPX_OP_TV_XY || mode != SIPX_MODE_WHOLE || d->transform != SIPX_TRANSFORM_NONE))
     throw std::runtime_error(L21_JOINT_ROUTE);
+  // so is total nuclear variation (tnv.h), which takes no vectors either
+  if (d->proj == SIPX_PROJ_TNV) {
+    if (s.op != SIPX_OP_TV_XY || mode != SIPX_MODE_WHOLE || d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(TNV_ROUTE);
+    if (d->lb || d->ub) throw std::runtime_error(TNV_NO_WEIGHTS);
+  }
   // so is the l2,1 ball over fibers or slices (l21_groups.h): a one-block operator, no transform, no component, a mode
   if (d->proj == SIPX_PROJ_L21_GROUPS) {
     if (s.custom || s.nblk > 1) throw std::runtime_error(L21G_ONE_BLOCK);
@@ -228,7 +233,7 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (s.nblk > 1 && !frames) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
   }
   auto ext = [&](int kind) {
-    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
+    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT && kind != EXT_TNV) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
     s.ext_kind = kind;
     s.spec.kind = kind;
     s.spec.ndim = c.ndim;
@@ -392,6 +397,12 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
       ext(EXT_L21_JOINT);
       weights("l21_joint");
+      break;
+    case SIPX_PROJ_TNV:        // total nuclear variation: the Jacobians of the pixels across the frames of TV_xy (op, mode, transform, vectors: above)
+      if (s.comp) throw std::runtime_error("the TV_xy operator takes no Minkowski component");      // (the operator's own text, for sipx_project)
+      refuse_sharded(c, Sharded::L21);
+      if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+      ext(EXT_TNV);
       break;
     case SIPX_PROJ_L21_GROUPS: {  // group sparsity: one group per fiber or slice of the valid block (op, transform, component, mode: above)
       if (c.ndim == 2 && mode == SIPX_MODE_SLICE) throw std::runtime_error(L21G_2D_SLICE);

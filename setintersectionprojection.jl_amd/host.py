@@ -40,13 +40,14 @@ EXPORTED_SYMBOLS = [
     "sipx_q_terms", "sipx_set_data", "sipx_set_data_dev", "sipx_segment_norms", "sipx_segment_norms_dev",
     "sipx_l21_norm", "sipx_l21_norm_dev", "sipx_l21_norms", "sipx_l21_norms_dev",
     "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev", "sipx_l21_weighted_norm", "sipx_l21_weighted_norm_dev",
-    "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev",
+    "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev", "sipx_tnv_norm", "sipx_tnv_norm_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
-        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16}
+        "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16,
+        "tnv": 17}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -56,6 +57,11 @@ L21_WHOLE_ONLY = "the l2,1 ball applies to the whole array (mode matrix/tensor)"
 L21_FRAMES_Z = "the l2,1 ball on TV_xy: frames run along z -- the mode must be (slice, z), or tensor for the whole array"
 # the joint l2,1 ball (csrc/l21_joint.h): one group per pixel across the frames of TV_xy; the engine's refusal, word for word
 L21_JOINT_NEEDS_TV_XY = "the joint l2,1 ball groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor"
+# total nuclear variation (csrc/tnv.h): the nuclear-norm ball on the 2 x n3 Jacobians of the pixels of TV_xy; the engine's refusals
+# (csrc/ext_proj.h), word for word
+TNV_NEEDS_TV_XY = "total nuclear variation couples the frames of TV_xy: TD_OP must be TV_xy, mode tensor, no transform"
+TNV_NO_WEIGHTS = ("total nuclear variation (tnv) takes no weights or vectors (lb, ub): the weighted set across the frames is "
+                  "(\"l21_joint\", \"TV_xy\")")
 # one weight per group (csrc/l21_weighted.h): what takes them, and what to do where they are refused
 L21_WEIGHTS_WHERE = ("weights belong to the l2,1 sets on the whole array -- (\"l21\", \"TV\"), (\"l21\", \"TV_xy\") in tensor mode and "
                      "(\"l21_joint\", \"TV_xy\"): drop them, or use one of these sets")
@@ -398,6 +404,22 @@ class Projector:
         self.pmin = self.pmax = 0.0
         self.transform = 0
         self.weighted = False        # an l2,1 set built with one weight per group (in lb)
+        if st == "tnv":
+            # total nuclear variation: the Jacobians of the pixels across the frames of TV_xy (csrc/tnv.h); max is the radius
+            cust = constraint.custom_TD_OP[0]
+            if constraint.TD_OP != "TV_xy" or not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+                raise SipxError(TNV_NEEDS_TV_XY)
+            if len(n) != 3:
+                raise SipxError(TV_XY_NEEDS_3D)
+            if self.mode:
+                raise SipxError(TNV_NEEDS_TV_XY)
+            if getattr(constraint, "weights", None) is not None or np.ndim(constraint.max) != 0 or np.ndim(constraint.min) != 0:
+                raise SipxError(TNV_NO_WEIGHTS)
+            if not float(constraint.max) > 0:
+                raise SipxError("Radius of L1 ball is negative")
+            self.seg_radii = False
+            self.kind, self.pmax, self.op = "tnv", float(constraint.max), "TV_xy"
+            return
         if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint", "l21_groups"):
             raise SipxError(f"set type {st!r} takes no weights: " + L21_WEIGHTS_WHERE)
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
@@ -638,6 +660,8 @@ class Projector:
             raise SipxError(L21_NEEDS_TV)
         if self.kind == "l21_joint" and op.kind != "TV_xy":
             raise SipxError(L21_JOINT_NEEDS_TV_XY)
+        if self.kind == "tnv" and op.kind != "TV_xy":
+            raise SipxError(TNV_NEEDS_TV_XY)
         if self.kind == "l21_groups":
             if op.kind == "custom":
                 raise SipxError(L21G_NO_CUSTOM)
@@ -707,8 +731,8 @@ class Projector:
         if v.dtype.type != self.TF or not v.flags.c_contiguous:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
-                                                                              "subspace", "l21", "l21_joint", "l21_groups")
-        l21 = self.kind in ("l21", "l21_joint", "l21_groups")
+                                                                              "subspace", "l21", "l21_joint", "l21_groups", "tnv")
+        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv")
         if l21:                      # the M-vector of the TV range (l21_groups: of its operator's) in the reference's row order, on the grid
             op = TDOperator(self.op, self.comp_grid, self.TF)
             rows = op.shape[0]
@@ -785,7 +809,9 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
     is the engine's own too and needs no keyword: the reference has no error to preserve there.  So are ("l21", "TV_xy") on the
     in-plane gradient of a 3-D grid -- the whole array or per z-slice (csrc/l21_seg.h) -- and ("l21_joint", "TV_xy") in tensor mode,
     the ball whose groups span the frames: one budget on the sum over pixels of the l2 norm of all in-plane differences at that
-    pixel in all frames (vectorial total variation, csrc/l21_joint.h).
+    pixel in all frames (vectorial total variation, csrc/l21_joint.h).  ("tnv", "TV_xy") in tensor mode is total nuclear variation
+    (csrc/tnv.h): one budget on the sum over the pixels of the nuclear norm of the 2 x n3 matrix of that pixel's in-plane gradients in
+    all frames, so that the frames share the direction of their gradients and not only where the edges are; it takes no weights.
 
     ("l21_groups", op, ("fiber", d) / ("slice", d)) on the identity, D_x, D_y or D_z is group sparsity (csrc/l21_groups.h): ONE ball of
     radius max on the sum over the fibers / slices of the array of shape TD_n of their l2 norms, optionally with one weight per segment
@@ -807,7 +833,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.max = np.asarray(c.max, TF)
         if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
             c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
-        if c.set_type in ("l21", "l21_joint", "l21_groups"):
+        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -1994,6 +2020,16 @@ def l21_joint_norm(x, comp_grid, weights=None):
                                    weights, int(n[0]) * int(n[1]))
         return out if on_dev else out[0]
     out, on_dev = _l21_observe("l21_joint_norm", x, comp_grid, True, False, "sipx_l21_joint_norm", (), ())
+    return out if on_dev else out[0]
+
+
+def tnv_norm(x, comp_grid):
+    """The total nuclear variation of the frames of x on a 3-D grid: the sum over the pixels (i, j) of the nuclear norm of the 2 x n3
+    matrix whose column k is (D_y x, D_x x) at that pixel in frame k, one number of the working precision (that of x).  Computed by
+    the Gram march, the decomposition and the first-pass sum of the ("tnv", "TV_xy") projector (sipx_tnv_norm): used as the radius it
+    leaves TV_xy x unwritten.  x: a numpy vector (a numpy scalar comes back) or a 1-D torch tensor on a GPU (a tensor of one entry
+    there; nothing crosses PCIe, the call orders itself against torch's current stream)."""
+    out, on_dev = _l21_observe("tnv_norm", x, comp_grid, True, False, "sipx_tnv_norm", (), ())
     return out if on_dev else out[0]
 
 
