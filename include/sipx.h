@@ -166,7 +166,24 @@ enum {
                                 no floating-point atomics: two calls give the same bits (csrc/tnv.h).  Holds no replaceable
                                 vectors.  Contexts with a communicator, a slab decomposition or set ownership refuse it, as they
                                 refuse the operator.  sipx_project takes the M-vector of the TV_xy range in the row order of
-                                SIPX_OP_TV_XY; sipx_tnv_norm observes the norm */
+                                SIPX_OP_TV_XY; sipx_tnv_norm observes the norm */,
+  SIPX_PROJ_L1_WEIGHTED = 18 /* the weighted l1 ball (no counterpart in the reference): { v : sum_i w_i |v_i| <= pmax } on the rows of
+                                A x, one weight per row of the operator -- the set of iteratively reweighted l1, of anisotropic TV with a
+                                weight per direction, of masks.  op: IDENTITY, DX, DY, DZ, TV or TV_XY, mode WHOLE, transform NONE, no
+                                component, no custom operator; each of the others is refused with a text that names the way out
+                                (csrc/l1_weighted.h).  lb = TF[Mtrue] finite weights >= 0 in the reference's row order (the order of A x
+                                and of y_i, l_i), reserved = Mtrue (another count is refused), ub = NULL (refused); lb = NULL: the
+                                weights come with sipx_set_data(_dev) before the first solve, until then no row is constrained.  A
+                                negative, NaN or infinite weight is refused, naming the first offender; from device memory it counts
+                                as 0.  pmax = tau > 0 ("Radius of L1 ball is negative" otherwise, NaN included).  a_i = |v_i|; asum =
+                                sum w a in twice the working precision; (TF)asum <= tau: v is not written, -0.0 included; otherwise
+                                theta by the weighted Michelot iteration of SIPX_PROJ_L21's weighted form on (a, w), and y_i =
+                                sign(v_i) max(a_i - theta w_i, 0) with the product rounded in TF; an entry on the threshold is zeroed,
+                                a row of weight 0 is neither used nor written, whatever it holds; no floating-point atomics: two
+                                calls give the same bits.  sipx_set_data(_dev) replaces the weights (lb, Mtrue entries; ub refused).
+                                Contexts with a communicator, a slab decomposition or set ownership refuse it.  sipx_project takes
+                                the M-vector of the operator's range in the reference's row order; sipx_l1_weighted_norm observes
+                                the norm */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -189,10 +206,12 @@ typedef struct {
   double pmin, pmax; /* constraint[i].min / .max (set_definitions, src/SetIntersectionProjection.jl:142-149) */
   const void* lb;    /* BOUNDS_VEC / HISTOGRAM: host TF vectors (see the kinds above); L1 / L2 / ANNULUS in mode FIBER / SLICE: NULL or
                         the radii per segment, TF[nseg]; L21 in mode WHOLE / L21_JOINT / L21_GROUPS: NULL or one weight per group
-                        (lb alone, and `reserved` holds their number); else NULL */
+                        (lb alone, and `reserved` holds their number); L1_WEIGHTED: one weight per row of the operator (lb alone,
+                        `reserved` holds their number); else NULL */
   const void* ub;
   int32_t ncvx;      /* set_Prop.ncvx[i] (src/setup_constraints.jl:89-97) */
-  int32_t reserved;  /* 0; a weighted L21 / L21_JOINT / L21_GROUPS set: the entries of lb, refused unless it is the group count */
+  int32_t reserved;  /* 0; a weighted L21 / L21_JOINT / L21_GROUPS set: the entries of lb, refused unless it is the group count;
+                        L1_WEIGHTED: the rows of the operator (Mtrue), refused otherwise */
   int32_t mode;      /* SIPX_MODE_* */
   int32_t dir;       /* direction of the fibers / normal of the slices */
   const void* basis; /* SUBSPACE: host TF[basis_rows x basis_cols], column-major (constraint.custom_TD_OP[1]) */
@@ -461,6 +480,13 @@ int sipx_l21_weighted_norm_dev(sipx_ctx* ctx, int op, int joint, const void* x, 
  * where the set is refused. */
 int sipx_l21_groups_norm(sipx_ctx* ctx, int op, int mode, int dir, const void* x, const void* w, void* out);
 int sipx_l21_groups_norm_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, const void* w, void* out);
+/* The weighted l1 norm of A x: *out = one TF, (TF) sum_i w_i |(A x)_i| over the rows of op (IDENTITY, DX, DY, DZ, TV, TV_XY), w TF[Mtrue]
+ * in the reference's row order, summed by the first pass of the SIPX_PROJ_L1_WEIGHTED projector (csrc/l1_weighted.h).  CONTRACT: the value
+ * is the very number that projector compares with pmax, so a radius observed on x leaves A x unwritten.  x, w, out: host memory, a
+ * weight that is negative, NaN or infinite is refused; the _dev form takes all three in device memory of the context's GPU, ordered like
+ * sipx_l21_norm_dev against the caller's stream, and there such a weight counts as 0.  Refused where the set is refused. */
+int sipx_l1_weighted_norm(sipx_ctx* ctx, int op, const void* x, const void* w, void* out);
+int sipx_l1_weighted_norm_dev(sipx_ctx* ctx, int op, const void* x, const void* w, void* out);
 /* nearest-neighbour resampling of an array of shape nc to shape nf, the grid transfer of PARSDMM_multi_level:
  * out[k] = in[round(1 + (k-1)(nc-1)/(nf-1))] per axis (Interpolations.BSpline(Constant()) evaluated on
  * range(1, stop=nc, length=nf); src/PARSDMM_multi_level.jl:41-45,61-65, src/interpolate_y_l.jl:32-88) */

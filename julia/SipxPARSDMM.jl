@@ -62,6 +62,10 @@ const OPS  = Dict("identity" => 0, "D_x" => 1, "D_y" => 2, "D_z" => 3, "TV" => 4
 # such name, so setup_constraints of this shim cannot build the set; the code is mirrored for callers of the C ABI.
 const SIPX_OP_TV_XY = 6
 const SIPX_PROJ_TNV = 17     # total nuclear variation on the range of TV_xy (include/sipx.h), set_type = "tnv"
+# the weighted l1 ball { sum_i w_i |(A x)_i| <= max } with one weight per row of identity, D_x, D_y, D_z, TV or TV_xy in lb, reserved = the
+# rows (include/sipx.h, csrc/l1_weighted.h), set_type = "l1_weighted".  The reference's set_definitions has no field for weights and this
+# binding does not carry them: the constant is mirrored for callers of the C ABI, projector_fields refuses the tag and names ("l1", op).
+const SIPX_PROJ_L1_WEIGHTED = 18
 const MODE = Dict("matrix" => 0, "tensor" => 0, "fiber" => 1, "slice" => 2)
 const SPECIAL = ("DFT", "DCT", "wavelet", "curvelet")          # src/setup_constraints.jl:54
 # the seven @timeit sections of src/PARSDMM.jl:40,100,105,113,152,163,229
@@ -146,6 +150,7 @@ function projector_fields(c, TF)
         c.max > 0 || error("Radius of L1 ball is negative")
         return (16, 0.0, Float64(c.max), nothing_[3:5]...)
     end
+    st == "l1_weighted" && error("the weighted l1 ball (l1_weighted, SIPX_PROJ_L1_WEIGHTED) needs one weight per row of the operator, which this binding does not carry: use the plain (\"l1\", op), or the C ABI")
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "l2"          && return (3, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "annulus"     && return (4, Float64(c.min), Float64(c.max), nothing_[3:5]...)

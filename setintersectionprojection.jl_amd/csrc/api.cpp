@@ -162,6 +162,12 @@ int sipx_l21_weighted_norm(sipx_ctx* c, int op, int joint, const void* x, const 
 int sipx_l21_weighted_norm_dev(sipx_ctx* c, int op, int joint, const void* x, const void* w, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_weighted_norm(op, joint != 0, x, w, out, true))
 }
+int sipx_l1_weighted_norm(sipx_ctx* c, int op, const void* x, const void* w, void* out) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l1_weighted_norm(op, x, w, out, false))
+}
+int sipx_l1_weighted_norm_dev(sipx_ctx* c, int op, const void* x, const void* w, void* out) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l1_weighted_norm(op, x, w, out, true))
+}
 int sipx_tnv_norm(sipx_ctx* c, const void* x, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_TNV, SIPX_OP_TV_XY, SIPX_MODE_WHOLE, 0, x, out, nullptr, false, false))
 }

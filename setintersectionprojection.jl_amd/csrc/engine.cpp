@@ -386,6 +386,7 @@ class Engine : public EngineBase {
       if (s.op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
       if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG || s.ext_kind == EXT_L21_JOINT || s.ext_kind == EXT_TNV) refuse_sharded(ctx, Sharded::L21);
       if (s.ext_kind == EXT_L21_GROUPS) refuse_sharded(ctx, Sharded::L21_GROUPS);
+      if (s.ext_kind == EXT_L1_WEIGHTED) refuse_sharded(ctx, Sharded::L1_WEIGHTED);
     }
     FinalizePlan P;
     plan_sets();
@@ -2944,11 +2945,13 @@ class Engine : public EngineBase {
                                "subspace bases are fixed at sipx_add_set" + way_out);
     if (s.seg_radii && lb && s.ext_kind != EXT_ANNULUS_SEG)
       throw std::runtime_error(what + ": only the annulus has inner radii (lb); the radii of an l1 / l2 set are its ub");
+    if (s.ext_kind == EXT_L1_WEIGHTED && ub) throw std::runtime_error(what + ": " + L1W_SET_DATA_UB);
     if (s.weighted && ub)
       throw std::runtime_error(what + ": the weights of an l2,1 set are its lb; it has no ub (the radius is fixed at sipx_add_set)");
     const ConfigCtx ctx = config_ctx();
     const long long len = data_len(ctx, s);
-    if (s.weighted && lb && !on_device) check_l21_weights((const T*)lb, len, s.ext_kind == EXT_L21_JOINT ? "l21_joint" : (s.ext_kind == EXT_L21_GROUPS ? "l21_groups" : "l21"));
+    if (s.ext_kind == EXT_L1_WEIGHTED && lb && !on_device) check_l1w_weights((const T*)lb, len);
+    else if (s.weighted && lb && !on_device) check_l21_weights((const T*)lb, len, s.ext_kind == EXT_L21_JOINT ? "l21_joint" : (s.ext_kind == EXT_L21_GROUPS ? "l21_groups" : "l21"));
     if (s.seg_radii && (s.ext_kind == EXT_L1_SEG || s.ext_kind == EXT_L21_SEG) && ub && !on_device) check_l1_radii((const T*)ub, len);
     if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
       throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
@@ -3406,6 +3409,59 @@ class Engine : public EngineBase {
     finish_call(on_device, out, dout, 1);
   }
 
+  // SIPX_PROJ_L1_WEIGHTED of sipx_project: the M-vector of the operator's range in the reference's row order, as project_l21 takes it
+  void project_l1_weighted(const sipx_set_desc* d, void* v, int64_t len) {
+    if (d->op == SIPX_OP_CSC) throw std::runtime_error(L1W_NO_CUSTOM);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> st;
+    configure_op(ctx, st, d->op);
+    if (st.op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
+    configure_proj(ctx, st, d);
+    if (!d->lb) throw std::runtime_error(L1W_NEEDS_WEIGHTS);
+    if (len != st.Mtrue)
+      throw std::runtime_error("the weighted l1 ball projects a vector of the operator's range: " + std::to_string(st.Mtrue) +
+                               " entries on this grid, " + std::to_string((long long)len) + " given");
+    st.spec.lb = st.host_lb.data();
+    DeviceMemory tmp;
+    T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
+    upload_rows(st, (const T*)v, dv);
+    {
+      ExtProj<T> ext(st.spec, stream_);
+      ext.project(dv, false, nullptr, nullptr, nullptr);
+      download_rows(st, dv, (T*)v);               // (synchronises the stream)
+    }
+  }
+
+  // sipx_l1_weighted_norm(_dev): (T) sum_i w_i |(A x)_i| of the weighted l1 set behind op, by the observe() of a throw-away projector of
+  // that set: the first pass of its iteration (l1_weighted.h)
+  void l1_weighted_norm(int op, const void* x, const void* w, void* out, bool on_device) override {
+    if (!x || !w || !out) throw std::runtime_error("weighted l1 norm: x, w and out are needed");
+    SIPX_HIP(hipSetDevice(device_));
+    if (op == SIPX_OP_CSC) throw std::runtime_error(L1W_NO_CUSTOM);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, op);
+    if (op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
+    sipx_set_desc d{};
+    d.op = op; d.proj = SIPX_PROJ_L1_WEIGHTED; d.mode = SIPX_MODE_WHOLE; d.pmax = 1.0;
+    d.lb = on_device ? nullptr : w;            // (device weights: brought by set_data below, unchecked -- a bad one counts as 0)
+    d.reserved = (int32_t)s.Mtrue;
+    configure_proj(ctx, s, &d);                // the refusals, the check of host weights, and the ExtSpec
+    s.spec.lb = on_device ? nullptr : s.host_lb.data();
+    DeviceMemory tmp;
+    const OpScratch ws = forward_scratch(tmp, s, on_device);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
+    ExtProj<T> ext(s.spec, stream_);
+    const T* dv = queue_forward(ws, s, x, on_device);     // (device x, w: the engine stream is behind the caller's from here on)
+    if (on_device) ext.set_data((const T*)w, nullptr, true);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, 2.0 * (double)s.Mpad * sizeof(T));
+      ext.observe(dv, dout, nullptr, nullptr, nullptr);
+    }
+    finish_call(on_device, out, dout, 1);
+  }
+
   // sipx_l21_groups_norm(_dev): (T) sum_s w_s g_s over the segments of the (op, mode, dir) set on A x (w NULL: every weight 1), by the
   // observe() of a throw-away projector of that set: its norms launch and the first pass of its iteration (l21_groups.h)
   void l21_groups_norm(int op, int mode, int dir, const void* x, const void* w, void* out, bool on_device) override {
@@ -3439,6 +3495,10 @@ class Engine : public EngineBase {
     SIPX_HIP(hipSetDevice(device_));
     if (d->proj == SIPX_PROJ_L21 || d->proj == SIPX_PROJ_L21_JOINT || d->proj == SIPX_PROJ_L21_GROUPS || d->proj == SIPX_PROJ_TNV) {
       project_l21(d, v, len);
+      return;
+    }
+    if (d->proj == SIPX_PROJ_L1_WEIGHTED) {
+      project_l1_weighted(d, v, len);
       return;
     }
     Grid g1;
@@ -3667,7 +3727,7 @@ class Engine : public EngineBase {
     // weighted l2,1 sets: the Michelot passes and the flag reads of the last projection (summed over such sets), their calls and groups
     long long wc[4] = {0, 0, 0, 0};
     for (const auto& st : sets_) {
-      if (!st.ext || !st.weighted || st.ext_kind == EXT_L21_GROUPS) continue;
+      if (!st.ext || !st.weighted || st.ext_kind == EXT_L21_GROUPS || st.ext_kind == EXT_L1_WEIGHTED) continue;
       long long c[4];
       st.ext->route_counts(c);
       for (int q = 0; q < 4; ++q) wc[q] += c[q];
@@ -3683,7 +3743,17 @@ class Engine : public EngineBase {
       for (int q = 0; q < 4; ++q) gc[q] += c[q];
     }
     o += ", \"l21_groups\": {\"passes\": " + std::to_string(gc[0]) + ", \"flag_reads\": " + std::to_string(gc[1]) +
-         ", \"calls\": " + std::to_string(gc[2]) + ", \"nseg\": " + std::to_string(gc[3]) + "}}";
+         ", \"calls\": " + std::to_string(gc[2]) + ", \"nseg\": " + std::to_string(gc[3]) + "}";
+    // weighted l1 sets: the same counts, and the padded rows their passes run over
+    long long lc[4] = {0, 0, 0, 0};
+    for (const auto& st : sets_) {
+      if (!st.ext || st.ext_kind != EXT_L1_WEIGHTED) continue;
+      long long c[4];
+      st.ext->route_counts(c);
+      for (int q = 0; q < 4; ++q) lc[q] += c[q];
+    }
+    o += ", \"l1_weighted\": {\"passes\": " + std::to_string(lc[0]) + ", \"flag_reads\": " + std::to_string(lc[1]) +
+         ", \"calls\": " + std::to_string(lc[2]) + ", \"n\": " + std::to_string(lc[3]) + "}}";
     if (!peek) start_stats(enable);
     return o.c_str();
   }

@@ -18,7 +18,9 @@
 // weighted iteration (L21WSearch): its norms and its scale kernel are its own.
 // Total nuclear variation (EXT_TNV, tnv.h, TnvProj) has the groups and the z-march of the joint ball, two numbers per pixel in the search
 // and a 2 x 2 matrix per pixel in place of the weight.
-// Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the two projectors.
+// The weighted l1 ball on the rows of an operator (EXT_L1_WEIGHTED, l1_weighted.h, L1WProj) is the weighted iteration once more, on the pairs
+// (|v_i|, w_i) of the flat padded array: a pass kernel that reads v itself (k_l1w_part) and a soft-threshold apply (k_l1w_apply).
+// Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the projectors.
 // A projector's observe() runs the norms launch and the first sum of its own project(): what it reports is what project() decides on.
 #include "ext_family.h"
 #include "l21.h"
@@ -26,6 +28,7 @@
 #include "l21_seg.h"
 #include "l21_groups.h"
 #include "l21_weighted.h"
+#include "l1_weighted.h"
 #include "tnv.h"
 
 namespace sipx {
@@ -284,6 +287,66 @@ __global__ __launch_bounds__(BLOCK) void k_l21w_scale(L21Args a, T* __restrict__
           if (mem[k] && wk[k] > T(0)) vq[k] = x.v[k];
       }
     }
+  }
+}
+
+// ---- EXT_L1_WEIGHTED: the weighted l1 ball on the rows of an operator (l1_weighted.h), one weight per row -----------------------------------
+// v and w are ONE flat array of n = max(nblk, 1) N entries each: the blocks of the padded layout lie side by side (bstride == N), and
+// w holds 0 at every row a block does not have, so neither kernel needs a coordinate.
+//     k_l1w_part      k_l21w_part with a = |v| taken in registers: no norms launch, no g array          reads 2 n words
+//     k_l21w_finish   as above, unchanged
+//     k_l1w_apply     the soft threshold theta w_i; entries of weight 0 are not written                reads 2 n words, writes n
+template <typename T, int VW, bool FIRST>
+__global__ __launch_bounds__(BLOCK) void k_l1w_part(unsigned n, const T* __restrict__ v, const T* __restrict__ w,
+                                                    const L21WState* __restrict__ st, double* __restrict__ part) {
+  if (!FIRST && st->done) return;
+  __shared__ double red[5 * BLOCK];
+  const double th = FIRST ? 0.0 : st->theta;
+  const unsigned nvec = n / VW, step = gridDim.x * BLOCK;
+  L21WSums a;
+  auto take = [&](const Vec<T, VW>& xv, const Vec<T, VW>& wv) {
+#pragma unroll
+    for (int k = 0; k < VW; ++k) l1w_take<T, FIRST>(a, xv.v[k], l21w_clean<T>(wv.v[k]), th);
+  };
+  unsigned vi = blockIdx.x * BLOCK + threadIdx.x;
+  for (; vi + (L21W_LOADS - 1) * step < nvec; vi += L21W_LOADS * step) {
+    Vec<T, VW> xv[L21W_LOADS], wv[L21W_LOADS];
+#pragma unroll
+    for (int u = 0; u < L21W_LOADS; ++u) {
+      xv[u] = ldv<T, VW>(v + (size_t)(vi + u * step) * VW);
+      wv[u] = ldv<T, VW>(w + (size_t)(vi + u * step) * VW);
+    }
+#pragma unroll
+    for (int u = 0; u < L21W_LOADS; ++u) take(xv[u], wv[u]);
+  }
+  for (; vi < nvec; vi += step) take(ldv<T, VW>(v + (size_t)vi * VW), ldv<T, VW>(w + (size_t)vi * VW));
+  l21w_tree<BLOCK>(a, red);
+  if (threadIdx.x == 0) {
+    double* o = part + 5 * (size_t)blockIdx.x;
+    o[0] = a.S.hi; o[1] = a.S.lo; o[2] = a.C.hi; o[3] = a.C.lo; o[4] = a.cnt;
+  }
+}
+template <typename T, int VW>
+__global__ __launch_bounds__(BLOCK) void k_l1w_apply(unsigned n, T* __restrict__ v, const T* __restrict__ w, const L21WState* __restrict__ st,
+                                                     const T* __restrict__ theta) {
+  if (!st->need) return;
+  const T th = theta[0];
+  const unsigned nvec = n / VW, step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const Vec<T, VW> wv = ldv<T, VW>(w + (size_t)vi * VW);
+    T wk[VW];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      wk[k] = l21w_clean<T>(wv.v[k]);
+      any = any || wk[k] > T(0);
+    }
+    if (!any) continue;                // rows of weight 0, pads among them: nothing to do
+    T* const p = v + (size_t)vi * VW;
+    Vec<T, VW> x = ldv<T, VW>(p);
+#pragma unroll
+    for (int k = 0; k < VW; ++k) x.v[k] = wk[k] > T(0) ? l1w_shrink<T>(x.v[k], wk[k], th) : x.v[k];      // (weight 0: its own bits go back)
+    stv<T, VW>(p, x);
   }
 }
 
@@ -682,7 +745,8 @@ static void l21_frames(hipStream_t s, const ExtSpec& sp, const T* g, T tau, cons
 
 // ---- the weighted Michelot iteration on n entries (g, w) (l21_weighted.h): the device state and the launches, for BallProj's weighted
 // route and for GroupsProj.  wide: 16-byte loads of g and w (n a multiple of 16 bytes' worth of entries, both arrays aligned).
-template <typename T>
+// L1: the pass kernel is k_l1w_part, which takes g = |v| from v itself (l1_weighted.h, L1WProj); the finish, the batches, the flag are these.
+template <typename T, bool L1 = false>
 struct L21WSearch {
   L21WState* st = nullptr;             // the state of the iteration
   double* part = nullptr;              // the partials of a pass, 5 per workgroup
@@ -705,9 +769,10 @@ struct L21WSearch {
   void pass(hipStream_t stream, long long n, const T* g, const T* w, bool wide, T tau) {
     constexpr int W = l21_vec_width<T>();
     const int grid = fit_grid((n / (wide ? W : 1) + L21W_LOADS - 1) / L21W_LOADS, L21W_GRID);
-    void (*const k)(unsigned, const T*, const T*, const L21WState*, double*) = wide ? k_l21w_part<T, W, FIRST> : k_l21w_part<T, 1, FIRST>;
+    void (*const k)(unsigned, const T*, const T*, const L21WState*, double*) =
+        L1 ? (wide ? k_l1w_part<T, W, FIRST> : k_l1w_part<T, 1, FIRST>) : (wide ? k_l21w_part<T, W, FIRST> : k_l21w_part<T, 1, FIRST>);
     {
-      ObsScope obs(KID_L21W_PASS, stream, 2.0 * n * sizeof(T));
+      ObsScope obs(L1 ? KID_L1W_PASS : KID_L21W_PASS, stream, 2.0 * n * sizeof(T));
       hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), 0, stream, (unsigned)n, g, w, st, part);
     }
     hipLaunchKernelGGL((k_l21w_finish<T, FIRST>), dim3(1), dim3(BLOCK), 0, stream, grid, tau, part, st, theta, flag);
@@ -724,7 +789,9 @@ struct L21WSearch {
       SIPX_HIP(hipStreamSynchronize(stream));
       ++last_reads;
       if (*h_flag) break;
-      if (queued > n + 1) throw std::runtime_error("the weighted l2,1 ball: the threshold iteration did not end within n + 1 passes");
+      if (queued > n + 1)
+        throw std::runtime_error(L1 ? "the weighted l1 ball: the threshold iteration did not end within n + 1 passes"
+                                    : "the weighted l2,1 ball: the threshold iteration did not end within n + 1 passes");
       pass<false>(stream, n, g, w, wide, tau);
       ++queued;
     }
@@ -1087,8 +1154,96 @@ struct GroupsProj : ExtImpl<T> {
   }
 };
 
+// ---- EXT_L1_WEIGHTED: the weighted l1 ball on the rows of identity, D_x, D_y, D_z, TV or TV_xy (l1_weighted.h) ------------------------------
+// The iteration of the weighted route with k_l1w_part as its pass on the flat pair (v, w), then k_l1w_apply.  w lives in the padded layout of
+// the operator: the weights arrive in the reference's row order (spec.lb, set_data) and go through the transfer kernel of the y_i / l_i
+// (kernels_io.hip), which writes the rows a block has and nothing else -- the pads keep the zeros w was allocated with.  Nothing is kept
+// between calls.
+static void l1w_check_spec(const ExtSpec& sp) {
+  if (sp.mode != SIPX_MODE_WHOLE) throw std::runtime_error(L1W_NO_MODE);
+  if (!sp.weighted) throw std::runtime_error(L1W_NEEDS_WEIGHTS);
+  if (sp.ub) throw std::runtime_error(L1W_NO_UB);
+  if (sp.nblk < 0 || sp.nblk > 3 || sp.nblk > sp.ndim) throw std::runtime_error("the weighted l1 ball: 0 to 3 operator blocks, no more than grid dimensions");
+  for (int q = 0; q < sp.nblk; ++q) {
+    if (sp.bdir[q] < 0 || sp.bdir[q] >= sp.ndim) throw std::runtime_error("the weighted l1 ball: block direction out of range");
+    if (sp.G.n[sp.bdir[q]] < 2) throw std::runtime_error("the weighted l1 ball: difference along a dimension of size 1");
+    for (int r = 0; r < q; ++r)
+      if (sp.bdir[q] == sp.bdir[r]) throw std::runtime_error("the weighted l1 ball: two blocks along one direction");
+  }
+  if (sp.nblk > 1 && sp.bstride != sp.G.N) throw std::runtime_error("the weighted l1 ball: the blocks must lie side by side (bstride == N)");
+  if ((long long)std::max(sp.nblk, 1) * sp.G.N >= (1ll << 31)) throw std::runtime_error("the weighted l1 ball: the operator needs fewer than 2^31 padded rows");
+}
+template <typename T>
+struct L1WProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  long long n = 0;                     // entries of the padded layout: max(nblk, 1) N, the length of the search
+  long long rows = 0;                  // rows of the operator (Mtrue): the weights a caller hands over
+  long long blk_rows[3] = {0, 0, 0};
+  T* w = nullptr;                      // the weights in the padded layout, 0 at every pad
+  T* wrows = nullptr;                  // where host weights land in row order before they are expanded
+  L21WSearch<T, true> ws;
+  L1WProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    l1w_check_spec(sp);
+    if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+    n = (long long)std::max(sp.nblk, 1) * sp.G.N;
+    for (int q = 0; q < sp.nblk; ++q) {
+      blk_rows[q] = sp.G.N / sp.G.n[sp.bdir[q]] * (sp.G.n[sp.bdir[q]] - 1);
+      rows += blk_rows[q];
+    }
+    if (sp.nblk == 0) rows = sp.G.N;
+    w = this->mem.template alloc<T>((size_t)n, Mem::Zeroed);      // (until weights arrive no row is constrained; the pads stay 0 for good)
+    wrows = this->template alloc<T>((size_t)rows);
+    ws.build(*this);
+    if (sp.lb) expand((const T*)sp.lb, false);
+  }
+  // w <- the weights given in row order, host or device memory, block by block into the rows each block has
+  void expand(const T* src, bool on_device) {
+    if (!on_device) {
+      SIPX_HIP(hipMemcpyAsync(wrows, src, sizeof(T) * (size_t)rows, hipMemcpyHostToDevice, stream));
+      src = wrows;
+    }
+    IoArgs<T> A;
+    if (sp.nblk == 0) io_seg_shape<T>(A.seg[A.nseg++], sp.G, -1, rows, src, w);
+    long long r0 = 0;
+    for (int q = 0; q < sp.nblk; ++q) {
+      io_seg_shape<T>(A.seg[A.nseg++], sp.G, sp.bdir[q], blk_rows[q], src + r0, w + (long long)q * sp.G.N);
+      r0 += blk_rows[q];
+    }
+    io_rows<T>(stream, A, false, NB);
+    if (!on_device) SIPX_HIP(hipStreamSynchronize(stream));      // (the caller's host vector may go once the call returns)
+  }
+  bool wide(const T* v) const { return sp.G.n[0] % 4 == 0 && aligned16(v, w); }
+  void apply(T* v) {
+    constexpr int W = l21_vec_width<T>();
+    const bool wd = wide(v);
+    ObsScope obs(KID_L1W_APPLY, stream, 3.0 * n * sizeof(T));
+    hipLaunchKernelGGL((wd ? k_l1w_apply<T, W> : k_l1w_apply<T, 1>), dim3(fit_grid(n / (wd ? W : 1), NB)), dim3(BLOCK), 0, stream, (unsigned)n, v, w,
+                       ws.st, ws.theta);
+    SIPX_HIP(hipGetLastError());
+  }
+  void project(T* v, bool, double*, T*, T*) override {
+    ws.run(stream, n, v, w, wide(v), (T)sp.pmax);
+    apply(v);
+  }
+  // out[0] <- (T)asum as project decides on it: the first pass of its iteration with an infinite radius
+  void observe(const T* v, T* out, double*, T*, T*) override {
+    ws.template pass<true>(stream, n, v, w, wide(v), (T)INFINITY);
+    ws.pick(stream, out);
+  }
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    if (new_ub) throw std::runtime_error(L1W_SET_DATA_UB);
+    if (new_lb) expand(new_lb, on_device);
+  }
+  // the passes of the last call (the first included), the reads of the flag it took, the calls so far, the padded rows
+  void route_counts(long long out[4]) const override {
+    out[0] = ws.last_passes; out[1] = ws.last_reads; out[2] = ws.calls; out[3] = n;
+  }
+};
+
 template <typename T>
 ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
+  if (spec.kind == EXT_L1_WEIGHTED) return new L1WProj<T>(spec, stream);
   if (spec.kind == EXT_L21_GROUPS) return new GroupsProj<T>(spec, stream);
   if (spec.kind == EXT_TNV) return new TnvProj<T>(spec, stream);
   if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);

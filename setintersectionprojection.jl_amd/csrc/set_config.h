@@ -11,6 +11,7 @@
 #include "ext_family.h"      // (sipx.h, sipx_common.h, ext_proj.h; make_segmap / seg_count)
 #include "l21_groups.h"      // (the refusals and the descriptor check of the l2,1 ball over fibers / slices)
 #include "l21_weighted.h"    // (the host checks of the weighted l2,1 sets)
+#include "l1_weighted.h"     // (the refusals and the host checks of the weighted l1 ball)
 
 namespace sipx {
 
@@ -72,7 +73,8 @@ struct SetConfig {
   int bmode = SIPX_MODE_WHOLE, bdir = 0;   // SIPX_PROJ_BOUNDS_VEC: one bound per row (WHOLE) or per coordinate along bdir (FIBER)
   int ext_kind = 0;                  // projector acting on a materialised vector (ext_proj.h)
   bool seg_radii = false;            // EXT_L1_SEG / L2_SEG / ANNULUS_SEG built with one radius per segment (host_lb / host_ub, then the projector's)
-  bool weighted = false;             // EXT_L21 (whole array) / EXT_L21_JOINT / EXT_L21_GROUPS built with one weight per group in lb (host_lb, then the projector's)
+  bool weighted = false;             // EXT_L21 (whole array) / EXT_L21_JOINT / EXT_L21_GROUPS built with one weight per group in lb (host_lb, then the projector's);
+                                     // EXT_L1_WEIGHTED: always, one weight per row of the operator
   ExtSpec spec;
   std::vector<T> host_basis;
   std::vector<long long> ata_off;
@@ -98,7 +100,8 @@ void expand_fiber_bounds(const ConfigCtx& c, const SetConfig<T>& s, const T* per
 // solve would each need its share of them.  L21: the groups of the l2,1 ball span the blocks of the TV operator, the gather route
 // of a slab-decomposed solve is single-block.  TV_XY: the slab routes know TV's one block per dimension only.  L21_GROUPS: the segments
 // of the l2,1 ball over fibers / slices share one budget, a rank would see its slab's segments (or its part of every slice) only.
-enum class Sharded { RADII, L21, TV_XY, L21_GROUPS };
+// L1_WEIGHTED: the weights live in the one projector of a single process, in the padded layout of the whole operator.
+enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED };
 inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
   if (c.single_process) return;
   switch (which) {
@@ -113,6 +116,8 @@ inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
                                "or set ownership: use D_x and D_y sets, or a single process");
     case Sharded::L21_GROUPS:
       throw std::runtime_error(L21G_SHARDED);
+    case Sharded::L1_WEIGHTED:
+      throw std::runtime_error(L1W_SHARDED);
   }
 }
 // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
@@ -224,6 +229,13 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (s.comp) throw std::runtime_error(L21G_NO_MINKOWSKI);
     if (mode == SIPX_MODE_WHOLE) throw std::runtime_error(L21G_NEEDS_MODE);
   }
+  // so is the weighted l1 ball (l1_weighted.h): a built-in operator, no transform, no component, the whole array
+  if (d->proj == SIPX_PROJ_L1_WEIGHTED) {
+    if (s.custom) throw std::runtime_error(L1W_NO_CUSTOM);
+    if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(L1W_NO_TRANSFORM);
+    if (s.comp) throw std::runtime_error(L1W_NO_MINKOWSKI);
+    if (mode != SIPX_MODE_WHOLE) throw std::runtime_error(L1W_NO_MODE);
+  }
   if (mode != SIPX_MODE_WHOLE) {
     if (dir < 0 || dir >= c.ndim) throw std::runtime_error("application mode: direction out of range for this grid");
     // the one multi-block set with a mode of its own: the l2,1 ball per z-slice on TV_xy (l21_seg.h)
@@ -233,7 +245,7 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (s.nblk > 1 && !frames) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
   }
   auto ext = [&](int kind) {
-    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT && kind != EXT_TNV) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
+    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT && kind != EXT_TNV && kind != EXT_L1_WEIGHTED) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
     s.ext_kind = kind;
     s.spec.kind = kind;
     s.spec.ndim = c.ndim;
@@ -419,6 +431,20 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       }
       break;
     }
+    case SIPX_PROJ_L1_WEIGHTED: {  // one weight per row of the operator in lb (operator, transform, component, mode: above); lb NULL: the
+                                   // weights come with sipx_set_data(_dev) before the first solve, until then no row is constrained
+      refuse_sharded(c, Sharded::L1_WEIGHTED);
+      if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+      ext(EXT_L1_WEIGHTED);
+      l1w_check_desc(d->ub != nullptr, d->reserved, s.Mtrue);      // (reserved: the entries lb holds)
+      s.weighted = true;
+      s.spec.weighted = 1;
+      if (d->lb) {
+        check_l1w_weights((const T*)d->lb, s.Mtrue);
+        s.host_lb.assign((const T*)d->lb, (const T*)d->lb + s.Mtrue);
+      }
+      break;
+    }
     case SIPX_PROJ_RANK: ext(EXT_RANK); break;
     case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;
     case SIPX_PROJ_HISTOGRAM:
@@ -464,6 +490,7 @@ std::vector<long long> default_ata_offsets(const ConfigCtx& c, const SetConfig<T
 // entries of the vectors a set takes (sipx_add_set, sipx_set_data): radii per segment, bounds per fiber coordinate, or one per row
 template <typename T>
 long long data_len(const ConfigCtx& c, const SetConfig<T>& s) {
+  if (s.ext_kind == EXT_L1_WEIGHTED) return s.Mtrue;
   if (s.weighted) return s.ext_kind == EXT_L21_GROUPS ? seg_count(s.spec) : l21_groups(c, s.ext_kind);
   if (s.seg_radii) return s.ext_kind == EXT_L21_SEG ? c.G.n[2] : seg_count(s.spec);
   if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;

@@ -41,13 +41,14 @@ EXPORTED_SYMBOLS = [
     "sipx_l21_norm", "sipx_l21_norm_dev", "sipx_l21_norms", "sipx_l21_norms_dev",
     "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev", "sipx_l21_weighted_norm", "sipx_l21_weighted_norm_dev",
     "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev", "sipx_tnv_norm", "sipx_tnv_norm_dev",
+    "sipx_l1_weighted_norm", "sipx_l1_weighted_norm_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16,
-        "tnv": 17}
+        "tnv": 17, "l1_weighted": 18}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -83,6 +84,21 @@ L21G_NO_CUSTOM = ("the l2,1 ball over fibers or slices (l21_groups) takes no cus
                   "grid-shaped range -- TD_OP must be the identity, D_x, D_y or D_z")
 L21G_NO_COARSE = ("multilevel: the l2,1 ball over fibers or slices (l21_groups) has no rule that takes its radius to a coarser grid yet -- "
                   "solve on one level")
+# the weighted l1 ball (csrc/l1_weighted.h): one weight per row of identity, D_x, D_y, D_z, TV or TV_xy; the engine's refusals, word for
+# word, and the front end's own
+L1W_OPERATORS = ("identity", "D_x", "D_y", "D_z", "TV", "D2D", "D3D", "TV_xy")
+L1W_NO_MODE = ("the weighted l1 ball (l1_weighted) applies to the whole array (matrix / tensor mode): per fiber or slice use "
+               "(\"l1\", op, mode) with segment_norms=True, which takes one radius per segment")
+L1W_NO_TRANSFORM = ("the weighted l1 ball (l1_weighted) takes no transform (DFT, DCT, wavelet): its weights are one per row of "
+                    "identity, D_x, D_y, D_z, TV or TV_xy -- behind a transform use the plain (\"l1\", transform)")
+L1W_NO_CUSTOM = ("the weighted l1 ball (l1_weighted) takes no custom operator: its weights follow the rows of identity, D_x, "
+                 "D_y, D_z, TV or TV_xy -- scale the rows of the operator and use the plain (\"l1\", op)")
+L1W_NO_MINKOWSKI = "the weighted l1 ball (l1_weighted) takes no Minkowski component: use the plain (\"l1\", op) there"
+L1W_NEEDS_WEIGHTS = ("the weighted l1 ball (l1_weighted) needs weights, one per row of the operator: without weights the set is the "
+                     "plain (\"l1\", op)")
+L1W_NO_COARSE = ("multilevel: the weighted l1 ball (l1_weighted) has no rule that takes its weights to a coarser grid yet -- solve on one "
+                 "level, or use the plain (\"l1\", op)")
+L1W_WEIGHTS_ARE_LB = ("set_data: the weights of the weighted l1 ball are its lb; it has no ub (the radius is fixed when the set is built)")
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
 TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
 TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
@@ -228,7 +244,8 @@ class set_definitions:
     app_mode: Tuple[str, str]
     custom_TD_OP: Tuple[Any, bool] = ((), False)
     weights: Any = None      # the l2,1 sets on the whole array: one weight >= 0 per group (csrc/l21_weighted.h), None: the plain ball;
-                             # l21_groups: one per fiber / slice, in the order of segment_norms (csrc/l21_groups.h)
+                             # l21_groups: one per fiber / slice, in the order of segment_norms (csrc/l21_groups.h);
+                             # l1_weighted: one per row of the operator, in the order of A @ x (csrc/l1_weighted.h), required
 
 
 @dataclass
@@ -420,10 +437,35 @@ class Projector:
             self.seg_radii = False
             self.kind, self.pmax, self.op = "tnv", float(constraint.max), "TV_xy"
             return
-        if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint", "l21_groups"):
+        if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint", "l21_groups", "l1_weighted"):
             raise SipxError(f"set type {st!r} takes no weights: " + L21_WEIGHTS_WHERE)
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
         self.op = None               # the operator a stand-alone call of the projector acts behind (l21: the TV range), None: the identity
+        if st == "l1_weighted":
+            # the weighted l1 ball: one weight per row of a built-in operator (csrc/l1_weighted.h); max is the radius
+            cust = constraint.custom_TD_OP[0]
+            if not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+                raise SipxError(L1W_NO_CUSTOM)
+            if constraint.TD_OP in SPECIAL_OPERATORS:
+                raise SipxError(L1W_NO_TRANSFORM)
+            if constraint.TD_OP not in L1W_OPERATORS:
+                raise SipxError(L1W_NO_CUSTOM if constraint.TD_OP == "D_xz" else UNKNOWN_OPERATOR)
+            if constraint.TD_OP == "TV_xy" and len(n) != 3:
+                raise SipxError(TV_XY_NEEDS_3D)
+            if constraint.TD_OP == "D_y" and len(n) == 2:
+                raise SipxError(UNKNOWN_OPERATOR)
+            if self.mode:
+                raise SipxError(L1W_NO_MODE)
+            if np.ndim(constraint.max) != 0:
+                raise SipxError("the weighted l1 ball takes one radius (constraint.max a scalar)")
+            if not float(constraint.max) > 0:
+                raise SipxError("Radius of L1 ball is negative")
+            if getattr(constraint, "weights", None) is None:
+                raise SipxError(L1W_NEEDS_WEIGHTS)
+            self.kind, self.pmax, self.op = "l1_weighted", float(constraint.max), constraint.TD_OP
+            self._take_weights(constraint, TDOperator(constraint.TD_OP, comp_grid, self.TF).shape[0],
+                               f"row of {constraint.TD_OP}, in the order of A @ x")
+            return
         if st == "l21_groups":
             # group sparsity: one l2,1 ball whose groups are the fibers / slices of the range of a one-block operator (csrc/l21_groups.h);
             # max is the radius, weights one per segment in the order of segment_norms()
@@ -669,6 +711,13 @@ class Projector:
                 raise SipxError(L21G_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
             if getattr(op, "component", 0):
                 raise SipxError(L21G_NO_MINKOWSKI)
+        if self.kind == "l1_weighted":
+            if op.kind == "custom":
+                raise SipxError(L1W_NO_CUSTOM)
+            if OPS[op.kind] != OPS[self.op]:
+                raise SipxError(f"the weighted l1 ball (l1_weighted) was built with one weight per row of {self.op}, the operator is {op.kind}")
+            if getattr(op, "component", 0):
+                raise SipxError(L1W_NO_MINKOWSKI)
         if op.kind == "custom" and (self.mode or self.transform or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank",
                                                                                      "nuclear", "histogram", "subspace")):
             raise SipxError("custom sparse operators take the whole-array projectors only")
@@ -731,13 +780,14 @@ class Projector:
         if v.dtype.type != self.TF or not v.flags.c_contiguous:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
-                                                                              "subspace", "l21", "l21_joint", "l21_groups", "tnv")
-        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv")
+                                                                              "subspace", "l21", "l21_joint", "l21_groups", "tnv", "l1_weighted")
+        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted")
         if l21:                      # the M-vector of the TV range (l21_groups: of its operator's) in the reference's row order, on the grid
             op = TDOperator(self.op, self.comp_grid, self.TF)
             rows = op.shape[0]
             if v.shape != (rows,):
-                raise SipxError(f"the l2,1 ball projects a vector of the {self.op} range: {rows} entries on this grid, {v.size} given")
+                what = "weighted l1 ball" if self.kind == "l1_weighted" else "l2,1 ball"
+                raise SipxError(f"the {what} projects a vector of the {self.op} range: {rows} entries on this grid, {v.size} given")
             self.check_rows(op)
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
         try:
@@ -815,7 +865,11 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
 
     ("l21_groups", op, ("fiber", d) / ("slice", d)) on the identity, D_x, D_y or D_z is group sparsity (csrc/l21_groups.h): ONE ball of
     radius max on the sum over the fibers / slices of the array of shape TD_n of their l2 norms, optionally with one weight per segment
-    (weights, in the order of segment_norms()).  ("l2", op, same mode) gives every segment a ball of its own instead."""
+    (weights, in the order of segment_norms()).  ("l2", op, same mode) gives every segment a ball of its own instead.
+
+    ("l1_weighted", op, matrix / tensor) on the identity, D_x, D_y, D_z, TV or TV_xy is the weighted l1 ball (csrc/l1_weighted.h):
+    sum_i w_i |(A x)_i| <= max with one finite weight >= 0 per row of A in the order of A @ x (weights, required; 0 leaves a row free) --
+    the set of iteratively reweighted l1 and of anisotropic TV with a weight per direction."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -833,7 +887,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.max = np.asarray(c.max, TF)
         if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
             c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
-        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv"):
+        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -1116,7 +1170,7 @@ class Context:
             _check_l1_radii("l1" if P.kind == "l21" else P.kind, arrs[1])
         if P is not None and P.weighted:
             if arrs[1] is not None:
-                raise SipxError(L21_WEIGHTS_ARE_LB)
+                raise SipxError(L1W_WEIGHTS_ARE_LB if P.kind == "l1_weighted" else L21_WEIGHTS_ARE_LB)
             if arrs[0] is not None:
                 _check_l21_weights(P.kind, arrs[0])
         _chk(lib().sipx_set_data(self.h, int(i), _ptr(arrs[0]), _ptr(arrs[1])))
@@ -1569,11 +1623,15 @@ L21_WEIGHTS_ARE_LB = "set_data: the weights of an l2,1 set are its lb; it has no
 
 
 def _check_l21_weights(kind, w):
-    """No host path hands the device a weight of the weighted l2,1 ball that is negative, NaN or infinite (csrc/l21_weighted.h)."""
+    """No host path hands the device a weight of the weighted l2,1 ball that is negative, NaN or infinite (csrc/l21_weighted.h); nor one
+    of the weighted l1 ball (kind "l1_weighted", csrc/l1_weighted.h), in words of its own."""
     w = np.asarray(w)
     ok = np.isfinite(w) & (w >= 0)
     if not np.all(ok):
         bad = int(np.flatnonzero(~ok)[0])
+        if kind in ("l1_weighted", "l1_weighted_norm"):
+            raise SipxError(f"the weighted l1 ball (l1_weighted): weight {bad} is negative, NaN or infinite ({w[bad]!r}) -- every weight must "
+                            "be finite and >= 0 (0 leaves its row free)")
         raise SipxError(f"the weighted l2,1 ball ({kind}): weight {bad} is negative, NaN or infinite ({w[bad]!r}) -- every weight must be "
                         "finite and >= 0 (0 leaves its group unconstrained)")
 
@@ -1721,7 +1779,7 @@ class Solver:
                             "and annulus sets built with a vector of radii do, and the l2,1 sets built with weights; build a new "
                             "Solver for other data")
         if self.P_sub[i].weighted and ub is not None:
-            raise SipxError(L21_WEIGHTS_ARE_LB)
+            raise SipxError(L1W_WEIGHTS_ARE_LB if self.P_sub[i].kind == "l1_weighted" else L21_WEIGHTS_ARE_LB)
         if self.P_sub[i].seg_radii and lb is not None and self.P_sub[i].kind != "annulus":
             raise SipxError(f"set_data: set {i} is an {self.P_sub[i].kind} set: its radii are ub, only the annulus has inner radii (lb)")
         given = [(k, a) for k, a in (("lb", lb), ("ub", ub)) if a is not None]
@@ -2002,6 +2060,27 @@ def l21_groups_norm(x, comp_grid, TD_OP: str, app_mode, weights=None):
         out, on_dev = _l21_observe("l21_groups_norm", x, comp_grid, False, False, fn, (OPS[TD_OP], P.mode, P.dir), (), None, 0, (None,))
     else:
         out, on_dev = _l21_observe("l21_groups_norm", x, comp_grid, False, False, fn, (OPS[TD_OP], P.mode, P.dir), (), weights, nseg)
+    return out if on_dev else out[0]
+
+
+def l1_weighted_norm(x, comp_grid, TD_OP: str, weights):
+    """sum_i w_i |(A x)_i| over the rows of A = TD_OP, one of identity, D_x, D_y, D_z, TV (D2D, D3D), TV_xy: one number of the working
+    precision (that of x), (T)asum as the first pass of the ("l1_weighted", TD_OP) projector sums and compares it
+    (sipx_l1_weighted_norm, csrc/l1_weighted.h) -- used as the radius it leaves A x unwritten.  x: a numpy vector (a numpy scalar comes
+    back) or a 1-D torch tensor on a GPU (a tensor of one entry there; nothing crosses PCIe, the call orders itself against torch's
+    current stream).  weights: one finite weight >= 0 per row of A in the order of A @ x, of the kind and precision of x."""
+    TF = _tensor_TF("x", x) if _is_tensor(x) else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("l1_weighted_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    if weights is None:
+        raise SipxError(L1W_NEEDS_WEIGHTS)
+    if TD_OP in SPECIAL_OPERATORS:
+        raise SipxError(L1W_NO_TRANSFORM)
+    if TD_OP not in L1W_OPERATORS:
+        raise SipxError(L1W_NO_CUSTOM if TD_OP == "D_xz" else UNKNOWN_OPERATOR)
+    rows = TDOperator(TD_OP, comp_grid, TF).shape[0]           # (TV_xy, D_y on a 2-D grid: refused here)
+    out, on_dev = _l21_observe("l1_weighted_norm", x, comp_grid, TD_OP == "TV_xy", False, "sipx_l1_weighted_norm", (OPS[TD_OP],), (),
+                               weights, rows)
     return out if on_dev else out[0]
 
 
