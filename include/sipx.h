@@ -183,7 +183,21 @@ enum {
                                 calls give the same bits.  sipx_set_data(_dev) replaces the weights (lb, Mtrue entries; ub refused).
                                 Contexts with a communicator, a slab decomposition or set ownership refuse it.  sipx_project takes
                                 the M-vector of the operator's range in the reference's row order; sipx_l1_weighted_norm observes
-                                the norm */
+                                the norm */,
+  SIPX_PROJ_SIMPLEX = 19 /* simplex sets (no counterpart in the reference): every fiber (mode FIBER) or slice (mode SLICE, 3-D grids) v
+                            of the array of shape TD_n has v_i >= 0 and pmin <= sum_i v_i <= pmax, 0 <= pmin <= pmax, pmax > 0, both
+                            finite and shared by all segments (pmin = pmax = 1: the probability simplex, pmin = 0: the capped one) --
+                            material fractions, class probabilities, frames of known mass.  op: IDENTITY, DX, DY or DZ, transform NONE,
+                            no component, no custom operator, lb = ub = NULL, reserved = 0; mode WHOLE, a multi-block operator, vectors
+                            and sharded contexts are refused, each with a text that names the way out (csrc/seg_simplex.h).  Per
+                            segment: spos = sum max(v_i, 0) and sall = sum v_i in twice the working precision, nneg = #{v_i < 0};
+                            pmin <= (TF)spos <= pmax and nneg = 0: not written, -0.0 included; nneg > 0: only the negative entries
+                            are written, as +0; otherwise b = pmax if (TF)spos > pmax else pmin, theta by Michelot's fixed point
+                            from (sall - b) / L over A_k = {v_i > theta_k} until the integer count repeats (theta < 0 on the lower
+                            side), rounded once to TF, y_i = max(v_i - theta, +0) in TF; an all-zero segment with pmin > 0 is filled
+                            with pmin / L.  No floating-point atomics, no state between calls: two calls give the same bits.  Holds
+                            no replaceable vectors.  sipx_project takes the M-vector of the operator's range in the reference's row
+                            order; sipx_segment_sums observes (TF)spos */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -437,6 +451,13 @@ int sipx_project(sipx_ctx* ctx, const sipx_set_desc* desc, void* v, int64_t len)
  * and nothing crosses PCIe.  Learning from several arrays is a loop with an element-wise maximum / minimum over the results. */
 int sipx_segment_norms(sipx_ctx* ctx, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg);
 int sipx_segment_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg);
+/* The sums of the positive parts of the fibers / slices of A x: out[s] = (TF) sum_i max((A x)_i, 0) over segment s, TF[nseg], arguments,
+ * count, order, queries and the _dev form as sipx_segment_norms.  Summed in twice the working precision by pass 1 of the
+ * SIPX_PROJ_SIMPLEX projector on (op, mode, dir), by the route that projector takes there (csrc/seg_simplex.h).  CONTRACT: the numbers
+ * are the very ones that projector compares with pmin and pmax, so a nonnegative A x is not written by a set built with pmin = the
+ * smallest and pmax = the largest of them.  Refused where the set is refused. */
+int sipx_segment_sums(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
+int sipx_segment_sums_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
 /* The isotropic total variation of x: *out = ||TV x||_2,1 as one TF, x TF[N] on the 2-D or 3-D grid of the context (which needs no sets
  * and no finalize).  TV x comes from the engine's operator product into scratch of the call; the group norms are formed by the kernel of
  * SIPX_PROJ_L21 and summed by the first pass of its threshold search.  CONTRACT: the value is the very number the projector compares

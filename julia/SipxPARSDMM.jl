@@ -66,6 +66,10 @@ const SIPX_PROJ_TNV = 17     # total nuclear variation on the range of TV_xy (in
 # rows (include/sipx.h, csrc/l1_weighted.h), set_type = "l1_weighted".  The reference's set_definitions has no field for weights and this
 # binding does not carry them: the constant is mirrored for callers of the C ABI, projector_fields refuses the tag and names ("l1", op).
 const SIPX_PROJ_L1_WEIGHTED = 18
+# simplex sets: every fiber / slice of the range of identity, D_x, D_y or D_z has entries >= 0 and a sum in [min, max] (include/sipx.h,
+# csrc/seg_simplex.h), set_type = "simplex".  The reference's setup_constraints cannot set such a set up and this binding does not build it
+# yet: the constant is mirrored for callers of the C ABI, projector_fields refuses the tag and names the stand-in.
+const SIPX_PROJ_SIMPLEX = 19
 const MODE = Dict("matrix" => 0, "tensor" => 0, "fiber" => 1, "slice" => 2)
 const SPECIAL = ("DFT", "DCT", "wavelet", "curvelet")          # src/setup_constraints.jl:54
 # the seven @timeit sections of src/PARSDMM.jl:40,100,105,113,152,163,229
@@ -151,6 +155,7 @@ function projector_fields(c, TF)
         return (16, 0.0, Float64(c.max), nothing_[3:5]...)
     end
     st == "l1_weighted" && error("the weighted l1 ball (l1_weighted, SIPX_PROJ_L1_WEIGHTED) needs one weight per row of the operator, which this binding does not carry: use the plain (\"l1\", op), or the C ABI")
+    st == "simplex" && error("simplex sets (simplex, SIPX_PROJ_SIMPLEX) are not built in this binding yet: use (\"bounds\") together with (\"l1\", op, mode) and segment_norms=true, or the C ABI")
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "l2"          && return (3, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "annulus"     && return (4, Float64(c.min), Float64(c.max), nothing_[3:5]...)

@@ -138,6 +138,12 @@ int sipx_segment_norms(sipx_ctx* c, int op, int mode, int dir, int norm, const v
 int sipx_segment_norms_dev(sipx_ctx* c, int op, int mode, int dir, int norm, const void* x, void* out, int64_t* nseg) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->segment_norms(op, mode, dir, norm, x, out, nseg, true))
 }
+int sipx_segment_sums(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->segment_sums(op, mode, dir, x, out, nseg, false))
+}
+int sipx_segment_sums_dev(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->segment_sums(op, mode, dir, x, out, nseg, true))
+}
 int sipx_l21_norm(sipx_ctx* c, const void* x, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21, SIPX_OP_TV, SIPX_MODE_WHOLE, 0, x, out, nullptr, false, false))
 }

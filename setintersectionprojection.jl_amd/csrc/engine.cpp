@@ -387,6 +387,7 @@ class Engine : public EngineBase {
       if (s.ext_kind == EXT_L21 || s.ext_kind == EXT_L21_SEG || s.ext_kind == EXT_L21_JOINT || s.ext_kind == EXT_TNV) refuse_sharded(ctx, Sharded::L21);
       if (s.ext_kind == EXT_L21_GROUPS) refuse_sharded(ctx, Sharded::L21_GROUPS);
       if (s.ext_kind == EXT_L1_WEIGHTED) refuse_sharded(ctx, Sharded::L1_WEIGHTED);
+      if (s.ext_kind == EXT_SIMPLEX_SEG) refuse_sharded(ctx, Sharded::SIMPLEX);
     }
     FinalizePlan P;
     plan_sets();
@@ -3432,6 +3433,57 @@ class Engine : public EngineBase {
     }
   }
 
+  // SIPX_PROJ_SIMPLEX of sipx_project: the M-vector of the range of its one-block operator in the reference's row order
+  void project_simplex(const sipx_set_desc* d, void* v, int64_t len) {
+    if (d->op != SIPX_OP_IDENTITY && d->op != SIPX_OP_DX && d->op != SIPX_OP_DY && d->op != SIPX_OP_DZ) throw std::runtime_error(SIMPLEX_ONE_BLOCK);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> st;
+    configure_op(ctx, st, d->op);
+    configure_proj(ctx, st, d);
+    if (len != st.Mtrue)
+      throw std::runtime_error("the simplex set projects a vector of the operator's range: " + std::to_string(st.Mtrue) +
+                               " entries on this grid, " + std::to_string((long long)len) + " given");
+    DeviceMemory tmp;
+    T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
+    upload_rows(st, (const T*)v, dv);
+    {
+      ExtProj<T> ext(st.spec, stream_);
+      ext.project(dv, false, nullptr, nullptr, nullptr);
+      long long c[4];                            // the route of a stand-alone call counts like a set's (simplex row of sipx_kernel_stats)
+      ext.route_counts(c);
+      for (int q = 0; q < 3; ++q) project_sc_[q] += c[q];
+      project_sc_[3] = c[3];
+      download_rows(st, dv, (T*)v);               // (synchronises the stream)
+    }
+  }
+
+  // sipx_segment_sums(_dev): (T) sum of the positive parts of every fiber / slice of A x, in the order of sipx_segment_norms, by the
+  // observe() of a throw-away projector of the simplex set on (op, mode, dir): pass 1 of its own route (seg_simplex.h)
+  void segment_sums(int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device) override {
+    SIPX_HIP(hipSetDevice(device_));
+    if (op != SIPX_OP_IDENTITY && op != SIPX_OP_DX && op != SIPX_OP_DY && op != SIPX_OP_DZ) throw std::runtime_error(SIMPLEX_ONE_BLOCK);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, op);
+    sipx_set_desc d{};
+    d.op = op; d.proj = SIPX_PROJ_SIMPLEX; d.mode = mode; d.dir = dir; d.pmin = 0.0; d.pmax = 1.0;
+    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the set
+    const long long ns = seg_count(s.spec);
+    if (nseg) *nseg = ns;
+    if (!x || !out) return;                    // (a query of the length)
+    DeviceMemory tmp;
+    const OpScratch w = forward_scratch(tmp, s, on_device);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(ns);
+    ExtProj<T> ext(s.spec, stream_);
+    const T* dv = queue_forward(w, s, x, on_device);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)s.Mtrue * sizeof(T));
+      ext.observe(dv, dout, nullptr, nullptr, nullptr);
+    }
+    finish_call(on_device, out, dout, ns);
+  }
+
   // sipx_l1_weighted_norm(_dev): (T) sum_i w_i |(A x)_i| of the weighted l1 set behind op, by the observe() of a throw-away projector of
   // that set: the first pass of its iteration (l1_weighted.h)
   void l1_weighted_norm(int op, const void* x, const void* w, void* out, bool on_device) override {
@@ -3499,6 +3551,10 @@ class Engine : public EngineBase {
     }
     if (d->proj == SIPX_PROJ_L1_WEIGHTED) {
       project_l1_weighted(d, v, len);
+      return;
+    }
+    if (d->proj == SIPX_PROJ_SIMPLEX) {
+      project_simplex(d, v, len);
       return;
     }
     Grid g1;
@@ -3753,7 +3809,19 @@ class Engine : public EngineBase {
       for (int q = 0; q < 4; ++q) lc[q] += c[q];
     }
     o += ", \"l1_weighted\": {\"passes\": " + std::to_string(lc[0]) + ", \"flag_reads\": " + std::to_string(lc[1]) +
-         ", \"calls\": " + std::to_string(lc[2]) + ", \"n\": " + std::to_string(lc[3]) + "}}";
+         ", \"calls\": " + std::to_string(lc[2]) + ", \"n\": " + std::to_string(lc[3]) + "}";
+    // simplex sets: the calls since the reset, those of the lane route and of the tile route (summed over such sets and the stand-alone
+    // projections of this context), the segments of the last one
+    long long sc[4] = {project_sc_[0], project_sc_[1], project_sc_[2], project_sc_[3]};
+    for (const auto& st : sets_) {
+      if (!st.ext || st.ext_kind != EXT_SIMPLEX_SEG) continue;
+      long long c[4];
+      st.ext->route_counts(c);
+      for (int q = 0; q < 3; ++q) sc[q] += c[q];
+      sc[3] = c[3];
+    }
+    o += ", \"simplex\": {\"calls\": " + std::to_string(sc[0]) + ", \"lane\": " + std::to_string(sc[1]) + ", \"tile\": " +
+         std::to_string(sc[2]) + ", \"nseg\": " + std::to_string(sc[3]) + "}}";
     if (!peek) start_stats(enable);
     return o.c_str();
   }
@@ -4484,6 +4552,7 @@ class Engine : public EngineBase {
   long long batch_searches_ = 0, batch_fallbacks_ = 0;
   long long routes_[RT_COUNT] = {};     // launches per route since finalize (RouteId; obs_route)
   long long project_rc_[4] = {0, 0, 0, 0};   // route counters of the rank projectors that project() built and dropped
+  long long project_sc_[4] = {0, 0, 0, 0};   // ... and of the simplex projectors (calls, lane route, tile route; the segments of the last)
   T* fbuf_ = nullptr;                 // fast segments: world x two-pass sets x (fcap + header)
   bool yl_multi_ = true;              // SIPX_YL_MULTI=0: never take the one-sweep y/l update (A/B switch)
   bool x0_mode_ = false;              // s_0 = A x_0 recomputed from a snapshot of x (see finalize)

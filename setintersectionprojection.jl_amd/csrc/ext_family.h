@@ -1,7 +1,8 @@
 // Private to the ext_*.hip units: what ExtProj<T> (ext_proj.h) forwards to, one object per family of projectors --
 //   ext_transform.hip  DFT mask, l1 and cardinality behind the DFT, DCT, DWT
 //   ext_rank.hip       slice / matrix rank, nuclear norm
-//   ext_segments.hip   cardinality, l1, l2 and annulus per fiber / slice (seg_norm.h), relaxed histogram, subspace
+//   ext_segments.hip   cardinality, l1, l2 and annulus per fiber / slice (seg_norm.h), the simplex per fiber / slice (seg_simplex.h),
+//                      relaxed histogram, subspace
 //   ext_group.hip      the l2,1 ball across the blocks of the TV / TV_xy operator: BallProj on the whole array (l21.h) or with groups
 //                      across the frames (l21_joint.h), FrameProj per z-slice (l21_seg.h); GroupsProj: the l2,1 ball whose groups are the
 //                      fibers or slices of a one-block operator's range (l21_groups.h); L1WProj: the weighted l1 ball on the rows of an

@@ -1,12 +1,14 @@
 // Projectors on the fibers, the slices or the whole of a materialised vector v that need no transform:
 //   cardinality per fiber / slice (one kernel), the l1 ball, the l2 ball and the annulus per fiber / slice (one kernel,
-//   seg_norm.h), the relaxed histogram (hipCUB sort), the subspace projection (rocBLAS).
+//   seg_norm.h), the simplex per fiber / slice (two kernels, seg_simplex.h), the relaxed histogram (hipCUB sort), the subspace
+//   projection (rocBLAS).
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
 
 #include "ext_family.h"
 #include "seg_norm.h"
+#include "seg_simplex.h"
 
 namespace sipx {
 
@@ -242,6 +244,59 @@ void seg_observe(const ExtSpec& spec, int norm_l2, const T* v, T* out, hipStream
 template void seg_observe<float>(const ExtSpec&, int, const float*, float*, hipStream_t);
 template void seg_observe<double>(const ExtSpec&, int, const double*, double*, hipStream_t);
 
+// The simplex of every fiber / slice (seg_simplex.h): nonnegative entries with a sum in [pmin, pmax], one pair of scalars for all
+// segments.  Short fibers with contiguous neighbours go through the lane route, one lane a segment; everything else through the tile
+// mapping of the norm sets.  Nothing is kept between calls; the counters are for sipx_kernel_stats.
+template <typename T>
+struct SimplexSegProj : ExtImpl<T> {
+  SegMap map{};
+  SegNormPlan plan{};
+  int bucket = 0;                     // simplex_lane_bucket: 0: the tile route
+  long long nchunk = 0, ntile = 0;    // lane route: tiles of 64 segments a row, in all
+  unsigned lane_grid = 1;
+  long long calls = 0;
+  SimplexSegProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    if (spec.mode != SIPX_MODE_FIBER && spec.mode != SIPX_MODE_SLICE) throw std::runtime_error(SIMPLEX_NEEDS_MODE);
+    if (spec.ndim == 2 && spec.mode != SIPX_MODE_FIBER) throw std::runtime_error(SIMPLEX_2D_SLICE);
+    if (spec.lb || spec.ub) throw std::runtime_error(SIMPLEX_NO_VECTORS);
+    simplex_check_bounds<T>(spec.pmin, spec.pmax);
+    map = make_segmap(spec);
+    if (map.nseg < 1 || map.L < 1 || map.L >= (1ll << 31)) throw std::runtime_error("simplex sets: empty or oversize segments");
+    plan = seg_norm_plan(map, (int)sizeof(T));
+    bucket = simplex_lane_bucket(map);
+    nchunk = (map.SA + 63) / 64;
+    ntile = nchunk * (map.nseg / map.SA);
+    const long long nb = (ntile + BLOCK / 64 - 1) / (BLOCK / 64);
+    lane_grid = (unsigned)(nb < SEGN_MAX_GRID ? (nb < 1 ? 1 : nb) : SEGN_MAX_GRID);
+  }
+  template <int LB, bool OBS>
+  void lane(T* v, T* out) {
+    hipLaunchKernelGGL((k_simplex_lane<T, LB, OBS>), dim3(lane_grid), dim3(BLOCK), 0, this->stream, map, nchunk, ntile, v,
+                       (T)this->sp.pmin, (T)this->sp.pmax, out);
+  }
+  template <bool OBS>
+  void launch(T* v, T* out) {
+    if (bucket == 4) lane<4, OBS>(v, out);
+    else if (bucket == 8) lane<8, OBS>(v, out);
+    else if (bucket == 16) lane<16, OBS>(v, out);
+    else
+      hipLaunchKernelGGL((k_simplex_tile<T, OBS>), dim3(plan.grid), dim3(BLOCK), OBS ? 0u : plan.lds_bytes, this->stream, map, plan, v,
+                         (T)this->sp.pmin, (T)this->sp.pmax, out);
+    SIPX_HIP(hipGetLastError());
+  }
+  void project(T* v, bool, double*, T*, T*) override {
+    ++calls;
+    launch<false>(v, (T*)nullptr);
+  }
+  // out[s] <- (T)spos of segment s (nseg entries): pass 1 of the projector's own route; v is not written
+  void observe(const T* v, T* out, double*, T*, T*) override { launch<true>(const_cast<T*>(v), out); }
+  void reset() override { calls = 0; }
+  // calls, those of the lane route, those of the tile route, the segments
+  void route_counts(long long out[4]) const override {
+    out[0] = calls; out[1] = bucket ? calls : 0; out[2] = bucket ? 0 : calls; out[3] = map.nseg;
+  }
+};
+
 template <typename T>
 struct HistogramProj : ExtImpl<T> {
   SegMap map{};
@@ -334,6 +389,7 @@ template <typename T>
 ExtImpl<T>* make_segment_family(const ExtSpec& spec, hipStream_t stream) {
   if (spec.kind == EXT_CARD_SEG) return new CardSegProj<T>(spec, stream);
   if (spec.kind == EXT_L1_SEG || spec.kind == EXT_L2_SEG || spec.kind == EXT_ANNULUS_SEG) return new NormSegProj<T>(spec, stream);
+  if (spec.kind == EXT_SIMPLEX_SEG) return new SimplexSegProj<T>(spec, stream);
   if (spec.kind == EXT_HISTOGRAM) return new HistogramProj<T>(spec, stream);
   return new SubspaceProj<T>(spec, stream);
 }

@@ -12,6 +12,7 @@
 #include "l21_groups.h"      // (the refusals and the descriptor check of the l2,1 ball over fibers / slices)
 #include "l21_weighted.h"    // (the host checks of the weighted l2,1 sets)
 #include "l1_weighted.h"     // (the refusals and the host checks of the weighted l1 ball)
+#include "seg_simplex.h"     // (the refusals and the check of the bounds of the simplex sets)
 
 namespace sipx {
 
@@ -101,7 +102,8 @@ void expand_fiber_bounds(const ConfigCtx& c, const SetConfig<T>& s, const T* per
 // of a slab-decomposed solve is single-block.  TV_XY: the slab routes know TV's one block per dimension only.  L21_GROUPS: the segments
 // of the l2,1 ball over fibers / slices share one budget, a rank would see its slab's segments (or its part of every slice) only.
 // L1_WEIGHTED: the weights live in the one projector of a single process, in the padded layout of the whole operator.
-enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED };
+// SIMPLEX: not built for sharded contexts yet (seg_simplex.h); a rank would see its part of every slice only.
+enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX };
 inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
   if (c.single_process) return;
   switch (which) {
@@ -118,6 +120,8 @@ inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
       throw std::runtime_error(L21G_SHARDED);
     case Sharded::L1_WEIGHTED:
       throw std::runtime_error(L1W_SHARDED);
+    case Sharded::SIMPLEX:
+      throw std::runtime_error(SIMPLEX_SHARDED);
   }
 }
 // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
@@ -235,6 +239,13 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(L1W_NO_TRANSFORM);
     if (s.comp) throw std::runtime_error(L1W_NO_MINKOWSKI);
     if (mode != SIPX_MODE_WHOLE) throw std::runtime_error(L1W_NO_MODE);
+  }
+  // so are the simplex sets (seg_simplex.h): a one-block operator, no transform, no component, a mode
+  if (d->proj == SIPX_PROJ_SIMPLEX) {
+    if (s.custom || s.nblk > 1) throw std::runtime_error(SIMPLEX_ONE_BLOCK);
+    if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(SIMPLEX_NO_TRANSFORM);
+    if (s.comp) throw std::runtime_error(SIMPLEX_NO_MINKOWSKI);
+    if (mode == SIPX_MODE_WHOLE) throw std::runtime_error(SIMPLEX_NEEDS_MODE);
   }
   if (mode != SIPX_MODE_WHOLE) {
     if (dir < 0 || dir >= c.ndim) throw std::runtime_error("application mode: direction out of range for this grid");
@@ -445,6 +456,13 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       }
       break;
     }
+    case SIPX_PROJ_SIMPLEX:  // entries >= 0 and a sum in [pmin, pmax] per fiber or slice (operator, transform, component, mode: above)
+      if (c.ndim == 2 && mode == SIPX_MODE_SLICE) throw std::runtime_error(SIMPLEX_2D_SLICE);
+      if (d->lb || d->ub) throw std::runtime_error(SIMPLEX_NO_VECTORS);
+      refuse_sharded(c, Sharded::SIMPLEX);
+      simplex_check_bounds<T>(d->pmin, d->pmax);
+      ext(EXT_SIMPLEX_SEG);
+      break;
     case SIPX_PROJ_RANK: ext(EXT_RANK); break;
     case SIPX_PROJ_NUCLEAR: ext(EXT_NUCLEAR); break;
     case SIPX_PROJ_HISTOGRAM:

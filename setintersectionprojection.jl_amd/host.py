@@ -41,14 +41,14 @@ EXPORTED_SYMBOLS = [
     "sipx_l21_norm", "sipx_l21_norm_dev", "sipx_l21_norms", "sipx_l21_norms_dev",
     "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev", "sipx_l21_weighted_norm", "sipx_l21_weighted_norm_dev",
     "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev", "sipx_tnv_norm", "sipx_tnv_norm_dev",
-    "sipx_l1_weighted_norm", "sipx_l1_weighted_norm_dev",
+    "sipx_l1_weighted_norm", "sipx_l1_weighted_norm_dev", "sipx_segment_sums", "sipx_segment_sums_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16,
-        "tnv": 17, "l1_weighted": 18}
+        "tnv": 17, "l1_weighted": 18, "simplex": 19}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -99,6 +99,23 @@ L1W_NEEDS_WEIGHTS = ("the weighted l1 ball (l1_weighted) needs weights, one per 
 L1W_NO_COARSE = ("multilevel: the weighted l1 ball (l1_weighted) has no rule that takes its weights to a coarser grid yet -- solve on one "
                  "level, or use the plain (\"l1\", op)")
 L1W_WEIGHTS_ARE_LB = ("set_data: the weights of the weighted l1 ball are its lb; it has no ub (the radius is fixed when the set is built)")
+# simplex sets (csrc/seg_simplex.h): entries >= 0 and a sum in [min, max] on every fiber / slice of the range of a one-block operator; the
+# engine's refusals, word for word, and the front end's own
+SIMPLEX_NEEDS_MODE = ("the simplex set (simplex) on the whole array is not built yet: it constrains every fiber or slice -- use a "
+                      "(\"fiber\", d) or (\"slice\", d) mode, or (\"bounds\") together with (\"l1\") on the whole array as a stand-in")
+SIMPLEX_2D_SLICE = "for 2D models, the mode of application for simplex sets needs to be (fiber,x) or (fiber,z)"
+SIMPLEX_ONE_BLOCK = ("the simplex set (simplex) constrains the fibers or slices of the range of a one-block operator: TD_OP must "
+                     "be the identity, D_x, D_y or D_z -- for TV or a custom operator use one set per direction")
+SIMPLEX_NO_TRANSFORM = ("the simplex set (simplex) takes no transform (DFT, DCT, wavelet): it acts on A x itself -- use it "
+                        "with TD_OP identity, D_x, D_y or D_z")
+SIMPLEX_NO_MINKOWSKI = ("the simplex set (simplex) takes no Minkowski component: constrain the sum of the components "
+                        "with a set on the identity instead")
+SIMPLEX_NO_VECTORS = ("the simplex set (simplex) takes one pair of scalars (min, max) for all segments for now and no lb / ub "
+                      "vectors: use (\"l1\", op, mode) with one radius per segment beside (\"bounds\")")
+SIMPLEX_BAD_BOUNDS = ("the simplex set (simplex) needs 0 <= min <= max, max > 0, both finite: every segment has entries >= 0 "
+                      "and a sum in [min, max] (min = max = 1: the probability simplex, min = 0: the capped one)")
+SIMPLEX_NO_WEIGHTS = "the simplex set (simplex) takes no weights: scale the array, or use (\"l1_weighted\", op) beside (\"bounds\")"
+SIMPLEX_NO_COARSE = ("multilevel: the simplex set (simplex) has no rule that takes its segments to a coarser grid yet -- solve on one level")
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
 TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
 TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
@@ -437,6 +454,8 @@ class Projector:
             self.seg_radii = False
             self.kind, self.pmax, self.op = "tnv", float(constraint.max), "TV_xy"
             return
+        if getattr(constraint, "weights", None) is not None and st == "simplex":
+            raise SipxError(SIMPLEX_NO_WEIGHTS)
         if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint", "l21_groups", "l1_weighted"):
             raise SipxError(f"set type {st!r} takes no weights: " + L21_WEIGHTS_WHERE)
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
@@ -465,6 +484,28 @@ class Projector:
             self.kind, self.pmax, self.op = "l1_weighted", float(constraint.max), constraint.TD_OP
             self._take_weights(constraint, TDOperator(constraint.TD_OP, comp_grid, self.TF).shape[0],
                                f"row of {constraint.TD_OP}, in the order of A @ x")
+            return
+        if st == "simplex":
+            # entries >= 0 and min <= sum <= max on every fiber / slice of the range of a one-block operator (csrc/seg_simplex.h)
+            cust = constraint.custom_TD_OP[0]
+            if not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+                raise SipxError(SIMPLEX_ONE_BLOCK)
+            if constraint.TD_OP in SPECIAL_OPERATORS:
+                raise SipxError(SIMPLEX_NO_TRANSFORM)
+            if constraint.TD_OP not in ONE_BLOCK_OPERATORS:
+                raise SipxError(SIMPLEX_ONE_BLOCK)
+            if constraint.TD_OP == "D_y" and len(n) == 2:
+                raise SipxError(UNKNOWN_OPERATOR)
+            if not self.mode:
+                raise SipxError(SIMPLEX_NEEDS_MODE)
+            if len(n) == 2 and self.mode == MODES["slice"]:
+                raise SipxError(SIMPLEX_2D_SLICE)
+            if np.ndim(constraint.max) != 0 or np.ndim(constraint.min) != 0:
+                raise SipxError(SIMPLEX_NO_VECTORS)
+            lo, hi = self.TF(constraint.min), self.TF(constraint.max)
+            if not (lo >= 0 and lo <= hi and hi > 0 and np.isfinite(hi)):
+                raise SipxError(SIMPLEX_BAD_BOUNDS)
+            self.kind, self.pmin, self.pmax, self.op = "simplex", float(constraint.min), float(constraint.max), constraint.TD_OP
             return
         if st == "l21_groups":
             # group sparsity: one l2,1 ball whose groups are the fibers / slices of the range of a one-block operator (csrc/l21_groups.h);
@@ -711,6 +752,11 @@ class Projector:
                 raise SipxError(L21G_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
             if getattr(op, "component", 0):
                 raise SipxError(L21G_NO_MINKOWSKI)
+        if self.kind == "simplex":
+            if op.kind != self.op:
+                raise SipxError(SIMPLEX_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
+            if getattr(op, "component", 0):
+                raise SipxError(SIMPLEX_NO_MINKOWSKI)
         if self.kind == "l1_weighted":
             if op.kind == "custom":
                 raise SipxError(L1W_NO_CUSTOM)
@@ -780,13 +826,14 @@ class Projector:
         if v.dtype.type != self.TF or not v.flags.c_contiguous:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
-                                                                              "subspace", "l21", "l21_joint", "l21_groups", "tnv", "l1_weighted")
-        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted")
+                                                                              "subspace", "l21", "l21_joint", "l21_groups", "tnv", "l1_weighted",
+                                                                              "simplex")
+        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex")
         if l21:                      # the M-vector of the TV range (l21_groups: of its operator's) in the reference's row order, on the grid
             op = TDOperator(self.op, self.comp_grid, self.TF)
             rows = op.shape[0]
             if v.shape != (rows,):
-                what = "weighted l1 ball" if self.kind == "l1_weighted" else "l2,1 ball"
+                what = {"l1_weighted": "weighted l1 ball", "simplex": "simplex set"}.get(self.kind, "l2,1 ball")
                 raise SipxError(f"the {what} projects a vector of the {self.op} range: {rows} entries on this grid, {v.size} given")
             self.check_rows(op)
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
@@ -869,7 +916,12 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
 
     ("l1_weighted", op, matrix / tensor) on the identity, D_x, D_y, D_z, TV or TV_xy is the weighted l1 ball (csrc/l1_weighted.h):
     sum_i w_i |(A x)_i| <= max with one finite weight >= 0 per row of A in the order of A @ x (weights, required; 0 leaves a row free) --
-    the set of iteratively reweighted l1 and of anisotropic TV with a weight per direction."""
+    the set of iteratively reweighted l1 and of anisotropic TV with a weight per direction.
+
+    ("simplex", op, min, max, ("fiber", d) / ("slice", d)) on the identity, D_x, D_y or D_z makes every fiber / slice of the array of shape
+    TD_n nonnegative with a sum in [min, max] (csrc/seg_simplex.h): min = max = 1 is the probability simplex of material fractions and
+    class probabilities along the frame axis, min = 0 the capped one; one pair of scalars for all segments.  segment_sums() observes the
+    sums."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -887,7 +939,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.max = np.asarray(c.max, TF)
         if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
             c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
-        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted"):
+        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -1929,10 +1981,16 @@ def segment_norms(x, comp_grid, TD_OP: str, app_mode, norm: str):
     TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
     if TF not in (np.float32, np.float64):
         raise SipxError("segment_norms: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    return _segment_observe(x, comp_grid, TD_OP, am, TF, on_dev, "l2", "sipx_segment_norms", (0 if norm == "l1" else 1,))
+
+
+def _segment_observe(x, comp_grid, TD_OP, am, TF, on_dev, set_type, fn_name, extra):
+    """What segment_norms and segment_sums share: one number per fiber / slice of A x by the library call fn_name (its _dev form for a
+    tensor), in a context of its own; set_type names the set whose mode, direction and refusals apply."""
     n, _ = _grid(comp_grid)
     if TD_OP == "D_y" and len(n) == 2:
         raise SipxError("provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options")
-    P = Projector(set_definitions("l2", TD_OP, 0.0, 1.0, am), comp_grid, TF)      # mode, direction and their refusals
+    P = Projector(set_definitions(set_type, TD_OP, 0.0, 1.0, am), comp_grid, TF)      # mode, direction and their refusals
     nseg = P.nseg(TDOperator(TD_OP, comp_grid, TF))
     N = int(np.prod(n))
     if on_dev:
@@ -1942,25 +2000,44 @@ def segment_norms(x, comp_grid, TD_OP: str, app_mode, norm: str):
         device = x.device.index if x.device.index is not None else torch.cuda.current_device()
         out = torch.empty(nseg, dtype=x.dtype, device=torch.device("cuda", device))
         xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
-        fn = lib().sipx_segment_norms_dev
+        fn = getattr(lib(), fn_name + "_dev")
     else:
         x = _check_array("x", x, TF, N)
         device = None
         out = np.empty(nseg, TF)
         xp, op_ = _ptr(x), _ptr(out)
-        fn = lib().sipx_segment_norms
+        fn = getattr(lib(), fn_name)
     ctx = Context(comp_grid, TF, device)
     try:
         if on_dev:
             ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
         cnt = C.c_int64()
-        _chk(fn(ctx.h, OPS[TD_OP], P.mode, P.dir, 0 if norm == "l1" else 1, None, None, C.byref(cnt)))      # the count only
+        _chk(fn(ctx.h, OPS[TD_OP], P.mode, P.dir, *extra, None, None, C.byref(cnt)))      # the count only
         if cnt.value != nseg:
             raise SipxError(f"internal: the engine counts {cnt.value} segments, the host {nseg}")
-        _chk(fn(ctx.h, OPS[TD_OP], P.mode, P.dir, 0 if norm == "l1" else 1, xp, op_, C.byref(cnt)))
+        _chk(fn(ctx.h, OPS[TD_OP], P.mode, P.dir, *extra, xp, op_, C.byref(cnt)))
     finally:
         ctx.close()
     return out
+
+
+def segment_sums(x, comp_grid, TD_OP: str, app_mode):
+    """The sum of the positive parts of every fiber / slice of A x, sum_i max((A x)_i, 0): nseg numbers of the working precision (that of
+    x) in the order of segment_norms(), arguments as there.  Computed by pass 1 of the ("simplex", TD_OP, app_mode) projector
+    (sipx_segment_sums, csrc/seg_simplex.h): the very numbers it compares with min and max, so a nonnegative A x is not written by a
+    simplex set built with min = the smallest and max = the largest of them.  x: a numpy vector or a 1-D torch tensor on a GPU."""
+    if TD_OP in SPECIAL_OPERATORS:
+        raise SipxError(SIMPLEX_NO_TRANSFORM)
+    if TD_OP not in ONE_BLOCK_OPERATORS:
+        raise SipxError(SIMPLEX_ONE_BLOCK)
+    am = tuple(app_mode)
+    if len(am) != 2 or am[0] not in ("fiber", "slice"):
+        raise SipxError(SIMPLEX_NEEDS_MODE)
+    on_dev = _is_tensor(x)
+    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("segment_sums: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    return _segment_observe(x, comp_grid, TD_OP, am, TF, on_dev, "simplex", "sipx_segment_sums", ())
 
 
 def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after, weights=None, groups=0, no_weights=()):

@@ -30,6 +30,8 @@ def constraint2coarse(constraint, comp_grid, cf):
             raise host.SipxError(host.L21G_NO_COARSE)
         if c.set_type == "l1_weighted":
             raise host.SipxError(host.L1W_NO_COARSE)
+        if c.set_type == "simplex":
+            raise host.SipxError(host.SIMPLEX_NO_COARSE)
         if getattr(c, "weights", None) is not None:
             raise host.SipxError(host.L21_WEIGHTS_NO_COARSE)
         if c.set_type == "rank":
