@@ -197,7 +197,25 @@ enum {
                             side), rounded once to TF, y_i = max(v_i - theta, +0) in TF; an all-zero segment with pmin > 0 is filled
                             with pmin / L.  No floating-point atomics, no state between calls: two calls give the same bits.  Holds
                             no replaceable vectors.  sipx_project takes the M-vector of the operator's range in the reference's row
-                            order; sipx_segment_sums observes (TF)spos */
+                            order; sipx_segment_sums observes (TF)spos */,
+  SIPX_PROJ_CARD_GROUPS = 20 /* group cardinality (no counterpart in the reference): { v = A x : at most k segments of v are non-zero },
+                                a segment being a fiber along dir (mode FIBER) or a slice orthogonal to it (mode SLICE, 3-D grids) of the
+                                array of shape TD_n, nseg segments in the order of sipx_segment_norms -- the non-convex counterpart of
+                                SIPX_PROJ_L21_GROUPS ("at most k traces change", "at most k frames are active"); set ncvx = 1.  op:
+                                IDENTITY, DX, DY or DZ, transform NONE, no component, no custom operator.  pmax = k, an integer >= 1
+                                that, where k < nseg, is exactly representable in TF (Float32: k <= 2^24); pmin is ignored, lb = ub =
+                                NULL, reserved = 0.  g_s = the l2 norm of segment s, the bits SIPX_PROJ_L21_GROUPS forms (fibers: those
+                                of sipx_segment_norms with norm 1); #{g_s > 0} <= k, k >= nseg included: nothing is written, -0.0
+                                included; otherwise the k first segments of the stable descending order of g (magnitude descending,
+                                ties to the lower segment index) are neither read again nor written, and every entry of the others is
+                                written +0.  Pads of the layout are neither read nor written; no floating-point atomics: two calls give
+                                the same bits (csrc/card_groups.h).  Mode WHOLE, multi-block and custom operators, transforms, Minkowski
+                                components, vectors and contexts with a communicator, a slab decomposition or set ownership are
+                                refused, each with a text that names the way out.  Holds no replaceable vectors (sipx_set_data
+                                refuses).  sipx_project takes the M-vector of the operator's range in the reference's row order;
+                                sipx_group_norms observes g.  sipx_kernel_stats_json reports "card_groups": {calls, small,
+                                search, nseg}: projections since the reset, the selections run by either route (a projection with
+                                k >= nseg runs none), the segments */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -458,6 +476,17 @@ int sipx_segment_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, int norm, c
  * smallest and pmax = the largest of them.  Refused where the set is refused. */
 int sipx_segment_sums(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
 int sipx_segment_sums_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
+/* The l2 norms of the fibers / slices of A x as SIPX_PROJ_CARD_GROUPS selects on them: out[s] = g_s, TF[nseg], arguments, count, order,
+ * queries and the _dev form as sipx_segment_norms.  Formed by the norms launch of that projector on (op, mode, dir)
+ * (csrc/card_groups.h) -- fibers: the bits of sipx_segment_norms with norm 1; slices: chunked compensated sums, within one unit of TF of
+ * the exactly summed norm.  CONTRACT: the array is the selection key itself: the projector keeps the first k segments of its stable
+ * descending order, and the count it compares with k is the number of non-zero entries of out.  Refused where the set is refused. */
+int sipx_group_norms(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
+int sipx_group_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
+/* A hook of the tests and of tools/card_groups_bench.py, not for applications: the selection route of the SIPX_PROJ_CARD_GROUPS projectors
+ * built from now on in this process.  0: by the number of segments (the default), 1: the one-workgroup rank count (refused for more than
+ * CARDG_SMALL_MAX segments), 2: the engine's cardinality search.  Both routes give the same bits. */
+int sipx_card_groups_route(int route);
 /* The isotropic total variation of x: *out = ||TV x||_2,1 as one TF, x TF[N] on the 2-D or 3-D grid of the context (which needs no sets
  * and no finalize).  TV x comes from the engine's operator product into scratch of the call; the group norms are formed by the kernel of
  * SIPX_PROJ_L21 and summed by the first pass of its threshold search.  CONTRACT: the value is the very number the projector compares

@@ -70,6 +70,10 @@ const SIPX_PROJ_L1_WEIGHTED = 18
 # csrc/seg_simplex.h), set_type = "simplex".  The reference's setup_constraints cannot set such a set up and this binding does not build it
 # yet: the constant is mirrored for callers of the C ABI, projector_fields refuses the tag and names the stand-in.
 const SIPX_PROJ_SIMPLEX = 19
+# group cardinality: at most k non-zero fibers / slices of the range of identity, D_x, D_y or D_z (include/sipx.h, csrc/card_groups.h),
+# set_type = "card_groups", max = k, min ignored.  Not a set of the reference; its setup_constraints leaves ncvx false for an unknown
+# tag, so set set_Prop.ncvx[i] = true for such a set, as for cardinality and rank.
+const SIPX_PROJ_CARD_GROUPS = 20
 const MODE = Dict("matrix" => 0, "tensor" => 0, "fiber" => 1, "slice" => 2)
 const SPECIAL = ("DFT", "DCT", "wavelet", "curvelet")          # src/setup_constraints.jl:54
 # the seven @timeit sections of src/PARSDMM.jl:40,100,105,113,152,163,229
@@ -155,6 +159,15 @@ function projector_fields(c, TF)
         return (16, 0.0, Float64(c.max), nothing_[3:5]...)
     end
     st == "l1_weighted" && error("the weighted l1 ball (l1_weighted, SIPX_PROJ_L1_WEIGHTED) needs one weight per row of the operator, which this binding does not carry: use the plain (\"l1\", op), or the C ABI")
+    if st == "card_groups"
+        op in ("identity", "D_x", "D_y", "D_z") && c.custom_TD_OP[1] == [] ||
+            error("group cardinality (card_groups) counts the fibers or slices of the range of a one-block operator: TD_OP must be the identity, D_x, D_y or D_z (on TV or a custom operator use the cardinality set, which counts entries)")
+        c.app_mode[1] in ("fiber", "slice") ||
+            error("group cardinality (card_groups) needs a fiber or slice mode: on the whole array it has one group, which every k >= 1 keeps -- drop the set, or count entries with the cardinality set")
+        (c.max isa Real && isfinite(c.max) && c.max >= 1 && c.max == floor(c.max)) ||
+            error("group cardinality (card_groups) needs an integer k >= 1, the number of fibers or slices kept (k = 0 is the zero array: use bounds)")
+        return (SIPX_PROJ_CARD_GROUPS, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
     st == "simplex" && error("simplex sets (simplex, SIPX_PROJ_SIMPLEX) are not built in this binding yet: use (\"bounds\") together with (\"l1\", op, mode) and segment_norms=true, or the C ABI")
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "l2"          && return (3, 0.0, Float64(c.max), nothing_[3:5]...)

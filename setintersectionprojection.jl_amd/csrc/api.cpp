@@ -5,6 +5,7 @@
 
 #include "comm.h"
 #include "engine.h"
+#include "ext_proj.h"
 #include "learn.h"
 
 struct sipx_ctx {
@@ -143,6 +144,13 @@ int sipx_segment_sums(sipx_ctx* c, int op, int mode, int dir, const void* x, voi
 }
 int sipx_segment_sums_dev(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->segment_sums(op, mode, dir, x, out, nseg, true))
+}
+int sipx_card_groups_route(int route) { SIPX_TRY(sipx::card_groups_force_route(route)) }
+int sipx_group_norms(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->group_norms(op, mode, dir, x, out, nseg, false))
+}
+int sipx_group_norms_dev(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->group_norms(op, mode, dir, x, out, nseg, true))
 }
 int sipx_l21_norm(sipx_ctx* c, const void* x, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21, SIPX_OP_TV, SIPX_MODE_WHOLE, 0, x, out, nullptr, false, false))

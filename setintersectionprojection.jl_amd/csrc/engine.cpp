@@ -388,6 +388,7 @@ class Engine : public EngineBase {
       if (s.ext_kind == EXT_L21_GROUPS) refuse_sharded(ctx, Sharded::L21_GROUPS);
       if (s.ext_kind == EXT_L1_WEIGHTED) refuse_sharded(ctx, Sharded::L1_WEIGHTED);
       if (s.ext_kind == EXT_SIMPLEX_SEG) refuse_sharded(ctx, Sharded::SIMPLEX);
+      if (s.ext_kind == EXT_CARD_GROUPS) refuse_sharded(ctx, Sharded::CARD_GROUPS);
     }
     FinalizePlan P;
     plan_sets();
@@ -2938,6 +2939,7 @@ class Engine : public EngineBase {
       throw std::runtime_error(what + ": set index " + std::to_string(set) + " out of range (" + std::to_string(nsets) + " sets)");
     SetState<T>& s = sets_[set];
     if (s.comp) throw std::runtime_error(what + " is not available for Minkowski sets" + way_out);
+    if (s.ext_kind == EXT_CARD_GROUPS) throw std::runtime_error(what + ": " + CARDG_NO_SET_DATA);
     const bool bounds = !s.ext_kind && s.prox == SIPX_PROJ_BOUNDS_VEC, hist = s.ext_kind == EXT_HISTOGRAM || s.seg_radii || s.weighted;
     if (!bounds && !hist)
       throw std::runtime_error(what + ": set " + std::to_string(set) + " holds no replaceable vectors -- element-wise and per-fiber bounds "
@@ -3484,6 +3486,58 @@ class Engine : public EngineBase {
     finish_call(on_device, out, dout, ns);
   }
 
+  // SIPX_PROJ_CARD_GROUPS of sipx_project: the M-vector of the range of its one-block operator in the reference's row order
+  void project_card_groups(const sipx_set_desc* d, void* v, int64_t len) {
+    if (d->op != SIPX_OP_IDENTITY && d->op != SIPX_OP_DX && d->op != SIPX_OP_DY && d->op != SIPX_OP_DZ) throw std::runtime_error(CARDG_ONE_BLOCK);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> st;
+    configure_op(ctx, st, d->op);
+    configure_proj(ctx, st, d);
+    if (len != st.Mtrue)
+      throw std::runtime_error("group cardinality projects a vector of the operator's range: " + std::to_string(st.Mtrue) +
+                               " entries on this grid, " + std::to_string((long long)len) + " given");
+    DeviceMemory tmp;
+    T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
+    const SearchScratch q(tmp, seg_count(st.spec), false);
+    upload_rows(st, (const T*)v, dv);
+    {
+      ExtProj<T> ext(st.spec, stream_);
+      ext.project(dv, false, q.part, q.mp, q.dc);
+      long long c[4];                            // the route of a stand-alone call counts like a set's (card_groups row of sipx_kernel_stats)
+      ext.route_counts(c);
+      for (int r = 0; r < 3; ++r) project_gc_[r] += c[r];
+      project_gc_[3] = c[3];
+      download_rows(st, dv, (T*)v);               // (synchronises the stream)
+    }
+  }
+
+  // sipx_group_norms(_dev): the l2 norm of every fiber / slice of A x, in the order of sipx_segment_norms, by the observe() of a throw-away
+  // projector of the card_groups set on (op, mode, dir): its own norms launch (card_groups.h)
+  void group_norms(int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device) override {
+    SIPX_HIP(hipSetDevice(device_));
+    if (op != SIPX_OP_IDENTITY && op != SIPX_OP_DX && op != SIPX_OP_DY && op != SIPX_OP_DZ) throw std::runtime_error(CARDG_ONE_BLOCK);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, op);
+    sipx_set_desc d{};
+    d.op = op; d.proj = SIPX_PROJ_CARD_GROUPS; d.mode = mode; d.dir = dir; d.pmax = 1.0;
+    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the set
+    const long long ns = seg_count(s.spec);
+    if (nseg) *nseg = ns;
+    if (!x || !out) return;                    // (a query of the length)
+    DeviceMemory tmp;
+    const OpScratch w = forward_scratch(tmp, s, on_device);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(ns);
+    ExtProj<T> ext(s.spec, stream_);
+    const T* dv = queue_forward(w, s, x, on_device);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)s.Mtrue * sizeof(T));
+      ext.observe(dv, dout, nullptr, nullptr, nullptr);
+    }
+    finish_call(on_device, out, dout, ns);
+  }
+
   // sipx_l1_weighted_norm(_dev): (T) sum_i w_i |(A x)_i| of the weighted l1 set behind op, by the observe() of a throw-away projector of
   // that set: the first pass of its iteration (l1_weighted.h)
   void l1_weighted_norm(int op, const void* x, const void* w, void* out, bool on_device) override {
@@ -3555,6 +3609,10 @@ class Engine : public EngineBase {
     }
     if (d->proj == SIPX_PROJ_SIMPLEX) {
       project_simplex(d, v, len);
+      return;
+    }
+    if (d->proj == SIPX_PROJ_CARD_GROUPS) {
+      project_card_groups(d, v, len);
       return;
     }
     Grid g1;
@@ -3821,7 +3879,19 @@ class Engine : public EngineBase {
       sc[3] = c[3];
     }
     o += ", \"simplex\": {\"calls\": " + std::to_string(sc[0]) + ", \"lane\": " + std::to_string(sc[1]) + ", \"tile\": " +
-         std::to_string(sc[2]) + ", \"nseg\": " + std::to_string(sc[3]) + "}}";
+         std::to_string(sc[2]) + ", \"nseg\": " + std::to_string(sc[3]) + "}";
+    // card_groups sets: the projections since the reset, the selections run by the small route and by the search route -- a projection
+    // with k >= nseg runs none -- (summed over such sets and the stand-alone projections of this context), the segments of the last one
+    long long cg[4] = {project_gc_[0], project_gc_[1], project_gc_[2], project_gc_[3]};
+    for (const auto& st : sets_) {
+      if (!st.ext || st.ext_kind != EXT_CARD_GROUPS) continue;
+      long long c[4];
+      st.ext->route_counts(c);
+      for (int q = 0; q < 3; ++q) cg[q] += c[q];
+      cg[3] = c[3];
+    }
+    o += ", \"card_groups\": {\"calls\": " + std::to_string(cg[0]) + ", \"small\": " + std::to_string(cg[1]) + ", \"search\": " +
+         std::to_string(cg[2]) + ", \"nseg\": " + std::to_string(cg[3]) + "}}";
     if (!peek) start_stats(enable);
     return o.c_str();
   }
@@ -4553,6 +4623,7 @@ class Engine : public EngineBase {
   long long routes_[RT_COUNT] = {};     // launches per route since finalize (RouteId; obs_route)
   long long project_rc_[4] = {0, 0, 0, 0};   // route counters of the rank projectors that project() built and dropped
   long long project_sc_[4] = {0, 0, 0, 0};   // ... and of the simplex projectors (calls, lane route, tile route; the segments of the last)
+  long long project_gc_[4] = {0, 0, 0, 0};   // ... and of the card_groups projectors (calls, small route, search route; the segments of the last)
   T* fbuf_ = nullptr;                 // fast segments: world x two-pass sets x (fcap + header)
   bool yl_multi_ = true;              // SIPX_YL_MULTI=0: never take the one-sweep y/l update (A/B switch)
   bool x0_mode_ = false;              // s_0 = A x_0 recomputed from a snapshot of x (see finalize)

@@ -16,17 +16,23 @@
 // passes k_l21w_part / k_l21w_finish in batches gated on a device flag, then k_l21w_scale; without weights not one launch differs.
 // The ball whose groups are the fibers or slices of a one-block operator's range (EXT_L21_GROUPS, l21_groups.h, GroupsProj) shares only the
 // weighted iteration (L21WSearch): its norms and its scale kernel are its own.
+// Group cardinality on the same fibers or slices (EXT_CARD_GROUPS, card_groups.h, CardGroupsProj) shares that norms launch (GroupNorms) and
+// the coordinate -> segment arithmetic of the scale kernel; it selects by rank counting in one workgroup (k_cardg_rank) or by the engine's
+// cardinality search, and its apply kernel (k_cardg_zero) only stores.
 // Total nuclear variation (EXT_TNV, tnv.h, TnvProj) has the groups and the z-march of the joint ball, two numbers per pixel in the search
 // and a 2 x 2 matrix per pixel in place of the weight.
 // The weighted l1 ball on the rows of an operator (EXT_L1_WEIGHTED, l1_weighted.h, L1WProj) is the weighted iteration once more, on the pairs
 // (|v_i|, w_i) of the flat padded array: a pass kernel that reads v itself (k_l1w_part) and a soft-threshold apply (k_l1w_apply).
 // Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the projectors.
 // A projector's observe() runs the norms launch and the first sum of its own project(): what it reports is what project() decides on.
+#include <atomic>
+
 #include "ext_family.h"
 #include "l21.h"
 #include "l21_joint.h"
 #include "l21_seg.h"
 #include "l21_groups.h"
+#include "card_groups.h"
 #include "l21_weighted.h"
 #include "l1_weighted.h"
 #include "tnv.h"
@@ -637,6 +643,83 @@ __global__ __launch_bounds__(BLOCK) void k_l21g_scale(L21GArgs a, T* __restrict_
   }
 }
 
+// ---- EXT_CARD_GROUPS: at most k non-zero fibers or slices of a one-block operator's range (card_groups.h) -----------------------------------
+//     the norms launch of EXT_L21_GROUPS (GroupNorms)        g[s]                                           reads N words, writes nseg
+//     k_cardg_rank, or the engine's cardinality search on g   (need, tau, cut) into a ProjScalars            nseg words, which stay in cache
+//     k_cardg_zero                                            coords -> segment -> dropped: +0                reads nseg words, writes <= N
+// The small route of the selection: ONE workgroup, g staged in LDS; thread s owns segment s and counts its place r_s in the stable
+// descending order (cardg_rank_of).  The places are a permutation, so exactly one segment has r_s == k - 1 and writes (tau, cut); thread 0
+// writes need, and the values of "nothing is dropped" when there is none.  No atomics, no host read.
+template <typename T>
+__global__ __launch_bounds__(CARDG_SMALL_MAX) void k_cardg_rank(int nseg, int k, const T* __restrict__ g, ProjScalars<T>* __restrict__ ps) {
+  static_assert(CARDG_SMALL_MAX <= 1024 && CARDG_SMALL_MAX % 64 == 0, "one segment a thread of one workgroup");
+  __shared__ T sg[CARDG_SMALL_MAX];
+  __shared__ int snz[CARDG_SMALL_MAX / 64];
+  const int s = (int)threadIdx.x;
+  const T gs = s < nseg ? g[s] : T(0);
+  sg[s] = gs;
+  int nz = gs > T(0) ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nz += __shfl_down(nz, o, 64);
+  if ((threadIdx.x & 63) == 0) snz[threadIdx.x >> 6] = nz;
+  __syncthreads();                     // (sg and snz are complete)
+  int nnz = 0;
+#pragma unroll
+  for (int i = 0; i < CARDG_SMALL_MAX / 64; ++i) nnz += snz[i];
+  const bool need = k < nseg && nnz > k;
+  if (threadIdx.x == 0) {
+    ps->need = need ? 1 : 0;
+    if (!need) { ps->tau = T(0); ps->quota = CARDG_NO_CUT; }
+  }
+  if (!need || s >= nseg) return;
+  int r = 0;
+  for (int t = 0; t < nseg; ++t) {
+    const T gt = sg[t];                  // (every lane reads the same word: an LDS broadcast)
+    r += (gt > gs || (gt == gs && t < s)) ? 1 : 0;
+  }
+  if (r == k - 1) { ps->tau = gs; ps->quota = (long long)s; }
+}
+
+// Grid-stride over the padded grid, VW points of one grid line per thread, the coordinate -> segment arithmetic of k_l21g_scale.  v is
+// never loaded: a dropped segment's entries are stored as +0 -- one 16-byte store where all VW points are valid and dropped, scalar
+// stores otherwise -- and a kept segment, a pad, or anything at all when the selection found nothing to drop, is not touched.
+template <typename T, int VW>
+__global__ __launch_bounds__(BLOCK) void k_cardg_zero(L21GArgs a, T* __restrict__ v, const T* __restrict__ g, const ProjScalars<T>* __restrict__ ps) {
+  if (!ps->need) return;
+  const T tau = ps->tau;
+  const long long cut = ps->quota;
+  const unsigned nvec = (unsigned)(a.G.N / VW), step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    const Coord c = coords(a.G, (long long)p);
+    if (c.j >= a.d[1] || c.k >= a.d[2]) continue;
+    const int sb = c.j * a.cs[1] + c.k * a.cs[2];
+    bool drop[VW], any = false, all = true;
+#pragma unroll
+    for (int q = 0; q < VW; ++q) {
+      drop[q] = false;
+      const int i = c.i + q;
+      if (i < a.d[0]) {
+        const int s = sb + i * a.cs[0];
+        drop[q] = !cardg_keeps<T>(g[s], (long long)s, tau, cut);
+      }
+      any = any || drop[q];
+      all = all && drop[q];
+    }
+    if (!any) continue;
+    if (all) {
+      Vec<T, VW> z;
+#pragma unroll
+      for (int q = 0; q < VW; ++q) z.v[q] = T(0);
+      stv<T, VW>(v + p, z);
+    } else {
+#pragma unroll
+      for (int q = 0; q < VW; ++q)
+        if (drop[q]) v[p + q] = T(0);
+    }
+  }
+}
+
 static void l21_check_spec(const ExtSpec& sp) {
   if (sp.nblk != 2 && sp.nblk != 3) throw std::runtime_error("the l2,1 ball needs the 2 or 3 blocks of the TV or TV_xy operator");
   if (sp.nblk > sp.ndim) throw std::runtime_error("the l2,1 ball: more blocks than grid dimensions");
@@ -1060,38 +1143,24 @@ static void l21g_check_spec(const ExtSpec& sp) {
   if (sp.ndim == 2 && sp.mode == SIPX_MODE_SLICE) throw std::runtime_error(L21G_2D_SLICE);
   if (sp.G.N >= (1ll << 31)) throw std::runtime_error("the l2,1 ball over fibers or slices: the grid needs fewer than 2^31 points");
 }
+// The norms launch of the sets whose groups are the fibers or slices of the valid block, with its plan, its g and its chunk partials:
+// GroupsProj and CardGroupsProj hold one each.  g[s], s < n, in the order of sipx_segment_norms (l21_groups.h RULE, PLAN).
 template <typename T>
-struct GroupsProj : ExtImpl<T> {
-  using ExtImpl<T>::sp;
-  using ExtImpl<T>::stream;
+struct GroupNorms {
   SegMap map{};
   L21GroupsPlan plan{};
-  long long n = 0;                     // segments: the entries of g and w, the length of the search
-  T *g = nullptr, *w = nullptr;
+  long long n = 0;                     // segments: the entries of g
+  T* g = nullptr;
   double* part = nullptr;              // slices: the chunk partials, 2 per (slice, chunk)
-  L21WSearch<T> ws;
-  GroupsProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
-    l21g_check_spec(sp);
-    if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-    map = make_segmap(sp);
-    if (map.nseg < 1 || map.L < 1) throw std::runtime_error("the l2,1 ball over fibers or slices: empty segments");
-    plan = l21_groups_plan(map, sp.mode, (int)sizeof(T));
+  void build(ExtImpl<T>& owner, const char* empty) {
+    map = make_segmap(owner.sp);
+    if (map.nseg < 1 || map.L < 1) throw std::runtime_error(empty);
+    plan = l21_groups_plan(map, owner.sp.mode, (int)sizeof(T));
     n = map.nseg;
-    g = this->template alloc<T>(n);
-    w = this->template alloc<T>(n);
-    if (plan.slices) part = this->template alloc<double>(2 * (size_t)(plan.ntA * plan.F * plan.nchunk));
-    ws.build(*this);
-    if (sp.lb) {
-      SIPX_HIP(hipMemcpy(w, sp.lb, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
-    } else if (sp.weighted) {
-      SIPX_HIP(hipMemsetAsync(w, 0, sizeof(T) * (size_t)n, s));      // (set_data brings them; until then no segment is constrained)
-    } else {
-      const std::vector<T> ones((size_t)n, T(1));
-      SIPX_HIP(hipMemcpy(w, ones.data(), sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
-    }
+    g = owner.template alloc<T>(n);
+    if (plan.slices) part = owner.template alloc<double>(2 * (size_t)(plan.ntA * plan.F * plan.nchunk));
   }
-  bool search_wide() const { return n % 4 == 0 && aligned16(g, w); }
-  void norms(const T* v) {
+  void run(hipStream_t stream, const ExtSpec& sp, const T* v) const {
     if (!plan.slices) {                // k_seg_observe with the tile mapping of seg_norm.h: the bits of sipx_segment_norms
       ObsScope obs(KID_L21G_NORMS, stream, (double)(map.nseg * map.L + n) * sizeof(T));
       hipLaunchKernelGGL((k_seg_observe<T, SEGN_L2>), dim3(plan.fiber.grid), dim3(BLOCK), 0, stream, map, plan.fiber, v, g);
@@ -1113,34 +1182,65 @@ struct GroupsProj : ExtImpl<T> {
     }
     SIPX_HIP(hipGetLastError());
   }
+};
+// grid point -> segment for k_l21g_scale and k_cardg_zero
+static L21GArgs l21g_args(const ExtSpec& sp) {
+  L21GArgs a;
+  a.G = sp.G;
+  a.G.set_fast_div();
+  for (int q = 0; q < 3; ++q) { a.d[q] = (int)sp.dims[q]; a.cs[q] = 0; }
+  if (sp.mode == SIPX_MODE_SLICE) {
+    a.cs[sp.dir] = 1;
+  } else {                             // make_segmap: s = c_a + d_a c_b over the two other axes a < b
+    const int ax = sp.dir == 0 ? 1 : 0, bx = sp.dir == 2 ? 1 : 2;
+    a.cs[ax] = 1;
+    a.cs[bx] = (int)sp.dims[ax];
+  }
+  return a;
+}
+
+template <typename T>
+struct GroupsProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  GroupNorms<T> nm;
+  long long n = 0;                     // segments: the entries of g and w, the length of the search
+  T* w = nullptr;
+  L21WSearch<T> ws;
+  GroupsProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    l21g_check_spec(sp);
+    if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+    nm.build(*this, "the l2,1 ball over fibers or slices: empty segments");
+    n = nm.n;
+    w = this->template alloc<T>(n);
+    ws.build(*this);
+    if (sp.lb) {
+      SIPX_HIP(hipMemcpy(w, sp.lb, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+    } else if (sp.weighted) {
+      SIPX_HIP(hipMemsetAsync(w, 0, sizeof(T) * (size_t)n, s));      // (set_data brings them; until then no segment is constrained)
+    } else {
+      const std::vector<T> ones((size_t)n, T(1));
+      SIPX_HIP(hipMemcpy(w, ones.data(), sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+    }
+  }
+  bool search_wide() const { return n % 4 == 0 && aligned16(nm.g, w); }
   void scale(T* v) {
     constexpr int W = l21_vec_width<T>();
     const bool wide = sp.G.n[0] % 4 == 0 && aligned16(v);
-    L21GArgs a;
-    a.G = sp.G;
-    a.G.set_fast_div();
-    for (int q = 0; q < 3; ++q) { a.d[q] = (int)sp.dims[q]; a.cs[q] = 0; }
-    if (sp.mode == SIPX_MODE_SLICE) {
-      a.cs[sp.dir] = 1;
-    } else {                           // make_segmap: s = c_a + d_a c_b over the two other axes a < b
-      const int ax = sp.dir == 0 ? 1 : 0, bx = sp.dir == 2 ? 1 : 2;
-      a.cs[ax] = 1;
-      a.cs[bx] = (int)sp.dims[ax];
-    }
     ObsScope obs(KID_L21G_SCALE, stream, (2.0 * sp.G.N + 2.0 * n) * sizeof(T));
-    hipLaunchKernelGGL((wide ? k_l21g_scale<T, W> : k_l21g_scale<T, 1>), dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream, a,
-                       v, g, w, ws.st, ws.theta);
+    hipLaunchKernelGGL((wide ? k_l21g_scale<T, W> : k_l21g_scale<T, 1>), dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream,
+                       l21g_args(sp), v, nm.g, w, ws.st, ws.theta);
     SIPX_HIP(hipGetLastError());
   }
   void project(T* v, bool, double*, T*, T*) override {
-    norms(v);
-    ws.run(stream, n, g, w, search_wide(), (T)sp.pmax);
+    nm.run(stream, sp, v);
+    ws.run(stream, n, nm.g, w, search_wide(), (T)sp.pmax);
     scale(v);
   }
   // out[0] <- (T)asum as project decides on it: its norms launch into its g, then the first pass of its iteration
   void observe(const T* v, T* out, double*, T*, T*) override {
-    norms(v);
-    ws.template pass<true>(stream, n, g, w, search_wide(), (T)INFINITY);
+    nm.run(stream, sp, v);
+    ws.template pass<true>(stream, n, nm.g, w, search_wide(), (T)INFINITY);
     ws.pick(stream, out);
   }
   void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
@@ -1151,6 +1251,79 @@ struct GroupsProj : ExtImpl<T> {
   // the passes of the last call (the first included), the reads of the flag it took, the calls so far, the segments
   void route_counts(long long out[4]) const override {
     out[0] = ws.last_passes; out[1] = ws.last_reads; out[2] = ws.calls; out[3] = n;
+  }
+};
+
+// ---- EXT_CARD_GROUPS: at most k non-zero fibers or slices of the valid block (card_groups.h) ------------------------------------------------
+// The norms launch of GroupsProj into a g of its own, the selection by one of two routes into the need / tau / quota of a ProjScalars,
+// k_cardg_zero.  The route is fixed when the projector is built: the small route where nseg <= CARDG_SMALL_MAX, unless
+// sipx_card_groups_route (a hook of the tests and of tools/card_groups_bench.py) forces one.  The search keeps one state for the y update
+// and one for the feasibility estimate; they warm-start its probes and do not change what it selects.  k >= nseg launches nothing.
+// (an atomic word: a test thread may set it while another builds a context; a projector reads it once, in its constructor)
+static std::atomic<int> g_cardg_route{0};      // 0: by nseg; 1: the small route (refused above its cap); 2: the search route
+void card_groups_force_route(int route) {
+  if (route < 0 || route > 2) throw std::runtime_error("sipx_card_groups_route: 0 (by the number of segments), 1 (small route) or 2 (search route)");
+  g_cardg_route.store(route, std::memory_order_relaxed);
+}
+static void cardg_check_spec(const ExtSpec& sp) {
+  if (sp.nblk > 1) throw std::runtime_error(CARDG_ONE_BLOCK);
+  if (sp.mode != SIPX_MODE_FIBER && sp.mode != SIPX_MODE_SLICE) throw std::runtime_error(CARDG_NEEDS_MODE);
+  if (sp.ndim == 2 && sp.mode == SIPX_MODE_SLICE) throw std::runtime_error(CARDG_2D_SLICE);
+  if (sp.lb || sp.ub) throw std::runtime_error(CARDG_NO_VECTORS);
+  if (sp.G.N >= (1ll << 31)) throw std::runtime_error(CARDG_TOO_LARGE);
+}
+template <typename T>
+struct CardGroupsProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  GroupNorms<T> nm;
+  long long n = 0, k = 0;              // segments; segments kept, clamped to n
+  bool small = false;
+  SearchState<T> search;               // search route: both states; small route: ps alone holds the result
+  long long calls = 0, selections = 0;      // projections since the reset; those that ran a selection (k < nseg)
+  CardGroupsProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    cardg_check_spec(sp);
+    nm.build(*this, "group cardinality (card_groups): empty segments");
+    n = nm.n;
+    cardg_check_k<T>(sp.pmax, n);
+    k = sp.pmax >= (double)n ? n : (long long)sp.pmax;
+    const int route = g_cardg_route.load(std::memory_order_relaxed);
+    if (route == 1 && n > CARDG_SMALL_MAX)
+      throw std::runtime_error("sipx_card_groups_route: the small route holds at most " + std::to_string(CARDG_SMALL_MAX) + " segments, this set has " +
+                               std::to_string(n));
+    small = route == 1 || (route == 0 && n <= CARDG_SMALL_MAX);
+    search.build(this->mem, s, small ? 0 : n);      // cidx: the tie cut of the search
+  }
+  void reset() override { search.reinit(stream); calls = selections = 0; }
+  void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
+    ++calls;
+    if (k >= n) return;                // every segment stays: nothing to select, nothing to write
+    ++selections;
+    nm.run(stream, sp, v);
+    ProjScalars<T>* ps = small ? search.ps : search.pick(feas);
+    if (small) {
+      ObsScope obs(KID_CARDG_RANK, stream, (double)n * sizeof(T));
+      hipLaunchKernelGGL((k_cardg_rank<T>), dim3(1), dim3(CARDG_SMALL_MAX), 0, stream, (int)n, (int)k, nm.g, ps);
+    } else {
+      K<T>::proj_scalars_arr(stream, n, nm.g, PX_CARD, T(0), (T)k, ps, partials, maxpart, compact, n);
+    }
+    constexpr int W = l21_vec_width<T>();
+    const bool wide = sp.G.n[0] % 4 == 0 && aligned16(v);
+    ObsScope obs(KID_CARDG_ZERO, stream, (double)sp.G.N * sizeof(T), ((double)nm.map.nseg * nm.map.L + n) * sizeof(T));
+    hipLaunchKernelGGL((wide ? k_cardg_zero<T, W> : k_cardg_zero<T, 1>), dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream,
+                       l21g_args(sp), v, nm.g, ps);
+    SIPX_HIP(hipGetLastError());
+  }
+  // out[s] <- g_s (nseg entries): the norms launch of project() into its own g, copied out; v is not written
+  void observe(const T* v, T* out, double*, T*, T*) override {
+    nm.run(stream, sp, v);
+    SIPX_HIP(hipMemcpyAsync(out, nm.g, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+  }
+  void set_data(const T*, const T*, bool) override { throw std::runtime_error(CARDG_NO_SET_DATA); }
+  // projections since the reset, the selections the small route ran, those the search route ran (a projection with k >= nseg runs
+  // none), the segments
+  void route_counts(long long out[4]) const override {
+    out[0] = calls; out[1] = small ? selections : 0; out[2] = small ? 0 : selections; out[3] = n;
   }
 };
 
@@ -1245,6 +1418,7 @@ template <typename T>
 ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
   if (spec.kind == EXT_L1_WEIGHTED) return new L1WProj<T>(spec, stream);
   if (spec.kind == EXT_L21_GROUPS) return new GroupsProj<T>(spec, stream);
+  if (spec.kind == EXT_CARD_GROUPS) return new CardGroupsProj<T>(spec, stream);
   if (spec.kind == EXT_TNV) return new TnvProj<T>(spec, stream);
   if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);
   if (spec.kind != EXT_L21 && spec.kind != EXT_L21_JOINT) throw std::runtime_error("unknown external projector");

@@ -13,6 +13,7 @@
 #include "l21_weighted.h"    // (the host checks of the weighted l2,1 sets)
 #include "l1_weighted.h"     // (the refusals and the host checks of the weighted l1 ball)
 #include "seg_simplex.h"     // (the refusals and the check of the bounds of the simplex sets)
+#include "card_groups.h"     // (the refusals and the check of k of group cardinality)
 
 namespace sipx {
 
@@ -103,7 +104,8 @@ void expand_fiber_bounds(const ConfigCtx& c, const SetConfig<T>& s, const T* per
 // of the l2,1 ball over fibers / slices share one budget, a rank would see its slab's segments (or its part of every slice) only.
 // L1_WEIGHTED: the weights live in the one projector of a single process, in the padded layout of the whole operator.
 // SIMPLEX: not built for sharded contexts yet (seg_simplex.h); a rank would see its part of every slice only.
-enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX };
+// CARD_GROUPS: the segments compete for k places across the whole array (card_groups.h).
+enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX, CARD_GROUPS };
 inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
   if (c.single_process) return;
   switch (which) {
@@ -122,6 +124,8 @@ inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
       throw std::runtime_error(L1W_SHARDED);
     case Sharded::SIMPLEX:
       throw std::runtime_error(SIMPLEX_SHARDED);
+    case Sharded::CARD_GROUPS:
+      throw std::runtime_error(CARDG_SHARDED);
   }
 }
 // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
@@ -246,6 +250,13 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(SIMPLEX_NO_TRANSFORM);
     if (s.comp) throw std::runtime_error(SIMPLEX_NO_MINKOWSKI);
     if (mode == SIPX_MODE_WHOLE) throw std::runtime_error(SIMPLEX_NEEDS_MODE);
+  }
+  // so is group cardinality (card_groups.h): a one-block operator, no transform, no component, a mode
+  if (d->proj == SIPX_PROJ_CARD_GROUPS) {
+    if (s.custom || s.nblk > 1) throw std::runtime_error(CARDG_ONE_BLOCK);
+    if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(CARDG_NO_TRANSFORM);
+    if (s.comp) throw std::runtime_error(CARDG_NO_MINKOWSKI);
+    if (mode == SIPX_MODE_WHOLE) throw std::runtime_error(CARDG_NEEDS_MODE);
   }
   if (mode != SIPX_MODE_WHOLE) {
     if (dir < 0 || dir >= c.ndim) throw std::runtime_error("application mode: direction out of range for this grid");
@@ -456,6 +467,14 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       }
       break;
     }
+    case SIPX_PROJ_CARD_GROUPS:  // at most pmax non-zero fibers or slices of the valid block (operator, transform, component, mode: above)
+      if (c.ndim == 2 && mode == SIPX_MODE_SLICE) throw std::runtime_error(CARDG_2D_SLICE);
+      if (d->lb || d->ub || d->reserved) throw std::runtime_error(CARDG_NO_VECTORS);
+      refuse_sharded(c, Sharded::CARD_GROUPS);
+      if (G.N >= (1ll << 31)) throw std::runtime_error(CARDG_TOO_LARGE);
+      ext(EXT_CARD_GROUPS);
+      cardg_check_k<T>(d->pmax, seg_count(s.spec));
+      break;
     case SIPX_PROJ_SIMPLEX:  // entries >= 0 and a sum in [pmin, pmax] per fiber or slice (operator, transform, component, mode: above)
       if (c.ndim == 2 && mode == SIPX_MODE_SLICE) throw std::runtime_error(SIMPLEX_2D_SLICE);
       if (d->lb || d->ub) throw std::runtime_error(SIMPLEX_NO_VECTORS);

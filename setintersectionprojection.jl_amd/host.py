@@ -42,13 +42,14 @@ EXPORTED_SYMBOLS = [
     "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev", "sipx_l21_weighted_norm", "sipx_l21_weighted_norm_dev",
     "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev", "sipx_tnv_norm", "sipx_tnv_norm_dev",
     "sipx_l1_weighted_norm", "sipx_l1_weighted_norm_dev", "sipx_segment_sums", "sipx_segment_sums_dev",
+    "sipx_group_norms", "sipx_group_norms_dev", "sipx_card_groups_route",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16,
-        "tnv": 17, "l1_weighted": 18, "simplex": 19}
+        "tnv": 17, "l1_weighted": 18, "simplex": 19, "card_groups": 20}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -116,6 +117,31 @@ SIMPLEX_BAD_BOUNDS = ("the simplex set (simplex) needs 0 <= min <= max, max > 0,
                       "and a sum in [min, max] (min = max = 1: the probability simplex, min = 0: the capped one)")
 SIMPLEX_NO_WEIGHTS = "the simplex set (simplex) takes no weights: scale the array, or use (\"l1_weighted\", op) beside (\"bounds\")"
 SIMPLEX_NO_COARSE = ("multilevel: the simplex set (simplex) has no rule that takes its segments to a coarser grid yet -- solve on one level")
+# group cardinality (csrc/card_groups.h): at most k non-zero fibers / slices of the range of a one-block operator; the engine's refusals,
+# word for word, and the front end's own
+CARDG_NEEDS_MODE = ("group cardinality (card_groups) needs a fiber or slice mode: on the whole array it has one group, which "
+                    "every k >= 1 keeps -- drop the set, or count entries with the cardinality set")
+CARDG_2D_SLICE = "for 2D models, the mode of application for card_groups sets needs to be (fiber,x) or (fiber,z)"
+CARDG_ONE_BLOCK = ("group cardinality (card_groups) counts the fibers or slices of the range of a one-block operator: TD_OP "
+                   "must be the identity, D_x, D_y or D_z (on TV or a custom operator use the cardinality set, which counts "
+                   "entries)")
+CARDG_NO_TRANSFORM = ("group cardinality (card_groups) takes no transform (DFT, DCT, wavelet): it acts on A x itself -- use "
+                      "the cardinality set behind the transform, which counts coefficients")
+CARDG_NO_MINKOWSKI = "group cardinality (card_groups) takes no Minkowski component: constrain the sum of the components"
+CARDG_NO_VECTORS = ("group cardinality (card_groups) takes one k for the whole array and no lb / ub / weights: a segment is kept "
+                    "or dropped whole -- for weights per segment use the l21_groups set")
+CARDG_NO_SET_DATA = ("group cardinality (card_groups) holds no vectors to replace: k is fixed when the set is added -- build a "
+                     "new context for another k")
+CARDG_SHARDED = ("group cardinality (card_groups) takes single-process contexts only, this one has a communicator, a slab "
+                 "decomposition or set ownership: its segments compete for k places across the whole array -- use a "
+                 "single process")
+CARDG_BAD_K = ("group cardinality (card_groups) needs an integer k >= 1, the number of fibers or slices kept (k = 0 is the "
+               "zero array: use bounds)")
+CARDG_K_INEXACT = ("group cardinality (card_groups): a k below the number of segments must be exactly representable in the "
+                   "working precision, since the search reads k from it -- Float32: k <= 2^24; use Float64")
+CARDG_TOO_LARGE = "group cardinality (card_groups): the grid needs fewer than 2^31 points -- split the array"
+CARDG_NO_COARSE = ("multilevel: group cardinality (card_groups) has no rule that takes k to a grid with another number of segments -- "
+                   "solve on one level")
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
 TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
 TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
@@ -456,6 +482,8 @@ class Projector:
             return
         if getattr(constraint, "weights", None) is not None and st == "simplex":
             raise SipxError(SIMPLEX_NO_WEIGHTS)
+        if getattr(constraint, "weights", None) is not None and st == "card_groups":
+            raise SipxError(CARDG_NO_VECTORS)
         if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint", "l21_groups", "l1_weighted"):
             raise SipxError(f"set type {st!r} takes no weights: " + L21_WEIGHTS_WHERE)
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
@@ -506,6 +534,32 @@ class Projector:
             if not (lo >= 0 and lo <= hi and hi > 0 and np.isfinite(hi)):
                 raise SipxError(SIMPLEX_BAD_BOUNDS)
             self.kind, self.pmin, self.pmax, self.op = "simplex", float(constraint.min), float(constraint.max), constraint.TD_OP
+            return
+        if st == "card_groups":
+            # at most k = max non-zero fibers / slices of the range of a one-block operator (csrc/card_groups.h); min is ignored
+            cust = constraint.custom_TD_OP[0]
+            if not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+                raise SipxError(CARDG_ONE_BLOCK)
+            if constraint.TD_OP in SPECIAL_OPERATORS:
+                raise SipxError(CARDG_NO_TRANSFORM)
+            if constraint.TD_OP not in ONE_BLOCK_OPERATORS:
+                raise SipxError(CARDG_ONE_BLOCK)
+            if constraint.TD_OP == "D_y" and len(n) == 2:
+                raise SipxError(UNKNOWN_OPERATOR)
+            if not self.mode:
+                raise SipxError(CARDG_NEEDS_MODE)
+            if len(n) == 2 and self.mode == MODES["slice"]:
+                raise SipxError(CARDG_2D_SLICE)
+            if np.ndim(constraint.max) != 0:
+                raise SipxError(CARDG_NO_VECTORS)
+            if int(np.prod(n)) >= 2 ** 31:
+                raise SipxError(CARDG_TOO_LARGE)
+            k = constraint.max
+            if isinstance(k, (bool, np.bool_)) or not np.isfinite(float(k)) or float(k) != np.floor(float(k)) or float(k) < 1:
+                raise SipxError(CARDG_BAD_K)
+            self.kind, self.pmax, self.op = "card_groups", float(k), constraint.TD_OP
+            if self.pmax < self.nseg(TDOperator(constraint.TD_OP, comp_grid, self.TF)) and float(self.TF(self.pmax)) != self.pmax:
+                raise SipxError(CARDG_K_INEXACT)
             return
         if st == "l21_groups":
             # group sparsity: one l2,1 ball whose groups are the fibers / slices of the range of a one-block operator (csrc/l21_groups.h);
@@ -752,6 +806,11 @@ class Projector:
                 raise SipxError(L21G_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
             if getattr(op, "component", 0):
                 raise SipxError(L21G_NO_MINKOWSKI)
+        if self.kind == "card_groups":
+            if op.kind != self.op:
+                raise SipxError(CARDG_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
+            if getattr(op, "component", 0):
+                raise SipxError(CARDG_NO_MINKOWSKI)
         if self.kind == "simplex":
             if op.kind != self.op:
                 raise SipxError(SIMPLEX_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
@@ -827,13 +886,13 @@ class Projector:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
                                                                               "subspace", "l21", "l21_joint", "l21_groups", "tnv", "l1_weighted",
-                                                                              "simplex")
-        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex")
+                                                                              "simplex", "card_groups")
+        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups")
         if l21:                      # the M-vector of the TV range (l21_groups: of its operator's) in the reference's row order, on the grid
             op = TDOperator(self.op, self.comp_grid, self.TF)
             rows = op.shape[0]
             if v.shape != (rows,):
-                what = {"l1_weighted": "weighted l1 ball", "simplex": "simplex set"}.get(self.kind, "l2,1 ball")
+                what = {"l1_weighted": "weighted l1 ball", "simplex": "simplex set", "card_groups": "group cardinality set"}.get(self.kind, "l2,1 ball")
                 raise SipxError(f"the {what} projects a vector of the {self.op} range: {rows} entries on this grid, {v.size} given")
             self.check_rows(op)
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
@@ -921,7 +980,13 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
     ("simplex", op, min, max, ("fiber", d) / ("slice", d)) on the identity, D_x, D_y or D_z makes every fiber / slice of the array of shape
     TD_n nonnegative with a sum in [min, max] (csrc/seg_simplex.h): min = max = 1 is the probability simplex of material fractions and
     class probabilities along the frame axis, min = 0 the capped one; one pair of scalars for all segments.  segment_sums() observes the
-    sums."""
+    sums.
+
+    ("card_groups", op, 0, k, ("fiber", d) / ("slice", d)) on the identity, D_x, D_y or D_z is group cardinality (csrc/card_groups.h): at
+    most k fibers / slices of the array of shape TD_n are non-zero -- "at most k traces change" on D_z per fiber z, "at most k frames are
+    active" on the identity per slice z.  The non-convex counterpart of l21_groups (ncvx is set, as for cardinality and rank): the k
+    segments of largest l2 norm stay as they are, ties to the lower segment index, the others become zero.  k is an integer >= 1; min is
+    ignored.  group_norms() observes the norms it selects on."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -930,6 +995,8 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.min, c.max = [np.asarray(a, TF) if np.ndim(a) else (TF(a) if isinstance(a, (float, np.floating)) else a) for a in (c.min, c.max)]
         elif c.set_type == "l21" and np.ndim(c.max):
             pass                                       # (radii per frame: converted below)
+        elif c.set_type == "card_groups":
+            pass                                       # (max is k, a count: Projector must see it unrounded to refuse one that TF cannot hold)
         elif np.ndim(c.min) == 0:
             if isinstance(c.min, (float, np.floating)):
                 c.min, c.max = TF(c.min), TF(c.max)
@@ -939,7 +1006,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.max = np.asarray(c.max, TF)
         if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
             c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
-        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex"):
+        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -965,7 +1032,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
         prop.AtA_diag.append(AtA_diag); prop.dense.append(dense); prop.TD_n.append(TD_n)
         prop.banded.append(banded); prop.AtA_offsets.append(None)
         prop.tag.append((c.set_type, c.TD_OP, c.app_mode[0], c.app_mode[1]))
-        if c.set_type in ("rank", "cardinality"):
+        if c.set_type in ("rank", "cardinality", "card_groups"):
             ncvx = True
         elif c.set_type in ("bounds", "histogram") and c.TD_OP != "identity" and TF(np.max(c.min)) > TF(0):
             ncvx = True
@@ -1824,6 +1891,8 @@ class Solver:
             raise SipxError(f"set_data: index {i} is the distance term, which holds no vectors (its data is m)")
         if not 0 <= i < pp:
             raise SipxError(f"set_data: set index {i} out of range ({pp} sets)")
+        if self.P_sub[i].kind == "card_groups":
+            raise SipxError("set_data: " + CARDG_NO_SET_DATA)
         want = self.P_sub[i].data_len(self.TD_OP[i])
         if want is None:
             raise SipxError(f"set_data: set {i} ({self.set_Prop.tag[i][0]} on {self.set_Prop.tag[i][1]}) holds no replaceable vectors -- "
@@ -2038,6 +2107,27 @@ def segment_sums(x, comp_grid, TD_OP: str, app_mode):
     if TF not in (np.float32, np.float64):
         raise SipxError("segment_sums: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
     return _segment_observe(x, comp_grid, TD_OP, am, TF, on_dev, "simplex", "sipx_segment_sums", ())
+
+
+def group_norms(x, comp_grid, TD_OP: str, app_mode):
+    """The l2 norm of every fiber / slice of A x: nseg numbers g of the working precision (that of x) in the order of segment_norms(),
+    arguments as there.  Computed by the norms launch of the ("card_groups", TD_OP, app_mode) projector (sipx_group_norms,
+    csrc/card_groups.h): the very array it selects on -- it keeps the first k segments of the stable descending order of g (ties to the
+    lower index), so k can be picked from the sorted values.  The count the projector compares with k is count_nonzero(group_norms):
+    at most k non-zero norms and it writes nothing.  Fibers: the bits of segment_norms(..., "l2"); slices: chunked compensated sums,
+    within one unit in the last place of the exactly summed norm.  x: a numpy vector or a 1-D torch tensor on a GPU."""
+    if TD_OP in SPECIAL_OPERATORS:
+        raise SipxError(CARDG_NO_TRANSFORM)
+    if TD_OP not in ONE_BLOCK_OPERATORS:
+        raise SipxError(CARDG_ONE_BLOCK)
+    am = tuple(app_mode)
+    if len(am) != 2 or am[0] not in ("fiber", "slice"):
+        raise SipxError(CARDG_NEEDS_MODE)
+    on_dev = _is_tensor(x)
+    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("group_norms: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    return _segment_observe(x, comp_grid, TD_OP, am, TF, on_dev, "card_groups", "sipx_group_norms", ())
 
 
 def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after, weights=None, groups=0, no_weights=()):

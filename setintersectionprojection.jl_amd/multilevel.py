@@ -32,6 +32,8 @@ def constraint2coarse(constraint, comp_grid, cf):
             raise host.SipxError(host.L1W_NO_COARSE)
         if c.set_type == "simplex":
             raise host.SipxError(host.SIMPLEX_NO_COARSE)
+        if c.set_type == "card_groups":
+            raise host.SipxError(host.CARDG_NO_COARSE)
         if getattr(c, "weights", None) is not None:
             raise host.SipxError(host.L21_WEIGHTS_NO_COARSE)
         if c.set_type == "rank":
