@@ -215,7 +215,29 @@ enum {
                                 refuses).  sipx_project takes the M-vector of the operator's range in the reference's row order;
                                 sipx_group_norms observes g.  sipx_kernel_stats_json reports "card_groups": {calls, small,
                                 search, nseg}: projections since the reset, the selections run by either route (a projection with
-                                k >= nseg runs none), the segments */
+                                k >= nseg runs none), the segments */,
+  SIPX_PROJ_L20 = 21 /* the l2,0 set on total variation, L0 gradient smoothing (no counterpart in the reference): { v = TV x : at most k
+                        grid points p have a non-zero gradient vector v_p }, the group of p being that of SIPX_PROJ_L21 (the forward
+                        differences that start at p); the non-convex counterpart of SIPX_PROJ_L21, set ncvx = 1.  op: TV (mode WHOLE) or
+                        TV_XY (mode WHOLE: one budget over the N grid points; mode SLICE with dir = 2: every z-slice has its own budget
+                        over its n1 n2 pixels), transform NONE, no component, no custom operator.  pmax = k, an integer >= 1 that, where
+                        it is below the number of groups, is exactly representable in TF (Float32: k <= 2^24); per frame ub may hold
+                        TF[n3] such integers instead (pmax ignored), which sipx_set_data replaces; pmin is ignored, lb = NULL,
+                        reserved = 0.  g_p = the group norm SIPX_PROJ_L21 forms, bit for bit; #{g_p > 0} <= k (per frame: in that frame),
+                        k >= the number of groups included: nothing is written, -0.0 included, and with one k >= the number of groups
+                        not one kernel is launched; otherwise the k first groups of the stable descending order of g (magnitude
+                        descending, ties to the lower point index, per frame the in-frame pixel index) are neither read again nor
+                        written, and every member of the others is written +0.  Pads of the layout are neither read nor written; no
+                        floating-point atomics: two calls give the same bits (csrc/l20.h).  Other operators and modes, transforms,
+                        components, weights, a vector k off the per-frame form, and contexts with a communicator, a slab decomposition
+                        or set ownership are refused, each with a text that names the way out.  sipx_project takes the M-vector of the
+                        operator's range in the reference's row order; sipx_tv_group_norms observes g.  sipx_kernel_stats_json reports
+                        "l20": {calls, small, search, frames, groups}: projections since the reset, the selections run by the two routes
+                        of SIPX_PROJ_CARD_GROUPS and by the per-frame kernel, the groups of the last such set */,
+  SIPX_PROJ_L20_JOINT = 22 /* the joint l2,0 set: { v = TV_xy x : at most k pixels (i, j) carry a non-zero gradient in any frame }, the
+                              group of a pixel being that of SIPX_PROJ_L21_JOINT -- one common edge set for all frames; set ncvx = 1.
+                              op TV_XY, mode WHOLE only.  pmax = k as above with n1 n2 groups; g from the z-march of
+                              SIPX_PROJ_L21_JOINT, bit for bit; ties to the lower pixel index; the rest as SIPX_PROJ_L20 */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -487,6 +509,14 @@ int sipx_group_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x
  * built from now on in this process.  0: by the number of segments (the default), 1: the one-workgroup rank count (refused for more than
  * CARDG_SMALL_MAX segments), 2: the engine's cardinality search.  Both routes give the same bits. */
 int sipx_card_groups_route(int route);
+/* The norms of the gradient groups of A x as SIPX_PROJ_L20 (joint = 0) or SIPX_PROJ_L20_JOINT (joint != 0) selects on them: out[p] = g_p,
+ * TF[*ngroups]; op TV or TV_XY (joint: TV_XY); ngroups = N in point order, joint: n1 n2 in pixel order (the per-frame set selects on the
+ * same N numbers as the whole-array set, frame by frame); x TF[N]; x = out = NULL asks for *ngroups alone.  Formed by the norms launch of
+ * that projector (csrc/l20.h), which is the one of SIPX_PROJ_L21 / SIPX_PROJ_L21_JOINT.  CONTRACT: the array is the selection key itself:
+ * the projector keeps the first k groups of its stable descending order, and the count it compares with k is the number of non-zero
+ * entries of out.  The _dev form takes device pointers, ordered against the caller's stream.  Refused where the set is refused. */
+int sipx_tv_group_norms(sipx_ctx* ctx, int op, int joint, const void* x, void* out, int64_t* ngroups);
+int sipx_tv_group_norms_dev(sipx_ctx* ctx, int op, int joint, const void* x, void* out, int64_t* ngroups);
 /* The isotropic total variation of x: *out = ||TV x||_2,1 as one TF, x TF[N] on the 2-D or 3-D grid of the context (which needs no sets
  * and no finalize).  TV x comes from the engine's operator product into scratch of the call; the group norms are formed by the kernel of
  * SIPX_PROJ_L21 and summed by the first pass of its threshold search.  CONTRACT: the value is the very number the projector compares

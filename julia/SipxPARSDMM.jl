@@ -74,6 +74,9 @@ const SIPX_PROJ_SIMPLEX = 19
 # set_type = "card_groups", max = k, min ignored.  Not a set of the reference; its setup_constraints leaves ncvx false for an unknown
 # tag, so set set_Prop.ncvx[i] = true for such a set, as for cardinality and rank.
 const SIPX_PROJ_CARD_GROUPS = 20
+# the l2,0 sets on the gradient groups of TV / TV_xy (include/sipx.h, csrc/l20.h), set_type = "l20" and "l20_joint", max = k
+const SIPX_PROJ_L20 = 21
+const SIPX_PROJ_L20_JOINT = 22
 const MODE = Dict("matrix" => 0, "tensor" => 0, "fiber" => 1, "slice" => 2)
 const SPECIAL = ("DFT", "DCT", "wavelet", "curvelet")          # src/setup_constraints.jl:54
 # the seven @timeit sections of src/PARSDMM.jl:40,100,105,113,152,163,229
@@ -167,6 +170,28 @@ function projector_fields(c, TF)
         (c.max isa Real && isfinite(c.max) && c.max >= 1 && c.max == floor(c.max)) ||
             error("group cardinality (card_groups) needs an integer k >= 1, the number of fibers or slices kept (k = 0 is the zero array: use bounds)")
         return (SIPX_PROJ_CARD_GROUPS, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
+    # the l2,0 sets on total variation, L0 gradient smoothing: at most k grid points (l20) or pixels in any frame (l20_joint) carry a
+    # gradient vector (include/sipx.h, SIPX_PROJ_L20 / SIPX_PROJ_L20_JOINT, csrc/l20.h; not sets of the reference).  max = k, min ignored;
+    # per frame -- ("slice", "z") on TV_xy -- max may be a vector of n3 budgets, which travels in ub.  As for "l21_joint", TV_xy reaches
+    # libsipx only from a caller that assembles the descriptor list itself.  Set set_Prop.ncvx[i] = true, as for cardinality and rank.
+    if st == "l20"
+        op in ("TV", "D2D", "D3D", "TV_xy") && c.custom_TD_OP[1] == [] ||
+            error("the l2,0 set (l20) counts the gradient vectors of the TV operator: TD_OP must be TV (D2D, D3D) or TV_xy, not a one-block or custom operator (there use the cardinality set, which counts entries, or card_groups)")
+        c.app_mode[1] in ("matrix", "tensor") || (op == "TV_xy" && c.app_mode == ("slice", "z")) ||
+            error("the l2,0 set (l20) applies to the whole array (matrix / tensor mode), or per frame as (\"slice\", \"z\") on TV_xy: fiber modes and other slices have no gradient groups -- use card_groups on D_x, D_y or D_z there")
+        ks = c.max isa AbstractVector ? c.max : [c.max]
+        (c.max isa AbstractVector ? c.app_mode[1] == "slice" : true) && all(k -> k isa Real && isfinite(k) && k >= 1 && k == floor(k), ks) ||
+            error("the l2,0 set (l20, l20_joint) needs an integer k >= 1, the number of grid points that may carry a gradient (k = 0 is the constant array: use bounds on TV)")
+        c.max isa AbstractVector && return (SIPX_PROJ_L20, 0.0, Float64(maximum(ks)), nothing, convert(Vector{TF}, c.max), Int32(0))
+        return (SIPX_PROJ_L20, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
+    if st == "l20_joint"
+        op == "TV_xy" && c.custom_TD_OP[1] == [] && c.app_mode[1] in ("matrix", "tensor") ||
+            error("the joint l2,0 set (l20_joint) needs the TV_xy operator of a 3-D grid in tensor mode: its groups span the frames -- for one budget over all grid points use (\"l20\", \"TV_xy\"), per frame (\"l20\", \"TV_xy\", (\"slice\", \"z\"))")
+        (c.max isa Real && isfinite(c.max) && c.max >= 1 && c.max == floor(c.max)) ||
+            error("the l2,0 set (l20, l20_joint) needs an integer k >= 1, the number of grid points that may carry a gradient (k = 0 is the constant array: use bounds on TV)")
+        return (SIPX_PROJ_L20_JOINT, 0.0, Float64(c.max), nothing_[3:5]...)
     end
     st == "simplex" && error("simplex sets (simplex, SIPX_PROJ_SIMPLEX) are not built in this binding yet: use (\"bounds\") together with (\"l1\", op, mode) and segment_norms=true, or the C ABI")
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)

@@ -152,6 +152,12 @@ int sipx_group_norms(sipx_ctx* c, int op, int mode, int dir, const void* x, void
 int sipx_group_norms_dev(sipx_ctx* c, int op, int mode, int dir, const void* x, void* out, int64_t* nseg) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->group_norms(op, mode, dir, x, out, nseg, true))
 }
+int sipx_tv_group_norms(sipx_ctx* c, int op, int joint, const void* x, void* out, int64_t* ngroups) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->tv_group_norms(op, joint != 0, x, out, ngroups, false))
+}
+int sipx_tv_group_norms_dev(sipx_ctx* c, int op, int joint, const void* x, void* out, int64_t* ngroups) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->tv_group_norms(op, joint != 0, x, out, ngroups, true))
+}
 int sipx_l21_norm(sipx_ctx* c, const void* x, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21, SIPX_OP_TV, SIPX_MODE_WHOLE, 0, x, out, nullptr, false, false))
 }

@@ -389,6 +389,7 @@ class Engine : public EngineBase {
       if (s.ext_kind == EXT_L1_WEIGHTED) refuse_sharded(ctx, Sharded::L1_WEIGHTED);
       if (s.ext_kind == EXT_SIMPLEX_SEG) refuse_sharded(ctx, Sharded::SIMPLEX);
       if (s.ext_kind == EXT_CARD_GROUPS) refuse_sharded(ctx, Sharded::CARD_GROUPS);
+      if (s.ext_kind == EXT_L20 || s.ext_kind == EXT_L20_SEG || s.ext_kind == EXT_L20_JOINT) refuse_sharded(ctx, Sharded::L20);
     }
     FinalizePlan P;
     plan_sets();
@@ -2940,6 +2941,9 @@ class Engine : public EngineBase {
     SetState<T>& s = sets_[set];
     if (s.comp) throw std::runtime_error(what + " is not available for Minkowski sets" + way_out);
     if (s.ext_kind == EXT_CARD_GROUPS) throw std::runtime_error(what + ": " + CARDG_NO_SET_DATA);
+    if (s.ext_kind == EXT_L20 || s.ext_kind == EXT_L20_JOINT || (s.ext_kind == EXT_L20_SEG && !s.seg_radii))
+      throw std::runtime_error(what + ": " + L20_NO_SET_DATA);
+    if (s.ext_kind == EXT_L20_SEG && lb) throw std::runtime_error(what + ": " + L20_SET_DATA_UB);
     const bool bounds = !s.ext_kind && s.prox == SIPX_PROJ_BOUNDS_VEC, hist = s.ext_kind == EXT_HISTOGRAM || s.seg_radii || s.weighted;
     if (!bounds && !hist)
       throw std::runtime_error(what + ": set " + std::to_string(set) + " holds no replaceable vectors -- element-wise and per-fiber bounds "
@@ -2956,6 +2960,7 @@ class Engine : public EngineBase {
     if (s.ext_kind == EXT_L1_WEIGHTED && lb && !on_device) check_l1w_weights((const T*)lb, len);
     else if (s.weighted && lb && !on_device) check_l21_weights((const T*)lb, len, s.ext_kind == EXT_L21_JOINT ? "l21_joint" : (s.ext_kind == EXT_L21_GROUPS ? "l21_groups" : "l21"));
     if (s.seg_radii && (s.ext_kind == EXT_L1_SEG || s.ext_kind == EXT_L21_SEG) && ub && !on_device) check_l1_radii((const T*)ub, len);
+    if (s.ext_kind == EXT_L20_SEG && ub && !on_device) l20_check_k_vector<T>((const T*)ub, len, G_.n[0] * G_.n[1]);
     if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
       throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
     if (!lb && !ub) return;
@@ -3511,6 +3516,70 @@ class Engine : public EngineBase {
     }
   }
 
+  // SIPX_PROJ_L20 / SIPX_PROJ_L20_JOINT of sipx_project: the M-vector of the TV / TV_xy range in the reference's row order
+  void project_l20(const sipx_set_desc* d, void* v, int64_t len) {
+    if (d->proj == SIPX_PROJ_L20_JOINT && d->op != SIPX_OP_TV_XY) throw std::runtime_error(L20_JOINT_ROUTE);
+    if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY) throw std::runtime_error(L20_NEEDS_TV);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> st;
+    configure_op(ctx, st, d->op);
+    if (d->op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
+    configure_proj(ctx, st, d);
+    if (len != st.Mtrue)
+      throw std::runtime_error(std::string("the l2,0 set projects a vector of the ") + (d->op == SIPX_OP_TV ? "TV" : "TV_xy") + " range: " +
+                               std::to_string(st.Mtrue) + " entries on this grid, " + std::to_string((long long)len) + " given");
+    st.spec.ub = st.host_ub.empty() ? nullptr : st.host_ub.data();      // (per frame: one budget each)
+    DeviceMemory tmp;
+    T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
+    const SearchScratch q(tmp, G_.N, false);
+    upload_rows(st, (const T*)v, dv);
+    {
+      ExtProj<T> ext(st.spec, stream_);
+      ext.project(dv, false, q.part, q.mp, q.dc);
+      long long c[4];                            // the route of a stand-alone call counts like a set's (l20 row of sipx_kernel_stats)
+      ext.route_counts(c);
+      l20_count(st.ext_kind, c, project_l20c_);
+      download_rows(st, dv, (T*)v);               // (synchronises the stream)
+    }
+  }
+  // the l20 row of sipx_kernel_stats from a projector's route_counts: calls, small, search, frames, groups
+  static void l20_count(int ext_kind, const long long c[4], long long row[5]) {
+    row[0] += c[0];
+    if (ext_kind == EXT_L20_SEG) row[3] += c[2];
+    else { row[1] += c[1]; row[2] += c[2]; }
+    row[4] = c[3];
+  }
+
+  // sipx_tv_group_norms(_dev): the norm of every gradient group of A x -- N entries in point order, joint: n1 n2 in pixel order -- by the
+  // observe() of a throw-away projector of the l20 / l20_joint set on op: its own norms launch (l20.h)
+  void tv_group_norms(int op, bool joint, const void* x, void* out, int64_t* ngroups, bool on_device) override {
+    SIPX_HIP(hipSetDevice(device_));
+    if (joint && op != SIPX_OP_TV_XY) throw std::runtime_error(L20_JOINT_ROUTE);
+    if (op != SIPX_OP_TV && op != SIPX_OP_TV_XY) throw std::runtime_error(L20_NEEDS_TV);
+    const ConfigCtx ctx = config_ctx();
+    SetConfig<T> s;
+    configure_op(ctx, s, op);
+    if (op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
+    sipx_set_desc d{};
+    d.op = op; d.proj = joint ? SIPX_PROJ_L20_JOINT : SIPX_PROJ_L20; d.mode = SIPX_MODE_WHOLE; d.pmax = 1.0;
+    configure_proj(ctx, s, &d);                // the refusals, and the ExtSpec, of the set
+    const long long ng = joint ? G_.st[2] : G_.N;
+    if (ngroups) *ngroups = ng;
+    if (!x && !out) return;                    // (a query of the length)
+    if (!x || !out) throw std::runtime_error("sipx_tv_group_norms: x and out are needed");
+    DeviceMemory tmp;
+    const OpScratch w = forward_scratch(tmp, s, on_device);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(ng);
+    ExtProj<T> ext(s.spec, stream_);
+    const T* dv = queue_forward(w, s, x, on_device);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 1) * G_.N * sizeof(T));
+      ext.observe(dv, dout, nullptr, nullptr, nullptr);
+    }
+    finish_call(on_device, out, dout, ng);
+  }
+
   // sipx_group_norms(_dev): the l2 norm of every fiber / slice of A x, in the order of sipx_segment_norms, by the observe() of a throw-away
   // projector of the card_groups set on (op, mode, dir): its own norms launch (card_groups.h)
   void group_norms(int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device) override {
@@ -3613,6 +3682,10 @@ class Engine : public EngineBase {
     }
     if (d->proj == SIPX_PROJ_CARD_GROUPS) {
       project_card_groups(d, v, len);
+      return;
+    }
+    if (d->proj == SIPX_PROJ_L20 || d->proj == SIPX_PROJ_L20_JOINT) {
+      project_l20(d, v, len);
       return;
     }
     Grid g1;
@@ -3891,7 +3964,19 @@ class Engine : public EngineBase {
       cg[3] = c[3];
     }
     o += ", \"card_groups\": {\"calls\": " + std::to_string(cg[0]) + ", \"small\": " + std::to_string(cg[1]) + ", \"search\": " +
-         std::to_string(cg[2]) + ", \"nseg\": " + std::to_string(cg[3]) + "}}";
+         std::to_string(cg[2]) + ", \"nseg\": " + std::to_string(cg[3]) + "}";
+    // l20 / l20_joint sets: the projections since the reset, the selections run by the small route, by the search route and by the
+    // per-frame kernel -- a projection whose k keeps every group runs none -- (summed over such sets and the stand-alone projections of
+    // this context), the groups of the last one (per frame: of a frame)
+    long long l0c[5] = {project_l20c_[0], project_l20c_[1], project_l20c_[2], project_l20c_[3], project_l20c_[4]};
+    for (const auto& st : sets_) {
+      if (!st.ext || (st.ext_kind != EXT_L20 && st.ext_kind != EXT_L20_SEG && st.ext_kind != EXT_L20_JOINT)) continue;
+      long long c[4];
+      st.ext->route_counts(c);
+      l20_count(st.ext_kind, c, l0c);
+    }
+    o += ", \"l20\": {\"calls\": " + std::to_string(l0c[0]) + ", \"small\": " + std::to_string(l0c[1]) + ", \"search\": " +
+         std::to_string(l0c[2]) + ", \"frames\": " + std::to_string(l0c[3]) + ", \"groups\": " + std::to_string(l0c[4]) + "}}";
     if (!peek) start_stats(enable);
     return o.c_str();
   }
@@ -4623,6 +4708,7 @@ class Engine : public EngineBase {
   long long routes_[RT_COUNT] = {};     // launches per route since finalize (RouteId; obs_route)
   long long project_rc_[4] = {0, 0, 0, 0};   // route counters of the rank projectors that project() built and dropped
   long long project_sc_[4] = {0, 0, 0, 0};   // ... and of the simplex projectors (calls, lane route, tile route; the segments of the last)
+  long long project_l20c_[5] = {0, 0, 0, 0, 0};   // ... and of the l20 projectors (calls, small route, search route, per-frame kernel; the groups of the last)
   long long project_gc_[4] = {0, 0, 0, 0};   // ... and of the card_groups projectors (calls, small route, search route; the segments of the last)
   T* fbuf_ = nullptr;                 // fast segments: world x two-pass sets x (fcap + header)
   bool yl_multi_ = true;              // SIPX_YL_MULTI=0: never take the one-sweep y/l update (A/B switch)

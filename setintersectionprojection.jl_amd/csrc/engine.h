@@ -53,6 +53,8 @@ struct EngineBase {
   virtual void segment_sums(int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device) = 0;
   // sipx_group_norms(_dev): the segment norms a card_groups set selects on
   virtual void group_norms(int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device) = 0;
+  // sipx_tv_group_norms(_dev): the norms of the gradient groups an l20 / l20_joint set selects on
+  virtual void tv_group_norms(int op, bool joint, const void* x, void* out, int64_t* ngroups, bool on_device) = 0;
   // the six sipx_l21_*norm* calls and sipx_tnv_norm(_dev): proj SIPX_PROJ_L21, SIPX_PROJ_L21_JOINT or SIPX_PROJ_TNV; query: x and out both null ask for *nseg alone
   virtual void l21_norms(int proj, int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device, bool query) = 0;
   virtual void l21_weighted_norm(int op, bool joint, const void* x, const void* w, void* out, bool on_device) = 0;

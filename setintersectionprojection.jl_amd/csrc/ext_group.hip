@@ -19,6 +19,9 @@
 // Group cardinality on the same fibers or slices (EXT_CARD_GROUPS, card_groups.h, CardGroupsProj) shares that norms launch (GroupNorms) and
 // the coordinate -> segment arithmetic of the scale kernel; it selects by rank counting in one workgroup (k_cardg_rank) or by the engine's
 // cardinality search, and its apply kernel (k_cardg_zero) only stores.
+// The l2,0 sets on the groups of the TV / TV_xy operator (EXT_L20, EXT_L20_SEG, EXT_L20_JOINT, l20.h, L20Proj and L20FrameProj) take the norms
+// launch of the l2,1 balls as their key, the selection of group cardinality (CardgSelect, which CardGroupsProj holds too) or, per frame, a
+// radix select in one workgroup per frame (k_l20_frames), and a store-only apply across the blocks (k_l20_zero).
 // Total nuclear variation (EXT_TNV, tnv.h, TnvProj) has the groups and the z-march of the joint ball, two numbers per pixel in the search
 // and a 2 x 2 matrix per pixel in place of the weight.
 // The weighted l1 ball on the rows of an operator (EXT_L1_WEIGHTED, l1_weighted.h, L1WProj) is the weighted iteration once more, on the pairs
@@ -33,6 +36,7 @@
 #include "l21_seg.h"
 #include "l21_groups.h"
 #include "card_groups.h"
+#include "l20.h"
 #include "l21_weighted.h"
 #include "l1_weighted.h"
 #include "tnv.h"
@@ -720,6 +724,211 @@ __global__ __launch_bounds__(BLOCK) void k_cardg_zero(L21GArgs a, T* __restrict_
   }
 }
 
+// ---- EXT_L20, EXT_L20_SEG, EXT_L20_JOINT: at most k grid points (pixels) with a non-zero gradient vector (l20.h) ------------------------------
+//     the norms launch of the l2,1 ball on the same operator (l21_norms)   g[p], or g[pixel] for the joint set
+//     CardgSelect on g, or k_l20_frames per frame                          (need, tau, cut), one triple or one per frame
+//     k_l20_zero                                                           reads N words of g (joint: L, which stay in cache), writes <= nblk N
+// The loop of k_l21_scale: grid-stride over the N points, VW points of one grid line per thread, l21_members for the pads.  v is never
+// loaded: the members of a dropped group are stored as +0 -- one 16-byte store per block where all VW points are members and dropped,
+// scalar stores otherwise -- and a kept group, a pad, a frame without need, or anything at all when the selection found nothing to drop, is
+// not touched.  The group index the rule compares with the cut: the point index p, the in-frame pixel index (FRAMES) or the pixel index
+// (JOINT), both p - k L.  32-bit index arithmetic, no LDS, no atomics.
+template <typename T, int NBLK, int VW, bool FRAMES, bool JOINT>
+__global__ __launch_bounds__(BLOCK) void k_l20_zero(L21Args a, T* __restrict__ v, const T* __restrict__ g, const ProjScalars<T>* __restrict__ ps,
+                                                    const int* __restrict__ need, const T* __restrict__ ftau, const int* __restrict__ fcut) {
+  T tau = T(0);
+  long long cut = 0;
+  if constexpr (!FRAMES) {
+    if (!ps->need) return;
+    tau = ps->tau;
+    cut = ps->quota;
+  }
+  const unsigned nvec = (unsigned)(a.G.N / VW), step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    const Coord c = coords(a.G, (long long)p);
+    if constexpr (FRAMES) {
+      if (!need[c.k]) continue;
+      tau = ftau[c.k];
+      cut = (long long)fcut[c.k];
+    }
+    const unsigned px = (FRAMES || JOINT) ? p - (unsigned)c.k * (unsigned)a.G.st[2] : p;
+    const Vec<T, VW> gv = ldv<T, VW>(g + (JOINT ? px : p));
+    bool drop[VW], any = false;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      drop[k] = !cardg_keeps<T>(gv.v[k], (long long)(px + (unsigned)k), tau, cut);
+      any = any || drop[k];
+    }
+    if (!any) continue;
+#pragma unroll
+    for (int q = 0; q < NBLK; ++q) {
+      bool mem[VW];
+      l21_members<VW>(a, c, q, mem);
+      T* vq = v + (size_t)q * (size_t)a.bstride + p;
+      bool all = true;
+#pragma unroll
+      for (int k = 0; k < VW; ++k) all = all && mem[k] && drop[k];
+      if (all) {
+        Vec<T, VW> z;
+#pragma unroll
+        for (int k = 0; k < VW; ++k) z.v[k] = T(0);
+        stv<T, VW>(vq, z);
+      } else {            // a kept neighbour, or the far face along dir[q]: rows the block does not have are not written
+#pragma unroll
+        for (int k = 0; k < VW; ++k)
+          if (mem[k] && drop[k]) vq[k] = T(0);
+      }
+    }
+  }
+}
+
+// The per-frame selection (l20.h, l20_frame_select): one workgroup per frame, grid-stride over the frames, on g alone (frame f at g + f L).
+// The plan of k_l21_frames: the frame's L keys are staged in LDS when they fit seg_norm.h's budget, otherwise every pass re-reads them.
+//   1. the count of the keys > 0; at most k of them (k >= L included, then without a read): need = 0
+//   2. radix select on the bit pattern, 8 bits a pass, a 256-bin histogram in LDS: tau = the k-th largest key, kk = how many keys equal
+//      to it stay.  The bins are LDS atomics (integer: the counts do not depend on the order).  Keys of one frame share their high bytes,
+//      so the first passes would send a whole wave to one bin; one round of aggregation takes that out: the lanes that share the bin of
+//      the wave's first live lane add once, through that lane, the others add one each.
+//   3. cut = the in-frame index of the kk-th key equal to tau.  Where all the keys equal to tau stay (no tie across the k-th place) that
+//      is the last of them: one more streamed pass and a max-reduction.  Otherwise one ordered pass, BLOCK keys a step, with wave
+//      ballots -- a chain of L / BLOCK dependent loads and barriers, which only an input with ties across the cut pays.
+// A budget from device memory that is not >= 1 (every host path refuses it) keeps no group: tau = +inf.  Nothing is kept between calls.
+template <typename T> struct L20Bits;
+template <> struct L20Bits<float> {
+  using U = unsigned int;
+  static __device__ __forceinline__ U of(float x) { return __float_as_uint(x); }
+  static __device__ __forceinline__ float back(U u) { return __uint_as_float(u); }
+};
+template <> struct L20Bits<double> {
+  using U = unsigned long long;
+  static __device__ __forceinline__ U of(double x) { return (U)__double_as_longlong(x); }
+  static __device__ __forceinline__ double back(U u) { return __longlong_as_double((long long)u); }
+};
+constexpr int L20_NO_CUT = 0x7fffffff;      // the cut of a frame where nothing is dropped
+template <typename T, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_l20_frames(L21SegPlan p, unsigned L, unsigned nframes, const T* __restrict__ g, T kall,
+                                                      const T* __restrict__ kvec, int* __restrict__ need, T* __restrict__ tau,
+                                                      int* __restrict__ cut) {
+  using B = L20Bits<T>;
+  using U = typename B::U;
+  constexpr int BITS = (int)sizeof(U) * 8;
+  static_assert(BLOCK == 256, "one histogram bin a thread, four waves");
+  extern __shared__ __align__(16) unsigned char l20_lds[];
+  __shared__ unsigned int hist[256];
+  __shared__ unsigned int s_w[BLOCK / 64];
+  __shared__ U s_prefix;
+  __shared__ unsigned int s_kk, s_neq, s_run, s_cut;
+  T* const sm = reinterpret_cast<T*>(l20_lds);
+  const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (unsigned f = blockIdx.x; f < nframes; f += gridDim.x) {
+    const T* const gf = g + (size_t)f * L;
+    const T kf = VEC ? kvec[f] : kall;
+    if (kf >= (T)L) {                  // every group of the frame stays (uniform: no thread has read anything)
+      if (tid == 0) { need[f] = 0; tau[f] = T(0); cut[f] = L20_NO_CUT; }
+      continue;
+    }
+    const unsigned k = kf >= T(1) ? (unsigned)kf : 0u;
+    unsigned nz = 0;
+    l21_seg_each<T>(gf, L, [&](unsigned t, T x) {
+      if (p.lds) sm[t] = x;
+      nz += x > T(0) ? 1u : 0u;
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nz += __shfl_down(nz, o, 64);
+    if (lane == 0) s_w[w] = nz;
+    __syncthreads();                   // (sm and s_w are complete)
+    const unsigned nnz = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    __syncthreads();
+    if (nnz <= k || k == 0) {          // uniform
+      if (tid == 0) {
+        need[f] = k == 0 && nnz > 0 ? 1 : 0;
+        tau[f] = k == 0 && nnz > 0 ? (T)INFINITY : T(0);
+        cut[f] = k == 0 && nnz > 0 ? -1 : L20_NO_CUT;
+      }
+      continue;
+    }
+    auto each = [&](auto&& fn) {       // (two calls, so that the loads keep their address space)
+      if (p.lds) l21_seg_each<T>(sm, L, fn);
+      else l21_seg_each<T>(gf, L, fn);
+    };
+    U prefix = 0, mask = 0;
+    unsigned kk = k;
+    for (int shift = BITS - 8; shift >= 0; shift -= 8) {
+      hist[tid] = 0;
+      __syncthreads();
+      each([&](unsigned, T x) {
+        const U key = B::of(x);
+        const bool act = (key & mask) == prefix;
+        const unsigned bin = (unsigned)(key >> shift) & 255u;
+        const unsigned long long live = __ballot(act);
+        if (live) {
+          const int lead = __ffsll((long long)live) - 1;
+          const unsigned lb = (unsigned)__shfl((int)bin, lead, 64);
+          const unsigned long long same = __ballot(act && bin == lb);
+          if (lane == lead) atomicAdd(&hist[lb], (unsigned)__popcll(same));
+          else if (act && bin != lb) atomicAdd(&hist[bin], 1u);
+        }
+      });
+      __syncthreads();
+      if (tid == 0) {
+        unsigned cum = 0;
+        int b = 255;
+        for (; b > 0; --b) {
+          if (cum + hist[b] >= kk) break;
+          cum += hist[b];
+        }
+        s_prefix = prefix | ((U)b << shift);
+        s_kk = kk - cum;
+        s_neq = hist[b];               // (after the last pass: the keys equal to tau)
+      }
+      __syncthreads();
+      prefix = s_prefix;
+      kk = s_kk;
+      mask |= (U)255 << shift;
+    }
+    // prefix = the bits of the k-th largest key, kk >= 1 of the s_neq keys equal to it stay: the cut is the index of the kk-th of them
+    if (kk == s_neq) {                 // uniform.  All of them stay -- no tie across the k-th place, the usual case: the cut is the last
+      unsigned last = 0;               // of them, one more streamed pass with its loads in flight and one reduction
+      each([&](unsigned t, T x) { last = (B::of(x) == prefix && t > last) ? t : last; });
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned other = (unsigned)__shfl_down((int)last, o, 64);
+        last = other > last ? other : last;
+      }
+      if (lane == 0) s_w[w] = last;
+      __syncthreads();
+      if (tid == 0) {
+        unsigned m = s_w[0];
+        for (int i = 1; i < BLOCK / 64; ++i) m = s_w[i] > m ? s_w[i] : m;
+        need[f] = 1; tau[f] = B::back(prefix); cut[f] = (int)m;
+      }
+      __syncthreads();                 // (s_w, s_neq and sm are free for the next frame)
+      continue;
+    }
+    if (tid == 0) { s_run = 0; s_cut = 0; }
+    __syncthreads();
+    for (unsigned c0 = 0; c0 < L; c0 += BLOCK) {
+      const unsigned t = c0 + (unsigned)tid;
+      const bool eq = t < L && B::of(p.lds ? sm[t] : gf[t]) == prefix;
+      const unsigned long long bal = __ballot(eq);
+      const unsigned rank = (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+      if (lane == 0) s_w[w] = (unsigned)__popcll(bal);
+      __syncthreads();
+      unsigned off = s_run;
+      for (int i = 0; i < w; ++i) off += s_w[i];
+      if (eq && off + rank + 1 == kk) s_cut = t;
+      const unsigned tot = s_run + s_w[0] + s_w[1] + s_w[2] + s_w[3];
+      __syncthreads();
+      if (tid == 0) s_run = tot;
+      __syncthreads();
+      if (tot >= kk) break;            // uniform: the cut is found
+    }
+    if (tid == 0) { need[f] = 1; tau[f] = B::back(prefix); cut[f] = (int)s_cut; }
+    __syncthreads();                   // (s_cut and sm are free for the next frame)
+  }
+}
+
 static void l21_check_spec(const ExtSpec& sp) {
   if (sp.nblk != 2 && sp.nblk != 3) throw std::runtime_error("the l2,1 ball needs the 2 or 3 blocks of the TV or TV_xy operator");
   if (sp.nblk > sp.ndim) throw std::runtime_error("the l2,1 ball: more blocks than grid dimensions");
@@ -768,7 +977,7 @@ static void l21_norms(hipStream_t s, const ExtSpec& sp, const T* v, T* g, double
   constexpr int W = l21_vec_width<T>();
   const bool wide = l21_wide(sp, v, g);
   const long long N = sp.G.N, L = sp.G.st[2];
-  if (sp.kind != EXT_L21_JOINT) {
+  if (sp.kind != EXT_L21_JOINT && sp.kind != EXT_L20_JOINT) {
     void (*const k)(L21Args, const T*, T*) = sp.nblk == 2 ? (wide ? k_l21_norms<T, 2, W> : k_l21_norms<T, 2, 1>)
                                                           : (wide ? k_l21_norms<T, 3, W> : k_l21_norms<T, 3, 1>);
     ObsScope obs(KID_L21_NORMS, s, (double)(sp.nblk + 1) * N * sizeof(T));
@@ -1272,14 +1481,43 @@ static void cardg_check_spec(const ExtSpec& sp) {
   if (sp.lb || sp.ub) throw std::runtime_error(CARDG_NO_VECTORS);
   if (sp.G.N >= (1ll << 31)) throw std::runtime_error(CARDG_TOO_LARGE);
 }
+// The selection of the k-th place of the stable descending order of n keys g, for the projectors that keep the k largest groups
+// (CardGroupsProj, L20Proj): the route, fixed when the projector is built, the search's states, the two launches.  The result is the
+// need / tau / quota of the ProjScalars run() returns (card_groups.h RULE, SELECTION).
+template <typename T>
+struct CardgSelect {
+  long long n = 0, k = 0;              // keys; places, k < n wherever run() is called
+  bool small = false;
+  SearchState<T> search;               // search route: both states; small route: ps alone holds the result
+  void build(DeviceMemory& mem, hipStream_t s, long long n_, long long k_) {
+    n = n_;
+    k = k_;
+    const int route = g_cardg_route.load(std::memory_order_relaxed);
+    if (route == 1 && n > CARDG_SMALL_MAX)
+      throw std::runtime_error("sipx_card_groups_route: the small route holds at most " + std::to_string(CARDG_SMALL_MAX) + " segments, this set has " +
+                               std::to_string(n));
+    small = route == 1 || (route == 0 && n <= CARDG_SMALL_MAX);
+    search.build(mem, s, small ? 0 : n);      // cidx: the tie cut of the search
+  }
+  void reinit(hipStream_t s) { search.reinit(s); }
+  ProjScalars<T>* run(hipStream_t stream, const T* g, bool feas, double* partials, T* maxpart, T* compact) {
+    ProjScalars<T>* ps = small ? search.ps : search.pick(feas);
+    if (small) {
+      ObsScope obs(KID_CARDG_RANK, stream, (double)n * sizeof(T));
+      hipLaunchKernelGGL((k_cardg_rank<T>), dim3(1), dim3(CARDG_SMALL_MAX), 0, stream, (int)n, (int)k, g, ps);
+    } else {
+      K<T>::proj_scalars_arr(stream, n, g, PX_CARD, T(0), (T)k, ps, partials, maxpart, compact, n);
+    }
+    return ps;
+  }
+};
 template <typename T>
 struct CardGroupsProj : ExtImpl<T> {
   using ExtImpl<T>::sp;
   using ExtImpl<T>::stream;
   GroupNorms<T> nm;
   long long n = 0, k = 0;              // segments; segments kept, clamped to n
-  bool small = false;
-  SearchState<T> search;               // search route: both states; small route: ps alone holds the result
+  CardgSelect<T> sel;
   long long calls = 0, selections = 0;      // projections since the reset; those that ran a selection (k < nseg)
   CardGroupsProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
     cardg_check_spec(sp);
@@ -1287,26 +1525,15 @@ struct CardGroupsProj : ExtImpl<T> {
     n = nm.n;
     cardg_check_k<T>(sp.pmax, n);
     k = sp.pmax >= (double)n ? n : (long long)sp.pmax;
-    const int route = g_cardg_route.load(std::memory_order_relaxed);
-    if (route == 1 && n > CARDG_SMALL_MAX)
-      throw std::runtime_error("sipx_card_groups_route: the small route holds at most " + std::to_string(CARDG_SMALL_MAX) + " segments, this set has " +
-                               std::to_string(n));
-    small = route == 1 || (route == 0 && n <= CARDG_SMALL_MAX);
-    search.build(this->mem, s, small ? 0 : n);      // cidx: the tie cut of the search
+    sel.build(this->mem, s, n, k);
   }
-  void reset() override { search.reinit(stream); calls = selections = 0; }
+  void reset() override { sel.reinit(stream); calls = selections = 0; }
   void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
     ++calls;
     if (k >= n) return;                // every segment stays: nothing to select, nothing to write
     ++selections;
     nm.run(stream, sp, v);
-    ProjScalars<T>* ps = small ? search.ps : search.pick(feas);
-    if (small) {
-      ObsScope obs(KID_CARDG_RANK, stream, (double)n * sizeof(T));
-      hipLaunchKernelGGL((k_cardg_rank<T>), dim3(1), dim3(CARDG_SMALL_MAX), 0, stream, (int)n, (int)k, nm.g, ps);
-    } else {
-      K<T>::proj_scalars_arr(stream, n, nm.g, PX_CARD, T(0), (T)k, ps, partials, maxpart, compact, n);
-    }
+    ProjScalars<T>* ps = sel.run(stream, nm.g, feas, partials, maxpart, compact);
     constexpr int W = l21_vec_width<T>();
     const bool wide = sp.G.n[0] % 4 == 0 && aligned16(v);
     ObsScope obs(KID_CARDG_ZERO, stream, (double)sp.G.N * sizeof(T), ((double)nm.map.nseg * nm.map.L + n) * sizeof(T));
@@ -1323,8 +1550,143 @@ struct CardGroupsProj : ExtImpl<T> {
   // projections since the reset, the selections the small route ran, those the search route ran (a projection with k >= nseg runs
   // none), the segments
   void route_counts(long long out[4]) const override {
-    out[0] = calls; out[1] = small ? selections : 0; out[2] = small ? 0 : selections; out[3] = n;
+    out[0] = calls; out[1] = sel.small ? selections : 0; out[2] = sel.small ? 0 : selections; out[3] = n;
   }
+};
+
+// ---- EXT_L20, EXT_L20_JOINT: at most k grid points (pixels) with a non-zero gradient vector (l20.h) ------------------------------------------
+// BallProj's norms launch into a g of its own -- N entries, or the L pixels of the joint set with its chunk plan --, CardGroupsProj's
+// selection (CardgSelect: sipx_card_groups_route forces the route of both), k_l20_zero.  k >= the number of groups launches nothing.
+static void l20_check_spec(const ExtSpec& sp, bool frames) {
+  if (sp.G.N >= (1ll << 31)) throw std::runtime_error(L20_TOO_LARGE);
+  if (sp.nblk < 2) throw std::runtime_error(L20_NEEDS_TV);
+  l21_check_spec(sp);
+  if (sp.lb || sp.weighted) throw std::runtime_error(L20_NO_WEIGHTS);
+  if (frames) {
+    if (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0 || sp.mode != SIPX_MODE_SLICE || sp.dir != 2)
+      throw std::runtime_error(L20_MODES);
+    return;
+  }
+  if (sp.mode != SIPX_MODE_WHOLE) throw std::runtime_error(L20_MODES);
+  if (sp.ub) throw std::runtime_error(L20_K_VECTOR);
+  if (sp.kind == EXT_L20_JOINT && (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0)) throw std::runtime_error(L20_JOINT_ROUTE);
+}
+// v <- the members of the dropped groups set to +0, for the three sets: (ps) the one selection, or (need, tau, cut) per frame
+template <typename T>
+static void l20_zero(hipStream_t s, const ExtSpec& sp, T* v, const T* g, long long ngroups, const ProjScalars<T>* ps, const int* need,
+                     const T* tau, const int* cut) {
+  constexpr int W = l21_vec_width<T>();
+  const bool wide = l21_wide(sp, v, g);
+  void (*const k)(L21Args, T*, const T*, const ProjScalars<T>*, const int*, const T*, const int*) =
+      sp.kind == EXT_L20_SEG     ? (wide ? k_l20_zero<T, 2, W, true, false> : k_l20_zero<T, 2, 1, true, false>)
+      : sp.kind == EXT_L20_JOINT ? (wide ? k_l20_zero<T, 2, W, false, true> : k_l20_zero<T, 2, 1, false, true>)
+      : sp.nblk == 2             ? (wide ? k_l20_zero<T, 2, W, false, false> : k_l20_zero<T, 2, 1, false, false>)
+                                 : (wide ? k_l20_zero<T, 3, W, false, false> : k_l20_zero<T, 3, 1, false, false>);
+  ObsScope obs(KID_L20_ZERO, s, (double)ngroups * sizeof(T), (double)sp.nblk * sp.G.N * sizeof(T));
+  hipLaunchKernelGGL(k, dim3(fit_grid(sp.G.N / (wide ? W : 1), NB)), dim3(BLOCK), 0, s, l21_args(sp), v, g, ps, need, tau, cut);
+  SIPX_HIP(hipGetLastError());
+}
+template <typename T>
+struct L20Proj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  const bool joint;
+  long long n = 0, k = 0;              // groups: the entries of g; groups kept, clamped to n
+  T* g = nullptr;                      // the keys
+  double* part = nullptr;              // EXT_L20_JOINT: the chunk sums, nchunk L entries, when the plan chunks
+  CardgSelect<T> sel;
+  long long calls = 0, selections = 0;      // projections since the reset; those that ran a selection (k < n)
+  L20Proj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s), joint(spec.kind == EXT_L20_JOINT) {
+    l20_check_spec(sp, false);
+    n = joint ? sp.G.st[2] : sp.G.N;
+    l20_check_k<T>(sp.pmax, n);
+    k = sp.pmax >= (double)n ? n : (long long)sp.pmax;
+    g = this->template alloc<T>(n);
+    const int nchunk = joint ? l21_joint_plan(n, sp.G.n[2], (int)sizeof(T)).nchunk : 1;
+    if (nchunk > 1) part = this->template alloc<double>((size_t)nchunk * n);
+    sel.build(this->mem, s, n, k);
+  }
+  void reset() override { sel.reinit(stream); calls = selections = 0; }
+  void project(T* v, bool feas, double* partials, T* maxpart, T* compact) override {
+    ++calls;
+    if (k >= n) return;                // every group stays: nothing to select, nothing to write
+    ++selections;
+    l21_norms<T>(stream, sp, v, g, part);
+    const ProjScalars<T>* ps = sel.run(stream, g, feas, partials, maxpart, compact);
+    l20_zero<T>(stream, sp, v, g, n, ps, nullptr, nullptr, nullptr);
+  }
+  // out[p] <- g_p (n entries): the norms launch of project() into its own g, copied out; v is not written
+  void observe(const T* v, T* out, double*, T*, T*) override {
+    l21_norms<T>(stream, sp, v, g, part);
+    SIPX_HIP(hipMemcpyAsync(out, g, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+  }
+  void set_data(const T*, const T*, bool) override { throw std::runtime_error(L20_NO_SET_DATA); }
+  // projections since the reset, the selections the small route ran, those the search route ran (k >= n runs none), the groups
+  void route_counts(long long out[4]) const override {
+    out[0] = calls; out[1] = sel.small ? selections : 0; out[2] = sel.small ? 0 : selections; out[3] = n;
+  }
+};
+
+// ---- EXT_L20_SEG: at most k (or k[frame]) pixels with a non-zero gradient vector in every z-slice, on the range of TV_xy (l20.h) ------------
+//     k_l21_norms     as FrameProj launches it                                            reads 2 N words, writes N
+//     k_l20_frames    one workgroup per frame on g alone: (need, tau, cut) of the frame   reads N (LDS) or (2 + bytes of T) N
+//     k_l20_zero      the per-frame form; frames without need are skipped                 reads up to N, writes up to 2 N
+// Nothing is kept between calls.  Built with ExtSpec::ub every frame has its own budget (kvec, n3 entries of T), sipx_set_data replaces them.
+template <typename T>
+struct L20FrameProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  T *g = nullptr, *tau = nullptr, *kvec = nullptr;
+  int *need = nullptr, *cut = nullptr;
+  long long nf = 0, L = 0;
+  long long calls = 0, selections = 0;
+  L20FrameProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s) {
+    l20_check_spec(sp, true);
+    nf = sp.G.n[2];
+    L = sp.G.n[0] * sp.G.n[1];
+    if (sp.ub) l20_check_k_vector<T>((const T*)sp.ub, nf, L);
+    else l20_check_k<T>(sp.pmax, L);
+    g = this->template alloc<T>(sp.G.N);
+    tau = this->template alloc<T>(nf);
+    need = this->template alloc<int>(2 * nf);
+    cut = need + nf;
+    if (sp.ub) {
+      kvec = this->template alloc<T>(nf);
+      SIPX_HIP(hipMemcpy(kvec, sp.ub, sizeof(T) * (size_t)nf, hipMemcpyHostToDevice));
+    }
+  }
+  void reset() override { calls = selections = 0; }
+  void project(T* v, bool, double*, T*, T*) override {
+    ++calls;
+    if (!kvec && sp.pmax >= (double)L) return;      // every group of every frame stays: nothing to select, nothing to write
+    ++selections;
+    l21_norms<T>(stream, sp, v, g);
+    const L21SegPlan plan = l21_seg_plan(L, nf, (int)sizeof(T));
+    {
+      ObsScope obs(KID_L20_FRAMES, stream, (double)sp.G.N * sizeof(T));
+      if (kvec)
+        hipLaunchKernelGGL((k_l20_frames<T, true>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, stream, plan, (unsigned)L, (unsigned)nf, g,
+                           T(0), kvec, need, tau, cut);
+      else
+        hipLaunchKernelGGL((k_l20_frames<T, false>), dim3(plan.grid), dim3(BLOCK), plan.lds_bytes, stream, plan, (unsigned)L, (unsigned)nf, g,
+                           (T)sp.pmax, (const T*)nullptr, need, tau, cut);
+      SIPX_HIP(hipGetLastError());
+    }
+    l20_zero<T>(stream, sp, v, g, sp.G.N, nullptr, need, tau, cut);
+  }
+  // out[p] <- g_p (N entries, point order): the norms launch of project() into its own g, copied out; v is not written
+  void observe(const T* v, T* out, double*, T*, T*) override {
+    l21_norms<T>(stream, sp, v, g);
+    SIPX_HIP(hipMemcpyAsync(out, g, sizeof(T) * (size_t)sp.G.N, hipMemcpyDeviceToDevice, stream));
+  }
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    if (!kvec) throw std::runtime_error(L20_NO_SET_DATA);
+    if (new_lb) throw std::runtime_error(L20_SET_DATA_UB);
+    if (new_ub)
+      SIPX_HIP(hipMemcpyAsync(kvec, new_ub, sizeof(T) * (size_t)nf, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  }
+  // projections since the reset, none by the small route, those that ran the per-frame selection, the groups of a frame
+  void route_counts(long long out[4]) const override { out[0] = calls; out[1] = 0; out[2] = selections; out[3] = L; }
 };
 
 // ---- EXT_L1_WEIGHTED: the weighted l1 ball on the rows of identity, D_x, D_y, D_z, TV or TV_xy (l1_weighted.h) ------------------------------
@@ -1419,6 +1781,8 @@ ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
   if (spec.kind == EXT_L1_WEIGHTED) return new L1WProj<T>(spec, stream);
   if (spec.kind == EXT_L21_GROUPS) return new GroupsProj<T>(spec, stream);
   if (spec.kind == EXT_CARD_GROUPS) return new CardGroupsProj<T>(spec, stream);
+  if (spec.kind == EXT_L20 || spec.kind == EXT_L20_JOINT) return new L20Proj<T>(spec, stream);
+  if (spec.kind == EXT_L20_SEG) return new L20FrameProj<T>(spec, stream);
   if (spec.kind == EXT_TNV) return new TnvProj<T>(spec, stream);
   if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);
   if (spec.kind != EXT_L21 && spec.kind != EXT_L21_JOINT) throw std::runtime_error("unknown external projector");

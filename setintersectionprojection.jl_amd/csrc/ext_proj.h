@@ -15,7 +15,10 @@ enum { EXT_L1_DFT = 1, EXT_RANK = 2, EXT_NUCLEAR = 3, EXT_CARD_SEG = 4, EXT_HIST
        EXT_TNV = 18 /* total nuclear variation: the nuclear-norm ball on the 2 x n3 Jacobians of the pixels of TV_xy (tnv.h) */,
        EXT_L1_WEIGHTED = 19 /* the weighted l1 ball on the rows of identity, D_x, D_y, D_z, TV or TV_xy, one weight per row (l1_weighted.h) */,
        EXT_SIMPLEX_SEG = 20 /* the simplex of every fiber or slice: entries >= 0, sum in [pmin, pmax] (seg_simplex.h) */,
-       EXT_CARD_GROUPS = 21 /* at most pmax non-zero fibers or slices of a one-block operator's range (card_groups.h) */ };
+       EXT_CARD_GROUPS = 21 /* at most pmax non-zero fibers or slices of a one-block operator's range (card_groups.h) */,
+       EXT_L20 = 22 /* at most pmax grid points with a non-zero gradient vector on the range of TV / TV_xy (l20.h) */,
+       EXT_L20_SEG = 23 /* ... at most pmax (or ub[frame]) pixels in every z-slice of TV_xy */,
+       EXT_L20_JOINT = 24 /* ... at most pmax pixels that carry a gradient in any frame of TV_xy */ };
 
 // The refusal of an EXT_L21_JOINT set off its operator or mode, worded once: set_config.h (sipx_add_set), the stand-alone calls of the
 // engine and the projector's own check throw this text (its cases: tests/test_l21_joint_cpu.py, tests/test_gpu_l21_joint.py)
@@ -64,7 +67,7 @@ class ExtProj {
   void project(T* v, bool feas, double* partials, T* maxpart, T* compact);
   // the l2,1 sets (ext_group.hip): out (device) <- what project(v, ...) would compare with the radius, summed and rounded by the
   // projector's own launches -- ||v||_2,1 for EXT_L21, the sum of the n1 n2 group norms for EXT_L21_JOINT, one sum per z-slice (n3
-  // entries) for EXT_L21_SEG, the weighted sum of the segment norms for EXT_L21_GROUPS, the sum of the 2 n1 n2 singular values for EXT_TNV; and sum_i w_i |v_i| for EXT_L1_WEIGHTED; one sum of the positive parts per segment (nseg entries, SegMap's order) for EXT_SIMPLEX_SEG; the l2 norm of every segment (nseg entries, the selection key) for EXT_CARD_GROUPS.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
+  // entries) for EXT_L21_SEG, the weighted sum of the segment norms for EXT_L21_GROUPS, the sum of the 2 n1 n2 singular values for EXT_TNV; and sum_i w_i |v_i| for EXT_L1_WEIGHTED; one sum of the positive parts per segment (nseg entries, SegMap's order) for EXT_SIMPLEX_SEG; the l2 norm of every segment (nseg entries, the selection key) for EXT_CARD_GROUPS; the norm of every gradient group (N entries in point order, EXT_L20_JOINT: the n1 n2 pixels; the selection key) for the EXT_L20 kinds.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
   void observe(const T* v, T* out, double* partials, T* maxpart, T* compact);
   // rank projector: calls since construction, calls served by the warm-started subspace route, calls that decomposed fully,
   // products with the Gram matrices the subspace route spent (all zero for the other kinds)
@@ -89,7 +92,7 @@ template <typename T>
 void seg_observe(const ExtSpec& spec, int norm_l2, const T* v, T* out, hipStream_t stream);
 
 // sipx_card_groups_route, a hook of the tests and of tools/card_groups_bench.py: the selection route of the EXT_CARD_GROUPS projectors built
-// from now on in this process -- 0: by the number of segments, 1: the small route (k_cardg_rank), 2: the engine's search
+// and of the EXT_L20 / EXT_L20_JOINT projectors (tools/l20_bench.py) from now on in this process -- 0: by the number of segments, 1: the small route (k_cardg_rank), 2: the engine's search
 void card_groups_force_route(int route);
 
 // sum (projected - original)^2 and sum original^2 into partial slots dst[0..NB), dst[NB..2NB)

@@ -4,7 +4,7 @@
 //   ext_rank.hip       slice / matrix rank, nuclear norm
 //   ext_segments.hip   cardinality, l1, l2, annulus and the simplex per fiber / slice, relaxed histogram, subspace
 //   ext_group.hip      the l2,1 ball across the blocks of the TV / TV_xy operator, whole array, per z-slice or jointly across the frames;
-//                      the l2,1 ball over the fibers or slices of a one-block operator's range and group cardinality on the same segments; the weighted l1 ball on the rows of an operator
+//                      the l2,1 ball over the fibers or slices of a one-block operator's range and group cardinality on the same segments; the l2,0 sets on the groups of TV / TV_xy; the weighted l1 ball on the rows of an operator
 #include "ext_family.h"
 
 namespace sipx {
@@ -34,7 +34,7 @@ ExtProj<T>::ExtProj(const ExtSpec& spec, hipStream_t stream) : impl_(nullptr) {
     case EXT_RANK: case EXT_NUCLEAR: impl_ = make_rank_family<T>(spec, stream); break;
     case EXT_CARD_SEG: case EXT_L1_SEG: case EXT_L2_SEG: case EXT_ANNULUS_SEG: case EXT_SIMPLEX_SEG: case EXT_HISTOGRAM: case EXT_SUBSPACE:
       impl_ = make_segment_family<T>(spec, stream); break;
-    case EXT_L21: case EXT_L21_SEG: case EXT_L21_JOINT: case EXT_L21_GROUPS: case EXT_CARD_GROUPS: case EXT_TNV: case EXT_L1_WEIGHTED: impl_ = make_group_family<T>(spec, stream); break;
+    case EXT_L21: case EXT_L21_SEG: case EXT_L21_JOINT: case EXT_L21_GROUPS: case EXT_CARD_GROUPS: case EXT_L20: case EXT_L20_SEG: case EXT_L20_JOINT: case EXT_TNV: case EXT_L1_WEIGHTED: impl_ = make_group_family<T>(spec, stream); break;
     default: throw std::runtime_error("unknown external projector");
   }
 }

@@ -14,6 +14,7 @@
 #include "l1_weighted.h"     // (the refusals and the host checks of the weighted l1 ball)
 #include "seg_simplex.h"     // (the refusals and the check of the bounds of the simplex sets)
 #include "card_groups.h"     // (the refusals and the check of k of group cardinality)
+#include "l20.h"             // (the refusals and the checks of k of the l2,0 sets on TV / TV_xy)
 
 namespace sipx {
 
@@ -105,7 +106,8 @@ void expand_fiber_bounds(const ConfigCtx& c, const SetConfig<T>& s, const T* per
 // L1_WEIGHTED: the weights live in the one projector of a single process, in the padded layout of the whole operator.
 // SIMPLEX: not built for sharded contexts yet (seg_simplex.h); a rank would see its part of every slice only.
 // CARD_GROUPS: the segments compete for k places across the whole array (card_groups.h).
-enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX, CARD_GROUPS };
+// L20: the gradient groups span the blocks of TV and compete for k places across the whole array (l20.h).
+enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX, CARD_GROUPS, L20 };
 inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
   if (c.single_process) return;
   switch (which) {
@@ -126,6 +128,8 @@ inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
       throw std::runtime_error(SIMPLEX_SHARDED);
     case Sharded::CARD_GROUPS:
       throw std::runtime_error(CARDG_SHARDED);
+    case Sharded::L20:
+      throw std::runtime_error(L20_SHARDED);
   }
 }
 // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
@@ -258,16 +262,26 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (s.comp) throw std::runtime_error(CARDG_NO_MINKOWSKI);
     if (mode == SIPX_MODE_WHOLE) throw std::runtime_error(CARDG_NEEDS_MODE);
   }
+  // so are the l2,0 sets (l20.h): the TV or TV_xy operator, no transform, no component, the whole array or (slice, z) on TV_xy
+  if (d->proj == SIPX_PROJ_L20 || d->proj == SIPX_PROJ_L20_JOINT) {
+    const bool jt = d->proj == SIPX_PROJ_L20_JOINT;
+    if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(L20_NO_TRANSFORM);
+    if (jt && (s.op != SIPX_OP_TV_XY || mode != SIPX_MODE_WHOLE)) throw std::runtime_error(L20_JOINT_ROUTE);
+    if (s.custom || (s.op != SIPX_OP_TV && s.op != SIPX_OP_TV_XY)) throw std::runtime_error(L20_NEEDS_TV);
+    if (s.comp) throw std::runtime_error(L20_NO_MINKOWSKI);
+    if (mode != SIPX_MODE_WHOLE && !(s.op == SIPX_OP_TV_XY && mode == SIPX_MODE_SLICE && dir == 2)) throw std::runtime_error(L20_MODES);
+  }
   if (mode != SIPX_MODE_WHOLE) {
     if (dir < 0 || dir >= c.ndim) throw std::runtime_error("application mode: direction out of range for this grid");
     // the one multi-block set with a mode of its own: the l2,1 ball per z-slice on TV_xy (l21_seg.h)
-    const bool frames = d->proj == SIPX_PROJ_L21 && s.op == SIPX_OP_TV_XY && d->transform == SIPX_TRANSFORM_NONE;
+    const bool l20_frames = d->proj == SIPX_PROJ_L20;      // ((slice, z) on TV_xy: checked above)
+    const bool frames = (d->proj == SIPX_PROJ_L21 && s.op == SIPX_OP_TV_XY && d->transform == SIPX_TRANSFORM_NONE) || l20_frames;
     if (frames && !(mode == SIPX_MODE_SLICE && dir == 2))
       throw std::runtime_error("the l2,1 ball on TV_xy: frames run along z -- the mode must be (slice, z), or tensor for the whole array");
     if (s.nblk > 1 && !frames) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
   }
   auto ext = [&](int kind) {
-    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT && kind != EXT_TNV && kind != EXT_L1_WEIGHTED) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
+    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT && kind != EXT_TNV && kind != EXT_L1_WEIGHTED && kind != EXT_L20 && kind != EXT_L20_SEG && kind != EXT_L20_JOINT) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
     s.ext_kind = kind;
     s.spec.kind = kind;
     s.spec.ndim = c.ndim;
@@ -475,6 +489,26 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       ext(EXT_CARD_GROUPS);
       cardg_check_k<T>(d->pmax, seg_count(s.spec));
       break;
+    case SIPX_PROJ_L20:        // at most pmax grid points carry a gradient vector, or per frame pmax / ub[frame] pixels (operator, transform,
+    case SIPX_PROJ_L20_JOINT:  // component, mode: above); at most pmax pixels carry one in any frame
+      if (d->lb || d->reserved) throw std::runtime_error(L20_NO_WEIGHTS);
+      if (d->ub && mode == SIPX_MODE_WHOLE) throw std::runtime_error(L20_K_VECTOR);
+      refuse_sharded(c, Sharded::L20);
+      if (G.N >= (1ll << 31)) throw std::runtime_error(L20_TOO_LARGE);
+      if (mode == SIPX_MODE_WHOLE) {
+        ext(d->proj == SIPX_PROJ_L20_JOINT ? EXT_L20_JOINT : EXT_L20);
+        l20_check_k<T>(d->pmax, d->proj == SIPX_PROJ_L20_JOINT ? G.st[2] : G.N);
+      } else {
+        ext(EXT_L20_SEG);
+        if (d->ub) {
+          s.seg_radii = true;
+          s.host_ub.assign((const T*)d->ub, (const T*)d->ub + G.n[2]);
+          l20_check_k_vector<T>(s.host_ub.data(), G.n[2], G.n[0] * G.n[1]);
+        } else {
+          l20_check_k<T>(d->pmax, G.n[0] * G.n[1]);
+        }
+      }
+      break;
     case SIPX_PROJ_SIMPLEX:  // entries >= 0 and a sum in [pmin, pmax] per fiber or slice (operator, transform, component, mode: above)
       if (c.ndim == 2 && mode == SIPX_MODE_SLICE) throw std::runtime_error(SIMPLEX_2D_SLICE);
       if (d->lb || d->ub) throw std::runtime_error(SIMPLEX_NO_VECTORS);
@@ -529,7 +563,7 @@ template <typename T>
 long long data_len(const ConfigCtx& c, const SetConfig<T>& s) {
   if (s.ext_kind == EXT_L1_WEIGHTED) return s.Mtrue;
   if (s.weighted) return s.ext_kind == EXT_L21_GROUPS ? seg_count(s.spec) : l21_groups(c, s.ext_kind);
-  if (s.seg_radii) return s.ext_kind == EXT_L21_SEG ? c.G.n[2] : seg_count(s.spec);
+  if (s.seg_radii) return (s.ext_kind == EXT_L21_SEG || s.ext_kind == EXT_L20_SEG) ? c.G.n[2] : seg_count(s.spec);
   if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;
   return c.G.n[s.bdir] - ((s.nblk == 1 && s.dir[0] == s.bdir) ? 1 : 0);
 }

@@ -42,14 +42,14 @@ EXPORTED_SYMBOLS = [
     "sipx_l21_joint_norm", "sipx_l21_joint_norm_dev", "sipx_l21_weighted_norm", "sipx_l21_weighted_norm_dev",
     "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev", "sipx_tnv_norm", "sipx_tnv_norm_dev",
     "sipx_l1_weighted_norm", "sipx_l1_weighted_norm_dev", "sipx_segment_sums", "sipx_segment_sums_dev",
-    "sipx_group_norms", "sipx_group_norms_dev", "sipx_card_groups_route",
+    "sipx_group_norms", "sipx_group_norms_dev", "sipx_card_groups_route", "sipx_tv_group_norms", "sipx_tv_group_norms_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16,
-        "tnv": 17, "l1_weighted": 18, "simplex": 19, "card_groups": 20}
+        "tnv": 17, "l1_weighted": 18, "simplex": 19, "card_groups": 20, "l20": 21, "l20_joint": 22}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -142,6 +142,34 @@ CARDG_K_INEXACT = ("group cardinality (card_groups): a k below the number of seg
 CARDG_TOO_LARGE = "group cardinality (card_groups): the grid needs fewer than 2^31 points -- split the array"
 CARDG_NO_COARSE = ("multilevel: group cardinality (card_groups) has no rule that takes k to a grid with another number of segments -- "
                    "solve on one level")
+# the l2,0 sets on total variation (csrc/l20.h): at most k grid points (pixels) carry a gradient vector; the engine's refusals, word for word
+L20_NEEDS_TV = ("the l2,0 set (l20) counts the gradient vectors of the TV operator: TD_OP must be TV (D2D, D3D) or TV_xy, not a "
+                "one-block or custom operator (there use the cardinality set, which counts entries, or card_groups)")
+L20_JOINT_ROUTE = ("the joint l2,0 set (l20_joint) needs the TV_xy operator of a 3-D grid in tensor mode: its groups span "
+                   "the frames -- for one budget over all grid points use (\"l20\", \"TV_xy\"), per frame (\"l20\", \"TV_xy\", "
+                   "(\"slice\", \"z\"))")
+L20_MODES = ("the l2,0 set (l20) applies to the whole array (matrix / tensor mode), or per frame as (\"slice\", \"z\") on TV_xy: "
+             "fiber modes and other slices have no gradient groups -- use card_groups on D_x, D_y or D_z there")
+L20_NO_TRANSFORM = ("the l2,0 set (l20, l20_joint) takes no transform (DFT, DCT, wavelet): it acts on TV x itself -- use the "
+                    "cardinality set behind the transform, which counts coefficients")
+L20_NO_MINKOWSKI = "the l2,0 set (l20, l20_joint) takes no Minkowski component: constrain the sum of the components"
+L20_NO_WEIGHTS = ("the l2,0 set (l20, l20_joint) takes no weights and no lb: a group is kept or dropped whole by its plain "
+                  "norm -- for weighted groups use the l21 set with weights")
+L20_K_VECTOR = ("the l2,0 set (l20) takes one k, or per frame -- (\"slice\", \"z\") on TV_xy -- a vector of n3 integers in max; "
+                "every other form has one budget: pass a scalar")
+L20_NO_SET_DATA = ("the l2,0 set (l20, l20_joint) built with a scalar k holds no vectors to replace -- build the per-frame "
+                   "set with a vector of n3 budgets to replace them, or a new context for another k")
+L20_SET_DATA_UB = "the l2,0 set (l20) per frame: the budgets are its ub, n3 integers >= 1; it has no lb"
+L20_SHARDED = ("the l2,0 set (l20, l20_joint) takes single-process contexts only, this one has a communicator, a slab "
+               "decomposition or set ownership: its groups span the blocks of TV and compete for k places across the "
+               "whole array -- use a single process")
+L20_NO_COARSE = ("multilevel: the l2,0 set (l20, l20_joint) has no rule that takes k to a grid with another number of "
+                 "points -- solve on one level")
+L20_BAD_K = ("the l2,0 set (l20, l20_joint) needs an integer k >= 1, the number of grid points that may carry a gradient "
+             "(k = 0 is the constant array: use bounds on TV)")
+L20_K_INEXACT = ("the l2,0 set (l20, l20_joint): a k below the number of groups must be exactly representable in the "
+                 "working precision, since the search reads k from it -- Float32: k <= 2^24; use Float64")
+L20_TOO_LARGE = "the l2,0 set (l20, l20_joint): the grid needs fewer than 2^31 points -- split the array"
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
 TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
 TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
@@ -484,6 +512,8 @@ class Projector:
             raise SipxError(SIMPLEX_NO_WEIGHTS)
         if getattr(constraint, "weights", None) is not None and st == "card_groups":
             raise SipxError(CARDG_NO_VECTORS)
+        if getattr(constraint, "weights", None) is not None and st in ("l20", "l20_joint"):
+            raise SipxError(L20_NO_WEIGHTS)
         if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint", "l21_groups", "l1_weighted"):
             raise SipxError(f"set type {st!r} takes no weights: " + L21_WEIGHTS_WHERE)
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
@@ -589,6 +619,38 @@ class Projector:
             what = "fiber along" if self.mode == MODES["fiber"] else "slice orthogonal to"
             self._take_weights(constraint, nseg, f"segment, a segment being a {what} dimension {self.dir + 1} of the array of shape "
                                                  f"{tuple(tdn)} (TD_n), in the order of segment_norms()")
+            return
+        if st in ("l20", "l20_joint"):
+            # at most k = max grid points (pixels) carry a gradient vector of TV / TV_xy (csrc/l20.h); min is ignored
+            joint = st == "l20_joint"
+            cust = constraint.custom_TD_OP[0]
+            if constraint.TD_OP in SPECIAL_OPERATORS:
+                raise SipxError(L20_NO_TRANSFORM)
+            if not (isinstance(cust, (tuple, list)) and len(cust) == 0):
+                raise SipxError(L20_JOINT_ROUTE if joint else L20_NEEDS_TV)
+            if joint and (constraint.TD_OP != "TV_xy" or self.mode):
+                raise SipxError(L20_JOINT_ROUTE)
+            if constraint.TD_OP not in TV_OPERATORS + ("TV_xy",):
+                raise SipxError(L20_NEEDS_TV)
+            if constraint.TD_OP == "TV_xy" and len(n) != 3:
+                raise SipxError(TV_XY_NEEDS_3D)
+            if self.mode and not (constraint.TD_OP == "TV_xy" and (self.mode, self.dir) == (MODES["slice"], 2)):
+                raise SipxError(L20_MODES)
+            if np.ndim(constraint.min) != 0:
+                raise SipxError(L20_NO_WEIGHTS)
+            if int(np.prod(n)) >= 2 ** 31:
+                raise SipxError(L20_TOO_LARGE)
+            self.kind, self.op = st, ("TV_xy" if constraint.TD_OP == "TV_xy" else "TV")
+            ngroups = int(n[0]) * int(n[1]) if (joint or self.mode) else int(np.prod(n))
+            if np.ndim(constraint.max) != 0:
+                if not self.mode or np.ndim(constraint.max) != 1:
+                    raise SipxError(L20_K_VECTOR)
+                ks = [_check_l20_k(k, ngroups, self.TF) for k in np.asarray(constraint.max).tolist()]
+                self.seg_radii = True
+                self.ub = np.ascontiguousarray(ks, self.TF)
+                self.pmax = float(max(ks)) if ks else 1.0
+            else:
+                self.pmax = _check_l20_k(constraint.max, ngroups, self.TF)
             return
         if st == "l21_joint":
             # joint (vectorial) total variation: one group per pixel across the frames of TV_xy (csrc/l21_joint.h); max is the radius
@@ -784,7 +846,7 @@ class Projector:
         if not self.mode:
             return 0
         n = list(op.n)
-        if self.kind == "l21":          # frames of the grid itself
+        if self.kind in ("l21", "l20"):          # frames of the grid itself
             return int(n[2])
         if op.kind in ("D_x", "D_y", "D_z"):
             n[{"D_x": 0, "D_y": 1, "D_z": len(n) - 1}[op.kind]] -= 1
@@ -799,6 +861,12 @@ class Projector:
             raise SipxError(L21_JOINT_NEEDS_TV_XY)
         if self.kind == "tnv" and op.kind != "TV_xy":
             raise SipxError(TNV_NEEDS_TV_XY)
+        if self.kind == "l20" and (op.kind != "TV_xy" if self.op == "TV_xy" else op.kind not in TV_OPERATORS):
+            raise SipxError(L20_NEEDS_TV)
+        if self.kind == "l20_joint" and op.kind != "TV_xy":
+            raise SipxError(L20_JOINT_ROUTE)
+        if self.kind in ("l20", "l20_joint") and getattr(op, "component", 0):
+            raise SipxError(L20_NO_MINKOWSKI)
         if self.kind == "l21_groups":
             if op.kind == "custom":
                 raise SipxError(L21G_NO_CUSTOM)
@@ -835,7 +903,11 @@ class Projector:
             want = n[self.dir] if self.mode == MODES["fiber"] else rows
             if self.lb.shape != (want,) or self.ub.shape != (want,):
                 raise SipxError(f"bounds vectors need {want} entries for this operator / application mode")
-        if self.seg_radii and self.kind == "l21":
+        if self.seg_radii and self.kind == "l20":
+            if self.ub.shape != (n[2],):
+                raise SipxError(f"l20 budgets per frame: max has {self.ub.shape[0]} entries, n3 = {n[2]} are needed -- one per z-slice "
+                                f"of the grid of shape {tuple(n)}")
+        elif self.seg_radii and self.kind == "l21":
             if self.ub.shape != (n[2],):
                 raise SipxError(f"l21 radii per frame: max has {self.ub.shape[0]} entries, n3 = {n[2]} are needed -- one per z-slice "
                                 f"of the grid of shape {tuple(n)}")
@@ -886,13 +958,14 @@ class Projector:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
                                                                               "subspace", "l21", "l21_joint", "l21_groups", "tnv", "l1_weighted",
-                                                                              "simplex", "card_groups")
-        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups")
+                                                                              "simplex", "card_groups", "l20", "l20_joint")
+        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint")
         if l21:                      # the M-vector of the TV range (l21_groups: of its operator's) in the reference's row order, on the grid
             op = TDOperator(self.op, self.comp_grid, self.TF)
             rows = op.shape[0]
             if v.shape != (rows,):
-                what = {"l1_weighted": "weighted l1 ball", "simplex": "simplex set", "card_groups": "group cardinality set"}.get(self.kind, "l2,1 ball")
+                what = {"l1_weighted": "weighted l1 ball", "simplex": "simplex set", "card_groups": "group cardinality set", "l20": "l2,0 set",
+                        "l20_joint": "l2,0 set"}.get(self.kind, "l2,1 ball")
                 raise SipxError(f"the {what} projects a vector of the {self.op} range: {rows} entries on this grid, {v.size} given")
             self.check_rows(op)
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
@@ -986,7 +1059,15 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
     most k fibers / slices of the array of shape TD_n are non-zero -- "at most k traces change" on D_z per fiber z, "at most k frames are
     active" on the identity per slice z.  The non-convex counterpart of l21_groups (ncvx is set, as for cardinality and rank): the k
     segments of largest l2 norm stay as they are, ties to the lower segment index, the others become zero.  k is an integer >= 1; min is
-    ignored.  group_norms() observes the norms it selects on."""
+    ignored.  group_norms() observes the norms it selects on.
+
+    ("l20", "TV" | "TV_xy", 0, k, ("matrix" | "tensor", "")) is the l2,0 set on total variation (csrc/l20.h), L0 gradient smoothing: at most
+    k grid points carry a non-zero gradient vector -- a piecewise-constant model with at most k edge points whose edges keep their
+    contrast.  ("l20", "TV_xy", 0, k, ("slice", "z")) gives every frame its own budget, k one integer or a vector of n3 (replaceable with
+    Solver.set_data as ub); ("l20_joint", "TV_xy", 0, k, ("tensor", "")) lets at most k pixels carry an edge in any frame, one common edge
+    set.  The non-convex counterparts of the l21 / l21_joint sets (ncvx is set): the k groups of largest norm stay as they are, ties to
+    the lower point index, every member of the others becomes zero.  ("cardinality", "TV") is another set: it counts differences, so a
+    diagonal edge costs two.  tv_group_norms() observes the norms it selects on."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -995,7 +1076,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.min, c.max = [np.asarray(a, TF) if np.ndim(a) else (TF(a) if isinstance(a, (float, np.floating)) else a) for a in (c.min, c.max)]
         elif c.set_type == "l21" and np.ndim(c.max):
             pass                                       # (radii per frame: converted below)
-        elif c.set_type == "card_groups":
+        elif c.set_type in ("card_groups", "l20", "l20_joint"):
             pass                                       # (max is k, a count: Projector must see it unrounded to refuse one that TF cannot hold)
         elif np.ndim(c.min) == 0:
             if isinstance(c.min, (float, np.floating)):
@@ -1006,7 +1087,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.max = np.asarray(c.max, TF)
         if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
             c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
-        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups"):
+        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -1032,7 +1113,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
         prop.AtA_diag.append(AtA_diag); prop.dense.append(dense); prop.TD_n.append(TD_n)
         prop.banded.append(banded); prop.AtA_offsets.append(None)
         prop.tag.append((c.set_type, c.TD_OP, c.app_mode[0], c.app_mode[1]))
-        if c.set_type in ("rank", "cardinality", "card_groups"):
+        if c.set_type in ("rank", "cardinality", "card_groups", "l20", "l20_joint"):
             ncvx = True
         elif c.set_type in ("bounds", "histogram") and c.TD_OP != "identity" and TF(np.max(c.min)) > TF(0):
             ncvx = True
@@ -1285,7 +1366,10 @@ class Context:
                 a = _check_array(name, a, self.TF, want)
             arrs.append(a)
         P = self._keep_proj[int(i)] if 0 <= int(i) < len(self._keep_proj) else None
-        if P is not None and P.seg_radii and arrs[1] is not None:
+        if P is not None and P.kind == "l20" and P.seg_radii and arrs[1] is not None:
+            for k in arrs[1].tolist():
+                _check_l20_k(k, int(np.prod(_grid(P.comp_grid)[0][:2])), self.TF)
+        elif P is not None and P.seg_radii and arrs[1] is not None:
             _check_l1_radii("l1" if P.kind == "l21" else P.kind, arrs[1])
         if P is not None and P.weighted:
             if arrs[1] is not None:
@@ -1755,6 +1839,18 @@ def _check_l21_weights(kind, w):
                         "finite and >= 0 (0 leaves its group unconstrained)")
 
 
+def _check_l20_k(k, ngroups, TF):
+    """One budget of an l2,0 set over ngroups groups in precision TF (csrc/l20.h, l20_check_k): an integer >= 1 that TF holds."""
+    if isinstance(k, (bool, np.bool_)) or np.ndim(k) != 0:
+        raise SipxError(L20_BAD_K)
+    k = float(k)
+    if not np.isfinite(k) or k != np.floor(k) or k < 1:
+        raise SipxError(L20_BAD_K)
+    if k < ngroups and float(TF(k)) != k:
+        raise SipxError(L20_K_INEXACT)
+    return k
+
+
 def _check_l1_radii(kind, r):
     """project_l1_Duchi!.jl:22 for every segment: no host path hands the device an l1 radius that is not > 0."""
     if kind == "l1" and not np.all(np.asarray(r) > 0):
@@ -1893,6 +1989,10 @@ class Solver:
             raise SipxError(f"set_data: set index {i} out of range ({pp} sets)")
         if self.P_sub[i].kind == "card_groups":
             raise SipxError("set_data: " + CARDG_NO_SET_DATA)
+        if self.P_sub[i].kind in ("l20", "l20_joint") and not self.P_sub[i].seg_radii:
+            raise SipxError("set_data: " + L20_NO_SET_DATA)
+        if self.P_sub[i].kind == "l20" and lb is not None:
+            raise SipxError("set_data: " + L20_SET_DATA_UB)
         want = self.P_sub[i].data_len(self.TD_OP[i])
         if want is None:
             raise SipxError(f"set_data: set {i} ({self.set_Prop.tag[i][0]} on {self.set_Prop.tag[i][1]}) holds no replaceable vectors -- "
@@ -1920,7 +2020,10 @@ class Solver:
         else:
             for k, a in given:
                 _check_array(k, a, self.TF, want)
-            if self.P_sub[i].seg_radii and ub is not None:
+            if self.P_sub[i].kind == "l20" and ub is not None:
+                for k in np.asarray(ub).tolist():
+                    _check_l20_k(k, int(np.prod(_grid(self.comp_grid)[0][:2])), self.TF)
+            elif self.P_sub[i].seg_radii and ub is not None:
                 _check_l1_radii("l1" if self.P_sub[i].kind == "l21" else self.P_sub[i].kind, ub)
             if self.P_sub[i].weighted and lb is not None:
                 _check_l21_weights(self.P_sub[i].kind, lb)
@@ -2128,6 +2231,56 @@ def group_norms(x, comp_grid, TD_OP: str, app_mode):
     if TF not in (np.float32, np.float64):
         raise SipxError("group_norms: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
     return _segment_observe(x, comp_grid, TD_OP, am, TF, on_dev, "card_groups", "sipx_group_norms", ())
+
+
+def tv_group_norms(x, comp_grid, TD_OP: str = "TV", joint: bool = False):
+    """The norms of the gradient groups of TV x (TD_OP "TV", "D2D", "D3D" or "TV_xy"): N numbers g of the working precision (that of x) in
+    grid-point order (column-major), or with joint=True the n1 n2 numbers of the pixels of TV_xy across all frames.  Computed by the norms
+    launch of the ("l20", TD_OP) / ("l20_joint", "TV_xy") projector (sipx_tv_group_norms, csrc/l20.h), which is the one of the l21 /
+    l21_joint sets: the very array the set selects on -- it keeps the first k groups of the stable descending order of g (ties to the
+    lower index), so k can be picked from the sorted values; per frame it selects on g[frame] of g.reshape(n3, n1 n2).  The count the
+    projector compares with k is count_nonzero(g).  x: a numpy vector or a 1-D torch tensor on a GPU."""
+    if TD_OP in SPECIAL_OPERATORS:
+        raise SipxError(L20_NO_TRANSFORM)
+    if joint and TD_OP != "TV_xy":
+        raise SipxError(L20_JOINT_ROUTE)
+    if TD_OP not in TV_OPERATORS + ("TV_xy",):
+        raise SipxError(L20_NEEDS_TV)
+    on_dev = _is_tensor(x)
+    TF = _tensor_TF("x", x) if on_dev else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("tv_group_norms: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    n, _ = _grid(comp_grid)
+    if TD_OP == "TV_xy" and len(n) != 3:
+        raise SipxError(TV_XY_NEEDS_3D)
+    N = int(np.prod(n))
+    ng = int(n[0]) * int(n[1]) if joint else N
+    if on_dev:
+        import torch
+        _check_tensor("x", x, TF, N, None)
+        _check_one_hip_runtime()
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        out = torch.empty(ng, dtype=x.dtype, device=torch.device("cuda", device))
+        xp, op_ = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr())
+        fn = lib().sipx_tv_group_norms_dev
+    else:
+        x = _check_array("x", x, TF, N)
+        device = None
+        out = np.empty(ng, TF)
+        xp, op_ = _ptr(x), _ptr(out)
+        fn = lib().sipx_tv_group_norms
+    ctx = Context(comp_grid, TF, device)
+    try:
+        if on_dev:
+            ctx.set_caller_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        cnt = C.c_int64()
+        _chk(fn(ctx.h, OPS[TD_OP], int(bool(joint)), None, None, C.byref(cnt)))      # the count only
+        if cnt.value != ng:
+            raise SipxError(f"internal: the engine counts {cnt.value} groups, the host {ng}")
+        _chk(fn(ctx.h, OPS[TD_OP], int(bool(joint)), xp, op_, C.byref(cnt)))
+    finally:
+        ctx.close()
+    return out
 
 
 def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after, weights=None, groups=0, no_weights=()):

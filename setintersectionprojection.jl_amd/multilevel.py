@@ -34,6 +34,8 @@ def constraint2coarse(constraint, comp_grid, cf):
             raise host.SipxError(host.SIMPLEX_NO_COARSE)
         if c.set_type == "card_groups":
             raise host.SipxError(host.CARDG_NO_COARSE)
+        if c.set_type in ("l20", "l20_joint"):
+            raise host.SipxError(host.L20_NO_COARSE)
         if getattr(c, "weights", None) is not None:
             raise host.SipxError(host.L21_WEIGHTS_NO_COARSE)
         if c.set_type == "rank":
