@@ -237,7 +237,20 @@ enum {
   SIPX_PROJ_L20_JOINT = 22 /* the joint l2,0 set: { v = TV_xy x : at most k pixels (i, j) carry a non-zero gradient in any frame }, the
                               group of a pixel being that of SIPX_PROJ_L21_JOINT -- one common edge set for all frames; set ncvx = 1.
                               op TV_XY, mode WHOLE only.  pmax = k as above with n1 n2 groups; g from the z-march of
-                              SIPX_PROJ_L21_JOINT, bit for bit; ties to the lower pixel index; the rest as SIPX_PROJ_L20 */
+                              SIPX_PROJ_L21_JOINT, bit for bit; ties to the lower pixel index; the rest as SIPX_PROJ_L20 */,
+  SIPX_PROJ_L21_STACKED = 23 /* the l2,1 ball across the equal-sized blocks of a caller-supplied stacked operator (csrc/l21_stacked.h):
+                                { v = A x : sum_p ||v_p||_2 <= pmax }, A = [A_0; ...; A_{B-1}] given as SIPX_OP_CSC with M = B G rows,
+                                B = the descriptor's `blocks` (1 .. 8, M % B == 0 or the set is refused with both numbers), the group of
+                                p < G being { v[q G + p] : q < B }: every row is a member, a zero row contributes nothing.  With A the
+                                Hessian of the grid (the front end's named operator "Hessian": B = 3 in 2-D, 6 in 3-D, the mixed blocks
+                                scaled by sqrt 2) this is second-order isotropic TV, sum_p ||H x(p)||_F <= pmax, whose null space is the
+                                affine functions.  op SIPX_OP_CSC, mode WHOLE, no transform, no component, lb = ub = NULL, reserved = 0,
+                                pmax > 0; pmin is ignored; ncvx = 0.  g_p, the threshold search, the Float64 refinement and the
+                                unwritten inside case are those of SIPX_PROJ_L21; no floating-point atomics: two calls give the same
+                                bits.  Both forms of Q work: ata_R with up to 9 bands, or ata_R = NULL, the matrix-free term (the
+                                Hessian's A'A has 13 / 25 bands: it enters matrix-free).  Contexts with a communicator, a slab
+                                decomposition or set ownership are refused.  sipx_project takes the M-vector itself (len = M entries,
+                                `blocks` set; op and the CSC arrays are not looked at); sipx_l21_stacked_norm observes the norm */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -287,6 +300,10 @@ typedef struct {
                         BOUNDS, BOUNDS_VEC, L1 or CARDINALITY (mode WHOLE), op the identity.  WAVELET = the db4 transform above;
                         proj must be BOUNDS (scalar), L1 or CARDINALITY (mode WHOLE), op the identity.  The DFT has its own kinds above. */
   int32_t pad_;
+  int32_t blocks;    /* SIPX_PROJ_L21_STACKED: B, the number of equal-sized blocks of the stacked operator (1 .. 8); 0 for every other
+                        kind.  Appended behind the older fields: a descriptor zero-initialised by a caller that does not know the
+                        field configures every older kind as before */
+  int32_t pad2_;
 } sipx_set_desc;
 
 /* PARSDMM_options (src/SetIntersectionProjection.jl:110-128); Blas_active / parallel / FL /
@@ -530,6 +547,14 @@ int sipx_l21_norm_dev(sipx_ctx* ctx, const void* x, void* out);
  * receives the number of values; x = out = NULL only asks for it.  Every other combination is refused as sipx_add_set refuses it. */
 int sipx_l21_norms(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
 int sipx_l21_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, void* out, int64_t* nseg);
+/* The norm SIPX_PROJ_L21_STACKED compares with pmax: *out = one TF, the sum over p < G of the group norms of A x, A the SIPX_OP_CSC
+ * operator of the descriptor d (op, csc_* and blocks are read; proj may be left 0), x TF[N] on the grid of the context (which needs no
+ * sets and no finalize).  A x comes from the engine's sparse product into scratch of the call, the group norms from the kernel of the
+ * projector, the sum from the first pass of its threshold search.  CONTRACT: the value is the very number the projector compares with
+ * pmax, so a radius observed on x leaves A x unwritten.  x, out: host memory; the _dev form takes both in device memory of the
+ * context's GPU, ordered like sipx_l21_norm_dev against the caller's stream.  Refused where the set is refused. */
+int sipx_l21_stacked_norm(sipx_ctx* ctx, const sipx_set_desc* d, const void* x, void* out);
+int sipx_l21_stacked_norm_dev(sipx_ctx* ctx, const sipx_set_desc* d, const void* x, void* out);
 /* The joint total variation of the frames of x: *out = one TF, the sum over the pixels (i, j) of the group norms g_ij of SIPX_PROJ_L21_JOINT
  * on [D_y; D_x] x, x TF[N] on the 3-D grid of the context.  The norms come from the z-march of the projector, the sum from the first
  * pass of its threshold search.  CONTRACT: the value is the very number the projector compares with pmax, so a radius observed on x

@@ -39,6 +39,7 @@ struct SipxSetDesc                     # sipx_set_desc
     component::Int32
     csc_colptr::Ptr{Int64}; csc_rowval::Ptr{Int64}; csc_nzval::Ptr{Cvoid}; csc_rows::Int64
     transform::Int32; pad_::Int32
+    blocks::Int32; pad2_::Int32          # SIPX_PROJ_L21_STACKED: the equal-sized blocks of the stacked operator; 0 otherwise
 end
 
 struct SipxOptions                     # sipx_options
@@ -77,6 +78,12 @@ const SIPX_PROJ_CARD_GROUPS = 20
 # the l2,0 sets on the gradient groups of TV / TV_xy (include/sipx.h, csrc/l20.h), set_type = "l20" and "l20_joint", max = k
 const SIPX_PROJ_L20 = 21
 const SIPX_PROJ_L20_JOINT = 22
+# the l2,1 ball across the equal-sized blocks of a caller-supplied stacked operator (include/sipx.h, csrc/l21_stacked.h), set_type =
+# "l21_stacked", custom_TD_OP = (A, false) with A = [A_0; ...; A_{B-1}] a SparseMatrixCSC of M = B G rows, max = the radius.  The
+# reference's set_definitions has no field for B: it travels in min (an integer 1 .. 8), which the set does not use otherwise.
+# With A the Hessian of the grid (D_11, D_22[, D_33], sqrt(2) D_12[, sqrt(2) D_13, sqrt(2) D_23], each zero-padded to N rows) this is
+# second-order isotropic TV; the Python front end assembles that operator under the name "Hessian".
+const SIPX_PROJ_L21_STACKED = 23
 const MODE = Dict("matrix" => 0, "tensor" => 0, "fiber" => 1, "slice" => 2)
 const SPECIAL = ("DFT", "DCT", "wavelet", "curvelet")          # src/setup_constraints.jl:54
 # the seven @timeit sections of src/PARSDMM.jl:40,100,105,113,152,163,229
@@ -192,6 +199,17 @@ function projector_fields(c, TF)
         (c.max isa Real && isfinite(c.max) && c.max >= 1 && c.max == floor(c.max)) ||
             error("the l2,0 set (l20, l20_joint) needs an integer k >= 1, the number of grid points that may carry a gradient (k = 0 is the constant array: use bounds on TV)")
         return (SIPX_PROJ_L20_JOINT, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
+    if st == "l21_stacked"
+        c.custom_TD_OP[1] == [] && error("the stacked l2,1 ball (l21_stacked) groups the rows of a caller-supplied sparse operator across its blocks: the operator must be SIPX_OP_CSC (custom_TD_OP, or the named \"Hessian\") -- on the built-in TV operator the set is (\"l21\", \"TV\")")
+        c.app_mode[1] in ("matrix", "tensor") ||
+            error("the stacked l2,1 ball (l21_stacked) applies to the whole array (matrix / tensor mode): its groups are the rows p, G + p, 2 G + p, ... of the operator, fibers and slices have no meaning there")
+        (c.min isa Real && c.min == floor(c.min) && 1 <= c.min <= 8) ||
+            error("the stacked l2,1 ball (l21_stacked): blocks = $(c.min), the number of equal-sized blocks of the operator must be 1 .. 8")
+        size(c.custom_TD_OP[1], 1) % Int(c.min) == 0 ||
+            error("the stacked l2,1 ball (l21_stacked): the operator has M = $(size(c.custom_TD_OP[1], 1)) rows, not a multiple of blocks = $(Int(c.min)) -- every block needs the same number of rows (pad a shorter block with zero rows)")
+        c.max > 0 || error("Radius of L1 ball is negative")
+        return (SIPX_PROJ_L21_STACKED, 0.0, Float64(c.max), nothing_[3:5]...)
     end
     st == "simplex" && error("simplex sets (simplex, SIPX_PROJ_SIMPLEX) are not built in this binding yet: use (\"bounds\") together with (\"l1\", op, mode) and segment_norms=true, or the C ABI")
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
@@ -439,7 +457,8 @@ function PARSDMM(m         ::Vector{TF},
                             0,                                                # Minkowski component (see INTEGRATION.md)
                             colptr === nothing ? C_NULL : pointer(colptr), rowval === nothing ? C_NULL : pointer(rowval),
                             nzval === nothing ? C_NULL : pointer(nzval), rows,
-                            transform, 0)
+                            transform, 0,
+                            kind == SIPX_PROJ_L21_STACKED ? Int32(c.min) : Int32(0), 0)
             # AtA[i] in CDS (N x d_i) with its offsets.  A custom sparse TD_OP of a set that is not banded
             # (set_Prop.banded[i] == false: the reference keeps its AtA sparse, PARSDMM_precompute_distribute.jl:51-59) goes
             # without AtA: libsipx applies it as a matrix-free term of Q.  JOLI / dense AtA stay outside libsipx.

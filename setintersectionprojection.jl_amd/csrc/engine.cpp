@@ -390,6 +390,7 @@ class Engine : public EngineBase {
       if (s.ext_kind == EXT_SIMPLEX_SEG) refuse_sharded(ctx, Sharded::SIMPLEX);
       if (s.ext_kind == EXT_CARD_GROUPS) refuse_sharded(ctx, Sharded::CARD_GROUPS);
       if (s.ext_kind == EXT_L20 || s.ext_kind == EXT_L20_SEG || s.ext_kind == EXT_L20_JOINT) refuse_sharded(ctx, Sharded::L20);
+      if (s.ext_kind == EXT_L21_STACKED) refuse_sharded(ctx, Sharded::L21_STACKED);
     }
     FinalizePlan P;
     plan_sets();
@@ -1061,6 +1062,10 @@ class Engine : public EngineBase {
       if (s.ext_kind) {
         SetArgs<T> a = set_args(s, rho_[i], gamma_[i], 0);
         a.x = mm;
+        if (s.custom) {                                        // (EXT_L21_STACKED: s = A m materialised, the projector acts on its M entries)
+          custom_fwd(stream_, s, mm, s.sbuf);
+          a.x = s.sbuf;
+        }
         ext_feasibility(s, a, dst);
       } else if (s.custom) {                                   // s = A m materialised, then as for an identity set
         custom_fwd(stream_, s, mm, s.sbuf);
@@ -1677,7 +1682,7 @@ class Engine : public EngineBase {
       a.v = s.fanv;
       a.vsrc = 2;
     } else if (s.ext_kind) {   // library-backed projector: materialise v, project it in place, hand y to the fused update
-      K<T>::store_v(q, G_, a, 0, scr_v_);
+      K<T>::store_v(q, s.custom ? gs : G_, a, 0, scr_v_);      // (a custom operator: the M entries of s = A x, EXT_L21_STACKED)
       {
         ObsScope obs(KID_EXT, stream_, 0.0);
         s.ext->project(scr_v_, false, scr.ptmp, scr.mpart, scr.cbuf);
@@ -3666,6 +3671,60 @@ class Engine : public EngineBase {
     finish_call(on_device, out, dout, 1);
   }
 
+  // SIPX_PROJ_L21_STACKED of sipx_project: the M-vector itself, d->blocks blocks of len / blocks entries (l21_stacked.h); the operator of
+  // the descriptor is not looked at
+  void project_l21_stacked(const sipx_set_desc* d, void* v, int64_t len) {
+    if (d->mode != SIPX_MODE_WHOLE) throw std::runtime_error(L21S_WHOLE_ONLY);
+    if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(L21S_NO_TRANSFORM);
+    if (d->component) throw std::runtime_error(L21S_NO_MINKOWSKI);
+    if (d->lb || d->ub || d->reserved) throw std::runtime_error(L21S_NO_VECTORS);
+    l21s_check_shape(len, d->blocks);
+    refuse_sharded(config_ctx(), Sharded::L21_STACKED);
+    if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+    ExtSpec sp;
+    l21s_spec(sp, len, d->blocks);
+    sp.pmax = d->pmax;
+    DeviceMemory tmp;
+    T* dv = tmp.alloc<T>(len);
+    const SearchScratch q(tmp, len / d->blocks, false);
+    SIPX_HIP(hipMemcpy(dv, v, len * sizeof(T), hipMemcpyHostToDevice));
+    {
+      ExtProj<T> ext(sp, stream_);
+      ext.project(dv, false, q.part, q.mp, q.dc);
+      finish_call(false, v, dv, len);
+    }
+  }
+
+  // sipx_l21_stacked_norm(_dev): what the SIPX_PROJ_L21_STACKED set of descriptor d compares with its radius on A x -- A x by custom_fwd
+  // through a CSR copy in scratch of the call, then the observe() of a throw-away projector of that set (ext_group.hip, BallProj): the
+  // norms launch and the first pass of the search of its project()
+  void l21_stacked_norm(const sipx_set_desc* d, const void* x, void* out, bool on_device) override {
+    if (!d || !x || !out) throw std::runtime_error("stacked l2,1 norm: the descriptor, x and out are needed");
+    SIPX_HIP(hipSetDevice(device_));
+    if (d->op != SIPX_OP_CSC) throw std::runtime_error(L21S_NEEDS_CSC);
+    const ConfigCtx ctx = config_ctx();
+    SetState<T> s;
+    configure_custom(ctx, s, d);
+    sipx_set_desc dd = *d;
+    dd.proj = SIPX_PROJ_L21_STACKED; dd.pmax = 1.0; dd.ncvx = 0;
+    configure_proj(ctx, s, &dd);               // the refusals, and the ExtSpec, of the set
+    DeviceMemory tmp;
+    upload_custom(s, tmp);
+    T* dx = on_device ? nullptr : tmp.alloc<T>(G_.N);
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
+    const SearchScratch q(tmp, s.spec.bstride, false);
+    ExtProj<T> ext(s.spec, stream_);
+    if (on_device) engine_after_caller();
+    else SIPX_HIP(hipMemcpyAsync(dx, x, G_.N * sizeof(T), hipMemcpyHostToDevice, stream_));
+    custom_fwd(stream_, s, on_device ? (const T*)x : dx, s.sbuf);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)(s.spec.nblk + 1) * s.spec.bstride * sizeof(T));
+      ext.observe(s.sbuf, dout, q.part, q.mp, q.dc);
+    }
+    finish_call(on_device, out, dout, 1);
+  }
+
   void project(const sipx_set_desc* d, void* v, int64_t len) override {
     SIPX_HIP(hipSetDevice(device_));
     if (d->proj == SIPX_PROJ_L21 || d->proj == SIPX_PROJ_L21_JOINT || d->proj == SIPX_PROJ_L21_GROUPS || d->proj == SIPX_PROJ_TNV) {
@@ -3686,6 +3745,10 @@ class Engine : public EngineBase {
     }
     if (d->proj == SIPX_PROJ_L20 || d->proj == SIPX_PROJ_L20_JOINT) {
       project_l20(d, v, len);
+      return;
+    }
+    if (d->proj == SIPX_PROJ_L21_STACKED) {
+      project_l21_stacked(d, v, len);
       return;
     }
     Grid g1;
@@ -4183,6 +4246,10 @@ class Engine : public EngineBase {
   // of the column-major entries keeps that order) for s = A x
   void upload_custom(SetState<T>& s) {
     if (s.mfree) { upload_mfree(s); return; }
+    upload_custom(s, mem_);
+  }
+  // (mem: the context's memory for a set; the scratch of a stand-alone call, sipx_l21_stacked_norm)
+  void upload_custom(SetState<T>& s, DeviceMemory& mem) {
     const long long N = G_.N, M = s.Mtrue, nnz = (long long)s.h_rowval.size();
     std::vector<long long> rowptr(M + 1, 0), colidx(nnz);
     std::vector<T> rval(nnz);
@@ -4197,12 +4264,12 @@ class Engine : public EngineBase {
       }
     auto up = [&](auto*& dst, const auto& src) {
       using E = typename std::remove_reference<decltype(src)>::type::value_type;
-      dst = mem_.alloc<E>(src.size(), Mem::NoFill);
-      SIPX_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice));
+      dst = mem.alloc<E>(std::max<size_t>(src.size(), 1), Mem::NoFill);
+      if (!src.empty()) SIPX_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice));
     };
     up(s.d_colptr, s.h_colptr); up(s.d_rowval, s.h_rowval); up(s.d_nzval, s.h_nzval);
     up(s.d_rowptr, rowptr); up(s.d_colidx, colidx); up(s.d_rval, rval);
-    s.sbuf = mem_.alloc<T>(M, Mem::State);
+    s.sbuf = mem.alloc<T>(M, Mem::State);
     s.h_colptr.clear(); s.h_rowval.clear(); s.h_nzval.clear();
   }
 
@@ -4470,7 +4537,7 @@ class Engine : public EngineBase {
 
   // ||P(s) - s||^2, ||s||^2 for a library-backed projector: s = A x materialised twice, one copy projected
   void ext_feasibility(SetState<T>& s, const SetArgs<T>& a, double* dst) {
-    K<T>::store_v(stream_, G_, a, 1, scr_v_);
+    K<T>::store_v(stream_, s.custom ? s.gm : G_, a, 1, scr_v_);      // (a custom operator: a.x is s = A x, M entries)
     SIPX_HIP(hipMemcpyAsync(scr_w_, scr_v_, s.Mpad * sizeof(T), hipMemcpyDeviceToDevice, stream_));
     s.ext->project(scr_v_, true, part_tmp_, maxpart_, scr_c_);
     ext_dist2<T>(stream_, s.Mpad, scr_v_, scr_w_, dst);

@@ -58,6 +58,8 @@ struct EngineBase {
   // the six sipx_l21_*norm* calls and sipx_tnv_norm(_dev): proj SIPX_PROJ_L21, SIPX_PROJ_L21_JOINT or SIPX_PROJ_TNV; query: x and out both null ask for *nseg alone
   virtual void l21_norms(int proj, int op, int mode, int dir, const void* x, void* out, int64_t* nseg, bool on_device, bool query) = 0;
   virtual void l21_weighted_norm(int op, bool joint, const void* x, const void* w, void* out, bool on_device) = 0;
+  // sipx_l21_stacked_norm(_dev): the norm a SIPX_PROJ_L21_STACKED set of descriptor d compares with its radius on A x
+  virtual void l21_stacked_norm(const sipx_set_desc* d, const void* x, void* out, bool on_device) = 0;
   virtual void l1_weighted_norm(int op, const void* x, const void* w, void* out, bool on_device) = 0;
   // sipx_l21_groups_norm(_dev): w null: every weight 1
   virtual void l21_groups_norm(int op, int mode, int dir, const void* x, const void* w, void* out, bool on_device) = 0;

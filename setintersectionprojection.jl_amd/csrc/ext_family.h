@@ -4,7 +4,8 @@
 //   ext_segments.hip   cardinality, l1, l2 and annulus per fiber / slice (seg_norm.h), the simplex per fiber / slice (seg_simplex.h),
 //                      relaxed histogram, subspace
 //   ext_group.hip      the l2,1 ball across the blocks of the TV / TV_xy operator: BallProj on the whole array (l21.h) or with groups
-//                      across the frames (l21_joint.h), FrameProj per z-slice (l21_seg.h); GroupsProj: the l2,1 ball whose groups are the
+//                      across the frames (l21_joint.h) or across the equal-sized blocks of a caller-supplied stacked operator (l21_stacked.h),
+//                      FrameProj per z-slice (l21_seg.h); GroupsProj: the l2,1 ball whose groups are the
 //                      fibers or slices of a one-block operator's range (l21_groups.h); CardGroupsProj: at most k non-zero ones (card_groups.h); L20Proj / L20FrameProj: at most k non-zero gradient groups of TV / TV_xy (l20.h); L1WProj: the weighted l1 ball on the rows of an
 //                      operator (l1_weighted.h)
 // -- and what more than one family uses.

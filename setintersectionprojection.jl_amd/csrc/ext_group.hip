@@ -26,6 +26,8 @@
 // and a 2 x 2 matrix per pixel in place of the weight.
 // The weighted l1 ball on the rows of an operator (EXT_L1_WEIGHTED, l1_weighted.h, L1WProj) is the weighted iteration once more, on the pairs
 // (|v_i|, w_i) of the flat padded array: a pass kernel that reads v itself (k_l1w_part) and a soft-threshold apply (k_l1w_apply).
+// The ball whose groups run across the equal-sized blocks of a caller-supplied stacked operator (EXT_L21_STACKED, l21_stacked.h: the Hessian
+// of second-order TV) is BallProj once more with k_l21s_norms / k_l21s_scale in place of the TV kernels: no coordinates, no pads.
 // Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the projectors.
 // A projector's observe() runs the norms launch and the first sum of its own project(): what it reports is what project() decides on.
 #include <atomic>
@@ -34,6 +36,7 @@
 #include "l21.h"
 #include "l21_joint.h"
 #include "l21_seg.h"
+#include "l21_stacked.h"
 #include "l21_groups.h"
 #include "card_groups.h"
 #include "l20.h"
@@ -174,6 +177,58 @@ __global__ __launch_bounds__(BLOCK) void k_l21_theta_final(int nparts, unsigned 
 template <typename T>
 __global__ void k_l21_pick(const ProjScalars<T>* __restrict__ ps, T* __restrict__ out) {
   if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = (T)ps->asum;
+}
+
+// ---- the ball across the blocks of a stacked operator (l21_stacked.h, EXT_L21_STACKED) ----------------------------------------------------
+//     k_l21s_norms    g[p] <- the l2 norm of { v[q G + p] : q < B }                          reads B G words, writes G
+//     k_l21s_scale    v[q G + p] <- v[q G + p] * f_p unless the search found v inside         reads (B + 1) G words, writes B G
+// Grid-stride over the G groups with 32-bit indices (B G < 2^31 is checked when the projector is built), no LDS, VW consecutive groups per
+// thread: 16 bytes of every block and of g when G % VW == 0 (then every block base q G is 16-byte aligned), one group otherwise.  Every
+// position is a member, so there is no coordinate arithmetic and no partial store.  NBLK = 3 and 6 (the Hessian of a 2-D / 3-D grid) are
+// compiled as constants, NBLK = 0 loops over the runtime B.
+template <typename T, int NBLK, int VW>
+__global__ __launch_bounds__(BLOCK) void k_l21s_norms(unsigned G, int B, const T* __restrict__ v, T* __restrict__ g) {
+  const int nb = NBLK > 0 ? NBLK : B;
+  const unsigned nvec = G / VW, step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    double ss[VW];
+#pragma unroll
+    for (int k = 0; k < VW; ++k) ss[k] = 0.0;
+#pragma unroll
+    for (int q = 0; q < nb; ++q) {
+      const Vec<T, VW> x = ldv<T, VW>(v + l21s_index((unsigned)q, G, p));
+#pragma unroll
+      for (int k = 0; k < VW; ++k) ss[k] = l21s_add_square<T>(ss[k], x.v[k]);
+    }
+    Vec<T, VW> out;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) out.v[k] = l21_norm_of<T>(ss[k]);
+    stv<T, VW>(g + p, out);
+  }
+}
+template <typename T, int NBLK, int VW>
+__global__ __launch_bounds__(BLOCK) void k_l21s_scale(unsigned G, int B, T* __restrict__ v, const T* __restrict__ g,
+                                                      const ProjScalars<T>* __restrict__ ps, const T* __restrict__ theta) {
+  if (!ps->need) return;
+  const T th = theta ? theta[0] : ps->theta;          // (Float64: the threshold k_l21_theta_final left)
+  const int nb = NBLK > 0 ? NBLK : B;
+  const unsigned nvec = G / VW, step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    const Vec<T, VW> gv = ldv<T, VW>(g + p);
+    T f[VW];
+#pragma unroll
+    for (int k = 0; k < VW; ++k) f[k] = l21_weight<T>(gv.v[k], th);
+#pragma unroll
+    for (int q = 0; q < nb; ++q) {
+      T* vq = v + l21s_index((unsigned)q, G, p);
+      Vec<T, VW> x = ldv<T, VW>(vq);
+#pragma unroll
+      for (int k = 0; k < VW; ++k) x.v[k] = l21s_scaled<T>(x.v[k], f[k]);
+      stv<T, VW>(vq, x);
+    }
+  }
 }
 
 // ---- the weighted ball (l21_weighted.h): one weight per group, EXT_L21 and EXT_L21_JOINT built with ExtSpec::weighted ---------------------
@@ -1035,6 +1090,46 @@ static void l21_frames(hipStream_t s, const ExtSpec& sp, const T* g, T tau, cons
   SIPX_HIP(hipGetLastError());
 }
 
+// ---- EXT_L21_STACKED (l21_stacked.h): the spec -- nblk = B blocks of bstride = G rows on the 1-D grid of the M = B G rows -- and the launchers
+static void l21s_check_spec(const ExtSpec& sp) {
+  const long long G = l21s_check_shape(sp.G.N, sp.nblk);
+  if (sp.bstride != G) throw std::runtime_error("the stacked l2,1 ball: the block stride must be the rows of one block");
+  if (sp.mode != SIPX_MODE_WHOLE) throw std::runtime_error(L21S_WHOLE_ONLY);
+  if (sp.weighted || sp.lb || sp.ub) throw std::runtime_error(L21S_NO_VECTORS);
+}
+// 16-byte accesses: G a multiple of the vector width (every block base q G then is 16-byte aligned) and 16-byte aligned arrays
+template <typename T>
+static bool l21s_wide(const ExtSpec& sp, const T* v, const T* g) {
+  return sp.bstride % l21_vec_width<T>() == 0 && aligned16(v, g);
+}
+// the thread-iterations of one trip of the grid-stride loops: with VW groups each, G above L21S_TRIP * VW takes a second trip
+constexpr long long L21S_TRIP = (long long)NB * BLOCK;
+template <typename T>
+static void l21s_norms(hipStream_t s, const ExtSpec& sp, const T* v, T* g) {
+  constexpr int W = l21_vec_width<T>();
+  const bool wide = l21s_wide(sp, v, g);
+  const long long G = sp.bstride;
+  void (*const k)(unsigned, int, const T*, T*) = sp.nblk == 3   ? (wide ? k_l21s_norms<T, 3, W> : k_l21s_norms<T, 3, 1>)
+                                                 : sp.nblk == 6 ? (wide ? k_l21s_norms<T, 6, W> : k_l21s_norms<T, 6, 1>)
+                                                                : (wide ? k_l21s_norms<T, 0, W> : k_l21s_norms<T, 0, 1>);
+  ObsScope obs(KID_L21S_NORMS, s, (double)(sp.nblk + 1) * G * sizeof(T));
+  hipLaunchKernelGGL(k, dim3(fit_grid(G / (wide ? W : 1), NB)), dim3(BLOCK), 0, s, (unsigned)G, sp.nblk, v, g);
+  SIPX_HIP(hipGetLastError());
+}
+template <typename T>
+static void l21s_scale(hipStream_t s, const ExtSpec& sp, T* v, const T* g, const ProjScalars<T>* ps, const T* theta) {
+  constexpr int W = l21_vec_width<T>();
+  const bool wide = l21s_wide(sp, v, g);
+  const long long G = sp.bstride;
+  void (*const k)(unsigned, int, T*, const T*, const ProjScalars<T>*, const T*) =
+      sp.nblk == 3   ? (wide ? k_l21s_scale<T, 3, W> : k_l21s_scale<T, 3, 1>)
+      : sp.nblk == 6 ? (wide ? k_l21s_scale<T, 6, W> : k_l21s_scale<T, 6, 1>)
+                     : (wide ? k_l21s_scale<T, 0, W> : k_l21s_scale<T, 0, 1>);
+  ObsScope obs(KID_L21S_SCALE, s, (double)(2 * sp.nblk + 1) * G * sizeof(T));
+  hipLaunchKernelGGL(k, dim3(fit_grid(G / (wide ? W : 1), NB)), dim3(BLOCK), 0, s, (unsigned)G, sp.nblk, v, g, ps, theta);
+  SIPX_HIP(hipGetLastError());
+}
+
 // ---- the weighted Michelot iteration on n entries (g, w) (l21_weighted.h): the device state and the launches, for BallProj's weighted
 // route and for GroupsProj.  wide: 16-byte loads of g and w (n a multiple of 16 bytes' worth of entries, both arrays aligned).
 // L1: the pass kernel is k_l1w_part, which takes g = |v| from v itself (l1_weighted.h, L1WProj); the finish, the batches, the flag are these.
@@ -1097,13 +1192,14 @@ struct L21WSearch {
   }
 };
 
-// ---- EXT_L21, EXT_L21_JOINT: one ball on the whole array -- the norms, the engine's search on g, Float64: the refinement, the scale ----
-// The two sets differ in what a group is, hence in the norms launch and in the length of g: the N grid points, or the L pixels.
+// ---- EXT_L21, EXT_L21_JOINT, EXT_L21_STACKED: one ball on the whole array -- the norms, the engine's search on g, Float64: the refinement, the scale ----
+// The sets differ in what a group is, hence in the norms and scale launches and in the length of g: the N grid points, the L pixels, or the
+// G rows of one block of a stacked operator.
 template <typename T>
 struct BallProj : ExtImpl<T> {
   using ExtImpl<T>::sp;
   using ExtImpl<T>::stream;
-  const bool joint;
+  const bool joint, stacked;
   long long n = 0;                     // groups: the entries of g, the length of the search
   T* g = nullptr;                      // the group norms
   double* part = nullptr;              // EXT_L21_JOINT: the chunk sums, nchunk L entries, when the plan chunks
@@ -1115,11 +1211,12 @@ struct BallProj : ExtImpl<T> {
   T* w = nullptr;                      // one weight per group
   L21WSearch<T> ws;                    // the iteration on (g, w)
   void reset() override { search.reinit(stream); }
-  BallProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s), joint(spec.kind == EXT_L21_JOINT) {
-    if (joint) l21_joint_check_spec(sp);
+  BallProj(const ExtSpec& spec, hipStream_t s) : ExtImpl<T>(spec, s), joint(spec.kind == EXT_L21_JOINT), stacked(spec.kind == EXT_L21_STACKED) {
+    if (stacked) l21s_check_spec(sp);
+    else if (joint) l21_joint_check_spec(sp);
     else l21_check_spec(sp);
     if (!(sp.pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
-    n = joint ? sp.G.st[2] : sp.G.N;
+    n = stacked ? sp.bstride : (joint ? sp.G.st[2] : sp.G.N);
     g = this->template alloc<T>(n);
     const int nchunk = joint ? l21_joint_plan(n, sp.G.n[2], (int)sizeof(T)).nchunk : 1;
     if (nchunk > 1) part = this->template alloc<double>((size_t)nchunk * n);
@@ -1135,6 +1232,11 @@ struct BallProj : ExtImpl<T> {
       theta = this->template alloc<T>(1);
     }
     search.build(this->mem, s, 0);
+  }
+  // g <- the group norms of v
+  void norms(const T* v) {
+    if (stacked) l21s_norms<T>(stream, sp, v, g);
+    else l21_norms<T>(stream, sp, v, g, part);
   }
   // the search on g; Float64: then the threshold of its active set in twice the working precision, left in theta[0]
   void threshold(ProjScalars<T>* ps, double* partials, T* maxpart, T* compact) {
@@ -1178,9 +1280,10 @@ struct BallProj : ExtImpl<T> {
       return;
     }
     ProjScalars<T>* ps = search.pick(feas);
-    l21_norms<T>(stream, sp, v, g, part);
+    norms(v);
     threshold(ps, partials, maxpart, compact);
-    if (joint) l21_scale<T>(stream, sp, KID_L21J_SCALE, (4 * N + n) * sizeof(T), v, g, ps, theta, nullptr);
+    if (stacked) l21s_scale<T>(stream, sp, v, g, ps, theta);
+    else if (joint) l21_scale<T>(stream, sp, KID_L21J_SCALE, (4 * N + n) * sizeof(T), v, g, ps, theta, nullptr);
     else l21_scale<T>(stream, sp, KID_L21_SCALE, (2 * sp.nblk + 1) * N * sizeof(T), v, g, ps, theta, nullptr);
   }
   // out[0] <- the sum of the group norms as project decides on it: its norms launch into its g, then the first pass of a search with
@@ -1193,7 +1296,7 @@ struct BallProj : ExtImpl<T> {
       return;
     }
     if (!ps_obs) ps_obs = this->template alloc<ProjScalars<T>>(1);
-    l21_norms<T>(stream, sp, v, g, part);
+    norms(v);
     K<T>::ps_init(stream, ps_obs, nullptr);
     K<T>::proj_scalars_arr(stream, n, g, PX_L1, T(0), (T)INFINITY, ps_obs, partials, maxpart, compact, n);
     hipLaunchKernelGGL((k_l21_pick<T>), dim3(1), dim3(64), 0, stream, ps_obs, out);
@@ -1785,7 +1888,7 @@ ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
   if (spec.kind == EXT_L20_SEG) return new L20FrameProj<T>(spec, stream);
   if (spec.kind == EXT_TNV) return new TnvProj<T>(spec, stream);
   if (spec.kind == EXT_L21_SEG) return new FrameProj<T>(spec, stream);
-  if (spec.kind != EXT_L21 && spec.kind != EXT_L21_JOINT) throw std::runtime_error("unknown external projector");
+  if (spec.kind != EXT_L21 && spec.kind != EXT_L21_JOINT && spec.kind != EXT_L21_STACKED) throw std::runtime_error("unknown external projector");
   return new BallProj<T>(spec, stream);
 }
 

@@ -15,6 +15,7 @@
 #include "seg_simplex.h"     // (the refusals and the check of the bounds of the simplex sets)
 #include "card_groups.h"     // (the refusals and the check of k of group cardinality)
 #include "l20.h"             // (the refusals and the checks of k of the l2,0 sets on TV / TV_xy)
+#include "l21_stacked.h"     // (the refusals and the shape check of the l2,1 ball across the blocks of a stacked operator)
 
 namespace sipx {
 
@@ -107,7 +108,8 @@ void expand_fiber_bounds(const ConfigCtx& c, const SetConfig<T>& s, const T* per
 // SIMPLEX: not built for sharded contexts yet (seg_simplex.h); a rank would see its part of every slice only.
 // CARD_GROUPS: the segments compete for k places across the whole array (card_groups.h).
 // L20: the gradient groups span the blocks of TV and compete for k places across the whole array (l20.h).
-enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX, CARD_GROUPS, L20 };
+// L21_STACKED: the groups span the blocks of a caller-supplied operator (l21_stacked.h); no sharded route materialises its range.
+enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX, CARD_GROUPS, L20, L21_STACKED };
 inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
   if (c.single_process) return;
   switch (which) {
@@ -130,6 +132,8 @@ inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
       throw std::runtime_error(CARDG_SHARDED);
     case Sharded::L20:
       throw std::runtime_error(L20_SHARDED);
+    case Sharded::L21_STACKED:
+      throw std::runtime_error(L21S_SHARDED);
   }
 }
 // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
@@ -137,6 +141,21 @@ template <typename T>
 void check_l1_radii(const T* r, long long n) {
   for (long long k = 0; k < n; ++k)
     if (!(r[k] > T(0))) throw std::runtime_error("Radius of L1 ball is negative (segment " + std::to_string(k) + ")");
+}
+
+// the ExtSpec of an EXT_L21_STACKED projector on M rows in B blocks (checked: l21s_check_shape): the 1-D grid of the M rows, B blocks
+// of G = M / B rows each.  The engine's set and its stand-alone calls (sipx_project, sipx_l21_stacked_norm) build it here.
+inline void l21s_spec(ExtSpec& sp, long long M, int B) {
+  sp.kind = EXT_L21_STACKED;
+  sp.ndim = 2;
+  sp.G = Grid{};
+  sp.G.n[0] = M; sp.G.n[1] = 1; sp.G.n[2] = 1; sp.G.N = M; sp.G.st[0] = 1; sp.G.st[1] = M; sp.G.st[2] = M;
+  sp.dims[0] = M; sp.dims[1] = 1; sp.dims[2] = 1;
+  sp.mode = SIPX_MODE_WHOLE;
+  sp.dir = 0;
+  sp.nblk = B;
+  sp.bstride = M / B;
+  for (int q = 0; q < 3; ++q) sp.bdir[q] = 0;
 }
 
 // the groups of a weighted l2,1 set on TV / TV_xy (l21_weighted.h): the grid points of EXT_L21, the pixels of EXT_L21_JOINT
@@ -270,6 +289,15 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (s.custom || (s.op != SIPX_OP_TV && s.op != SIPX_OP_TV_XY)) throw std::runtime_error(L20_NEEDS_TV);
     if (s.comp) throw std::runtime_error(L20_NO_MINKOWSKI);
     if (mode != SIPX_MODE_WHOLE && !(s.op == SIPX_OP_TV_XY && mode == SIPX_MODE_SLICE && dir == 2)) throw std::runtime_error(L20_MODES);
+  }
+  // so is the l2,1 ball across the blocks of a stacked operator (l21_stacked.h): a caller-supplied operator, the whole array, no
+  // transform, no component, no vectors
+  if (d->proj == SIPX_PROJ_L21_STACKED) {
+    if (!s.custom) throw std::runtime_error(L21S_NEEDS_CSC);
+    if (mode != SIPX_MODE_WHOLE) throw std::runtime_error(L21S_WHOLE_ONLY);
+    if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(L21S_NO_TRANSFORM);
+    if (s.comp) throw std::runtime_error(L21S_NO_MINKOWSKI);
+    if (d->lb || d->ub || d->reserved) throw std::runtime_error(L21S_NO_VECTORS);
   }
   if (mode != SIPX_MODE_WHOLE) {
     if (dir < 0 || dir >= c.ndim) throw std::runtime_error("application mode: direction out of range for this grid");
@@ -509,6 +537,15 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
         }
       }
       break;
+    case SIPX_PROJ_L21_STACKED: {  // one group per row index of a block, across the d->blocks equal-sized blocks of the caller-supplied
+                                   // operator (operator, mode, transform, component, vectors: above)
+      l21s_check_shape(s.Mtrue, d->blocks);
+      refuse_sharded(c, Sharded::L21_STACKED);
+      if (!(d->pmax > 0)) throw std::runtime_error("Radius of L1 ball is negative");
+      ext(EXT_L21_STACKED);
+      l21s_spec(s.spec, s.Mtrue, d->blocks);
+      break;
+    }
     case SIPX_PROJ_SIMPLEX:  // entries >= 0 and a sum in [pmin, pmax] per fiber or slice (operator, transform, component, mode: above)
       if (c.ndim == 2 && mode == SIPX_MODE_SLICE) throw std::runtime_error(SIMPLEX_2D_SLICE);
       if (d->lb || d->ub) throw std::runtime_error(SIMPLEX_NO_VECTORS);
@@ -580,7 +617,8 @@ SetConfig<T> configure_set(const ConfigCtx& c, const sipx_set_desc* d, const voi
     if (d->component) throw std::runtime_error("the TV_xy operator takes no Minkowski component");
   }
   configure_proj(c, s, d);
-  if (s.custom && (s.comp || s.ext_kind))
+  // (the one materialised projector a custom operator takes: the l2,1 ball across its blocks, which acts on s = A x as a whole)
+  if (s.custom && (s.comp || (s.ext_kind && s.ext_kind != EXT_L21_STACKED)))
     throw std::runtime_error("custom sparse operators (SIPX_OP_CSC): Minkowski components and library-backed projectors are not available; "
                              "use one of the built-in operators for such a set");
   if (s.custom && !ata_R) {              // matrix-free term of Q: no bands, the products go through the operator itself

@@ -43,13 +43,14 @@ EXPORTED_SYMBOLS = [
     "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev", "sipx_tnv_norm", "sipx_tnv_norm_dev",
     "sipx_l1_weighted_norm", "sipx_l1_weighted_norm_dev", "sipx_segment_sums", "sipx_segment_sums_dev",
     "sipx_group_norms", "sipx_group_norms_dev", "sipx_card_groups_route", "sipx_tv_group_norms", "sipx_tv_group_norms_dev",
+    "sipx_l21_stacked_norm", "sipx_l21_stacked_norm_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16,
-        "tnv": 17, "l1_weighted": 18, "simplex": 19, "card_groups": 20, "l20": 21, "l20_joint": 22}
+        "tnv": 17, "l1_weighted": 18, "simplex": 19, "card_groups": 20, "l20": 21, "l20_joint": 22, "l21_stacked": 23}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -170,6 +171,34 @@ L20_BAD_K = ("the l2,0 set (l20, l20_joint) needs an integer k >= 1, the number 
 L20_K_INEXACT = ("the l2,0 set (l20, l20_joint): a k below the number of groups must be exactly representable in the "
                  "working precision, since the search reads k from it -- Float32: k <= 2^24; use Float64")
 L20_TOO_LARGE = "the l2,0 set (l20, l20_joint): the grid needs fewer than 2^31 points -- split the array"
+# the l2,1 ball across the equal-sized blocks of a stacked operator (csrc/l21_stacked.h): the engine's refusals, word for word
+L21S_MAX_BLOCKS = 8
+L21S_NEEDS_CSC = ("the stacked l2,1 ball (l21_stacked) groups the rows of a caller-supplied sparse operator across its blocks: "
+                  "the operator must be SIPX_OP_CSC (custom_TD_OP, or the named \"Hessian\") -- on the built-in TV operator "
+                  "the set is (\"l21\", \"TV\")")
+L21S_WHOLE_ONLY = ("the stacked l2,1 ball (l21_stacked) applies to the whole array (matrix / tensor mode): its groups are the "
+                   "rows p, G + p, 2 G + p, ... of the operator, fibers and slices have no meaning there")
+L21S_NO_TRANSFORM = "the stacked l2,1 ball (l21_stacked) takes no transform (DFT, DCT, wavelet): it acts on A x itself"
+L21S_NO_MINKOWSKI = "the stacked l2,1 ball (l21_stacked) takes no Minkowski component: custom operators have none"
+L21S_NO_VECTORS = "the stacked l2,1 ball (l21_stacked) takes no weights and no vectors (lb, ub): weights per group are not built"
+L21S_SHARDED = ("the stacked l2,1 ball (l21_stacked) takes single-process contexts only, this one has a communicator, a slab "
+                "decomposition or set ownership: its groups span the blocks of a caller-supplied operator -- use a single process")
+L21S_NO_COARSE = ("multilevel: the stacked l2,1 ball (l21_stacked, (\"l21\", \"Hessian\")) is not built for PARSDMM_multi_level: "
+                  "solve on one level")
+HESSIAN_SMALL_GRID = ("the Hessian operator needs at least 3 grid points along every dimension (a second difference has three "
+                      "points), this grid is {n}")
+
+
+def l21s_bad_blocks(B):
+    return (f"the stacked l2,1 ball (l21_stacked): blocks = {B}, the number of equal-sized blocks of the operator must be 1 .. "
+            f"{L21S_MAX_BLOCKS}")
+
+
+def l21s_bad_rows(M, B):
+    return (f"the stacked l2,1 ball (l21_stacked): the operator has M = {M} rows, not a multiple of blocks = {B} -- every block needs "
+            "the same number of rows (pad a shorter block with zero rows)")
+
+
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
 TV_XY_NEEDS_3D = UNKNOWN_OPERATOR + " (TV_xy is the in-plane gradient of a 3-D grid; on a 2-D grid TV is in-plane already)"
 TV_XY_NO_MINKOWSKI = "the TV_xy operator takes no Minkowski component"
@@ -180,6 +209,7 @@ SPECIAL_OPERATORS = ("DFT", "DCT", "wavelet", "curvelet")     # src/setup_constr
 YL_FEAS, YL_BB, YL_FIRST = 1, 2, 4
 Q_MODES = {"cds": 0, "stencil": 1}
 MAX_Q_BANDS = 32        # bands the engine keeps of Q in CDS form (MAXD, csrc/sipx_common.h)
+MAX_SET_BANDS = 9       # bands of A'A one set may hand over (csrc/set_config.h, configure_set)
 
 
 class SipxError(RuntimeError):
@@ -192,7 +222,7 @@ class _SetDesc(C.Structure):
                 ("mode", C.c_int32), ("dir", C.c_int32), ("basis", C.c_void_p), ("basis_rows", C.c_int64),
                 ("basis_cols", C.c_int32), ("basis_orth", C.c_int32), ("component", C.c_int32),
                 ("csc_colptr", C.c_void_p), ("csc_rowval", C.c_void_p), ("csc_nzval", C.c_void_p), ("csc_rows", C.c_int64),
-                ("transform", C.c_int32), ("pad_", C.c_int32)]
+                ("transform", C.c_int32), ("pad_", C.c_int32), ("blocks", C.c_int32), ("pad2_", C.c_int32)]
 
 
 class _Options(C.Structure):
@@ -317,6 +347,8 @@ class set_definitions:
     weights: Any = None      # the l2,1 sets on the whole array: one weight >= 0 per group (csrc/l21_weighted.h), None: the plain ball;
                              # l21_groups: one per fiber / slice, in the order of segment_norms (csrc/l21_groups.h);
                              # l1_weighted: one per row of the operator, in the order of A @ x (csrc/l1_weighted.h), required
+    blocks: Any = None       # l21_stacked: B, the number of equal-sized blocks of the stacked operator (csrc/l21_stacked.h), 1 .. 8;
+                             # None: that of the named operator ("Hessian": 3 on a 2-D grid, 6 on a 3-D one)
 
 
 @dataclass
@@ -492,6 +524,8 @@ class Projector:
         self.pmin = self.pmax = 0.0
         self.transform = 0
         self.weighted = False        # an l2,1 set built with one weight per group (in lb)
+        self.blocks = 0              # l21_stacked: the equal-sized blocks of the operator the groups run across
+        self.rows = None             # l21_stacked: the rows M of that operator, the length of the vector a stand-alone call projects
         if st == "tnv":
             # total nuclear variation: the Jacobians of the pixels across the frames of TV_xy (csrc/tnv.h); max is the radius
             cust = constraint.custom_TD_OP[0]
@@ -651,6 +685,43 @@ class Projector:
                 self.pmax = float(max(ks)) if ks else 1.0
             else:
                 self.pmax = _check_l20_k(constraint.max, ngroups, self.TF)
+            return
+        if st == "l21_stacked" or (st == "l21" and constraint.TD_OP == "Hessian"):
+            # the l2,1 ball across the blocks of a stacked operator (csrc/l21_stacked.h); ("l21", "Hessian"): second-order isotropic TV
+            cust = constraint.custom_TD_OP[0]
+            has_cust = not (isinstance(cust, (tuple, list)) and len(cust) == 0)
+            if getattr(constraint, "weights", None) is not None or np.ndim(constraint.max) != 0 or np.ndim(constraint.min) != 0:
+                raise SipxError(L21S_NO_VECTORS)
+            if constraint.TD_OP in SPECIAL_OPERATORS:
+                raise SipxError(L21S_NO_TRANSFORM)
+            if st == "l21" and has_cust:
+                raise SipxError(L21_NEEDS_TV)
+            if not has_cust and constraint.TD_OP != "Hessian":
+                raise SipxError(L21S_NEEDS_CSC)
+            if self.mode:
+                raise SipxError(L21S_WHOLE_ONLY)
+            B = getattr(constraint, "blocks", None)
+            if has_cust:
+                if B is None:
+                    raise SipxError("the stacked l2,1 ball (l21_stacked) on a caller-supplied operator needs blocks, the number of its "
+                                    "equal-sized blocks")
+                M = int(cust.shape[0])
+            else:
+                _hessian_check_grid(n)
+                nb = len(n) * (len(n) + 1) // 2
+                if B is not None and int(B) != nb:
+                    raise SipxError(f"the Hessian of this grid has {nb} blocks, blocks = {B} was given (leave it None)")
+                B, M = nb, nb * int(np.prod(n))
+            if isinstance(B, (float, np.floating)) and B != int(B):
+                raise SipxError(l21s_bad_blocks(B))
+            B = int(B)
+            if B < 1 or B > L21S_MAX_BLOCKS:
+                raise SipxError(l21s_bad_blocks(B))
+            if M % B:
+                raise SipxError(l21s_bad_rows(M, B))
+            if not float(constraint.max) > 0:
+                raise SipxError("Radius of L1 ball is negative")
+            self.kind, self.pmax, self.op, self.blocks, self.rows = "l21_stacked", float(constraint.max), "custom", B, M
             return
         if st == "l21_joint":
             # joint (vectorial) total variation: one group per pixel across the frames of TV_xy (csrc/l21_joint.h); max is the radius
@@ -884,6 +955,15 @@ class Projector:
                 raise SipxError(SIMPLEX_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
             if getattr(op, "component", 0):
                 raise SipxError(SIMPLEX_NO_MINKOWSKI)
+        if self.kind == "l21_stacked":
+            if op.kind != "custom":
+                raise SipxError(L21S_NEEDS_CSC)
+            if getattr(op, "component", 0):
+                raise SipxError(L21S_NO_MINKOWSKI)
+            if self.blocks < 1 or self.blocks > L21S_MAX_BLOCKS:
+                raise SipxError(l21s_bad_blocks(self.blocks))
+            if int(op.shape[0]) % self.blocks:
+                raise SipxError(l21s_bad_rows(int(op.shape[0]), self.blocks))
         if self.kind == "l1_weighted":
             if op.kind == "custom":
                 raise SipxError(L1W_NO_CUSTOM)
@@ -948,6 +1028,7 @@ class Projector:
         d.ncvx, d.reserved = int(bool(ncvx)), (int(self.lb.shape[0]) if self.weighted else 0)
         d.mode, d.dir = self.mode, self.dir
         d.transform = self.transform
+        d.blocks = self.blocks
         if self.basis is not None:
             d.basis, d.basis_rows, d.basis_cols = _ptr(self.basis), self.basis.shape[0], self.basis.shape[1]
             d.basis_orth = int(self.basis_orth)
@@ -960,6 +1041,16 @@ class Projector:
                                                                               "subspace", "l21", "l21_joint", "l21_groups", "tnv", "l1_weighted",
                                                                               "simplex", "card_groups", "l20", "l20_joint")
         l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint")
+        if self.kind == "l21_stacked":      # the M-vector of the stacked operator's range itself: blocks blocks of M / blocks entries
+            if v.shape != (self.rows,):
+                raise SipxError(f"the stacked l2,1 ball projects a vector of the operator's range: {self.rows} entries, {v.size} given")
+            ctx = Context(self.comp_grid, self.TF)
+            try:
+                d = self.desc("custom", False)
+                _chk(lib().sipx_project(ctx.h, C.byref(d), _ptr(v), C.c_int64(len(v))))
+            finally:
+                ctx.close()
+            return v
         if l21:                      # the M-vector of the TV range (l21_groups: of its operator's) in the reference's row order, on the grid
             op = TDOperator(self.op, self.comp_grid, self.TF)
             rows = op.shape[0]
@@ -1008,6 +1099,8 @@ def get_TD_operator(comp_grid, TD_type: str, TF):
         Dx = sp.kron(sp.identity(n2, dtype=TFt, format="csc"), fwd(n1, h[0]), format="csc")            # on (n1, n2)
         Dz = sp.kron(fwd(n2, h[1]), sp.identity(n1 - 1, dtype=TFt, format="csc"), format="csc")        # on (n1-1, n2)
         return CustomOperator((Dz @ Dx).astype(TFt), comp_grid, TF), False, False, (n1 - 1, n2 - 1), True
+    if TD_type == "Hessian":
+        return hessian_operator(comp_grid, TF), False, False, n, True
     if TD_type == "TV_xy" and len(n) != 3:
         raise SipxError(TV_XY_NEEDS_3D)
     A = TDOperator(TD_type, comp_grid, TF)
@@ -1023,6 +1116,52 @@ def get_TD_operator(comp_grid, TD_type: str, TF):
                 "D_z": (n1, n2, n3 - 1), "D_y": (n1, n2 - 1, n3), "D_x": (n1 - 1, n2, n3),
                 "TV_xy": (2 * n1 - 1, 2 * n2 - 1, n3)}[TD_type]      # (bookkeeping only, as the TV entries are)
     return A, False, False, TD_n, True
+
+
+def _hessian_check_grid(n):
+    if len(n) not in (2, 3) or min(n) < 3:
+        raise SipxError(HESSIAN_SMALL_GRID.format(n=tuple(n)))
+
+
+def hessian_operator(comp_grid, TF):
+    """The named operator "Hessian" (csrc/l21_stacked.h): a CustomOperator of B N rows, B = 3 on a 2-D grid (D_11, D_22, sqrt(2) D_12)
+    and 6 on a 3-D one (D_11, D_22, D_33, sqrt(2) D_12, sqrt(2) D_13, sqrt(2) D_23); row q N + p is entry q of the Hessian at grid
+    point p, a zero row where the stencil leaves the grid.  Assembled in TF from the forward-difference factors -+fl(1/h) of D_xz:
+    D_aa = the product of two of them, (x[i-1] - 2 x[i] + x[i+1]) ih_a^2 centred at 1 <= i <= n_a - 2; D_ab = the forward difference
+    along a of the forward difference along b that starts at p (the reference's D_z * D_x), scaled by fl(sqrt(2)) so that the group
+    norm is the Frobenius norm of the symmetric Hessian."""
+    import scipy.sparse as sp
+    n, h = _grid(comp_grid)
+    _hessian_check_grid(n)
+    TFt = np.dtype(TF).type
+    nd = len(n)
+
+    def fwd(k, hk):       # (k-1) x k forward difference with entries -+fl(1/h)   (get_discrete_Grad.jl:22-23)
+        ih = TFt(1) / TFt(hk)
+        return sp.diags([np.full(k - 1, -ih, TFt), np.full(k - 1, ih, TFt)], [0, 1], shape=(k - 1, k), dtype=TFt, format="csc")
+
+    def rows_into(k, first, count):      # k x count: row first + i takes row i (the other rows stay empty)
+        return sp.csc_matrix((np.ones(count, TFt), (np.arange(count) + first, np.arange(count))), shape=(k, count), dtype=TFt)
+
+    def along(factors):      # the operator on the grid from one k x k factor per axis (column-major: axis 0 fastest)
+        out = factors[0]
+        for f in factors[1:]:
+            out = sp.kron(f, out, format="csc")
+        return out.astype(TFt)
+    eye = [sp.identity(k, dtype=TFt, format="csc") for k in n]
+    first = [(rows_into(k, 0, k - 1) @ fwd(k, hk)).astype(TFt) for k, hk in zip(n, h)]               # starts at i, empty last row
+    second = [(rows_into(k, 1, k - 2) @ (fwd(k - 1, hk) @ fwd(k, hk))).astype(TFt) for k, hk in zip(n, h)]   # centred at i, empty first and last row
+    blocks = [along([second[c] if c == a else eye[c] for c in range(nd)]) for a in range(nd)]
+    r2 = TFt(np.sqrt(TFt(2)))
+    for a in range(nd):
+        for b in range(a + 1, nd):
+            D = along([first[c] if c in (a, b) else eye[c] for c in range(nd)])
+            blocks.append((D * r2).astype(TFt))
+    H = sp.vstack(blocks, format="csc", dtype=TFt)
+    H.eliminate_zeros()
+    op = CustomOperator(H, comp_grid, TF)
+    op.named = "Hessian"
+    return op
 
 
 def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_norms=False):
@@ -1087,7 +1226,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.max = np.asarray(c.max, TF)
         if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
             c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
-        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint"):
+        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint", "l21_stacked"):
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -1100,8 +1239,9 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             cust0 = c.custom_TD_OP[0]
             if c.TD_OP in ("TV", "D2D", "D3D", "D_xz", "TV_xy") or not (isinstance(cust0, (tuple, list)) and len(cust0) == 0):
                 raise SipxError("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)")
-        A, AtA_diag, dense, TD_n, banded = get_TD_operator(comp_grid, c.TD_OP, TF)
         cust = c.custom_TD_OP[0] if c.set_type != "subspace" else ()
+        named = "identity" if c.set_type == "l21_stacked" and not (isinstance(cust, (tuple, list)) and len(cust) == 0) else c.TD_OP
+        A, AtA_diag, dense, TD_n, banded = get_TD_operator(comp_grid, named, TF)      # (l21_stacked: the name of a caller-supplied operator is free)
         if not (isinstance(cust, (tuple, list)) and len(cust) == 0):          # setup_constraints.jl:70-72
             A = CustomOperator(cust, comp_grid, TF)
             AtA_diag, dense = False, False
@@ -1126,8 +1266,8 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
 def PARSDMM_precompute_distribute(TD_OP, set_Prop, comp_grid, options):
     """src/PARSDMM_precompute_distribute.jl:6-77.  AtA[i] = None means "generate the CDS bands of
     A_i'A_i on the device from the descriptor" (bit-identical to mat2CDS(TD_OP'*TD_OP)).
-    A custom operator whose set is marked set_Prop.banded[i] = False, or whose A'A has more diagonals than the engine keeps
-    bands (MAX_Q_BANDS), gets AtA[i] = None and empty AtA_offsets[i] too: the engine applies it as a matrix-free term of Q,
+    A custom operator whose set is marked set_Prop.banded[i] = False, or whose A'A has more diagonals than one set hands over
+    (MAX_SET_BANDS), gets AtA[i] = None and empty AtA_offsets[i] too: the engine applies it as a matrix-free term of Q,
     the reference's sparse Q of a set that is not banded (PARSDMM_precompute_distribute.jl:51-59, argmin_x.jl:42-51)."""
     TF = np.dtype(options.FL).type
     n, _ = _grid(comp_grid)
@@ -1143,7 +1283,8 @@ def PARSDMM_precompute_distribute(TD_OP, set_Prop, comp_grid, options):
     for i in range(p):
         kind = TD_OP[i].kind
         if kind == "custom":
-            if not set_Prop.banded[i] or TD_OP[i].ata_diagonals() > MAX_Q_BANDS:
+            # (more diagonals than one set hands over, as the named "Hessian" has with 13 / 25: the operator enters Q matrix-free)
+            if not set_Prop.banded[i] or TD_OP[i].ata_diagonals() > min(MAX_SET_BANDS, MAX_Q_BANDS):
                 AtA[i], set_Prop.AtA_offsets[i] = None, np.zeros(0, np.int64)
             else:
                 AtA[i], set_Prop.AtA_offsets[i] = TD_OP[i].ata_cds()
@@ -2329,6 +2470,32 @@ def _l21_observe(name, x, comp_grid, needs_3d, per_frame, fn, before, after, wei
     finally:
         ctx.close()
     return out, on_dev
+
+
+def l21_stacked_norm(x, comp_grid, TD_OP, blocks=None):
+    """sum_p ||(A x)_p||_2 over the groups of the stacked l2,1 ball (csrc/l21_stacked.h), one number of the working precision (that of
+    x): TD_OP = "Hessian" gives sum_p ||H x(p)||_F, the second-order total variation of x (blocks: None); TD_OP a sparse matrix with
+    N columns and M rows gives the norm of the ("l21_stacked", ...) set on it, blocks = B its equal-sized blocks.  Computed by the
+    engine's sparse product, the norms kernel and the first-pass sum of the projector (sipx_l21_stacked_norm): used as the radius it
+    leaves A x untouched.  x: a numpy vector (a numpy scalar comes back) or a 1-D torch tensor on a GPU (a tensor of one entry there;
+    nothing of x crosses PCIe, the call orders itself against torch's current stream)."""
+    TF = _tensor_TF("x", x) if _is_tensor(x) else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("l21_stacked_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    named = isinstance(TD_OP, str)
+    if named and TD_OP != "Hessian":
+        raise SipxError(L21S_NEEDS_CSC)
+    c = set_definitions("l21_stacked", "Hessian" if named else "custom", 0.0, 1.0, ("matrix", ""),
+                        custom_TD_OP=((), False) if named else (TD_OP, False), blocks=blocks)
+    P = Projector(c, comp_grid, TF)
+    op = hessian_operator(comp_grid, TF) if named else CustomOperator(TD_OP, comp_grid, TF)
+    P.check_rows(op)
+    d = P.desc("custom", False)
+    cp = np.ascontiguousarray(op.A.indptr, np.int64); ri = np.ascontiguousarray(op.A.indices, np.int64)
+    nz = np.ascontiguousarray(op.A.data, TF)
+    d.csc_colptr, d.csc_rowval, d.csc_nzval, d.csc_rows = cp.ctypes.data, ri.ctypes.data, nz.ctypes.data, int(op.A.shape[0])
+    out, on_dev = _l21_observe("l21_stacked_norm", x, comp_grid, False, False, "sipx_l21_stacked_norm", (C.byref(d),), ())
+    return out if on_dev else out[0]
 
 
 def l21_norm(x, comp_grid, TD_OP: str = "TV", app_mode=None, weights=None):
