@@ -250,7 +250,27 @@ enum {
                                 bits.  Both forms of Q work: ata_R with up to 9 bands, or ata_R = NULL, the matrix-free term (the
                                 Hessian's A'A has 13 / 25 bands: it enters matrix-free).  Contexts with a communicator, a slab
                                 decomposition or set ownership are refused.  sipx_project takes the M-vector itself (len = M entries,
-                                `blocks` set; op and the CSC arrays are not looked at); sipx_l21_stacked_norm observes the norm */
+                                `blocks` set; op and the CSC arrays are not looked at); sipx_l21_stacked_norm observes the norm */,
+  SIPX_PROJ_L2INF = 24 /* the l2,inf ball on the gradient (csrc/l2inf.h): { v = TV x : ||v_p||_2 <= c_p at every grid point p }, an isotropic
+                          slope bound, the group of p being that of SIPX_PROJ_L21.  op TV or TV_XY, mode WHOLE, no transform, no component,
+                          pmin = 0, lb = NULL, ncvx = 0.  c is pmax > 0 (ub = NULL, reserved = 0), or ub = TF[N] bounds >= 0 in grid-point
+                          order (that of sipx_tv_group_norms) with reserved = N: +inf leaves a point free, 0 flattens it, the entry of a
+                          point without a member is not looked at; sipx_set_data replaces ub in a live context.  CONTRACT: g_p is the
+                          group norm SIPX_PROJ_L21 forms, bit for bit; where g_p <= c_p in TF the group keeps its bits (-0.0 included),
+                          otherwise every member is multiplied by c_p / g_p, quotient and products in TF; rows a block does not have are
+                          never written; no search, no state between calls, no floating-point atomics: two calls give the same bits.
+                          The norm observed on the output exceeds c_p by at most 4 (Float32) or m + 4 (Float64, m members) units of
+                          (eps / 2) c_p (the derivation: csrc/l2inf.h).  Contexts with a communicator, a slab decomposition or set
+                          ownership are refused.  sipx_project takes the M-vector of the operator's range in the reference's row order;
+                          sipx_l2inf_norm observes max_p g_p */,
+  SIPX_PROJ_L2INF_JOINT = 25 /* the joint l2,inf ball: the same with the group of a pixel (i, j) that of SIPX_PROJ_L21_JOINT -- its in-plane
+                                differences in all frames, g from that set's z-march bit for bit.  op TV_XY, mode WHOLE only; c is pmax or
+                                ub = TF[n1 n2] in pixel order with reserved = n1 n2; the rest as SIPX_PROJ_L2INF */,
+  SIPX_PROJ_L2INF_STACKED = 26 /* the l2,inf ball across the equal-sized blocks of a caller-supplied stacked operator: the groups, `blocks`
+                                  and the limits of SIPX_PROJ_L21_STACKED (on the Hessian a pointwise curvature bound ||H x(p)||_F <= c_p).
+                                  op SIPX_OP_CSC, mode WHOLE; c is pmax or ub = TF[G], G = M / blocks, with reserved = G; the rest as
+                                  SIPX_PROJ_L2INF.  sipx_project takes the M-vector itself (len = M entries, `blocks` set; op and the CSC
+                                  arrays are not looked at) */
 };
 /* constraint.app_mode (set_definitions): ("matrix"|"tensor", _) = WHOLE, ("fiber", d), ("slice", d).
  * dir is the 0-based array dimension: "x" = 0, "y" = 1, "z" = 2 on a 3-D grid, "z" = 1 on a 2-D grid. */
@@ -278,7 +298,8 @@ typedef struct {
   const void* ub;
   int32_t ncvx;      /* set_Prop.ncvx[i] (src/setup_constraints.jl:89-97) */
   int32_t reserved;  /* 0; a weighted L21 / L21_JOINT / L21_GROUPS set: the entries of lb, refused unless it is the group count;
-                        L1_WEIGHTED: the rows of the operator (Mtrue), refused otherwise */
+                        L1_WEIGHTED: the rows of the operator (Mtrue), refused otherwise; the L2INF kinds with ub: the entries of ub,
+                        refused unless it is the group count */
   int32_t mode;      /* SIPX_MODE_* */
   int32_t dir;       /* direction of the fibers / normal of the slices */
   const void* basis; /* SUBSPACE: host TF[basis_rows x basis_cols], column-major (constraint.custom_TD_OP[1]) */
@@ -555,6 +576,14 @@ int sipx_l21_norms_dev(sipx_ctx* ctx, int op, int mode, int dir, const void* x, 
  * context's GPU, ordered like sipx_l21_norm_dev against the caller's stream.  Refused where the set is refused. */
 int sipx_l21_stacked_norm(sipx_ctx* ctx, const sipx_set_desc* d, const void* x, void* out);
 int sipx_l21_stacked_norm_dev(sipx_ctx* ctx, const sipx_set_desc* d, const void* x, void* out);
+/* The largest group norm of the SIPX_PROJ_L2INF kinds: *out = one TF, max_p g_p of A x, x TF[N] on the grid of the context (which needs no
+ * sets and no finalize).  The descriptor d names the set: proj SIPX_PROJ_L2INF with op TV or TV_XY, SIPX_PROJ_L2INF_JOINT with op TV_XY, or
+ * SIPX_PROJ_L2INF_STACKED with op SIPX_OP_CSC, its csc_* arrays and blocks; pmin, pmax, lb, ub and reserved are not looked at.  The norms
+ * come from the norms launch of the projector (the arithmetic of its clip kernels), the maximum from a two-stage reduction in a fixed
+ * order.  CONTRACT: a set built with the value as its scalar bound leaves A x unwritten.  x, out: host memory; the _dev form takes both
+ * in device memory of the context's GPU, ordered like sipx_l21_norm_dev against the caller's stream.  Refused where the set is refused. */
+int sipx_l2inf_norm(sipx_ctx* ctx, const sipx_set_desc* d, const void* x, void* out);
+int sipx_l2inf_norm_dev(sipx_ctx* ctx, const sipx_set_desc* d, const void* x, void* out);
 /* The joint total variation of the frames of x: *out = one TF, the sum over the pixels (i, j) of the group norms g_ij of SIPX_PROJ_L21_JOINT
  * on [D_y; D_x] x, x TF[N] on the 3-D grid of the context.  The norms come from the z-march of the projector, the sum from the first
  * pass of its threshold search.  CONTRACT: the value is the very number the projector compares with pmax, so a radius observed on x

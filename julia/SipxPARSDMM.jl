@@ -84,6 +84,12 @@ const SIPX_PROJ_L20_JOINT = 22
 # With A the Hessian of the grid (D_11, D_22[, D_33], sqrt(2) D_12[, sqrt(2) D_13, sqrt(2) D_23], each zero-padded to N rows) this is
 # second-order isotropic TV; the Python front end assembles that operator under the name "Hessian".
 const SIPX_PROJ_L21_STACKED = 23
+# the l2,inf ball: every group norm of TV / TV_xy (l2inf), of the pixels of TV_xy across the frames (l2inf_joint) or across the blocks of
+# a stacked operator (l2inf_stacked) at most max (include/sipx.h, csrc/l2inf.h), set_type = "l2inf" / "l2inf_joint"; min must be 0, max is
+# one positive number or a vector with one bound >= 0 per group (it travels in ub, its length in the descriptor's `reserved`)
+const SIPX_PROJ_L2INF = 24
+const SIPX_PROJ_L2INF_JOINT = 25
+const SIPX_PROJ_L2INF_STACKED = 26
 const MODE = Dict("matrix" => 0, "tensor" => 0, "fiber" => 1, "slice" => 2)
 const SPECIAL = ("DFT", "DCT", "wavelet", "curvelet")          # src/setup_constraints.jl:54
 # the seven @timeit sections of src/PARSDMM.jl:40,100,105,113,152,163,229
@@ -211,6 +217,21 @@ function projector_fields(c, TF)
         c.max > 0 || error("Radius of L1 ball is negative")
         return (SIPX_PROJ_L21_STACKED, 0.0, Float64(c.max), nothing_[3:5]...)
     end
+    if st == "l2inf" || st == "l2inf_joint"
+        joint = st == "l2inf_joint"
+        c.custom_TD_OP[1] == [] && (joint ? op == "TV_xy" : op in ("TV", "D2D", "D3D", "TV_xy")) ||
+            error(joint ? "the joint l2,inf ball (l2inf_joint) groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor -- per frame bounds are (\"l2inf\", \"TV_xy\")" :
+                          "the l2,inf ball (l2inf) bounds the gradient magnitude at every grid point: TD_OP must be TV (D2D, D3D), TV_xy or the named \"Hessian\" -- a bound on one difference direction is (\"bounds\", \"D_z\"), a caller-supplied stacked operator takes (\"l2inf_stacked\", name, 0, c, mode, custom_TD_OP=(A, False), blocks=B)")
+        c.app_mode[1] in ("matrix", "tensor") ||
+            error("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) applies to the whole array (matrix / tensor mode), fibers and slices are not built: (\"slice\", \"z\") on TV_xy is the vector form with c constant within every frame -- pass max = np.repeat(c_frames, n1 * n2)")
+        (c.min isa Real && c.min == 0) ||
+            error("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) bounds the group norms from above only: min must be 0 -- a lower bound on the gradient magnitude is not convex and not built")
+        kind = joint ? SIPX_PROJ_L2INF_JOINT : SIPX_PROJ_L2INF
+        c.max isa AbstractVector && return (kind, 0.0, 1.0, nothing, convert(Vector{TF}, c.max), Int32(0))      # (checked by libsipx: length, entries >= 0)
+        c.max > 0 || error("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) needs a bound c > 0 as a scalar (c = 0 is the constant array: use bounds on TV, or a vector of zeros to flatten chosen points)")
+        return (kind, 0.0, Float64(c.max), nothing_[3:5]...)
+    end
+    st == "l2inf_stacked" && error("the stacked l2,inf ball (l2inf_stacked, SIPX_PROJ_L2INF_STACKED) is not built in this binding: the reference's set_definitions has no field for the number of blocks and min must stay 0 -- use the C ABI or the Python front end")
     st == "simplex" && error("simplex sets (simplex, SIPX_PROJ_SIMPLEX) are not built in this binding yet: use (\"bounds\") together with (\"l1\", op, mode) and segment_norms=true, or the C ABI")
     st == "l1"          && return (2, 0.0, Float64(c.max), nothing_[3:5]...)
     st == "l2"          && return (3, 0.0, Float64(c.max), nothing_[3:5]...)
@@ -450,7 +471,8 @@ function PARSDMM(m         ::Vector{TF},
             push!(keep, (lb, ub, basis, colptr, rowval, nzval))
             d = SipxSetDesc(opcode, kind, pmin, pmax,
                             lb === nothing ? C_NULL : pointer(lb), ub === nothing ? C_NULL : pointer(ub),
-                            set_Prop.ncvx[i] ? 1 : 0, 0,
+                            set_Prop.ncvx[i] ? 1 : 0,
+                            (kind in (SIPX_PROJ_L2INF, SIPX_PROJ_L2INF_JOINT) && ub !== nothing) ? Int32(length(ub)) : Int32(0),   # reserved: the entries of an l2inf ub
                             MODE[c.app_mode[1]], dir_of(c.app_mode[2], ndim),
                             basis === nothing ? C_NULL : pointer(basis), basis === nothing ? 0 : size(basis, 1),
                             basis === nothing ? 0 : size(basis, 2), basis === nothing ? 0 : Int32(c.custom_TD_OP[2]),

@@ -176,6 +176,12 @@ int sipx_l21_stacked_norm(sipx_ctx* c, const sipx_set_desc* d, const void* x, vo
 int sipx_l21_stacked_norm_dev(sipx_ctx* c, const sipx_set_desc* d, const void* x, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_stacked_norm(d, x, out, true))
 }
+int sipx_l2inf_norm(sipx_ctx* c, const sipx_set_desc* d, const void* x, void* out) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l2inf_norm(d, x, out, false))
+}
+int sipx_l2inf_norm_dev(sipx_ctx* c, const sipx_set_desc* d, const void* x, void* out) {
+  SIPX_TRY(sipx::refresh_env_knobs(); c->e->l2inf_norm(d, x, out, true))
+}
 int sipx_l21_joint_norm(sipx_ctx* c, const void* x, void* out) {
   SIPX_TRY(sipx::refresh_env_knobs(); c->e->l21_norms(SIPX_PROJ_L21_JOINT, SIPX_OP_TV_XY, SIPX_MODE_WHOLE, 0, x, out, nullptr, false, false))
 }

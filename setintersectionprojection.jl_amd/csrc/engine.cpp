@@ -391,6 +391,7 @@ class Engine : public EngineBase {
       if (s.ext_kind == EXT_CARD_GROUPS) refuse_sharded(ctx, Sharded::CARD_GROUPS);
       if (s.ext_kind == EXT_L20 || s.ext_kind == EXT_L20_SEG || s.ext_kind == EXT_L20_JOINT) refuse_sharded(ctx, Sharded::L20);
       if (s.ext_kind == EXT_L21_STACKED) refuse_sharded(ctx, Sharded::L21_STACKED);
+      if (is_l2inf(s.ext_kind)) refuse_sharded(ctx, Sharded::L2INF);
     }
     FinalizePlan P;
     plan_sets();
@@ -2949,6 +2950,8 @@ class Engine : public EngineBase {
     if (s.ext_kind == EXT_L20 || s.ext_kind == EXT_L20_JOINT || (s.ext_kind == EXT_L20_SEG && !s.seg_radii))
       throw std::runtime_error(what + ": " + L20_NO_SET_DATA);
     if (s.ext_kind == EXT_L20_SEG && lb) throw std::runtime_error(what + ": " + L20_SET_DATA_UB);
+    if (is_l2inf(s.ext_kind) && lb) throw std::runtime_error(what + ": " + L2INF_NO_WEIGHTS);
+    if (is_l2inf(s.ext_kind) && !s.seg_radii) throw std::runtime_error(what + ": " + L2INF_NO_SET_DATA);
     const bool bounds = !s.ext_kind && s.prox == SIPX_PROJ_BOUNDS_VEC, hist = s.ext_kind == EXT_HISTOGRAM || s.seg_radii || s.weighted;
     if (!bounds && !hist)
       throw std::runtime_error(what + ": set " + std::to_string(set) + " holds no replaceable vectors -- element-wise and per-fiber bounds "
@@ -2966,6 +2969,10 @@ class Engine : public EngineBase {
     else if (s.weighted && lb && !on_device) check_l21_weights((const T*)lb, len, s.ext_kind == EXT_L21_JOINT ? "l21_joint" : (s.ext_kind == EXT_L21_GROUPS ? "l21_groups" : "l21"));
     if (s.seg_radii && (s.ext_kind == EXT_L1_SEG || s.ext_kind == EXT_L21_SEG) && ub && !on_device) check_l1_radii((const T*)ub, len);
     if (s.ext_kind == EXT_L20_SEG && ub && !on_device) l20_check_k_vector<T>((const T*)ub, len, G_.n[0] * G_.n[1]);
+    if (is_l2inf(s.ext_kind) && ub && !on_device) {
+      const long long per = s.ext_kind == EXT_L2INF && s.op == SIPX_OP_TV_XY ? G_.st[2] : len;
+      l2inf_check_vector<T>((const T*)ub, len, [&](long long p) { return s.ext_kind == EXT_L2INF_STACKED || p % per != per - 1; });
+    }
     if (bounds && s.bmode == SIPX_MODE_FIBER && s.custom)
       throw std::runtime_error(what + ": per-fiber bounds need one of the built-in operators" + way_out);
     if (!lb && !ub) return;
@@ -3695,6 +3702,107 @@ class Engine : public EngineBase {
     }
   }
 
+  // the SIPX_PROJ_L2INF kinds of sipx_project (l2inf.h): the M-vector of the TV / TV_xy range in the reference's row order, or for the
+  // stacked set the M-vector itself, d->blocks blocks of len / blocks entries (the operator of the descriptor is not looked at)
+  void project_l2inf(const sipx_set_desc* d, void* v, int64_t len) {
+    const ConfigCtx ctx = config_ctx();
+    if (d->proj == SIPX_PROJ_L2INF_STACKED) {
+      if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(L2INF_NO_TRANSFORM);
+      if (d->component) throw std::runtime_error(L2INF_NO_MINKOWSKI);
+      if (d->mode != SIPX_MODE_WHOLE) throw std::runtime_error(L2INF_MODES);
+      if (d->pmin != 0) throw std::runtime_error(L2INF_MIN);
+      if (d->lb) throw std::runtime_error(L2INF_NO_WEIGHTS);
+      const long long G = l2infs_check_shape(len, d->blocks);
+      refuse_sharded(ctx, Sharded::L2INF);
+      if (d->ub) {
+        if (d->reserved != G) throw std::runtime_error(l2inf_bad_length(d->reserved, G));
+        l2inf_check_vector<T>((const T*)d->ub, G, [](long long) { return true; });
+      } else {
+        l2inf_check_c(d->pmax);
+      }
+      ExtSpec sp;
+      l21s_spec(sp, len, d->blocks);
+      sp.kind = EXT_L2INF_STACKED;
+      sp.pmax = d->pmax;
+      sp.ub = d->ub;
+      DeviceMemory tmp;
+      T* dv = tmp.alloc<T>(len);
+      SIPX_HIP(hipMemcpy(dv, v, len * sizeof(T), hipMemcpyHostToDevice));
+      {
+        ExtProj<T> ext(sp, stream_);
+        ext.project(dv, false, nullptr, nullptr, nullptr);
+        finish_call(false, v, dv, len);
+      }
+      return;
+    }
+    if (d->proj == SIPX_PROJ_L2INF_JOINT && d->op != SIPX_OP_TV_XY) throw std::runtime_error(L2INF_JOINT_ROUTE);
+    if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY) throw std::runtime_error(L2INF_NEEDS_TV);
+    SetConfig<T> st;
+    configure_op(ctx, st, d->op);
+    if (d->op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
+    configure_proj(ctx, st, d);
+    if (len != st.Mtrue)
+      throw std::runtime_error(std::string("the l2,inf ball projects a vector of the ") + (d->op == SIPX_OP_TV ? "TV" : "TV_xy") + " range: " +
+                               std::to_string(st.Mtrue) + " entries on this grid, " + std::to_string((long long)len) + " given");
+    st.spec.ub = st.host_ub.empty() ? nullptr : st.host_ub.data();      // (one bound per group)
+    DeviceMemory tmp;
+    T* dv = tmp.alloc<T>(st.Mpad);               // (zeroed: the rows a block does not have)
+    upload_rows(st, (const T*)v, dv);
+    {
+      ExtProj<T> ext(st.spec, stream_);
+      ext.project(dv, false, nullptr, nullptr, nullptr);
+      download_rows(st, dv, (T*)v);               // (synchronises the stream)
+    }
+  }
+
+  // sipx_l2inf_norm(_dev): max_p g_p of A x for the SIPX_PROJ_L2INF kind the descriptor names, by the observe() of a throw-away projector
+  // of that set (ext_group.hip, L2InfProj): the norms launch whose arithmetic its clip kernels repeat, and the two-stage maximum
+  void l2inf_norm(const sipx_set_desc* d, const void* x, void* out, bool on_device) override {
+    if (!d || !x || !out) throw std::runtime_error("l2,inf norm: the descriptor, x and out are needed");
+    SIPX_HIP(hipSetDevice(device_));
+    if (d->proj != SIPX_PROJ_L2INF && d->proj != SIPX_PROJ_L2INF_JOINT && d->proj != SIPX_PROJ_L2INF_STACKED)
+      throw std::runtime_error("l2,inf norm: the descriptor's proj must be SIPX_PROJ_L2INF, SIPX_PROJ_L2INF_JOINT or SIPX_PROJ_L2INF_STACKED");
+    const ConfigCtx ctx = config_ctx();
+    sipx_set_desc dd = *d;
+    dd.pmin = 0.0; dd.pmax = 1.0; dd.ncvx = 0; dd.lb = dd.ub = nullptr; dd.reserved = 0;
+    DeviceMemory tmp;
+    T* dout = on_device ? (T*)out : tmp.alloc<T>(1);
+    if (d->proj == SIPX_PROJ_L2INF_STACKED) {
+      if (d->op != SIPX_OP_CSC) throw std::runtime_error(L2INF_STACKED_NEEDS_CSC);
+      SetState<T> s;
+      configure_custom(ctx, s, d);
+      configure_proj(ctx, s, &dd);               // the refusals, and the ExtSpec, of the set
+      upload_custom(s, tmp);
+      T* dx = on_device ? nullptr : tmp.alloc<T>(G_.N);
+      ExtProj<T> ext(s.spec, stream_);
+      if (on_device) engine_after_caller();
+      else SIPX_HIP(hipMemcpyAsync(dx, x, G_.N * sizeof(T), hipMemcpyHostToDevice, stream_));
+      custom_fwd(stream_, s, on_device ? (const T*)x : dx, s.sbuf);
+      {
+        ObserverGuard og(observer());
+        ObsScope obs(KID_EXT, stream_, (double)(s.spec.nblk + 2) * s.spec.bstride * sizeof(T));
+        ext.observe(s.sbuf, dout, nullptr, nullptr, nullptr);
+      }
+      finish_call(on_device, out, dout, 1);
+      return;
+    }
+    if (d->proj == SIPX_PROJ_L2INF_JOINT && d->op != SIPX_OP_TV_XY) throw std::runtime_error(L2INF_JOINT_ROUTE);
+    if (d->op != SIPX_OP_TV && d->op != SIPX_OP_TV_XY) throw std::runtime_error(L2INF_NEEDS_TV);
+    SetConfig<T> s;
+    configure_op(ctx, s, d->op);
+    if (d->op == SIPX_OP_TV_XY) refuse_sharded(ctx, Sharded::TV_XY);
+    configure_proj(ctx, s, &dd);                 // the refusals, and the ExtSpec, of the set
+    const OpScratch w = forward_scratch(tmp, s, on_device);
+    ExtProj<T> ext(s.spec, stream_);
+    const T* dv = queue_forward(w, s, x, on_device);
+    {
+      ObserverGuard og(observer());
+      ObsScope obs(KID_EXT, stream_, (double)(s.nblk + 2) * G_.N * sizeof(T));
+      ext.observe(dv, dout, nullptr, nullptr, nullptr);
+    }
+    finish_call(on_device, out, dout, 1);
+  }
+
   // sipx_l21_stacked_norm(_dev): what the SIPX_PROJ_L21_STACKED set of descriptor d compares with its radius on A x -- A x by custom_fwd
   // through a CSR copy in scratch of the call, then the observe() of a throw-away projector of that set (ext_group.hip, BallProj): the
   // norms launch and the first pass of the search of its project()
@@ -3749,6 +3857,10 @@ class Engine : public EngineBase {
     }
     if (d->proj == SIPX_PROJ_L21_STACKED) {
       project_l21_stacked(d, v, len);
+      return;
+    }
+    if (d->proj == SIPX_PROJ_L2INF || d->proj == SIPX_PROJ_L2INF_JOINT || d->proj == SIPX_PROJ_L2INF_STACKED) {
+      project_l2inf(d, v, len);
       return;
     }
     Grid g1;

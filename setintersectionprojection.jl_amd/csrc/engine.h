@@ -60,6 +60,8 @@ struct EngineBase {
   virtual void l21_weighted_norm(int op, bool joint, const void* x, const void* w, void* out, bool on_device) = 0;
   // sipx_l21_stacked_norm(_dev): the norm a SIPX_PROJ_L21_STACKED set of descriptor d compares with its radius on A x
   virtual void l21_stacked_norm(const sipx_set_desc* d, const void* x, void* out, bool on_device) = 0;
+  // sipx_l2inf_norm(_dev): the largest group norm of A x for the SIPX_PROJ_L2INF kind the descriptor d names
+  virtual void l2inf_norm(const sipx_set_desc* d, const void* x, void* out, bool on_device) = 0;
   virtual void l1_weighted_norm(int op, const void* x, const void* w, void* out, bool on_device) = 0;
   // sipx_l21_groups_norm(_dev): w null: every weight 1
   virtual void l21_groups_norm(int op, int mode, int dir, const void* x, const void* w, void* out, bool on_device) = 0;

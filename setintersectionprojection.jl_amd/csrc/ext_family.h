@@ -7,7 +7,8 @@
 //                      across the frames (l21_joint.h) or across the equal-sized blocks of a caller-supplied stacked operator (l21_stacked.h),
 //                      FrameProj per z-slice (l21_seg.h); GroupsProj: the l2,1 ball whose groups are the
 //                      fibers or slices of a one-block operator's range (l21_groups.h); CardGroupsProj: at most k non-zero ones (card_groups.h); L20Proj / L20FrameProj: at most k non-zero gradient groups of TV / TV_xy (l20.h); L1WProj: the weighted l1 ball on the rows of an
-//                      operator (l1_weighted.h)
+//                      operator (l1_weighted.h); L2InfProj: every group norm of TV / TV_xy, of the joint groups or of a stacked operator
+//                      bounded on its own (l2inf.h)
 // -- and what more than one family uses.
 #pragma once
 #define ROCBLAS_BETA_FEATURES_API 1

@@ -28,6 +28,9 @@
 // (|v_i|, w_i) of the flat padded array: a pass kernel that reads v itself (k_l1w_part) and a soft-threshold apply (k_l1w_apply).
 // The ball whose groups run across the equal-sized blocks of a caller-supplied stacked operator (EXT_L21_STACKED, l21_stacked.h: the Hessian
 // of second-order TV) is BallProj once more with k_l21s_norms / k_l21s_scale in place of the TV kernels: no coordinates, no pads.
+// The l2,inf ball on the same groups (EXT_L2INF, EXT_L2INF_JOINT, EXT_L2INF_STACKED, l2inf.h, L2InfProj) bounds every group norm on its own:
+// no search at all, one sweep that takes the norm, decides and scales (k_l2inf_clip / k_l2infs_clip), the joint set the z-march and
+// k_l2inf_scale.
 // Order of the file: the kernels, the checks of a spec, one launcher per kernel (l21_norms, l21_scale, l21_frames), the projectors.
 // A projector's observe() runs the norms launch and the first sum of its own project(): what it reports is what project() decides on.
 #include <atomic>
@@ -37,6 +40,7 @@
 #include "l21_joint.h"
 #include "l21_seg.h"
 #include "l21_stacked.h"
+#include "l2inf.h"
 #include "l21_groups.h"
 #include "card_groups.h"
 #include "l20.h"
@@ -231,8 +235,191 @@ __global__ __launch_bounds__(BLOCK) void k_l21s_scale(unsigned G, int B, T* __re
   }
 }
 
+// ---- the l2,inf ball (l2inf.h): ||v_p||_2 <= c_p for every group, EXT_L2INF, EXT_L2INF_JOINT, EXT_L2INF_STACKED ----------------------------
+//     k_l2inf_clip     TV / TV_xy: norm, decision and scaling of VW grid points in one sweep      reads nblk N (+ N) words, writes <= nblk N
+//     k_l2infs_clip    the same across the B blocks of a stacked operator                          reads B G (+ G) words, writes <= B G
+//     k_l2inf_scale    the joint set: g per pixel from the z-march of the l2,1 ball (l21_norms)    reads 2 N + L (+ L) words, writes <= 2 N
+//     k_l2inf_max_part / k_l2inf_max_final   the observer: max_p g_p in two stages, fixed order    reads the groups' words of g
+// No search and no ProjScalars: the bound is the scalar c, or VEC: one entry of cv per group.  The clip kernels keep the NBLK (stacked: up
+// to L21S_MAX_BLOCKS) blocks of their VW groups in registers between the load and the store, so v is read once; a thread none of whose VW
+// groups is clipped stores nothing, and in a stored vector the lanes of unclipped groups carry the bits they were loaded with.  Launch
+// shapes, index width and the 16-byte rule are those of k_l21_scale / k_l21s_scale; no LDS outside the observer, no scratch.
+template <typename T, int NBLK, int VW, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_l2inf_clip(L21Args a, T* __restrict__ v, const T* __restrict__ cv, T c) {
+  const unsigned nvec = (unsigned)(a.G.N / VW), step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    const Coord co = coords(a.G, (long long)p);
+    Vec<T, VW> x[NBLK];
+    bool mem[NBLK][VW];
+    double ss[VW];
+#pragma unroll
+    for (int k = 0; k < VW; ++k) ss[k] = 0.0;
+#pragma unroll
+    for (int q = 0; q < NBLK; ++q) {
+      l21_members<VW>(a, co, q, mem[q]);
+      x[q] = ldv<T, VW>(v + (size_t)q * (size_t)a.bstride + p);
+#pragma unroll
+      for (int k = 0; k < VW; ++k) ss[k] += l21_square<T>(x[q].v[k], mem[q][k]);
+    }
+    Vec<T, VW> cc;
+    if constexpr (VEC) cc = ldv<T, VW>(cv + p);
+    T f[VW];
+    bool clip[VW], any = false;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      const T g = l21_norm_of<T>(ss[k]), ck = VEC ? cc.v[k] : c;
+      clip[k] = l2inf_clipped<T>(g, ck);
+      f[k] = clip[k] ? l2inf_factor<T>(g, ck) : T(1);
+      any = any || clip[k];
+    }
+    if (!any) continue;
+#pragma unroll
+    for (int q = 0; q < NBLK; ++q) {
+      T* vq = v + (size_t)q * (size_t)a.bstride + p;
+      bool all = true;
+#pragma unroll
+      for (int k = 0; k < VW; ++k) {
+        if (clip[k]) x[q].v[k] = l2inf_scaled<T>(x[q].v[k], f[k]);
+        all = all && mem[q][k];
+      }
+      if (all) {
+        stv<T, VW>(vq, x[q]);
+      } else {            // the far face along dir[q]: rows the block does not have are not written
+#pragma unroll
+        for (int k = 0; k < VW; ++k)
+          if (mem[q][k] && clip[k]) vq[k] = x[q].v[k];
+      }
+    }
+  }
+}
+// NBLK = 3 and 6 (the Hessian of a 2-D / 3-D grid) are compiled as constants; NBLK = 0 takes the runtime B through a loop unrolled to
+// L21S_MAX_BLOCKS with a guard on q < B, which keeps every block in a register of its own: v is not re-read
+template <typename T, int NBLK, int VW, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_l2infs_clip(unsigned G, int B, T* __restrict__ v, const T* __restrict__ cv, T c) {
+  constexpr int NQ = NBLK > 0 ? NBLK : L21S_MAX_BLOCKS;
+  const int nb = NBLK > 0 ? NBLK : B;
+  const unsigned nvec = G / VW, step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    Vec<T, VW> x[NQ];
+    double ss[VW];
+#pragma unroll
+    for (int k = 0; k < VW; ++k) ss[k] = 0.0;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (q < nb) {
+        x[q] = ldv<T, VW>(v + l21s_index((unsigned)q, G, p));
+#pragma unroll
+        for (int k = 0; k < VW; ++k) ss[k] = l21s_add_square<T>(ss[k], x[q].v[k]);
+      }
+    }
+    Vec<T, VW> cc;
+    if constexpr (VEC) cc = ldv<T, VW>(cv + p);
+    T f[VW];
+    bool clip[VW], any = false;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      const T g = l21_norm_of<T>(ss[k]), ck = VEC ? cc.v[k] : c;
+      clip[k] = l2inf_clipped<T>(g, ck);
+      f[k] = clip[k] ? l2inf_factor<T>(g, ck) : T(1);
+      any = any || clip[k];
+    }
+    if (!any) continue;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (q < nb) {
+#pragma unroll
+        for (int k = 0; k < VW; ++k)
+          if (clip[k]) x[q].v[k] = l2inf_scaled<T>(x[q].v[k], f[k]);
+        stv<T, VW>(v + l21s_index((unsigned)q, G, p), x[q]);
+      }
+    }
+  }
+}
+// JOINT: g holds one norm per pixel (and cv one bound), read at the pixel index p - k L of grid point p as k_l21_scale<..., JOINT = true> does
+template <typename T, int NBLK, int VW, bool VEC, bool JOINT>
+__global__ __launch_bounds__(BLOCK) void k_l2inf_scale(L21Args a, T* __restrict__ v, const T* __restrict__ g, const T* __restrict__ cv, T c) {
+  const unsigned nvec = (unsigned)(a.G.N / VW), step = gridDim.x * BLOCK;
+  for (unsigned vi = blockIdx.x * BLOCK + threadIdx.x; vi < nvec; vi += step) {
+    const unsigned p = vi * VW;
+    const Coord co = coords(a.G, (long long)p);
+    const unsigned pg = JOINT ? p - (unsigned)co.k * (unsigned)a.G.st[2] : p;
+    const Vec<T, VW> gv = ldv<T, VW>(g + pg);
+    Vec<T, VW> cc;
+    if constexpr (VEC) cc = ldv<T, VW>(cv + pg);
+    T f[VW];
+    bool clip[VW], any = false;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) {
+      const T ck = VEC ? cc.v[k] : c;
+      clip[k] = l2inf_clipped<T>(gv.v[k], ck);
+      f[k] = clip[k] ? l2inf_factor<T>(gv.v[k], ck) : T(1);
+      any = any || clip[k];
+    }
+    if (!any) continue;            // nothing of v is read or written where no group is clipped
+#pragma unroll
+    for (int q = 0; q < NBLK; ++q) {
+      bool mem[VW];
+      l21_members<VW>(a, co, q, mem);
+      T* vq = v + (size_t)q * (size_t)a.bstride + p;
+      Vec<T, VW> x = ldv<T, VW>(vq);
+      bool all = true;
+#pragma unroll
+      for (int k = 0; k < VW; ++k) {
+        if (clip[k]) x.v[k] = l2inf_scaled<T>(x.v[k], f[k]);
+        all = all && mem[k];
+      }
+      if (all) {
+        stv<T, VW>(vq, x);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VW; ++k)
+          if (mem[k] && clip[k]) vq[k] = x.v[k];
+      }
+    }
+  }
+}
+// the observer: the maximum of g (n entries, all >= 0) -- every workgroup the maximum of its grid-stride share into part[block], then one
+// workgroup the maximum of the partials; the tree over the BLOCK threads is the same in both.  No atomics.
+template <typename T>
+__device__ __forceinline__ T l2inf_block_max(T m, T* red) {
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int w = BLOCK / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      const T o = red[threadIdx.x + w];
+      if (o > red[threadIdx.x]) red[threadIdx.x] = o;
+    }
+    __syncthreads();
+  }
+  return red[0];
+}
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_l2inf_max_part(unsigned n, const T* __restrict__ g, T* __restrict__ part) {
+  __shared__ T red[BLOCK];
+  T m = T(0);
+  for (unsigned p = blockIdx.x * BLOCK + threadIdx.x; p < n; p += gridDim.x * BLOCK) {
+    const T a = g[p];
+    if (a > m) m = a;
+  }
+  m = l2inf_block_max<T>(m, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_l2inf_max_final(int nparts, const T* __restrict__ part, T* __restrict__ out) {
+  __shared__ T red[BLOCK];
+  T m = T(0);
+  for (int b = threadIdx.x; b < nparts; b += BLOCK) {
+    const T a = part[b];
+    if (a > m) m = a;
+  }
+  m = l2inf_block_max<T>(m, red);
+  if (threadIdx.x == 0) out[0] = m;
+}
+
 // ---- the weighted ball (l21_weighted.h): one weight per group, EXT_L21 and EXT_L21_JOINT built with ExtSpec::weighted ---------------------
-//     k_l21w_part     one Michelot pass: the sums (S, C, count) of the groups in A_k, one partial per workgroup   reads 2 n words
+//     k_l21w_part    one Michelot pass: the sums (S, C, count) of the groups in A_k, one partial per workgroup   reads 2 n words
 //     k_l21w_finish   one workgroup: the partials in the same tree, then l21w_start / l21w_step on the device state
 //     k_l21w_scale    k_l21_scale with w read alongside g; groups of weight 0 are skipped without a load or a store of v
 // Both pass kernels return at once when the state says done, so the host enqueues them in batches and reads one word per batch
@@ -1032,7 +1219,7 @@ static void l21_norms(hipStream_t s, const ExtSpec& sp, const T* v, T* g, double
   constexpr int W = l21_vec_width<T>();
   const bool wide = l21_wide(sp, v, g);
   const long long N = sp.G.N, L = sp.G.st[2];
-  if (sp.kind != EXT_L21_JOINT && sp.kind != EXT_L20_JOINT) {
+  if (sp.kind != EXT_L21_JOINT && sp.kind != EXT_L20_JOINT && sp.kind != EXT_L2INF_JOINT) {
     void (*const k)(L21Args, const T*, T*) = sp.nblk == 2 ? (wide ? k_l21_norms<T, 2, W> : k_l21_norms<T, 2, 1>)
                                                           : (wide ? k_l21_norms<T, 3, W> : k_l21_norms<T, 3, 1>);
     ObsScope obs(KID_L21_NORMS, s, (double)(sp.nblk + 1) * N * sizeof(T));
@@ -1879,8 +2066,127 @@ struct L1WProj : ExtImpl<T> {
   }
 };
 
+// ---- EXT_L2INF, EXT_L2INF_JOINT, EXT_L2INF_STACKED: the group norms bounded one by one (l2inf.h) --------------------------------------------
+// One sweep (k_l2inf_clip, k_l2infs_clip), or for the joint set the z-march of the l2,1 ball into g and k_l2inf_scale.  No search, no warm
+// start, nothing kept between calls.  Built with ExtSpec::ub every group has its own bound (cvec, n entries of T), sipx_set_data replaces
+// them.  g and the partial maxima exist for the joint set and, from its first call on, for the observer.
+static void l2inf_check_spec(const ExtSpec& sp) {
+  if (sp.kind == EXT_L2INF_STACKED) {
+    const long long G = l2infs_check_shape(sp.G.N, sp.nblk);
+    if (sp.bstride != G) throw std::runtime_error("the stacked l2,inf ball: the block stride must be the rows of one block");
+  } else {
+    if (sp.nblk < 2) throw std::runtime_error(L2INF_NEEDS_TV);
+    l21_check_spec(sp);
+    if (sp.kind == EXT_L2INF_JOINT && (sp.ndim != 3 || sp.nblk != 2 || sp.bdir[0] != 1 || sp.bdir[1] != 0)) throw std::runtime_error(L2INF_JOINT_ROUTE);
+  }
+  if (sp.mode != SIPX_MODE_WHOLE) throw std::runtime_error(L2INF_MODES);
+  if (sp.lb || sp.weighted) throw std::runtime_error(L2INF_NO_WEIGHTS);
+  if (!sp.ub) l2inf_check_c(sp.pmax);
+}
+// the groups of a spec: the entries of a vector of bounds and of g
+static long long l2inf_groups(const ExtSpec& sp) {
+  return sp.kind == EXT_L2INF_STACKED ? sp.bstride : (sp.kind == EXT_L2INF_JOINT ? sp.G.st[2] : sp.G.N);
+}
+template <typename T>
+struct L2InfProj : ExtImpl<T> {
+  using ExtImpl<T>::sp;
+  using ExtImpl<T>::stream;
+  const bool joint, stacked;
+  long long n = 0;                     // groups: the entries of cvec and of g
+  T* cvec = nullptr;                   // one bound per group, or none: the scalar sp.pmax
+  T* g = nullptr;                      // the group norms: the joint set's, and the observer's
+  double* part = nullptr;              // EXT_L2INF_JOINT: the chunk sums, nchunk L entries, when the plan chunks
+  T* mpart = nullptr;                  // the observer's maxima of the workgroups, NB entries
+  long long calls = 0;
+  L2InfProj(const ExtSpec& spec, hipStream_t s)
+      : ExtImpl<T>(spec, s), joint(spec.kind == EXT_L2INF_JOINT), stacked(spec.kind == EXT_L2INF_STACKED) {
+    l2inf_check_spec(sp);
+    n = l2inf_groups(sp);
+    if (sp.ub) {
+      cvec = this->template alloc<T>(n);
+      SIPX_HIP(hipMemcpy(cvec, sp.ub, sizeof(T) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    if (joint) norms_memory();
+  }
+  void norms_memory() {
+    if (g) return;
+    g = this->template alloc<T>(n);
+    const int nchunk = joint ? l21_joint_plan(n, sp.G.n[2], (int)sizeof(T)).nchunk : 1;
+    if (nchunk > 1) part = this->template alloc<double>((size_t)nchunk * n);
+  }
+  // g <- the group norms of v by the norms launch of the l2,1 ball on the same operator
+  void norms(const T* v) {
+    norms_memory();
+    if (stacked) l21s_norms<T>(stream, sp, v, g);
+    else l21_norms<T>(stream, sp, v, g, part);
+  }
+  void reset() override { calls = 0; }
+  void project(T* v, bool, double*, T*, T*) override {
+    ++calls;
+    constexpr int W = l21_vec_width<T>();
+    const T c = (T)sp.pmax;
+    const double cw = cvec ? 1.0 : 0.0;      // (the words of c a group reads; the booked traffic is that of a call that clips everywhere)
+    if (stacked) {
+      const bool wide = l21s_wide(sp, v, cvec);
+      const long long G = sp.bstride;
+      void (*const k)(unsigned, int, T*, const T*, T) =
+          sp.nblk == 3   ? (cvec ? (wide ? k_l2infs_clip<T, 3, W, true> : k_l2infs_clip<T, 3, 1, true>)
+                                 : (wide ? k_l2infs_clip<T, 3, W, false> : k_l2infs_clip<T, 3, 1, false>))
+          : sp.nblk == 6 ? (cvec ? (wide ? k_l2infs_clip<T, 6, W, true> : k_l2infs_clip<T, 6, 1, true>)
+                                 : (wide ? k_l2infs_clip<T, 6, W, false> : k_l2infs_clip<T, 6, 1, false>))
+                         : (cvec ? (wide ? k_l2infs_clip<T, 0, W, true> : k_l2infs_clip<T, 0, 1, true>)
+                                 : (wide ? k_l2infs_clip<T, 0, W, false> : k_l2infs_clip<T, 0, 1, false>));
+      ObsScope obs(KID_L2INFS_CLIP, stream, (double)(2 * sp.nblk + cw) * G * sizeof(T));
+      hipLaunchKernelGGL(k, dim3(fit_grid(G / (wide ? W : 1), NB)), dim3(BLOCK), 0, stream, (unsigned)G, sp.nblk, v, (const T*)cvec, c);
+      SIPX_HIP(hipGetLastError());
+      return;
+    }
+    const bool wide = l21_wide(sp, v, cvec);
+    const long long N = sp.G.N;
+    const int grid = fit_grid(N / (wide ? W : 1), NB);
+    if (joint) {
+      norms(v);
+      void (*const k)(L21Args, T*, const T*, const T*, T) =
+          cvec ? (wide ? k_l2inf_scale<T, 2, W, true, true> : k_l2inf_scale<T, 2, 1, true, true>)
+               : (wide ? k_l2inf_scale<T, 2, W, false, true> : k_l2inf_scale<T, 2, 1, false, true>);
+      ObsScope obs(KID_L2INF_SCALE, stream, (4.0 * N + (1 + cw) * n) * sizeof(T));
+      hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), 0, stream, l21_args(sp), v, (const T*)g, (const T*)cvec, c);
+      SIPX_HIP(hipGetLastError());
+      return;
+    }
+    void (*const k)(L21Args, T*, const T*, T) =
+        sp.nblk == 2 ? (cvec ? (wide ? k_l2inf_clip<T, 2, W, true> : k_l2inf_clip<T, 2, 1, true>)
+                             : (wide ? k_l2inf_clip<T, 2, W, false> : k_l2inf_clip<T, 2, 1, false>))
+                     : (cvec ? (wide ? k_l2inf_clip<T, 3, W, true> : k_l2inf_clip<T, 3, 1, true>)
+                             : (wide ? k_l2inf_clip<T, 3, W, false> : k_l2inf_clip<T, 3, 1, false>));
+    ObsScope obs(KID_L2INF_CLIP, stream, (double)(2 * sp.nblk + cw) * N * sizeof(T));
+    hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), 0, stream, l21_args(sp), v, (const T*)cvec, c);
+    SIPX_HIP(hipGetLastError());
+  }
+  // out[0] <- max_p g_p: the norms launch on the operator of the set -- the arithmetic of the clip kernels, bit for bit -- and the
+  // maximum of g in two stages; v is not written
+  void observe(const T* v, T* out, double*, T*, T*) override {
+    norms(v);
+    if (!mpart) mpart = this->template alloc<T>(NB);
+    const int grid = fit_grid(n, NB);
+    hipLaunchKernelGGL((k_l2inf_max_part<T>), dim3(grid), dim3(BLOCK), 0, stream, (unsigned)n, (const T*)g, mpart);
+    SIPX_HIP(hipGetLastError());
+    hipLaunchKernelGGL((k_l2inf_max_final<T>), dim3(1), dim3(BLOCK), 0, stream, grid, (const T*)mpart, out);
+    SIPX_HIP(hipGetLastError());
+  }
+  void set_data(const T* new_lb, const T* new_ub, bool on_device) override {
+    if (new_lb) throw std::runtime_error(L2INF_NO_WEIGHTS);
+    if (!cvec) throw std::runtime_error(L2INF_NO_SET_DATA);
+    if (new_ub)
+      SIPX_HIP(hipMemcpyAsync(cvec, new_ub, sizeof(T) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  }
+  // projections since the reset; the groups
+  void route_counts(long long out[4]) const override { out[0] = calls; out[1] = out[2] = 0; out[3] = n; }
+};
+
 template <typename T>
 ExtImpl<T>* make_group_family(const ExtSpec& spec, hipStream_t stream) {
+  if (spec.kind == EXT_L2INF || spec.kind == EXT_L2INF_JOINT || spec.kind == EXT_L2INF_STACKED) return new L2InfProj<T>(spec, stream);
   if (spec.kind == EXT_L1_WEIGHTED) return new L1WProj<T>(spec, stream);
   if (spec.kind == EXT_L21_GROUPS) return new GroupsProj<T>(spec, stream);
   if (spec.kind == EXT_CARD_GROUPS) return new CardGroupsProj<T>(spec, stream);

@@ -19,7 +19,10 @@ enum { EXT_L1_DFT = 1, EXT_RANK = 2, EXT_NUCLEAR = 3, EXT_CARD_SEG = 4, EXT_HIST
        EXT_L20 = 22 /* at most pmax grid points with a non-zero gradient vector on the range of TV / TV_xy (l20.h) */,
        EXT_L20_SEG = 23 /* ... at most pmax (or ub[frame]) pixels in every z-slice of TV_xy */,
        EXT_L20_JOINT = 24 /* ... at most pmax pixels that carry a gradient in any frame of TV_xy */,
-       EXT_L21_STACKED = 25 /* the l2,1 ball across the equal-sized blocks of a caller-supplied operator (l21_stacked.h) */ };
+       EXT_L21_STACKED = 25 /* the l2,1 ball across the equal-sized blocks of a caller-supplied operator (l21_stacked.h) */,
+       EXT_L2INF = 26 /* every group norm of TV / TV_xy at most pmax, or ub[grid point] (l2inf.h) */,
+       EXT_L2INF_JOINT = 27 /* ... every norm of the groups of EXT_L21_JOINT at most pmax, or ub[pixel] */,
+       EXT_L2INF_STACKED = 28 /* ... every norm of the groups of EXT_L21_STACKED at most pmax, or ub[row of a block] */ };
 
 // The refusal of an EXT_L21_JOINT set off its operator or mode, worded once: set_config.h (sipx_add_set), the stand-alone calls of the
 // engine and the projector's own check throw this text (its cases: tests/test_l21_joint_cpu.py, tests/test_gpu_l21_joint.py)
@@ -49,6 +52,8 @@ struct ExtSpec {
   int nblk = 0;                   // EXT_L21(_SEG): blocks of the operator (2 or 3), block q at v + q * bstride holding the differences along bdir[q]
                                   // EXT_L21_STACKED: the B blocks (1 .. 8) of the caller-supplied operator, bstride = G their rows each, G the
                                   // 1-D grid of the M = B G rows; bdir is not looked at
+                                  // EXT_L2INF, EXT_L2INF_JOINT as EXT_L21, EXT_L2INF_STACKED as EXT_L21_STACKED; ub: host TF[groups], one bound per
+                                  // group, or nullptr: the scalar pmax
   long long bstride = 0;
   int bdir[3] = {0, 0, 0};
   int weighted = 0;               // EXT_L21 (whole array) / EXT_L21_JOINT / EXT_L21_GROUPS: 1: one weight per group (l21_weighted.h) -- lb: host TF[groups], or
@@ -70,7 +75,7 @@ class ExtProj {
   void project(T* v, bool feas, double* partials, T* maxpart, T* compact);
   // the l2,1 sets (ext_group.hip): out (device) <- what project(v, ...) would compare with the radius, summed and rounded by the
   // projector's own launches -- ||v||_2,1 for EXT_L21, the sum of the G group norms across the blocks for EXT_L21_STACKED, the sum of the n1 n2 group norms for EXT_L21_JOINT, one sum per z-slice (n3
-  // entries) for EXT_L21_SEG, the weighted sum of the segment norms for EXT_L21_GROUPS, the sum of the 2 n1 n2 singular values for EXT_TNV; and sum_i w_i |v_i| for EXT_L1_WEIGHTED; one sum of the positive parts per segment (nseg entries, SegMap's order) for EXT_SIMPLEX_SEG; the l2 norm of every segment (nseg entries, the selection key) for EXT_CARD_GROUPS; the norm of every gradient group (N entries in point order, EXT_L20_JOINT: the n1 n2 pixels; the selection key) for the EXT_L20 kinds.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
+  // entries) for EXT_L21_SEG, the weighted sum of the segment norms for EXT_L21_GROUPS, the sum of the 2 n1 n2 singular values for EXT_TNV; and sum_i w_i |v_i| for EXT_L1_WEIGHTED; one sum of the positive parts per segment (nseg entries, SegMap's order) for EXT_SIMPLEX_SEG; the l2 norm of every segment (nseg entries, the selection key) for EXT_CARD_GROUPS; the norm of every gradient group (N entries in point order, EXT_L20_JOINT: the n1 n2 pixels; the selection key) for the EXT_L20 kinds; the largest group norm (one number) for the EXT_L2INF kinds.  v and the warm starts are not written; the scratch is that of project.  The other kinds throw.
   void observe(const T* v, T* out, double* partials, T* maxpart, T* compact);
   // rank projector: calls since construction, calls served by the warm-started subspace route, calls that decomposed fully,
   // products with the Gram matrices the subspace route spent (all zero for the other kinds)

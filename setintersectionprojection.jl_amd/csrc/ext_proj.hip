@@ -34,7 +34,7 @@ ExtProj<T>::ExtProj(const ExtSpec& spec, hipStream_t stream) : impl_(nullptr) {
     case EXT_RANK: case EXT_NUCLEAR: impl_ = make_rank_family<T>(spec, stream); break;
     case EXT_CARD_SEG: case EXT_L1_SEG: case EXT_L2_SEG: case EXT_ANNULUS_SEG: case EXT_SIMPLEX_SEG: case EXT_HISTOGRAM: case EXT_SUBSPACE:
       impl_ = make_segment_family<T>(spec, stream); break;
-    case EXT_L21: case EXT_L21_SEG: case EXT_L21_JOINT: case EXT_L21_GROUPS: case EXT_CARD_GROUPS: case EXT_L20: case EXT_L20_SEG: case EXT_L20_JOINT: case EXT_TNV: case EXT_L1_WEIGHTED: case EXT_L21_STACKED: impl_ = make_group_family<T>(spec, stream); break;
+    case EXT_L21: case EXT_L21_SEG: case EXT_L21_JOINT: case EXT_L21_GROUPS: case EXT_CARD_GROUPS: case EXT_L20: case EXT_L20_SEG: case EXT_L20_JOINT: case EXT_TNV: case EXT_L1_WEIGHTED: case EXT_L21_STACKED: case EXT_L2INF: case EXT_L2INF_JOINT: case EXT_L2INF_STACKED: impl_ = make_group_family<T>(spec, stream); break;
     default: throw std::runtime_error("unknown external projector");
   }
 }

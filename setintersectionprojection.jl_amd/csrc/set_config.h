@@ -16,6 +16,7 @@
 #include "card_groups.h"     // (the refusals and the check of k of group cardinality)
 #include "l20.h"             // (the refusals and the checks of k of the l2,0 sets on TV / TV_xy)
 #include "l21_stacked.h"     // (the refusals and the shape check of the l2,1 ball across the blocks of a stacked operator)
+#include "l2inf.h"           // (the refusals and the checks of the bounds of the l2,inf sets)
 
 namespace sipx {
 
@@ -109,7 +110,8 @@ void expand_fiber_bounds(const ConfigCtx& c, const SetConfig<T>& s, const T* per
 // CARD_GROUPS: the segments compete for k places across the whole array (card_groups.h).
 // L20: the gradient groups span the blocks of TV and compete for k places across the whole array (l20.h).
 // L21_STACKED: the groups span the blocks of a caller-supplied operator (l21_stacked.h); no sharded route materialises its range.
-enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX, CARD_GROUPS, L20, L21_STACKED };
+// L2INF: the groups span the blocks of TV / TV_xy or of a caller-supplied operator, the bounds live in the one projector (l2inf.h).
+enum class Sharded { RADII, L21, TV_XY, L21_GROUPS, L1_WEIGHTED, SIMPLEX, CARD_GROUPS, L20, L21_STACKED, L2INF };
 inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
   if (c.single_process) return;
   switch (which) {
@@ -134,6 +136,8 @@ inline void refuse_sharded(const ConfigCtx& c, Sharded which) {
       throw std::runtime_error(L20_SHARDED);
     case Sharded::L21_STACKED:
       throw std::runtime_error(L21S_SHARDED);
+    case Sharded::L2INF:
+      throw std::runtime_error(L2INF_SHARDED);
   }
 }
 // every host path refuses an l1 radius that is not > 0 (project_l1_Duchi!.jl:22); device-supplied ones: seg_norm.h
@@ -156,6 +160,12 @@ inline void l21s_spec(ExtSpec& sp, long long M, int B) {
   sp.nblk = B;
   sp.bstride = M / B;
   for (int q = 0; q < 3; ++q) sp.bdir[q] = 0;
+}
+
+// the l2,inf kinds (l2inf.h) and their groups: the entries of a vector of bounds
+inline bool is_l2inf(int ext_kind) { return ext_kind == EXT_L2INF || ext_kind == EXT_L2INF_JOINT || ext_kind == EXT_L2INF_STACKED; }
+inline long long l2inf_groups(const ConfigCtx& c, int ext_kind, const ExtSpec& sp) {
+  return ext_kind == EXT_L2INF_STACKED ? sp.bstride : (ext_kind == EXT_L2INF_JOINT ? c.G.st[2] : c.G.N);
 }
 
 // the groups of a weighted l2,1 set on TV / TV_xy (l21_weighted.h): the grid points of EXT_L21, the pixels of EXT_L21_JOINT
@@ -299,6 +309,18 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (s.comp) throw std::runtime_error(L21S_NO_MINKOWSKI);
     if (d->lb || d->ub || d->reserved) throw std::runtime_error(L21S_NO_VECTORS);
   }
+  // so are the l2,inf sets (l2inf.h): TV or TV_xy, TV_xy for the joint set, a caller-supplied operator for the stacked one; the whole
+  // array, no transform, no component, no lower bound, no weights
+  if (d->proj == SIPX_PROJ_L2INF || d->proj == SIPX_PROJ_L2INF_JOINT || d->proj == SIPX_PROJ_L2INF_STACKED) {
+    if (d->transform != SIPX_TRANSFORM_NONE) throw std::runtime_error(L2INF_NO_TRANSFORM);
+    if (d->proj == SIPX_PROJ_L2INF_JOINT && s.op != SIPX_OP_TV_XY) throw std::runtime_error(L2INF_JOINT_ROUTE);
+    if (d->proj == SIPX_PROJ_L2INF_STACKED && !s.custom) throw std::runtime_error(L2INF_STACKED_NEEDS_CSC);
+    if (d->proj == SIPX_PROJ_L2INF && (s.custom || (s.op != SIPX_OP_TV && s.op != SIPX_OP_TV_XY))) throw std::runtime_error(L2INF_NEEDS_TV);
+    if (s.comp) throw std::runtime_error(L2INF_NO_MINKOWSKI);
+    if (mode != SIPX_MODE_WHOLE) throw std::runtime_error(L2INF_MODES);
+    if (d->pmin != 0) throw std::runtime_error(L2INF_MIN);
+    if (d->lb) throw std::runtime_error(L2INF_NO_WEIGHTS);
+  }
   if (mode != SIPX_MODE_WHOLE) {
     if (dir < 0 || dir >= c.ndim) throw std::runtime_error("application mode: direction out of range for this grid");
     // the one multi-block set with a mode of its own: the l2,1 ball per z-slice on TV_xy (l21_seg.h)
@@ -309,7 +331,7 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
     if (s.nblk > 1 && !frames) throw std::runtime_error("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)");
   }
   auto ext = [&](int kind) {
-    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT && kind != EXT_TNV && kind != EXT_L1_WEIGHTED && kind != EXT_L20 && kind != EXT_L20_SEG && kind != EXT_L20_JOINT) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
+    if (s.nblk > 1 && kind != EXT_L21 && kind != EXT_L21_SEG && kind != EXT_L21_JOINT && kind != EXT_TNV && kind != EXT_L1_WEIGHTED && kind != EXT_L20 && kind != EXT_L20_SEG && kind != EXT_L20_JOINT && kind != EXT_L2INF && kind != EXT_L2INF_JOINT) throw std::runtime_error("this projector needs an operator with one block (identity, D_x, D_y, D_z)");
     s.ext_kind = kind;
     s.spec.kind = kind;
     s.spec.ndim = c.ndim;
@@ -546,6 +568,31 @@ void configure_proj(const ConfigCtx& c, SetConfig<T>& s, const sipx_set_desc* d)
       l21s_spec(s.spec, s.Mtrue, d->blocks);
       break;
     }
+    case SIPX_PROJ_L2INF:          // every group norm at most pmax, or ub[group] with `reserved` its entries (operator, mode, transform,
+    case SIPX_PROJ_L2INF_JOINT:    // component, pmin, lb: above): the groups of SIPX_PROJ_L21, of SIPX_PROJ_L21_JOINT,
+    case SIPX_PROJ_L2INF_STACKED: {  // of SIPX_PROJ_L21_STACKED
+      const int kind = d->proj == SIPX_PROJ_L2INF ? EXT_L2INF : (d->proj == SIPX_PROJ_L2INF_JOINT ? EXT_L2INF_JOINT : EXT_L2INF_STACKED);
+      if (kind == EXT_L2INF_STACKED) l2infs_check_shape(s.Mtrue, d->blocks);
+      refuse_sharded(c, Sharded::L2INF);
+      ext(kind);
+      if (kind == EXT_L2INF_STACKED) {
+        l21s_spec(s.spec, s.Mtrue, d->blocks);
+        s.spec.kind = kind;
+      }
+      const long long groups = l2inf_groups(c, kind, s.spec);
+      if (!d->ub) {
+        if (d->reserved) throw std::runtime_error(l2inf_bad_length(d->reserved, 0) + " -- reserved counts the entries of ub, which is NULL");
+        l2inf_check_c(d->pmax);
+        break;
+      }
+      if (d->reserved != groups) throw std::runtime_error(l2inf_bad_length(d->reserved, groups));      // (reserved: the entries ub holds)
+      // (a group without a member -- the last corner of the grid, of every frame of TV_xy, the last pixel -- is not looked at)
+      const long long per = kind == EXT_L2INF && s.op == SIPX_OP_TV_XY ? G.st[2] : groups;
+      l2inf_check_vector<T>((const T*)d->ub, groups, [&](long long p) { return kind == EXT_L2INF_STACKED || p % per != per - 1; });
+      s.seg_radii = true;
+      s.host_ub.assign((const T*)d->ub, (const T*)d->ub + groups);
+      break;
+    }
     case SIPX_PROJ_SIMPLEX:  // entries >= 0 and a sum in [pmin, pmax] per fiber or slice (operator, transform, component, mode: above)
       if (c.ndim == 2 && mode == SIPX_MODE_SLICE) throw std::runtime_error(SIMPLEX_2D_SLICE);
       if (d->lb || d->ub) throw std::runtime_error(SIMPLEX_NO_VECTORS);
@@ -599,6 +646,7 @@ std::vector<long long> default_ata_offsets(const ConfigCtx& c, const SetConfig<T
 template <typename T>
 long long data_len(const ConfigCtx& c, const SetConfig<T>& s) {
   if (s.ext_kind == EXT_L1_WEIGHTED) return s.Mtrue;
+  if (is_l2inf(s.ext_kind)) return l2inf_groups(c, s.ext_kind, s.spec);
   if (s.weighted) return s.ext_kind == EXT_L21_GROUPS ? seg_count(s.spec) : l21_groups(c, s.ext_kind);
   if (s.seg_radii) return (s.ext_kind == EXT_L21_SEG || s.ext_kind == EXT_L20_SEG) ? c.G.n[2] : seg_count(s.spec);
   if (s.ext_kind || s.bmode != SIPX_MODE_FIBER) return s.Mtrue;
@@ -617,8 +665,8 @@ SetConfig<T> configure_set(const ConfigCtx& c, const sipx_set_desc* d, const voi
     if (d->component) throw std::runtime_error("the TV_xy operator takes no Minkowski component");
   }
   configure_proj(c, s, d);
-  // (the one materialised projector a custom operator takes: the l2,1 ball across its blocks, which acts on s = A x as a whole)
-  if (s.custom && (s.comp || (s.ext_kind && s.ext_kind != EXT_L21_STACKED)))
+  // (the materialised projectors a custom operator takes: the l2,1 and the l2,inf ball across its blocks, which act on s = A x as a whole)
+  if (s.custom && (s.comp || (s.ext_kind && s.ext_kind != EXT_L21_STACKED && s.ext_kind != EXT_L2INF_STACKED)))
     throw std::runtime_error("custom sparse operators (SIPX_OP_CSC): Minkowski components and library-backed projectors are not available; "
                              "use one of the built-in operators for such a set");
   if (s.custom && !ata_R) {              // matrix-free term of Q: no bands, the products go through the operator itself

@@ -68,7 +68,8 @@ enum KernelId {
   KID_PS_RESCALE, KID_CARD, KID_EXT, KID_BB_RULE, KID_OTHER, KID_MF_FWD, KID_MF_ADJ, KID_L21_NORMS, KID_L21_FRAMES, KID_L21_SCALE,
   KID_L21J_NORMS, KID_L21J_FINISH, KID_L21J_SCALE, KID_L21W_PASS, KID_L21W_SCALE,
   KID_L21G_NORMS, KID_L21G_FINISH, KID_L21G_SCALE, KID_TNV_GRAM, KID_TNV_FINISH, KID_TNV_APPLY, KID_L1W_PASS, KID_L1W_APPLY,
-  KID_CARDG_RANK, KID_CARDG_ZERO, KID_L20_FRAMES, KID_L20_ZERO, KID_L21S_NORMS, KID_L21S_SCALE, KID_COUNT
+  KID_CARDG_RANK, KID_CARDG_ZERO, KID_L20_FRAMES, KID_L20_ZERO, KID_L21S_NORMS, KID_L21S_SCALE,
+  KID_L2INF_CLIP, KID_L2INFS_CLIP, KID_L2INF_SCALE, KID_COUNT
 };
 inline const char* kernel_name(int k) {
   static const char* const names[KID_COUNT] = {
@@ -79,7 +80,8 @@ inline const char* kernel_name(int k) {
       "k_bb_rule", "other", "k_mf_fwd", "k_mf_adj", "k_l21_norms", "k_l21_frames", "k_l21_scale",
       "k_l21j_norms", "k_l21j_finish", "k_l21j_scale", "k_l21w_part", "k_l21w_scale",
       "k_l21g_norms", "k_l21g_finish", "k_l21g_scale", "k_tnv_gram", "k_tnv_finish", "k_tnv_apply", "k_l1w_part", "k_l1w_apply",
-      "k_cardg_rank", "k_cardg_zero", "k_l20_frames", "k_l20_zero", "k_l21s_norms", "k_l21s_scale"};      // (the last twenty-two: inside ext_proj)
+      "k_cardg_rank", "k_cardg_zero", "k_l20_frames", "k_l20_zero", "k_l21s_norms", "k_l21s_scale",
+      "k_l2inf_clip", "k_l2infs_clip", "k_l2inf_scale"};      // (the last twenty-five: inside ext_proj)
   return (k >= 0 && k < KID_COUNT) ? names[k] : "?";
 }
 // Which kernel served a launch where one observer name covers two of them (the z-marching product and right-hand side run

@@ -43,14 +43,15 @@ EXPORTED_SYMBOLS = [
     "sipx_l21_groups_norm", "sipx_l21_groups_norm_dev", "sipx_tnv_norm", "sipx_tnv_norm_dev",
     "sipx_l1_weighted_norm", "sipx_l1_weighted_norm_dev", "sipx_segment_sums", "sipx_segment_sums_dev",
     "sipx_group_norms", "sipx_group_norms_dev", "sipx_card_groups_route", "sipx_tv_group_norms", "sipx_tv_group_norms_dev",
-    "sipx_l21_stacked_norm", "sipx_l21_stacked_norm_dev",
+    "sipx_l21_stacked_norm", "sipx_l21_stacked_norm_dev", "sipx_l2inf_norm", "sipx_l2inf_norm_dev",
 ]
 
 SIPX_F32, SIPX_F64 = 0, 1
 OPS = {"identity": 0, "D_x": 1, "D_y": 2, "D_z": 3, "TV": 4, "D2D": 4, "D3D": 4, "custom": 5, "TV_xy": 6}
 PROJ = {"bounds": 0, "bounds_vec": 1, "l1": 2, "l2": 3, "annulus": 4, "cardinality": 5, "prox_l1": 6, "l1_dft": 7, "rank": 8,
         "nuclear": 9, "histogram": 10, "subspace": 11, "bounds_dft": 12, "card_dft": 13, "l21": 14, "l21_joint": 15, "l21_groups": 16,
-        "tnv": 17, "l1_weighted": 18, "simplex": 19, "card_groups": 20, "l20": 21, "l20_joint": 22, "l21_stacked": 23}
+        "tnv": 17, "l1_weighted": 18, "simplex": 19, "card_groups": 20, "l20": 21, "l20_joint": 22, "l21_stacked": 23,
+        "l2inf": 24, "l2inf_joint": 25, "l2inf_stacked": 26}
 TV_OPERATORS = ("TV", "D2D", "D3D")      # one name per grid dimension count for the same operator (get_TD_operator.jl)
 # the engine's refusal of the l2,1 ball off the TV operator (csrc/set_config.h, configure_proj), word for word; a mode on TV the
 # engine refuses as it does for every multi-block operator, the front end in words of the set's own
@@ -197,6 +198,68 @@ def l21s_bad_blocks(B):
 def l21s_bad_rows(M, B):
     return (f"the stacked l2,1 ball (l21_stacked): the operator has M = {M} rows, not a multiple of blocks = {B} -- every block needs "
             "the same number of rows (pad a shorter block with zero rows)")
+
+
+# the l2,inf ball: pointwise bounds on the group norms of TV / TV_xy, of the joint groups or of a stacked operator (csrc/l2inf.h): the
+# engine's refusals, word for word
+L2INF_KINDS = ("l2inf", "l2inf_joint", "l2inf_stacked")
+L2INF_NEEDS_TV = ("the l2,inf ball (l2inf) bounds the gradient magnitude at every grid point: TD_OP must be TV (D2D, D3D), TV_xy "
+                  "or the named \"Hessian\" -- a bound on one difference direction is (\"bounds\", \"D_z\"), a caller-supplied "
+                  "stacked operator takes (\"l2inf_stacked\", name, 0, c, mode, custom_TD_OP=(A, False), blocks=B)")
+L2INF_JOINT_ROUTE = ("the joint l2,inf ball (l2inf_joint) groups the frames of TV_xy: TD_OP must be TV_xy, mode tensor -- per "
+                     "frame bounds are (\"l2inf\", \"TV_xy\")")
+L2INF_STACKED_NEEDS_CSC = ("the stacked l2,inf ball (l2inf_stacked) groups the rows of a caller-supplied sparse operator across its "
+                           "blocks: the operator must be SIPX_OP_CSC (custom_TD_OP, or the named \"Hessian\") -- on the built-in TV "
+                           "operator the set is (\"l2inf\", \"TV\")")
+L2INF_MIN = ("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) bounds the group norms from above only: min must be 0 -- a lower "
+             "bound on the gradient magnitude is not convex and not built")
+L2INF_BAD_C = ("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) needs a bound c > 0 as a scalar (c = 0 is the constant array: "
+               "use bounds on TV, or a vector of zeros to flatten chosen points)")
+L2INF_MODES = ("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) applies to the whole array (matrix / tensor mode), fibers and "
+               "slices are not built: (\"slice\", \"z\") on TV_xy is the vector form with c constant within every frame -- pass "
+               "max = np.repeat(c_frames, n1 * n2)")
+L2INF_NO_TRANSFORM = ("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) takes no transform (DFT, DCT, wavelet): it acts on the "
+                      "differences of x themselves")
+L2INF_NO_WEIGHTS = ("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) takes no weights (lb): a weight per group is its bound, pass "
+                    "the vector of bounds as max (ub)")
+L2INF_NO_MINKOWSKI = "the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) takes no Minkowski component: bound the sum itself"
+L2INF_SHARDED = ("the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) takes single-process contexts only, this one has a "
+                 "communicator, a slab decomposition or set ownership: its groups span the blocks of the operator -- use "
+                 "(\"bounds\", \"TV\"), or a single process")
+L2INF_NO_COARSE = ("multilevel: the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked) is not built for PARSDMM_multi_level: a bound on "
+                   "the gradient magnitude does not carry over to a coarser grid unchanged -- solve on one level")
+L2INF_NO_SET_DATA = ("this l2,inf set was built with a scalar bound, which is fixed at sipx_add_set: build it with a vector of bounds "
+                     "(ub) to replace them in a live context")
+
+
+def l2inf_bad_length(given, groups):
+    return (f"the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked): the vector of bounds has {given} entries, the set has "
+            f"{groups} groups (one bound per grid point, per pixel of the joint set, or per row of one block)")
+
+
+def l2inf_bad_entry(p):
+    return (f"the l2,inf ball (l2inf, l2inf_joint, l2inf_stacked): bound {p} is negative or NaN -- every bound must be >= 0 "
+            "(+inf leaves a point free, 0 flattens it)")
+
+
+def l2inf_bad_blocks(B):
+    return f"the stacked l2,inf ball (l2inf_stacked): blocks = {B}, the number of equal-sized blocks of the operator must be 1 .. 8"
+
+
+def l2inf_bad_rows(M, B):
+    return (f"the stacked l2,inf ball (l2inf_stacked): the operator has M = {M} rows, not a multiple of blocks = {B} -- every block needs "
+            "the same number of rows (pad a shorter block with zero rows)")
+
+
+def _check_l2inf_bounds(c, per, stacked):
+    """A host vector of bounds of an l2,inf set (csrc/l2inf.h, l2inf_check_vector): every entry >= 0, NaN refused; the entry of a group
+    without a member -- index per - 1 of every run of per entries; a stacked operator has none -- is not looked at."""
+    c = np.asarray(c)
+    bad = ~(c >= 0)
+    if not stacked and per:
+        bad[per - 1::per] = False
+    if bad.any():
+        raise SipxError(l2inf_bad_entry(int(np.flatnonzero(bad)[0])))
 
 
 UNKNOWN_OPERATOR = "provided an unknown transform domain operator. check function get_TD_operator(comp_grid,TD_type,TF) for options"
@@ -548,6 +611,8 @@ class Projector:
             raise SipxError(CARDG_NO_VECTORS)
         if getattr(constraint, "weights", None) is not None and st in ("l20", "l20_joint"):
             raise SipxError(L20_NO_WEIGHTS)
+        if getattr(constraint, "weights", None) is not None and st in L2INF_KINDS:
+            raise SipxError(L2INF_NO_WEIGHTS)
         if getattr(constraint, "weights", None) is not None and st not in ("l21", "l21_joint", "l21_groups", "l1_weighted"):
             raise SipxError(f"set type {st!r} takes no weights: " + L21_WEIGHTS_WHERE)
         self.seg_radii = False       # an l1 / l2 / annulus set per fiber or slice built with one radius per segment (in ub; lb: the annulus' inner radii)
@@ -685,6 +750,66 @@ class Projector:
                 self.pmax = float(max(ks)) if ks else 1.0
             else:
                 self.pmax = _check_l20_k(constraint.max, ngroups, self.TF)
+            return
+        if st in L2INF_KINDS:
+            # every group norm at most max, one number or one per group (csrc/l2inf.h); ("l2inf", "Hessian") is the stacked set on the
+            # named operator
+            cust = constraint.custom_TD_OP[0]
+            has_cust = not (isinstance(cust, (tuple, list)) and len(cust) == 0)
+            if constraint.TD_OP in SPECIAL_OPERATORS:
+                raise SipxError(L2INF_NO_TRANSFORM)
+            stacked = st == "l2inf_stacked" or (st == "l2inf" and constraint.TD_OP == "Hessian" and not has_cust)
+            if st == "l2inf_joint" and (has_cust or constraint.TD_OP != "TV_xy"):
+                raise SipxError(L2INF_JOINT_ROUTE)
+            if st == "l2inf_stacked" and not has_cust and constraint.TD_OP != "Hessian":
+                raise SipxError(L2INF_STACKED_NEEDS_CSC)
+            if st == "l2inf" and not stacked and (has_cust or constraint.TD_OP not in TV_OPERATORS + ("TV_xy",)):
+                raise SipxError(L2INF_NEEDS_TV)
+            if not stacked and constraint.TD_OP == "TV_xy" and len(n) != 3:
+                raise SipxError(TV_XY_NEEDS_3D)
+            if self.mode:
+                raise SipxError(L2INF_MODES)
+            if np.ndim(constraint.min) != 0:
+                raise SipxError(L2INF_NO_WEIGHTS)
+            if constraint.min != 0:
+                raise SipxError(L2INF_MIN)
+            if stacked:
+                B = getattr(constraint, "blocks", None)
+                if has_cust:
+                    if B is None:
+                        raise SipxError("the stacked l2,inf ball (l2inf_stacked) on a caller-supplied operator needs blocks, the number of "
+                                        "its equal-sized blocks")
+                    M = int(cust.shape[0])
+                else:
+                    _hessian_check_grid(n)
+                    nb = len(n) * (len(n) + 1) // 2
+                    if B is not None and int(B) != nb:
+                        raise SipxError(f"the Hessian of this grid has {nb} blocks, blocks = {B} was given (leave it None)")
+                    B, M = nb, nb * int(np.prod(n))
+                if isinstance(B, (float, np.floating)) and B != int(B):
+                    raise SipxError(l2inf_bad_blocks(B))
+                B = int(B)
+                if B < 1 or B > L21S_MAX_BLOCKS:
+                    raise SipxError(l2inf_bad_blocks(B))
+                if M % B:
+                    raise SipxError(l2inf_bad_rows(M, B))
+                self.kind, self.op, self.blocks, self.rows = "l2inf_stacked", "custom", B, M
+                groups = per = M // B
+            else:
+                self.kind, self.op = st, ("TV_xy" if constraint.TD_OP == "TV_xy" else "TV")
+                per = int(n[0]) * int(n[1]) if self.op == "TV_xy" else int(np.prod(n))
+                groups = per if st == "l2inf_joint" else int(np.prod(n))
+            self.groups, self.per = groups, per
+            if np.ndim(constraint.max) != 0:
+                c = np.ascontiguousarray(constraint.max, self.TF)
+                if c.ndim != 1 or c.shape[0] != groups:
+                    raise SipxError(l2inf_bad_length(int(c.size), groups))
+                _check_l2inf_bounds(c, per, stacked)
+                self.seg_radii, self.ub, self.pmax = True, c, 1.0
+            else:
+                if not float(constraint.max) > 0:
+                    raise SipxError(L2INF_BAD_C)
+                self.pmax = float(self.TF(constraint.max))
             return
         if st == "l21_stacked" or (st == "l21" and constraint.TD_OP == "Hessian"):
             # the l2,1 ball across the blocks of a stacked operator (csrc/l21_stacked.h); ("l21", "Hessian"): second-order isotropic TV
@@ -955,6 +1080,21 @@ class Projector:
                 raise SipxError(SIMPLEX_ONE_BLOCK + f" -- this set was built for {self.op}, the operator is {op.kind}")
             if getattr(op, "component", 0):
                 raise SipxError(SIMPLEX_NO_MINKOWSKI)
+        if self.kind == "l2inf" and (op.kind != "TV_xy" if self.op == "TV_xy" else op.kind not in TV_OPERATORS):
+            raise SipxError(L2INF_NEEDS_TV)
+        if self.kind == "l2inf_joint" and op.kind != "TV_xy":
+            raise SipxError(L2INF_JOINT_ROUTE)
+        if self.kind in L2INF_KINDS and getattr(op, "component", 0):
+            raise SipxError(L2INF_NO_MINKOWSKI)
+        if self.kind == "l2inf_stacked":
+            if op.kind != "custom":
+                raise SipxError(L2INF_STACKED_NEEDS_CSC)
+            if int(op.shape[0]) % self.blocks:
+                raise SipxError(l2inf_bad_rows(int(op.shape[0]), self.blocks))
+            if int(op.shape[0]) != self.rows:
+                raise SipxError(l2inf_bad_length(self.groups, int(op.shape[0]) // self.blocks))
+        if self.kind in L2INF_KINDS and self.seg_radii and self.ub.shape != (self.groups,):
+            raise SipxError(l2inf_bad_length(int(self.ub.shape[0]), self.groups))
         if self.kind == "l21_stacked":
             if op.kind != "custom":
                 raise SipxError(L21S_NEEDS_CSC)
@@ -983,7 +1123,9 @@ class Projector:
             want = n[self.dir] if self.mode == MODES["fiber"] else rows
             if self.lb.shape != (want,) or self.ub.shape != (want,):
                 raise SipxError(f"bounds vectors need {want} entries for this operator / application mode")
-        if self.seg_radii and self.kind == "l20":
+        if self.kind in L2INF_KINDS:
+            pass                                   # (checked above)
+        elif self.seg_radii and self.kind == "l20":
             if self.ub.shape != (n[2],):
                 raise SipxError(f"l20 budgets per frame: max has {self.ub.shape[0]} entries, n3 = {n[2]} are needed -- one per z-slice "
                                 f"of the grid of shape {tuple(n)}")
@@ -1009,6 +1151,8 @@ class Projector:
             return int(op.shape[0])
         if self.weighted:
             return int(self.lb.shape[0])
+        if self.seg_radii and self.kind in L2INF_KINDS:
+            return int(self.groups)
         if self.seg_radii:
             return self.nseg(op)
         if self.kind != "bounds_vec" or self.transform:
@@ -1026,6 +1170,8 @@ class Projector:
         d.pmin, d.pmax = self.pmin, self.pmax
         d.lb, d.ub = _ptr(self.lb), _ptr(self.ub)
         d.ncvx, d.reserved = int(bool(ncvx)), (int(self.lb.shape[0]) if self.weighted else 0)
+        if self.kind in L2INF_KINDS and self.seg_radii:
+            d.reserved = int(self.ub.shape[0])       # (the entries ub holds)
         d.mode, d.dir = self.mode, self.dir
         d.transform = self.transform
         d.blocks = self.blocks
@@ -1039,11 +1185,13 @@ class Projector:
             raise SipxError("projector input must be a contiguous vector of the working precision")
         grid_kind = self.mode != 0 or self.transform != 0 or self.kind in ("l1_dft", "bounds_dft", "card_dft", "rank", "nuclear", "histogram",
                                                                               "subspace", "l21", "l21_joint", "l21_groups", "tnv", "l1_weighted",
-                                                                              "simplex", "card_groups", "l20", "l20_joint")
-        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint")
-        if self.kind == "l21_stacked":      # the M-vector of the stacked operator's range itself: blocks blocks of M / blocks entries
+                                                                              "simplex", "card_groups", "l20", "l20_joint", "l2inf", "l2inf_joint")
+        l21 = self.kind in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint", "l2inf",
+                            "l2inf_joint")
+        if self.kind in ("l21_stacked", "l2inf_stacked"):      # the M-vector of the stacked operator's range itself: blocks blocks of M / blocks entries
             if v.shape != (self.rows,):
-                raise SipxError(f"the stacked l2,1 ball projects a vector of the operator's range: {self.rows} entries, {v.size} given")
+                what = "l2,1" if self.kind == "l21_stacked" else "l2,inf"
+                raise SipxError(f"the stacked {what} ball projects a vector of the operator's range: {self.rows} entries, {v.size} given")
             ctx = Context(self.comp_grid, self.TF)
             try:
                 d = self.desc("custom", False)
@@ -1056,7 +1204,7 @@ class Projector:
             rows = op.shape[0]
             if v.shape != (rows,):
                 what = {"l1_weighted": "weighted l1 ball", "simplex": "simplex set", "card_groups": "group cardinality set", "l20": "l2,0 set",
-                        "l20_joint": "l2,0 set"}.get(self.kind, "l2,1 ball")
+                        "l20_joint": "l2,0 set", "l2inf": "l2,inf ball", "l2inf_joint": "l2,inf ball"}.get(self.kind, "l2,1 ball")
                 raise SipxError(f"the {what} projects a vector of the {self.op} range: {rows} entries on this grid, {v.size} given")
             self.check_rows(op)
         ctx = Context(self.comp_grid if grid_kind else compgrid((1.0, 1.0), (max(len(v), 1), 1)), self.TF)
@@ -1206,7 +1354,15 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
     Solver.set_data as ub); ("l20_joint", "TV_xy", 0, k, ("tensor", "")) lets at most k pixels carry an edge in any frame, one common edge
     set.  The non-convex counterparts of the l21 / l21_joint sets (ncvx is set): the k groups of largest norm stay as they are, ties to
     the lower point index, every member of the others becomes zero.  ("cardinality", "TV") is another set: it counts differences, so a
-    diagonal edge costs two.  tv_group_norms() observes the norms it selects on."""
+    diagonal edge costs two.  tv_group_norms() observes the norms it selects on.
+
+    ("l2inf", "TV" | "TV_xy", 0, c, ("matrix" | "tensor", "")) is the l2,inf ball on total variation (csrc/l2inf.h): the gradient magnitude
+    ||grad x(p)||_2 <= c_p at every grid point, the rotation-invariant slope constraint (("bounds", "TV") bounds every direction on its
+    own).  c is one positive number or a vector with one bound >= 0 per grid point in the order of tv_group_norms() (+inf frees a point,
+    0 flattens it; replaceable with Solver.set_data as ub).  ("l2inf_joint", "TV_xy", 0, c, ("tensor", "")) bounds the norm of a pixel's
+    in-plane differences across all frames (c: a scalar or n1 n2 numbers); ("l2inf", "Hessian", 0, c, mode) and ("l2inf_stacked", name,
+    0, c, mode, custom_TD_OP=(A, False), blocks=B) bound the group norms across the blocks of a stacked operator (c: a scalar or one per
+    row of a block).  min must be 0.  l2inf_norm() observes the largest group norm."""
     TF = np.dtype(TF).type
     P_sub, TD_OP, prop = [], [], set_properties()
     for c in constraint:
@@ -1215,6 +1371,8 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.min, c.max = [np.asarray(a, TF) if np.ndim(a) else (TF(a) if isinstance(a, (float, np.floating)) else a) for a in (c.min, c.max)]
         elif c.set_type == "l21" and np.ndim(c.max):
             pass                                       # (radii per frame: converted below)
+        elif c.set_type in L2INF_KINDS:
+            pass                                       # (max: one bound or one per group, converted by Projector)
         elif c.set_type in ("card_groups", "l20", "l20_joint"):
             pass                                       # (max is k, a count: Projector must see it unrounded to refuse one that TF cannot hold)
         elif np.ndim(c.min) == 0:
@@ -1226,7 +1384,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             c.max = np.asarray(c.max, TF)
         if getattr(c, "weights", None) is not None and isinstance(c.weights, np.ndarray) and c.weights.dtype.kind == "f":
             c.weights = np.asarray(c.weights, TF)             # (like min / max: floating-point data takes the working precision)
-        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint", "l21_stacked"):
+        if c.set_type in ("l21", "l21_joint", "l21_groups", "tnv", "l1_weighted", "simplex", "card_groups", "l20", "l20_joint", "l21_stacked") + L2INF_KINDS:
             Projector(c, comp_grid, TF)      # a set of the engine's own: its refusals come before the operator is looked at
         if c.set_type in ("nuclear", "rank") and c.app_mode[0] in ("matrix", "tensor") and len(comp_grid.n) == 3:
             raise SipxError("requested rank or nuclear norm constraints on a tensor, use mode=(slice,x) e.t.c. to "
@@ -1240,7 +1398,7 @@ def setup_constraints(constraint: List[set_definitions], comp_grid, TF, segment_
             if c.TD_OP in ("TV", "D2D", "D3D", "D_xz", "TV_xy") or not (isinstance(cust0, (tuple, list)) and len(cust0) == 0):
                 raise SipxError("fiber / slice modes need an operator with one block (identity, D_x, D_y, D_z)")
         cust = c.custom_TD_OP[0] if c.set_type != "subspace" else ()
-        named = "identity" if c.set_type == "l21_stacked" and not (isinstance(cust, (tuple, list)) and len(cust) == 0) else c.TD_OP
+        named = "identity" if c.set_type in ("l21_stacked", "l2inf_stacked") and not (isinstance(cust, (tuple, list)) and len(cust) == 0) else c.TD_OP
         A, AtA_diag, dense, TD_n, banded = get_TD_operator(comp_grid, named, TF)      # (l21_stacked: the name of a caller-supplied operator is free)
         if not (isinstance(cust, (tuple, list)) and len(cust) == 0):          # setup_constraints.jl:70-72
             A = CustomOperator(cust, comp_grid, TF)
@@ -1510,6 +1668,13 @@ class Context:
         if P is not None and P.kind == "l20" and P.seg_radii and arrs[1] is not None:
             for k in arrs[1].tolist():
                 _check_l20_k(k, int(np.prod(_grid(P.comp_grid)[0][:2])), self.TF)
+        elif P is not None and P.kind in L2INF_KINDS:
+            if arrs[0] is not None:
+                raise SipxError("set_data: " + L2INF_NO_WEIGHTS)
+            if not P.seg_radii:
+                raise SipxError("set_data: " + L2INF_NO_SET_DATA)
+            if arrs[1] is not None:
+                _check_l2inf_bounds(arrs[1], P.per, P.kind == "l2inf_stacked")
         elif P is not None and P.seg_radii and arrs[1] is not None:
             _check_l1_radii("l1" if P.kind == "l21" else P.kind, arrs[1])
         if P is not None and P.weighted:
@@ -2134,6 +2299,10 @@ class Solver:
             raise SipxError("set_data: " + L20_NO_SET_DATA)
         if self.P_sub[i].kind == "l20" and lb is not None:
             raise SipxError("set_data: " + L20_SET_DATA_UB)
+        if self.P_sub[i].kind in L2INF_KINDS and lb is not None:
+            raise SipxError("set_data: " + L2INF_NO_WEIGHTS)
+        if self.P_sub[i].kind in L2INF_KINDS and not self.P_sub[i].seg_radii:
+            raise SipxError("set_data: " + L2INF_NO_SET_DATA)
         want = self.P_sub[i].data_len(self.TD_OP[i])
         if want is None:
             raise SipxError(f"set_data: set {i} ({self.set_Prop.tag[i][0]} on {self.set_Prop.tag[i][1]}) holds no replaceable vectors -- "
@@ -2164,6 +2333,9 @@ class Solver:
             if self.P_sub[i].kind == "l20" and ub is not None:
                 for k in np.asarray(ub).tolist():
                     _check_l20_k(k, int(np.prod(_grid(self.comp_grid)[0][:2])), self.TF)
+            elif self.P_sub[i].kind in L2INF_KINDS:
+                if ub is not None:
+                    _check_l2inf_bounds(ub, self.P_sub[i].per, self.P_sub[i].kind == "l2inf_stacked")
             elif self.P_sub[i].seg_radii and ub is not None:
                 _check_l1_radii("l1" if self.P_sub[i].kind == "l21" else self.P_sub[i].kind, ub)
             if self.P_sub[i].weighted and lb is not None:
@@ -2495,6 +2667,38 @@ def l21_stacked_norm(x, comp_grid, TD_OP, blocks=None):
     nz = np.ascontiguousarray(op.A.data, TF)
     d.csc_colptr, d.csc_rowval, d.csc_nzval, d.csc_rows = cp.ctypes.data, ri.ctypes.data, nz.ctypes.data, int(op.A.shape[0])
     out, on_dev = _l21_observe("l21_stacked_norm", x, comp_grid, False, False, "sipx_l21_stacked_norm", (C.byref(d),), ())
+    return out if on_dev else out[0]
+
+
+def l2inf_norm(x, comp_grid, TD_OP="TV", joint=False, blocks=None):
+    """max_p ||(A x)_p||_2 over the groups of the l2,inf sets (csrc/l2inf.h), one number of the working precision (that of x): the
+    steepest gradient magnitude of x for TD_OP "TV" ("D2D", "D3D") or "TV_xy", with joint=True the largest norm over the pixels of TV_xy
+    across all frames, for TD_OP = "Hessian" the largest Frobenius norm of the Hessian, for TD_OP a sparse matrix with N columns the
+    largest group norm across its `blocks` equal-sized blocks.  Computed by the projector's own norms launch and a two-stage maximum
+    (sipx_l2inf_norm): a set built with the value as its bound leaves A x untouched.  x: a numpy vector (a numpy scalar comes back) or a
+    1-D torch tensor on a GPU (a tensor of one entry there)."""
+    TF = _tensor_TF("x", x) if _is_tensor(x) else (x.dtype.type if isinstance(x, np.ndarray) else None)
+    if TF not in (np.float32, np.float64):
+        raise SipxError("l2inf_norm: x must be a Float32 or Float64 numpy vector or torch tensor on a GPU")
+    named = isinstance(TD_OP, str)
+    if named and TD_OP != "Hessian":
+        c = set_definitions("l2inf_joint" if joint else "l2inf", TD_OP, 0.0, 1.0, ("matrix", ""))
+        P = Projector(c, comp_grid, TF)
+        d = P.desc(P.op, False)
+        keep = ()
+    else:
+        if joint:
+            raise SipxError(L2INF_JOINT_ROUTE)
+        c = set_definitions("l2inf_stacked", "Hessian" if named else "custom", 0.0, 1.0, ("matrix", ""),
+                            custom_TD_OP=((), False) if named else (TD_OP, False), blocks=blocks)
+        P = Projector(c, comp_grid, TF)
+        op = hessian_operator(comp_grid, TF) if named else CustomOperator(TD_OP, comp_grid, TF)
+        P.check_rows(op)
+        d = P.desc("custom", False)
+        keep = (np.ascontiguousarray(op.A.indptr, np.int64), np.ascontiguousarray(op.A.indices, np.int64), np.ascontiguousarray(op.A.data, TF))
+        d.csc_colptr, d.csc_rowval, d.csc_nzval, d.csc_rows = keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, int(op.A.shape[0])
+    out, on_dev = _l21_observe("l2inf_norm", x, comp_grid, False, False, "sipx_l2inf_norm", (C.byref(d),), ())
+    del keep
     return out if on_dev else out[0]
 
 

@@ -36,6 +36,8 @@ def constraint2coarse(constraint, comp_grid, cf):
             raise host.SipxError(host.CARDG_NO_COARSE)
         if c.set_type in ("l20", "l20_joint"):
             raise host.SipxError(host.L20_NO_COARSE)
+        if c.set_type in host.L2INF_KINDS:
+            raise host.SipxError(host.L2INF_NO_COARSE)
         if c.set_type == "l21_stacked" or c.TD_OP == "Hessian":
             raise host.SipxError(host.L21S_NO_COARSE)
         if getattr(c, "weights", None) is not None:
@@ -58,6 +60,8 @@ def setup_multi_level_PARSDMM(m, n_levels, coarsening_factor, comp_grid, constra
     cf = coarsening_factor
     if any(c.TD_OP == "TV_xy" for c in constraint):
         raise host.SipxError(host.TV_XY_NO_MULTILEVEL)
+    if any(c.set_type in host.L2INF_KINDS for c in constraint):
+        raise host.SipxError(host.L2INF_NO_COARSE)
     if any(c.set_type == "l21_stacked" or c.TD_OP == "Hessian" for c in constraint):
         raise host.SipxError(host.L21S_NO_COARSE)
     P_sub, TD_OP, prop = host.setup_constraints(copy.deepcopy(constraint), comp_grid, TF)
@@ -161,6 +165,8 @@ def PARSDMM_multi_level(m, TD_OP_levels, AtA_levels, P_sub_levels, set_Prop_leve
         raise host.SipxError(f"outputs must be 'all' or 'x', not {outputs!r}")
     if any(getattr(A, "kind", None) == "TV_xy" for ops in TD_OP_levels for A in ops):
         raise host.SipxError(host.TV_XY_NO_MULTILEVEL)
+    if any(getattr(P, "kind", None) in host.L2INF_KINDS for Ps in P_sub_levels for P in Ps):
+        raise host.SipxError(host.L2INF_NO_COARSE)
     if any(getattr(P, "kind", None) == "l21_stacked" for Ps in P_sub_levels for P in Ps):
         raise host.SipxError(host.L21S_NO_COARSE)
     import time
